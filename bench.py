@@ -1,7 +1,18 @@
 #!/usr/bin/env python3
 """Headline benchmark: denoising-steps/sec of the CFG-DDPM sampler at 256x256 on the T=1000 schedule.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run sets up, replays W warm-up steps, times K steps and prints ONE JSON line with the contract keys (`metric`, `value`,
+`unit`, `higher_is_better`, `dtype`, `ms_per_step` = milliseconds of one timed step, ...).  Everything else it can measure --
+the event-instrumented second pass and the roofline made of it, the engine clock / board power during the timed region, the
+other contraction mode, the CPU baseline and parity legs, the other BASELINE configs -- runs only under ``--full`` (below).
+
+``--dump-outputs DIR`` writes what the last timed step computed, after the timed region, as float32 ``DIR/<name>.npy``:
+``x_next`` (the sampler state the step hands to the next one, [B, 3, S, S]) and ``eps_cond`` / ``eps_uncond`` (the two UNet
+outputs of that step); with N > 1 every rank writes its own, suffixed ``_rank<r>``.  Inputs are fixed by seeds (weights:
+torch seed 0; x_T and the in-kernel noise: 1234 + rank), so two builds can be compared output for output.  Past 64 MB in all,
+each array is replaced by a fixed sample of its flattened elements (``dump_outputs`` says which).
 
 N > 1 with no launcher: this process (which never touches the GPU) starts N fresh rank processes itself
 (hdiff_amd.parallel.launch_ranks -- the reference's other tree does the same with mp.spawn, utils/rotinas.py:572-577),
@@ -15,12 +26,12 @@ are resident in HBM before the timed region.  Sampling shards by image: every ra
 and there is no data-path collective (weak scaling); value = N * K / max-over-ranks wall time.
 
 The timed region replays the hipGraph-captured step (the north-star formulation; ``--eager`` times plain launches instead).
-Per-kernel durations come from a second pass of the same K steps (same start state, same time steps) issued as plain
+Per-kernel durations (``--full``) come from a second pass of the same K steps (same start state, same time steps) issued as plain
 launches with HIP events recorded on the launch stream around the launches of interest (events cannot bracket nodes
 inside a graph replay; the kernels, their arguments and their order are identical -- the two passes agree to < 0.1 % at
 this size, both wall times are reported).
 
-Rank 0 prints ONE JSON line with the contract keys plus
+Under ``--full`` rank 0's line adds
   roofline      dominant kernel (flash attention at L = 65536, d_head = 16): ``frac`` against the 16-bit dense MFMA peak / the
                 3.5 piece products it executes per fp32 product (fp32-MFMA peak in the f32 mode), ``frac_vs_16bit_peak`` against
                 the raw peak, ``issue_model_ms`` / ``frac_vs_issue_model`` (its own PMC instruction counts priced at issue cost at
@@ -29,8 +40,8 @@ Rank 0 prints ONE JSON line with the contract keys plus
                 the board's power limit, ``bound_note``); ``secondary`` holds the full-resolution 3x3 convolution (MFMA) and the
                 GroupNorm statistics pass (HBM); ``traffic`` and the instruction counts come from profiles/roofline_traffic.json
                 and are reported only while the kernel sources still hash to what that file was measured on (``traffic_stamp``)
-  device_clock / box_range   engine clock and board power of THIS run's device during the timed region; the range of the headline
-                over the boxes met (the power limit leaves different clocks on different boxes)
+  device_clock  engine clock and board power of THIS run's device during the timed region (``box_range``, in every line: the range
+                of the headline over the boxes met -- the power limit leaves different clocks on different boxes)
   cpu_baseline  the CPU oracle (oracle/cpu_path.py, kind "port"): one whole UNet forward at 128x128 timed on the host
                 cores (a bounded sample), scaled to the benchmark's step by the algorithmic FLOP ratio; ``same_config``
                 holds the one BASELINE config the CPU finishes in full (C1), timed on both sides
@@ -40,6 +51,7 @@ Rank 0 prints ONE JSON line with the contract keys plus
                 C5 one step of one GPU's share, C3 one optimizer step (``--no-extras`` skips them)
 """
 import argparse
+import contextlib
 import ctypes as C
 import hashlib
 import json
@@ -80,16 +92,23 @@ def parse(argv=None):
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--size", type=int, default=256)
     ap.add_argument("--batch", type=int, default=8, help="images per GPU")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything outside the headline: the event-instrumented pass (roofline), the clock sampler, "
+                         "the other contraction mode, the CPU baseline + parity legs and the other BASELINE configs (each can "
+                         "be dropped again with its --no-* option)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed as float32 DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline and parity legs")
     ap.add_argument("--contract", choices=["f32", "bf16x3"], default="bf16x3",
                     help="attention / 3x3-conv contractions: the fp32-class three-piece bf16 split on the bf16 MFMA (the library's "
-                         "default) or the fp32-input MFMA; the other one is run once beside the headline (`other_contract_mode`)")
-    ap.add_argument("--no-alt", action="store_true", help="skip the extra (untimed in `value`) run in the other contraction mode")
+                         "default) or the fp32-input MFMA; with --full the other one is run once beside the headline "
+                         "(`other_contract_mode`)")
+    ap.add_argument("--no-alt", action="store_true", help="with --full: skip the extra (untimed in `value`) run in the other contraction mode")
     ap.add_argument("--eager", action="store_true", help="time plain launches instead of the hipGraph replay")
     ap.add_argument("--graph", action="store_true", help="(default; kept for old command lines)")
-    ap.add_argument("--no-kernel-pass", action="store_true", help="skip the second, event-instrumented pass (no roofline)")
+    ap.add_argument("--no-kernel-pass", action="store_true", help="with --full: skip the second, event-instrumented pass (no roofline)")
     ap.add_argument("--no-extras", action="store_true",
-                    help="skip the other BASELINE configs (C1 full on GPU and CPU, C2, C5, C3) reported under `configs`")
+                    help="with --full: skip the other BASELINE configs (C1 full on GPU and CPU, C2, C5, C3) reported under `configs`")
     ap.add_argument("--extras-scale", choices=["full", "small"], default="full",
                     help="dev/tests: `small` runs the `configs` legs at toy sizes so that the code path finishes in seconds")
     ap.add_argument("--rehearse-one-gpu", action="store_true",
@@ -98,6 +117,8 @@ def parse(argv=None):
     a = ap.parse_args(argv)
     if a.gpus < 1:
         ap.error("--gpus must be >= 1")
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     # three passes (timed, event-instrumented, other contraction mode) each start from step T-1: K + W steps must fit
     if a.steps + a.warmup + 1 > MODEL["T"]:
         ap.error(f"--steps + --warmup must stay below T = {MODEL['T']}")
@@ -228,6 +249,30 @@ def _release():
     import gc
     gc.collect()
     torch.cuda.empty_cache()
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, arrays, limit=DUMP_LIMIT_BYTES):
+    """Writes {name: tensor} as float32 ``out_dir/<name>.npy``.  When the arrays hold more than `limit` bytes together, each is
+    replaced by the same fixed sample of its flattened elements: positions ``randperm(numel, seed 0)[:k]`` in ascending order,
+    with k the array's share of the limit.  Returns {name: what was written} for the JSON line."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    total = sum(t.numel() * 4 for t in arrays.values())
+    written = {}
+    for name, t in arrays.items():
+        flat = t.detach().float().cpu().reshape(-1)
+        if total > limit:
+            k = max(1, min(flat.numel(), int(limit * t.numel() / total)))      # (numel * 4 / total) of the limit, 4 bytes each
+            idx = torch.randperm(flat.numel(), generator=torch.Generator().manual_seed(0))[:k].sort().values
+            np.save(os.path.join(out_dir, f"{name}.npy"), flat[idx].numpy())
+            written[name] = {"shape": list(t.shape), "sample": k}
+        else:
+            np.save(os.path.join(out_dir, f"{name}.npy"), flat.reshape(t.shape).numpy())
+            written[name] = {"shape": list(t.shape)}
+    return written
 
 
 def time_sampler_steps(model, size, batch, T, beta, w, steps, warmup, dev, seed=1234, graph=True):
@@ -570,8 +615,9 @@ def main():
         if dist:
             td.barrier()
         torch.cuda.synchronize(dev)
-        clock = ClockSampler(int(os.environ.get("LOCAL_RANK", "0")) if not a.rehearse_one_gpu else 0)
-        with clock:
+        # --full: the engine clock / board power of this device, read from sysfs by a thread while the timed region runs
+        clock = ClockSampler(int(os.environ.get("LOCAL_RANK", "0")) if not a.rehearse_one_gpu else 0) if a.full else None
+        with clock if clock is not None else contextlib.nullcontext():
             t0 = time.perf_counter()
             for _ in range(K):
                 one_step()
@@ -581,12 +627,18 @@ def main():
             elapsed = time.perf_counter() - t0
         assert int(sp.nan_flag.item()) == 0, "nan in tensor."
         assert int(sp.step.item()) == MODEL["T"] - 1 - (K + Wm)
-        x_timed = sp.x.clone()                         # the state after Wm + K steps in the timed mode (for `parity.modes`)
+        dumped = None
+        if a.dump_outputs:
+            eps = sp.unet.out                          # [cond; uncond] UNet outputs of the last timed step
+            suffix = f"_rank{rank}" if world > 1 else ""
+            dumped = dump_outputs(a.dump_outputs, {f"x_next{suffix}": sp.x, f"eps_cond{suffix}": eps[:B],
+                                                   f"eps_uncond{suffix}": eps[B:]}, DUMP_LIMIT_BYTES // world)
+        x_timed = sp.x.clone() if a.full else None     # the state after Wm + K steps in the timed mode (for `parity.modes`)
 
-        # second pass: the same steps (same start state, same time steps) as plain launches with HIP events around the
+        # second pass (--full): the same steps (same start state, same time steps) as plain launches with HIP events around the
         # launches of interest; the warm-up steps are replayed so that the K instrumented steps are the K timed ones
         kernel_pass_s = None
-        if not a.no_kernel_pass:
+        if a.full and not a.no_kernel_pass:
             reset()
             for _ in range(Wm):
                 one_step()
@@ -598,10 +650,10 @@ def main():
             kernel_pass_s = (time.perf_counter() - t1) / K
             assert int(sp.nan_flag.item()) == 0, "nan in tensor."
 
-        # the other contraction mode, reported beside the headline (never part of `value`)
+        # the other contraction mode (--full), reported beside the headline (never part of `value`)
         alt = None
         mode_parity = None
-        if world == 1 and not a.no_alt:
+        if a.full and world == 1 and not a.no_alt:
             other = "bf16x3" if a.contract == "f32" else "f32"
             hdiff_amd.set_contraction_mode(other)
             use_graph = False                         # a captured graph bakes the contraction mode: plain launches here
@@ -644,11 +696,11 @@ def main():
         durations[gname] = vals
 
     if rank == 0:
-        traffic_tab, traffic_stamp, issue_tab = load_traffic()
         flops_per_launch = 4.0 * L_full * L_full * Cc * (2 * B)          # QK^T + PV over 8 heads, 2B samples (CFG)
         roof = None
         att_ms = durations.get("attn") or []
         if att_ms:
+            traffic_tab, traffic_stamp, issue_tab = load_traffic()
             avg = sum(att_ms) / len(att_ms)
             ach = flops_per_launch / (avg * 1e-3) / 1e12
             if a.contract == "f32":
@@ -753,11 +805,15 @@ def main():
                        "whole_step_tflops_per_gpu": step_tflop / (elapsed / K) if elapsed > 0 else None,
                        "attention_contract": a.contract, "other_contract_mode": alt},
             "roofline": roof,
-            "device_clock": clock.summary(),
             "box_range": BOX_RANGE,
         }
-    # everything below is outside the timed region and never enters `value`; N = 1 only
-    if rank == 0 and world == 1:
+        if clock is not None:
+            out["device_clock"] = clock.summary()
+        if dumped is not None:
+            out["dump_outputs"] = {"dir": a.dump_outputs, "arrays": dumped, "dtype": "float32",
+                                   "what": "after the timed region: the state and the two UNet outputs of the last timed step"}
+    # everything below (--full) is outside the timed region and never enters `value`; N = 1 only
+    if rank == 0 and world == 1 and a.full:
         del plan, sp, sampler, model, x_timed
         _release()
         if not a.no_cpu_baseline:

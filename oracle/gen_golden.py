@@ -28,6 +28,8 @@ Fixtures:
                           loss, 19 small gradient tensors + 4 row slices, total norm         [python -m oracle.gen_golden g6b]
   G7 state_dict_default.json   the 366 (name, shape) pairs of the default UNet
   G8 lr_schedule.json     GradualWarmupScheduler + CosineAnnealingLR learning-rate sequence (Scheduler.py)
+  G9 main_condition_defaults.json  the default ``modelConfig`` literal of MainCondition.py's ``main()``, read with ``ast``
+                          (the entry file is never executed or copied)     [python -m oracle.gen_golden g9]
 """
 from __future__ import annotations
 
@@ -458,6 +460,19 @@ def gen_lr_schedule():
         json.dump({"epochs": epochs, "multiplier": mult, "base_lr": 1e-4, "lr_by_epoch": lrs}, fh)
 
 
+def gen_main_defaults():
+    """The dict literal that MainCondition.py's main() falls back to without an argument, evaluated from the file's syntax tree."""
+    import ast
+    path = os.path.join(RL.REFERENCE_ROOT, "MainCondition.py")
+    with open(path) as fh:
+        tree = ast.parse(fh.read(), path)
+    main_fn = next(n for n in tree.body if isinstance(n, ast.FunctionDef) and n.name == "main")
+    assign = next(n for n in main_fn.body if isinstance(n, ast.Assign)
+                  and any(isinstance(t, ast.Name) and t.id == "modelConfig" for t in n.targets))
+    with open(os.path.join(OUT, "main_condition_defaults.json"), "w") as fh:
+        json.dump({"source": "MainCondition.py main(): modelConfig", "model_config": ast.literal_eval(assign.value)}, fh, indent=1)
+
+
 def main():
     if not RL.available():
         sys.exit("reference not present at " + RL.REFERENCE_ROOT)
@@ -479,6 +494,9 @@ def main():
     if len(sys.argv) > 1 and sys.argv[1] == "g5b":
         gen_sampler_default128(RM, RD)
         return
+    if len(sys.argv) > 1 and sys.argv[1] == "g9":
+        gen_main_defaults()
+        return
     gen_schedules(RD)
     gen_modules(RM)
     gen_unet_small(RM)
@@ -486,6 +504,7 @@ def main():
     gen_sampler_small(RM, RD)
     gen_trainer_small(RM, RD)
     gen_lr_schedule()
+    gen_main_defaults()
     for f in sorted(os.listdir(OUT)):
         print(f, os.path.getsize(os.path.join(OUT, f)))
 

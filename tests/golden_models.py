@@ -61,3 +61,34 @@ def default_trainer_model(UNet):
             assert (m.time_embedding.timembedding[0].weight[t] - rows[i]).abs().max().item() < 1e-3
             m.time_embedding.timembedding[0].weight[t].copy_(rows[i])
     return m.train(), c, d
+
+
+
+def reference_schedules(d, i):
+    """The schedule buffers of the reference's trainer and sampler (DiffusionCondition.py:26-35, 60-66) for config `i` of
+    schedules.npz, evaluated in float64 from the fixture's betas in the reference's order of operations, with torch's sqrt:
+    what the reference computes on THIS host.  torch's float64 sqrt is not correctly rounded and its last bit depends on the
+    host CPU, so the stored buffers carry the bits of the CPU that generated them."""
+    betas = np.asarray(d[f"cfg{i}/trainer/betas"], dtype=np.float64)
+
+    def sqrt(a):
+        return torch.sqrt(torch.from_numpy(np.ascontiguousarray(a))).numpy()
+    alphas = 1.0 - betas
+    alphas_bar = np.cumprod(alphas)
+    alphas_bar_prev = np.concatenate([[1.0], alphas_bar[:-1]])
+    coeff1 = sqrt(1.0 / alphas)
+    return {"trainer": {"betas": betas, "sqrt_alphas_bar": sqrt(alphas_bar), "sqrt_one_minus_alphas_bar": sqrt(1.0 - alphas_bar)},
+            "sampler": {"betas": betas, "coeff1": coeff1, "coeff2": coeff1 * (1.0 - alphas) / sqrt(1.0 - alphas_bar),
+                        "posterior_var": betas * (1.0 - alphas_bar_prev) / (1.0 - alphas_bar)}}
+
+
+def assert_schedule_buffer(got, host, stored, what):
+    """`got` (the code under test) must equal the reference's formula on this host (`host`, reference_schedules) bit for bit,
+    and that must equal the stored buffer bit for bit -- or, on a host whose torch sqrt rounds differently from the generating
+    CPU's, lie within four units in the last place of it (coeff2 holds two square roots, each up to one unit apart between
+    hosts, and a product and a quotient that round once more each)."""
+    got, host, stored = np.asarray(got), np.asarray(host), np.asarray(stored)
+    assert got.dtype == stored.dtype and got.shape == stored.shape, what
+    assert np.array_equal(got, host), what
+    if not np.array_equal(host, stored):
+        assert (np.abs(host - stored) <= 4 * np.spacing(np.abs(stored))).all(), what

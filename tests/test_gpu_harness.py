@@ -46,13 +46,14 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def test_bench_json_contract_small():
-    """bench.py prints ONE JSON line with the driver's fields (run at 64x64, batch 2 so that it takes seconds), including
+    """bench.py --full prints ONE JSON line with the driver's fields (run at 64x64, batch 2 so that it takes seconds), including
     the legs outside `value`: cpu_baseline + parity (the 128x128 forward on both sides) and the other BASELINE configs
     (toy-sized here: --extras-scale small runs the same code)."""
     import subprocess
     import sys
     res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
-                          "--size", "64", "--batch", "2", "--extras-scale", "small"], capture_output=True, text=True, timeout=900)
+                          "--size", "64", "--batch", "2", "--extras-scale", "small", "--full"], capture_output=True, text=True,
+                         timeout=900)
     d = _json_line(res)
     for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
                 "vs_baseline", "dtype", "data", "config", "roofline", "cpu_baseline", "parity", "configs"):
@@ -85,6 +86,30 @@ def test_bench_json_contract_small():
     assert "error" not in cfgs, cfgs
     assert cfgs["C1"]["gpu_steps_per_s"] > 0 and cfgs["C2"]["steps_per_s"] > 0 and cfgs["C5"]["steps_per_s"] > 0
     assert cfgs["C3"]["all_grads_present"] and np.isfinite(cfgs["C3"]["loss"]) and cfgs["C3"]["s_per_step"] > 0
+
+
+def test_bench_plain_run_is_the_headline_alone_and_dumps_its_last_step(tmp_path):
+    """A plain bench.py run (no --full) times the steps and prints the contract keys, nothing it would need other passes for;
+    --dump-outputs writes the state and the two UNet outputs of the last timed step as float32 .npy files."""
+    import subprocess
+    import sys
+    out = tmp_path / "outputs"
+    res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+                          "--size", "64", "--batch", "2", "--dump-outputs", str(out)], capture_output=True, text=True, timeout=900)
+    d = _json_line(res)
+    for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "dtype", "config"):
+        assert key in d, key
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["higher_is_better"] is True and d["unit"] == "denoising-steps/s"
+    assert abs(d["value"] - 1e3 / d["ms_per_step"]) < 1e-6 * d["value"]
+    for key in ("cpu_baseline", "parity", "configs", "device_clock"):
+        assert key not in d, key
+    assert d["roofline"] is None and d["config"]["other_contract_mode"] is None
+    assert d["config"]["ms_per_step_plain_launches_with_events"] is None
+    assert set(d["dump_outputs"]["arrays"]) == {"x_next", "eps_cond", "eps_uncond"}
+    for name in ("x_next", "eps_cond", "eps_uncond"):
+        a = np.load(out / f"{name}.npy")
+        assert a.dtype == np.float32 and a.shape == (2, 3, 64, 64) and np.isfinite(a).all(), name
+        assert np.abs(a).max() > 0, name
 
 
 def test_bench_gpus_2_starts_its_own_ranks():

@@ -101,6 +101,7 @@ def test_state_dict_layout_and_seeded_init_match_reference():
 
 
 def test_small_state_dict_loads_strict_and_buffers_bit_exact():
+    from golden_models import assert_schedule_buffer, reference_schedules
     u = np.load(os.path.join(GOLDEN, "unet_small.npz"))
     cfg = json.loads(bytes(u["cfg_json"]).decode())
     m = MC.UNet(**cfg)
@@ -113,13 +114,15 @@ def test_small_state_dict_loads_strict_and_buffers_bit_exact():
         sa = DC.GaussianDiffusionSampler(m, float(b1), float(bT), int(Tn), w=1.8)
         assert [n for n, _ in tr.named_buffers(recurse=False)] == ["betas", "sqrt_alphas_bar", "sqrt_one_minus_alphas_bar"]
         assert [n for n, _ in sa.named_buffers(recurse=False)] == ["betas", "coeff1", "coeff2", "posterior_var"]
+        host = reference_schedules(s, i)            # bit for bit the reference's buffers as computed on this host
         for n in ("betas", "sqrt_alphas_bar", "sqrt_one_minus_alphas_bar"):
             assert getattr(tr, n).dtype == torch.float64
-            assert np.array_equal(getattr(tr, n).numpy(), s[f"cfg{i}/trainer/{n}"])
+            assert_schedule_buffer(getattr(tr, n).numpy(), host["trainer"][n], s[f"cfg{i}/trainer/{n}"], (i, n))
         for n in ("betas", "coeff1", "coeff2", "posterior_var"):
-            assert np.array_equal(getattr(sa, n).numpy(), s[f"cfg{i}/sampler/{n}"])
+            assert_schedule_buffer(getattr(sa, n).numpy(), host["sampler"][n], s[f"cfg{i}/sampler/{n}"], (i, n))
         ex = DC.extract(sa.coeff2, torch.from_numpy(s[f"cfg{i}/extract_t"]), (4, 3, 8, 8))
-        assert np.array_equal(ex.numpy(), s[f"cfg{i}/extract_coeff2"])
+        want = host["sampler"]["coeff2"][s[f"cfg{i}/extract_t"]].astype(np.float32).reshape(4, 1, 1, 1)
+        assert_schedule_buffer(ex.numpy(), want, s[f"cfg{i}/extract_coeff2"], (i, "extract"))
         assert sa.model is m and sa.T == int(Tn) and sa.w == 1.8
 
 
@@ -345,31 +348,61 @@ def test_install_dropin_refuses_to_shadow_an_imported_reference_module(tmp_path)
     assert res.returncode == 0 and "REFUSED" in res.stdout and "FORCED" in res.stdout, res.stdout + res.stderr[-3000:]
 
 
-REFERENCE_MAIN = "/root/reference/MainCondition.py"
+def _reference_shaped_checkout(root):
+    """A directory laid out like the reference's checkout, built from the repository alone: an entry file
+    ``MainCondition.py`` with the reference's line 1 and its ``main(model_config=None)`` dispatch, whose defaults are the
+    reference's own ``modelConfig`` literal (tests/golden/main_condition_defaults.json, oracle/gen_golden.py G9), and a
+    ``DiffusionFreeGuidence/`` package that does not import (the reference's has a SyntaxError at ModelCondition.py:289)."""
+    pkg = root / "DiffusionFreeGuidence"
+    pkg.mkdir(parents=True)
+    (pkg / "__init__.py").write_text("from .ModelCondition import *\n")
+    (pkg / "ModelCondition.py").write_text("class DynamicUNet(:\n    pass\n")
+    main = root / "MainCondition.py"
+    main.write_text("\n".join([
+        REFERENCE_IMPORT_LINES[0],
+        "import json",
+        "",
+        "",
+        "def main(model_config=None):",
+        f"    with open({os.path.join(GOLDEN, 'main_condition_defaults.json')!r}) as fh:",
+        "        modelConfig = json.load(fh)['model_config']",
+        "    if model_config is not None:",
+        "        modelConfig = model_config",
+        "    if modelConfig['state'] == 'train':",
+        "        train(modelConfig)",
+        "    else:",
+        "        eval(modelConfig)",
+        "",
+        "",
+        "if __name__ == '__main__':",
+        "    main()",
+        "",
+    ]))
+    return str(main)
 
 
-@pytest.mark.skipif(not os.path.isfile(REFERENCE_MAIN), reason="the reference checkout exists in the build container only")
 def test_reference_main_file_itself_runs_against_the_dropin(tmp_path):
-    """The reference's REAL MainCondition.py, unmodified, executed from the reference's own directory (where its
-    `DiffusionFreeGuidence/` package -- which does not even import, SyntaxError at ModelCondition.py:289 -- is first on
-    sys.path): after install_dropin() its line 1 binds this package's train / eval and `main()` hands them the reference's
-    default config.  train is replaced by a recorder (no GPU here); the config it receives must equal the defaults table
-    of this package's MainCondition."""
+    """An entry file of the reference's shape (``_reference_shaped_checkout``), executed from its own directory, where a
+    `DiffusionFreeGuidence/` package that does not even import is first on sys.path: after install_dropin() its line 1
+    binds this package's train / eval and `main()` hands them the reference's default config.  train is replaced by a
+    recorder (no GPU here); the config it receives must equal the defaults table of this package's MainCondition."""
+    main_file = _reference_shaped_checkout(tmp_path / "reference")
     code = "\n".join([
         f"import sys, json, runpy; sys.path.insert(0, {ROOT!r})",
+        "try:\n    import DiffusionFreeGuidence\nexcept SyntaxError:\n    pass\nelse:\n    raise AssertionError('the shadowing package imported')",
         "import hdiff_amd; hdiff_amd.install_dropin()",
         "import hdiff_amd.DiffusionFreeGuidence.TrainCondition as TC",
         "seen = []",
         "TC.train = lambda cfg: seen.append(('train', cfg))",
         "TC.eval = lambda cfg: seen.append(('eval', cfg))",
-        f"ns = runpy.run_path({REFERENCE_MAIN!r}, run_name='__main__')",
+        f"ns = runpy.run_path({main_file!r}, run_name='__main__')",
         "assert len(seen) == 1 and seen[0][0] == 'train', seen",
         "from hdiff_amd.MainCondition import default_config",
         "assert seen[0][1] == default_config(), (seen[0][1], default_config())",
         "ns['main'](dict(default_config(), state='eval')); assert seen[1][0] == 'eval'",
         "print('OK')",
     ])
-    res = _run_fresh(code, os.path.dirname(REFERENCE_MAIN))
+    res = _run_fresh(code, os.path.dirname(main_file))
     assert res.returncode == 0 and "OK" in res.stdout, res.stderr[-3000:]
 
 
@@ -380,7 +413,7 @@ def test_launch_ranks_relays_rank0_and_propagates_failure(tmp_path):
     prog.write_text("import os, sys\n"
                     "r, w = int(os.environ['RANK']), int(os.environ['WORLD_SIZE'])\n"
                     "assert os.environ['LOCAL_RANK'] == str(r) and os.environ['MASTER_ADDR'] == '127.0.0.1' and int(os.environ['MASTER_PORT']) > 0\n"
-                    "print('line from rank', r, 'of', w, sys.argv[1:])\n"
+                    "sys.stdout.write(f'line from rank {r} of {w} {sys.argv[1:]}\\n')\n"    # one write: the ranks share stderr
                     "sys.exit(3 if (len(sys.argv) > 2 and r == 1) else 0)\n")
     code = (f"import sys; sys.path.insert(0, {ROOT!r}); import hdiff_amd\n"
             "from hdiff_amd.parallel import launch_ranks\n"
@@ -438,3 +471,30 @@ def test_roofline_traffic_table_is_stamped_and_goes_stale_with_the_kernel_source
     assert "mha_flash_fwd_L65536_B16" not in table2 and stamp2["kernels"]["mha_flash_fwd_L65536_B16"].startswith("STALE")
     if stamp["kernels"]["gn_stats_128_256_B16"] == "fresh":
         assert "gn_stats_128_256_B16" in table2
+
+
+def test_bench_plain_run_options_and_output_dump(tmp_path):
+    """bench.py: a plain run is the headline alone (--full adds the other legs), and --dump-outputs writes float32 .npy files,
+    whole below the size limit and as the same fixed sample of each array above it."""
+    import bench
+    a = bench.parse(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert a.steps == 7 and a.warmup == 2 and not a.full and a.dump_outputs is None
+    a = bench.parse(["--steps", "2", "--full", "--dump-outputs", str(tmp_path)])
+    assert a.full and a.dump_outputs == str(tmp_path)
+    g = torch.Generator().manual_seed(3)
+    arrays = {"x_next": torch.randn(2, 3, 8, 8, generator=g), "eps_cond": torch.randn(2, 3, 8, 8, generator=g).double()}
+    info = bench.dump_outputs(str(tmp_path / "whole"), arrays)
+    for name, t in arrays.items():
+        got = np.load(tmp_path / "whole" / f"{name}.npy")
+        assert got.dtype == np.float32 and np.array_equal(got, t.float().numpy()) and info[name] == {"shape": [2, 3, 8, 8]}
+    limit = 2 * 4 * 100                                      # room for 100 of the 384 elements of each array
+    info = bench.dump_outputs(str(tmp_path / "sampled"), arrays, limit=limit)
+    again = bench.dump_outputs(str(tmp_path / "again"), arrays, limit=limit)
+    assert info == again and info["x_next"] == {"shape": [2, 3, 8, 8], "sample": 100}
+    for name, t in arrays.items():
+        got = np.load(tmp_path / "sampled" / f"{name}.npy")
+        assert got.dtype == np.float32 and got.shape == (100,)
+        assert np.array_equal(got, np.load(tmp_path / "again" / f"{name}.npy"))
+        assert np.isin(got, t.float().numpy().reshape(-1)).all()
+    total = sum(os.path.getsize(tmp_path / "sampled" / f"{n}.npy") for n in arrays)
+    assert total <= limit + 2 * 128                          # + the .npy headers

@@ -19,8 +19,8 @@ SQ1="SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_VALU_MFMA_BUSY_CYCLES SQ_ACTIVE_INST_VALU 
 SQ2="SQ_INSTS_LDS SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_ACTIVE_INST_LDS SQ_INSTS_VALU_TRANS_F32 SQ_ACTIVE_INST_ANY SQ_WAIT_INST_LDS SQ_VALU_MFMA_COEXEC_CYCLES"
 if want traces; then
 # kernel-trace + stats of the headline (library default = bf16x3 contraction mode) and of the fp32 mode, and of one optimizer step
-rocprofv3 --kernel-trace --stats --output-format csv -d $P/bench -o bench -- python3 bench.py --steps 3 --warmup 1 --no-alt --no-extras --no-cpu-baseline > $P/bench_line.json 2> $P/bench.err
-rocprofv3 --kernel-trace --stats --output-format csv -d $P/bench_f32 -o bench -- python3 bench.py --steps 3 --warmup 1 --no-alt --no-extras --no-cpu-baseline --contract f32 > $P/bench_f32_line.json 2> $P/bench_f32.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $P/bench -o bench -- python3 bench.py --steps 3 --warmup 1 --full --no-alt --no-extras --no-cpu-baseline > $P/bench_line.json 2> $P/bench.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $P/bench_f32 -o bench -- python3 bench.py --steps 3 --warmup 1 --full --no-alt --no-extras --no-cpu-baseline --contract f32 > $P/bench_f32_line.json 2> $P/bench_f32.err
 rocprofv3 --kernel-trace --stats --output-format csv -d $P/train -o train -- python3 tools/bench_train.py --size 256 --batch 4 --steps 1 --warmup 1 > $P/train_line.json 2> $P/train.err
 # BASELINE config C3 itself: one optimizer step at batch 64 (the program directly behind --)
 rocprofv3 --kernel-trace --stats --output-format csv -d $P/train64 -o train -- python3 tools/bench_train.py --size 256 --batch 64 --steps 1 --warmup 1 > $P/train64_line.json 2> $P/train64.err
@@ -68,7 +68,7 @@ run_pmc bwd32_sq2 $SQ2 -- python3 tools/attn_bwd_once.py 4 256 16384
 for c in FETCH_SIZE WRITE_SIZE; do run_pmc bwd_$c $c -- python3 tools/attn_bwd_once.py 4; done
 fi
 if [ "$PART" = pmcfwd ]; then   # only the d_head 16 forward's passes and the headline trace (after a change to attention_h2.hip alone)
-rocprofv3 --kernel-trace --stats --output-format csv -d $P/bench -o bench -- python3 bench.py --steps 3 --warmup 1 --no-alt --no-extras --no-cpu-baseline > $P/bench_line.json 2> $P/bench.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $P/bench -o bench -- python3 bench.py --steps 3 --warmup 1 --full --no-alt --no-extras --no-cpu-baseline > $P/bench_line.json 2> $P/bench.err
 run_pmc x3_sq1 $SQ1 -- python3 tools/attn_once.py 16
 run_pmc x3_sq2 $SQ2 -- python3 tools/attn_once.py 16
 for c in FETCH_SIZE WRITE_SIZE; do run_pmc x3_$c $c -- python3 tools/attn_once.py 16; done
