@@ -12,6 +12,9 @@ emits) with its hand-written backward:
   _FlashFn     flash attention core; bwd recomputes P from the saved log-sum-exp (attention_bwd.hip)
   _LinearFn / _VecFn   the small dense layers (time / label MLPs, per-block projections)
   _SqErrFn     the unreduced squared error
+  _StridedConvFn / _PoolFn / _ResizeFn / _TrainTailFn   the second tree (DynamicUNet, diffusion/Model.py): the image encoder's
+               stride-2 convs (dgrad = 4 output-parity phases), its global average pool, the skip resize, and the trainer's
+               fused loss tail (mse, y0_pred, colour term; train_b_ops.hip)
 
 PyTorch provides the autograd graph, gradient accumulation and the optimizer; no arithmetic of the model runs in ATen.
 """
@@ -396,14 +399,18 @@ class _LinearFn(Function):
         lib = _capi.lib()
         B, N, K = int(dy.shape[0]), int(W.shape[0]), int(W.shape[1])
         n_rows = int(x.shape[0]) if idx is not None else 0
-        d_W = torch.empty_like(W)
-        d_b = torch.empty(N, device=W.device) if ctx.has_bias else None
+        # a frozen layer (requires_grad False, e.g. a middle block gated off by DynamicUNet.dynamic_forward) launches no
+        # weight-gradient kernel: the input gradient alone still flows through it
+        want_w = ctx.needs_input_grad[2] or (ctx.has_bias and ctx.needs_input_grad[3])
+        d_W = torch.empty_like(W) if want_w else None
+        d_b = torch.empty(N, device=W.device) if (ctx.has_bias and want_w) else None
         d_x = None
         if ctx.needs_input_grad[0]:
             d_x = torch.zeros_like(x) if idx is not None else torch.empty_like(x)
-        _capi.check(lib.hdiff_linear_rows_bwd(x.data_ptr(), _p(idx), n_rows, W.data_ptr(), dy.data_ptr(), _p(d_x),
-                                              d_W.data_ptr(), _p(d_b), B, K, N, int(ctx.swish), 0, ctx.pad_row,
-                                              _stream(W.device)), "linear_rows_bwd")
+        if d_W is not None or d_x is not None:
+            _capi.check(lib.hdiff_linear_rows_bwd(x.data_ptr(), _p(idx), n_rows, W.data_ptr(), dy.data_ptr(), _p(d_x),
+                                                  _p(d_W), _p(d_b), B, K, N, int(ctx.swish), 0, ctx.pad_row,
+                                                  _stream(W.device)), "linear_rows_bwd")
         return d_x, None, d_W, d_b, None, None
 
 
@@ -582,3 +589,206 @@ def unet_forward_with_grad(model, x, t, labels):
 
 def sq_err_with_grad(eps_hat, noise):
     return _SqErrFn.apply(eps_hat, noise)
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# second tree: DynamicUNet (diffusion/Model.py:382-517) and the loss tail of its trainer (diffusion/Diffusion.py:26-180)
+# ----------------------------------------------------------------------------------------------------------------------
+def _s2_phase_taps(py: int, px: int) -> E.TapSet:
+    """Input-gradient phase (py, px) of Conv2d(3, stride 2, pad 1): dX[2y+py][2x+px] gathers dY[y+dy][x+dx] * w[ky][kx] over
+    the kernel elements with ky = py + 1 - 2*dy (forward: iy = 2*oy - 1 + ky)."""
+    kys = [ky for ky in range(3) if (ky - py - 1) % 2 == 0]
+    kxs = [kx for kx in range(3) if (kx - px - 1) % 2 == 0]
+    t = E.TapSet([], [], [], [])
+    for ky in kys:
+        for kx in kxs:
+            t.dy.append((py + 1 - ky) // 2)
+            t.dx.append((px + 1 - kx) // 2)
+            t.ky.append(ky)
+            t.kx.append(kx)
+    return t
+
+
+class _StridedConvFn(Function):
+    """nn.Conv2d(cin, cout, 3, stride=2, padding=1) with bias and nothing fused: the three convs of the image encoder
+    (ConditionalEmbedding, diffusion/Model.py:115-117; cin = 3, ch/16, ch/8)."""
+
+    @staticmethod
+    def forward(ctx, x, w, b):
+        x, w = x.contiguous(), w.contiguous()
+        B, cin, H, W = (int(v) for v in x.shape)
+        cout = int(w.shape[0])
+        OH, OW = (H - 1) // 2 + 1, (W - 1) // 2 + 1
+        taps = E.conv_taps(3, 1)
+        out = torch.empty(B, cout, OH, OW, device=x.device)
+        _run_conv(x, None, [(w, 0, taps.ky, taps.kx, 0)], taps, cout, cin, b, out, B=B, H=H, W=W, VH=OH, VW=OW, in_stride=2)
+        ctx.save_for_backward(x, w)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        x, w = ctx.saved_tensors
+        dout = dout.contiguous()
+        need = ctx.needs_input_grad
+        B, cin, H, W = (int(v) for v in x.shape)
+        cout, OH, OW = int(w.shape[0]), int(dout.shape[2]), int(dout.shape[3])
+        _, d_b = _plane_sums(dout, False, need[2])
+        d_w = None
+        if need[1]:
+            # the generic wgrad kernel's stride-2 tile holds 16 channels x 9 taps only for narrow planes; the 25-tap stencil of
+            # DownSample's folded 5x5 (4 channels per tile) fits everywhere: the 3x3 is its centre (taps off it are not unpacked)
+            d_w = torch.empty_like(w)
+            t5 = E.conv_taps(5, 2)
+            ky3, kx3 = _down_center_map(t5)
+            _run_wgrad(x, None, None, dout, t5, cout, cin, B=B, H=H, W=W, VH=OH, VW=OW, in_stride=2,
+                       targets=[(d_w, 0, ky3, kx3, 0)])
+        d_x = None
+        if need[0]:
+            # the transposed conv of dY as 4 output-parity phases, the weight read as [GEMM-in = cout][GEMM-out = cin] (mode 1)
+            d_x = torch.zeros_like(x) if (H % 2 or W % 2) else torch.empty_like(x)
+            for py in (0, 1):
+                for px in (0, 1):
+                    pt = _s2_phase_taps(py, px)
+                    VH, VW = (H - py + 1) // 2, (W - px + 1) // 2
+                    if VH <= 0 or VW <= 0:
+                        continue
+                    _run_conv(dout, None, [(w, 1, pt.ky, pt.kx, 0)], pt, cin, cout, None, d_x, B=B, H=OH, W=OW, VH=VH, VW=VW,
+                              out_map=(2, py, 2, px))
+        return d_x, d_w, d_b
+
+
+class _PoolFn(Function):
+    """nn.AdaptiveAvgPool2d((1, 1)) + flatten: [B, C, H, W] -> [B, C] (diffusion/Model.py:150-153)."""
+
+    @staticmethod
+    def forward(ctx, x):
+        x = x.contiguous()
+        B, Cc, H, W = (int(v) for v in x.shape)
+        y = torch.empty(B, Cc, device=x.device)
+        _capi.check(_capi.lib().hdiff_avgpool_global(x.data_ptr(), y.data_ptr(), B * Cc, H * W, _stream(x.device)), "avgpool_global")
+        ctx.shape = (B, Cc, H, W)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        B, Cc, H, W = ctx.shape
+        dy = dy.contiguous()
+        dx = torch.empty(B, Cc, H, W, device=dy.device)
+        _capi.check(_capi.lib().hdiff_avgpool_global_bwd(dy.data_ptr(), dx.data_ptr(), B * Cc, H * W, _stream(dy.device)),
+                    "avgpool_global_bwd")
+        return dx
+
+
+class _ResizeFn(Function):
+    """F.interpolate(skip, size=(OH, OW), mode="nearest") of a skip tensor (diffusion/Model.py:505-508)."""
+
+    @staticmethod
+    def forward(ctx, x, OH: int, OW: int):
+        x = x.contiguous()
+        B, Cc, H, W = (int(v) for v in x.shape)
+        y = torch.empty(B, Cc, OH, OW, device=x.device)
+        _capi.check(_capi.lib().hdiff_resize_nearest(x.data_ptr(), y.data_ptr(), B * Cc, H, W, OH, OW, _stream(x.device)),
+                    "resize_nearest")
+        ctx.shape = (B, Cc, H, W)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        B, Cc, H, W = ctx.shape
+        dy = dy.contiguous()
+        dx = torch.empty(B, Cc, H, W, device=dy.device)
+        _capi.check(_capi.lib().hdiff_resize_nearest_bwd(dy.data_ptr(), dx.data_ptr(), B * Cc, H, W, int(dy.shape[2]),
+                                                         int(dy.shape[3]), _stream(dy.device)), "resize_nearest_bwd")
+        return dx, None, None
+
+
+class _TrainTailFn(Function):
+    """The trainer's loss tail (diffusion/Diffusion.py:102-107, :172-174) in one launch pair: -> (mse [B,3,H,W], y0_pred
+    [B,3,H,W], col_loss []).  Backward: ONE pass forming d noise_pred from the three incoming gradients (any may be absent)."""
+
+    @staticmethod
+    def forward(ctx, noise_pred, noise, y_t, gt, t, sa, s1m):
+        noise_pred = noise_pred.contiguous()
+        lib = _capi.lib()
+        B, Cc, H, W = (int(v) for v in noise_pred.shape)
+        if Cc != 3:
+            raise RuntimeError(f"hdiff: the loss tail takes 3-channel images, got {Cc}")
+        dev = noise_pred.device
+        mse, y0 = torch.empty_like(noise_pred), torch.empty_like(noise_pred)
+        col = torch.empty((), device=dev)
+        nbytes = C.c_int64(0)
+        _capi.check(lib.hdiff_train_b_loss_workspace(B * H * W, C.byref(nbytes)), "train_b_loss_workspace")
+        ws = torch.empty(nbytes.value // 4, dtype=torch.float32, device=dev)
+        _capi.check(lib.hdiff_train_b_loss_fwd(noise_pred.data_ptr(), noise.data_ptr(), y_t.data_ptr(), gt.data_ptr(), t.data_ptr(),
+                                               sa.data_ptr(), s1m.data_ptr(), int(sa.numel()), B, H * W, mse.data_ptr(),
+                                               y0.data_ptr(), col.data_ptr(), ws.data_ptr(), _stream(dev)), "train_b_loss_fwd")
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(noise_pred, noise, y0, gt, t, sa, s1m)
+        return mse, y0, col
+
+    @staticmethod
+    def backward(ctx, d_mse, d_y0, d_col):
+        noise_pred, noise, y0, gt, t, sa, s1m = ctx.saved_tensors
+        d_np = None
+        if ctx.needs_input_grad[0] and not (d_mse is None and d_y0 is None and d_col is None):
+            B, _, H, W = (int(v) for v in noise_pred.shape)
+            d_np = torch.empty_like(noise_pred)
+            d_mse, d_y0, d_col = _c(d_mse), _c(d_y0), _c(d_col)
+            _capi.check(_capi.lib().hdiff_train_b_loss_bwd(noise_pred.data_ptr(), noise.data_ptr(), y0.data_ptr(), gt.data_ptr(),
+                                                           t.data_ptr(), sa.data_ptr(), s1m.data_ptr(), int(sa.numel()), B, H * W,
+                                                           _p(d_mse), _p(d_y0), _p(d_col), d_np.data_ptr(),
+                                                           _stream(noise_pred.device)), "train_b_loss_bwd")
+        return d_np, None, None, None, None, None, None
+
+
+def train_b_loss_tail(noise_pred, noise, y_t, gt, t, sqrt_ab, sqrt_1mab):
+    """(mse, y0_pred, col_loss) of GaussianDiffusionTrainer.forward; sqrt_ab / sqrt_1mab are fp32 tables of length T."""
+    return _TrainTailFn.apply(noise_pred, noise.contiguous(), y_t.contiguous(), gt.contiguous(), t.contiguous(),
+                              sqrt_ab.contiguous(), sqrt_1mab.contiguous())
+
+
+def cond_image_embedding(ce, label):
+    """ConditionalEmbedding.forward (diffusion/Model.py:135-166) with gradients: three stride-2 convs (no activation), global
+    average pool, Linear -> Swish -> Linear.  The label image itself gets no gradient."""
+    x = label
+    for conv in (ce.conv1, ce.conv2, ce.conv3):
+        x = _StridedConvFn.apply(x, conv.weight, conv.bias)
+    pooled = _PoolFn.apply(x)
+    h = _LinearFn.apply(pooled, None, ce.linear1.weight, ce.linear1.bias, False)
+    return _LinearFn.apply(h, None, ce.linear2.weight, ce.linear2.bias, True)
+
+
+def dyn_unet_forward_with_grad(model, x, t, labels, context_zero: bool):
+    """DynamicUNet.forward (diffusion/Model.py:475-515) with autograd through the HIP kernels.  ``x`` is the 6-channel
+    [conditioning image | noisy image] input, which gets no gradient (the head conv computes its weight gradient only).
+    The middle blocks gated off by ``dynamic_forward`` have requires_grad False: they launch no weight-gradient kernels and
+    the input gradient flows through them."""
+    from .DiffusionFreeGuidence.ModelCondition import ResBlock as ResBlockA
+    from .diffusion.Model import ResBlock
+    training = model.training
+    B = int(x.shape[0])
+    temb = embed_mlp(model.time_embedding.timembedding, t)
+    if context_zero:
+        cemb = torch.zeros(B, int(temb.shape[1]), device=x.device)      # torch.zeros_like(temb): cond_proj's bias still applies
+    else:
+        cemb = cond_image_embedding(model.cond_embedding, labels)
+    h = fused_conv(x, None, model.head.weight, model.head.bias, k=3)
+    hs = [h]
+    for layer in model.downblocks:
+        if isinstance(layer, (ResBlock, ResBlockA)):
+            h = res_block(layer, h, None, temb, cemb, training)
+        else:
+            h = _DownFn.apply(h, layer.c1.weight, layer.c1.bias, layer.c2.weight, layer.c2.bias)
+        hs.append(h)
+    for layer in model.middleblocks:
+        h = res_block(layer, h, None, temb, cemb, training)
+    for layer in model.upblocks:
+        if isinstance(layer, (ResBlock, ResBlockA)):
+            skip = hs.pop()
+            if tuple(skip.shape[2:]) != tuple(h.shape[2:]):
+                skip = _ResizeFn.apply(skip, int(h.shape[2]), int(h.shape[3]))
+            h = res_block(layer, h, skip, temb, cemb, training)
+        else:
+            u = _TConvFn.apply(h, layer.t.weight, layer.t.bias)
+            h = fused_conv(u, None, layer.c.weight, layer.c.bias, k=3)
+    return fused_conv(h, None, model.tail[2].weight, model.tail[2].bias, model.tail[0].weight, model.tail[0].bias, k=3)

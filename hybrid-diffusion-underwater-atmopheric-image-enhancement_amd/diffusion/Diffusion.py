@@ -1,8 +1,8 @@
-"""Drop-in for the sampler of the reference's ``diffusion/Diffusion.py``: ``extract`` (:16-23) and
-``GaussianDiffusionSampler`` (:182-269) -- the image-conditioned ancestral sampler and the deterministic DDIM sampler --
-with the same constructor / ``forward`` signature, registered float64 buffers and plain attributes.
+"""Drop-in for the reference's ``diffusion/Diffusion.py``: ``extract`` (:16-23), ``GaussianDiffusionTrainer`` (:26-180) and
+``GaussianDiffusionSampler`` (:182-269) -- the image-conditioned trainer, the ancestral sampler and the deterministic DDIM
+sampler -- with the same constructor / ``forward`` signatures, registered float64 buffers and plain attributes.
 
-Underneath: one DynamicUNet evaluation + one fused update kernel per step, the whole step captured into a hipGraph and
+Sampler underneath: one DynamicUNet evaluation + one fused update kernel per step, the whole step captured into a hipGraph and
 replayed (device-resident step counter, time-step and coefficient tables); y_t is updated in place in the plan's buffer.
 
 Kept as written in the reference, on purpose:
@@ -12,7 +12,12 @@ Kept as written in the reference, on purpose:
     so one evaluation is issued here;
   * DDIM lays its time steps over a literal 1000 and reads ``alphas_bar[t + 1]`` (:243-251); ``eta = 0`` makes the
     per-step ``c1 * randn`` term an exact zero (:260-263).
-The trainer of this file (:26-180) needs pretrained VGG / DINO / LPIPS networks and is out of scope.
+
+Trainer underneath: q_sample and the 3 + 3 channel concat are HIP launches, the DynamicUNet runs its autograd path
+(``autograd.dyn_unet_forward_with_grad``) and the loss tail -- the squared error, ``y_0_pred`` and the angular-colour term,
+and their joint backward -- is one fused kernel pair (``csrc/train_b_ops.hip``).  The reference's pretrained DINOv2
+perceptual loss and kornia MS-SSIM are not part of this package: they are passed in as callables (``dino_loss=``,
+``msssim_loss=``); a term without one is returned as zero and left out of ``loss``.
 """
 from __future__ import annotations
 
@@ -27,8 +32,9 @@ import torch.nn.functional as F
 
 from .. import _capi
 from .. import engine as E
+from ..DiffusionFreeGuidence.DiffusionCondition import _gpu_input, _timesteps
 
-__all__ = ["extract", "GaussianDiffusionSampler"]
+__all__ = ["extract", "GaussianDiffusionTrainer", "GaussianDiffusionSampler"]
 
 
 def extract(v, t, x_shape):
@@ -36,6 +42,103 @@ def extract(v, t, x_shape):
     device = t.device
     out = torch.gather(v, index=t, dim=0).float().to(device)
     return out.view([t.shape[0]] + [1] * (len(x_shape) - 1))
+
+
+class GaussianDiffusionTrainer(nn.Module):
+    """forward(gt_images, input_image, stage) -> [loss, mse_loss, perceptual_dino, msssim, col_loss] (reference :26-180).
+
+    ``perceptual_vgg`` / ``perceptual_dino`` are the reference's model names; they are recorded but never loaded (no
+    ``torch.hub``, no kornia).  ``dino_loss`` / ``msssim_loss`` are the caller's callables ``(y_0_pred, gt) -> scalar tensor``
+    for those two terms; they run under torch autograd and their gradient reaches the model through ``y_0_pred``."""
+
+    DINO_WEIGHT, MSSSIM_WEIGHT, COL_WEIGHT = 0.5, 0.0045, 1.0          # reference :165
+
+    def __init__(self, model, beta_1, beta_T, T, perceptual_vgg: str = "vgg16", perceptual_dino: str = "dinov2_vits14", *,
+                 dino_loss=None, msssim_loss=None):
+        super().__init__()
+        self.model = model
+        self.T = T
+        self.register_buffer('betas', torch.linspace(beta_1, beta_T, T).double())
+        alphas_bar = torch.cumprod(1. - self.betas, dim=0)
+        self.register_buffer('sqrt_alphas_bar', torch.sqrt(alphas_bar))
+        self.register_buffer('sqrt_one_minus_alphas_bar', torch.sqrt(1. - alphas_bar))
+        self.num = 0
+        self.stage = 0
+        self.perceptual_vgg, self.perceptual_dino = perceptual_vgg, perceptual_dino
+        self.loss_perceptual_dino = dino_loss
+        self.ms_ssim_loss = msssim_loss
+        self._warned_missing = False
+
+    def _warn_missing(self):
+        missing = [f"{name} (weight {w})" for name, fn, w in
+                   (("the DINOv2 perceptual loss '" + str(self.perceptual_dino) + "'", self.loss_perceptual_dino, self.DINO_WEIGHT),
+                    ("the MS-SSIM loss", self.ms_ssim_loss, self.MSSSIM_WEIGHT)) if fn is None]
+        if missing and not self._warned_missing:
+            self._warned_missing = True
+            warnings.warn("GaussianDiffusionTrainer: no callable for " + " and ".join(missing) + "; the reference adds it to "
+                          "the loss, here it is returned as zero and left out (pass dino_loss= / msssim_loss=)",
+                          RuntimeWarning, stacklevel=3)
+
+    def forward(self, gt_images, input_image, stage, *, t=None, noise=None, context_zero=None):
+        """Images in [0, 255] (uint8 or float).  ``t`` / ``noise`` / ``context_zero`` inject the random draws (parity tests); by
+        default they are drawn where the reference draws them: ``torch.randint`` and ``torch.randn_like`` on the device, then
+        the host ``torch.rand(1) < 0.02`` (reference :50-67).  As there, a drawn False calls ``model(input, t, gt_images)``,
+        whose default is ``context_zero=True``; an injected value is passed to the model as given."""
+        self.stage = stage
+        self._warn_missing()
+        if not (gt_images.is_cuda and input_image.is_cuda):
+            E.require_gpu_tensor(gt_images if not gt_images.is_cuda else input_image, "images")
+        input_image = (input_image.float() / 255.0) * 2 - 1                                       # :46-47
+        gt_images = (gt_images.float() / 255.0) * 2 - 1
+        input_image = _gpu_input(input_image, "input_image")
+        gt_images = _gpu_input(gt_images, "gt_images")
+        if tuple(input_image.shape) != tuple(gt_images.shape) or int(gt_images.shape[1]) != 3:
+            raise RuntimeError(f"GaussianDiffusionTrainer: expected two [B, 3, H, W] images, got {tuple(gt_images.shape)} and "
+                               f"{tuple(input_image.shape)}")
+        dev = gt_images.device
+        B, _, H, W = (int(v) for v in gt_images.shape)
+        if t is None:
+            t = torch.randint(self.T, size=(B,), device=dev)                                       # :51
+        else:
+            t = _timesteps(t, self.T, dev)
+        if noise is None:
+            noise = torch.randn_like(gt_images, dtype=torch.float32)                               # :52
+        noise = _gpu_input(noise, "noise")
+        if tuple(noise.shape) != tuple(gt_images.shape):
+            raise RuntimeError(f"GaussianDiffusionTrainer: noise has shape {tuple(noise.shape)}, expected {tuple(gt_images.shape)}")
+        lib = _capi.lib()
+        sa = self.sqrt_alphas_bar.float().to(dev).contiguous()            # extract(): the fp32 cast of the float64 schedule
+        s1m = self.sqrt_one_minus_alphas_bar.float().to(dev).contiguous()
+        with torch.cuda.device(dev):
+            s = torch.cuda.current_stream(dev).cuda_stream
+            y_t = torch.empty_like(gt_images)
+            _capi.check(lib.hdiff_q_sample(gt_images.data_ptr(), noise.data_ptr(), t.data_ptr(), sa.data_ptr(), s1m.data_ptr(),
+                                           y_t.data_ptr(), B, 3 * H * W, self.T, s), "q_sample")          # :53-55
+            x6 = torch.empty(B, 6, H, W, device=dev)
+            _capi.check(lib.hdiff_concat2(input_image.data_ptr(), y_t.data_ptr(), x6.data_ptr(), B, 3 * H * W, 3 * H * W, s),
+                        "concat2")                                                                         # :57
+            if context_zero is None:
+                if torch.rand(1) < 0.02:                                                                   # :61-64
+                    noise_pred = self.model(x6, t, gt_images, context_zero=True)
+                else:
+                    noise_pred = self.model(x6, t, gt_images)
+            else:
+                noise_pred = self.model(x6, t, gt_images, context_zero=bool(context_zero))
+            from ..autograd import train_b_loss_tail
+            # mse_loss (:102), y_0_pred with the reference's trailing / 255.0 (sic, :106-107: kept), colour term (:172)
+            mse_loss, y_0_pred, col = train_b_loss_tail(noise_pred, noise, y_t, gt_images, t, sa, s1m)
+        zero = torch.zeros((), device=dev)
+        loss = mse_loss
+        perceptual_dino, msssim = zero, zero
+        if self.loss_perceptual_dino is not None:
+            perceptual_dino = self.loss_perceptual_dino(y_0_pred, gt_images) * self.DINO_WEIGHT           # :168-169
+            loss = loss + perceptual_dino
+        if self.ms_ssim_loss is not None:
+            msssim = self.ms_ssim_loss(y_0_pred, gt_images) * self.MSSSIM_WEIGHT                          # :171-172
+            loss = loss + msssim
+        col_loss = col * self.COL_WEIGHT                                                                   # :174-175
+        loss = loss + col_loss
+        return [loss, mse_loss, perceptual_dino, msssim, col_loss]
 
 
 class _StepPlan:

@@ -3,9 +3,10 @@ is built from -- same class names, constructor / ``forward`` signatures, paramet
 ``state_dict`` of the default configuration) and initialisation order (``torch.manual_seed`` gives the reference's weights).
 
 As in ``DiffusionFreeGuidence/ModelCondition.py`` the ``torch.nn`` leaf modules are parameter containers only; every
-``forward`` issues hand-written gfx950 kernels through ``libhdiff.so``.  Inference only: this tree's trainer
-(``diffusion/Diffusion.py:26-180``) is built on pretrained VGG / DINO perceptual losses and is out of scope, so a forward that
-would have to record an autograd graph raises.
+``forward`` issues hand-written gfx950 kernels through ``libhdiff.so``.  Without autograd (and in eval mode) ``DynamicUNet``
+runs a cached static launch plan; when a graph has to be recorded, or train-mode dropout is active, it runs the eager autograd
+path (``autograd.dyn_unet_forward_with_grad``: hand-written backward kernels, the gradient of the trainer of
+``diffusion/Diffusion.py``).  No gradient is computed for the 6-channel input itself.
 """
 from __future__ import annotations
 
@@ -165,12 +166,10 @@ class DynamicUNet(nn.Module):
     def forward(self, x, t, labels=None, context_zero=True):
         x, t = _inputs(x=x, t=t)
         self.dynamic_forward(x)
-        if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters())):
-            raise NotImplementedError("hdiff: DynamicUNet runs inference only on the HIP path (call it under torch.no_grad()); "
-                                      "this tree's trainer depends on pretrained perceptual networks and is out of scope")
-        if _dropout_active(self):
-            raise NotImplementedError("hdiff: DynamicUNet runs inference only on the HIP path: call .eval() (train-mode dropout "
-                                      "belongs to this tree's trainer, which is out of scope)")
+        records = torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters()))
+        if records and x.requires_grad:
+            raise RuntimeError("hdiff: DynamicUNet computes no gradient with respect to its input x; detach it (the trainer's "
+                               "input is data)")
         B, Cx, H, W = (int(v) for v in x.shape)
         if Cx != 6:
             raise RuntimeError(f"expected input[{B}, {Cx}, {H}, {W}] to have 6 channels")
@@ -181,6 +180,12 @@ class DynamicUNet(nn.Module):
             if labels is None:
                 raise AttributeError("'NoneType' object has no attribute 'shape'")      # what the reference's conv would hit
             labels = _inputs(labels=labels)
+        if records or _dropout_active(self):
+            # training, or train-mode dropout under no_grad (nn.Dropout applies there too, Model.py:283): the eager
+            # launches through the autograd Functions, which carry the backward and the dropout kernels
+            from ..autograd import dyn_unet_forward_with_grad
+            with torch.cuda.device(x.device):
+                return dyn_unet_forward_with_grad(self, x, t, labels, bool(context_zero))
         up = self.plan_for(B, H, W, x.device, context_zero)
         up.cond.copy_(x[:, :3])
         up.y.copy_(x[:, 3:])

@@ -37,6 +37,7 @@ class AdamW(torch.optim.Optimizer):
         self._tables: dict = {}          # group index -> (signature, table tensor, chunk tensor, nchunks)
         self._scratch: Optional[torch.Tensor] = None
         self._norm_coef: Optional[torch.Tensor] = None
+        self._chunk_cache: dict = {}     # (group, chunk table, cohort) -> the cohort's chunk list on the device
 
     # -- state: one flat buffer per group for each moment, the per-parameter entries are views (torch's state layout) ------------
     def _ensure_state(self, gi: int, group: dict) -> None:
@@ -47,8 +48,8 @@ class AdamW(torch.optim.Optimizer):
         n = sum(p.numel() for p in need)
         m_flat, v_flat = torch.zeros(n, dtype=torch.float32, device=dev), torch.zeros(n, dtype=torch.float32, device=dev)
         off = 0
-        shared_step = torch.tensor(0.0)      # ONE step counter object for the parameters that start together (incremented once per step)
-        for p in need:
+        shared_step = torch.tensor(0.0)      # one counter object for the parameters that start together; a parameter that
+        for p in need:                       # skips a step leaves it (step(): counts advance only with a gradient)
             st = self.state[p]
             st["step"] = shared_step
             st["exp_avg"] = m_flat[off:off + p.numel()].view_as(p)
@@ -80,6 +81,38 @@ class AdamW(torch.optim.Optimizer):
         c_dev = torch.tensor(chunks, dtype=torch.int32).to(dev)
         self._tables[gi] = (sig, t_dev, c_dev, len(chunks), ps)
         return self._tables[gi]
+
+    def _cohorts(self, group: dict, ps) -> List[Tuple[int, List[int], list]]:
+        """[(next step count, indices into ps, [(counter, indices into ps, shared with a parameter outside ps?)])] in increasing
+        count order.  Parameters that start together share one counter object while they keep stepping together."""
+        holders: dict = {}
+        for p in group["params"]:
+            st = self.state.get(p)
+            if st is not None and "step" in st:
+                holders[id(st["step"])] = holders.get(id(st["step"]), 0) + 1
+        objs: dict = {}
+        for i, p in enumerate(ps):
+            c = self.state[p]["step"]
+            objs.setdefault(id(c), (c, []))[1].append(i)
+        by: dict = {}
+        for c, idx in objs.values():
+            k = int(c.item()) if torch.is_tensor(c) else int(c)
+            ent = by.setdefault(k, ([], []))
+            ent[0].extend(idx)
+            ent[1].append((c, idx, holders.get(id(c), 0) > len(idx)))
+        return [(k + 1, sorted(by[k][0]), by[k][1]) for k in sorted(by)]
+
+    def _cohort_chunks(self, gi: int, ps, idx: List[int], c_dev: torch.Tensor) -> torch.Tensor:
+        """The chunk list of the tensors ``idx`` of the group's table (cached per table and cohort)."""
+        key = (gi, c_dev.data_ptr(), tuple(idx))
+        hit = self._chunk_cache.get(key)
+        if hit is None:
+            ch = [(i, c) for i in idx for c in range((ps[i].numel() + self._chunk - 1) // self._chunk)]
+            hit = torch.tensor(ch, dtype=torch.int32).to(c_dev.device)
+            if len(self._chunk_cache) > 64:
+                self._chunk_cache.clear()
+            self._chunk_cache[key] = hit
+        return hit
 
     @torch.no_grad()
     def step(self, closure=None, max_grad_norm: Optional[float] = None):
@@ -118,23 +151,24 @@ class AdamW(torch.optim.Optimizer):
                             "grad_norm_clip_coef")
                 self._keep = (t_dev, c_dev)
             coef_ptr = self._norm_coef.data_ptr()
-        for group, (_, t_dev, c_dev, n, ps) in zip(self.param_groups, tables):
+        for gi, (group, (_, t_dev, c_dev, n, ps)) in enumerate(zip(self.param_groups, tables)):
             if n == 0:
                 continue
-            counters = {id(self.state[p]["step"]): self.state[p]["step"] for p in ps}      # distinct counter objects (one, unless states were loaded)
-            steps = {int(c.item()) if torch.is_tensor(c) else int(c) for c in counters.values()}
-            if len(steps) != 1:
-                raise RuntimeError("hdiff_amd.optim.AdamW: the parameters of a group must have taken the same number of steps")
-            step = steps.pop() + 1
             b1, b2 = group["betas"]
-            _capi.check(self._lib.hdiff_adamw_step(t_dev.data_ptr(), c_dev.data_ptr(), n, coef_ptr, float(group["lr"]), float(b1), float(b2),
-                                                   float(group["eps"]), float(group["weight_decay"]), step, stream), "adamw_step")
-            if all(torch.is_tensor(c) for c in counters.values()):
-                for c in counters.values():
-                    c.fill_(float(step))
-            else:
-                for p in ps:
-                    self.state[p]["step"] = torch.tensor(float(step))
+            # cohorts of equal step count (torch's AdamW keeps one count per parameter and advances only those with a gradient:
+            # a parameter that skips steps -- DynamicUNet's gated middle blocks -- falls behind), one launch per cohort
+            for step, idx, counters in self._cohorts(group, ps):
+                chunks = c_dev if len(idx) == len(ps) else self._cohort_chunks(gi, ps, idx, c_dev)
+                _capi.check(self._lib.hdiff_adamw_step(t_dev.data_ptr(), chunks.data_ptr(), int(chunks.shape[0]), coef_ptr,
+                                                       float(group["lr"]), float(b1), float(b2), float(group["eps"]),
+                                                       float(group["weight_decay"]), step, stream), "adamw_step")
+                for c, cidx, shared_outside in counters:
+                    if torch.is_tensor(c) and not shared_outside:
+                        c.fill_(float(step))
+                    else:       # the counter's other holders took no step: these parameters go on with a counter of their own
+                        fresh = torch.tensor(float(step))
+                        for i in cidx:
+                            self.state[ps[i]]["step"] = fresh
         if max_grad_norm is not None:
             return self._norm_coef[0].clone()
         return loss

@@ -337,6 +337,29 @@ int hdiff_fill_from_table(int64_t* dst, const int32_t* table, const int32_t* idx
 int hdiff_resize_nearest(const float* x, float* y, int BC, int H, int W, int OH, int OW, hdiff_stream_t stream);
 int hdiff_avgpool_global(const float* x, float* y, int BC, int HW, hdiff_stream_t stream);
 int hdiff_concat2(const float* a, const float* b, float* out, int B, int64_t n0, int64_t n1, hdiff_stream_t stream);
+/* ------------------------------------------------------------------------------------------------------------------
+ * Trainer of the second tree (diffusion/Diffusion.py:26-180) and the backward passes of its image encoder / skip resize.
+ *   hdiff_train_b_loss_fwd   from noise_pred, noise, y_t, gt [B][3][HW] and t: mse = (noise_pred - noise)^2,
+ *                            y0_pred = ((1 / sqrt_ab[t]) * (y_t - sqrt_1mab[t] * noise_pred)) / 255 (the reference's trailing
+ *                            / 255 kept), col[0] = 1 - mean over pixels of cosine_similarity(normalize(y0_pred), normalize(gt))
+ *                            over the channel axis (eps 1e-12 / 1e-8 as torch).  sqrt_ab / sqrt_1mab: fp32 tables of length T,
+ *                            t[b] clamped into [0, T).  workspace: hdiff_train_b_loss_workspace(B * HW) bytes (per-block
+ *                            partial sums, reduced in a fixed order: bitwise reproducible)
+ *   hdiff_train_b_loss_bwd   d_noise_pred from d_mse [B][3][HW], d_y0 (an external dL/dy0_pred) and d_col (device scalar),
+ *                            each of which may be NULL, in one pass
+ *   hdiff_avgpool_global_bwd dx[bc][i] = dy[bc] / HW (AdaptiveAvgPool2d((1,1)), Model.py:150)
+ *   hdiff_resize_nearest_bwd the backward of hdiff_resize_nearest ([BC][H][W] -> [BC][OH][OW]) in gather form: dx[bc][iy][ix] =
+ *                            the sum, in increasing output order, of the dy elements that read it (no atomics)
+ * ------------------------------------------------------------------------------------------------------------------ */
+int hdiff_train_b_loss_workspace(int64_t pixels, int64_t* bytes);
+int hdiff_train_b_loss_fwd(const float* noise_pred, const float* noise, const float* y_t, const float* gt, const int64_t* t,
+                           const float* sqrt_ab, const float* sqrt_1mab, int T, int B, int HW, float* mse, float* y0_pred,
+                           float* col, void* workspace, hdiff_stream_t stream);
+int hdiff_train_b_loss_bwd(const float* noise_pred, const float* noise, const float* y0_pred, const float* gt, const int64_t* t,
+                           const float* sqrt_ab, const float* sqrt_1mab, int T, int B, int HW, const float* d_mse,
+                           const float* d_y0, const float* d_col, float* d_noise_pred, hdiff_stream_t stream);
+int hdiff_avgpool_global_bwd(const float* dy, float* dx, int BC, int HW, hdiff_stream_t stream);
+int hdiff_resize_nearest_bwd(const float* dy, float* dx, int BC, int H, int W, int OH, int OW, hdiff_stream_t stream);
 /* final clip (:98) */
 int hdiff_clip(const float* x, float* y, float lo, float hi, int64_t n, hdiff_stream_t stream);
 /* out = a*x + b*y (y may be NULL): bias merges and other weight-preparation arithmetic */

@@ -10,7 +10,14 @@ Every rank trains on its own synthetic batch (seed = base + rank); the step adds
 training (hdiff_amd.parallel.FlatGradients: reduce-scatter + all-gather of the 190.8 MB flat gradient buffer).  Timing:
 barrier + synchronize on both sides, max over ranks; rank 0 prints one JSON line (samples/s = world * batch / time).
 The step itself is bench.train_steps -- the same code bench.py runs for its `configs.C3` entry.
-No 8-GPU run has been made from the build box (one GPU); the driver can run this."""
+No 8-GPU run has been made from the build box (one GPU); the driver can run this.
+
+  python tools/bench_train.py --tree b --size 256 --batch 2 --steps 10       the second tree (image-conditioned DynamicUNet,
+                                                                             default config ch=128, ch_mult=[1,2,2,2], 2 res
+                                                                             blocks, dropout 0.15): GaussianDiffusionTrainer
+                                                                             fwd + bwd + clip(1.0) + native AdamW, one GPU;
+                                                                             prints ms per optimizer step.  No DINOv2 / MS-SSIM
+                                                                             term (not part of the package)."""
 import argparse, json, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__))); sys.path.insert(0, ROOT)
 import torch
@@ -20,9 +27,52 @@ ap.add_argument("--gpus", type=int, default=None, help="ranks (one per GPU); > 1
 ap.add_argument("--size", type=int, default=256); ap.add_argument("--batch", type=int, default=8)
 ap.add_argument("--steps", type=int, default=3); ap.add_argument("--warmup", type=int, default=1)
 ap.add_argument("--dropout", type=float, default=0.15)
+ap.add_argument("--tree", choices=("a", "b"), default="a", help="a: the CFG-DDPM UNet (default); b: the image-conditioned DynamicUNet")
 ap.add_argument("--rehearse-one-gpu", action="store_true",
                 help="dev: the data-parallel code path with every rank on cuda:0 over gloo (RCCL refuses two ranks on one device)")
 a = ap.parse_args()
+
+
+def tree_b_steps(size, batch, steps, warmup, dropout):
+    import time
+    import warnings
+    from hdiff_amd import optim as HO
+    from hdiff_amd.diffusion.Diffusion import GaussianDiffusionTrainer
+    from hdiff_amd.diffusion.Model import DynamicUNet
+    dev = torch.device("cuda", 0)
+    torch.manual_seed(0)
+    m = DynamicUNet(T=1000, ch=128, ch_mult=[1, 2, 2, 2], num_res_blocks=2, dropout=dropout).to(dev).train()
+    tr = GaussianDiffusionTrainer(m, 1e-4, 0.02, 1000)
+    opt = HO.AdamW(m.parameters(), lr=1e-4, weight_decay=1e-4)
+    g = torch.Generator().manual_seed(1)
+    label = torch.randint(0, 256, (batch, 3, size, size), generator=g).to(torch.uint8).to(dev)
+    inp = (label.float() * torch.tensor([0.4, 0.9, 1.0], device=dev).view(1, 3, 1, 1)).to(torch.uint8)   # underwater-like cast
+    losses, times = [], []
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore", RuntimeWarning)          # "no DINO / MS-SSIM callable": by design here
+        for k in range(warmup + steps):
+            torch.cuda.synchronize(dev)
+            t0 = time.perf_counter()
+            opt.zero_grad()
+            loss = tr(label, inp, 0)[0]                          # rotinas.py:441-443 shape: trainer -> mean -> backward -> step
+            loss.mean().backward()
+            opt.step(max_grad_norm=1.0)
+            torch.cuda.synchronize(dev)
+            if k >= warmup:
+                times.append(time.perf_counter() - t0)
+            losses.append(loss.mean().item())
+    times.sort()
+    return {"tree": "b", "config": "ch=128,ch_mult=[1,2,2,2],num_res_blocks=2,dropout=%g" % dropout, "size": size, "batch": batch,
+            "steps": steps, "warmup": warmup, "ms_per_step_median": round(1e3 * times[len(times) // 2], 2),
+            "ms_per_step_min": round(1e3 * times[0], 2), "losses": [round(v, 5) for v in losses],
+            "gpu": torch.cuda.get_device_name(dev)}
+
+
+if a.tree == "b":
+    if a.gpus not in (None, 1):
+        sys.exit("bench_train.py --tree b: one GPU only (no data-parallel path for the second tree)")
+    print(json.dumps(tree_b_steps(a.size, a.batch, a.steps, a.warmup, a.dropout)), flush=True)
+    sys.exit(0)
 if a.gpus and a.gpus > 1 and "WORLD_SIZE" not in os.environ:      # plain start: become the launcher (the GPU is untouched so far)
     from hdiff_amd.parallel import launch_ranks
     sys.exit(launch_ranks(os.path.abspath(__file__), sys.argv[1:], a.gpus))
