@@ -3,6 +3,10 @@
 // P = exp2(S - lse) or the pair (dO, V) to fp16 PAIRS; round 5 moves the rest: EVERY operand is an fp16 pair now.
 // Same contract, layouts and dQ slab protocol (reference: autograd through nn.MultiheadAttention, ModelCondition.py:189,
 // 204-208, TrainCondition.py:60): bitwise reproducible.
+// Kernels: mha_bwd_absmax_kernel and mha_bwd_split_h2_kernel make the piece tensors (d 16 and 32); mha_bwd_h2_kernel<32> (two
+// workgroup barriers per 32-query tile) + mha_dq_reduce_h2_kernel<32> at d 32; mha_bwd_h2p_kernel (a software pipeline, one
+// barrier per tile) + mha_dq_reduce_h2p_kernel at d 16.  Round 5's two-barrier kernel at d 16 and the A/B and timing-ablation
+// build switches of rounds 4-6 are retired: git show 840a6d1 has them.
 //
 // A pair is x = x0 + x1 with x0 = fp16(x) and x1 = fp16 of the exact residual: 2^-22 |x| at worst as long as x1 is a NORMAL fp16
 // number.  Two ways to keep it one:
@@ -27,9 +31,9 @@
 //                                back, form (ii); q0 2^-8 by v_pk_mul_f16 after the transposed read
 //   dQ'^T += k^T dS'^T           a: k0 s0, b: (k1 2^8) s0 + k0 (s1 2^8); a + b 2^-8 and the factor c_q when the tile leaves
 //                                contracted ACROSS the eight-wave workgroup: every wave's dS images stay in LDS until the tile's barrier, then each wave
-//                                takes one 16 x 16 output tile over the 128 keys of four waves -- two partial tiles to sum instead of eight (Geo::DQX)
-// Per 16x16 (query, key) tile at d 16: 8.5 MFMAs and ~33 vector instructions per lane in the ISA (exp2 4, P split 6, dS product + split 16,
-// operand shifts 3, the rest addressing and the dQ output path; round 4: 12.5 / ~36; round 3: 15 / ~52).
+//                                takes one 16 x 16 output tile over the keys of two (d 16) or four (d 32) waves
+// Per 16x16 (query, key) tile at d 16, round 5's two-barrier kernel: 8.5 MFMAs and ~33 vector instructions per lane in the ISA (exp2 4,
+// P split 6, dS product + split 16, operand shifts 3, the rest addressing and the dQ output path; round 4: 12.5 / ~36; round 3: 15 / ~52).
 // Error class (tests/test_gpu_backward.py, profiles/r05_attention_bwd_error_ratio.txt): rms against float64 <= the fp32-input
 // kernel's on every input family tried; the worst ELEMENT up to 2.3x (3x for one (sample, head) pair) -- where one score dominates
 // a row the pair's 2^-22 operand rounding is the whole error.
@@ -44,61 +48,40 @@ using namespace hdiff;
 
 namespace {
 
-#ifndef H2B_ABL
-#define H2B_ABL 0            // dev: timing ablations (bit mask), results are wrong with any bit set
-#endif
 constexpr int THREADS = 256;           // of the preparation kernels
-#ifndef H2B_WAVES
-#define H2B_WAVES 8
-#endif
-#ifndef H2B_WANT
-#define H2B_WANT 1024
-#endif
-#ifndef H2B_DMA
-#define H2B_DMA 1           // dev: the tile's piece rows global -> LDS by LDS-DMA (eight-wave form; 0: through registers; A/B)
-#endif
-#ifndef H2B_DQX
-#define H2B_DQX 3           // dev: bit 0 = dQ across the workgroup at d 16, bit 1 = at d 32 (A/B)
-#endif
 // Waves of a main-kernel workgroup, 32 keys each.  EIGHT: one workgroup per CU instead of two of four waves -- every query tile is
 // staged once per 256 keys instead of once per 128, and the workgroup's dQ partial tile (summed over its waves in LDS) goes to the
 // slab once per 256 keys: half the L2 float adds (timing ablation on the four-wave build: the adds were 13 % of the launch).
-constexpr int MW = H2B_WAVES;
+constexpr int MW = 8;
 constexpr int MTHREADS = 64 * MW;
 constexpr int KB = 32 * MW;            // keys per workgroup block
 constexpr int SROW = 72;               // bytes per key row of the dS image [key][32 queries] (64 + 8: conflict-free ds_write_b64)
 constexpr int SPART = 32 * SROW;       // 2304 per piece
 constexpr int SCRB = 2 * SPART;        // 4608 per wave (two pieces of dS)
 
-// Geometry by head width.  d 16: tiles of 64 queries (two subtiles of 32 = one contraction of the q-summed products), rows of
-// 32 bytes -- with ds_read_b128's real lane groups ({0-3, 12-15, 20-27}, ...) plain 32-byte rows are conflict-free for the row
-// reads, the transposed reads and the staging stores alike (48-byte rows: a third of all LDS cycles were bank conflicts,
-// SQ_LDS_BANK_CONFLICT / SQ_LDS_IDX_ACTIVE = 0.35).  d 32: tiles of 32 queries, rows of 64 bytes, two 16-row M tiles in the
-// products whose output rows are d.
-template <int D>
+// Geometry of the d_head 32 kernel: tiles of 32 queries, rows of 64 bytes, two 16-row M tiles in the products whose output rows are d.
 struct Geo {
-  static constexpr int TQ = (D == 16) ? 64 : 32;      // queries per staged tile
-  static constexpr int NSUB = TQ / 32;                // subtiles of 32 queries
+  static constexpr int D = 32;
+  static constexpr int TQ = 32;                       // queries per staged tile
+  static constexpr int NSUB = TQ / 32;                // subtiles of 32 queries: one (the sweep keeps its one-trip loop over them:
+                                                      // folded away, it leaves a differently ordered schedule)
   static constexpr int MT = D / 16;                   // 16-row M tiles of dV^T, dK^T, dQ^T
   static constexpr int GROW = 2 * D;                  // bytes per query row of a piece tensor in memory
-  static constexpr int RROW = GROW;                   // ... and in LDS: no padding (d 32: rows padded to 96 bytes, conflict-free for
+  static constexpr int RROW = GROW;                   // ... and in LDS: no padding (rows padded to 96 bytes, conflict-free for
                                                       // row and transposed reads alike, measured no faster: 16.39 vs 16.35 ms)
-  static constexpr int CPR = GROW / 16;               // 16-byte chunks per row
   static constexpr int RPART = TQ * RROW;
   // rows of (q0, q1 2^8); of Q 2^sq c_q (x0, x1: form (ii), unshifted); of dO scaled per query (o0, o1: form (ii)); of dO scaled per head likewise
   static constexpr int QA_OFF = 0, QE_OFF = 2 * RPART, OA_OFF = 4 * RPART, OH_OFF = 6 * RPART;
   static constexpr int SL_OFF = 8 * RPART, SD_OFF = SL_OFF + TQ * 4, SC_OFF = SD_OFF + TQ * 4, BUFB = SC_OFF + TQ * 4;
-  static constexpr int DQS = TQ + 4;                  // row stride (floats) of a wave's dQ partial tile [D][DQS], aliased on its scratch
+  static constexpr int DQS = TQ + 4;                  // row stride (floats) of a dQ partial tile [D][DQS]
   static_assert(TQ * GROW == 2048, "staging geometry: 128 chunks per piece");
-  static_assert(D * DQS * 4 <= SCRB, "dQ partial tile must fit in the wave's scratch");
-  // dQ across the workgroup (eight waves): every wave's dS images of the tile stay in LDS until the tile's barrier, then wave w contracts
-  // ONE 16 x 16 output tile (w & 3: d 16 -- 16-query group of the 64; d 32 -- (row half, 16-query group)) over the 128 keys of four waves
-  // (half w >> 2) -- two partial tiles to sum instead of eight (timing ablations: the eight-way sum was ~40 of a tile's ~340 instructions
-  // per thread).  d 16: -6 %; d 32: -2.6 % (the four waves' K^T operands cost it six spilled registers outside the tile loop).
-  static constexpr bool DQX = (MW == 8) && (D == 16 ? (H2B_DQX & 1) != 0 : (H2B_DQX & 2) != 0);
-  static constexpr int IMG_BYTES = MW * (DQX ? NSUB : 1) * SCRB;
-  static constexpr int PART_BYTES = D * DQS * 4;                    // one partial tile [D][DQS] (DQX: two of them behind the images)
-  static constexpr int LDS_BYTES = 2 * BUFB + IMG_BYTES + (DQX ? 2 * PART_BYTES : 0);      // dynamic (d 16: 119 KB, d 32: 70 KB)
+  // dQ across the workgroup: every wave's dS image of the tile stays in LDS until the tile's barrier, then wave w contracts ONE 16 x 16
+  // output tile (w & 3: row half, 16-query group) over the 128 keys of four waves (half w >> 2) -- two partial tiles to sum instead of
+  // eight (timing ablations: the eight-way sum was ~40 of a tile's ~340 instructions per thread).  -2.6 % (the four waves' K^T operands
+  // cost it six spilled registers outside the tile loop).
+  static constexpr int IMG_BYTES = MW * SCRB;
+  static constexpr int PART_BYTES = D * DQS * 4;                    // one partial tile [D][DQS] (two of them behind the images)
+  static constexpr int LDS_BYTES = 2 * BUFB + IMG_BYTES + 2 * PART_BYTES;      // dynamic (70 KB)
   static_assert(LDS_BYTES <= 160 * 1024, "LDS");
 };
 
@@ -118,10 +101,7 @@ __device__ __forceinline__ u32x2 lds_read_tr16(const unsigned char* p) {
 // Workgroup barrier that orders LDS traffic only.  __syncthreads() also waits for the wave's outstanding GLOBAL stores
 // (release fence: s_waitcnt vmcnt(0)); with one slab store per tile in flight that wait exposed the store's latency at
 // every barrier -- 23 ms of a 158 ms launch (timing ablation).  Nothing here hands global data to another wave.
-__device__ __forceinline__ void lds_barrier() {
-  if (H2B_ABL & 256) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  else asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-}
+__device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
 typedef __attribute__((address_space(3))) unsigned char lds_byte;
 // One 1 KiB run global -> LDS without staging registers (global_load_lds_dwordx4: lane i's 16 bytes at src + voff land at lds_dst + 16 i).
@@ -354,18 +334,16 @@ struct BwdH2Args {
 
 template <int D>
 __global__ __launch_bounds__(MTHREADS) void mha_bwd_h2_kernel(const BwdH2Args a) {
-  using G = Geo<D>;
-  constexpr int TQ = G::TQ, NSUB = G::NSUB, MT = G::MT, RROW = G::RROW, GROW = G::GROW, CPR = G::CPR, RPART = G::RPART, BUFB = G::BUFB, DQS = G::DQS;
-  constexpr bool DQX = G::DQX;
+  static_assert(D == Geo::D, "d_head 16 runs on mha_bwd_h2p_kernel");
+  using G = Geo;
+  constexpr int TQ = G::TQ, NSUB = G::NSUB, MT = G::MT, RROW = G::RROW, GROW = G::GROW, RPART = G::RPART, BUFB = G::BUFB, DQS = G::DQS;
   constexpr int QA_OFF = G::QA_OFF, QE_OFF = G::QE_OFF, OA_OFF = G::OA_OFF, OH_OFF = G::OH_OFF, SL_OFF = G::SL_OFF, SD_OFF = G::SD_OFF, SC_OFF = G::SC_OFF;
-  // d-contracted products (S, dP'), four terms x0 y0, (x1 2^8)(y0 2^-8), (x0 2^-8)(y1 2^8), x1 y1:
-  //   d 16: two terms share an MFMA's 32 slots -- row operand A0 = (x0 | x1 2^8) as staged, A1 = A0 2^-8; stationary B0 = (y0 | y0 2^-8),
-  //         B1 = (y1 2^8 | y1): 2 MFMAs;   d 32: one term per MFMA and the 2^-22 term x1 y1 dropped (the d_head 32 forward does the same:
-  //         its error against float64 does not move) -- A = x0, x1 2^8, x0 2^-8; B = y0, y0 2^-8, y1 2^8: 3 MFMAs
-  constexpr int NA = (D == 16) ? 1 : 2;        // row operands READ per 16 rows
-  constexpr int NT = (D == 16) ? 2 : 3;        // MFMAs of one d-contracted 16x16 tile = stationary operand sets per 16 keys; operands NA .. NT - 1 are
-                                               // the first NT - NA read ones times 2^-8
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];      // 2 * BUFB + MW * SCRB
+  // d-contracted products (S, dP'), four terms x0 y0, (x1 2^8)(y0 2^-8), (x0 2^-8)(y1 2^8), x1 y1: one term per MFMA and the 2^-22 term x1 y1
+  // dropped (the d_head 32 forward does the same: its error against float64 does not move) -- A = x0, x1 2^8, x0 2^-8; B = y0, y0 2^-8, y1 2^8
+  constexpr int NA = 2;        // row operands READ per 16 rows
+  constexpr int NT = 3;        // MFMAs of one d-contracted 16x16 tile = stationary operand sets per 16 keys; operands NA .. NT - 1 are
+                               // the first NT - NA read ones times 2^-8
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];      // Geo::LDS_BYTES
 
   const int C = a.C, L = a.L;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -393,39 +371,17 @@ __global__ __launch_bounds__(MTHREADS) void mha_bwd_h2_kernel(const BwdH2Args a)
   const float dsdn = __builtin_ldexpf(one, -DS_DOWN<D>);        // dS' = P' (dP' - delta') 2^-DS_DOWN
   const float up8 = __builtin_ldexpf(one, PAIR_SHIFT);
 
-  // contraction slots of this lane in the d-contracted products.  d 16: 8 consecutive d of one of the MFMA's two terms;
-  // d 32: 8 consecutive d of the one term
-  const int doff = (D == 16) ? 8 * (g & 1) : 8 * g;
-  const bool hi = (D == 16) && (g >> 1);
+  // contraction slots of this lane in the d-contracted products: 8 consecutive d of the one term
+  const int doff = 8 * g;
 
-  // ---- staging of one query tile: 1024 chunks of 16 bytes (two row pieces each of Q, of q c_q, of dO per query and of dO per head), two per thread;
-  // 14 - lse2, -delta' and c_q of the tile's queries by the first TQ threads
-  // the 1024 chunks: blocks {Q, q c_q, dO per query, dO per head} x 2 pieces x 128 chunks; thread tid takes chunk tid + MTHREADS i
-  // (BDMA) the eight 2 KiB piece regions of a tile are contiguous in the workspace and in LDS (no row padding): wave w copies region w as two
-  // 1 KiB LDS-DMA runs; only the three per-query vectors go through registers
-  constexpr bool BDMA = DQX && (H2B_DMA != 0);
-  static_assert(!BDMA || (RROW == GROW && RPART == 2048 && MW == 8), "LDS-DMA geometry");
-  constexpr int NST = BDMA ? 0 : 1024 / MTHREADS;
-  static_assert(MTHREADS == 256 || MTHREADS == 512, "staging geometry");
-  static_assert(S_O - S_Q == S_OH - S_QE && G::OA_OFF - G::QA_OFF == G::OH_OFF - G::QE_OFF, "chunk i + 1 of a thread = chunk i moved by a fixed amount");
-  unsigned goff0;
-  int lds_off0;
-  {
-    const int blk = tid >> 8, cv = tid & 255;             // (512 threads) block 0 / 1 for chunk 0, 2 / 3 for chunk 1; (256) block i for chunk i
-    const int p = cv >> 7, rem = cv & 127;
-    const int row = rem / CPR, ch = rem % CPR;
-    goff0 = (unsigned)(((blk ? S_QE : S_Q) + p) * piece_n * 2) + row * GROW + ch * 16;
-    lds_off0 = (blk ? QE_OFF : QA_OFF) + p * RPART + row * RROW + ch * 16;
-  }
-  // chunk i: (512 threads) + i (S_O - S_Q) slots / + i (OA_OFF - QA_OFF); (256 threads) slots S_Q, S_QE, S_O, S_OH in turn
-  auto gslot = [&](int i) -> size_t { return (size_t)(MTHREADS == 512 ? i * (S_O - S_Q) : (i == 0 ? 0 : i == 1 ? S_QE - S_Q : i == 2 ? S_O - S_Q : S_OH - S_Q)) * (piece_n * 2); };
-  auto lslot = [&](int i) { return MTHREADS == 512 ? i * (OA_OFF - QA_OFF) : (i == 0 ? 0 : i == 1 ? QE_OFF : i == 2 ? OA_OFF : OH_OFF); };
+  // ---- staging of one query tile: the eight 2 KiB piece regions (two pieces each of Q, of q c_q, of dO per query and of dO per head) are
+  // contiguous in the workspace and in LDS (no row padding): wave w copies region w as two 1 KiB LDS-DMA runs; only the three per-query
+  // vectors (14 - lse2, -delta' and c_q of the tile's queries) go through registers, by the first TQ threads
+  static_assert(RROW == GROW && RPART == 2048, "LDS-DMA geometry");
   const unsigned char* wsb = reinterpret_cast<const unsigned char*>(wsh);
-  u32x4 stage[NST ? NST : 1];
   float stage_l = 0.f, stage_d = 0.f, stage_c = 1.f;
   const unsigned lds0 = (unsigned)(size_t)(lds_byte*)smem;
   auto dma_tile = [&](int t, int buf) {
-    if (!BDMA) return;
     const int w_ = __builtin_amdgcn_readfirstlane(wave);                 // region w: slots S_Q, S_Q + 1, S_QE, S_QE + 1, S_O, S_O + 1, S_OH, S_OH + 1
     const int slot = (w_ < 4) ? w_ : w_ + (S_O - 4);
     const unsigned char* src = wsb + (size_t)slot * (piece_n * 2) + (size_t)t * (TQ * GROW);
@@ -434,14 +390,10 @@ __global__ __launch_bounds__(MTHREADS) void mha_bwd_h2_kernel(const BwdH2Args a)
     dma_1k(src + 1024, lane * 16, dst + 1024);
   };
   auto stage_load = [&](int t) {
-#pragma unroll
-    for (int i = 0; i < NST; ++i) stage[i] = *reinterpret_cast<const u32x4*>(wsb + gslot(i) + goff0 + (size_t)t * (TQ * GROW));
     if (tid < TQ) { stage_l = lbase[t * TQ + tid]; stage_d = dbase[t * TQ + tid]; stage_c = cbase[t * TQ + tid]; }      // consumed when stored
   };
   auto stage_store = [&](int buf) {
     unsigned char* tb = smem + buf * BUFB;
-#pragma unroll
-    for (int i = 0; i < NST; ++i) *reinterpret_cast<u32x4*>(tb + lslot(i) + lds_off0) = stage[i];
     if (tid < TQ) {
       *reinterpret_cast<float*>(tb + SL_OFF + tid * 4) = (float)P_UP - stage_l;
       *reinterpret_cast<float*>(tb + SD_OFF + tid * 4) = ((-stage_d * dscale_o) * dscale_v) / stage_c;      // delta'_q = delta_q 2^(so + t_q + sv): c_q is a power of two
@@ -450,15 +402,14 @@ __global__ __launch_bounds__(MTHREADS) void mha_bwd_h2_kernel(const BwdH2Args a)
   };
 
   // operand addresses inside a tile buffer
-  int a1addr[NA];       // row reads (Q and dO alike, + QA_OFF / OA_OFF): (d 16) the piece of this lane half / (d 32) piece j; row i16, 16 bytes at doff
+  int a1addr[NA];       // row reads (Q and dO alike, + QA_OFF / OA_OFF): piece j, row i16, 16 bytes at doff
 #pragma unroll
-  for (int j = 0; j < NA; ++j) a1addr[j] = ((D == 16) ? (hi ? 1 : 0) : j) * RPART + i16 * RROW + doff * 2;
+  for (int j = 0; j < NA; ++j) a1addr[j] = j * RPART + i16 * RROW + doff * 2;
   // transposed reads of the same tiles (A operands of the products that sum over queries): lane 4q + p of a 16-lane group
   // addresses row 4g + q (then 16 + 4g + q), columns d = 16 mt + 4p .. + 3
   const int a3addr = (4 * g + (i16 >> 2)) * RROW + 8 * (i16 & 3);
-  unsigned char* scr = smem + 2 * BUFB + wave * (DQX ? NSUB : 1) * SCRB;      // this wave's dS image(s): [subtile (DQX)][piece][key 0..31][SROW]
-  float* sdq = reinterpret_cast<float*>(scr);                                  // (per-wave form) the wave's partial tile, aliased on its image
-  unsigned char* const xpart = smem + 2 * BUFB + G::IMG_BYTES;                 // (DQX) partial tiles [key half][D][DQS]
+  unsigned char* scr = smem + 2 * BUFB + wave * SCRB;                          // this wave's dS image
+  unsigned char* const xpart = smem + 2 * BUFB + G::IMG_BYTES;                 // partial tiles [key half][D][DQS]
   // the dS image of this wave: [piece][key 0..31][SROW bytes of 32 queries]
   const int swaddr = i16 * SROW + 8 * g;                              // + piece * SPART + kt * 16 * SROW + jq * 32
   const int sraddr = (8 * g + (i16 >> 2)) * SROW + 8 * (i16 & 3);     // + piece * SPART + jq * 32 (+ 4 * SROW: second half)
@@ -473,35 +424,27 @@ __global__ __launch_bounds__(MTHREADS) void mha_bwd_h2_kernel(const BwdH2Args a)
   for (int kb = kb_begin; kb < kb_end; ++kb) {
     const int key0 = kb * KB + wave * 32;
     // ---- stationary operands of the wave's 32 keys, straight from the workspace
-    u32x4 kB[2][NT], vB[2][2], kT[MT][2];
+    u32x4 kB[2][NT], vB[2][2];
 #pragma unroll
     for (int kt = 0; kt < 2; ++kt)
 #pragma unroll
       for (int j = 0; j < NT; ++j) {
-        const int p = (D == 16) ? 2 * j + (hi ? 1 : 0) : j;         // pieces (y0, y0 2^-8, y1 2^8, y1)
-        const size_t off = (size_t)p * piece_n + (size_t)(key0 + kt * 16 + i16) * D + doff;
+        const size_t off = (size_t)j * piece_n + (size_t)(key0 + kt * 16 + i16) * D + doff;      // pieces (y0, y0 2^-8, y1 2^8)
         kB[kt][j] = *reinterpret_cast<const u32x4*>(wsh + (size_t)S_K * piece_n + off);
       }
-    // V' pieces (v0, v1), form (ii): d 16 -- MFMA j = (o0 | o1)(v_j | v_j); d 32 -- o0 v0, o1 v0, o0 v1
+    // V' pieces (v0, v1), form (ii): o0 v0, o1 v0, o0 v1
 #pragma unroll
     for (int kt = 0; kt < 2; ++kt)
 #pragma unroll
       for (int p = 0; p < 2; ++p)
         vB[kt][p] = *reinterpret_cast<const u32x4*>(wsh + (size_t)(S_V + p) * piece_n + (size_t)(key0 + kt * 16 + i16) * D + doff);
+    // k^T of the four waves of this wave's key half: [source wave][piece], rows d = 16 (row half) + i16, 32 keys along the contraction
+    u32x4 kT4[4][2];
 #pragma unroll
-    for (int mt = 0; mt < MT; ++mt)
+    for (int sw = 0; sw < 4; ++sw)
 #pragma unroll
       for (int p = 0; p < 2; ++p)
-        if (!DQX) kT[mt][p] = *reinterpret_cast<const u32x4*>(wsh + (size_t)(S_KT + p) * piece_n + (size_t)(16 * mt + i16) * L + key0 + 8 * g);
-    // (DQX) k^T of the four waves of this wave's key half: [source wave][piece], rows d = i16, 32 keys along the contraction
-    u32x4 kT4[DQX ? 4 : 1][2];
-    if (DQX) {
-#pragma unroll
-      for (int sw = 0; sw < 4; ++sw)
-#pragma unroll
-        for (int p = 0; p < 2; ++p)
-          kT4[sw][p] = *reinterpret_cast<const u32x4*>(wsh + (size_t)(S_KT + p) * piece_n + (size_t)((D == 16 ? 0 : 16 * ((wave & 3) >> 1)) + i16) * L + kb * KB + (4 * (wave >> 2) + sw) * 32 + 8 * g);
-    }
+        kT4[sw][p] = *reinterpret_cast<const u32x4*>(wsh + (size_t)(S_KT + p) * piece_n + (size_t)(16 * ((wave & 3) >> 1) + i16) * L + kb * KB + (4 * (wave >> 2) + sw) * 32 + 8 * g);
     f32x4 dKa[2][MT], dVa[2][MT];
 #pragma unroll
     for (int kt = 0; kt < 2; ++kt)
@@ -515,9 +458,9 @@ __global__ __launch_bounds__(MTHREADS) void mha_bwd_h2_kernel(const BwdH2Args a)
     stage_load(0);
     dma_tile(0, 0);
     stage_store(0);
-    if (BDMA) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
-    if (!(H2B_ABL & 8)) stage_load(1);
+    stage_load(1);
 
     // dQ goes to the key range's slab (layout [tile][d][TQ queries]: 4 KB per tile, contiguous): a plain store during the
     // range's first key block, fire-and-forget L2 float adds afterwards.  Only THIS thread ever touches its four slab words,
@@ -527,11 +470,10 @@ __global__ __launch_bounds__(MTHREADS) void mha_bwd_h2_kernel(const BwdH2Args a)
     for (int t = 0; t < ntiles; ++t) {
       const int buf = t & 1;
       const unsigned char* tb = smem + buf * BUFB;
-      // (BDMA) the rows of tile t + 1 into the other buffer: its piece regions were last read before the previous tile's first barrier
-      if (!(H2B_ABL & 8)) dma_tile(t + 1 < ntiles ? t + 1 : t, buf ^ 1);
+      // the rows of tile t + 1 into the other buffer: its piece regions were last read before the previous tile's first barrier
+      dma_tile(t + 1 < ntiles ? t + 1 : t, buf ^ 1);
       float* pdst = part + (size_t)t * (D * TQ) + tid;
 
-      f32x4 dQt[NSUB][2][MT];
 #pragma unroll
       for (int sub = 0; sub < NSUB; ++sub) {
         const unsigned char* sb = tb + sub * 32 * RROW;
@@ -565,11 +507,9 @@ __global__ __launch_bounds__(MTHREADS) void mha_bwd_h2_kernel(const BwdH2Args a)
             oT[p] = u32x4{o0[0], o0[1], o1[0], o1[1]};
           }
         };
-        u32x4 qT0[2], oT0[2];
-        if (MT == 1) load_transposed(0, qT0, oT0);       // d 16: read once per subtile, used by both key tiles
 
-        // term order of the four-term products: d 16 -- MFMA j = A_j B_j; d 32 -- (x0, y0), (x1 2^8, y0 2^-8), (x0 2^-8, y1 2^8), (x1, y1):
-        // row operand index {0, 1, 2, 3} = x0, x1 2^8, x0 2^-8, x1; stationary piece index {0, 1, 2, 3} = y0, y0 2^-8, y1 2^8, y1
+        // term order of the four-term products: (x0, y0), (x1 2^8, y0 2^-8), (x0 2^-8, y1 2^8), (x1, y1): row operand index
+        // {0, 1, 2, 3} = x0, x1 2^8, x0 2^-8, x1; stationary piece index {0, 1, 2, 3} = y0, y0 2^-8, y1 2^8, y1
 #pragma unroll
         for (int kt = 0; kt < 2; ++kt) {
           f32x4 S[2], dP[2];
@@ -580,10 +520,10 @@ __global__ __launch_bounds__(MTHREADS) void mha_bwd_h2_kernel(const BwdH2Args a)
             for (int j = 0; j < NT; ++j) acc = mfma_f16(qA[jq][j], kB[kt][j], acc);          // large term first
             S[jq] = acc;
             acc = negd[jq];
-            // (mutation test, bit 16: the cross product o0 v1 dropped -- with its MFMA partner o1 v1 at d 16)
+            // (mutation test, bit 16: the cross product o0 v1 dropped)
 #pragma unroll
             for (int j = 0; j < NT; ++j)
-              if (!((HDIFF_MUTANT & 16) && j == (D == 16 ? 1 : 2))) acc = mfma_f16(oA[jq][j], vB[kt][D == 16 ? j : j >> 1], acc);
+              if (!((HDIFF_MUTANT & 16) && j == 2)) acc = mfma_f16(oA[jq][j], vB[kt][j >> 1], acc);
             dP[jq] = acc;
           }
           u32x4 Pp[2], Sp[2];
@@ -595,37 +535,23 @@ __global__ __launch_bounds__(MTHREADS) void mha_bwd_h2_kernel(const BwdH2Args a)
               p[i] = __builtin_amdgcn_exp2f(S[jq][i]);
               ds[i] = p[i] * dP[jq][i];
             }
-            if (H2B_ABL & 16) {
-#pragma unroll
-              for (int h = 0; h < 2; ++h)
-#pragma unroll
-                for (int pc = 0; pc < 2; ++pc) {
-                  Pp[pc][2 * jq + h] = __builtin_bit_cast(unsigned, S[jq][2 * h]) + pc;
-                  Sp[pc][2 * jq + h] = __builtin_bit_cast(unsigned, dP[jq][2 * h + 1]) + pc;
-                }
-            } else {
-              unsigned sa0, sa1, sb0, sb1;
-              split2_scaled(ds[0], ds[1], ds[2], ds[3], dsdn, up8, sa0, sa1, sb0, sb1);
-              if (HDIFF_MUTANT & 64) { sa1 &= 0xffe0ffe0u; sb1 &= 0xffe0ffe0u; }      // (mutation test, bit 64: the low five bits of the second piece of dS': 2^-17 of dS)
-              Sp[0][2 * jq] = sa0; Sp[1][2 * jq] = sa1; Sp[0][2 * jq + 1] = sb0; Sp[1][2 * jq + 1] = sb1;
-              unsigned pa0, pa1, pb0, pb1;
-              split2(p[0], p[1], one, pa0, pa1);
-              split2(p[2], p[3], one, pb0, pb1);
-              Pp[0][2 * jq] = pa0; Pp[1][2 * jq] = pa1; Pp[0][2 * jq + 1] = pb0; Pp[1][2 * jq + 1] = pb1;
-            }
+            unsigned sa0, sa1, sb0, sb1;
+            split2_scaled(ds[0], ds[1], ds[2], ds[3], dsdn, up8, sa0, sa1, sb0, sb1);
+            if (HDIFF_MUTANT & 64) { sa1 &= 0xffe0ffe0u; sb1 &= 0xffe0ffe0u; }      // (mutation test, bit 64: the low five bits of the second piece of dS': 2^-17 of dS)
+            Sp[0][2 * jq] = sa0; Sp[1][2 * jq] = sa1; Sp[0][2 * jq + 1] = sb0; Sp[1][2 * jq + 1] = sb1;
+            unsigned pa0, pa1, pb0, pb1;
+            split2(p[0], p[1], one, pa0, pa1);
+            split2(p[2], p[3], one, pb0, pb1);
+            Pp[0][2 * jq] = pa0; Pp[1][2 * jq] = pa1; Pp[0][2 * jq + 1] = pb0; Pp[1][2 * jq + 1] = pb1;
             // the packed dS pieces of (key i16 of tile kt, queries 16 jq + 4g ..+3) into the wave's [key][query] image
-            if (!(H2B_ABL & 4)) {
 #pragma unroll
-              for (int pc = 0; pc < 2; ++pc)
-                *reinterpret_cast<u32x2*>(scr + (DQX ? sub * SCRB : 0) + pc * SPART + kt * 16 * SROW + jq * 32 + swaddr) = u32x2{Sp[pc][2 * jq], Sp[pc][2 * jq + 1]};
-            }
+            for (int pc = 0; pc < 2; ++pc)
+              *reinterpret_cast<u32x2*>(scr + sub * SCRB + pc * SPART + kt * 16 * SROW + jq * 32 + swaddr) = u32x2{Sp[pc][2 * jq], Sp[pc][2 * jq + 1]};
           }
 #pragma unroll
           for (int mt = 0; mt < MT; ++mt) {
-            u32x4 qTm[2], oTm[2];
-            if (MT > 1) load_transposed(mt, qTm, oTm);       // d 32: one M tile's operands at a time (registers)
-            const u32x4 (&qT)[2] = (MT == 1 ? qT0 : qTm);
-            const u32x4 (&oT)[2] = (MT == 1 ? oT0 : oTm);
+            u32x4 qT[2], oT[2];
+            load_transposed(mt, qT, oT);       // one M tile's operands at a time (registers)
             // small terms first; (mutation test, bit 32: the product o1 p0 of dV^T dropped)
             if (!(HDIFF_MUTANT & 32)) dVa[kt][mt] = mfma_f16(oT[1], Pp[0], dVa[kt][mt]);        // o1 p0
             dVa[kt][mt] = mfma_f16(oT[0], Pp[1], dVa[kt][mt]);        // o0 p1
@@ -635,125 +561,59 @@ __global__ __launch_bounds__(MTHREADS) void mha_bwd_h2_kernel(const BwdH2Args a)
             dKa[kt][mt] = mfma_f16(qT[0], Sp[0], dKa[kt][mt]);        // q0 s0
           }
         }
-
-        // ---- (per-wave form) dQ^T of the subtile over this wave's 32 keys: the dS image read back transposed, keys along the contraction
+        // two empty fences, where the retired per-wave dQ path sat between them: the scheduler keeps the tile's last MFMAs ahead of the
+        // barrier with them (one fence or none moves the barrier up)
         asm volatile("" ::: "memory");
-#pragma unroll
-        for (int jq = 0; jq < (DQX ? 0 : 2); ++jq) {
-          u32x4 sT[2];
-#pragma unroll
-          for (int p = 0; p < 2; ++p) {
-            const unsigned char* src = scr + p * SPART + jq * 32 + sraddr;
-            const u32x2 lo = lds_read_tr16(src), hi2 = lds_read_tr16(src + 4 * SROW);
-            sT[p] = u32x4{lo[0], lo[1], hi2[0], hi2[1]};
-          }
-#pragma unroll
-          for (int mt = 0; mt < MT; ++mt) {
-            f32x4 acca = f32x4{0.f, 0.f, 0.f, 0.f}, accb = f32x4{0.f, 0.f, 0.f, 0.f};
-            acca = mfma_f16(kT[mt][0], sT[0], acca);        // k0 s0
-            accb = mfma_f16(kT[mt][1], sT[0], accb);        // (k1 2^8) s0
-            accb = mfma_f16(kT[mt][0], sT[1], accb);        // k0 (s1 2^8)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) dQt[sub][jq][mt][r] = __builtin_fmaf(accb[r], dnb, acca[r]);
-          }
-        }
-        asm volatile("" ::: "memory");      // the next subtile's image stores stay behind these reads (same wave: in order)
+        asm volatile("" ::: "memory");
       }
 
-      if (DQX) {
-        // ---- dQ^T across the workgroup: every wave's images of this tile are complete behind the barrier
-        lds_barrier();
-        // output tile nt of four: d 16 -- queries 16 nt .. + 15 (subtile nt >> 1, 16-query group nt & 1); d 32 -- 16-query group nt & 1, rows d = 16 (nt >> 1) ..;
-        // keys of waves 4 kh .. 4 kh + 3
-        const int nt = wave & 3, kh = wave >> 2;
-        const int osub = (D == 16) ? (nt >> 1) : 0, ojq = nt & 1, omt = (D == 16) ? 0 : (nt >> 1);
-        f32x4 acca = f32x4{0.f, 0.f, 0.f, 0.f}, accb = f32x4{0.f, 0.f, 0.f, 0.f};
+      // ---- dQ^T across the workgroup: every wave's images of this tile are complete behind the barrier
+      lds_barrier();
+      // output tile nt of four: 16-query group nt & 1, rows d = 16 (nt >> 1) ..; keys of waves 4 kh .. 4 kh + 3
+      const int nt = wave & 3, kh = wave >> 2;
+      const int ojq = nt & 1, omt = nt >> 1;
+      f32x4 acca = f32x4{0.f, 0.f, 0.f, 0.f}, accb = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-        for (int sw = 0; sw < 4; ++sw) {
-          const unsigned char* img = smem + 2 * BUFB + ((4 * kh + sw) * NSUB + osub) * SCRB + ojq * 32 + sraddr;
-          u32x4 sT[2];
+      for (int sw = 0; sw < 4; ++sw) {
+        const unsigned char* img = smem + 2 * BUFB + (4 * kh + sw) * SCRB + ojq * 32 + sraddr;
+        u32x4 sT[2];
 #pragma unroll
-          for (int p = 0; p < 2; ++p) {
-            const u32x2 lo = lds_read_tr16(img + p * SPART), hi2 = lds_read_tr16(img + p * SPART + 4 * SROW);
-            sT[p] = u32x4{lo[0], lo[1], hi2[0], hi2[1]};
-          }
-          acca = mfma_f16(kT4[sw][0], sT[0], acca);        // k0 s0
-          accb = mfma_f16(kT4[sw][1], sT[0], accb);        // (k1 2^8) s0
-          accb = mfma_f16(kT4[sw][0], sT[1], accb);        // k0 (s1 2^8)
+        for (int p = 0; p < 2; ++p) {
+          const u32x2 lo = lds_read_tr16(img + p * SPART), hi2 = lds_read_tr16(img + p * SPART + 4 * SROW);
+          sT[p] = u32x4{lo[0], lo[1], hi2[0], hi2[1]};
         }
-        if (!(H2B_ABL & 2)) {
-          float* pw = reinterpret_cast<float*>(xpart + kh * G::PART_BYTES);
-#pragma unroll
-          for (int r = 0; r < 4; ++r) pw[(16 * omt + 4 * g + r) * DQS + 32 * osub + 16 * ojq + i16] = __builtin_fmaf(accb[r], dnb, acca[r]);
-        } else if (acca[0] + accb[1] == 12345.f) *pdst = 1.f;
-        // tile t + 1 into the other buffer BEFORE the barrier: the next tile starts without another one
-        stage_store(buf ^ 1);
-        if (BDMA) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // this wave's runs of tile t + 1 have landed
-        lds_barrier();
-        constexpr int NR = 1024 / MTHREADS;
-        float sum[NR];
-#pragma unroll
-        for (int r = 0; r < NR; ++r) {
-          const int e = tid + MTHREADS * r;
-          const float* s0 = reinterpret_cast<const float*>(xpart) + (e / TQ) * DQS + (e % TQ);
-          const float v = s0[0] + s0[G::PART_BYTES / 4];
-          sum[r] = __builtin_ldexpf(v * a.inv_sqrt_d, -(P_UP - DS_DOWN<D> + so + sv + bal)) * *reinterpret_cast<const float*>(tb + SC_OFF + (e % TQ) * 4);
-        }
-        if (!(H2B_ABL & 8)) stage_load(t + 2 < ntiles ? t + 2 : t);
-        if (!(H2B_ABL & 67) || t == 0) {
-          if (first_kb || (H2B_ABL & 32)) {
-#pragma unroll
-            for (int r = 0; r < NR; ++r) pdst[MTHREADS * r] = sum[r];
-          } else {
-#pragma unroll
-            for (int r = 0; r < NR; ++r) unsafeAtomicAdd(pdst + MTHREADS * r, sum[r]);
-          }
-        }
-        continue;      // no closing barrier: the next tile's first LDS write that anyone else reads is behind ITS barrier
+        acca = mfma_f16(kT4[sw][0], sT[0], acca);        // k0 s0
+        accb = mfma_f16(kT4[sw][1], sT[0], accb);        // (k1 2^8) s0
+        accb = mfma_f16(kT4[sw][0], sT[1], accb);        // k0 (s1 2^8)
       }
-      // (per-wave form) the wave's partial tile [d][query] over its own scratch (its reads above are done: same wave, in order)
-      if (H2B_ABL & 2) {
-        if (dQt[0][0][0][0] + dQt[0][1][0][1] == 12345.f) *pdst = 1.f;
-        stage_store(buf ^ 1);
-        if (!(H2B_ABL & 8)) stage_load(t + 2 < ntiles ? t + 2 : t);
+      float* pw = reinterpret_cast<float*>(xpart + kh * G::PART_BYTES);
+#pragma unroll
+      for (int r = 0; r < 4; ++r) pw[(16 * omt + 4 * g + r) * DQS + 16 * ojq + i16] = __builtin_fmaf(accb[r], dnb, acca[r]);
+      // tile t + 1 into the other buffer BEFORE the barrier: the next tile starts without another one
+      stage_store(buf ^ 1);
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // this wave's runs of tile t + 1 have landed
+      lds_barrier();
+      // thread -> floats tid + MTHREADS r of the [D][TQ] block: row d = e / TQ, query e % TQ;
+      // Y = dQ_q sqrt(d) 2^(bal + so + t_q + sv + 14 - DS_DOWN)
+      constexpr int NR = 1024 / MTHREADS;
+      static_assert(D * TQ == 1024, "slab tile");
+      float sum[NR];
+#pragma unroll
+      for (int r = 0; r < NR; ++r) {
+        const int e = tid + MTHREADS * r;
+        const float* s0 = reinterpret_cast<const float*>(xpart) + (e / TQ) * DQS + (e % TQ);
+        const float v = s0[0] + s0[G::PART_BYTES / 4];
+        sum[r] = __builtin_ldexpf(v * a.inv_sqrt_d, -(P_UP - DS_DOWN<D> + so + sv + bal)) * *reinterpret_cast<const float*>(tb + SC_OFF + (e % TQ) * 4);
+      }
+      stage_load(t + 2 < ntiles ? t + 2 : t);
+      if (first_kb) {
+#pragma unroll
+        for (int r = 0; r < NR; ++r) pdst[MTHREADS * r] = sum[r];
       } else {
 #pragma unroll
-        for (int sub = 0; sub < NSUB; ++sub)
-#pragma unroll
-          for (int jq = 0; jq < 2; ++jq)
-#pragma unroll
-            for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-              for (int r = 0; r < 4; ++r) sdq[(16 * mt + 4 * g + r) * DQS + 32 * sub + 16 * jq + i16] = dQt[sub][jq][mt][r];
-        lds_barrier();
-        // thread -> floats tid + MTHREADS r of the [D][TQ] block: row d = e / TQ, query e % TQ
-        constexpr int NR = 1024 / MTHREADS;
-        static_assert(D * TQ == 1024, "slab tile");
-        float sum[NR];
-#pragma unroll
-        for (int r = 0; r < NR; ++r) {
-          const int e = tid + MTHREADS * r;
-          const float* s0 = reinterpret_cast<const float*>(smem + 2 * BUFB) + (e / TQ) * DQS + (e % TQ);
-          float v = s0[0];
-#pragma unroll
-          for (int w = 1; w < MW; ++w) v += s0[w * (SCRB / 4)];
-          // Y = dQ_q sqrt(d) 2^(bal + so + t_q + sv + 14 - DS_DOWN)
-          sum[r] = __builtin_ldexpf(v * a.inv_sqrt_d, -(P_UP - DS_DOWN<D> + so + sv + bal)) * *reinterpret_cast<const float*>(tb + SC_OFF + (e % TQ) * 4);
-        }
-        // tile t + 1 into LDS, then the loads of tile t + 2
-        stage_store(buf ^ 1);
-        if (!(H2B_ABL & 8)) stage_load(t + 2 < ntiles ? t + 2 : t);
-        if (!(H2B_ABL & 65) || t == 0) {
-          if (first_kb || (H2B_ABL & 32)) {
-#pragma unroll
-            for (int r = 0; r < NR; ++r) pdst[MTHREADS * r] = sum[r];
-          } else {
-#pragma unroll
-            for (int r = 0; r < NR; ++r) unsafeAtomicAdd(pdst + MTHREADS * r, sum[r]);
-          }
-        }
+        for (int r = 0; r < NR; ++r) unsafeAtomicAdd(pdst + MTHREADS * r, sum[r]);
       }
-      lds_barrier();
+      // no closing barrier: the next tile's first LDS write that anyone else reads is behind ITS barrier
     }
 
     // ---- dK, dV of this key block (complete: the sweep covered every query).  X = dK sqrt(d) 2^(sq + so + sv + 14 - DS_DOWN) (the rows of Q 2^sq c_q),
@@ -778,7 +638,8 @@ __global__ __launch_bounds__(MTHREADS) void mha_bwd_h2_kernel(const BwdH2Args a)
 template <int D>
 __global__ void mha_dq_reduce_h2_kernel(const float* __restrict__ part, float* __restrict__ dqkv, int nsplit, int C, int L,
                                         size_t split_stride) {
-  constexpr int TQ = Geo<D>::TQ, Q4 = TQ / 4;
+  static_assert(D == Geo::D, "d_head 16 reduces with mha_dq_reduce_h2p_kernel");
+  constexpr int TQ = Geo::TQ, Q4 = TQ / 4;
   const int b = blockIdx.y;
   const size_t per_sample = (size_t)C * L;
   const float* src = part + (size_t)b * per_sample;
@@ -798,9 +659,9 @@ __global__ void mha_dq_reduce_h2_kernel(const float* __restrict__ part, float* _
 
 
 // ---------------------------------------------------------------------------------------------------------------------
-// Round 6: the d_head 16 kernel as a SOFTWARE PIPELINE over 32-query tiles, ONE workgroup barrier per tile.
-// Why (profiles/r05_pmc_summary.txt): the kernel above runs at ~52 % of its own issue floor, MFMA / vector co-execution
-// 0.25 -- per 64-query tile all eight waves meet at two barriers, and between them sits a phase that is nothing but latency: the
+// The d_head 16 kernel (round 6): a SOFTWARE PIPELINE over 32-query tiles, ONE workgroup barrier per tile.
+// Why (profiles/r05_pmc_summary.txt): round 5 ran d_head 16 on the two-barrier form of the kernel above, with 64-query
+// tiles, at ~52 % of its own issue floor, MFMA / vector co-execution 0.25 -- per tile all eight waves met at two barriers, and between them sits a phase that is nothing but latency: the
 // transposed reads of the dS images, a chain of dependent dQ MFMAs, the partial tile through LDS, a second barrier, the cross-wave sum and
 // the slab adds, with the matrix AND the vector pipe idle on every SIMD at once (the dQ output path: 23 % of the launch).
 // Here the three pieces of a tile's work run in three consecutive iterations, each between the same two barriers as the MAIN phase of a
@@ -814,26 +675,13 @@ __global__ void mha_dq_reduce_h2_kernel(const float* __restrict__ part, float* _
 //   barrier
 // Nothing per query is needed after the main phase: the two chain starts (14 - lse2, -delta') come per tile from the split pass and the factor
 // c_q = 2^-t_q is given back by the slab reduce kernel (a power of two: exact).  Same operand formats, same products, same summation order
-// inside a tile as the kernel above; dQ's key-quarter partials are summed in a fixed order: bitwise reproducible.
+// inside a tile as round 5's kernel; dQ's key-quarter partials are summed in a fixed order: bitwise reproducible.
+// Rows of 32 bytes: with ds_read_b128's real lane groups ({0-3, 12-15, 20-27}, ...) plain 32-byte rows are conflict-free for the row
+// reads, the transposed reads and the staging stores alike (48-byte rows: a third of all LDS cycles were bank conflicts,
+// SQ_LDS_BANK_CONFLICT / SQ_LDS_IDX_ACTIVE = 0.35).
 // What it bought (profiles/r06_pmc_summary.txt, r06_attention_bwd_pipeline.txt): 7.5 % fewer cycles, co-execution 0.25 -> 0.41 -- and 1-2 % of
 // wall time, because the board is on its power limit and returns the cycles as clock: the kernel is bound by the energy of its instructions.
 // ---------------------------------------------------------------------------------------------------------------------
-#ifndef H2B_PIPE
-#define H2B_PIPE 1            // dev: 0 = d_head 16 on the two-barrier kernel above (A/B)
-#endif
-#ifndef H2P_OPT
-#define H2P_OPT 3             // switches of the pipelined kernel (A/B builds with -DH2P_OPT=<bits>): 1 static priority for waves 4-7 (the second-dispatched
-#endif                        // half loses every issue arbitration to its SIMD partner otherwise: -1.3 %), 2 no trailing s_nop in the dS split statements
-                              // (the slot program puts an MFMA behind each: the partial-write hazard is covered; 0.0 %)
-#ifndef H2P_T4
-#define H2P_T4 1              // dev: 0 = the fourth terms of the two d-contracted products (q1 k1 in S', o1 v1 in dP': 2^-22 of their product) multiplied by
-#endif                        // ZEROS -- the stationary operands' high-half lanes cleared once per key block: same MFMAs, idle multipliers (energy A/B)
-#ifndef H2P_KTREG
-#define H2P_KTREG 1           // 1 = the dq stage's k^T operands in 16 registers for the whole sweep (the steady loop has no spill with them; -1.3 %),
-#endif                        // 0 = four LDS reads per tile out of a copy in MFMA operand order (A/B)
-#ifndef H2P_ABL
-#define H2P_ABL 0             // dev: timing ablations of the pipelined kernel (results wrong by construction): 1 no exp / split chain, 2 no dq stage,
-#endif                        // 4 no sum stage, 8 no main-phase MFMAs, 16 no dS image stores, 32 no barrier, 64 no tile copies, 128 no operand LDS reads
 struct GeoP {
   static constexpr int D = 16, TQ = 32, RROW = 32, RPART = TQ * RROW;      // a tile's piece region: 32 rows of 32 bytes = one 1 KiB LDS-DMA run
   static constexpr int QA_OFF = 0, QE_OFF = 2 * RPART, OA_OFF = 4 * RPART, OH_OFF = 6 * RPART, SL_OFF = 8 * RPART, SD_OFF = SL_OFF + TQ * 4;
@@ -844,7 +692,6 @@ struct GeoP {
   static constexpr int NBUF = 3;                                            // tile buffers: tile t lives in buffer t % 3 (copied two iterations ahead)
   static constexpr int KTB = MW * 2 * 1024;                                 // k^T of every wave's 32 keys as MFMA A operands: [wave][piece][lane][16 bytes]
   static constexpr int IMG_OFF = NBUF * BUFB, XP_OFF = IMG_OFF + 2 * IMGB, KT_OFF = XP_OFF + 2 * XPB, LDS_BYTES = KT_OFF + KTB;      // 133 888
-  static_assert(MW == 8 || !H2B_PIPE, "the pipelined kernel is written for eight waves");
   static_assert(LDS_BYTES <= 160 * 1024, "LDS");
 };
 
@@ -858,15 +705,13 @@ __device__ __forceinline__ void dma_256(const unsigned char* src, unsigned voff,
 }
 
 // the three stages of split2_scaled as separate statements (same instructions, same order per value): the pipelined kernel places them in
-// different issue slots between its MFMAs
+// different issue slots between its MFMAs.  No trailing s_nop: the slot program puts an MFMA behind each statement, which covers the
+// partial-write hazard (measured: 0.0 %)
 __device__ __forceinline__ void ds_split_a(float a0, float a1, float b0, float b1, float c, unsigned& ha0, unsigned& hb0) {
   asm("v_fma_mixlo_f16 %0, %2, %6, 0\n\t"
       "v_fma_mixlo_f16 %1, %4, %6, 0\n\t"
       "v_fma_mixhi_f16 %0, %3, %6, 0\n\t"
       "v_fma_mixhi_f16 %1, %5, %6, 0"
-#if !(H2P_OPT & 2)
-      "\n\ts_nop 0"
-#endif
       : "=&v"(ha0), "=&v"(hb0)
       : "v"(a0), "v"(a1), "v"(b0), "v"(b1), "v"(c));
 }
@@ -884,9 +729,6 @@ __device__ __forceinline__ void ds_split_c(float r0, float r1, float r2, float r
       "v_fma_mixlo_f16 %1, %4, %6, 0\n\t"
       "v_fma_mixhi_f16 %0, %3, %6, 0\n\t"
       "v_fma_mixhi_f16 %1, %5, %6, 0"
-#if !(H2P_OPT & 2)
-      "\n\ts_nop 0"
-#endif
       : "=&v"(ha1), "=&v"(hb1)
       : "v"(r0), "v"(r1), "v"(r2), "v"(r3), "v"(up));
 }
@@ -952,7 +794,8 @@ __global__ __launch_bounds__(MTHREADS) void mha_bwd_h2p_kernel(const BwdH2Args a
   };
 #define SLOT() __builtin_amdgcn_sched_barrier(0)
 
-  if ((H2P_OPT & 1) && !copier) __builtin_amdgcn_s_setprio(1);
+  // waves 4-7 at a higher static priority: the second-dispatched half loses every issue arbitration to its SIMD partner otherwise (-1.3 %)
+  if (!copier) __builtin_amdgcn_s_setprio(1);
   for (int kb = kb_begin; kb < kb_end; ++kb) {
     const int key0 = kb * KB + wave * 32;
     u32x4 kB[2][2], vB[2][2];
@@ -963,10 +806,10 @@ __global__ __launch_bounds__(MTHREADS) void mha_bwd_h2p_kernel(const BwdH2Args a
         const size_t row = (size_t)(key0 + kt * 16 + i16) * D + doff;
         kB[kt][j] = *reinterpret_cast<const u32x4*>(wsh + (size_t)(S_K + 2 * j + (hi ? 1 : 0)) * piece_n + row);      // (k0 | k0 2^-8), (k1 2^8 | k1)
         vB[kt][j] = *reinterpret_cast<const u32x4*>(wsh + (size_t)(S_V + j) * piece_n + row);                          // (o0 | o1)(v_j | v_j)
-        if (!H2P_T4 && j == 1 && hi) { kB[kt][j] = u32x4{0u, 0u, 0u, 0u}; vB[kt][j] = u32x4{0u, 0u, 0u, 0u}; }
       }
     // k^T of this wave's 32 keys (rows d = i16, keys along the contraction) in MFMA operand order into LDS: the dq stage reads the two waves
-    // of its key quarter from there every tile (lane-contiguous 16-byte reads) instead of holding 16 registers for the whole sweep
+    // of its key quarter from there (lane-contiguous 16-byte reads) into 16 registers it holds for the whole sweep (the steady loop has no
+    // spill with them: -1.3 % against four LDS reads per tile)
     u32x4 kTown[2];
 #pragma unroll
     for (int p = 0; p < 2; ++p) kTown[p] = *reinterpret_cast<const u32x4*>(wsh + (size_t)(S_KT + p) * piece_n + (size_t)i16 * L + key0 + 8 * g);
@@ -987,7 +830,6 @@ __global__ __launch_bounds__(MTHREADS) void mha_bwd_h2p_kernel(const BwdH2Args a
     f32x4 negl[2], negd[2];
     auto rd_rows = [&](int jq, int boff) {
       const unsigned char* tb = smem + boff;
-      if (H2P_ABL & 128) { qA[jq][0] = kB[0][0]; oA[jq] = vB[0][0]; negl[jq] = f32x4{0.f, 0.f, 0.f, 0.f}; negd[jq] = negl[jq]; return; }
       qA[jq][0] = *reinterpret_cast<const u32x4*>(tb + G::QA_OFF + a1addr + jq * 16 * RROW);
       oA[jq] = *reinterpret_cast<const u32x4*>(tb + G::OA_OFF + a1addr + jq * 16 * RROW);
       negl[jq] = *reinterpret_cast<const f32x4*>(tb + G::SL_OFF + (16 * jq + 4 * g) * 4);
@@ -995,28 +837,24 @@ __global__ __launch_bounds__(MTHREADS) void mha_bwd_h2p_kernel(const BwdH2Args a
     };
     rd_rows(0, 0); rd_rows(1, 0);
     qA[0][1] = down(qA[0][0]); qA[1][1] = down(qA[1][0]);
-    u32x4 kT2s[2][2];
-    if (H2P_KTREG) {
+    u32x4 kT2[2][2];
 #pragma unroll
-      for (int sw = 0; sw < 2; ++sw)
+    for (int sw = 0; sw < 2; ++sw)
 #pragma unroll
-        for (int p = 0; p < 2; ++p) kT2s[sw][p] = *reinterpret_cast<const u32x4*>(smem + G::KT_OFF + ((2 * kq + sw) * 2 + p) * 1024 + lane * 16);
-    }
+      for (int p = 0; p < 2; ++p) kT2[sw][p] = *reinterpret_cast<const u32x4*>(smem + G::KT_OFF + ((2 * kq + sw) * 2 + p) * 1024 + lane * 16);
 
     // One iteration = issue slots in a fixed order, fenced (sched_barrier) so that the order written here is the order issued: about one
     // MFMA and one group of ~4 vector instructions per slot (an MFMA holds the vector issue port for 8 of its 16 cycles; left to the scheduler
     // the matrix products clump and the dq / sum stages sink to the end of the block as a serial tail).  Chains of dependent MFMAs are
     // interleaved two and two.
     auto iteration = [&](auto main_tag, auto dq_tag, auto sum_tag, auto dma_tag, auto pre_tag, auto first_tag, int u, int bcur, int bnext, int bnn) {
-      constexpr bool MAIN = decltype(main_tag)::value, DQ = decltype(dq_tag)::value && !(H2P_ABL & 2), SUM = decltype(sum_tag)::value && !(H2P_ABL & 4);
+      constexpr bool MAIN = decltype(main_tag)::value, DQ = decltype(dq_tag)::value, SUM = decltype(sum_tag)::value;
       constexpr bool DMA = decltype(dma_tag)::value, PRE = decltype(pre_tag)::value, FIRST = decltype(first_tag)::value;
       const int par = u & 1;
       const unsigned char* tb = smem + bcur;
       unsigned char* scr = smem + G::IMG_OFF + par * G::IMGB + wave * SCRB;
       const unsigned char* img = smem + G::IMG_OFF + (par ^ 1) * G::IMGB + (2 * kq) * SCRB + ojq * 32 + sraddr;      // source wave 2 kq (+ SCRB: 2 kq + 1)
       u32x4 qT[2], oT[2], qTd, sT[2][2];
-      u32x4 kT2l[2][2];
-      u32x4 (&kT2)[2][2] = H2P_KTREG ? kT2s : kT2l;
       f32x4 S[2][2], dP[2][2], acca, accb;
       unsigned Pp[2][2][4], Sp[2][2][4];          // [key tile][piece][word]: the B operands of dV^T / dK^T over the tile's 32 queries
       auto vec4 = [](const unsigned (&w)[4]) { return u32x4{w[0], w[1], w[2], w[3]}; };
@@ -1025,14 +863,13 @@ __global__ __launch_bounds__(MTHREADS) void mha_bwd_h2p_kernel(const BwdH2Args a
       const float* xs0 = reinterpret_cast<const float*>(smem + G::XP_OFF + par * G::XPB) + (tid >> 5 & 7) * DQS + (tid & 31);
       // ---- memory roles first: the copy of tile u + 1 / the partial tile of tile u - 2 out of xpart[par]
       if (copier) {
-        if constexpr (MAIN && DMA && !(H2P_ABL & 64)) dma_tile(u + 2, bnn);
+        if constexpr (MAIN && DMA) dma_tile(u + 2, bnn);
       } else if constexpr (SUM) {
 #pragma unroll
         for (int q = 0; q < 4; ++q) sraw[q] = xs0[q * (G::PARTB / 4)];      // rows d = 0 .. 7; summed a few slots later: no wait here
       }
       SLOT();
       auto rd_tr = [&](int p) {
-        if (H2P_ABL & 128) { qT[p] = kB[1][p]; oT[p] = vB[1][p]; return; }
         const unsigned char* sqp = tb + G::QE_OFF + p * RPART + a3addr;
         const u32x2 q0 = lds_read_tr16(sqp), q1 = lds_read_tr16(sqp + 16 * RROW);
         qT[p] = u32x4{q0[0], q0[1], q1[0], q1[1]};
@@ -1043,25 +880,20 @@ __global__ __launch_bounds__(MTHREADS) void mha_bwd_h2p_kernel(const BwdH2Args a
       auto rd_img = [&](int sw) {
 #pragma unroll
         for (int p = 0; p < 2; ++p) {
-          if (!H2P_KTREG) kT2[sw][p] = *reinterpret_cast<const u32x4*>(smem + G::KT_OFF + ((2 * kq + sw) * 2 + p) * 1024 + lane * 16);
           const u32x2 lo = lds_read_tr16(img + sw * SCRB + p * SPART), hi2 = lds_read_tr16(img + sw * SCRB + p * SPART + 4 * SROW);
           sT[sw][p] = u32x4{lo[0], lo[1], hi2[0], hi2[1]};
         }
       };
       // MFMA steps
       auto mS = [&](int kt, int jq, int j) {
-        if (H2P_ABL & 8) { if (j == 0) S[kt][jq] = negl[jq] + __builtin_bit_cast(f32x4, qA[jq][0]); return; }
         S[kt][jq] = mfma_f16(qA[jq][j], kB[kt][j], j == 0 ? negl[jq] : S[kt][jq]); };      // large term first
       auto mP = [&](int kt, int jq, int j) {      // (mutation test, bit 16: the cross product o0 v1 dropped, with its MFMA partner o1 v1)
-        if (H2P_ABL & 8) { if (j == 0) dP[kt][jq] = negd[jq] + __builtin_bit_cast(f32x4, oA[jq]); return; }
         if (!((HDIFF_MUTANT & 16) && j == 1)) dP[kt][jq] = mfma_f16(oA[jq], vB[kt][j], j == 0 ? negd[jq] : dP[kt][jq]);
       };
       auto mV = [&](int kt, int j) {              // small terms first: o1 p0, o0 p1, o0 p0; (mutation test, bit 32: o1 p0 dropped)
-        if (H2P_ABL & 8) { if (j == 0) dVa[kt] += __builtin_bit_cast(f32x4, vec4(Pp[kt][0])) + __builtin_bit_cast(f32x4, vec4(Pp[kt][1])) + __builtin_bit_cast(f32x4, oT[0]) + __builtin_bit_cast(f32x4, oT[1]); return; }
         if (!((HDIFF_MUTANT & 32) && j == 0)) dVa[kt] = mfma_f16(oT[j == 0 ? 1 : 0], vec4(Pp[kt][j == 1 ? 1 : 0]), dVa[kt]);
       };
       auto mK = [&](int kt, int j) {              // q1 s0, (q0 2^-8)(s1 2^8), q0 s0
-        if (H2P_ABL & 8) { if (j == 0) dKa[kt] += __builtin_bit_cast(f32x4, vec4(Sp[kt][0])) + __builtin_bit_cast(f32x4, vec4(Sp[kt][1])) + __builtin_bit_cast(f32x4, qT[0]) + __builtin_bit_cast(f32x4, qT[1]) + __builtin_bit_cast(f32x4, qTd); return; }
         dKa[kt] = mfma_f16(j == 0 ? qT[1] : j == 1 ? qTd : qT[0], vec4(Sp[kt][j == 1 ? 1 : 0]), dKa[kt]);
       };
       auto mQ = [&](int sw, int j) {              // j 0: k0 s0 -> a; 1: (k1 2^8) s0 -> b; 2: k0 (s1 2^8) -> b
@@ -1070,47 +902,32 @@ __global__ __launch_bounds__(MTHREADS) void mha_bwd_h2p_kernel(const BwdH2Args a
       };
       // vector steps of one (key tile, 16-query group): 4 scores per lane
       auto cE = [&](int kt, int jq) {
-        if (H2P_ABL & 1) {
-#pragma unroll
-          for (int w = 0; w < 2; ++w)
-#pragma unroll
-            for (int pc = 0; pc < 2; ++pc) {
-              Pp[kt][pc][2 * jq + w] = __builtin_bit_cast(unsigned, S[kt][jq][2 * w]) + pc;
-              Sp[kt][pc][2 * jq + w] = __builtin_bit_cast(unsigned, dP[kt][jq][2 * w + 1]) + pc;
-            }
-          return;
-        }
 #pragma unroll
         for (int i = 0; i < 4; ++i) pe[kt][jq][i] = __builtin_amdgcn_exp2f(S[kt][jq][i]);
       };
       auto cM = [&](int kt, int jq) {
-        if (H2P_ABL & 1) return;
 #pragma unroll
         for (int i = 0; i < 4; ++i) ds[kt][jq][i] = pe[kt][jq][i] * dP[kt][jq][i];
       };
       auto cA = [&](int kt, int jq) {
-        if (H2P_ABL & 1) return; ds_split_a(ds[kt][jq][0], ds[kt][jq][1], ds[kt][jq][2], ds[kt][jq][3], dsdn, Sp[kt][0][2 * jq], Sp[kt][0][2 * jq + 1]); };
+        ds_split_a(ds[kt][jq][0], ds[kt][jq][1], ds[kt][jq][2], ds[kt][jq][3], dsdn, Sp[kt][0][2 * jq], Sp[kt][0][2 * jq + 1]); };
       auto cB = [&](int kt, int jq) {
-        if (H2P_ABL & 1) return;
         ds_split_b(ds[kt][jq][0], ds[kt][jq][1], ds[kt][jq][2], ds[kt][jq][3], dsdn, Sp[kt][0][2 * jq], Sp[kt][0][2 * jq + 1], rr[kt][jq][0], rr[kt][jq][1],
                    rr[kt][jq][2], rr[kt][jq][3]);
       };
       auto cC = [&](int kt, int jq) {
-        if (H2P_ABL & 1) return;
         unsigned h1a, h1b;
         ds_split_c(rr[kt][jq][0], rr[kt][jq][1], rr[kt][jq][2], rr[kt][jq][3], up8, h1a, h1b);
         if (HDIFF_MUTANT & 64) { h1a &= 0xffe0ffe0u; h1b &= 0xffe0ffe0u; }      // (mutation test, bit 64)
         Sp[kt][1][2 * jq] = h1a; Sp[kt][1][2 * jq + 1] = h1b;
       };
       auto cP = [&](int kt, int jq) {
-        if (H2P_ABL & 1) return;
         unsigned pa0, pa1, pb0, pb1;
         split2(pe[kt][jq][0], pe[kt][jq][1], one, pa0, pa1);
         split2(pe[kt][jq][2], pe[kt][jq][3], one, pb0, pb1);
         Pp[kt][0][2 * jq] = pa0; Pp[kt][1][2 * jq] = pa1; Pp[kt][0][2 * jq + 1] = pb0; Pp[kt][1][2 * jq + 1] = pb1;
       };
-      auto cW = [&](int kt, int jq) {
-        if (H2P_ABL & 16) return;             // (key i16 of tile kt, queries 16 jq + 4 g ..+3) into the wave's [key][query] image
+      auto cW = [&](int kt, int jq) {       // (key i16 of tile kt, queries 16 jq + 4 g ..+3) into the wave's [key][query] image
 #pragma unroll
         for (int pc = 0; pc < 2; ++pc)
           *reinterpret_cast<u32x2*>(scr + pc * SPART + kt * 16 * SROW + jq * 32 + swaddr) = u32x2{Sp[kt][pc][2 * jq], Sp[kt][pc][2 * jq + 1]};
@@ -1146,8 +963,6 @@ __global__ __launch_bounds__(MTHREADS) void mha_bwd_h2p_kernel(const BwdH2Args a
         mP(0, 1, 1); cB(0, 0); SLOT();
       }
       if constexpr (SUM) { slab_out(1); SLOT(); }
-      if constexpr (MAIN) {
-      }
       if constexpr (DQ) {
         mQ(0, 1); if constexpr (MAIN) cC(0, 0); SLOT();
         mQ(0, 0); if constexpr (MAIN) cP(0, 0); SLOT();
@@ -1193,8 +1008,7 @@ __global__ __launch_bounds__(MTHREADS) void mha_bwd_h2p_kernel(const BwdH2Args a
       }
       if constexpr (MAIN && DMA)
         if (copier) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // this wave's LDS-DMA runs of tile u + 1 have landed
-      if (H2P_ABL & 32) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      else lds_barrier();
+      lds_barrier();
     };
     using T = std::true_type;
     using F = std::false_type;
@@ -1255,7 +1069,7 @@ struct H2Geom { int nkb_total, per, nsplit; };
 H2Geom h2_geometry(int B, int heads, int L, int D) {
   H2Geom g;
   g.nkb_total = L / KB;
-  int want = cdiv(H2B_WANT, B * heads);                  // workgroups wanted in all: four rounds of one per CU on 256 CUs
+  int want = cdiv(1024, B * heads);                  // workgroups wanted in all: four rounds of one per CU on 256 CUs
   // At larger batches that leaves few key ranges per (sample, head) pair, and the workgroups of a pair are the ones that share
   // its Q / dO tile stream in their XCD's L2: up to 16 ranges per pair (batch 16: 567 -> 553 ms per launch; 32: 547) as
   // long as the slabs stay below the cap (16 GiB, or HDIFF_BWD_SLAB_GIB: mha_bwd_slab_cap_bytes).
@@ -1317,8 +1131,7 @@ static bool big_lds_granted() {
   signed char st = state[dev].load(std::memory_order_acquire);
   if (st == 0) {
     const bool ok =
-        hipFuncSetAttribute(reinterpret_cast<const void*>(&mha_bwd_h2_kernel<16>), hipFuncAttributeMaxDynamicSharedMemorySize, Geo<16>::LDS_BYTES) == hipSuccess &&
-        hipFuncSetAttribute(reinterpret_cast<const void*>(&mha_bwd_h2_kernel<32>), hipFuncAttributeMaxDynamicSharedMemorySize, Geo<32>::LDS_BYTES) == hipSuccess &&
+        hipFuncSetAttribute(reinterpret_cast<const void*>(&mha_bwd_h2_kernel<32>), hipFuncAttributeMaxDynamicSharedMemorySize, Geo::LDS_BYTES) == hipSuccess &&
         hipFuncSetAttribute(reinterpret_cast<const void*>(&mha_bwd_h2p_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, GeoP::LDS_BYTES) == hipSuccess;
     if (!ok) (void)hipGetLastError();
     st = ok ? 1 : -1;
@@ -1354,17 +1167,12 @@ bool launch_mha_bwd_h2(const float* qkv, const float* d_o, const float* lse2, co
   if (D == 16) {
     hipLaunchKernelGGL(mha_bwd_absmax_kernel<16>, mgrid, dim3(THREADS), 0, stream, qkv, d_o, absmax, C, L);
     hipLaunchKernelGGL(mha_bwd_split_h2_kernel<16>, sgrid, dim3(THREADS), 0, stream, qkv, d_o, pieces, absmax, lse2, delta, C, L, qscale, 1.0f);
-    if (H2B_PIPE && MW == 8) {
-      hipLaunchKernelGGL(mha_bwd_h2p_kernel, grid, dim3(MTHREADS), GeoP::LDS_BYTES, stream, a);
-      hipLaunchKernelGGL(mha_dq_reduce_h2p_kernel, dim3(bx, B), dim3(256), 0, stream, ws, pieces, dqkv, g.nsplit, C, L, a.split_stride);
-    } else {
-      hipLaunchKernelGGL(mha_bwd_h2_kernel<16>, grid, dim3(MTHREADS), Geo<16>::LDS_BYTES, stream, a);
-      hipLaunchKernelGGL(mha_dq_reduce_h2_kernel<16>, dim3(bx, B), dim3(256), 0, stream, ws, dqkv, g.nsplit, C, L, a.split_stride);
-    }
+    hipLaunchKernelGGL(mha_bwd_h2p_kernel, grid, dim3(MTHREADS), GeoP::LDS_BYTES, stream, a);
+    hipLaunchKernelGGL(mha_dq_reduce_h2p_kernel, dim3(bx, B), dim3(256), 0, stream, ws, pieces, dqkv, g.nsplit, C, L, a.split_stride);
   } else {
     hipLaunchKernelGGL(mha_bwd_absmax_kernel<32>, mgrid, dim3(THREADS), 0, stream, qkv, d_o, absmax, C, L);
     hipLaunchKernelGGL(mha_bwd_split_h2_kernel<32>, sgrid, dim3(THREADS), 0, stream, qkv, d_o, pieces, absmax, lse2, delta, C, L, qscale, 1.0f);
-    hipLaunchKernelGGL(mha_bwd_h2_kernel<32>, grid, dim3(MTHREADS), Geo<32>::LDS_BYTES, stream, a);
+    hipLaunchKernelGGL(mha_bwd_h2_kernel<32>, grid, dim3(MTHREADS), Geo::LDS_BYTES, stream, a);
     hipLaunchKernelGGL(mha_dq_reduce_h2_kernel<32>, dim3(bx, B), dim3(256), 0, stream, ws, dqkv, g.nsplit, C, L, a.split_stride);
   }
   return true;

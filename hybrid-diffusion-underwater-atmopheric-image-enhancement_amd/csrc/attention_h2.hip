@@ -53,18 +53,6 @@ using namespace hdiff;
 
 namespace {
 
-#ifndef H2_ABL
-#define H2_ABL 0      // timing ablations (wrong results by construction; tools/README.md): 1 no workgroup barrier, 2 no rolling
-#endif                // K / Q reloads, 4 no global -> LDS staging in the loop, 8 no reference check, 16 no V reload
-#ifndef H2_DIAG
-#define H2_DIAG 0       // diagnostic build: s_memtime / s_memrealtime around the tile loop (tools/h2w_clock.py); never set in the product
-#endif
-#ifndef H2_T4
-#define H2_T4 1       // dev: 0 = the fourth score term k1 q1 (2^-24 of a score) multiplied by ZEROS -- same MFMAs, a quarter of the score product's
-#endif                // multipliers idle (A/B for the energy of the kernel at the board's power limit; tools/scripts/r6_fwd_t4.sh)
-#ifndef H2_VALU_PER_STAGE
-#define H2_VALU_PER_STAGE 54
-#endif
 constexpr int KT = 64;
 constexpr int THREADS = 256;
 constexpr float OVERFLOW_LIMIT = 1.2379400e27f;   // 2^90: only NaN / inf inputs get here (the reference moves before fp16 overflows)
@@ -267,7 +255,7 @@ __global__ __launch_bounds__(THREADS) void qk_split_h2_kernel(const float* __res
     float xa = src[(size_t)(2 * j) * L + l] * sc, xb = src[(size_t)(2 * j + 1) * L + l] * sc;
     // the fp32 products and the packed first pieces are made opaque: left alone the compiler rounds x0 twice -- once from the
     // fp32 product for the stored piece, once from the EXACT product (v_fma_mixlo_f16) for the residual -- and where the two
-    // differ by an ulp the stored pieces no longer add up (found by tools/h2_qk_debug.py: 4e-4 instead of 5e-7)
+    // differ by an ulp the stored pieces no longer add up (found with an operand dump: 4e-4 instead of 5e-7)
     asm("" : "+v"(xa), "+v"(xb));
     unsigned u0 = __builtin_bit_cast(unsigned, f16x2v{(_Float16)xa, (_Float16)xb});
     asm("" : "+v"(u0));
@@ -334,9 +322,6 @@ __global__ __launch_bounds__(THREADS) void v_split_h2_kernel(const float* __rest
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
-#ifndef H2_DMA
-#define H2_DMA 1             // K tiles global -> LDS by LDS-DMA (0: through registers like V; dev A/B)
-#endif
 typedef __attribute__((address_space(3))) unsigned char lds_byte;
 // One 1 KiB run global -> LDS without staging registers: lane i's 16 bytes at src + voff land at lds_dst + 16 i (global_load_lds_dwordx4).
 // M0 is written in the statement that uses it and restored (cdna_hip_programming.md, 'What hipcc does not do').  The compiler does not
@@ -396,7 +381,7 @@ __global__ __launch_bounds__(THREADS, 2) void mha_flash_fwd_h2_kernel(const __bf
       // (asm: written as four v2f16 multiplications in C, hipcc 7.2 -O3 emits ONE v_pk_mul_f16 and broadcasts word 0 over the tuple)
       unsigned dnw[4];
 #pragma unroll
-      for (int w = 0; w < 4; ++w) asm("v_pk_mul_f16 %0, %1, %2" : "=v"(dnw[w]) : "v"(sel[w]), "v"((!H2_T4 && hi) ? 0u : dn2));
+      for (int w = 0; w < 4; ++w) asm("v_pk_mul_f16 %0, %1, %2" : "=v"(dnw[w]) : "v"(sel[w]), "v"(dn2));
       qop[qt][0] = sel;                                      // against K set 0 = (k0 | k0 2^-8)
       qop[qt][1] = u32x4{dnw[0], dnw[1], dnw[2], dnw[3]};    // against K set 1 = (k1 2^8 | k1)
     }
@@ -406,65 +391,36 @@ __global__ __launch_bounds__(THREADS, 2) void mha_flash_fwd_h2_kernel(const __bf
   for (int ks = 0; ks < NKS; ++ks) kaddr[ks] = (2 * ks + (hi ? 1 : 0)) * KPART + i16 * KROWB + doff * 2;
   const int vaddr = i16 * VROWB + 8 * g;
 
-  // staging: chunk c = i * 256 + tid of the tile's 16-byte chunks (four K pieces, then two V pieces), copied as they are
-  // (H2_DMA) the four K pieces of a tile are eight contiguous 1 KiB runs in the workspace AND in LDS ([piece][key][32 bytes], no padding):
+  // staging: the four K pieces of a tile are eight contiguous 1 KiB runs in the workspace AND in LDS ([piece][key][32 bytes], no padding):
   // each wave copies two of them by LDS-DMA -- no staging registers, no ds_write, no per-thread addresses; only V (padded rows) goes
-  // through registers
-  constexpr bool DMA = (H2_DMA != 0);
-  constexpr int NKC = DMA ? 0 : NKP * KT * D / 8, NVC = 2 * D * 8, NCH = NKC + NVC, NLD = (NCH + THREADS - 1) / THREADS;
-  static_assert(NLD * THREADS - NCH <= NVC, "staging geometry");
-  static_assert(!DMA || (KPART == 2048 && THREADS == 256), "LDS-DMA geometry: eight 1 KiB runs, two per wave");
-  const unsigned char* gsrc[NLD];
-  int lds_off[NLD], gstep[NLD];
-  u32x4 stage[NLD];
+  // through registers, 16-byte chunk tid of its two pieces per thread
+  static_assert(2 * D * 8 == THREADS, "staging geometry: one V chunk per thread");
+  static_assert(KPART == 2048 && THREADS == 256, "LDS-DMA geometry: eight 1 KiB runs, two per wave");
+  const unsigned char* gsrc;
+  int lds_off;
+  u32x4 stage;
   {
-    const __bf16* ksp = wsq + 2 * piece_n;
     const __bf16* vsp = wsq + 6 * piece_n;
-#pragma unroll
-    for (int i = 0; i < NLD; ++i) {
-      int c = i * THREADS + tid;
-      if (c >= NCH) c -= NLD * THREADS - NCH;
-      if (c < NKC) {
-        const int p = c / (KT * D / 8), rem = c - p * (KT * D / 8);
-        gsrc[i] = reinterpret_cast<const unsigned char*>(ksp + p * piece_n) + (size_t)rem * 16;
-        lds_off[i] = p * KPART + rem * 16;
-        gstep[i] = KT * D * 2;
-      } else {
-        const int cv = c - NKC;
-        const int p = cv / (D * 8), rem = cv - p * (D * 8);
-        const int d = rem >> 3, seg = rem & 7;
-        gsrc[i] = reinterpret_cast<const unsigned char*>(vsp + p * piece_n + (size_t)d * L) + seg * 16;
-        lds_off[i] = VBASE + p * VPART + d * VROWB + seg * 16;
-        gstep[i] = KT * 2;
-      }
-    }
+    const int p = tid / (D * 8), rem = tid - p * (D * 8);
+    const int d = rem >> 3, seg = rem & 7;
+    gsrc = reinterpret_cast<const unsigned char*>(vsp + p * piece_n + (size_t)d * L) + seg * 16;
+    lds_off = VBASE + p * VPART + d * VROWB + seg * 16;
   }
   const unsigned lds0 = (unsigned)(size_t)(lds_byte*)&smem[0][0];
   const unsigned char* kdma = reinterpret_cast<const unsigned char*>(wsq + 2 * piece_n);      // + piece * piece_n * 2 + tile * 2048 + half * 1024
   // wave w copies runs 2 w, 2 w + 1 of the tile: piece w, its two 32-key halves
   auto dma_k = [&](int t, int buf) {
-    if (!DMA) return;
     const int ws_ = __builtin_amdgcn_readfirstlane(wave);      // the asm operands must be scalar registers
     const unsigned char* src = kdma + (size_t)ws_ * (piece_n * 2) + (size_t)t * KPART;
     const unsigned dst = __builtin_amdgcn_readfirstlane(lds0 + buf * BUFB + ws_ * KPART);
     dma_1k(src, lane * 16, dst);
     dma_1k(src + 1024, lane * 16, dst + 1024);
   };
-  auto stage_load = [&](int t) {
-#pragma unroll
-    for (int i = 0; i < NLD; ++i) {
-      // the per-tile step is a compile-time constant for the rounds that hold only K or only V chunks
-      const int step = ((i + 1) * THREADS <= NKC) ? KT * D * 2 : (i * THREADS >= NKC ? KT * 2 : gstep[i]);
-      stage[i] = *reinterpret_cast<const u32x4*>(gsrc[i] + (size_t)t * step);
-    }
-  };
-  auto stage_store = [&](int buf) {
-#pragma unroll
-    for (int i = 0; i < NLD; ++i) {       // two 8-byte stores for K and V chunks alike: no per-thread branch
-      unsigned char* dst = &smem[buf][lds_off[i]];
-      *reinterpret_cast<u32x2*>(dst) = u32x2{stage[i][0], stage[i][1]};
-      *reinterpret_cast<u32x2*>(dst + 8) = u32x2{stage[i][2], stage[i][3]};
-    }
+  auto stage_load = [&](int t) { stage = *reinterpret_cast<const u32x4*>(gsrc + (size_t)t * (KT * 2)); };
+  auto stage_store = [&](int buf) {      // two 8-byte stores: the padded V rows are 8-byte aligned
+    unsigned char* dst = &smem[buf][lds_off];
+    *reinterpret_cast<u32x2*>(dst) = u32x2{stage[0], stage[1]};
+    *reinterpret_cast<u32x2*>(dst + 8) = u32x2{stage[2], stage[3]};
   };
 
   f32x4 O[MT][NQ];
@@ -515,7 +471,6 @@ __global__ __launch_bounds__(THREADS, 2) void mha_flash_fwd_h2_kernel(const __bf
 #pragma unroll
       for (int w = 0; w < 4; ++w) qb[w] &= 0xffe0ffe0u;
     S[par][kt] = mfma_f16(kop[kt][j], qb, j == 0 ? negm4[qt] : S[par][kt]);      // the chain starts from -m, large terms first
-    if (H2_ABL & 2) return;
     if (rollk >= 0) kop[kt][j] = *reinterpret_cast<const u32x4*>(smem[rollk] + kaddr[j] + kt * 16 * KROWB);
   };
   constexpr int NPV = 6 * MT;
@@ -614,15 +569,13 @@ __global__ __launch_bounds__(THREADS, 2) void mha_flash_fwd_h2_kernel(const __bf
         for (int n = NV * i / NM; n < NV * (i + 1) / NM; ++n) vstep(n);
         __builtin_amdgcn_sched_barrier(0);
       }
-      if (!(H2_ABL & 8)) {
-        // any lane with sum >= P_TRIP: some P of this stage may not fit fp16 (see above)
-        const unsigned long long cond = __builtin_amdgcn_ballot_w64(sum0 + sum1 >= P_TRIP);
-        const float delta = h2_rare_delta(cond, S[par], bp16, bp32);
-        h2_rare_rescale(cond, delta, O[0][QT], negm4[QT], l_run[QT], sum0, sum1);
+      // any lane with sum >= P_TRIP: some P of this stage may not fit fp16 (see above)
+      const unsigned long long cond = __builtin_amdgcn_ballot_w64(sum0 + sum1 >= P_TRIP);
+      const float delta = h2_rare_delta(cond, S[par], bp16, bp32);
+      h2_rare_rescale(cond, delta, O[0][QT], negm4[QT], l_run[QT], sum0, sum1);
 #pragma unroll
-        for (int kt = 0; kt < 4; ++kt)
-          h2_rare_exp_split(cond, delta, one, S[par][kt], u[kt][0], u[kt][1], r2[kt][0], r2[kt][1], sum0, sum1);
-      }
+      for (int kt = 0; kt < 4; ++kt)
+        h2_rare_exp_split(cond, delta, one, S[par][kt], u[kt][0], u[kt][1], r2[kt][0], r2[kt][1], sum0, sum1);
 #pragma unroll
       for (int kt = 0; kt < 4; ++kt) {
         const int c = kt >> 1, o = (kt & 1) * 2;
@@ -641,59 +594,32 @@ __global__ __launch_bounds__(THREADS, 2) void mha_flash_fwd_h2_kernel(const __bf
     const int buf = t & 1;
     if constexpr (FIRST) load_v(buf);
     stage_fn(std::integral_constant<int, 0>{}, first_tag, Pend{});
-    if constexpr (!FIRST) if (!(H2_ABL & 16)) load_v(buf);
+    if constexpr (!FIRST) load_v(buf);
     stage_fn(std::integral_constant<int, 1>{}, first_tag, std::true_type{});
-    if (!(H2_ABL & 4)) stage_store(buf ^ 1);                 // tile t + 1: its buffer was last read before the previous tile's barrier
-    if (DMA) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // this wave's K runs of tile t + 1 have landed in buffer buf ^ 1
-    if (!(H2_ABL & 1)) __syncthreads();
-    if (!(H2_ABL & 4)) stage_load((t + 2 < ntiles) ? t + 2 : ntiles - 1);
-    if (!(H2_ABL & 4)) dma_k((t + 2 < ntiles) ? t + 2 : ntiles - 1, buf);      // buffer buf is free: K(t) sits in kop since the last tile, V(t) was read above
+    stage_store(buf ^ 1);                 // tile t + 1: its buffer was last read before the previous tile's barrier
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // this wave's K runs of tile t + 1 have landed in buffer buf ^ 1
+    __syncthreads();
+    stage_load((t + 2 < ntiles) ? t + 2 : ntiles - 1);
+    dma_k((t + 2 < ntiles) ? t + 2 : ntiles - 1, buf);      // buffer buf is free: K(t) sits in kop since the last tile, V(t) was read above
     stage_fn(std::integral_constant<int, 2>{}, first_tag, std::true_type{}, buf ^ 1);    // K(t + 1) follows K(t) through kop
     stage_fn(std::integral_constant<int, 3>{}, first_tag, std::true_type{});
   };
 
-#if H2_DIAG
-  const unsigned long long diag_t0 = __builtin_amdgcn_s_memtime(), diag_r0 = __builtin_amdgcn_s_memrealtime();
-#endif
   stage_load(0);
   dma_k(0, 0);
   stage_store(0);
-  if (DMA) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
   stage_load(ntiles > 1 ? 1 : 0);
   dma_k(ntiles > 1 ? 1 : 0, 1);
   load_k(0);
 #pragma unroll
   for (int n = 0; n < 4 * NQK; ++n) qk_mfma(0, 0, n);
-#if H2_DIAG == 2
-  // scores of (query tile 0 of wave 0, key tile 0) of the first workgroup of every pair: S[0][kt][r] = s(query qblk0 + i16, key 16 kt + 4 g + r)
-  if (tile.x == 0 && wave == 0) {
-    float* dg = reinterpret_cast<float*>(reinterpret_cast<unsigned char*>(const_cast<__bf16*>(wsq + 8 * piece_n)) + 128) + lane * 16;
-#pragma unroll
-    for (int kt = 0; kt < 4; ++kt)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) dg[kt * 4 + r] = S[0][kt][r];
-    // ... and the operands the lane holds: Q sets 0, 1 of query tile 0 and K sets 0, 1 of key tile 0 (re-read from LDS)
-    unsigned* du = reinterpret_cast<unsigned*>(dg - lane * 16 + 64 * 16) + lane * 16;
-#pragma unroll
-    for (int w = 0; w < 4; ++w) {
-      du[w] = qop[0][0][w]; du[4 + w] = qop[0][1][w];
-      du[8 + w] = reinterpret_cast<const unsigned*>(smem[0] + kaddr[0])[w]; du[12 + w] = reinterpret_cast<const unsigned*>(smem[0] + kaddr[1])[w];
-    }
-  }
-#endif
   tile_fn(std::true_type{}, 0);
   for (int t = 1; t < ntiles; ++t) tile_fn(std::false_type{}, t);
 #pragma unroll
   for (int n = 0; n < NPV; ++n) pv_mfma(NQ - 1, 1, n);
 
-#if H2_DIAG
-  if (tid == 0) {
-    unsigned long long* dg = reinterpret_cast<unsigned long long*>(reinterpret_cast<unsigned char*>(const_cast<__bf16*>(wsq + 8 * piece_n)) + 64) + 2 * tile.x;
-    dg[0] = __builtin_amdgcn_s_memtime() - diag_t0;
-    dg[1] = __builtin_amdgcn_s_memrealtime() - diag_r0;
-  }
-#endif
   float* obase = out + ((size_t)b * C + (size_t)head * D) * L;
   const float* vinv = reinterpret_cast<const float*>(wsq + 8 * piece_n);      // 2^-s per channel of this head
 #pragma unroll

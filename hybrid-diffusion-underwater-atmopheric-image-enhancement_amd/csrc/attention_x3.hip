@@ -25,11 +25,9 @@ using namespace hdiff;
 
 namespace {
 
-#ifndef X3_VALU_PER_STAGE
-#define X3_VALU_PER_STAGE 80
-#endif
 constexpr int KT = 64;
 constexpr int THREADS = 256;
+constexpr int VALU_PER_STAGE = 80;                // vector instructions of a stage, spread over its MFMAs (the stage loop)
 constexpr float OVERFLOW_LIMIT = 1.2379400e27f;   // 2^90, as in attention.hip
 
 typedef float f32x2 __attribute__((ext_vector_type(2)));
@@ -279,7 +277,7 @@ __global__ __launch_bounds__(THREADS, 2) void mha_flash_fwd_x3_kernel(const floa
         // pin the interleave: one MFMA, then its share of the stage's VALU instructions (the scheduler otherwise clumps
         // the MFMAs, which costs about 9% -- measured)
         constexpr int nm = ((qt + 1 < NQ) ? 4 * NQK : 0) + ((qt > 0) ? 12 * MT : 0);
-        constexpr int per = X3_VALU_PER_STAGE / (nm > 0 ? nm : 1);
+        constexpr int per = VALU_PER_STAGE / (nm > 0 ? nm : 1);
 #pragma unroll
         for (int i = 0; i < nm; ++i) {
           __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);

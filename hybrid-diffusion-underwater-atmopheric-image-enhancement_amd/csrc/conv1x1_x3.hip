@@ -26,9 +26,6 @@ using namespace hdiff;
 
 namespace {
 
-#ifndef C1X3_ABL
-#define C1X3_ABL 0   // dev: timing ablations (wrong results with any bit set): 1 no X loads in the loop, 2 no weight loads in the loop,
-#endif               // 4 no split (raw bits as pieces), 8 no MFMAs, 16 no epilogue loads / stores (one store per lane)
 constexpr int THREADS = 256;
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
@@ -127,8 +124,7 @@ __global__ __launch_bounds__(THREADS, 3) void conv1x1_x3_kernel(const Conv1x1X3K
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         unsigned h0, h1, h2;
-        if (C1X3_ABL & 4) { h0 = __builtin_bit_cast(unsigned, x[2 * j][nt]); h1 = __builtin_bit_cast(unsigned, x[2 * j + 1][nt]); h2 = h0 ^ h1; }
-        else split3(x[2 * j][nt], x[2 * j + 1][nt], h0, h1, h2);
+        split3(x[2 * j][nt], x[2 * j + 1][nt], h0, h1, h2);
         xp[nt][0][j] = h0; xp[nt][1][j] = h1; xp[nt][2][j] = h2;
       }
 #pragma unroll
@@ -137,10 +133,7 @@ __global__ __launch_bounds__(THREADS, 3) void conv1x1_x3_kernel(const Conv1x1X3K
 #pragma unroll
       for (int mt = 0; mt < MT; ++mt)
 #pragma unroll
-        for (int nt = 0; nt < WN; ++nt) {
-          if (C1X3_ABL & 8) { acc[mt][nt][t] += __builtin_bit_cast(float, w[mt][TERM_W[t]][nt] ^ xp[nt][TERM_X[t]][mt]); }
-          else acc[mt][nt] = mfma_bf16(w[mt][TERM_W[t]], xp[nt][TERM_X[t]], acc[mt][nt]);
-        }
+        for (int nt = 0; nt < WN; ++nt) acc[mt][nt] = mfma_bf16(w[mt][TERM_W[t]], xp[nt][TERM_X[t]], acc[mt][nt]);
     }
   };
 
@@ -198,8 +191,8 @@ __global__ __launch_bounds__(THREADS, 3) void conv1x1_x3_kernel(const Conv1x1X3K
 #pragma unroll
       for (int i = 0; i < XD + 1; ++i) {
         if (c + i < nchunks) {                         // uniform
-          if (!(C1X3_ABL & 1)) load_x(xr[(i + XD) % (XD + 1)], c + i + XD);
-          if (!(C1X3_ABL & 2)) load_w(wr[(i + 1) & 1], c + i + 1);
+          load_x(xr[(i + XD) % (XD + 1)], c + i + XD);
+          load_w(wr[(i + 1) & 1], c + i + 1);
           mma(xr[i], wr[i & 1]);
         }
       }
@@ -210,17 +203,6 @@ __global__ __launch_bounds__(THREADS, 3) void conv1x1_x3_kernel(const Conv1x1X3K
   // accumulator register r of tile mt holds channel co0 + 32 mt + (r & 3) + 8 (r >> 2) + 4 h
   const size_t blk = ((size_t)b * p.Cout) * p.HW + px0;
   const bool full = co0 + 64 <= p.Cout;
-  if (C1X3_ABL & 16) {
-    float t = 0.f;
-#pragma unroll
-    for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-      for (int nt = 0; nt < WN; ++nt)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) t += acc[mt][nt][r];
-    p.out[blk + (size_t)(co0 + 4 * h) * p.HW + 2u * l31] = t;
-    return;
-  }
 #pragma unroll
   for (int mt = 0; mt < MT; ++mt) {
 #pragma unroll

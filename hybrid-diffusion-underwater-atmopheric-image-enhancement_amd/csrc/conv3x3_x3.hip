@@ -40,9 +40,6 @@ using namespace hdiff;
 
 namespace {
 
-#ifndef CONVH2_ABL
-#define CONVH2_ABL 0   // dev: timing ablations of the fp16-pair form (wrong results with any bit set; tools/README.md): 1 no staging of
-#endif                 // the next chunk, 2 no weight loads in the loop, 4 no barrier, 8 no B operand reads in the loop, 16 no Swish
 constexpr int THREADS = 256;
 constexpr int PH = 10, PW = 34, PPIX = PH * PW;      // patch of an 8 x 32 tile
 constexpr int NSLOT = (4 * PPIX + THREADS - 1) / THREADS;   // (channel quad, pixel) staging slots per thread: 6
@@ -201,10 +198,7 @@ __global__ __launch_bounds__(THREADS, OCC) void conv3x3_x3_kernel(const ConvX3K 
       const f32x4 sh = *reinterpret_cast<const f32x4*>(&sG[p.Cin + ci]);
       const bool inside = s_goff[i] >= 0;
 #pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        const float gk = (PAIR && (CONVH2_ABL & 16)) ? fmaf(v[k], sc[k], sh[k]) : swish_fast(fmaf(v[k], sc[k], sh[k]));
-        v[k] = inside ? gk : 0.f;
-      }
+      for (int k = 0; k < 4; ++k) v[k] = inside ? swish_fast(fmaf(v[k], sc[k], sh[k])) : 0.f;
     }
     typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
     if constexpr (PAIR) {
@@ -284,16 +278,15 @@ __global__ __launch_bounds__(THREADS, OCC) void conv3x3_x3_kernel(const ConvX3K 
     load_x(xp[0], sX, 0, 0);
 #pragma unroll
     for (int tap = 0; tap < NT; ++tap) {
-      if (PAIR && (CONVH2_ABL & 2)) {
-      } else if (tap + 2 < NT) load_w(w[(tap + 2) % 3], c, tap + 2);
+      if (tap + 2 < NT) load_w(w[(tap + 2) % 3], c, tap + 2);
       else if (WSTREAM && more) load_w(w[(tap + 2) % 3], c + 1, tap + 2 - NT);      // the next chunk's first two taps
 #pragma unroll
       for (int nt = 0; nt < 4; ++nt) {
         const int u = tap * 4 + nt;
-        if (u + 1 < 4 * NT && !(PAIR && (CONVH2_ABL & 8))) load_x(xp[(u + 1) & 1], sX, (u + 1) / 4, (u + 1) % 4);
-        mma_unit(w[tap % 3], xp[(PAIR && (CONVH2_ABL & 8)) ? 0 : (u & 1)], nt);
+        if (u + 1 < 4 * NT) load_x(xp[(u + 1) & 1], sX, (u + 1) / 4, (u + 1) % 4);
+        mma_unit(w[tap % 3], xp[u & 1], nt);
       }
-      if (more && tap < NSLOT && !(PAIR && (CONVH2_ABL & 1))) stage_slot(gn_tag, tap, (c + 1) * 16, sNext);
+      if (more && tap < NSLOT) stage_slot(gn_tag, tap, (c + 1) * 16, sNext);
     }
     if (more) {
 #pragma unroll
@@ -307,7 +300,7 @@ __global__ __launch_bounds__(THREADS, OCC) void conv3x3_x3_kernel(const ConvX3K 
     } else {
       if (c + 2 < nchunks) issue_loads((c + 2) * 16);
     }
-    if (!(PAIR && (CONVH2_ABL & 4))) __syncthreads();
+    __syncthreads();
   };
 
   const int nchunks = p.Cin / 16;
