@@ -59,7 +59,7 @@ __global__ __launch_bounds__(OT) void opt_clip_coef_kernel(const float* __restri
     const float norm = (float)sqrt(red[0]);
     out[0] = norm;
     const float c = max_norm / (norm + 1e-6f);
-    out[1] = c < 1.0f ? c : 1.0f;
+    out[1] = (c < 1.0f || c != c) ? c : 1.0f;      // torch.clamp(c, max=1) keeps a NaN: a NaN norm makes every gradient NaN
   }
 }
 

@@ -26,6 +26,9 @@ Fixtures:
   G6 trainer_small.npz    Trainer loss with recorded (t, noise); grads of named params; one clipped AdamW step
   G6b trainer_default64.npz  the DEFAULT model's trainer pass at 64x64, B = 2 (attention backward over L = 4096, d_head 16 / 32):
                           loss, 19 small gradient tensors + 4 row slices, total norm         [python -m oracle.gen_golden g6b]
+  G10 trainer_default32_b80.npz  MainCondition.py's default training run (32x32, B = 80, T = 500): six steps of the reference's
+                          loop (clip + AdamW + warm-up / cosine schedule), plain and peaked attention, fp32 and float64
+                          [python -m oracle.gen_golden g10; ~10 min, ~27 GB]
   G7 state_dict_default.json   the 366 (name, shape) pairs of the default UNet
   G8 lr_schedule.json     GradualWarmupScheduler + CosineAnnealingLR learning-rate sequence (Scheduler.py)
   G9 main_condition_defaults.json  the default ``modelConfig`` literal of MainCondition.py's ``main()``, read with ``ast``
@@ -38,6 +41,7 @@ import io
 import json
 import os
 import sys
+import time
 
 import numpy as np
 import torch
@@ -399,6 +403,16 @@ def gen_unet_wide(RM, RD):
     np.savez_compressed(os.path.join(OUT, "unet_wide.npz"), **out)
 
 
+G6B_NAMES = ["head.bias", "tail.2.weight", "tail.0.weight", "time_embedding.timembedding.3.bias",
+             "cond_embedding.condEmbedding.3.bias", "downblocks.0.block1.0.weight", "downblocks.0.attn.in_proj_bias",
+             "downblocks.0.attn.out_proj.bias", "downblocks.1.block2.3.bias", "downblocks.2.c1.bias",
+             "downblocks.3.shortcut.bias", "downblocks.3.attn.in_proj_bias", "downblocks.4.temb_proj.1.bias",
+             "middleblocks.0.attn.in_proj_bias", "middleblocks.1.cond_proj.1.bias", "upblocks.0.block1.0.bias",
+             "upblocks.3.t.bias", "upblocks.14.block2.0.weight", "upblocks.14.shortcut.bias"]
+G6B_ROW_NAMES = ["downblocks.0.attn.in_proj_weight", "downblocks.3.attn.in_proj_weight", "downblocks.0.block1.2.weight",
+                 "upblocks.14.block1.2.weight"]        # large tensors: the first 4 output rows are recorded
+
+
 def gen_trainer_default64(RM, RD):
     """G6b: one trainer pass of the DEFAULT model (ch=128, [1,2,2,2], d_head 16 / 32; attention over L = 4096 at the first
     level) from the REAL reference at 64x64, B = 2: loss, gradients of small tensors from every part of the network, the
@@ -425,20 +439,199 @@ def gen_trainer_default64(RM, RD):
            "x_0": _np(x_0), "labels": _np(labels), "t": _np(rec.randint[0]), "noise": _np(rec.randn[0]), "loss": _np(loss),
            "temb_rows": _np(m.time_embedding.timembedding[0].weight[rec.randint[0]])}
     params = dict(m.named_parameters())
-    names = ["head.bias", "tail.2.weight", "tail.0.weight", "time_embedding.timembedding.3.bias",
-             "cond_embedding.condEmbedding.3.bias", "downblocks.0.block1.0.weight", "downblocks.0.attn.in_proj_bias",
-             "downblocks.0.attn.out_proj.bias", "downblocks.1.block2.3.bias", "downblocks.2.c1.bias",
-             "downblocks.3.shortcut.bias", "downblocks.3.attn.in_proj_bias", "downblocks.4.temb_proj.1.bias",
-             "middleblocks.0.attn.in_proj_bias", "middleblocks.1.cond_proj.1.bias", "upblocks.0.block1.0.bias",
-             "upblocks.3.t.bias", "upblocks.14.block2.0.weight", "upblocks.14.shortcut.bias"]
-    for n in names:
+    for n in G6B_NAMES:
         out[f"grad/{n}"] = _np(params[n].grad)
     # slices of large tensors: the first 4 output rows
-    for n in ["downblocks.0.attn.in_proj_weight", "downblocks.3.attn.in_proj_weight", "downblocks.0.block1.2.weight",
-              "upblocks.14.block1.2.weight"]:
+    for n in G6B_ROW_NAMES:
         out[f"gradrows/{n}"] = _np(params[n].grad[:4])
     out["grad_total_norm"] = np.array([torch.nn.utils.clip_grad_norm_(m.parameters(), 1e9).item()])
     np.savez_compressed(os.path.join(OUT, "trainer_default64.npz"), **out)
+
+
+G10 = dict(B=80, H=32, T=500, steps=6, beta_1=1e-4, beta_T=0.028, lr=1e-4, weight_decay=1e-4, grad_clip=1.0, multiplier=2.5,
+           epoch=70, input_seed=3280, zero_label_step=2)
+
+
+def g10_inputs(step, B=G10["B"], H=G10["H"], T=G10["T"], seed=G10["input_seed"]):
+    """x_0, labels, t, noise of G10's training step ``step`` (0-based).  Only torch.rand / torch.randint draws and single IEEE
+    operations on them, so every host makes the same bits (a CPU randn does not: its last bits depend on the CPU generation).
+    x_0 is uniform in [-1, 1) like the normalised CIFAR images.  The noise is the Irwin-Hall sum of four uniforms scaled to
+    unit variance.  Labels are 1 .. 10 except in step ``zero_label_step``, where all are 0 (the reference's 10 % label drop).
+    On even steps sample 0 has t = 0 and the last sample t = T - 1."""
+    g = torch.Generator().manual_seed(seed + step)
+    x_0 = torch.rand(B, 3, H, H, generator=g) * 2 - 1
+    u = torch.rand(4, B, 3, H, H, generator=g)
+    noise = (((u[0] + u[1]) + (u[2] + u[3])) - 2.0) * 3.0 ** 0.5
+    labels = torch.randint(1, 11, (B,), generator=g)
+    if step == G10["zero_label_step"]:
+        labels.zero_()
+    t = torch.randint(0, T, (B,), generator=g)
+    if step % 2 == 0:
+        t[0], t[-1] = 0, T - 1
+    return x_0, labels, t, noise
+
+
+def bit_checksum(x):
+    """int64 sum of a float32 tensor's bit patterns (exact, order-independent)"""
+    return int(x.detach().float().contiguous().reshape(-1).view(torch.int32).to(torch.int64).sum().item())
+
+
+def g10_peaked_(m):
+    """G10's "peaked" variant: the q and k rows of every in_proj_weight times sqrt(3) (one fp32 multiply), so scores are 3x larger"""
+    with torch.no_grad():
+        for n, p in m.named_parameters():
+            if n.endswith("in_proj_weight"):
+                p[:2 * p.shape[1]].mul_(3.0 ** 0.5)
+
+
+class _Feed:
+    """Make the reference's torch.randint / torch.randn_like return the given t / noise (cast to the input's dtype)."""
+
+    def __init__(self, t, noise):
+        self.t, self.noise = t, noise
+
+    def __enter__(self):
+        self._orig = (torch.randint, torch.randn_like)
+        torch.randint = lambda *a, **k: self.t.clone()
+        torch.randn_like = lambda x, *a, **k: self.noise.to(x.dtype)
+        return self
+
+    def __exit__(self, *exc):
+        torch.randint, torch.randn_like = self._orig
+
+
+def _mean_max_softmax(attn, h, samples):
+    """mean over (sample, head, query row) of the largest softmax probability of MHA module ``attn`` on its input h (L, B, C)"""
+    with torch.no_grad():
+        _, w = attn(h[:, samples], h[:, samples], h[:, samples], need_weights=True, average_attn_weights=False)
+    return w.max(dim=-1).values.double().mean().item()
+
+
+def gen_trainer_default32_b80(RM, RD):
+    """G10: the first six optimizer steps of MainCondition.py's default training run (TrainCondition.py:59-63 with the
+    warm-up + cosine schedule of :41-44): 32x32, B = 80, T = 500, beta 1e-4 .. 0.028, lr 1e-4, grad_clip 1.0, multiplier 2.5,
+    epoch 70, the scheduler stepped once per optimizer step (as if each step were one epoch) so that the rate moves.
+
+    Model: the default UNet with dropout 0, G6b's seed recipe (seed 0, seeded MHA-bias perturbation).  The tensors whose values a
+    host's CPU could round differently -- the sinusoidal time table, the label embedding (normal_ init) and the perturbed MHA
+    biases -- are stored, the rest is pinned by weight checksums.  Inputs come from g10_inputs (checksums stored).
+    Two weight variants: "plain" and "peaked" (g10_peaked_; the mean largest softmax probability of the first attention block is
+    stored for both).  Each is run as the reference runs (fp32) and with module and inputs in float64 (t, noise, labels fed
+    the same).  Recorded per run: the loss, pre-clip total norm and learning rate of every step; the step-1 (pre-clip) gradients
+    of G6b's tensor list; those parameters after step 1 and after step 6 (row slices of the large ones).
+
+    Cost on an 8-CPU host: one reference step takes 13-16 s in fp32 (peak 14.7 GB) and 33-49 s in float64 (peak 26.4 GB);
+    the whole recipe 10-13 min."""
+    import copy
+    import warnings
+    RS = RL.load_scheduler()
+    cfg = dict(DEFAULT, T=G10["T"], dropout=0.0)
+    torch.manual_seed(DEFAULT_SEED)
+    m0 = RM.UNet(**cfg)
+    g = torch.Generator().manual_seed(DEFAULT_SEED + 1)
+    with torch.no_grad():
+        for n, p in sorted(m0.named_parameters()):
+            if n.endswith("in_proj_bias") or n.endswith("out_proj.bias"):
+                p.copy_(torch.randn(p.shape, generator=g) * 0.05)
+    stored = sorted([n for n, _ in m0.named_parameters() if n.endswith("in_proj_bias") or n.endswith("out_proj.bias")]
+                    + ["time_embedding.timembedding.0.weight", "cond_embedding.condEmbedding.0.weight"])
+    sd0 = m0.state_dict()
+    names, sums = weight_checksums(sd0)
+    B, steps = G10["B"], G10["steps"]
+    out = {"seed": np.array([DEFAULT_SEED]), "cfg_json": np.frombuffer(json.dumps(cfg).encode(), dtype=np.uint8),
+           "recipe_json": np.frombuffer(json.dumps(G10).encode(), dtype=np.uint8),
+           "weight_names": np.array(names), "weight_checksums": sums, "stored_names": np.array(stored)}
+    for n in stored:
+        out[f"init/{n}"] = _np(sd0[n])
+    ins = [g10_inputs(s) for s in range(steps)]
+    out["t"] = np.stack([_np(i[2]) for i in ins])
+    out["labels"] = np.stack([_np(i[1]) for i in ins])
+    out["input_checksums"] = np.array([[bit_checksum(i[0]), bit_checksum(i[3])] for i in ins], dtype=np.int64)
+    p0 = {}
+    for variant in ("plain", "peaked"):
+        mv = copy.deepcopy(m0)
+        if variant == "peaked":
+            g10_peaked_(mv)
+        p0[variant] = {n: _np(p) for n, p in mv.named_parameters()}
+        # how peaked the level-0 rows are: the first attention block's input at step 1, two samples
+        cap = {}
+        hook = mv.downblocks[0].attn.register_forward_hook(lambda mod, a, o: cap.update(h=a[0].detach()))
+        with torch.no_grad(), _Feed(ins[0][2][[0, B - 1]], ins[0][3][[0, B - 1]]):
+            RD.GaussianDiffusionTrainer(mv, G10["beta_1"], G10["beta_T"], G10["T"])(ins[0][0][[0, B - 1]], ins[0][1][[0, B - 1]])
+        hook.remove()
+        out[f"{variant}/mean_max_softmax_level0"] = np.array([_mean_max_softmax(mv.downblocks[0].attn, cap["h"], [0, 1])])
+        for prec, dt in (("f32", torch.float32), ("f64", torch.float64)):
+            t0 = time.time()
+            m = copy.deepcopy(mv).to(dt).train()
+            trainer = RD.GaussianDiffusionTrainer(m, G10["beta_1"], G10["beta_T"], G10["T"])
+            opt = torch.optim.AdamW(m.parameters(), lr=G10["lr"], weight_decay=G10["weight_decay"])
+            cos = torch.optim.lr_scheduler.CosineAnnealingLR(optimizer=opt, T_max=G10["epoch"], eta_min=0, last_epoch=-1)
+            warm = RS.GradualWarmupScheduler(optimizer=opt, multiplier=G10["multiplier"], warm_epoch=G10["epoch"] // 10,
+                                             after_scheduler=cos)
+            params = dict(m.named_parameters())
+            rec = {"loss": [], "norm": [], "lr": []}
+            pre = f"{variant}/{prec}/"
+            for s, (x_0, labels, t, noise) in enumerate(ins):
+                opt.zero_grad()
+                rec["lr"].append(opt.param_groups[0]["lr"])
+                with _Feed(t, noise):
+                    loss = trainer(x_0.to(dt), labels).sum() / B ** 2.
+                loss.backward()
+                if s == 0:
+                    for n in G6B_NAMES:
+                        out[f"{pre}grad/{n}"] = _np(params[n].grad)
+                    for n in G6B_ROW_NAMES:
+                        out[f"{pre}gradrows/{n}"] = _np(params[n].grad[:4])
+                rec["norm"].append(torch.nn.utils.clip_grad_norm_(m.parameters(), G10["grad_clip"]).item())
+                rec["loss"].append(loss.item())
+                opt.step()
+                with warnings.catch_warnings():
+                    warnings.simplefilter("ignore")
+                    warm.step()
+                if s in (0, steps - 1):
+                    for n in G6B_NAMES:
+                        out[f"{pre}p{s + 1}/{n}"] = _np(params[n])
+                    for n in G6B_ROW_NAMES:
+                        out[f"{pre}p{s + 1}rows/{n}"] = _np(params[n][:4])
+                print(f"G10 {variant} {prec} step {s + 1}: loss {rec['loss'][-1]:.9g} norm {rec['norm'][-1]:.9g} "
+                      f"lr {rec['lr'][-1]:.6g} ({time.time() - t0:.0f} s)", flush=True)
+            for k, v in rec.items():
+                out[pre + k] = np.array(v, dtype=np.float64)
+            del m, trainer, opt, params
+    np.savez_compressed(os.path.join(OUT, "trainer_default32_b80.npz"), **g10_pack(out, p0))
+
+
+def g10_pack(out, p0):
+    """Shrink G10's record below 1 MiB without losing what the gates need.  Parameters are stored as their change from the
+    initial value (p0[variant][name]) -- steps of ~lr, so float32 keeps them to ~1e-12.  The float64 run is stored as its
+    difference from the fp32 run, in float32: r64 = r32 + (r64 - r32) is then exact to ~1e-8 of that difference.  Of the
+    large tensors' row slices the first row is kept, of the sinusoidal table the rows of the recorded time steps."""
+    res = {}
+    table = "init/time_embedding.timembedding.0.weight"
+    rows = np.unique(out["t"])
+    res["temb_t"], res["temb_rows"] = rows, out[table][rows]
+    for k, v in out.items():
+        parts = k.split("/")
+        if k == table or (len(parts) > 2 and parts[1] == "f64"):
+            continue
+        if len(parts) > 2 and parts[1] == "f32":
+            variant, kind, name = parts[0], parts[2], "/".join(parts[3:])
+            f64 = out[k.replace("/f32/", "/f64/", 1)]
+            if kind.endswith("rows"):           # row slices: the first output row
+                v, f64 = v[:1], f64[:1]
+            if kind.startswith("p"):            # p1, p1rows, p6, p6rows -> change from the initial value
+                init = p0[variant][name][:1] if kind.endswith("rows") else p0[variant][name]
+                res[f"{variant}/f32/d{kind}/{name}"] = (v.astype(np.float64) - init).astype(np.float32)
+                res[f"{variant}/f64-f32/d{kind}/{name}"] = (f64 - v.astype(np.float64)).astype(np.float32)
+            elif kind in ("grad", "gradrows"):
+                res[f"{variant}/f32/{kind}/{name}"] = v
+                res[f"{variant}/f64-f32/{kind}/{name}"] = (f64 - v.astype(np.float64)).astype(np.float32)
+            else:                               # loss, norm, lr: float64 both
+                res[k], res[k.replace("/f32/", "/f64/", 1)] = v, f64
+            continue
+        res[k] = v
+    res["stored_names"] = np.array([n for n in out["stored_names"] if f"init/{n}" != table])
+    return res
 
 
 def gen_lr_schedule():
@@ -496,6 +689,9 @@ def main():
         return
     if len(sys.argv) > 1 and sys.argv[1] == "g9":
         gen_main_defaults()
+        return
+    if len(sys.argv) > 1 and sys.argv[1] == "g10":
+        gen_trainer_default32_b80(RM, RD)
         return
     gen_schedules(RD)
     gen_modules(RM)

@@ -92,3 +92,32 @@ def assert_schedule_buffer(got, host, stored, what):
     assert np.array_equal(got, host), what
     if not np.array_equal(host, stored):
         assert (np.abs(host - stored) <= 4 * np.spacing(np.abs(stored))).all(), what
+
+
+def default32_trainer_model(UNet, peaked=False):
+    """G10 (tests/golden/trainer_default32_b80.npz): the default configuration at T = 500 with dropout 0 from G6b's seed recipe;
+    the tensors a host's CPU could round differently (sinusoidal table, label embedding, perturbed MHA biases) come from the
+    fixture, every tensor is then pinned by its checksum.  ``peaked``: the fixture's second variant (q and k rows of every
+    in_proj_weight times sqrt(3)).  Returns (model on the CPU in train mode, config dict, npz)."""
+    from oracle.gen_golden import g10_peaked_
+    d = np.load(os.path.join(GOLDEN, "trainer_default32_b80.npz"))
+    c = json.loads(bytes(d["cfg_json"]).decode())
+    torch.manual_seed(int(d["seed"][0]))
+    m = UNet(**c)
+    with torch.no_grad():
+        sd = m.state_dict()
+        for n in d["stored_names"]:
+            sd[str(n)].copy_(torch.from_numpy(d[f"init/{n}"]))
+        # the sinusoidal table: its low bits depend on the host's vectorised sin / cos (as in G6b: up to ~1e-4 at large
+        # positions); the rows the recorded time steps read are stored
+        table = "time_embedding.timembedding.0.weight"
+        idx, rows = torch.from_numpy(d["temb_t"]), torch.from_numpy(d["temb_rows"])
+        assert (sd[table][idx] - rows).abs().max().item() < 1e-3
+        sd[table][idx] = rows
+    names, sums = state_checksums(m.state_dict())
+    assert list(d["weight_names"]) == names
+    bad = [n for n, a, b in zip(names, sums, d["weight_checksums"]) if n != table and not np.array_equal(a, b)]
+    assert not bad, f"seed recipe no longer reproduces the reference init for {bad[:8]} ({len(bad)} tensors)"
+    if peaked:
+        g10_peaked_(m)
+    return m.train(), c, d

@@ -41,6 +41,9 @@ def leaf(t, dev=None):
     return t.requires_grad_(True)
 
 
+DEFAULT32_SPLIT_MIN_B = 24        # the cases from this batch up are the default run's: their forward must take the split kernel
+
+
 @pytest.mark.parametrize("k,C0,C1,cout,H,W,B,gn,vec,res", [
     (3, 32, 0, 64, 16, 16, 2, True, True, True),
     (3, 64, 32, 64, 12, 20, 2, True, False, False),     # concat input, group straddles nothing (96/32 = 3 per group)
@@ -52,6 +55,11 @@ def leaf(t, dev=None):
     (1, 128, 0, 384, 16, 16, 2, False, False, False),   # in-projection shape: the 1x1 weight-gradient kernel (Cout % 128 == 0)
     (1, 256, 128, 128, 8, 16, 2, False, False, True),   # concat shortcut 384 -> 128: three 128-channel chunks across the seam
     (1, 96, 64, 256, 8, 8, 1, False, False, False),     # 160 input channels: a partial last chunk, seam inside a chunk
+    # the default 32x32, batch-80 training run: batches large enough for the split-operand forward kernels (DEFAULT32_SPLIT_MIN_B)
+    (3, 256, 128, 256, 16, 16, 24, True, True, True),   # 16x16 skip concat: groups of 12 straddle the seam at 256
+    (3, 256, 256, 256, 4, 4, 48, True, True, False),    # 4x4 level: a plane smaller than one tile, dgrad / wgrad at B = 48
+    (3, 128, 0, 3, 32, 32, 48, True, False, False),     # the 128 -> 3 tail
+    (3, 256, 128, 128, 32, 32, 24, True, True, True),   # 32x32 skip concat 256|128 -> 128: wgrad3x3 with concat, large nsplit
 ])
 def test_fused_conv_backward(k, C0, C1, cout, H, W, B, gn, vec, res):
     g = torch.Generator().manual_seed(k * 100 + C0 + cout)
@@ -88,6 +96,13 @@ def test_fused_conv_backward(k, C0, C1, cout, H, W, B, gn, vec, res):
     y_ref, g_ref = run(None, ref_fn)
     y_hip, g_hip = run(DEV, hip_fn)
     close(y_hip, y_ref, rel=3e-5, what="fwd")
+    if B >= DEFAULT32_SPLIT_MIN_B and hdiff_amd.get_contraction_mode() == "bf16x3":
+        hdiff_amd.set_contraction_mode("f32")
+        try:
+            y_f32, _ = run(DEV, hip_fn)
+        finally:
+            hdiff_amd.set_contraction_mode("bf16x3")
+        assert not torch.equal(y_hip, y_f32), "the split-operand forward did not run"
     names = ["dx0", "dx1", "dW", "dbias", "dgamma", "dbeta", "dvec", "dres"]
     for n, a, r in zip(names, g_hip, g_ref):
         if r is not None:
@@ -123,6 +138,34 @@ def test_downsample_and_tconv_backward():
     close(uh, u, rel=3e-5, what="tconv fwd")
     for n, a, r in zip(["dx", "dwt", "dbt"], hip_in, ref_in):
         close(a.grad, r.grad, rel=1e-4, what="tconv " + n)
+
+
+def test_tconv_backward_default32_4x4():
+    """UpSample 4 -> 8 of the default 32x32, batch-80 run (256 channels) through _TConvFn: the four parity phases forward, their
+    weight gradients and the 5x5 stride-2 input gradient, against CPU autograd with the tolerances of
+    test_downsample_and_tconv_backward.  The training path packs split-operand weights only for identity output maps
+    (autograd._run_conv), so the phases run the fp32-input kernel in both modes: the forward must agree bit for bit."""
+    g = torch.Generator().manual_seed(480)
+    B, Cc, H, W = 80, 256, 4, 4
+    x = torch.randn(B, Cc, H, W, generator=g)
+    wt, bt = torch.randn(Cc, Cc, 5, 5, generator=g) / 40, torch.randn(Cc, generator=g)
+    du = torch.randn(B, Cc, 2 * H, 2 * W, generator=g)
+    ref_in = [leaf(t) for t in (x, wt, bt)]
+    u = F.conv_transpose2d(ref_in[0], ref_in[1], ref_in[2], stride=2, padding=2, output_padding=1)
+    u.backward(du)
+    hip_in = [leaf(t, DEV) for t in (x, wt, bt)]
+    uh = A._TConvFn.apply(*hip_in)
+    uh.backward(du.to(DEV))
+    close(uh, u, rel=3e-5, what="tconv fwd")
+    for n, a, r in zip(["dx", "dwt", "dbt"], hip_in, ref_in):
+        close(a.grad, r.grad, rel=1e-4, what="tconv " + n)
+    mode = hdiff_amd.get_contraction_mode()
+    hdiff_amd.set_contraction_mode("f32" if mode == "bf16x3" else "bf16x3")
+    try:
+        other = A._TConvFn.apply(*[t.detach() for t in hip_in])
+    finally:
+        hdiff_amd.set_contraction_mode(mode)
+    assert torch.equal(uh.detach(), other)
 
 
 def attention_ref(qkv, heads):

@@ -26,6 +26,13 @@ FWD = ["tests/test_gpu_ops.py::test_conv3x3_split_bf16_is_fp32_class",
        "tests/test_gpu_ops.py::test_conv1x1_split_bf16_is_fp32_class",
        "tests/test_gpu_ops.py::test_flash_attention_split_bf16_is_fp32_class"]
 BWD = ["tests/test_gpu_backward.py::test_attention_backward_fp16_pairs_error_class_every_pair"]
+# the shapes of the default 32x32, batch-80 training run (partial tiles, guarded epilogue): {test: parametrizations}, each must turn red
+DEFAULT32 = {"tests/test_gpu_ops.py::test_conv3x3_fp16_pairs_default32_shapes": 14,
+             "tests/test_gpu_ops.py::test_conv3x3_split_bf16_default32_upsample_conv": 2,
+             "tests/test_gpu_ops.py::test_upsample_phases_default32_shapes": 2,
+             "tests/test_gpu_ops.py::test_conv1x1_split_bf16_default32_shapes": 2,
+             "tests/test_gpu_ops.py::test_flash_attention_fp16_pairs_default32_level0": 1,
+             "tests/test_gpu_ops.py::test_attention_backward_fp16_pairs_default32_level0": 1}
 
 
 def _run(targets, lib=None):
@@ -51,8 +58,12 @@ def _mutants():
 
 def test_a_dropped_low_order_piece_product_turns_the_error_class_tests_red():
     mutant, mutant2 = _mutants()
-    rc, out, failed = _run(FWD + BWD, mutant)
+    rc, out, failed = _run(FWD + BWD + list(DEFAULT32), mutant)
     assert rc == 1, out[-3000:]                                               # tests ran, some failed (not a collection / load error)
+    for target, n in DEFAULT32.items():
+        name = target.split("::")[1]
+        red = [l for l in failed if l.split(" ")[1].split("[")[0].endswith("::" + name)]
+        assert len(red) == n, (name, red, out[-2000:])
     conv = [l for l in failed if "test_conv3x3_split_bf16_is_fp32_class" in l]
     att_pre = [l for l in failed if "test_flash_attention_split_bf16_is_fp32_class" in l and "pre-split" in l]
     assert len(conv) == 4, (conv, out[-2000:])                               # every convolution shape
@@ -73,5 +84,5 @@ def test_a_dropped_low_order_piece_product_turns_the_error_class_tests_red():
     bwd = [l for l in failed if "test_attention_backward_fp16_pairs_error_class_every_pair" in l]
     assert len(bwd) == 2, (bwd, out[-2000:])
     # and the same selection is green on the real library (the suite runs it anyway; here: same process environment)
-    rc, out, failed = _run(FWD + BWD)
+    rc, out, failed = _run(FWD + BWD + list(DEFAULT32))
     assert rc == 0, out[-3000:]

@@ -5,6 +5,8 @@ Tolerances (fp32 path; exact-fp32 MFMA, so only summation order differs from the
 """
 import ctypes as C
 import math
+import os
+import sys
 
 import numpy as np
 import pytest
@@ -12,6 +14,7 @@ import torch
 import torch.nn.functional as F
 
 pytestmark = pytest.mark.gpu
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))      # _attn_bwd_cases
 
 import hdiff_amd  # noqa: E402
 from hdiff_amd import _capi, engine as E  # noqa: E402
@@ -89,7 +92,10 @@ def test_conv1x1_split_bf16_is_fp32_class(C0, C1, cout, S, B, bf16x3_mode):
     """conv1x1_x3.hip: the full-resolution 1x1 convs (attention projections, shortcuts) on bf16 triples in the bf16x3 mode --
     operands split in registers, no LDS.  Error against float64 in the class of the fp32-MFMA kernel's (conv1x1_direct.hip);
     concat input with the seam on a 16-channel boundary, a channel tail (cout 40), bias + vector + residual epilogue."""
-    lib = bf16x3_mode
+    _check_conv1x1_split(C0, C1, cout, S, B, bf16x3_mode)
+
+
+def _check_conv1x1_split(C0, C1, cout, S, B, lib):
     g = torch.Generator().manual_seed(C0 + 3 * C1 + cout)
     cin = C0 + C1
     x0 = torch.randn(B, C0, S, S, generator=g) * torch.exp(torch.randn(1, C0, 1, 1, generator=g))
@@ -450,7 +456,10 @@ def test_flash_attention_split_bf16_overflow_falls_back(workspace, bf16x3_mode):
 def test_conv3x3_split_bf16_is_fp32_class(C0, C1, cout, H, W, B, use_gn, bf16x3_mode):
     """HDIFF_CONTRACT_BF16X3 for the 3x3 convolutions (conv3x3_x3.hip): error against float64 of the same class as the
     fp32-MFMA kernel's, with the fused GroupNorm/Swish prologue, concat input, bias + vector + residual epilogue."""
-    lib = bf16x3_mode
+    _check_conv3x3_split(C0, C1, cout, H, W, B, use_gn, bf16x3_mode)
+
+
+def _check_conv3x3_split(C0, C1, cout, H, W, B, use_gn, lib):
     g = torch.Generator().manual_seed(C0 * 7 + cout + H)
     cin = C0 + C1
     x0 = torch.randn(B, C0, H, W, generator=g)
@@ -472,6 +481,7 @@ def test_conv3x3_split_bf16_is_fp32_class(C0, C1, cout, H, W, B, use_gn, bf16x3_
     assert not torch.equal(got_x3, got_f32), "the split-bf16 kernel did not run"
     close(got_x3, want.float(), rel=1e-5, what="conv3x3 split-bf16")
     rms = lambda t: (t.double().cpu() - want).pow(2).mean().sqrt().item()
+    print(f"conv3x3 {cin}->{cout} {H}x{W} B={B}: rms vs float64: triples {rms(got_x3):.3e}, fp32-MFMA {rms(got_f32):.3e}")
     assert rms(got_x3) <= 1.5 * rms(got_f32) + 1e-12, (rms(got_x3), rms(got_f32))
 
 
@@ -515,7 +525,15 @@ def test_conv3x3_fp16_pairs_is_fp32_class(C0, C1, cout, H, W, B, bf16x3_mode):
     two fixed by the GroupNorm weights (three products instead of six).  Error against float64 in the class of the fp32-MFMA
     kernel's (the bf16-triple kernel's gate) and not above the bf16-triple kernel's own; concat input, channels with very
     different scales and offsets, bias + vector + residual epilogue."""
-    lib = bf16x3_mode
+    _check_conv3x3_pairs(C0, C1, cout, H, W, B, bf16x3_mode)
+
+
+def _split_launch_blocks(cout, H, W, B):
+    """the workgroup count by which the conv dispatcher (conv_igemm.hip, is_x3_conv) picks the split-operand 3x3 kernel (>= 192)"""
+    return -(-W // 32) * -(-H // 8) * -(-cout // 64) * B
+
+
+def _check_conv3x3_pairs(C0, C1, cout, H, W, B, lib):
     g = torch.Generator().manual_seed(C0 * 5 + cout + H)
     cin = C0 + C1
     chan = lambda c: torch.exp(torch.randn(1, c, 1, 1, generator=g) * 1.5)
@@ -538,6 +556,109 @@ def test_conv3x3_fp16_pairs_is_fp32_class(C0, C1, cout, H, W, B, bf16x3_mode):
     assert rms(got_h2) <= 1.5 * rms(got_f32) + 1e-12, (rms(got_h2), rms(got_f32))
     assert rms(got_h2) <= 1.25 * rms(got_x3) + 1e-12, (rms(got_h2), rms(got_x3))
     assert worst(got_h2) <= 2.0 * worst(got_f32) + 1e-12, (worst(got_h2), worst(got_f32))
+
+
+# MainCondition.py's default training run (32x32, B = 80, ch 128, ch_mult [1, 2, 2, 2]): GroupNorm + Swish + 3x3 at the 16x16,
+# 8x8 and 4x4 levels and the middle (128 -> 256, 256 -> 256, skip concats 256|256 and 256|128: groups of 12 channels straddle the
+# seam at 256), and the 128 -> 3 tail at 32x32.  Planes narrower than the 32 x 8 tile and a channel tail below 64 send every output
+# through the guarded epilogue; 20x40 mixes full and partial tiles in both directions.  B is the smallest that reaches the split
+# kernel (>= 192 workgroups), except one B = 80 case at 4x4 and the tail at B = 80.
+DEFAULT32_PAIRS = [(128, 0, 256, 16, 16, 24), (256, 0, 256, 16, 16, 24), (256, 256, 256, 16, 16, 24), (256, 128, 256, 16, 16, 24),
+                   (128, 0, 256, 8, 8, 48), (256, 0, 256, 8, 8, 48), (256, 256, 256, 8, 8, 48), (256, 128, 256, 8, 8, 48),
+                   (128, 0, 256, 4, 4, 48), (256, 0, 256, 4, 4, 48), (256, 256, 256, 4, 4, 48), (256, 128, 256, 4, 4, 80),
+                   (128, 0, 3, 32, 32, 80), (128, 0, 256, 20, 40, 8)]
+
+
+@pytest.mark.parametrize("C0,C1,cout,H,W,B", DEFAULT32_PAIRS)
+def test_conv3x3_fp16_pairs_default32_shapes(C0, C1, cout, H, W, B, bf16x3_mode):
+    """The fp16-pair 3x3 kernel at the shapes of the default 32x32, batch-80 training run, same gates as
+    test_conv3x3_fp16_pairs_is_fp32_class (<= 1e-5 of max|ref|; rms <= 1.5x fp32-MFMA and <= 1.25x triples; worst <= 2x fp32)."""
+    blocks = _split_launch_blocks(cout, H, W, B)
+    assert blocks >= 192 and (B == 80 or _split_launch_blocks(cout, H, W, B - 1) < 192), blocks
+    assert H % 8 or W % 32 or cout % 64, "not a partial-tile shape"
+    _check_conv3x3_pairs(C0, C1, cout, H, W, B, bf16x3_mode)
+
+
+@pytest.mark.parametrize("H,B", [(16, 24), (8, 80)])
+def test_conv3x3_split_bf16_default32_upsample_conv(H, B, bf16x3_mode):
+    """UpSample.c (ModelCondition.py:87) of the default run: a 256 -> 256 3x3 conv with no GroupNorm in front on the bf16-triple
+    kernel, at 16x16 and 8x8 (planes smaller than one 32 x 8 tile: the guarded epilogue).  Same gates as
+    test_conv3x3_split_bf16_is_fp32_class."""
+    assert _split_launch_blocks(256, H, H, B) >= 192
+    _check_conv3x3_split(256, 0, 256, H, H, B, False, bf16x3_mode)
+
+
+@pytest.mark.parametrize("H,B", [(4, 80), (8, 48)])
+def test_upsample_phases_default32_shapes(H, B, bf16x3_mode):
+    """UpSample 4 -> 8 and 8 -> 16 of the default run (256 channels): the four transposed-conv phases from inputs smaller than one
+    tile on the bf16-triple kernel (output map), then UpSample.c; against float64 conv_transpose2d(stride 2, padding 2,
+    output_padding 1) + conv2d.  Same gates as test_upsample_phases_on_the_split_bf16_kernel."""
+    assert _split_launch_blocks(256, H, H, B) >= 192
+    _check_upsample_phases(256, H, H, B, bf16x3_mode)
+
+
+@pytest.mark.parametrize("C0,C1,cout", [(128, 0, 384), (256, 128, 128)])
+def test_conv1x1_split_bf16_default32_shapes(C0, C1, cout, bf16x3_mode):
+    """The 32x32 level's 1x1 convs at B = 80 (HW = 1024): the attention in-projection 128 -> 384 and the concat shortcut
+    256|128 -> 128 on conv1x1_x3.hip.  Same gates as test_conv1x1_split_bf16_is_fp32_class."""
+    _check_conv1x1_split(C0, C1, cout, 32, 80, bf16x3_mode)
+
+
+# (sample, head) pairs checked against float64 at B = 80: every head of sample 0, the last sample, and a few in between
+DEFAULT32_ATTN_PAIRS = [(0, h) for h in range(8)] + [(79, 0), (79, 7), (40, 3), (17, 5)]
+
+
+def _attn_pairs_ref(qkv, heads, pairs):
+    """float64 attention output of the listed (sample, head) pairs: [npairs, d, L]"""
+    B, C3, L = qkv.shape
+    Cc = C3 // 3
+    d = Cc // heads
+    out = []
+    for b, h in pairs:
+        q, k, v = [qkv[b, i * Cc + h * d:i * Cc + (h + 1) * d].double() for i in range(3)]
+        p = torch.softmax(q.t() @ k / math.sqrt(d), dim=-1)
+        out.append((p @ v.t()).t())
+    return torch.stack(out)
+
+
+def test_flash_attention_fp16_pairs_default32_level0(bf16x3_mode):
+    """The 32x32 level's attention of the default run: L = 1024, d_head 16, B = 80 (640 (sample, head) pairs), the fp16-pair
+    kernel the training forward runs (with a workspace).  Against float64 on a subset of pairs, the gates of
+    test_flash_attention_split_bf16_is_fp32_class: <= 2e-5 of max|ref|, rms <= 1.25x and worst <= 2x the fp32-MFMA kernel's."""
+    lib = bf16x3_mode
+    heads, d, L, B = 8, 16, 1024, 80
+    g = torch.Generator().manual_seed(1024 + B)
+    qkv = torch.randn(B, 3 * heads * d, L, generator=g) * 1.3
+    o_h2, _ = _flash(lib, qkv, heads, workspace=True)
+    _capi.check(lib.hdiff_set_contraction_mode(0))
+    o_f32, _ = _flash(lib, qkv, heads)
+    _capi.check(lib.hdiff_set_contraction_mode(1))
+    assert not torch.equal(o_h2, o_f32), "the fp16-pair kernel did not run"
+    pick = lambda o: torch.stack([o[b, h * d:(h + 1) * d] for b, h in DEFAULT32_ATTN_PAIRS]).cpu()
+    ref = _attn_pairs_ref(qkv, heads, DEFAULT32_ATTN_PAIRS)
+    close(pick(o_h2), ref.float(), rel=2e-5, abs_=2e-6, what="fp16-pair attention L=1024 B=80")
+    rms = lambda t: (pick(t).double() - ref).pow(2).mean().sqrt().item()
+    worst = lambda t: (pick(t).double() - ref).abs().max().item()
+    print(f"attention d16 L1024 B80: rms pairs {rms(o_h2):.3e} fp32-MFMA {rms(o_f32):.3e}; worst {worst(o_h2):.3e} {worst(o_f32):.3e}")
+    assert rms(o_h2) <= 1.25 * rms(o_f32) + 1e-12, (rms(o_h2), rms(o_f32))
+    assert worst(o_h2) <= 2.0 * worst(o_f32) + 1e-12, (worst(o_h2), worst(o_f32))
+
+
+def test_attention_backward_fp16_pairs_default32_level0(bf16x3_mode):
+    """The backward of the same attention (L = 1024, d_head 16, B = 80) against float64 on the same subset of pairs, with the gates of
+    test_attention_backward_fp16_pairs_error_class_every_pair: rms <= 1.25x and worst <= 3x the fp32-input kernel's over the
+    subset, and per pair rms <= 1.25x, worst <= 4x."""
+    import _attn_bwd_cases as K
+    g = torch.Generator().manual_seed(1024 + 80 + 1)
+    qkv, d_o = K.make_case("plain", 16, 1024, 80, 8, g)
+    st = K.error_stats(bf16x3_mode, qkv.to(DEV), d_o.to(DEV), 8, pairs=DEFAULT32_ATTN_PAIRS)
+    for name, s in st.items():
+        print(f"attention bwd d16 L1024 B80 {name}: rms {s['rms'][0]:.3e} vs fp32 {s['rms'][1]:.3e}, "
+              f"worst {s['worst'][0]:.3e} vs {s['worst'][1]:.3e}")
+        assert s["rms"][0] <= 1.25 * s["rms"][1], (name, s["rms"])
+        assert s["worst"][0] <= 3.0 * s["worst"][1], (name, s["worst"])
+        for (b, h, r2, r0, w2, w0, mag) in s["pair"]:
+            assert r2 <= 1.25 * r0 and w2 <= 4.0 * w0, (name, b, h, r2, r0, w2, w0)
 
 
 @pytest.mark.parametrize("name", ["lone-spike", "huge-gamma", "tiny-gamma", "huge-weights", "tiny-weights"])
@@ -776,7 +897,10 @@ def test_upsample_phases_on_the_split_bf16_kernel(Cc, H, W, B, bf16x3_mode):
     """UpSample.forward (ModelCondition.py:85-89): ConvTranspose2d(C, C, 5, 2, 2, 1) as four output-parity phases + Conv3x3.
     At these sizes every phase launch is large enough for the split-bf16 kernel (tap lists + output map, conv3x3_x3.hip):
     it must differ from the fp32-mode result (another program ran) and be fp32-class against float64."""
-    lib = bf16x3_mode
+    _check_upsample_phases(Cc, H, W, B, bf16x3_mode)
+
+
+def _check_upsample_phases(Cc, H, W, B, lib):
     g = torch.Generator().manual_seed(Cc + H)
     x = torch.randn(B, Cc, H, W, generator=g)
     P = {"u.t.weight": torch.randn(Cc, Cc, 5, 5, generator=g) / math.sqrt(Cc * 6.25), "u.t.bias": torch.randn(Cc, generator=g),
@@ -801,4 +925,5 @@ def test_upsample_phases_on_the_split_bf16_kernel(Cc, H, W, B, bf16x3_mode):
     want = F.conv2d(u, P["u.c.weight"].double(), P["u.c.bias"].double(), padding=1)
     close(got_x3, want.float(), rel=1e-5, what="upsample split-bf16")
     rms = lambda t: (t.double().cpu() - want).pow(2).mean().sqrt().item()
+    print(f"upsample {Cc} from {H}x{W} B={B}: rms vs float64: triples {rms(got_x3):.3e}, fp32-MFMA {rms(got_f32):.3e}")
     assert rms(got_x3) <= 1.5 * rms(got_f32) + 1e-12, (rms(got_x3), rms(got_f32))

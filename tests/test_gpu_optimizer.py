@@ -105,3 +105,38 @@ def test_adamw_refuses_cpu_parameters_and_works_with_the_harness_schedulers():
     assert lrs[0] > 1e-4 and len(set(lrs)) > 1
     sd = opt.state_dict()
     assert set(sd["state"][0].keys()) == {"step", "exp_avg", "exp_avg_sq"}       # torch.optim.AdamW's state layout
+
+
+@pytest.mark.parametrize("bad", [float("nan"), float("inf")], ids=["nan", "inf"])
+def test_clip_with_a_non_finite_gradient_matches_torch(bad):
+    """One non-finite gradient element, through clip_grad_norm_(params, 1.0) + torch.optim.AdamW and through the native tail.
+    NaN: the total norm is NaN, torch.clamp keeps the NaN coefficient, so EVERY gradient and then every parameter is NaN (a coefficient
+    of 1 would corrupt only the NaN element and let training go on silently).  inf: the norm is inf, the coefficient 0, so the gradients
+    are NaN at the inf element (inf * 0) and 0 elsewhere, and only that parameter turns NaN; the others take torch's decay-only step."""
+    pa, pb = _pair(5)
+    g = torch.Generator().manual_seed(6)
+    for i, (x, y) in enumerate(zip(pa, pb)):
+        gr = torch.randn(x.shape, generator=g)
+        if i == 3:
+            gr[1234] = bad
+        x.grad = gr.to(DEV); y.grad = gr.to(DEV).clone()
+    ours = HO.AdamW(pa, lr=1e-3, weight_decay=1e-4)
+    ref = torch.optim.AdamW(pb, lr=1e-3, weight_decay=1e-4)
+    want = torch.nn.utils.clip_grad_norm_(pb, 1.0)
+    ref.step()
+    got = ours.step(max_grad_norm=1.0)
+    if bad != bad:
+        assert torch.isnan(got) and torch.isnan(want)
+        assert all(torch.isnan(y.grad).all() and torch.isnan(y.detach()).all() for y in pb), "torch's behaviour changed"
+    else:
+        assert torch.isinf(got) and torch.isinf(want)
+    for i, (x, y) in enumerate(zip(pa, pb)):
+        assert torch.equal(torch.isnan(x.grad), torch.isnan(y.grad)), i
+        assert torch.equal(torch.isnan(x.detach()), torch.isnan(y.detach())), i
+        assert torch.equal(x.grad[~torch.isnan(y.grad)], y.grad[~torch.isnan(y.grad)]), i
+        fin = ~torch.isnan(y.detach())
+        if fin.any():
+            err = (x.detach()[fin] - y.detach()[fin]).abs().max().item()
+            assert err <= 1e-6 * max(1e-3, y.detach()[fin].abs().max().item()), (i, err)
+    if bad == float("inf"):
+        assert torch.isnan(pa[3].detach()[1234]) and int(torch.isnan(pa[3].detach()).sum()) == 1

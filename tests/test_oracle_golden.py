@@ -199,3 +199,37 @@ def test_oracle_default_model_loss_and_gradients_against_reference_golden():
         if key.startswith("gradrows/"):
             got = got[:4]
         assert ((got - ref).abs().max() / ref.abs().max()).item() < 2e-4, key
+
+
+def test_g10_inputs_model_and_schedule_reproduce_the_fixture():
+    """G10 (trainer_default32_b80.npz) stores checksums instead of its inputs: rebuilding x_0 / noise / labels / t from the recipe
+    (oracle.gen_golden.g10_inputs, torch.rand / randint only) reproduces them bit for bit, with the edges the recipe promises;
+    the seed recipe reproduces the reference's initial weights; the package's GradualWarmupScheduler + CosineAnnealingLR,
+    stepped once per optimizer step, gives the recorded learning rates."""
+    import hdiff_amd  # noqa: F401
+    from golden_models import default32_trainer_model
+    from hdiff_amd.DiffusionFreeGuidence.ModelCondition import UNet
+    from hdiff_amd.Scheduler import GradualWarmupScheduler
+    from oracle.gen_golden import bit_checksum, g10_inputs
+    d = load("trainer_default32_b80.npz")
+    r = json.loads(bytes(d["recipe_json"]).decode())
+    for s in range(r["steps"]):
+        x_0, labels, t, noise = g10_inputs(s)
+        assert x_0.shape == noise.shape == (r["B"], 3, r["H"], r["H"])
+        assert [bit_checksum(x_0), bit_checksum(noise)] == d["input_checksums"][s].tolist(), s
+        assert np.array_equal(t.numpy(), d["t"][s]) and np.array_equal(labels.numpy(), d["labels"][s]), s
+    assert (d["labels"][r["zero_label_step"]] == 0).all() and (np.delete(d["labels"], r["zero_label_step"], 0) > 0).all()
+    assert d["t"][0, 0] == 0 and d["t"][0, -1] == r["T"] - 1
+    assert d["peaked/mean_max_softmax_level0"][0] > 2 * d["plain/mean_max_softmax_level0"][0]
+    default32_trainer_model(UNet)                      # asserts the weight checksums
+    p = torch.nn.Parameter(torch.zeros(1))
+    opt = torch.optim.AdamW([p], lr=r["lr"], weight_decay=r["weight_decay"])
+    cos = torch.optim.lr_scheduler.CosineAnnealingLR(optimizer=opt, T_max=r["epoch"], eta_min=0, last_epoch=-1)
+    warm = GradualWarmupScheduler(optimizer=opt, multiplier=r["multiplier"], warm_epoch=r["epoch"] // 10, after_scheduler=cos)
+    lrs = []
+    for _ in range(r["steps"]):
+        lrs.append(opt.param_groups[0]["lr"])
+        opt.step()
+        warm.step()
+    assert lrs == d["plain/f32/lr"].tolist() == d["peaked/f64/lr"].tolist()
+    assert len(set(lrs)) == r["steps"]
