@@ -49,6 +49,18 @@ class ConvDesc(C.Structure):
     ]
 
 
+class MsssimDesc(C.Structure):
+    """hdiff_msssim_desc (include/hdiff.h)."""
+    MAX_PAIRS, MAX_SCALES, MAX_WINDOW = 15, 5, 33
+    _fields_ = [
+        ("B", C.c_int), ("C", C.c_int), ("H", C.c_int), ("W", C.c_int), ("nscales", C.c_int), ("window", C.c_int),
+        ("weights", C.POINTER(C.c_float)), ("npairs", C.c_int),
+        ("pair_chan", C.c_int * 15), ("pair_scale", C.c_int * 15), ("pair_cs_pow", C.c_int * 15), ("pair_l_pow", C.c_int * 15),
+        ("l1_scale", C.c_int), ("C1", C.c_float), ("C2", C.c_float), ("alpha", C.c_float), ("compensation", C.c_float),
+        ("data_range", C.c_float), ("mean", C.c_int),
+    ]
+
+
 class WgradDesc(C.Structure):
     _fields_ = [
         ("x0", C.c_void_p), ("x1", C.c_void_p), ("C0", C.c_int), ("C1", C.c_int),
@@ -130,6 +142,9 @@ _PROTOS = {
     "hdiff_train_b_loss_workspace": (C.c_int, [C.c_int64, C.POINTER(C.c_int64)]),
     "hdiff_train_b_loss_fwd": (C.c_int, [C.c_void_p] * 7 + [C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 5),
     "hdiff_train_b_loss_bwd": (C.c_int, [C.c_void_p] * 7 + [C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 5),
+    "hdiff_msssim_l1_workspace": (C.c_int, [C.POINTER(MsssimDesc), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "hdiff_msssim_l1_fwd": (C.c_int, [C.POINTER(MsssimDesc)] + [C.c_void_p] * 6),
+    "hdiff_msssim_l1_bwd": (C.c_int, [C.POINTER(MsssimDesc)] + [C.c_void_p] * 7),
     "hdiff_avgpool_global_bwd": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "hdiff_resize_nearest_bwd": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "hdiff_concat2": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.c_void_p]),

@@ -15,6 +15,7 @@ emits) with its hand-written backward:
   _StridedConvFn / _PoolFn / _ResizeFn / _TrainTailFn   the second tree (DynamicUNet, diffusion/Model.py): the image encoder's
                stride-2 convs (dgrad = 4 output-parity phases), its global average pool, the skip resize, and the trainer's
                fused loss tail (mse, y0_pred, colour term; train_b_ops.hip)
+  _MsssimL1Fn  the MS-SSIM + L1 loss of the second tree's trainer (msssim.hip); differentiated in the prediction only
 
 PyTorch provides the autograd graph, gradient accumulation and the optimizer; no arithmetic of the model runs in ATen.
 """
@@ -745,6 +746,132 @@ def train_b_loss_tail(noise_pred, noise, y_t, gt, t, sqrt_ab, sqrt_1mab):
     """(mse, y0_pred, col_loss) of GaussianDiffusionTrainer.forward; sqrt_ab / sqrt_1mab are fp32 tables of length T."""
     return _TrainTailFn.apply(noise_pred, noise.contiguous(), y_t.contiguous(), gt.contiguous(), t.contiguous(),
                               sqrt_ab.contiguous(), sqrt_1mab.contiguous())
+
+
+class MsssimConfig:
+    """Validated settings of the MS-SSIM + L1 loss: the host weight table and the pair table of ``hdiff_msssim_desc``."""
+
+    def __init__(self, layout, sigmas, data_range, K, alpha, compensation, reduction):
+        import numpy as np
+        if reduction not in ("mean", "sum"):
+            raise ValueError(f"hdiff: MS-SSIM + L1 reduction {reduction!r} is not supported; the limit is 'mean' or 'sum' "
+                             "(the per-pixel map, 'none', is never written out)")
+        if layout not in ("kornia", "per_channel"):
+            raise ValueError(f"hdiff: MS-SSIM layout {layout!r}; 'kornia' or 'per_channel'")
+        sig = [float(v) for v in sigmas]
+        M = _capi.MsssimDesc
+        if not 1 <= len(sig) <= M.MAX_SCALES:
+            raise ValueError(f"hdiff: MS-SSIM takes 1 to {M.MAX_SCALES} sigmas, got {len(sig)}")
+        if any(v <= 0 for v in sig) or any(b <= a for a, b in zip(sig, sig[1:])):
+            raise ValueError(f"hdiff: MS-SSIM sigmas must be positive and increasing, got {tuple(sig)}")
+        if sig[-1] > 8.0:
+            raise ValueError(f"hdiff: MS-SSIM sigma_max {sig[-1]} exceeds the limit of 8 (a window of {M.MAX_WINDOW} taps)")
+        if not float(data_range) > 0:
+            raise ValueError("hdiff: MS-SSIM data_range must be positive")
+        n = len(sig)
+        half = int(4 * sig[-1] + 1) // 2
+        k = np.arange(-half, half + 1, dtype=np.float64)
+        w = np.stack([np.exp(-k * k / (2.0 * v * v)) for v in sig])
+        w = (w / w.sum(axis=1, keepdims=True)).astype(np.float32)          # float64, normalised, then rounded to fp32
+        self.window = 2 * half + 1
+        self.weights = (C.c_float * w.size)(*w.reshape(-1).tolist())
+        if layout == "kornia":       # 3n maps; map o filters colour channel o // n with sigmas[o // 3]; lM over the last three
+            maps = [(o // n, o // 3, 1 if o >= 3 * n - 3 else 0) for o in range(3 * n)]
+        else:                        # every channel at every scale; lM over the three channels at sigma_max
+            maps = [(c, s, 1 if s == n - 1 else 0) for c in range(3) for s in range(n)]
+        pairs = {}
+        for c, s_, lp in maps:
+            e = pairs.setdefault((c, s_), [0, 0])
+            e[0] += 1
+            e[1] += lp
+        self.pairs = [(c, s_, m, lp) for (c, s_), (m, lp) in sorted(pairs.items())]
+        self.layout, self.sigmas, self.reduction = layout, tuple(sig), reduction
+        self.C1, self.C2 = (float(K[0]) * float(data_range)) ** 2, (float(K[1]) * float(data_range)) ** 2
+        self.alpha, self.compensation, self.data_range = float(alpha), float(compensation), float(data_range)
+
+    def desc(self, B: int, Cc: int, H: int, W: int) -> "_capi.MsssimDesc":
+        d = _capi.MsssimDesc()
+        d.B, d.C, d.H, d.W = B, Cc, H, W
+        d.nscales, d.window = len(self.sigmas), self.window
+        d.weights = C.cast(self.weights, C.POINTER(C.c_float))
+        d.npairs = len(self.pairs)
+        for i, (c, s_, m, lp) in enumerate(self.pairs):
+            d.pair_chan[i], d.pair_scale[i], d.pair_cs_pow[i], d.pair_l_pow[i] = c, s_, m, lp
+        d.l1_scale = len(self.sigmas) - 1
+        d.C1, d.C2, d.alpha, d.compensation, d.data_range = self.C1, self.C2, self.alpha, self.compensation, self.data_range
+        d.mean = 1 if self.reduction == "mean" else 0
+        return d
+
+
+def msssim_config(layout="kornia", sigmas=(0.5, 1.0, 2.0, 4.0, 8.0), data_range=1.0, K=(0.01, 0.03), alpha=0.025,
+                  compensation=200.0, reduction="mean") -> MsssimConfig:
+    return MsssimConfig(layout, sigmas, data_range, K, alpha, compensation, reduction)
+
+
+class _MsssimL1Fn(Function):
+    """MS-SSIM + L1 (msssim.hip): forward = moments, per-pixel loss, fixed-order sum (3 launches); backward = coefficient maps
+    from the saved moments, then the adjoint filters (2 launches)."""
+
+    @staticmethod
+    def forward(ctx, x, y, cfg):
+        lib = _capi.lib()
+        B, Cc, H, W = (int(v) for v in x.shape)
+        dev = x.device
+        d = cfg.desc(B, Cc, H, W)
+        saved_b, scratch_b = C.c_int64(0), C.c_int64(0)
+        _capi.check(lib.hdiff_msssim_l1_workspace(C.byref(d), C.byref(saved_b), C.byref(scratch_b)), "msssim_l1_workspace")
+        saved = torch.empty(saved_b.value // 4, dtype=torch.float32, device=dev)
+        scratch = torch.empty((scratch_b.value + 7) // 8, dtype=torch.float64, device=dev)
+        loss = torch.empty((), device=dev)
+        _capi.check(lib.hdiff_msssim_l1_fwd(C.byref(d), x.data_ptr(), y.data_ptr(), loss.data_ptr(), saved.data_ptr(),
+                                            scratch.data_ptr(), _stream(dev)), "msssim_l1_fwd")
+        ctx.cfg, ctx.scratch_bytes = cfg, scratch_b.value
+        ctx.save_for_backward(x, y, saved)
+        return loss
+
+    @staticmethod
+    def backward(ctx, d_loss):
+        x, y, saved = ctx.saved_tensors
+        if not ctx.needs_input_grad[0]:
+            return None, None, None
+        B, Cc, H, W = (int(v) for v in x.shape)
+        dev = x.device
+        d = ctx.cfg.desc(B, Cc, H, W)
+        d_loss = d_loss.to(torch.float32).contiguous()
+        scratch = torch.empty((ctx.scratch_bytes + 7) // 8, dtype=torch.float64, device=dev)
+        dx = torch.empty_like(x)
+        _capi.check(_capi.lib().hdiff_msssim_l1_bwd(C.byref(d), x.data_ptr(), y.data_ptr(), d_loss.data_ptr(), saved.data_ptr(),
+                                                    scratch.data_ptr(), dx.data_ptr(), _stream(dev)), "msssim_l1_bwd")
+        return dx, None, None
+
+
+def msssim_l1_loss(x, y, *, layout="kornia", sigmas=(0.5, 1.0, 2.0, 4.0, 8.0), data_range=1.0, K=(0.01, 0.03), alpha=0.025,
+                   compensation=200.0, reduction="mean", config: Optional[MsssimConfig] = None):
+    """MS-SSIM + L1 loss of a prediction ``x`` against a target ``y``, both [B, 3, H, W] fp32 on the GPU (any H, W >= 1).
+
+    With g_s the 1-D Gaussian exp(-k^2 / (2 s^2)), k = -(n // 2) .. n // 2, n = int(4 sigma_max + 1), normalised to sum 1, and
+    G_s * a the zero-padded 2-D correlation of a plane with g_s g_s^T: for a pair (channel c, scale s), mu_x = G*x_c, mu_y = G*y_c,
+    s_x = G*(x_c^2) - mu_x^2, s_y likewise, s_xy = G*(x_c y_c) - mu_x mu_y, l = (2 mu_x mu_y + C1) / (mu_x^2 + mu_y^2 + C1),
+    cs = (2 s_xy + C2) / (s_x + s_y + C2), C1 = (K[0] data_range)^2, C2 = (K[1] data_range)^2.  Per pixel, ms = 1 - lM PIcs with
+    PIcs the product of cs over the layout's 15 maps and lM the product of l over three of them; l1 = the channel mean of
+    G_{sigma_max} * |x_c - y_c|; loss = compensation (alpha ms + (1 - alpha) l1 / data_range), then 'mean' or 'sum' over [B, H, W].
+    ``layout``: 'kornia' (map o reads channel o // 5 at sigmas[o // 3], lM = l of the last three maps) or 'per_channel' (every
+    channel at every scale, lM over the channels at sigma_max).  Only ``x`` is differentiated."""
+    cfg = config if config is not None else msssim_config(layout, sigmas, data_range, K, alpha, compensation, reduction)
+    E.require_gpu_tensor(x, "input")
+    E.require_gpu_tensor(y, "target")
+    if y.requires_grad and torch.is_grad_enabled():
+        raise RuntimeError("hdiff: msssim_l1_loss differentiates only the prediction (the first argument); the target requires "
+                           "grad -- detach it")
+    if x.dtype != torch.float32 or y.dtype != torch.float32:
+        raise RuntimeError(f"hdiff: msssim_l1_loss computes in fp32; got {x.dtype} and {y.dtype} (the limit is float32 images)")
+    if x.dim() != 4 or tuple(x.shape) != tuple(y.shape) or int(x.shape[1]) != 3:
+        raise RuntimeError(f"hdiff: msssim_l1_loss takes two [B, 3, H, W] images (the limit is 3 channels), got {tuple(x.shape)} "
+                           f"and {tuple(y.shape)}")
+    if x.device != y.device:
+        raise RuntimeError("hdiff: msssim_l1_loss: input and target live on different devices")
+    with torch.cuda.device(x.device):
+        return _MsssimL1Fn.apply(x, y.detach(), cfg)
 
 
 def cond_image_embedding(ce, label):

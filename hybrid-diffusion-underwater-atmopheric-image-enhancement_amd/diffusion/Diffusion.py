@@ -15,9 +15,10 @@ Kept as written in the reference, on purpose:
 
 Trainer underneath: q_sample and the 3 + 3 channel concat are HIP launches, the DynamicUNet runs its autograd path
 (``autograd.dyn_unet_forward_with_grad``) and the loss tail -- the squared error, ``y_0_pred`` and the angular-colour term,
-and their joint backward -- is one fused kernel pair (``csrc/train_b_ops.hip``).  The reference's pretrained DINOv2
-perceptual loss and kornia MS-SSIM are not part of this package: they are passed in as callables (``dino_loss=``,
-``msssim_loss=``); a term without one is returned as zero and left out of ``loss``.
+and their joint backward -- is one fused kernel pair (``csrc/train_b_ops.hip``).  The reference's two further terms are passed in as
+callables (``dino_loss=``, ``msssim_loss=``); a term without one is returned as zero and left out of ``loss``.  The pretrained
+DINOv2 perceptual loss is not part of this package.  The MS-SSIM term is: ``Loss.loss.MSSSIMLoss()`` (hand-written kernels,
+``csrc/msssim.hip``) is what to pass as ``msssim_loss=``; nothing here imports kornia.
 """
 from __future__ import annotations
 
@@ -48,8 +49,9 @@ class GaussianDiffusionTrainer(nn.Module):
     """forward(gt_images, input_image, stage) -> [loss, mse_loss, perceptual_dino, msssim, col_loss] (reference :26-180).
 
     ``perceptual_vgg`` / ``perceptual_dino`` are the reference's model names; they are recorded but never loaded (no
-    ``torch.hub``, no kornia).  ``dino_loss`` / ``msssim_loss`` are the caller's callables ``(y_0_pred, gt) -> scalar tensor``
-    for those two terms; they run under torch autograd and their gradient reaches the model through ``y_0_pred``."""
+    ``torch.hub``, no kornia).  ``dino_loss`` / ``msssim_loss`` are callables ``(y_0_pred, gt) -> scalar tensor`` for those two
+    terms; their gradient reaches the model through ``y_0_pred``.  ``msssim_loss=Loss.loss.MSSSIMLoss()`` is the package's own
+    MS-SSIM + L1 loss on the HIP path; any other callable runs under torch autograd."""
 
     DINO_WEIGHT, MSSSIM_WEIGHT, COL_WEIGHT = 0.5, 0.0045, 1.0          # reference :165
 

@@ -360,6 +360,40 @@ int hdiff_train_b_loss_bwd(const float* noise_pred, const float* noise, const fl
                            const float* d_y0, const float* d_col, float* d_noise_pred, hdiff_stream_t stream);
 int hdiff_avgpool_global_bwd(const float* dy, float* dx, int BC, int HW, hdiff_stream_t stream);
 int hdiff_resize_nearest_bwd(const float* dy, float* dx, int BC, int H, int W, int OH, int OW, hdiff_stream_t stream);
+/* ------------------------------------------------------------------------------------------------------------------
+ * MS-SSIM + L1 loss of the second tree's trainer (Loss/loss.py:269-283 through kornia's MS_SSIMLoss; diffusion/Diffusion.py:171-172)
+ * and its gradient with respect to the prediction x (csrc/msssim.hip).  x, y: [B][3][H][W], any H, W >= 1.
+ *   A pair p filters channel pair_chan[p] with the 1-D Gaussian of scale pair_scale[p] (zero padding): l_p and cs_p from the five
+ *   moments.  Per pixel: PIcs = prod cs_p^pair_cs_pow[p], lM = prod l_p^pair_l_pow[p], ms = 1 - lM PIcs,
+ *   l1 = mean over channels of G_{l1_scale} * |x - y|, loss = compensation (alpha ms + (1 - alpha) l1 / data_range), then the mean
+ *   (mean != 0) or the sum over [B][H][W], in a fixed two-stage order (bitwise repeatable).
+ *   weights: HOST pointer, [nscales][window] normalised 1-D windows (window odd, <= 33); taps whose weight is at most 1e-12 beyond a
+ *   radius of 4 / 8 are skipped (csrc/msssim.hip).
+ *   hdiff_msssim_l1_workspace  saved_bytes: the moments the forward writes and the backward reads (B H W npairs 5 floats);
+ *                              scratch_bytes: enough for either call, free to reuse once the call's kernels have run
+ *   hdiff_msssim_l1_fwd        loss[0]; three launches
+ *   hdiff_msssim_l1_bwd        dx = d_loss[0] (device scalar) * d loss / d x from the forward's `saved`; two launches; sign(0) = 0
+ * Arguments are validated on the host before any launch (C != 3, more than 5 scales, a window above 33, null pointers: -1).
+ * ------------------------------------------------------------------------------------------------------------------ */
+#define HDIFF_MSSSIM_MAX_PAIRS 15
+#define HDIFF_MSSSIM_MAX_SCALES 5
+#define HDIFF_MSSSIM_MAX_WINDOW 33
+typedef struct hdiff_msssim_desc {
+  int B, C, H, W;
+  int nscales, window;
+  const float* weights;
+  int npairs;
+  int pair_chan[HDIFF_MSSSIM_MAX_PAIRS], pair_scale[HDIFF_MSSSIM_MAX_PAIRS];
+  int pair_cs_pow[HDIFF_MSSSIM_MAX_PAIRS], pair_l_pow[HDIFF_MSSSIM_MAX_PAIRS];
+  int l1_scale;
+  float C1, C2, alpha, compensation, data_range;
+  int mean;
+} hdiff_msssim_desc;
+int hdiff_msssim_l1_workspace(const hdiff_msssim_desc* d, int64_t* saved_bytes, int64_t* scratch_bytes);
+int hdiff_msssim_l1_fwd(const hdiff_msssim_desc* d, const float* x, const float* y, float* loss, void* saved, void* scratch,
+                        hdiff_stream_t stream);
+int hdiff_msssim_l1_bwd(const hdiff_msssim_desc* d, const float* x, const float* y, const float* d_loss, const void* saved,
+                        void* scratch, float* dx, hdiff_stream_t stream);
 /* final clip (:98) */
 int hdiff_clip(const float* x, float* y, float lo, float hi, int64_t n, hdiff_stream_t stream);
 /* out = a*x + b*y (y may be NULL): bias merges and other weight-preparation arithmetic */

@@ -16,8 +16,11 @@ No 8-GPU run has been made from the build box (one GPU); the driver can run this
                                                                              default config ch=128, ch_mult=[1,2,2,2], 2 res
                                                                              blocks, dropout 0.15): GaussianDiffusionTrainer
                                                                              fwd + bwd + clip(1.0) + native AdamW, one GPU;
-                                                                             prints ms per optimizer step.  No DINOv2 / MS-SSIM
-                                                                             term (not part of the package)."""
+                                                                             prints ms per optimizer step.  No DINOv2 term
+                                                                             (not part of the package); --msssim native adds
+                                                                             the MS-SSIM + L1 term (Loss.loss.MSSSIMLoss) and
+                                                                             prints the line of --msssim none beside it, both
+                                                                             measured in this call."""
 import argparse, json, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__))); sys.path.insert(0, ROOT)
 import torch
@@ -28,12 +31,14 @@ ap.add_argument("--size", type=int, default=256); ap.add_argument("--batch", typ
 ap.add_argument("--steps", type=int, default=3); ap.add_argument("--warmup", type=int, default=1)
 ap.add_argument("--dropout", type=float, default=0.15)
 ap.add_argument("--tree", choices=("a", "b"), default="a", help="a: the CFG-DDPM UNet (default); b: the image-conditioned DynamicUNet")
+ap.add_argument("--msssim", choices=("none", "native"), default="none",
+                help="--tree b: none = no MS-SSIM term (default); native = the HIP MS-SSIM + L1 loss, reported beside a run without it")
 ap.add_argument("--rehearse-one-gpu", action="store_true",
                 help="dev: the data-parallel code path with every rank on cuda:0 over gloo (RCCL refuses two ranks on one device)")
 a = ap.parse_args()
 
 
-def tree_b_steps(size, batch, steps, warmup, dropout):
+def tree_b_steps(size, batch, steps, warmup, dropout, msssim="none"):
     import time
     import warnings
     from hdiff_amd import optim as HO
@@ -42,7 +47,11 @@ def tree_b_steps(size, batch, steps, warmup, dropout):
     dev = torch.device("cuda", 0)
     torch.manual_seed(0)
     m = DynamicUNet(T=1000, ch=128, ch_mult=[1, 2, 2, 2], num_res_blocks=2, dropout=dropout).to(dev).train()
-    tr = GaussianDiffusionTrainer(m, 1e-4, 0.02, 1000)
+    msssim_loss = None
+    if msssim == "native":
+        from hdiff_amd.Loss.loss import MSSSIMLoss
+        msssim_loss = MSSSIMLoss()
+    tr = GaussianDiffusionTrainer(m, 1e-4, 0.02, 1000, msssim_loss=msssim_loss)
     opt = HO.AdamW(m.parameters(), lr=1e-4, weight_decay=1e-4)
     g = torch.Generator().manual_seed(1)
     label = torch.randint(0, 256, (batch, 3, size, size), generator=g).to(torch.uint8).to(dev)
@@ -62,7 +71,7 @@ def tree_b_steps(size, batch, steps, warmup, dropout):
                 times.append(time.perf_counter() - t0)
             losses.append(loss.mean().item())
     times.sort()
-    return {"tree": "b", "config": "ch=128,ch_mult=[1,2,2,2],num_res_blocks=2,dropout=%g" % dropout, "size": size, "batch": batch,
+    return {"tree": "b", "msssim": msssim, "config": "ch=128,ch_mult=[1,2,2,2],num_res_blocks=2,dropout=%g" % dropout, "size": size, "batch": batch,
             "steps": steps, "warmup": warmup, "ms_per_step_median": round(1e3 * times[len(times) // 2], 2),
             "ms_per_step_min": round(1e3 * times[0], 2), "losses": [round(v, 5) for v in losses],
             "gpu": torch.cuda.get_device_name(dev)}
@@ -72,6 +81,8 @@ if a.tree == "b":
     if a.gpus not in (None, 1):
         sys.exit("bench_train.py --tree b: one GPU only (no data-parallel path for the second tree)")
     print(json.dumps(tree_b_steps(a.size, a.batch, a.steps, a.warmup, a.dropout)), flush=True)
+    if a.msssim == "native":
+        print(json.dumps(tree_b_steps(a.size, a.batch, a.steps, a.warmup, a.dropout, "native")), flush=True)
     sys.exit(0)
 if a.gpus and a.gpus > 1 and "WORLD_SIZE" not in os.environ:      # plain start: become the launcher (the GPU is untouched so far)
     from hdiff_amd.parallel import launch_ranks
