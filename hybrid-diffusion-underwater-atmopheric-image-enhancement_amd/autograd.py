@@ -49,11 +49,11 @@ def _c(t: Optional[torch.Tensor]) -> Optional[torch.Tensor]:
 # launch helpers (immediate execution)
 # ----------------------------------------------------------------------------------------------------------------------
 def _run_conv(x0, x1, sources, taps: E.TapSet, cout: int, cin: int, bias, out, *, B, H, W, VH, VW, in_stride=1,
-              out_map=(1, 0, 1, 0), gn=None, addvec=None, residual=None, x3=None, act_range=None) -> None:
+              out_map=(1, 0, 1, 0), gn=None, addvec=None, residual=None, x3=None, act_range=None, dropout=None) -> None:
     """x3 = (forward weight [3x3], transposed?): also pack the split-bf16 copy, so that a plain 3x3 / stride-1 launch (the
     forward conv, or its input-gradient conv on the transposed, mirrored weight) runs conv3x3_x3.hip in the bf16x3 mode.
     act_range = (gamma, beta, group_elems, gain) of the GroupNorm + Swish the input went through (Plan.conv): the forward conv
-    then takes that kernel's fp16-pair form."""
+    then takes that kernel's fp16-pair form.  dropout = (keep bits, 1 / keep): train-mode dropout inside the prologue."""
     plan = E.Plan(x0.device)
     pk = E.PackedConv(x0.device, cout, cin, taps)
     for (w, mode, ky, kx, acc) in sources:
@@ -65,14 +65,14 @@ def _run_conv(x0, x1, sources, taps: E.TapSet, cout: int, cin: int, bias, out, *
             pk.enable_x3(x3[0], transposed=x3[1])
     plan.packs.append(pk)
     plan.conv(x0, x1, pk, bias, out, B=B, H=H, W=W, VH=VH, VW=VW, in_stride=in_stride, out_map=out_map, gn=gn,
-              addvec=addvec, residual=residual, act_range=act_range)
+              addvec=addvec, residual=residual, act_range=act_range, dropout=dropout)
     plan.pack_weights()
     plan.run()
 
 
 def _run_wgrad(x0, x1, gn, dy, taps: E.TapSet, cout: int, cin: int, *, B, H, W, VH, VW, in_stride=1, out_map=(1, 0, 1, 0),
-               targets: Sequence[Tuple[torch.Tensor, int, Sequence[int], Sequence[int], int]]) -> None:
-    """targets: (dw tensor in PyTorch layout, mode, tap_ky, tap_kx, accumulate)."""
+               targets: Sequence[Tuple[torch.Tensor, int, Sequence[int], Sequence[int], int]], dropout=None) -> None:
+    """targets: (dw tensor in PyTorch layout, mode, tap_ky, tap_kx, accumulate).  dropout = (keep bits, 1 / keep) of the forward."""
     lib = _capi.lib()
     dev = x0.device
     d = _capi.WgradDesc()
@@ -92,7 +92,11 @@ def _run_wgrad(x0, x1, gn, dy, taps: E.TapSet, cout: int, cin: int, *, B, H, W, 
     _capi.check(lib.hdiff_conv2d_wgrad_workspace(C.byref(d), C.byref(nsplit), C.byref(nfloats)), "wgrad_workspace")
     ws = torch.empty(nfloats.value, dtype=torch.float32, device=dev)
     s = _stream(dev)
-    _capi.check(lib.hdiff_conv2d_wgrad(C.byref(d), ws.data_ptr(), nsplit.value, s), "conv2d_wgrad")
+    if dropout is not None:
+        _capi.check(lib.hdiff_conv2d_wgrad_dropout(C.byref(d), dropout[0].data_ptr(), C.c_float(dropout[1]), ws.data_ptr(),
+                                                   nsplit.value, s), "conv2d_wgrad_dropout")
+    else:
+        _capi.check(lib.hdiff_conv2d_wgrad(C.byref(d), ws.data_ptr(), nsplit.value, s), "conv2d_wgrad")
     for dw, mode, ky, kx, acc in targets:
         kh, kw = int(dw.shape[2]), int(dw.shape[3])
         a_ky, a_kx = (C.c_int * n)(*ky), (C.c_int * n)(*kx)
@@ -119,6 +123,12 @@ def _gn_stats(x0, x1, gamma, beta, B, HW):
                                       C.c_float(GN_EPS), scale.data_ptr(), shift.data_ptr(), mean.data_ptr(),
                                       rstd.data_ptr(), s), "gn_finalize")
     return scale, shift, mean, rstd
+
+
+def _inv_keep(drop_p: float) -> float:
+    """1 / keep as the fp32 quotient of the fp32 keep probability: the scale hdiff_dropout_mask writes for the same drop_p."""
+    keep = C.c_float(1.0 - drop_p).value
+    return C.c_float(1.0 / keep).value      # a double quotient of two floats rounds to the correctly rounded float quotient
 
 
 def _plane_sums(dy, want_vec: bool, want_bias: bool):
@@ -148,42 +158,39 @@ class _FusedConv(Function):
         cout, cin = int(weight.shape[0]), int(weight.shape[1])
         assert cin == C0 + C1
         pad = k // 2
-        gn = mean = rstd = mask = act_range = None
-        conv_in0, conv_in1, conv_gn = x0, x1, None
+        gn = mean = rstd = bits = act_range = dropout = None
+        if drop_p > 0.0 and (gn_w is None or x1 is not None or k != 3):
+            raise RuntimeError("fused_conv: drop_p needs a 3x3 conv behind GroupNorm + Swish without a concat input")
         if gn_w is not None:
             scale, shift, mean, rstd = _gn_stats(x0, x1, gn_w, gn_b, B, H * W)
             gn = (scale, shift)
-            conv_gn = gn
-            # the conv's input is swish(GroupNorm(x)) (times mask / keep behind the dropout): its range follows from the
+            # the conv's input is swish(GroupNorm(x)) (times 1 / keep behind the dropout): its range follows from the
             # GroupNorm weights, which is what the fp16-pair 3x3 kernel stages its activations by
             act_range = (gn_w.detach(), gn_b.detach(), (cin // GN_GROUPS) * H * W, 1.0 / (1.0 - drop_p) if drop_p > 0.0 else 1.0)
             if drop_p > 0.0:
-                # nn.Dropout sits between Swish and the conv (ModelCondition.py:185): materialise a = swish(gn(x)) * mask
-                assert x1 is None
-                a = torch.empty_like(x0)
-                s = _stream(dev)
-                _capi.check(lib.hdiff_gn_swish_apply(x0.data_ptr(), scale.data_ptr(), shift.data_ptr(), a.data_ptr(), B, C0,
-                                                     H * W, s), "gn_swish_apply")
-                mask = torch.empty_like(x0)
-                _capi.check(lib.hdiff_dropout_mask(mask.data_ptr(), mask.numel(), C.c_float(1.0 - drop_p), C.c_uint64(seed),
-                                                   C.c_uint64(0), s), "dropout_mask")
-                _capi.check(lib.hdiff_mul(a.data_ptr(), mask.data_ptr(), a.data_ptr(), a.numel(), s), "mul")
-                conv_in0, conv_in1, conv_gn = a, None, None
+                # nn.Dropout sits between Swish and the conv (ModelCondition.py:185): the keep decisions as one bit per element,
+                # applied inside the conv's prologue -- neither the activation nor a mask is materialised
+                n = x0.numel()
+                bits = torch.empty((n + 31) // 32, dtype=torch.int32, device=dev)
+                _capi.check(lib.hdiff_dropout_keep_bits(bits.data_ptr(), n, C.c_float(1.0 - drop_p), C.c_uint64(seed),
+                                                        C.c_uint64(0), _stream(dev)), "dropout_keep_bits")
+                dropout = (bits, _inv_keep(drop_p))
         taps = E.conv_taps(k, pad)
         out = torch.empty(B, cout, H, W, device=dev)
-        _run_conv(conv_in0, conv_in1, [(weight, 0, taps.ky, taps.kx, 0)], taps, cout, cin, bias, out, B=B, H=H, W=W, VH=H,
-                  VW=W, gn=conv_gn, addvec=addvec, residual=residual, x3=(weight, False) if k in (1, 3) else None,
-                  act_range=act_range if k == 3 else None)
-        ctx.k, ctx.has_x1, ctx.has_gn, ctx.dropped = k, x1 is not None, gn_w is not None, mask is not None
+        _run_conv(x0, x1, [(weight, 0, taps.ky, taps.kx, 0)], taps, cout, cin, bias, out, B=B, H=H, W=W, VH=H,
+                  VW=W, gn=gn, addvec=addvec, residual=residual, x3=(weight, False) if k in (1, 3) else None,
+                  act_range=act_range if k == 3 else None, dropout=dropout)
+        ctx.k, ctx.has_x1, ctx.has_gn = k, x1 is not None, gn_w is not None
+        ctx.inv_keep = dropout[1] if dropout is not None else None
         ctx.has_bias, ctx.has_vec, ctx.has_res = bias is not None, addvec is not None, residual is not None
-        saved = [x0, x1, weight, gn_w, gn_b, mean, rstd, gn[0] if gn else None, gn[1] if gn else None, mask,
-                 conv_in0 if mask is not None else None]
+        saved = [x0, x1, weight, gn_w, gn_b, mean, rstd, gn[0] if gn else None, gn[1] if gn else None, bits]
         ctx.save_for_backward(*saved)
         return out
 
     @staticmethod
     def backward(ctx, dout):
-        x0, x1, weight, gn_w, gn_b, mean, rstd, scale, shift, mask, a_masked = ctx.saved_tensors
+        x0, x1, weight, gn_w, gn_b, mean, rstd, scale, shift, bits = ctx.saved_tensors
+        dropout = (bits, ctx.inv_keep) if bits is not None else None
         dout = dout.contiguous()
         lib = _capi.lib()
         dev = dout.device
@@ -201,12 +208,8 @@ class _FusedConv(Function):
         d_w = None
         if need[2]:
             d_w = torch.empty_like(weight)
-            if ctx.dropped:
-                _run_wgrad(a_masked, None, None, dout, taps, cout, cin, B=B, H=H, W=W, VH=H, VW=W,
-                           targets=[(d_w, 0, taps.ky, taps.kx, 0)])
-            else:
-                _run_wgrad(x0, x1, (scale, shift) if ctx.has_gn else None, dout, taps, cout, cin, B=B, H=H, W=W, VH=H, VW=W,
-                           targets=[(d_w, 0, taps.ky, taps.kx, 0)])
+            _run_wgrad(x0, x1, (scale, shift) if ctx.has_gn else None, dout, taps, cout, cin, B=B, H=H, W=W, VH=H, VW=W,
+                       targets=[(d_w, 0, taps.ky, taps.kx, 0)], dropout=dropout)
 
         d_x0 = d_x1 = d_gw = d_gb = None
         need_dx = need[0] or (ctx.has_x1 and need[1]) or (ctx.has_gn and (need[4] or need[5]))
@@ -218,13 +221,18 @@ class _FusedConv(Function):
             dA = torch.empty(B, cin, H, W, device=dev)
             _run_conv(dout, None, [(weight, 1, dtaps.ky, dtaps.kx, 0)], dtaps, cin, cout, None, dA, B=B, H=H, W=W, VH=H, VW=W,
                       x3=(weight, True) if k in (1, 3) else None)
-            if ctx.dropped:
-                _capi.check(lib.hdiff_mul(dA.data_ptr(), mask.data_ptr(), dA.data_ptr(), dA.numel(), s), "mul")
             if ctx.has_gn:
                 d_x0 = torch.empty_like(x0)
                 d_x1 = torch.empty_like(x1) if x1 is not None else None
                 d_gw, d_gb = torch.empty_like(gn_w), torch.empty_like(gn_b)
                 ws = torch.empty(2 * B * cin + 2 * B * GN_GROUPS, device=dev)
+                if dropout is not None:      # dA is the gradient of the DROPPED activation: the keep bits are applied as it is read
+                    _capi.check(lib.hdiff_gn_swish_dropout_bwd(x0.data_ptr(), C0, B, H * W, GN_GROUPS, dA.data_ptr(),
+                                                               bits.data_ptr(), C.c_float(ctx.inv_keep), mean.data_ptr(),
+                                                               rstd.data_ptr(), gn_w.data_ptr(), gn_b.data_ptr(), ws.data_ptr(),
+                                                               d_x0.data_ptr(), d_gw.data_ptr(), d_gb.data_ptr(), s),
+                                "gn_swish_dropout_bwd")
+                    return d_x0, None, d_w, d_bias, d_gw, d_gb, d_vec, d_res, None, None, None
                 _capi.check(lib.hdiff_gn_swish_bwd(x0.data_ptr(), _p(x1), C0, C1, B, H * W, GN_GROUPS, dA.data_ptr(),
                                                    mean.data_ptr(), rstd.data_ptr(), gn_w.data_ptr(), gn_b.data_ptr(),
                                                    ws.data_ptr(), d_x0.data_ptr(), _p(d_x1), d_gw.data_ptr(),

@@ -70,7 +70,8 @@ __device__ __forceinline__ TileId xcd_tile() {
 // conv_wgrad3x3.hip: the 3x3 / stride-1 weight-gradient kernel of the U-Net body (dispatched from conv_wgrad.hip)
 bool wgrad3x3_applicable(const hdiff_conv_wgrad_desc* d);
 int wgrad3x3_nsplit(const hdiff_conv_wgrad_desc* d);
-int launch_wgrad3x3(const hdiff_conv_wgrad_desc* d, float* dwp, int nsplit, hipStream_t stream);
+int launch_wgrad3x3(const hdiff_conv_wgrad_desc* d, float* dwp, int nsplit, hipStream_t stream, const unsigned* keep_bits = nullptr,
+                    float inv_keep = 1.0f);      // keep_bits: the dropout form (hdiff_conv2d_wgrad_dropout)
 bool wgrad1x1_applicable(const hdiff_conv_wgrad_desc* d);     // same file: the 1x1 / stride-1 convs without a prologue
 int wgrad1x1_nsplit(const hdiff_conv_wgrad_desc* d);
 int launch_wgrad1x1(const hdiff_conv_wgrad_desc* d, float* dwp, int nsplit, hipStream_t stream);
@@ -97,6 +98,10 @@ struct ConvX3K {
   const float* act_scale;          // device {2^s, 2^-s} of the staged activations (hdiff_gn_act_scale), NULL = bf16 triples
   const float* w_scale;            // the pack's tail {bits of max |w|, 2^-t, 2^t, 0} (hdiff_pack_conv_weight_h2)
   float one;                       // 1.0f, opaque to the compiler
+  // train-mode dropout between the prologue and the conv (hdiff_conv2d_fwd_dropout; the DROP instantiations only): the staged value
+  // is kept ? swish(..) * inv_keep : 0, bit (e & 31) of keep_bits[e >> 5] for the element's flat NCHW index e < 2^31 in x0
+  const unsigned* keep_bits;
+  float inv_keep;
 };
 void launch_conv3x3_x3(const ConvX3K& k, int B, hipStream_t stream);
 

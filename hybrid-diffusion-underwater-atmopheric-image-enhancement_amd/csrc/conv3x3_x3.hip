@@ -96,7 +96,12 @@ __device__ constexpr int TERM_X[6] = {0, 1, 2, 0, 1, 0};
 // NT: taps of the launch (9 = the 3x3 conv, 6 / 4 = transposed-conv phases with fewer taps); OUTMAP: the output pixel of
 // (vy, vx) is (vy * out_sy + out_oy, vx * out_sx + out_ox) of an OH x OW plane (transposed-conv phases) instead of (vy, vx).
 // PAIR: fp16 pairs and three products instead of bf16 triples and six (header).
-template <int NT, bool OUTMAP, bool PAIR, int OCC = 1>
+// DROP: train-mode dropout behind the GroupNorm + Swish prologue (nn.Dropout between Swish and the conv, ModelCondition.py:185):
+// the keep words of a slot's four channels (one word per channel) are requested while the slot before it is staged, one tap of
+// MFMAs ahead (a padding slot fetches the word of its channel plane's first element and never looks at it), and the staged value
+// is kept ? swish(..) * inv_keep : 0.  A compile-time variant: the instantiations without it carry none of this.  The DROP
+// instantiations are built with OCC = 2, which holds the register allocator to the occupancy of their siblings.
+template <int NT, bool OUTMAP, bool PAIR, int OCC = 1, bool DROP = false>
 __global__ __launch_bounds__(THREADS, OCC) void conv3x3_x3_kernel(const ConvX3K p) {
   constexpr int NP = PAIR ? 2 : 3;         // pieces per operand
   __shared__ __attribute__((aligned(16))) unsigned sXbuf[2][NP * PSTRIDE];     // double-buffered: chunk c + 1 is staged beside chunk c's MFMAs
@@ -165,6 +170,27 @@ __global__ __launch_bounds__(THREADS, OCC) void conv3x3_x3_kernel(const ConvX3K 
   // staging slot of chunk c + 1 consumed its load 400 cycles after it had left.
   constexpr bool XAHEAD = PAIR;
   f32x4 xv[NSLOT], xv2[XAHEAD ? NSLOT : 1];
+  // DROP: the four keep words of the slot that is staged NEXT (x1 == NULL and B * Cin * H * W < 2^31: checked on the host),
+  // requested while the slot before it is staged -- one tap of MFMAs ahead of their use, four registers in flight.  `tie` is a
+  // value of the slot just staged: the (empty) asm makes the element index depend on it.  Without it the compiler keeps the
+  // 24 per-(slot, channel) parts of the indices as loop invariants and requests a chunk's words all at once, and the kernel --
+  // 20 registers to spare at two waves per SIMD -- spills (31 VGPRs in the fp16-pair form).
+  unsigned kw[DROP ? 4 : 1];
+  unsigned ksh = 0;         // their four bit positions, five bits each
+  auto fetch_keep = [&](int i, int c0, unsigned tie) {
+    if constexpr (DROP) {
+      const unsigned hw = (unsigned)HW;
+      unsigned e = (unsigned)(b * p.Cin + c0 + 4 * s_quad[i]) * hw + (unsigned)(s_goff[i] >= 0 ? s_goff[i] : 0);
+      asm("" : "+v"(e) : "v"(tie));
+      ksh = 0;
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        kw[k] = p.keep_bits[e >> 5];
+        ksh |= (e & 31u) << (5 * k);
+        e += hw;
+      }
+    }
+  };
   auto issue_loads_to = [&](f32x4 (&dst)[XAHEAD ? NSLOT : 1], int c0) {
     const float* xbase = (c0 < p.C0) ? p.x0 + ((size_t)b * p.C0 + c0) * HW : p.x1 + ((size_t)b * p.C1 + (c0 - p.C0)) * HW;
 #pragma unroll
@@ -198,7 +224,19 @@ __global__ __launch_bounds__(THREADS, OCC) void conv3x3_x3_kernel(const ConvX3K 
       const f32x4 sh = *reinterpret_cast<const f32x4*>(&sG[p.Cin + ci]);
       const bool inside = s_goff[i] >= 0;
 #pragma unroll
-      for (int k = 0; k < 4; ++k) v[k] = inside ? swish_fast(fmaf(v[k], sc[k], sh[k])) : 0.f;
+      for (int k = 0; k < 4; ++k) {
+        if constexpr (DROP) {
+          const bool kept = (kw[k] >> ((ksh >> (5 * k)) & 31u)) & 1u;
+          v[k] = (inside && kept) ? swish_fast(fmaf(v[k], sc[k], sh[k])) * p.inv_keep : 0.f;
+        } else {
+          v[k] = inside ? swish_fast(fmaf(v[k], sc[k], sh[k])) : 0.f;
+        }
+      }
+      if constexpr (DROP) {                 // slots are staged in order 0 .. NSLOT - 1, chunk after chunk
+        const unsigned tie = __builtin_bit_cast(unsigned, v[0]);
+        if (i + 1 < NSLOT) fetch_keep(i + 1, c0, tie);
+        else fetch_keep(0, c0 + 16 < p.Cin ? c0 + 16 : c0, tie);      // branch-free: the last chunk re-reads its own words, unused
+      }
     }
     typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
     if constexpr (PAIR) {
@@ -305,6 +343,7 @@ __global__ __launch_bounds__(THREADS, OCC) void conv3x3_x3_kernel(const ConvX3K 
 
   const int nchunks = p.Cin / 16;
   issue_loads(0);
+  fetch_keep(0, 0, 0u);
   __syncthreads();     // sG visible
   if (has_gn) store_staged(std::true_type{}, 0, sXbuf[0]);
   else store_staged(std::false_type{}, 0, sXbuf[0]);
@@ -492,6 +531,11 @@ void launch_conv3x3_x3(const ConvX3K& k, int B, hipStream_t stream) {
   dim3 grid(k.tiles_x * tiles_y, cdiv(k.Cout, 64), B);
   const size_t dyn = (size_t)2 * k.Cin * sizeof(float);
   const bool outmap = !(k.out_sy == 1 && k.out_oy == 0 && k.out_sx == 1 && k.out_ox == 0 && k.OH == k.H && k.OW == k.W);
+  if (k.keep_bits != nullptr) {            // train-mode dropout in the prologue (hdiff_conv2d_fwd_dropout checked the descriptor)
+    if (k.act_scale != nullptr) hipLaunchKernelGGL((conv3x3_x3_kernel<9, false, true, 2, true>), grid, dim3(THREADS), dyn, stream, k);
+    else hipLaunchKernelGGL((conv3x3_x3_kernel<9, false, false, 2, true>), grid, dim3(THREADS), dyn, stream, k);
+    return;
+  }
   if (k.act_scale != nullptr) {            // fp16 pairs: the plain 3x3 conv behind GroupNorm + Swish (the dispatcher checked the shape)
     hipLaunchKernelGGL((conv3x3_x3_kernel<9, false, true>), grid, dim3(THREADS), dyn, stream, k);
     return;

@@ -43,6 +43,10 @@ struct ConvK {
   int B, ksplit, chunks_per_split; // split-K over input-channel chunks for small grids (partials -> conv_splitk_reduce)
   float* partial;                  // [ksplit][B][Cout][VH*VW]
   int tap_off[HDIFF_MAX_TAPS];
+  // train-mode dropout behind the prologue (hdiff_conv2d_fwd_dropout; the DROP instantiations only): bit (e & 31) of
+  // keep_bits[e >> 5] for the flat NCHW index e < 2^31 of an element of x0, kept values are scaled by inv_keep
+  const unsigned* keep_bits;
+  float inv_keep;
 };
 
 // Swish with the hardware reciprocal (1 ulp) instead of an IEEE division: the prologue runs once per staged element
@@ -60,7 +64,11 @@ __device__ __forceinline__ float swish_fast(float v) { return v * __builtin_amdg
 // blocks, so the second tile is always safe to compute and rows >= Cout are simply not stored; keeping this a template
 // parameter (not a runtime test) matters: a branch inside the unrolled MFMA loop stops the compiler from hoisting the LDS
 // operand reads across k-steps (it does not change the measured rate: the kernel is not bound by those reads).
-template <int WN, int CK, int NXS, int NWS, int SPEC, bool TWOM>
+// DROP: train-mode dropout between the GroupNorm + Swish prologue and the conv (3x3 / stride 1, x1 == NULL, every channel of a
+// chunk exists: checked on the host).  The keep bits of a thread's staging slots are fetched with the slots' activations -- from
+// the element index the activation itself is read at, so a padding slot reads no bit of its own -- into one mask register, and
+// the staged value is kept ? swish(..) * inv_keep : 0.  A compile-time variant: the other instantiations carry none of it.
+template <int WN, int CK, int NXS, int NWS, int SPEC, bool TWOM, bool DROP = false>
 __global__ __launch_bounds__(NTHREADS, 2) void conv_igemm_kernel(const ConvK p) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   float* sX = smem;                       // [CK][PLANE]
@@ -167,11 +175,17 @@ __global__ __launch_bounds__(NTHREADS, 2) void conv_igemm_kernel(const ConvK p) 
 
   float xr[NXS];
   float4 wr[NWS];
+  unsigned xkeep = 0;     // DROP: bit i = keep decision of staging slot i of the chunk in flight
   // SPEC: buffer resources of this sample's input tensors (range = the sample's channels: reads past Cin return 0)
   const __amdgpu_buffer_rsrc_t rsrc0 = __builtin_amdgcn_make_buffer_rsrc(
       const_cast<float*>(p.x0 + (size_t)b * p.C0 * HW), 0, p.C0 * (int)HW * 4, 0x00020000);
   const __amdgpu_buffer_rsrc_t rsrc1 = __builtin_amdgcn_make_buffer_rsrc(
       const_cast<float*>(p.x1 ? p.x1 + (size_t)b * p.C1 * HW : p.x0), 0, p.x1 ? p.C1 * (int)HW * 4 : 0, 0x00020000);
+  // DROP: the keep words through a buffer resource too (one offset register per load instead of a 64-bit address; range = the
+  // ceil(B * Cin * H * W / 32) words of the launch)
+  const __amdgpu_buffer_rsrc_t rsrck = __builtin_amdgcn_make_buffer_rsrc(
+      const_cast<unsigned*>(DROP ? p.keep_bits : nullptr), 0, DROP ? (int)((((unsigned)(p.B * p.Cin) * (unsigned)HW + 31u) >> 5) * 4u) : 0,
+      0x00020000);
   auto issue_loads = [&](int c0) {
     // a chunk never straddles the concat seam (C0 % CK == 0 is checked on the host)
     const float* xbase = (c0 < p.C0) ? p.x0 + ((size_t)b * p.C0 + c0) * HW : p.x1 + ((size_t)b * p.C1 + (c0 - p.C0)) * HW;
@@ -185,11 +199,29 @@ __global__ __launch_bounds__(NTHREADS, 2) void conv_igemm_kernel(const ConvK p) 
 #pragma unroll
       for (int i = 0; i < SPEC_SLOTS; ++i)
         xr[i] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(first ? rsrc0 : rsrc1, x_soff[i], soff, 0));
+      if constexpr (DROP) {
+        const unsigned e0 = (unsigned)(b * p.Cin + c0) * (unsigned)HW;
+        xkeep = 0;
+#pragma unroll
+        for (int i = 0; i < SPEC_SLOTS; ++i) {
+          unsigned boff = (unsigned)x_soff[i];      // (opaque: x_soff >> 2 would be hoisted out of the chunk loop as 11 more registers)
+          asm("" : "+v"(boff));
+          const unsigned e = e0 + (boff >> 2);      // the element the slot's load reads (the tile's first one for padding)
+          const unsigned word = (unsigned)__builtin_amdgcn_raw_buffer_load_b32(rsrck, (int)((e >> 5) << 2), 0, 0);
+          xkeep |= ((word >> (e & 31u)) & 1u) << i;
+        }
+      }
     } else {
+      if constexpr (DROP) xkeep = 0;
 #pragma unroll
       for (int i = 0; i < NXS; ++i) {
         const bool ok = x_soff[i] >= 0 && (x_meta[i] >> 24) < c_left;
         xr[i] = ok ? xbase[x_soff[i]] : 0.f;
+        if constexpr (DROP && CK == 8) {
+          const unsigned e = (unsigned)(b * p.Cin + c0) * (unsigned)HW + (unsigned)x_soff[i];      // (used under `ok` only)
+          const unsigned word = ok ? p.keep_bits[e >> 5] : 0u;
+          xkeep |= ((word >> (e & 31u)) & 1u) << i;
+        }
       }
     }
     const float* wbase = p.wp + (size_t)c0 * p.CoutPad + co0;
@@ -206,7 +238,11 @@ __global__ __launch_bounds__(NTHREADS, 2) void conv_igemm_kernel(const ConvK p) 
 #pragma unroll
         for (int i = 0; i < SPEC_SLOTS; ++i) {
           const float v = swish_fast(fmaf(xr[i], gsc, gsh));
-          if (i < SPEC_SLOTS - 1 || s_last) sX[x_meta[i]] = s_outb[i] ? 0.f : v;     // the conv pads the ACTIVATED tensor with zeros
+          if constexpr (DROP) {
+            if (i < SPEC_SLOTS - 1 || s_last) sX[x_meta[i]] = (s_outb[i] || !((xkeep >> i) & 1u)) ? 0.f : v * p.inv_keep;
+          } else {
+            if (i < SPEC_SLOTS - 1 || s_last) sX[x_meta[i]] = s_outb[i] ? 0.f : v;     // the conv pads the ACTIVATED tensor with zeros
+          }
         }
       } else {
 #pragma unroll
@@ -220,6 +256,15 @@ __global__ __launch_bounds__(NTHREADS, 2) void conv_igemm_kernel(const ConvK p) 
           float v = xr[i];
           const int ci = x_meta[i] >> 24;
           if (has_gn && x_soff[i] >= 0 && ci < c_left) v = swish_fast(fmaf(v, sG[c0 + ci], sG[p.Cin + c0 + ci]));
+          if constexpr (DROP && CK == 8) v = ((xkeep >> i) & 1u) ? v * p.inv_keep : 0.f;      // (padding slots hold 0 either way)
+          if constexpr (DROP && CK == 4) {
+            // the 20-slot configuration (planes at most four pixels wide) has no registers left for bits in flight beside the
+            // patch: it fetches each slot's word here, when the slot is stored
+            const bool ok = x_soff[i] >= 0 && ci < c_left;
+            const unsigned e = (unsigned)(b * p.Cin + c0) * (unsigned)HW + (unsigned)x_soff[i];      // (used under `ok` only)
+            const unsigned word = ok ? p.keep_bits[e >> 5] : 0u;
+            v = ((word >> (e & 31u)) & 1u) ? v * p.inv_keep : 0.f;
+          }
           sX[x_meta[i] & 0xFFFFFF] = v;
         }
       }
@@ -452,14 +497,14 @@ int ceil_log2(int v) {
   return l;
 }
 
-template <int WN, int CK, int NXS, int NWS, int SPEC, bool TWOM>
+template <int WN, int CK, int NXS, int NWS, int SPEC, bool TWOM, bool DROP = false>
 void launch_t(const ConvK& k, dim3 grid, size_t lds_bytes, hipStream_t stream) {
   static uint64_t attr_mask = 0;
   if (first_use_on_device(attr_mask)) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_igemm_kernel<WN, CK, NXS, NWS, SPEC, TWOM>),
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_igemm_kernel<WN, CK, NXS, NWS, SPEC, TWOM, DROP>),
                               hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
   }
-  hipLaunchKernelGGL((conv_igemm_kernel<WN, CK, NXS, NWS, SPEC, TWOM>), grid, dim3(NTHREADS), lds_bytes, stream, k);
+  hipLaunchKernelGGL((conv_igemm_kernel<WN, CK, NXS, NWS, SPEC, TWOM, DROP>), grid, dim3(NTHREADS), lds_bytes, stream, k);
 }
 
 template <int WN, int CK, int NXS, int NWS, int SPEC>
@@ -469,7 +514,10 @@ int launch(const ConvK& k, int B, size_t lds_bytes, hipStream_t stream) {
   const int tiles_y = cdiv(k.VH, BN / TW);
   dim3 grid(k.tiles_x * tiles_y, cdiv(k.Cout, BM), B * k.ksplit);
   (void)hipGetLastError();  // drop any stale error left by another HIP user in this thread
-  if (k.Cout > 32) launch_t<WN, CK, NXS, NWS, SPEC, true>(k, grid, lds_bytes, stream);
+  if (k.keep_bits != nullptr) {
+    if (k.Cout > 32) launch_t<WN, CK, NXS, NWS, SPEC, true, true>(k, grid, lds_bytes, stream);
+    else launch_t<WN, CK, NXS, NWS, SPEC, false, true>(k, grid, lds_bytes, stream);
+  } else if (k.Cout > 32) launch_t<WN, CK, NXS, NWS, SPEC, true>(k, grid, lds_bytes, stream);
   else launch_t<WN, CK, NXS, NWS, SPEC, false>(k, grid, lds_bytes, stream);
   if (k.ksplit > 1) {
     const size_t n = (size_t)B * k.Cout * k.VH * k.VW;
@@ -687,11 +735,14 @@ bool is_x3_1x1(const hdiff_conv_desc* d) {
 }
 }  // namespace
 
-extern "C" int hdiff_conv2d_fwd(const hdiff_conv_desc* d, hdiff_stream_t stream) {
+// keep_bits != NULL: the dropout form (hdiff_conv2d_fwd_dropout validated the descriptor; such a launch is never a 1x1)
+static int conv2d_fwd(const hdiff_conv_desc* d, const unsigned* keep_bits, float inv_keep, hdiff_stream_t stream) {
   ConvCfg c;
   const int rc = configure(d, c);
   if (rc != HDIFF_OK) return rc;
   ConvK& k = c.k;
+  k.keep_bits = keep_bits;
+  k.inv_keep = inv_keep;
   if (is_x3_conv(d)) {
     hdiff::ConvX3K q{};
     q.x0 = d->x0; q.x1 = d->x1; q.C0 = d->C0; q.C1 = d->C1; q.Cin = d->C0 + d->C1; q.H = d->H; q.W = d->W;
@@ -709,6 +760,7 @@ extern "C" int hdiff_conv2d_fwd(const hdiff_conv_desc* d, hdiff_stream_t stream)
     q.out = d->out; q.tiles_x = cdiv(d->W, 32); q.ntaps = d->ntaps;
     for (int t = 0; t < d->ntaps; ++t) q.tap_off[t] = ((d->tap_dy[t] + 1) * 34 + (d->tap_dx[t] + 1)) * 4;
     q.OH = d->OH; q.OW = d->OW; q.out_sy = d->out_sy; q.out_oy = d->out_oy; q.out_sx = d->out_sx; q.out_ox = d->out_ox;
+    q.keep_bits = keep_bits; q.inv_keep = inv_keep;
     (void)hipGetLastError();  // drop any stale error left by another HIP user in this thread
     hdiff::launch_conv3x3_x3(q, d->B, (hipStream_t)stream);
     HDIFF_CHECK_LAUNCH("conv3x3_x3_kernel");
@@ -749,4 +801,23 @@ extern "C" int hdiff_conv2d_fwd(const hdiff_conv_desc* d, hdiff_stream_t stream)
   if (c.WN == 2 && c.CK == 4) return launch<2, 4, 20, 7, 0>(k, d->B, c.lds, s);
   if (c.WN == 1 && c.CK == 8) return launch<1, 8, 12, 5, 0>(k, d->B, c.lds, s);
   return launch<1, 4, 20, 7, 0>(k, d->B, c.lds, s);
+}
+
+extern "C" int hdiff_conv2d_fwd(const hdiff_conv_desc* d, hdiff_stream_t stream) { return conv2d_fwd(d, nullptr, 1.0f, stream); }
+
+// conv(dropout(swish(GroupNorm(x)))) in one launch (nn.Dropout between Swish and block2's conv, ModelCondition.py:184-186)
+extern "C" int hdiff_conv2d_fwd_dropout(const hdiff_conv_desc* d, const uint32_t* keep_bits, float inv_keep, hdiff_stream_t stream) {
+  HDIFF_CHECK_ARG(d && keep_bits, "conv2d_fwd_dropout: null pointer");
+  HDIFF_CHECK_ARG(inv_keep >= 1.0f && inv_keep <= 3.0e38f, "conv2d_fwd_dropout: inv_keep = %g is not a finite 1 / keep with keep in (0, 1]",
+                  (double)inv_keep);
+  HDIFF_CHECK_ARG(d->x1 == nullptr && d->C1 == 0, "conv2d_fwd_dropout: a concat input (x1) is not supported");
+  HDIFF_CHECK_ARG(d->gn_scale != nullptr && d->gn_shift != nullptr, "conv2d_fwd_dropout: needs the GroupNorm + Swish prologue (gn_scale / gn_shift)");
+  bool plain = d->ntaps == 9 && d->in_stride == 1 && d->VH == d->H && d->VW == d->W && d->OH == d->H && d->OW == d->W &&
+               d->out_sy == 1 && d->out_oy == 0 && d->out_sx == 1 && d->out_ox == 0;
+  for (int t = 0; plain && t < 9; ++t) plain = d->tap_dy[t] == t / 3 - 1 && d->tap_dx[t] == t % 3 - 1;
+  HDIFF_CHECK_ARG(plain, "conv2d_fwd_dropout: not a plain 3x3 / stride-1 / pad-1 convolution (nine taps in row-major order, output grid = input grid)");
+  HDIFF_CHECK_ARG(d->C0 > 0 && d->C0 % 8 == 0, "conv2d_fwd_dropout: C0 = %d is not a multiple of 8", d->C0);
+  HDIFF_CHECK_ARG(d->B > 0 && d->H > 0 && d->W > 0 && (long long)d->B * d->C0 * d->H * d->W < (1ll << 31),
+                  "conv2d_fwd_dropout: inputs of 2^31 elements or more are not supported (32-bit bit indices)");
+  return conv2d_fwd(d, keep_bits, inv_keep, stream);
 }

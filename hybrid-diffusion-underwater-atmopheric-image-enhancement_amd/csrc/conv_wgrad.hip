@@ -43,13 +43,18 @@ struct WgradK {
   int CinPad, CoutPad, nsplit;
   float* dwp;
   int tap_off[HDIFF_MAX_TAPS];
+  // train-mode dropout behind the prologue (hdiff_conv2d_wgrad_dropout, the DROP instantiations): see conv3x3_x3.hip
+  const unsigned* keep_bits;
+  float inv_keep;
 };
 
 __device__ __forceinline__ float swish_fast_w(float v) { return v * __builtin_amdgcn_rcpf(1.0f + __expf(-v)); }
 
 // ROWS = input stride (1 or 2) when the tile is 4 rows x 32 pixels (each wave then owns one tile row and every LDS operand
 // address in the pixel loop is base + immediate: no VALU between the MFMAs); ROWS = 0 is the generic tile shape.
-template <int ROWS>
+// DROP: the recomputed activation is the forward's dropped one, kept ? swish(..) * inv_keep : 0; a slot's keep bit is fetched beside
+// its activation, under the same in-image test (padding and missing channels read no bit).  Compile-time variant.
+template <int ROWS, bool DROP = false>
 __global__ __launch_bounds__(NTHREADS) void conv_wgrad_kernel(const WgradK p) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   float* sY = smem;                          // [BM][DYROW]; reused for the cross-wave reduction
@@ -99,6 +104,7 @@ __global__ __launch_bounds__(NTHREADS) void conv_wgrad_kernel(const WgradK p) {
 
   float xr[NXS], yr[NYS];
   unsigned xlive = 0;   // bit i: slot i holds a real input element (not zero padding / a missing channel)
+  unsigned xkeep = 0;   // DROP: bit i = keep decision of slot i (0 where the slot is not live)
   // dY staging: element e = i*256 + tid -> pixel e % 128 (fixed per thread: consecutive lanes read consecutive pixels,
   // coalesced), channel e / 128 = 2*i + (tid >> 7)
   const int ypix = tid & (BNP - 1);
@@ -116,6 +122,7 @@ __global__ __launch_bounds__(NTHREADS) void conv_wgrad_kernel(const WgradK p) {
     tile_origin(t, b, vy0, vx0);
     const int iy0 = vy0 * p.in_stride + p.dy_min, ix0 = vx0 * p.in_stride + p.dx_min;
     xlive = 0;
+    if constexpr (DROP) xkeep = 0;
 #pragma unroll
     for (int i = 0; i < NXS; ++i) {
       float v = 0.f;
@@ -126,6 +133,10 @@ __global__ __launch_bounds__(NTHREADS) void conv_wgrad_kernel(const WgradK p) {
           const float* src = (c < p.C0) ? p.x0 + ((size_t)b * p.C0 + c) * HW : p.x1 + ((size_t)b * p.C1 + (c - p.C0)) * HW;
           v = src[(size_t)iy * p.W + ix];
           xlive |= 1u << i;
+          if constexpr (DROP) {     // x1 == NULL and B * Cin * H * W < 2^31 (checked on the host)
+            const unsigned e = (unsigned)(b * p.Cin + c) * (unsigned)HW + (unsigned)(iy * p.W + ix);
+            xkeep |= ((p.keep_bits[e >> 5] >> (e & 31u)) & 1u) << i;
+          }
         }
       }
       xr[i] = v;
@@ -152,6 +163,7 @@ __global__ __launch_bounds__(NTHREADS) void conv_wgrad_kernel(const WgradK p) {
       if (x_pos[i] >= 0) {
         float v = xr[i];
         if (has_gn && ((xlive >> i) & 1u)) v = swish_fast_w(fmaf(v, sG[x_pos[i] >> 20], sG[p.CKW + (x_pos[i] >> 20)]));
+        if constexpr (DROP) v = ((xkeep >> i) & 1u) ? v * p.inv_keep : 0.f;
         sX[(x_pos[i] >> 20) * p.PLANE + ((x_pos[i] >> 10) & 1023) * p.PWp + (x_pos[i] & 1023)] = v;
       }
     }
@@ -295,7 +307,9 @@ extern "C" int hdiff_conv2d_wgrad_workspace(const hdiff_conv_wgrad_desc* d, int*
   return HDIFF_OK;
 }
 
-extern "C" int hdiff_conv2d_wgrad(const hdiff_conv_wgrad_desc* d, float* dwp, int nsplit, hdiff_stream_t stream) {
+// keep_bits != NULL: the dropout form (hdiff_conv2d_wgrad_dropout validated the descriptor: a plain 3x3 with prologue, never a 1x1)
+static int conv2d_wgrad(const hdiff_conv_wgrad_desc* d, float* dwp, int nsplit, const unsigned* keep_bits, float inv_keep,
+                        hdiff_stream_t stream) {
   HDIFF_CHECK_ARG(d && d->x0 && d->dy && dwp, "conv2d_wgrad: null pointer");
   HDIFF_CHECK_ARG(d->C1 == 0 || d->x1, "conv2d_wgrad: C1 > 0 without x1");
   HDIFF_CHECK_ARG(d->ntaps >= 1 && d->ntaps <= HDIFF_MAX_TAPS, "conv2d_wgrad: ntaps %d out of range", d->ntaps);
@@ -305,9 +319,10 @@ extern "C" int hdiff_conv2d_wgrad(const hdiff_conv_wgrad_desc* d, float* dwp, in
                   "conv2d_wgrad: bad geometry");
   HDIFF_CHECK_ARG((d->gn_scale == nullptr) == (d->gn_shift == nullptr), "conv2d_wgrad: gn_scale/gn_shift must come together");
   if (wgrad1x1_applicable(d)) return launch_wgrad1x1(d, dwp, nsplit, (hipStream_t)stream);
-  if (wgrad3x3_applicable(d)) return launch_wgrad3x3(d, dwp, nsplit, (hipStream_t)stream);
+  if (wgrad3x3_applicable(d)) return launch_wgrad3x3(d, dwp, nsplit, (hipStream_t)stream, keep_bits, inv_keep);
 
   WgradK k{};
+  k.keep_bits = keep_bits; k.inv_keep = inv_keep;
   k.x0 = d->x0; k.x1 = d->x1; k.C0 = d->C0; k.C1 = d->C1; k.Cin = d->C0 + d->C1; k.H = d->H; k.W = d->W;
   k.gn_scale = d->gn_scale; k.gn_shift = d->gn_shift; k.dy = d->dy; k.Cout = d->Cout; k.OH = d->OH; k.OW = d->OW;
   k.VH = d->VH; k.VW = d->VW; k.in_stride = d->in_stride;
@@ -357,10 +372,16 @@ extern "C" int hdiff_conv2d_wgrad(const hdiff_conv_wgrad_desc* d, float* dwp, in
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_wgrad_kernel<0>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_wgrad_kernel<1>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_wgrad_kernel<2>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_wgrad_kernel<0, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_wgrad_kernel<1, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
   }
   dim3 grid(cdiv(d->Cout, BM), cdiv(d->CinPad, k.CKW), nsplit);
   (void)hipGetLastError();  // drop any stale error left by another HIP user in this thread
-  if (k.tw_log2 == 5 && d->in_stride == 1)
+  if (keep_bits != nullptr && k.tw_log2 == 5)          // (stride 1: checked by the dropout entry)
+    hipLaunchKernelGGL((conv_wgrad_kernel<1, true>), grid, dim3(NTHREADS), lds, (hipStream_t)stream, k);
+  else if (keep_bits != nullptr)
+    hipLaunchKernelGGL((conv_wgrad_kernel<0, true>), grid, dim3(NTHREADS), lds, (hipStream_t)stream, k);
+  else if (k.tw_log2 == 5 && d->in_stride == 1)
     hipLaunchKernelGGL(conv_wgrad_kernel<1>, grid, dim3(NTHREADS), lds, (hipStream_t)stream, k);
   else if (k.tw_log2 == 5 && d->in_stride == 2)
     hipLaunchKernelGGL(conv_wgrad_kernel<2>, grid, dim3(NTHREADS), lds, (hipStream_t)stream, k);
@@ -368,6 +389,28 @@ extern "C" int hdiff_conv2d_wgrad(const hdiff_conv_wgrad_desc* d, float* dwp, in
     hipLaunchKernelGGL(conv_wgrad_kernel<0>, grid, dim3(NTHREADS), lds, (hipStream_t)stream, k);
   HDIFF_CHECK_LAUNCH("conv_wgrad_kernel");
   return HDIFF_OK;
+}
+
+extern "C" int hdiff_conv2d_wgrad(const hdiff_conv_wgrad_desc* d, float* dwp, int nsplit, hdiff_stream_t stream) {
+  return conv2d_wgrad(d, dwp, nsplit, nullptr, 1.0f, stream);
+}
+
+// Weight gradient of hdiff_conv2d_fwd_dropout: the recomputed activation is masked and scaled like the forward's.  Same slabs, same
+// workspace query and the same ordered reduce (hdiff_conv_wgrad_unpack) as hdiff_conv2d_wgrad.
+extern "C" int hdiff_conv2d_wgrad_dropout(const hdiff_conv_wgrad_desc* d, const uint32_t* keep_bits, float inv_keep, float* dwp, int nsplit,
+                                          hdiff_stream_t stream) {
+  HDIFF_CHECK_ARG(d && keep_bits && dwp, "conv2d_wgrad_dropout: null pointer");
+  HDIFF_CHECK_ARG(inv_keep >= 1.0f && inv_keep <= 3.0e38f, "conv2d_wgrad_dropout: inv_keep = %g is not a finite 1 / keep with keep in (0, 1]",
+                  (double)inv_keep);
+  HDIFF_CHECK_ARG(d->x1 == nullptr && d->C1 == 0, "conv2d_wgrad_dropout: a concat input (x1) is not supported");
+  HDIFF_CHECK_ARG(d->gn_scale != nullptr && d->gn_shift != nullptr, "conv2d_wgrad_dropout: needs the GroupNorm + Swish prologue (gn_scale / gn_shift)");
+  bool plain = d->ntaps == 9 && d->in_stride == 1 && d->VH == d->H && d->VW == d->W && d->OH == d->H && d->OW == d->W &&
+               d->out_sy == 1 && d->out_oy == 0 && d->out_sx == 1 && d->out_ox == 0;
+  for (int t = 0; plain && t < 9; ++t) plain = d->tap_dy[t] == t / 3 - 1 && d->tap_dx[t] == t % 3 - 1;
+  HDIFF_CHECK_ARG(plain, "conv2d_wgrad_dropout: not a plain 3x3 / stride-1 / pad-1 convolution (nine taps in row-major order, output grid = input grid)");
+  HDIFF_CHECK_ARG(d->B > 0 && d->C0 > 0 && d->H > 0 && d->W > 0 && (long long)d->B * d->C0 * d->H * d->W < (1ll << 31),
+                  "conv2d_wgrad_dropout: inputs of 2^31 elements or more are not supported (32-bit bit indices)");
+  return conv2d_wgrad(d, dwp, nsplit, keep_bits, inv_keep, stream);
 }
 
 extern "C" int hdiff_conv_wgrad_unpack(const float* dwp, int nsplit, float* dw, int mode, int Cout, int Cin, int KH, int KW,

@@ -49,11 +49,17 @@ struct WgradF {
   int Cout, tiles_x, tiles_per_image, total_tiles, nsplit;
   int CinPad, CoutPad;
   float* dwp;
+  // train-mode dropout behind the prologue (hdiff_conv2d_wgrad_dropout, the DROP instantiation): see conv3x3_x3.hip
+  const unsigned* keep_bits;
+  float inv_keep;
 };
 
 __device__ __forceinline__ float swish_w3(float v) { return v * __builtin_amdgcn_rcpf(1.0f + __expf(-v)); }
 
-template <bool GN>
+// DROP: the recomputed activation is the forward's dropped one, kept ? swish(..) * inv_keep : 0 -- the keep bits of a thread's 17
+// patch elements are fetched with them (from the element index the activation is read at: padding elements read the bit of the
+// tile's safe element, which is discarded) into one mask register.  Compile-time: the other instantiations carry none of it.
+template <bool GN, bool DROP = false>
 __global__ __launch_bounds__(FT) void conv_wgrad3x3_kernel(const WgradF p) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -100,6 +106,7 @@ __global__ __launch_bounds__(FT) void conv_wgrad3x3_kernel(const WgradF p) {
   float4 yr[NY4];
   float gsc = 1.f, gsh = 0.f;
   unsigned xbad = 0;        // bit i: element i of the tile in flight lies outside the image (zero padding)
+  unsigned xkeep = 0;       // DROP: bit i = keep decision of element i
 
   auto tile_origin = [&](int t, int& b, int& y0, int& x0) {
     b = t / p.tiles_per_image;
@@ -116,6 +123,15 @@ __global__ __launch_bounds__(FT) void conv_wgrad3x3_kernel(const WgradF p) {
     xbad = (top ? m_top : 0u) | (bottom ? m_bot : 0u) | (left ? m_left : 0u) | (right ? m_right : 0u);
 #pragma unroll
     for (int i = 0; i < NXE; ++i) xr[i] = xs[((xbad >> i) & 1u) ? xsafe : xoff[i]];     // branch-free; zeroed when stored
+    if constexpr (DROP) {     // x1 == NULL and B * Cin * H * W < 2^31 (checked on the host): cg < C0 = Cin
+      const unsigned e0 = (unsigned)(b * p.Cin + cg) * (unsigned)HW + (unsigned)((y0 - 1) * p.W + (x0 - 1));     // wraps like the pointer: + offset >= W + 1
+      xkeep = 0;
+#pragma unroll
+      for (int i = 0; i < NXE; ++i) {
+        const unsigned e = e0 + (unsigned)(((xbad >> i) & 1u) ? xsafe : xoff[i]);
+        xkeep |= ((p.keep_bits[e >> 5] >> (e & 31u)) & 1u) << i;
+      }
+    }
     if (GN) {
       gsc = p.gn_scale[(size_t)b * p.Cin + cg];
       gsh = p.gn_shift[(size_t)b * p.Cin + cg];
@@ -131,7 +147,8 @@ __global__ __launch_bounds__(FT) void conv_wgrad3x3_kernel(const WgradF p) {
     for (int i = 0; i < NXE; ++i) {
       float v = xr[i];
       if (GN) v = swish_w3(fmaf(v, gsc, gsh));
-      sX[xlds[i]] = ((xbad >> i) & 1u) ? 0.f : v;             // the conv pads the ACTIVATED tensor with zeros
+      if constexpr (DROP) sX[xlds[i]] = (((xbad | ~xkeep) >> i) & 1u) ? 0.f : v * p.inv_keep;
+      else sX[xlds[i]] = ((xbad >> i) & 1u) ? 0.f : v;             // the conv pads the ACTIVATED tensor with zeros
     }
     const int pix = yrow * 32 + yc4 * 4;
 #pragma unroll
@@ -372,8 +389,10 @@ int wgrad3x3_nsplit(const hdiff_conv_wgrad_desc* d) {
   return ns < 1 ? 1 : ns;
 }
 
-int launch_wgrad3x3(const hdiff_conv_wgrad_desc* d, float* dwp, int nsplit, hipStream_t stream) {
+int launch_wgrad3x3(const hdiff_conv_wgrad_desc* d, float* dwp, int nsplit, hipStream_t stream, const unsigned* keep_bits,
+                    float inv_keep) {
   WgradF k{};
+  k.keep_bits = keep_bits; k.inv_keep = inv_keep;
   k.x = d->x0; k.x1 = d->x1; k.C0 = d->C0; k.C1 = d->C1; k.Cin = d->C0 + d->C1; k.H = d->H; k.W = d->W;
   k.gn_scale = d->gn_scale; k.gn_shift = d->gn_shift; k.dy = d->dy; k.Cout = d->Cout;
   k.tiles_x = d->W / 32;
@@ -386,10 +405,13 @@ int launch_wgrad3x3(const hdiff_conv_wgrad_desc* d, float* dwp, int nsplit, hipS
   if (first_use_on_device(attr_mask)) {
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_wgrad3x3_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_wgrad3x3_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_wgrad3x3_kernel<true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
   }
   dim3 grid(d->Cout / FM, k.Cin / FC, nsplit);
   (void)hipGetLastError();  // drop any stale error left by another HIP user in this thread
-  if (d->gn_scale)
+  if (keep_bits)
+    hipLaunchKernelGGL((conv_wgrad3x3_kernel<true, true>), grid, dim3(FT), lds, stream, k);
+  else if (d->gn_scale)
     hipLaunchKernelGGL(conv_wgrad3x3_kernel<true>, grid, dim3(FT), lds, stream, k);
   else
     hipLaunchKernelGGL(conv_wgrad3x3_kernel<false>, grid, dim3(FT), lds, stream, k);

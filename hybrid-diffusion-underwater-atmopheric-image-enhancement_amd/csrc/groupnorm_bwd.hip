@@ -6,6 +6,9 @@
 // pass 1: per (sample, channel) plane  p1 = sum dy, p2 = sum dy * xhat
 // pass 2: tiny -- group sums s1, s2 and the parameter gradients
 // pass 3: elementwise dx (dy recomputed), written to the two halves of the virtual concat input
+// DROP (hdiff_gn_swish_dropout_bwd): a train-mode dropout sat between the Swish and the consumer, so dA is read as
+// kept ? dA * inv_keep : 0 in passes 1 and 3 (bit (e & 31) of keep_bits[e >> 5] for the flat element index e) -- no masked copy
+// of dA is ever written.  A compile-time variant of the two streaming kernels.
 #include "common.h"
 
 using namespace hdiff;
@@ -28,12 +31,17 @@ __device__ __forceinline__ float dswish_times(float da, float y) {
   return da * sg * (1.0f + y * (1.0f - sg));
 }
 
-template <bool SWISH>
+__device__ __forceinline__ float dropped(float da, const unsigned* __restrict__ keep_bits, size_t e, float inv_keep) {
+  return ((keep_bits[e >> 5] >> (e & 31u)) & 1u) ? da * inv_keep : 0.f;
+}
+
+template <bool SWISH, bool DROP = false>
 __global__ __launch_bounds__(T) void gn_bwd_reduce_kernel(const float* __restrict__ x0, const float* __restrict__ x1, int C0,
                                                           int C1, int HW, int G, const float* __restrict__ dA,
                                                           const float* __restrict__ mean, const float* __restrict__ rstd,
                                                           const float* __restrict__ gamma, const float* __restrict__ beta,
-                                                          float* __restrict__ p1, float* __restrict__ p2) {
+                                                          float* __restrict__ p1, float* __restrict__ p2,
+                                                          const unsigned* __restrict__ keep_bits, float inv_keep) {
   __shared__ float red[4];
   const int C = C0 + C1, cpg = C / G;
   const int bc = blockIdx.x, b = bc / C, c = bc - b * C;
@@ -44,7 +52,8 @@ __global__ __launch_bounds__(T) void gn_bwd_reduce_kernel(const float* __restric
   float s1 = 0.f, s2 = 0.f;
   for (int i = threadIdx.x; i < HW; i += T) {
     const float xh = (xp[i] - mu) * rs;
-    const float dy = SWISH ? dswish_times(dp[i], fmaf(xh, ga, be)) : dp[i];
+    const float da = DROP ? dropped(dp[i], keep_bits, (size_t)bc * HW + i, inv_keep) : dp[i];
+    const float dy = SWISH ? dswish_times(da, fmaf(xh, ga, be)) : da;
     s1 += dy;
     s2 = fmaf(dy, xh, s2);
   }
@@ -84,13 +93,14 @@ __global__ void gn_bwd_finalize_kernel(const float* __restrict__ p1, const float
   }
 }
 
-template <bool SWISH>
+template <bool SWISH, bool DROP = false>
 __global__ __launch_bounds__(T) void gn_bwd_apply_kernel(const float* __restrict__ x0, const float* __restrict__ x1, int C0,
                                                          int C1, int HW, int G, const float* __restrict__ dA,
                                                          const float* __restrict__ mean, const float* __restrict__ rstd,
                                                          const float* __restrict__ gamma, const float* __restrict__ beta,
                                                          const float* __restrict__ gs1, const float* __restrict__ gs2,
-                                                         float* __restrict__ dx0, float* __restrict__ dx1) {
+                                                         float* __restrict__ dx0, float* __restrict__ dx1,
+                                                         const unsigned* __restrict__ keep_bits, float inv_keep) {
   const int C = C0 + C1, cpg = C / G;
   const int bc = blockIdx.x, b = bc / C, c = bc - b * C;   // plane index on x: B*C may exceed 65 535
   const int g = c / cpg;
@@ -102,7 +112,8 @@ __global__ __launch_bounds__(T) void gn_bwd_apply_kernel(const float* __restrict
   const float* dp = dA + (size_t)bc * HW;
   for (int i = blockIdx.y * T + threadIdx.x; i < HW; i += gridDim.y * T) {
     const float xh = (xp[i] - mu) * rs;
-    const float dy = SWISH ? dswish_times(dp[i], fmaf(xh, ga, be)) : dp[i];
+    const float da = DROP ? dropped(dp[i], keep_bits, (size_t)bc * HW + i, inv_keep) : dp[i];
+    const float dy = SWISH ? dswish_times(da, fmaf(xh, ga, be)) : da;
     op[i] = rs * (ga * dy - m1 - xh * m2);
   }
 }
@@ -155,24 +166,24 @@ __global__ void batch_sum_kernel(const float* __restrict__ dvec, int B, int C, f
 }  // namespace
 
 namespace {
-template <bool SWISH>
+template <bool SWISH, bool DROP = false>
 int gn_bwd_launch(const float* x0, const float* x1, int C0, int C1, int B, int HW, int G, const float* dA, const float* mean,
                   const float* rstd, const float* gamma, const float* beta, float* ws, float* dx0, float* dx1, float* dgamma,
-                  float* dbeta, hipStream_t s) {
+                  float* dbeta, hipStream_t s, const unsigned* keep_bits = nullptr, float inv_keep = 1.0f) {
   const int C = C0 + C1;
   float* p1 = ws;                 // [B][C]
   float* p2 = ws + (size_t)B * C; // [B][C]
   float* gs1 = p2 + (size_t)B * C; // [B][G]
   float* gs2 = gs1 + (size_t)B * G;
   (void)hipGetLastError();  // drop any stale error left by another HIP user in this thread
-  hipLaunchKernelGGL(gn_bwd_reduce_kernel<SWISH>, dim3(B * C), dim3(T), 0, s, x0, x1, C0, C1, HW, G, dA, mean, rstd, gamma, beta,
-                     p1, p2);
+  hipLaunchKernelGGL((gn_bwd_reduce_kernel<SWISH, DROP>), dim3(B * C), dim3(T), 0, s, x0, x1, C0, C1, HW, G, dA, mean, rstd, gamma, beta,
+                     p1, p2, keep_bits, inv_keep);
   const int n = (C > B * G ? C : B * G);
   hipLaunchKernelGGL(gn_bwd_finalize_kernel, dim3(cdiv(n, 256)), dim3(256), 0, s, p1, p2, gamma, B, C, G, gs1, gs2, dgamma,
                      dbeta);
   const int bx = cdiv(HW, T) < 32 ? cdiv(HW, T) : 32;
-  hipLaunchKernelGGL(gn_bwd_apply_kernel<SWISH>, dim3(B * C, bx), dim3(T), 0, s, x0, x1, C0, C1, HW, G, dA, mean, rstd, gamma,
-                     beta, gs1, gs2, dx0, dx1);
+  hipLaunchKernelGGL((gn_bwd_apply_kernel<SWISH, DROP>), dim3(B * C, bx), dim3(T), 0, s, x0, x1, C0, C1, HW, G, dA, mean, rstd, gamma,
+                     beta, gs1, gs2, dx0, dx1, keep_bits, inv_keep);
   HDIFF_CHECK_LAUNCH("gn backward kernels");
   return HDIFF_OK;
 }
@@ -186,6 +197,18 @@ extern "C" int hdiff_gn_swish_bwd(const float* x0, const float* x1, int C0, int 
   HDIFF_CHECK_ARG(G > 0 && (C0 + C1) % G == 0 && B > 0 && HW > 0, "gn_swish_bwd: bad sizes");
   return gn_bwd_launch<true>(x0, x1, C0, C1, B, HW, G, dA, mean, rstd, gamma, beta, ws, dx0, dx1, dgamma, dbeta,
                              (hipStream_t)stream);
+}
+
+// hdiff_gn_swish_bwd behind a dropout: dA is the gradient w.r.t. the DROPPED activation (the conv's input); x is one tensor
+extern "C" int hdiff_gn_swish_dropout_bwd(const float* x, int C, int B, int HW, int G, const float* dA, const uint32_t* keep_bits,
+                                          float inv_keep, const float* mean, const float* rstd, const float* gamma, const float* beta,
+                                          float* ws, float* dx, float* dgamma, float* dbeta, hdiff_stream_t stream) {
+  HDIFF_CHECK_ARG(x && dA && keep_bits && mean && rstd && gamma && beta && ws && dx && dgamma && dbeta, "gn_swish_dropout_bwd: null pointer");
+  HDIFF_CHECK_ARG(inv_keep >= 1.0f && inv_keep <= 3.0e38f, "gn_swish_dropout_bwd: inv_keep = %g is not a finite 1 / keep with keep in (0, 1]",
+                  (double)inv_keep);
+  HDIFF_CHECK_ARG(G > 0 && C > 0 && C % G == 0 && B > 0 && HW > 0, "gn_swish_dropout_bwd: bad sizes");
+  return gn_bwd_launch<true, true>(x, nullptr, C, 0, B, HW, G, dA, mean, rstd, gamma, beta, ws, dx, nullptr, dgamma, dbeta,
+                                   (hipStream_t)stream, keep_bits, inv_keep);
 }
 
 extern "C" int hdiff_gn_affine_bwd(const float* x, int C, int B, int HW, int G, const float* dY, const float* mean,

@@ -319,6 +319,26 @@ __global__ void dropout_mask_kernel(float* __restrict__ out, int64_t n, float ke
     }
   }
 }
+// The same keep decisions as ONE BIT each: bit (i & 31) of word (i >> 5) is set exactly where dropout_mask_kernel writes a non-zero
+// value for element i (same Philox counter q = i / 4, same compare); unused bits of the last word are 0.  One thread per word
+// (eight Philox calls), so no two threads write the same word.
+__global__ void dropout_keep_bits_kernel(uint32_t* __restrict__ bits, int64_t n, float keep, uint64_t seed, uint64_t offset) {
+  const int64_t nw = (n + 31) >> 5;
+  for (int64_t w = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; w < nw; w += (int64_t)gridDim.x * blockDim.x) {
+    uint32_t word = 0;
+    for (int j = 0; j < 8; ++j) {
+      const int64_t q = (w << 3) + j;
+      if ((q << 2) >= n) break;
+      uint32_t r[4];
+      philox4x32_10(seed, (uint64_t)q, offset, r);
+      for (int e = 0; e < 4; ++e) {
+        const int64_t i = (q << 2) + e;
+        if (i < n && (float)(r[e] >> 8) * (1.0f / 16777216.0f) < keep) word |= 1u << (4 * j + e);
+      }
+    }
+    bits[w] = word;
+  }
+}
 __global__ void mul_kernel(const float* __restrict__ a, const float* __restrict__ b, float* __restrict__ out, int64_t n) {
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
     out[i] = a[i] * b[i];
@@ -476,6 +496,17 @@ int hdiff_dropout_mask(float* out, int64_t n, float keep, uint64_t seed, uint64_
   (void)hipGetLastError();  // drop any stale error left by another HIP user in this thread
   hipLaunchKernelGGL(dropout_mask_kernel, dim3(grid_for(n, 4)), dim3(256), 0, (hipStream_t)stream, out, n, keep, seed, offset);
   HDIFF_CHECK_LAUNCH("dropout_mask_kernel");
+  return HDIFF_OK;
+}
+
+int hdiff_dropout_keep_bits(uint32_t* bits, int64_t n, float keep, uint64_t seed, uint64_t offset, hdiff_stream_t stream) {
+  HDIFF_CHECK_ARG(bits, "dropout_keep_bits: null pointer");
+  HDIFF_CHECK_ARG(n > 0, "dropout_keep_bits: n = %lld is not positive", (long long)n);
+  HDIFF_CHECK_ARG(keep > 0.f && keep <= 1.f, "dropout_keep_bits: keep = %g is outside (0, 1]", (double)keep);
+  (void)hipGetLastError();  // drop any stale error left by another HIP user in this thread
+  hipLaunchKernelGGL(dropout_keep_bits_kernel, dim3(grid_for((n + 31) >> 5)), dim3(256), 0, (hipStream_t)stream, bits, n, keep, seed,
+                     offset);
+  HDIFF_CHECK_LAUNCH("dropout_keep_bits_kernel");
   return HDIFF_OK;
 }
 

@@ -275,10 +275,13 @@ class Plan:
              out: torch.Tensor, *, B: int, H: int, W: int, VH: int, VW: int, in_stride: int = 1,
              out_map: Tuple[int, int, int, int] = (1, 0, 1, 0), gn: Optional[Tuple[torch.Tensor, torch.Tensor]] = None,
              addvec: Optional[torch.Tensor] = None, residual: Optional[torch.Tensor] = None,
-             act_range: Optional[Tuple[torch.Tensor, torch.Tensor, int, float]] = None) -> None:
+             act_range: Optional[Tuple[torch.Tensor, torch.Tensor, int, float]] = None,
+             dropout: Optional[Tuple[torch.Tensor, float]] = None) -> None:
         """act_range = (gamma, beta, group_elems, gain): the input tensor itself is gain * swish(GroupNorm(gamma, beta)(.)) of
-        groups of group_elems elements (an activation materialised by the caller, e.g. behind a dropout mask) -- what the
-        fp16-pair 3x3 kernel needs to know about its range; with ``gn`` from gn_scale_shift() the plan knows it already."""
+        groups of group_elems elements (an activation materialised by the caller, or the prologue's output behind a dropout
+        scaled by gain) -- what the fp16-pair 3x3 kernel needs to know about its range; with ``gn`` from gn_scale_shift() the
+        plan knows it already.  dropout = (keep bits, fp32 1 / keep): train-mode dropout between the prologue and the conv
+        (hdiff_conv2d_fwd_dropout; a plain 3x3 conv with ``gn``)."""
         d = _capi.ConvDesc()
         C0 = int(x0.shape[1])
         C1 = int(x1.shape[1]) if x1 is not None else 0
@@ -310,9 +313,12 @@ class Plan:
         if need.value > 0:               # small grid, long channel loop: split-K partial sums + ordered reduce
             ws = self.buf(need.value)
             d.splitk_ws, d.splitk_floats = ws.data_ptr(), need.value
-        self.keep((d, x0, x1, pk, bias, out, gn, addvec, residual, ws))
+        self.keep((d, x0, x1, pk, bias, out, gn, addvec, residual, ws, dropout))
         self.flops += 2.0 * pk.ntaps * pk.cin * pk.cout * VH * VW * B
-        self.call("hdiff_conv2d_fwd", C.byref(d))
+        if dropout is not None:
+            self.call("hdiff_conv2d_fwd_dropout", C.byref(d), dropout[0].data_ptr(), C.c_float(dropout[1]))
+        else:
+            self.call("hdiff_conv2d_fwd", C.byref(d))
         if ws is not None:
             self.free(ws)
 

@@ -84,8 +84,9 @@ int hdiff_pack_conv_weight_h2(const float* w, void* wp2, int Cout, int Cin, int 
 /* (ABI 5) Range of a GroupNorm + Swish output from the GroupNorm weights alone: |swish(gamma * xhat + beta)| <=
  * sqrt(n - 1) * max |gamma| + max |beta| =: A for groups of n = group_elems elements (a normalised value cannot leave
  * [-sqrt(n - 1), sqrt(n - 1)]).  out2[0] = 2^s, out2[1] = 2^-s with gain * A * 2^s in [2^13, 2^14): the power of two by which
- * the fp16-pair conv stages its activations (hdiff_conv_desc.act_scale); gain = 1, or 1 / keep when a dropout mask scaled by
- * 1 / keep sits between the activation and the conv (ModelCondition.py:185).  nn.GroupNorm at ModelCondition.py:169, 182. */
+ * the fp16-pair conv stages its activations (hdiff_conv_desc.act_scale); gain = 1, or 1 / keep when a dropout scaled by
+ * 1 / keep sits between the activation and the conv (ModelCondition.py:185) -- applied inside the prologue by
+ * hdiff_conv2d_fwd_dropout, or by the caller on a materialised tensor.  nn.GroupNorm at ModelCondition.py:169, 182. */
 int hdiff_gn_act_scale(const float* gamma, const float* beta, int C, int64_t group_elems, float gain, float* out2,
                        hdiff_stream_t stream);
 
@@ -142,6 +143,15 @@ typedef struct hdiff_conv_desc {
 
 int hdiff_conv2d_fwd_workspace(const hdiff_conv_desc* d, int64_t* floats_out);
 int hdiff_conv2d_fwd(const hdiff_conv_desc* d, hdiff_stream_t stream);
+/* conv(dropout(swish(GroupNorm(x)))) as ONE launch: nn.Dropout in train mode between Swish and block2's conv
+ * (ModelCondition.py:184-186).  The staged activation is kept ? swish(x * gn_scale + gn_shift) * inv_keep : 0, where the keep
+ * decision of the element with flat NCHW index e of x0 is bit (e & 31) of keep_bits[e >> 5] (hdiff_dropout_keep_bits) and
+ * inv_keep is the fp32 1 / keep.  Served by every kernel hdiff_conv2d_fwd dispatches such a conv to (both contraction modes,
+ * split-K included; same workspace query).  The descriptor must be a plain 3x3 / stride-1 / pad-1 conv (nine taps in row-major
+ * order, output grid = input grid) WITH gn_scale / gn_shift, without x1, C0 % 8 == 0, fewer than 2^31 input elements;
+ * act_scale, when set, must have been computed with gain = 1 / keep.  Anything else is HDIFF_ERR_INVALID, nothing is launched.
+ * Padding positions stage 0 and use no keep bit; no word outside the ceil(B*C0*H*W / 32) words is read. */
+int hdiff_conv2d_fwd_dropout(const hdiff_conv_desc* d, const uint32_t* keep_bits, float inv_keep, hdiff_stream_t stream);
 
 /* Weight gradient of hdiff_conv2d_fwd (autograd of the conv weights, TrainCondition.py:60).  Same geometry fields as the
  * forward descriptor; dy is the gradient of the forward's `out`.  The kernel writes `nsplit` packed partial slabs
@@ -166,6 +176,11 @@ typedef struct hdiff_conv_wgrad_desc {
 } hdiff_conv_wgrad_desc;
 int hdiff_conv2d_wgrad_workspace(const hdiff_conv_wgrad_desc* d, int* nsplit_out, int64_t* floats_out);
 int hdiff_conv2d_wgrad(const hdiff_conv_wgrad_desc* d, float* dwp, int nsplit, hdiff_stream_t stream);
+/* Weight gradient of hdiff_conv2d_fwd_dropout: the activation recomputed from x0 is masked and scaled like the forward's
+ * (same descriptor rules, same keep_bits / inv_keep).  Workspace and nsplit from hdiff_conv2d_wgrad_workspace; same slabs and
+ * the same ordered reduce (hdiff_conv_wgrad_unpack): no atomics, bitwise repeatable. */
+int hdiff_conv2d_wgrad_dropout(const hdiff_conv_wgrad_desc* d, const uint32_t* keep_bits, float inv_keep, float* dwp, int nsplit,
+                               hdiff_stream_t stream);
 int hdiff_conv_wgrad_unpack(const float* dwp, int nsplit, float* dw, int mode, int Cout, int Cin, int KH, int KW, int ntaps,
                             const int* tap_ky, const int* tap_kx, int CinPad, int CoutPad, int accumulate,
                             hdiff_stream_t stream);
@@ -194,6 +209,12 @@ int hdiff_gn_scale_shift(const float* x0, const float* x1, int C0, int C1, int B
 int hdiff_gn_swish_bwd(const float* x0, const float* x1, int C0, int C1, int B, int HW, int G, const float* dA,
                        const float* mean, const float* rstd, const float* gamma, const float* beta, float* ws, float* dx0,
                        float* dx1, float* dgamma, float* dbeta, hdiff_stream_t stream);
+/* hdiff_gn_swish_bwd behind a dropout (the backward of hdiff_conv2d_fwd_dropout's prologue): dA [B][C][HW] is the gradient
+ * w.r.t. the DROPPED activation and is read as kept ? dA * inv_keep : 0 in both passes that use it; x is one tensor.
+ * ws: 2*B*C + 2*B*G floats. */
+int hdiff_gn_swish_dropout_bwd(const float* x, int C, int B, int HW, int G, const float* dA, const uint32_t* keep_bits,
+                               float inv_keep, const float* mean, const float* rstd, const float* gamma, const float* beta,
+                               float* ws, float* dx, float* dgamma, float* dbeta, hdiff_stream_t stream);
 /* The same for GroupNorm WITHOUT Swish (AttnBlock's pre-norm, ModelCondition.py:103): dY is the gradient w.r.t. the
  * normalised tensor [B][C][HW].  ws: 2*B*C + 2*B*G floats. */
 int hdiff_gn_affine_bwd(const float* x, int C, int B, int HW, int G, const float* dY, const float* mean, const float* rstd,
@@ -204,7 +225,7 @@ int hdiff_bias_addvec_grad(const float* dy, int B, int C, int HW, float* dvec, f
 /* y = x*scale[b][c] + shift[b][c]: GroupNorm without Swish (AttnBlock, ModelCondition.py:103) */
 int hdiff_gn_affine_apply(const float* x, const float* scale, const float* shift, float* y, int B, int C, int HW,
                           hdiff_stream_t stream);
-/* Stand-alone y = swish(x*scale+shift) (used by tests and by the training path). */
+/* Stand-alone y = swish(x*scale+shift) (a plain Swish with scale 1 / shift 0 in the embedding MLPs; tests build references from it). */
 int hdiff_gn_swish_apply(const float* x, const float* scale, const float* shift, float* y, int B, int C, int HW,
                          hdiff_stream_t stream);
 
@@ -414,9 +435,15 @@ int hdiff_grad_norm_clip_coef(const hdiff_opt_tensor* table, const int* chunks, 
                               float* norm_coef, hdiff_stream_t stream);
 int hdiff_adamw_step(const hdiff_opt_tensor* table, const int* chunks, int nchunks, const float* norm_coef, double lr, double beta1,
                      double beta2, double eps, double weight_decay, int64_t step, hdiff_stream_t stream);
-/* nn.Dropout (train mode, ModelCondition.py:185): keep-mask scaled by 1/keep from the Philox stream, and out = a*b */
+/* nn.Dropout (train mode, ModelCondition.py:185) in its unfused form: keep-mask scaled by 1/keep from the Philox stream, and out = a*b
+ * (the training path uses the keep bits below; these two remain for callers that want the tensors) */
 int hdiff_dropout_mask(float* out, int64_t n, float keep, uint64_t seed, uint64_t offset, hdiff_stream_t stream);
 int hdiff_mul(const float* a, const float* b, float* out, int64_t n, hdiff_stream_t stream);
+/* The keep decisions of hdiff_dropout_mask(out, n, keep, seed, offset) as one bit each: bit (i & 31) of bits[i >> 5] is 1 exactly
+ * where that call writes a non-zero value for element i (same Philox stream, same compare); ceil(n / 32) words, unused bits
+ * of the last word are 0.  What the fused dropout entries (hdiff_conv2d_fwd_dropout, hdiff_conv2d_wgrad_dropout,
+ * hdiff_gn_swish_dropout_bwd) read, and all that a training step keeps of a dropout.  n > 0, keep in (0, 1]. */
+int hdiff_dropout_keep_bits(uint32_t* bits, int64_t n, float keep, uint64_t seed, uint64_t offset, hdiff_stream_t stream);
 /* standard-normal fill with the same Philox stream (used for in-graph noise and for tests of the generator) */
 int hdiff_randn(float* out, int64_t n, uint64_t seed, uint64_t offset, hdiff_stream_t stream);
 
