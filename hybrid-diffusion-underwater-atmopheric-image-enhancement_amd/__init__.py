@@ -23,7 +23,7 @@ from ._capi import build, lib
 __all__ = ["build", "lib", "install_dropin", "UNet", "GaussianDiffusionTrainer", "GaussianDiffusionSampler", "extract",
            "set_contraction_mode", "get_contraction_mode", "reserve_split_workspace"]
 
-_CONTRACT = {"f32": 0, "bf16x3": 1}
+_CONTRACT = {"f32": 0, "bf16x3": 1, "f16": 2}
 
 
 def set_contraction_mode(mode: str) -> None:
@@ -38,8 +38,17 @@ def set_contraction_mode(mode: str) -> None:
     i + j <= 2).  fp32-class accuracy: the error against float64 is <= 1.25x (attention) / 1.5x (conv) the fp32 kernels' rms
     (tests/test_gpu_ops.py, tests/test_gpu_backward.py), the whole golden / oracle suite passes in this mode at the fp32 tolerances
     (tests/conftest.py), mutants of each dropped-term class turn the gates red (tests/test_gpu_mutation.py).  ``"f32"``: the
-    fp32-input MFMA (an exact k-ordered fma chain), about 2.1x slower per step at 256x256.  The environment variable
-    ``HDIFF_CONTRACT`` sets the initial value."""
+    fp32-input MFMA (an exact k-ordered fma chain), about 2.1x slower per step at 256x256.
+
+    ``"f16"`` (opt-in, for SAMPLING): everything runs exactly what ``"bf16x3"`` runs, except the attention forward of inference
+    (no log-sum-exp asked for, d_head 16 / 32, L >= 512, L % 256 == 0, a plan's workspace): there q, k, v and the softmax weights
+    each travel as ONE fp16 number with fp32 accumulation (attention_f16.hip).  In plain words: half-precision operands.  An
+    attention output is then off by about 1e-4 .. 5e-4 (rms, relative to the channel's largest output; 3e-3 where the softmax
+    is nearly uniform) instead of 1e-6, and a 64x64 default-model forward by about 6e-5 rms on an output of rms 0.3 -- fine for
+    drawing samples, NOT for the golden tolerances.  Training in this mode is training in the default mode: the autograd
+    forward asks for the log-sum-exp and never reaches the fp16 kernels.
+
+    The environment variable ``HDIFF_CONTRACT`` sets the initial value."""
     if mode not in _CONTRACT:
         raise ValueError(f"contraction mode must be one of {sorted(_CONTRACT)}, got {mode!r}")
     _capi.check(lib().hdiff_set_contraction_mode(_CONTRACT[mode]), "set_contraction_mode")

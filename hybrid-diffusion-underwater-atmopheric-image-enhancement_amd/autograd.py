@@ -358,7 +358,7 @@ class _FlashFn(Function):
         need = C.c_int64(0)
         _capi.check(lib.hdiff_mha_flash_fwd_workspace(B, Cc, NUM_HEADS, L, C.byref(need)), "mha_flash_fwd_workspace")
         # scratch of the pre-split (bf16x3) forward: only allocated when that mode is on; freed when this call returns
-        ws = torch.empty(need.value // 4 + 1, device=qkv.device) if need.value > 0 and lib.hdiff_get_contraction_mode() == 1 else None
+        ws = torch.empty(need.value // 4 + 1, device=qkv.device) if need.value > 0 and lib.hdiff_get_contraction_mode() != 0 else None
         _capi.check(lib.hdiff_mha_flash_fwd_ws(qkv.data_ptr(), o.data_ptr(), lse.data_ptr(), B, Cc, NUM_HEADS, L,
                                                None if ws is None else ws.data_ptr(), 0 if ws is None else need.value,
                                                _stream(qkv.device)), "mha_flash_fwd")

@@ -548,8 +548,10 @@ int launch_d(const float* qkv, float* o, float* lse2, int B, int C, int heads, i
   } else {
     int nq = (L >= 512) ? 4 : 1;   // 4 query tiles per wave: 3 waves per SIMD at d_head 16, 2 at d_head 32 (8 tiles measured no faster)
     // d_head 32 on the fixed-reference kernel: 134 TFLOP/s against 120 on the running-max kernel (L = 16 384, batch 16)
-    if (nq == 4 && contraction_mode() == HDIFF_CONTRACT_BF16X3 &&
-        (launch_mha_fwd_h2(qkv, o, lse2, B, C, heads, L, qscale, ws, ws_bytes, stream) ||       // d_head 16, fp16 pairs (needs the workspace)
+    if (nq == 4 && split_operands_on() &&
+        ((contraction_mode() == HDIFF_CONTRACT_F16 &&
+          launch_mha_fwd_f16(qkv, o, lse2, B, C, heads, L, qscale, ws, ws_bytes, stream)) ||     // f16 mode, no lse: single fp16 pieces
+         launch_mha_fwd_h2(qkv, o, lse2, B, C, heads, L, qscale, ws, ws_bytes, stream) ||       // d_head 16, fp16 pairs (needs the workspace)
          launch_mha_fwd_x3p(qkv, o, lse2, B, C, heads, L, qscale, ws, ws_bytes, stream) ||      // d_head 32, fp16 pairs (needs the workspace)
          launch_mha_fwd_x3(qkv, o, lse2, B, C, heads, L, qscale, stream))) {                    // bf16 triples split in the loop
       // split-bf16 kernel (attention_x3.hip), same fixed-reference protocol: overflow-proof fp32 kernel in check mode behind it

@@ -1110,7 +1110,7 @@ bool mha_bwd_x3_shape_ok(int B, int C, int heads, int L) {
   return C % heads == 0 && (D == 16 || D == 32) && L % 256 == 0 && L >= 512 && (int64_t)B * heads * (L / 128) >= 256;
 }
 bool mha_bwd_x3_applicable(int B, int C, int heads, int L) {
-  return contraction_mode() == HDIFF_CONTRACT_BF16X3 && mha_bwd_x3_shape_ok(B, C, heads, L);
+  return split_operands_on() && mha_bwd_x3_shape_ok(B, C, heads, L);
 }
 
 // slabs (tile-major, one per key range: even a single range goes through the reduce kernel, which restores the [C][L] layout)

@@ -121,6 +121,8 @@ struct Conv1x1X3K {
 void launch_conv1x1_x3(const Conv1x1X3K& k, int B, hipStream_t stream);
 
 int contraction_mode();   // HDIFF_CONTRACT_*
+// the split-operand family is on (bf16x3, and f16, which is bf16x3 everywhere but in one attention-forward dispatch)
+inline bool split_operands_on() { return contraction_mode() != HDIFF_CONTRACT_F32; }
 
 // Mutation switch of the parity suite's own sensitivity tests (tests/test_gpu_mutation.py): a library built with
 // -DHDIFF_MUTANT=<mask> silently damages ONE low-order piece product per bit, at the 2^-16 / 2^-17 level of the product --
@@ -158,5 +160,9 @@ bool launch_mha_fwd_h2(const float* qkv, float* o, float* lse2, int B, int C, in
 void launch_qk_split_h2(const float* qkv, void* ws, int B, int C, int heads, int L, float qscale, hipStream_t stream);   // Q, K as fp16 score operands
 void launch_v_split_h2(const float* qkv, void* ws, int B, int C, int heads, int L, hipStream_t stream);                  // V as fp16 pairs, d_head 16 / 32
 bool launch_mha_fwd_x3(const float* qkv, float* o, float* lse2, int B, int C, int heads, int L, float qscale, hipStream_t stream);
+// attention_f16.hip: the inference forward of the f16 mode, d_head 16 / 32, every operand ONE fp16 piece, inside the same workspace.
+// Returns false (nothing launched) unless lse2 == NULL, the shape is covered and the workspace is there.
+bool launch_mha_fwd_f16(const float* qkv, float* o, float* lse2, int B, int C, int heads, int L, float qscale, void* ws,
+                        int64_t ws_bytes, hipStream_t stream);
 
 }  // namespace hdiff

@@ -690,7 +690,7 @@ bool is_h2_conv_shape(const hdiff_conv_desc* d, bool same) {
   return same && d->ntaps == 9 && d->wp_h2 != nullptr && d->act_scale != nullptr;
 }
 bool is_x3_conv(const hdiff_conv_desc* d) {
-  if ((d->wp_x3 == nullptr && d->wp_h2 == nullptr) || hdiff::contraction_mode() != HDIFF_CONTRACT_BF16X3) return false;
+  if ((d->wp_x3 == nullptr && d->wp_h2 == nullptr) || !hdiff::split_operands_on()) return false;
   if ((d->ntaps != 9 && d->ntaps != 6 && d->ntaps != 4) || d->in_stride != 1) return false;
   if (d->VH != d->H || d->VW != d->W) return false;
   const bool same = d->out_sy == 1 && d->out_oy == 0 && d->out_sx == 1 && d->out_ox == 0 && d->OH == d->H && d->OW == d->W;
@@ -730,7 +730,7 @@ bool is_direct_1x1(const hdiff_conv_desc* d) {
 // inputs, the same GEMM runs on the bf16 MFMA (conv1x1_x3.hip).
 bool is_x3_1x1(const hdiff_conv_desc* d) {
   const int Cin = d->C0 + d->C1;
-  return d->wp_x3 != nullptr && hdiff::contraction_mode() == HDIFF_CONTRACT_BF16X3 && Cin % 16 == 0 &&
+  return d->wp_x3 != nullptr && hdiff::split_operands_on() && Cin % 16 == 0 &&
          (d->C1 == 0 || d->C0 % 16 == 0) && ((long)d->H * d->W) % 256 == 0 && d->CoutPad % 64 == 0;
 }
 }  // namespace

@@ -40,8 +40,19 @@ int hdiff_device_count(void);
  *                                       about 1.5x faster; shapes it does not cover silently use the fp32 kernels
  *                                       (attention: d_head 16/32, L % 64 == 0; conv: 3x3 stride 1 with Cin % 16 == 0 and a
  *                                       descriptor that carries wp_x3).
- * The initial value comes from the environment variable HDIFF_CONTRACT ("f32" | "bf16x3"). */
-enum { HDIFF_CONTRACT_F32 = 0, HDIFF_CONTRACT_BF16X3 = 1 };
+ *   HDIFF_CONTRACT_F16    (2, opt-in)   a mode for SAMPLING.  Everything runs what HDIFF_CONTRACT_BF16X3 runs, bit for bit,
+ *                                       except ONE dispatch: hdiff_mha_flash_fwd_ws called with lse2 == NULL (nobody will
+ *                                       differentiate through it), d_head 16 or 32, L >= 512, L % 256 == 0 and a workspace of
+ *                                       hdiff_mha_flash_fwd_workspace bytes.  That call carries each operand as ONE fp16 piece
+ *                                       (q 2^-a, k 2^a balanced per head, v 2^s per channel row; P = fp16(exp2(S)) under a
+ *                                       moving softmax reference) with fp32 accumulation (attention_f16.hip).  What it does
+ *                                       NOT change: convolutions, the attention backward, a forward that returns the
+ *                                       log-sum-exp (training), other head widths, calls without workspace.  Accuracy class:
+ *                                       half-precision operands -- the output's error against float64 is about 1e-4 .. 5e-4
+ *                                       rms of a channel's largest output (3e-3 for near-uniform rows), against about 1e-6
+ *                                       in the other two modes; NOT an fp32-class result.
+ * The initial value comes from the environment variable HDIFF_CONTRACT ("f32" | "bf16x3" | "f16"). */
+enum { HDIFF_CONTRACT_F32 = 0, HDIFF_CONTRACT_BF16X3 = 1, HDIFF_CONTRACT_F16 = 2 };
 int hdiff_set_contraction_mode(int mode);
 int hdiff_get_contraction_mode(void);
 

@@ -1,6 +1,6 @@
 """Throughput of the second tree's DDIM sampler (DynamicUNet, image-conditioned) on one MI355X.
 
-    python tools/bench_ddim.py [--size 256] [--batch 8] [--ddim-step 100] [--reps 2]
+    python tools/bench_ddim.py [--size 256] [--batch 8] [--ddim-step 100] [--reps 2] [--contract bf16x3|f32|f16]
 
 One "step" = one DDIM iteration of diffusion/Diffusion.py:248-263 for the whole batch = one DynamicUNet forward + the fused
 update.  Prints one JSON line (same field names as bench.py where they apply)."""
@@ -16,7 +16,8 @@ ap.add_argument("--size", type=int, default=256)
 ap.add_argument("--batch", type=int, default=8)
 ap.add_argument("--ddim-step", type=int, default=100)
 ap.add_argument("--reps", type=int, default=2)
-ap.add_argument("--contract", choices=["f32", "bf16x3"], default="bf16x3", help="the library's default mode is bf16x3")
+ap.add_argument("--contract", choices=["f32", "bf16x3", "f16"], default="bf16x3",
+                help="the library's default mode is bf16x3; f16: the opt-in sampling mode (single-piece fp16 attention forward)")
 a = ap.parse_args()
 hdiff_amd.set_contraction_mode(a.contract)
 dev = torch.device("cuda", 0)

@@ -1,5 +1,7 @@
 """Dev tool (round 6): what clock and board power does ONE hot kernel hold when it runs back to back?
-  python tools/kernel_power.py bwd16|bwd32|fwd16|fwd32|conv3 [batch] [seconds]      (conv3: the 128 -> 128 3x3 convolution at 256x256 behind GroupNorm, fp16 pairs)
+  python tools/kernel_power.py bwd16|bwd32|fwd16|fwd32|conv3 [batch] [seconds] [--no-lse] [--contract f32|bf16x3|f16]
+(conv3: the 128 -> 128 3x3 convolution at 256x256 behind GroupNorm, fp16 pairs; --no-lse: the forward as inference calls it, lse2 = NULL --
+with --contract f16 that is the call the single-piece fp16 kernels of attention_f16.hip take)
 Runs the launch in a loop for `seconds` (default 4) after a 1 s warm-up, samples the engine clock and the board power from sysfs at
 20 Hz (bench.ClockSampler), prints ms per launch, MHz and W.  A kernel that sits on the board's power limit trades cycles for clock:
 an instruction-count saving then shows as a higher clock at the same wall time -- read this BEFORE believing a cycle model."""
@@ -16,6 +18,13 @@ from bench import ClockSampler  # noqa: E402
 
 lib = hdiff_amd.lib()
 s = torch.cuda.current_stream().cuda_stream
+no_lse = "--no-lse" in sys.argv
+if no_lse:
+    sys.argv.remove("--no-lse")
+if "--contract" in sys.argv:
+    i = sys.argv.index("--contract")
+    hdiff_amd.set_contraction_mode(sys.argv[i + 1])
+    del sys.argv[i:i + 2]
 what = sys.argv[1] if len(sys.argv) > 1 else "bwd16"
 B = int(sys.argv[2]) if len(sys.argv) > 2 else (16 if what.startswith("fwd") else 4)
 secs = float(sys.argv[3]) if len(sys.argv) > 3 else 4.0
@@ -52,7 +61,7 @@ elif what.startswith("fwd"):
     ws = torch.empty(max(need.value, 16), dtype=torch.uint8, device="cuda")
 
     def run():
-        rc = lib.hdiff_mha_flash_fwd_ws(qkv.data_ptr(), o.data_ptr(), lse.data_ptr(), B, Cc, 8, L, ws.data_ptr(), need.value, s)
+        rc = lib.hdiff_mha_flash_fwd_ws(qkv.data_ptr(), o.data_ptr(), None if no_lse else lse.data_ptr(), B, Cc, 8, L, ws.data_ptr(), need.value, s)
         assert rc == 0, lib.hdiff_last_error()
 else:
     d_o = torch.randn(B, Cc, L, device="cuda")
@@ -89,5 +98,5 @@ ms = e0.elapsed_time(e1) / n
 c = clock.summary()
 if what == "conv3":
     ms /= 50
-print(f"{what} B={B} C={Cc} L={L}: {ms:.3f} ms per launch over {n} launches; sclk {c.get('sclk_mhz_mean')} MHz "
+print(f"{what} [{hdiff_amd.get_contraction_mode()}{', no lse' if no_lse else ''}] B={B} C={Cc} L={L}: {ms:.3f} ms per launch over {n} launches; sclk {c.get('sclk_mhz_mean')} MHz "
       f"(min {c.get('sclk_mhz_min')}, max {c.get('sclk_mhz_max')}), board {c.get('board_power_w_mean')} W", flush=True)
