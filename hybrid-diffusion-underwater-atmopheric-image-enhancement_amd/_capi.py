@@ -195,7 +195,7 @@ MUTANT2_PATH = os.path.join(CSRC, "build", "libhdiff_mutant2.so")
 
 def build_mutant(verbose: bool = False) -> str:
     """Test infrastructure (tests/test_gpu_mutation.py): the library with ONE low-order piece product damaged in each
-    split-operand kernel (csrc/common.h lists the HDIFF_MUTANT bits), and a second one with the third-piece terms of dS in the
+    split-operand kernel (csrc/device.h lists the HDIFF_MUTANT bits), and a second one with the third-piece terms of dS in the
     attention backward alone.  Never loaded by the product."""
     res = subprocess.run(["make", "-C", CSRC, "-j4", "mutant", "mutant2"], capture_output=True, text=True)
     if verbose or res.returncode != 0:

@@ -292,8 +292,7 @@ class _DownFn(Function):
             for py in (0, 1):
                 for px in (0, 1):
                     pt = E.tconv_phase_taps(py, px)
-                    k3y = [ky - 1 if (1 <= ky <= 3 and 1 <= kx <= 3) else -1 for ky, kx in zip(pt.ky, pt.kx)]
-                    k3x = [kx - 1 if (1 <= ky <= 3 and 1 <= kx <= 3) else 0 for ky, kx in zip(pt.ky, pt.kx)]
+                    k3y, k3x = _down_center_map(pt)
                     VH, VW = (H - py + 1) // 2, (W - px + 1) // 2
                     if VH <= 0 or VW <= 0:
                         continue

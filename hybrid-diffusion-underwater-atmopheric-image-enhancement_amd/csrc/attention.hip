@@ -29,6 +29,7 @@
 #include <type_traits>
 
 #include "common.h"
+#include "device.h"
 
 using namespace hdiff;
 
@@ -38,8 +39,6 @@ constexpr int KT = 64;          // keys per tile
 constexpr int KROW = KT + 4;    // LDS row stride (floats), 16-byte aligned rows
 constexpr int ATT_THREADS = 256;
 constexpr float RESCALE_LIMIT = 1.8446744e19f;   // 2^64: a row sum at or above it (or inf) triggers the max update
-
-typedef float f32x2 __attribute__((ext_vector_type(2)));
 
 // one v_pk_add_f32 (pure: no memory, no side effects -- the compiler may schedule and CSE it like any VALU instruction)
 __device__ __forceinline__ f32x2 pk_add(f32x2 a, f32x2 b) {
@@ -289,7 +288,6 @@ __global__ __launch_bounds__(ATT_THREADS) void mha_flash_fwd_kernel(const float*
 // QK^T MFMA chain -- so per 16x16 score tile the VALU work is 4 v_exp_f32 + 2 v_pk_add_f32 per lane and nothing else
 // (on gfx950 every VALU instruction is fp32-MFMA issue time).
 // ---------------------------------------------------------------------------------------------------------------------
-constexpr float FAST_OVERFLOW_LIMIT = 1.2379400e27f;   // 2^90: a row sum at or above it (or NaN) -> recompute safely
 
 template <int D, int NQ>
 __global__ __launch_bounds__(ATT_THREADS) void mha_flash_fwd_fast_kernel(const float* __restrict__ qkv,
@@ -512,7 +510,7 @@ __global__ __launch_bounds__(ATT_THREADS) void mha_flash_fwd_fast_kernel(const f
     float lt = l_run[qt].x + l_run[qt].y;
     lt += __shfl_xor(lt, 16, 64);
     lt += __shfl_xor(lt, 32, 64);
-    const bool bad = !(lt < FAST_OVERFLOW_LIMIT);            // overflow (or NaN): hand this query block to the safe kernel
+    const bool bad = !(lt < OVERFLOW_LIMIT);            // overflow (or NaN): hand this query block to the safe kernel
     const float inv = bad ? __builtin_nanf("") : 1.0f / lt;
     const int q = qblk0 + qt * 16 + i16;
     if (lse2 != nullptr && q < L && g == 0)

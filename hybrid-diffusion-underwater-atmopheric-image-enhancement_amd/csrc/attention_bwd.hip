@@ -25,6 +25,7 @@
 #include <type_traits>
 
 #include "common.h"
+#include "device.h"
 
 using namespace hdiff;
 

@@ -43,6 +43,7 @@
 #include <type_traits>
 
 #include "common.h"
+#include "device.h"
 
 using namespace hdiff;
 
@@ -85,11 +86,6 @@ struct Geo {
   static_assert(LDS_BYTES <= 160 * 1024, "LDS");
 };
 
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 typedef short s16x4 __attribute__((ext_vector_type(4)));
 
 // gfx950 transposing LDS read: per 16-lane group a block of 4 rows x 16 columns of 16-bit elements; lane 4q + p of the
@@ -103,31 +99,6 @@ __device__ __forceinline__ u32x2 lds_read_tr16(const unsigned char* p) {
 // every barrier -- 23 ms of a 158 ms launch (timing ablation).  Nothing here hands global data to another wave.
 __device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
-typedef __attribute__((address_space(3))) unsigned char lds_byte;
-// One 1 KiB run global -> LDS without staging registers (global_load_lds_dwordx4: lane i's 16 bytes at src + voff land at lds_dst + 16 i).
-// M0 is written in the statement that uses it and restored; the compiler does not count this load: the kernel waits with its own
-// s_waitcnt vmcnt(0) in front of the barrier that publishes the tile (attention_h2.hip does the same for its K tiles).
-__device__ __forceinline__ void dma_1k(const unsigned char* src, unsigned voff, unsigned lds_dst) {
-  unsigned keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep)
-               : "v"(voff), "s"(src), "s"(lds_dst)
-               : "memory");
-}
-__device__ __forceinline__ f32x4 mfma_f16(u32x4 a, u32x4 b, f32x4 c) {
-  return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
-}
-// (a, b) -> two packed fp16 pairs, a = h0.lo + h1.lo up to 2^-23 |a| (or 2^-25 absolute); see attention_h2.hip.  `one` is
-// 1.0f in a register the compiler cannot see through (the residual must stay an fma: v_fma_mixlo / mixhi_f16).
-__device__ __forceinline__ void split2(float a, float b, float one, unsigned& h0, unsigned& h1) {
-  const f16x2 p = {(_Float16)a, (_Float16)b};
-  unsigned u = __builtin_bit_cast(unsigned, p);
-  asm("" : "+v"(u));
-  const f16x2 q = __builtin_bit_cast(f16x2, u);
-  const f16x2 r = {(_Float16)__builtin_fmaf(a, one, -(float)q[0]), (_Float16)__builtin_fmaf(b, one, -(float)q[1])};
-  h0 = u;
-  h1 = __builtin_bit_cast(unsigned, r);
-}
 // (a c, b c) -> two packed fp16 pairs with the SECOND piece times 2^8: h0 = fp16(a c) by v_fma_mixlo / mixhi_f16 (fma(a, c, 0)), r = the
 // EXACT residual fma(a, c, -h0) in fp32 (v_fma_mix_f32 reads h0 as fp16), h1 = fp16(256 r).  Three instructions per value (an unshifted
 // residual would take two: but dS' is typically 2^-7 where the softmax is flat over 65 536 keys -- the bound 2^15 belongs to a row that
@@ -154,8 +125,6 @@ __device__ __forceinline__ void split2_scaled(float a0, float a1, float b0, floa
       : "=&v"(ha0), "=&v"(ha1), "=&v"(hb0), "=&v"(hb1), "=&v"(r0), "=&v"(r1), "=&v"(r2), "=&v"(r3)
       : "v"(a0), "v"(a1), "v"(b0), "v"(b1), "v"(c), "v"(up));
 }
-constexpr int PAIR_SHIFT = 8;                 // second pieces are stored times 2^8
-constexpr unsigned PAIR_DOWN2 = 0x1c001c00u;  // (2^-8, 2^-8) as packed fp16
 // exponent e of a tensor's maximum |x| (given as the bits of the fp32 value), clamped: all-zero / denormal / huge tensors get a fixed
 // scale (inf and NaN stay what they are)
 __device__ __forceinline__ int max_exp(unsigned amax_bits) {
@@ -174,13 +143,6 @@ constexpr int P_UP = 14;       // P' = exp2(S - lse2 + 14) <= 2^14, as in round 
                                // instead -- tried -- every accumulation of S rounds at the magnitude of ~33 and the exponent loses three bits)
 // dS' = P' (dP' - delta') 2^-DS_DOWN <= 2^15: |dP'| <= d 2^14 2^14, |delta'| = |sum_k P dP'| likewise, P' <= 2^14
 template <int D> constexpr int DS_DOWN = (D == 16) ? 32 : 33;
-// the score balance of this (sample, head): k = K 2^a, q = Q qscale 2^-a with the two maxima in the same binade (attention_h2.hip)
-__device__ __forceinline__ int balance_exp(unsigned qmax_bits, unsigned kmax_bits, float qscale) {
-  const float mq = __builtin_bit_cast(float, qmax_bits) * qscale;
-  const int eq = (int)((__builtin_bit_cast(unsigned, mq) >> 23) & 0xffu), ek = (int)((kmax_bits >> 23) & 0xffu);
-  int a = (eq == 0 || ek == 0 || eq == 255 || ek == 255) ? 0 : (eq - ek) / 2;
-  return a < -60 ? -60 : (a > 60 ? 60 : a);
-}
 
 // Piece slots of one (sample, head), each L * D fp16: rows of q (q0, q1 2^8); rows of Q 2^sq c_q (x0, x1); rows of k (k0, k0 2^-8,
 // k1 2^8, k1); k transposed [D][L] (k0, k1 2^8); rows of V' (v0, v1: form (ii), two slots used of the four reserved); rows of dO scaled per query (o0, o1: unshifted); rows of
@@ -205,7 +167,7 @@ __global__ __launch_bounds__(THREADS) void mha_bwd_absmax_kernel(const float* __
   for (int d = 0; d < D; ++d)
     for (int i = threadIdx.x * 4; i < 4096 && l0 + i < L; i += THREADS * 4) {
       const f32x4 v = *reinterpret_cast<const f32x4*>(src + (size_t)d * L + l0 + i);
-      m = fmaxf(m, fmaxf(fmaxf(fabsf(v[0]), fabsf(v[1])), fmaxf(fabsf(v[2]), fabsf(v[3]))));
+      m = absmax4(m, v);
     }
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
@@ -215,22 +177,8 @@ __global__ __launch_bounds__(THREADS) void mha_bwd_absmax_kernel(const float* __
 // ---------------------------------------------------------------------------------------------------------------------
 // fp32 qkv [B][3C][L] and dO [B][C][L] -> the piece tensors above.  grid (L / 256, 4 * heads, B): blockIdx.y / heads selects
 // Q, K, V or dO; thread = one position, all D channels (K^T: thread = two neighbouring positions of each channel).
-// The fp32 scaled value and the packed first pieces are made opaque to the compiler: left alone it rounds x0 twice (once from
-// the fp32 product for the stored piece, once from the exact product for the residual: attention_h2.hip).
+// The four-piece layout comes from pair4 (device.h), as in the forward's split pass.
 // ---------------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ void pair4(float xa, float xb, float up, unsigned& x0, unsigned& x0s, unsigned& x1s, unsigned& x1) {
-  asm("" : "+v"(xa), "+v"(xb));
-  unsigned u0 = __builtin_bit_cast(unsigned, f16x2{(_Float16)xa, (_Float16)xb});
-  asm("" : "+v"(u0));
-  const f16x2 h = __builtin_bit_cast(f16x2, u0);
-  const float ra = xa - (float)h[0], rb = xb - (float)h[1];            // exact
-  const f16x2 dn = {(_Float16)(1.0f / (1 << PAIR_SHIFT)), (_Float16)(1.0f / (1 << PAIR_SHIFT))};
-  x0 = u0;
-  x0s = __builtin_bit_cast(unsigned, h * dn);
-  x1s = __builtin_bit_cast(unsigned, f16x2{(_Float16)(ra * up), (_Float16)(rb * up)});
-  x1 = __builtin_bit_cast(unsigned, f16x2{(_Float16)ra, (_Float16)rb});
-}
-
 template <int D>
 __global__ __launch_bounds__(THREADS) void mha_bwd_split_h2_kernel(const float* __restrict__ qkv, const float* __restrict__ d_o,
                                                                    __bf16* __restrict__ ws, const unsigned* __restrict__ absmax,

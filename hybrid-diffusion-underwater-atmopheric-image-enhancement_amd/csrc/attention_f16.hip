@@ -5,7 +5,7 @@
 //
 // FORMAT (tests/_f16_attention_emul.py emulates this text, not the code):
 //   q = fp16(Q qscale 2^-a), k = fp16(K 2^a): qscale = log2(e) / sqrt(d); the balance a per (sample, head) from the maxima of the
-//       head's Q and K channel rows exactly as qk_split_h2_kernel (attention_h2.hip): a = (eq - ek) / 2 (C division) of the biased
+//       head's Q and K channel rows exactly as qk_split_h2_kernel (balance_exp, device.h): a = (eq - ek) / 2 (C division) of the biased
 //       exponents of max |Q| qscale and max |K|, clamped to +-60, 0 when either is zero / inf / NaN.
 //   v = fp16(V 2^s), s per channel row with max |V 2^s| in [2^14, 2^15), as v_split_h2_kernel (exponent clamped to [-100, 127]).
 //   S = k . q on the fp16 MFMA into an fp32 accumulator that starts from -m;  P = fp16(exp2(S)) by v_cvt_pk_f16_f32 alone;
@@ -40,30 +40,17 @@
 #include <stdlib.h>
 
 #include "common.h"
+#include "device.h"
 
 using namespace hdiff;
 
 namespace {
 
 constexpr int THREADS = 256;
-constexpr float OVERFLOW_LIMIT = 1.2379400e27f;   // 2^90: only NaN / inf inputs get here (the reference moves before fp16 overflows)
-constexpr float P_SHIFT = 8.0f;                   // the reference point enters as P = 2^8
-constexpr float P_TRIP = 32768.0f;                // per-lane sum of one stage's P values that moves the reference
-
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
 typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
 __device__ __forceinline__ f32x4 mfma16k16(u32x2 a, u32x2 b, f32x4 c) {
   return __builtin_amdgcn_mfma_f32_16x16x16f16(__builtin_bit_cast(f16x4, a), __builtin_bit_cast(f16x4, b), c, 0, 0, 0);
-}
-__device__ __forceinline__ f32x4 mfma16k32(u32x4 a, u32x4 b, f32x4 c) {
-  return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
-}
-__device__ __forceinline__ f32x16 mfma32k16(u32x4 a, u32x4 b, f32x16 c) {
-  return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
 }
 __device__ __forceinline__ unsigned pack_f16(float a, float b) {      // v_cvt_pk_f16_f32: round to nearest even
   return __builtin_bit_cast(unsigned, f16x2{(_Float16)a, (_Float16)b});
@@ -78,19 +65,7 @@ __device__ __forceinline__ int v_exponent(float amax) {
 // Pass 1: max |x| of every Q / K / V channel row into rowmax[B][3C] (grid (3C, B)).
 // ---------------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(THREADS) void f16_rowmax_kernel(const float* __restrict__ qkv, float* __restrict__ rowmax, int C, int L) {
-  const int row = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
-  const float* src = qkv + ((size_t)b * 3 * C + row) * L;
-  __shared__ float red[THREADS / 64];
-  float amax = 0.f;
-  for (int i = tid; i < L / 4; i += THREADS) {
-    const f32x4 v = *reinterpret_cast<const f32x4*>(src + 4 * (size_t)i);
-    amax = fmaxf(amax, fmaxf(fmaxf(fabsf(v[0]), fabsf(v[1])), fmaxf(fabsf(v[2]), fabsf(v[3]))));
-  }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) amax = fmaxf(amax, __shfl_xor(amax, o, 64));
-  if ((tid & 63) == 0) red[tid >> 6] = amax;
-  __syncthreads();
-  if (tid == 0) rowmax[(size_t)b * 3 * C + row] = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
+  qkv_rowmax<3>(qkv, rowmax, C, L);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -116,10 +91,7 @@ __global__ __launch_bounds__(THREADS) void f16_split_kernel(const float* __restr
       mq = fmaxf(mq, rm[head * D + d]);
       mk = fmaxf(mk, rm[C + head * D + d]);
     }
-    mq *= qscale;
-    const int eq = (int)((__builtin_bit_cast(unsigned, mq) >> 23) & 0xffu), ek = (int)((__builtin_bit_cast(unsigned, mk) >> 23) & 0xffu);
-    int a = (eq == 0 || ek == 0 || eq == 255 || ek == 255) ? 0 : (eq - ek) / 2;      // k 2^a, q 2^-a
-    a = a < -60 ? -60 : (a > 60 ? 60 : a);
+    const int a = balance_exp(__builtin_bit_cast(unsigned, mq), __builtin_bit_cast(unsigned, mk), qscale);      // k 2^a, q 2^-a
     const float sc = which == 0 ? qscale * __builtin_bit_cast(float, (unsigned)(127 - a) << 23) : __builtin_bit_cast(float, (unsigned)(127 + a) << 23);
     unsigned h[D / 2];
 #pragma unroll
@@ -137,18 +109,6 @@ __global__ __launch_bounds__(THREADS) void f16_split_kernel(const float* __restr
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
-typedef __attribute__((address_space(3))) unsigned char lds_byte;
-// One 1 KiB run global -> LDS without staging registers: lane i's 16 bytes at src + voff land at lds_dst + 16 i
-// (global_load_lds_dwordx4).  M0 is written in the statement that uses it and restored.  The compiler does not count this load: the
-// kernel waits with its own s_waitcnt vmcnt(0) in front of the barrier that publishes the tile (attention_h2.hip has the same).
-__device__ __forceinline__ void dma_1k(const unsigned char* src, unsigned voff, unsigned lds_dst) {
-  unsigned keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep)
-               : "v"(voff), "s"(src), "s"(lds_dst)
-               : "memory");
-}
-
 // ---------------------------------------------------------------------------------------------------------------------
 // d_head 16.  Wave = 4 query tiles of 16; key tile = 128 keys = two stages of 64 keys (four 16-key score tiles each).
 // ---------------------------------------------------------------------------------------------------------------------
@@ -284,7 +244,7 @@ __global__ __launch_bounds__(THREADS, 2) void mha_flash_fwd_f16_d16_kernel(const
       u32x4 pp[2];
       softmax(S[qt & 1], qt, pp);
 #pragma unroll
-      for (int c = 0; c < 2; ++c) O[qt] = mfma16k32(vop[c], pp[c], O[qt]);
+      for (int c = 0; c < 2; ++c) O[qt] = mfma_f16(vop[c], pp[c], O[qt]);
     }
   };
 
@@ -420,7 +380,7 @@ __global__ __launch_bounds__(THREADS, 2) void mha_flash_fwd_f16_d32_kernel(const
 #pragma unroll
     for (int r = 0; r < 16; ++r) S[r] = nm;    // the chain starts from -m: the accumulator holds s - m
 #pragma unroll
-    for (int s = 0; s < KS; ++s) S = mfma32k16(kop[s], qop[G][s], S);
+    for (int s = 0; s < KS; ++s) S = mfma_f16(kop[s], qop[G][s], S);
     return S;
   };
   auto exp_pack = [&](const f32x16& S, u32x4 (&pop)[2], float& sum0, float& sum1) {
@@ -484,7 +444,7 @@ __global__ __launch_bounds__(THREADS, 2) void mha_flash_fwd_f16_d32_kernel(const
       u32x4 pop[2];
       softmax(S2[G], G, pop);
 #pragma unroll
-      for (int ab = 0; ab < 2; ++ab) O[G] = mfma32k16(vop[ab], pop[ab], O[G]);
+      for (int ab = 0; ab < 2; ++ab) O[G] = mfma_f16(vop[ab], pop[ab], O[G]);
     }
   };
   for (int t = 0; t < ntiles; ++t) {

@@ -48,6 +48,7 @@
 #include <type_traits>
 
 #include "common.h"
+#include "device.h"
 
 using namespace hdiff;
 
@@ -55,33 +56,6 @@ namespace {
 
 constexpr int KT = 64;
 constexpr int THREADS = 256;
-constexpr float OVERFLOW_LIMIT = 1.2379400e27f;   // 2^90: only NaN / inf inputs get here (the reference moves before fp16 overflows)
-constexpr float P_SHIFT = 8.0f;                   // the reference point enters as P = 2^8
-constexpr float P_TRIP = 32768.0f;                // per-lane sum of one stage's 16 P values that moves the reference
-
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ f32x4 mfma_f16(u32x4 a, u32x4 b, f32x4 c) {
-  return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
-}
-
-// (a, b) -> two packed fp16 pairs with a = h0.lo + h1.lo up to 2^-23 |a| (or 2^-25 absolute), b likewise in the high halves.
-// `one` is 1.0f in a register the compiler cannot see through: fma(a, 1, -h) must stay an fma (v_fma_mixlo_f16), a - h
-// would be a conversion and a subtraction.
-__device__ __forceinline__ void split2(float a, float b, float one, unsigned& h0, unsigned& h1) {
-  const f16x2 p = {(_Float16)a, (_Float16)b};                 // v_cvt_pk_f16_f32: round to nearest even
-  unsigned u = __builtin_bit_cast(unsigned, p);
-  asm("" : "+v"(u));                                          // the halves are read back out of the packed register
-  const f16x2 q = __builtin_bit_cast(f16x2, u);
-  const f16x2 r = {(_Float16)__builtin_fmaf(a, one, -(float)q[0]), (_Float16)__builtin_fmaf(b, one, -(float)q[1])};
-  h0 = u;
-  h1 = __builtin_bit_cast(unsigned, r);
-}
-
 // ---------------------------------------------------------------------------------------------------------------------
 // Moving the softmax reference, exactly, in the stage that needs it.  A stage whose lane sum of 16 P values reached P_TRIP
 // (so some P may not fit fp16) is made again from its S accumulators, which are still in registers, under a reference
@@ -196,11 +170,10 @@ __device__ __forceinline__ void h2_rare_exp_split(unsigned long long cond, float
 
 // Score operands.  K pieces in the workspace / LDS: 0 = k0, 1 = k0 2^-8, 2 = k1 2^8, 3 = k1; Q pieces in registers: q0, q1 2^8 read
 // from the workspace, q0 2^-8 and q1 made from them.  MFMA j contracts K operand set j (pieces 2 j | 2 j + 1 on the low | high 16
-// slots) with Q operand set j: MFMA 0 = k0 q0 + (k0 2^-8)(q1 2^8), MFMA 1 = (k1 2^8)(q0 2^-8) + k1 q1.
-constexpr int QK_SHIFT = 8;
+// slots) with Q operand set j: MFMA 0 = k0 q0 + (k0 2^-8)(q1 2^8), MFMA 1 = (k1 2^8)(q0 2^-8) + k1 q1.  (PAIR_SHIFT, pair4: device.h)
 
 // ---------------------------------------------------------------------------------------------------------------------
-// Q and K of qkv [B][3C][L] (fp32) -> fp16 score operands (see QK_SHIFT) in the workspace, per (sample, head):
+// Q and K of qkv [B][3C][L] (fp32) -> fp16 score operands (see PAIR_SHIFT) in the workspace, per (sample, head):
 //   piece 0: q0 [L][D], 1: q1 2^8 [L][D], 2..5: k0, k0 2^-8, k1 2^8, k1 [L][D]   (q = q_in qscale 2^-a, k = k_in 2^a)
 // Pass 1 (qk_rowmax_kernel, grid (2C, B)): max |x| of every Q / K channel row into rowmax[B][2C] behind the pairs.
 // Pass 2 (qk_split_h2_kernel, grid (L / 256, 2 heads, B)): thread = one position, all D channels; the balance a puts the two
@@ -209,19 +182,7 @@ constexpr int QK_SHIFT = 8;
 // output is then NaN and the caller's check pass takes the query block, as for every kernel of this family).
 // ---------------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(THREADS) void qk_rowmax_kernel(const float* __restrict__ qkv, float* __restrict__ rowmax, int C, int L) {
-  const int row = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
-  const float* src = qkv + ((size_t)b * 3 * C + row) * L;
-  __shared__ float red[THREADS / 64];
-  float amax = 0.f;
-  for (int i = tid; i < L / 4; i += THREADS) {
-    const f32x4 v = *reinterpret_cast<const f32x4*>(src + 4 * (size_t)i);
-    amax = fmaxf(amax, fmaxf(fmaxf(fabsf(v[0]), fabsf(v[1])), fmaxf(fabsf(v[2]), fabsf(v[3]))));
-  }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) amax = fmaxf(amax, __shfl_xor(amax, o, 64));
-  if ((tid & 63) == 0) red[tid >> 6] = amax;
-  __syncthreads();
-  if (tid == 0) rowmax[(size_t)b * 2 * C + row] = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
+  qkv_rowmax<2>(qkv, rowmax, C, L);
 }
 
 template <int D>
@@ -237,41 +198,22 @@ __global__ __launch_bounds__(THREADS) void qk_split_h2_kernel(const float* __res
     mq = fmaxf(mq, rowmax[(size_t)b * 2 * C + head * D + d]);
     mk = fmaxf(mk, rowmax[(size_t)b * 2 * C + C + head * D + d]);
   }
-  mq *= qscale;
-  const int eq = (int)((__builtin_bit_cast(unsigned, mq) >> 23) & 0xffu), ek = (int)((__builtin_bit_cast(unsigned, mk) >> 23) & 0xffu);
-  int a = (eq == 0 || ek == 0 || eq == 255 || ek == 255) ? 0 : (eq - ek) / 2;      // k 2^a, q 2^-a (zero / inf / NaN rows: no balance)
-  a = a < -60 ? -60 : (a > 60 ? 60 : a);
+  const int a = balance_exp(__builtin_bit_cast(unsigned, mq), __builtin_bit_cast(unsigned, mk), qscale);      // k 2^a, q 2^-a
   const float sc = which == 0 ? qscale * __builtin_bit_cast(float, (unsigned)(127 - a) << 23) : __builtin_bit_cast(float, (unsigned)(127 + a) << 23);
   if (l >= L) return;
   const float* src = qkv + ((size_t)b * 3 * C + (size_t)which * C + (size_t)head * D) * L;
   const size_t piece = (size_t)L * D;
-  __bf16* pair = ws + ((size_t)b * heads + head) * 9 * piece;
-  const float up = (float)(1 << QK_SHIFT) * one;
-  typedef _Float16 f16x2v __attribute__((ext_vector_type(2)));
-  const f16x2v dn = {(_Float16)(1.0f / (1 << QK_SHIFT)), (_Float16)(1.0f / (1 << QK_SHIFT))};
+  __bf16* pair = ws + ((size_t)b * heads + head) * F_COUNT * piece;
+  const float up = (float)(1 << PAIR_SHIFT) * one;
   unsigned h[4][D / 2];          // x0, x0 2^-8, x1 2^8, x1 as packed fp16 pairs (channels 2 j, 2 j + 1)
 #pragma unroll
-  for (int j = 0; j < D / 2; ++j) {
-    float xa = src[(size_t)(2 * j) * L + l] * sc, xb = src[(size_t)(2 * j + 1) * L + l] * sc;
-    // the fp32 products and the packed first pieces are made opaque: left alone the compiler rounds x0 twice -- once from the
-    // fp32 product for the stored piece, once from the EXACT product (v_fma_mixlo_f16) for the residual -- and where the two
-    // differ by an ulp the stored pieces no longer add up (found with an operand dump: 4e-4 instead of 5e-7)
-    asm("" : "+v"(xa), "+v"(xb));
-    unsigned u0 = __builtin_bit_cast(unsigned, f16x2v{(_Float16)xa, (_Float16)xb});
-    asm("" : "+v"(u0));
-    const f16x2v x0 = __builtin_bit_cast(f16x2v, u0);
-    const float ra = xa - (float)x0[0], rb = xb - (float)x0[1];            // exact
-    const f16x2v x1s = {(_Float16)(ra * up), (_Float16)(rb * up)}, x1 = {(_Float16)ra, (_Float16)rb};
-    h[0][j] = __builtin_bit_cast(unsigned, x0);
-    h[1][j] = __builtin_bit_cast(unsigned, x0 * dn);
-    h[2][j] = __builtin_bit_cast(unsigned, x1s);
-    h[3][j] = __builtin_bit_cast(unsigned, x1);
-  }
+  for (int j = 0; j < D / 2; ++j)
+    pair4(src[(size_t)(2 * j) * L + l] * sc, src[(size_t)(2 * j + 1) * L + l] * sc, up, h[0][j], h[1][j], h[2][j], h[3][j]);
   // Q: pieces 0 (q0) and 1 (q1 2^8); K: pieces 2 .. 5
 #pragma unroll
   for (int p = 0; p < 4; ++p) {
     if (which == 0 && (p == 1 || p == 3)) continue;
-    const int slot = which == 0 ? (p == 0 ? 0 : 1) : 2 + p;
+    const int slot = which == 0 ? F_Q + (p == 0 ? 0 : 1) : F_K + p;
     u32x4* o = reinterpret_cast<u32x4*>(pair + slot * piece + (size_t)l * D);
 #pragma unroll
     for (int j = 0; j < D / 8; ++j) o[j] = u32x4{h[p][4 * j], h[p][4 * j + 1], h[p][4 * j + 2], h[p][4 * j + 3]};
@@ -280,7 +222,7 @@ __global__ __launch_bounds__(THREADS) void qk_split_h2_kernel(const float* __res
 
 // ---------------------------------------------------------------------------------------------------------------------
 // V of qkv [B][3C][L] (fp32)  ->  two fp16 pieces of V * 2^s, s per channel row, in the V region of the pre-split workspace:
-// per (sample, head)  Vh[2][D][L] (fp16) at piece slot 6, and the D factors 2^-s (fp32) at piece slot 8.
+// per (sample, head)  Vh[2][D][L] (fp16) at piece slot F_V, and the D factors 2^-s (fp32) at piece slot F_VINV.
 // One workgroup per (sample, channel) row: a maximum pass, then the split pass (the row comes back from L2).
 // ---------------------------------------------------------------------------------------------------------------------
 template <int D>
@@ -291,26 +233,16 @@ __global__ __launch_bounds__(THREADS) void v_split_h2_kernel(const float* __rest
   const int tid = threadIdx.x;
   const float* src = qkv + ((size_t)b * 3 * C + 2 * (size_t)C + row) * L;
   const size_t piece = (size_t)L * D;
-  __bf16* pair = ws + ((size_t)b * heads + head) * 9 * piece;
-  _Float16* dst = reinterpret_cast<_Float16*>(pair + 6 * piece) + (size_t)d * L;
-  __shared__ float red[THREADS / 64];
+  __bf16* pair = ws + ((size_t)b * heads + head) * F_COUNT * piece;
+  _Float16* dst = reinterpret_cast<_Float16*>(pair + F_V * piece) + (size_t)d * L;
 
-  float amax = 0.f;
-  for (int i = tid; i < L / 4; i += THREADS) {
-    const f32x4 v = *reinterpret_cast<const f32x4*>(src + 4 * (size_t)i);
-    amax = fmaxf(amax, fmaxf(fmaxf(fabsf(v[0]), fabsf(v[1])), fmaxf(fabsf(v[2]), fabsf(v[3]))));
-  }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) amax = fmaxf(amax, __shfl_xor(amax, o, 64));
-  if ((tid & 63) == 0) red[tid >> 6] = amax;
-  __syncthreads();
-  amax = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
+  const float amax = row_absmax(src, L, tid);
   // 2^s with max |v| 2^s in [2^14, 2^15); exponent clamped so that both 2^s and 2^-s are normal numbers (an all-zero or
   // denormal row is scaled by 2^114 at most, an infinite one by 2^-113: inf / NaN elements stay inf / NaN in fp16)
   int e = (int)((__builtin_bit_cast(unsigned, amax) >> 23) & 0xffu) - 127;
   e = e < -100 ? -100 : (e > 127 ? 127 : e);
   const float scale = __builtin_bit_cast(float, (unsigned)(14 - e + 127) << 23);
-  if (tid == 0) reinterpret_cast<float*>(pair + 8 * piece)[d] = __builtin_bit_cast(float, (unsigned)(e - 14 + 127) << 23);
+  if (tid == 0) reinterpret_cast<float*>(pair + F_VINV * piece)[d] = __builtin_bit_cast(float, (unsigned)(e - 14 + 127) << 23);
   for (int i = tid; i < L / 4; i += THREADS) {
     const f32x4 v = *reinterpret_cast<const f32x4*>(src + 4 * (size_t)i);
     unsigned a0, a1, c0, c1;
@@ -322,24 +254,12 @@ __global__ __launch_bounds__(THREADS) void v_split_h2_kernel(const float* __rest
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
-typedef __attribute__((address_space(3))) unsigned char lds_byte;
-// One 1 KiB run global -> LDS without staging registers: lane i's 16 bytes at src + voff land at lds_dst + 16 i (global_load_lds_dwordx4).
-// M0 is written in the statement that uses it and restored (cdna_hip_programming.md, 'What hipcc does not do').  The compiler does not
-// count this load: the kernel waits with its own s_waitcnt vmcnt(0) in front of the barrier that publishes the tile.
-__device__ __forceinline__ void dma_1k(const unsigned char* src, unsigned voff, unsigned lds_dst) {
-  unsigned keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep)
-               : "v"(voff), "s"(src), "s"(lds_dst)
-               : "memory");
-}
-
 template <int D, int NQ>
 __global__ __launch_bounds__(THREADS, 2) void mha_flash_fwd_h2_kernel(const __bf16* __restrict__ ws, float* __restrict__ out,
                                                                       float* __restrict__ lse2, int C, int L, float one) {
   static_assert(D == 16, "head dim: two terms share one MFMA's 32 contraction slots");
   static_assert(NQ == 4, "the stage pipeline is written for four query tiles per wave");
-  constexpr int NKP = 4;                   // K pieces (see QK_SHIFT)
+  constexpr int NKP = 4;                   // K pieces (see PAIR_SHIFT)
   constexpr int NKS = 2;                   // K operand sets per 16 keys = QK^T MFMAs per 16x16 score tile
   constexpr int NQK = NKS;
   constexpr int MT = D / 16;               // 16-row tiles of the output
@@ -364,14 +284,13 @@ __global__ __launch_bounds__(THREADS, 2) void mha_flash_fwd_h2_kernel(const __bf
   const bool hi = g >> 1;
 
   const size_t piece_n = (size_t)L * D;
-  const __bf16* wsq = ws + ((size_t)b * gridDim.y + head) * 9 * piece_n;
+  const __bf16* wsq = ws + ((size_t)b * gridDim.y + head) * F_COUNT * piece_n;
   // Q operands of the wave's four query tiles, in registers for the whole kernel: [query tile][MFMA].  The workspace holds q0 and
   // q1 2^8; q0 2^-8 and q1 are their multiples (v_pk_mul_f16 by 2^-8: exact, or rounded into fp16's subnormals like the split
   // pass would have).
   u32x4 qop[NQ][NQK];
   {
-    static_assert(QK_SHIFT == 8, "packed fp16 constant below");
-    const unsigned dn2 = 0x1c001c00u;                // (2^-8, 2^-8) as packed fp16
+    const unsigned dn2 = PAIR_DOWN2;
 #pragma unroll
     for (int qt = 0; qt < NQ; ++qt) {
       const int q = qblk0 + qt * 16 + i16;
@@ -400,14 +319,14 @@ __global__ __launch_bounds__(THREADS, 2) void mha_flash_fwd_h2_kernel(const __bf
   int lds_off;
   u32x4 stage;
   {
-    const __bf16* vsp = wsq + 6 * piece_n;
+    const __bf16* vsp = wsq + F_V * piece_n;
     const int p = tid / (D * 8), rem = tid - p * (D * 8);
     const int d = rem >> 3, seg = rem & 7;
     gsrc = reinterpret_cast<const unsigned char*>(vsp + p * piece_n + (size_t)d * L) + seg * 16;
     lds_off = VBASE + p * VPART + d * VROWB + seg * 16;
   }
   const unsigned lds0 = (unsigned)(size_t)(lds_byte*)&smem[0][0];
-  const unsigned char* kdma = reinterpret_cast<const unsigned char*>(wsq + 2 * piece_n);      // + piece * piece_n * 2 + tile * 2048 + half * 1024
+  const unsigned char* kdma = reinterpret_cast<const unsigned char*>(wsq + F_K * piece_n);      // + piece * piece_n * 2 + tile * 2048 + half * 1024
   // wave w copies runs 2 w, 2 w + 1 of the tile: piece w, its two 32-key halves
   auto dma_k = [&](int t, int buf) {
     const int ws_ = __builtin_amdgcn_readfirstlane(wave);      // the asm operands must be scalar registers
@@ -621,7 +540,7 @@ __global__ __launch_bounds__(THREADS, 2) void mha_flash_fwd_h2_kernel(const __bf
   for (int n = 0; n < NPV; ++n) pv_mfma(NQ - 1, 1, n);
 
   float* obase = out + ((size_t)b * C + (size_t)head * D) * L;
-  const float* vinv = reinterpret_cast<const float*>(wsq + 8 * piece_n);      // 2^-s per channel of this head
+  const float* vinv = reinterpret_cast<const float*>(wsq + F_VINV * piece_n);      // 2^-s per channel of this head
 #pragma unroll
   for (int qt = 0; qt < NQ; ++qt) {
     float lt = l_run[qt];

@@ -9,6 +9,7 @@
 // Heads of width <= 64 go to the flash kernels (hdiff_mha_flash_fwd with heads = 1).  qkv is [B][3C][L], out [B][C][L].
 // hdiff_mha_wide_bwd (any width) is the backward of both: a row pass for dQ, a column pass for dK and dV.
 #include "common.h"
+#include "device.h"
 
 using namespace hdiff;
 

@@ -20,6 +20,7 @@
 #include <type_traits>
 
 #include "common.h"
+#include "device.h"
 
 using namespace hdiff;
 
@@ -28,31 +29,8 @@ namespace {
 constexpr int KT = 64;
 constexpr int THREADS = 256;
 constexpr int VALU_PER_STAGE = 80;                // vector instructions of a stage, spread over its MFMAs (the stage loop)
-constexpr float OVERFLOW_LIMIT = 1.2379400e27f;   // 2^90, as in attention.hip
 
-typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-
-// (a, b) -> three packed bf16 pairs with a = a0 + a1 + a2 exactly (b likewise): each piece is the top 16 bits of what is
-// left (8 significand bits, truncated), the remainders are exact fp32 subtractions.  Only plain VALU instructions
-// (v_and, v_sub, v_perm): v_dot2c_f32_bf16 and the packed-fp32 instructions would be fewer, but tools/mfma_bf16_coexec.hip
-// shows that those stall against the bf16 MFMA stream instead of running beside it.
-__device__ __forceinline__ unsigned pack_hi16(float lo, float hi) {
-  return __builtin_amdgcn_perm(__builtin_bit_cast(unsigned, hi), __builtin_bit_cast(unsigned, lo), 0x07060302u);
-}
-__device__ __forceinline__ float top16(float x) {
-  return __builtin_bit_cast(float, __builtin_bit_cast(unsigned, x) & 0xffff0000u);
-}
-__device__ __forceinline__ void split3(float a, float b, unsigned& h0, unsigned& h1, unsigned& h2) {
-  h0 = pack_hi16(a, b);
-  const float ra = a - top16(a), rb = b - top16(b);
-  h1 = pack_hi16(ra, rb);
-  const float sa = ra - top16(ra), sb = rb - top16(rb);
-  h2 = pack_hi16(sa, sb);
-}
 
 // one v_add_f32 the vectoriser cannot pair into v_pk_add_f32 (which stalls against the bf16 MFMA stream like the other
 // packed-fp32 forms: tools/valu_rates.hip -- 2.5 cycles for the plain add, 4.6 + a stall for the packed one)
@@ -68,10 +46,6 @@ __device__ __forceinline__ float add1_after_trans(float a, float b) {
   float r;
   asm("s_nop 0\n\tv_add_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
   return r;
-}
-
-__device__ __forceinline__ f32x4 mfma_bf16(u32x4 a, u32x4 b, f32x4 c) {
-  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
 }
 
 // split-product terms kept (piece of K or V, piece of Q or P): all i + j <= 2

@@ -32,6 +32,7 @@
 #include <stdlib.h>
 
 #include "common.h"
+#include "device.h"
 
 using namespace hdiff;
 
@@ -41,30 +42,6 @@ constexpr int D = 32;
 constexpr int KT = 64;
 constexpr int THREADS = 256;
 constexpr int NQT = 3;                            // score product terms = K pieces staged = Q pieces held
-constexpr float OVERFLOW_LIMIT = 1.2379400e27f;   // 2^90, as in attention.hip
-constexpr float P_SHIFT = 8.0f;                   // the reference point enters as P = 2^8 ...
-constexpr float P_TRIP = 32768.0f;                // ... and moves when a lane's 16 P values of one block sum to 2^15 (attention_h2.hip)
-
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ f32x16 mfma32h(u32x4 a, u32x4 b, f32x16 c) {
-  return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
-}
-// (a, b) -> two packed fp16 pairs, a = h0.lo + h1.lo up to 2^-23 |a| (or 2^-25 absolute); attention_h2.hip.  `one` is 1.0f in a
-// register the compiler cannot see through (the residual must stay an fma: v_fma_mixlo / mixhi_f16).
-__device__ __forceinline__ void split2(float a, float b, float one, unsigned& h0, unsigned& h1) {
-  const f16x2 p = {(_Float16)a, (_Float16)b};
-  unsigned u = __builtin_bit_cast(unsigned, p);
-  asm("" : "+v"(u));
-  const f16x2 q = __builtin_bit_cast(f16x2, u);
-  const f16x2 r = {(_Float16)__builtin_fmaf(a, one, -(float)q[0]), (_Float16)__builtin_fmaf(b, one, -(float)q[1])};
-  h0 = u;
-  h1 = __builtin_bit_cast(unsigned, r);
-}
 
 __global__ __launch_bounds__(THREADS, 2) void mha_flash_fwd_x3p_kernel(const __bf16* __restrict__ ws, float* __restrict__ out,
                                                                       float* __restrict__ lse2, int C, int L, float one) {
@@ -89,9 +66,9 @@ __global__ __launch_bounds__(THREADS, 2) void mha_flash_fwd_x3p_kernel(const __b
   const int heads = gridDim.y;
   const int qblk0 = tile.x * QB + wave * 64;
   const size_t piece = (size_t)L * D;
-  const __bf16* qs = ws + ((size_t)b * heads + head) * 9 * piece;
-  const __bf16* ks = qs + 2 * piece;
-  const __bf16* vs = qs + 6 * piece;
+  const __bf16* qs = ws + ((size_t)b * heads + head) * F_COUNT * piece;
+  const __bf16* ks = qs + F_K * piece;
+  const __bf16* vs = qs + F_V * piece;
   const int ntiles = L / KT;
 
   // Q operands (B of S^T = K Q^T): lane (query l31, half h) holds d = 16 s + 8 h .. + 7 of each piece; piece 2 = q0 2^-8 is a
@@ -105,7 +82,7 @@ __global__ __launch_bounds__(THREADS, 2) void mha_flash_fwd_x3p_kernel(const __b
 #pragma unroll
       for (int s = 0; s < KS; ++s)
         qop[G][p][s] = *reinterpret_cast<const u32x4*>(qs + p * piece + (size_t)q * D + 16 * s + 8 * h);
-    const unsigned dn2 = 0x1c001c00u;          // (2^-8, 2^-8) as packed fp16
+    const unsigned dn2 = PAIR_DOWN2;
 #pragma unroll
     for (int s = 0; s < KS; ++s) {
       unsigned w4[4];
@@ -200,7 +177,7 @@ __global__ __launch_bounds__(THREADS, 2) void mha_flash_fwd_x3p_kernel(const __b
         if ((HDIFF_MUTANT & 2) && term == 1)         // (mutation test: the low five bits of q1 2^8 dropped: 2^-17 of q)
 #pragma unroll
           for (int w = 0; w < 4; ++w) qb[w] &= 0xffe0ffe0u;
-        S = mfma32h(kop[term][s], qb, S);
+        S = mfma_f16(kop[term][s], qb, S);
       }
     return S;
   };
@@ -247,9 +224,9 @@ __global__ __launch_bounds__(THREADS, 2) void mha_flash_fwd_x3p_kernel(const __b
   auto pv = [&](const u32x4 (&vop)[2][2], const u32x4 (&pop)[2][2], int G) {
 #pragma unroll
     for (int ab = 0; ab < 2; ++ab) {                   // small terms first
-      O[G] = mfma32h(vop[ab][1], pop[ab][0], O[G]);    // v1 p0
-      O[G] = mfma32h(vop[ab][0], pop[ab][1], O[G]);    // v0 p1
-      O[G] = mfma32h(vop[ab][0], pop[ab][0], O[G]);    // v0 p0
+      O[G] = mfma_f16(vop[ab][1], pop[ab][0], O[G]);    // v1 p0
+      O[G] = mfma_f16(vop[ab][0], pop[ab][1], O[G]);    // v0 p1
+      O[G] = mfma_f16(vop[ab][0], pop[ab][0], O[G]);    // v0 p0
     }
   };
 
@@ -330,7 +307,7 @@ namespace hdiff {
 int64_t mha_fwd_x3p_workspace(int B, int C, int heads, int L) {
   const int Dh = C / heads;
   if ((Dh != 16 && Dh != 32) || L % 256 != 0 || L < 512) return 0;
-  return (int64_t)B * 3 * C * L * 6 + mha_fwd_h2_tail_bytes(B, C);
+  return (int64_t)B * C * L * F_COUNT * 2 + mha_fwd_h2_tail_bytes(B, C);      // F_COUNT fp16 slots of L * D per (sample, head)
 }
 
 // The d_head 32 forward on the pre-split fp16 operands.  Returns false when the shape is not covered or the workspace is missing.

@@ -13,6 +13,7 @@
 #include <stdlib.h>
 
 #include "common.h"
+#include "device.h"
 
 using namespace hdiff;
 
@@ -36,7 +37,6 @@ namespace {
 constexpr int THREADS = 256;
 constexpr int EC = 8;     // channel rows per epilogue group
 constexpr int U = 2;      // k-steps per software-pipeline stage (4 measured no faster)
-typedef float f32x2 __attribute__((ext_vector_type(2)));
 
 // A wave owns 64 output channels x 128 pixels as 2 x 4 accumulators of 32x32.  The tile <-> index maps are chosen so that
 // one vector load feeds all tiles of an operand: lane l31 holds pixels 4*l31 .. 4*l31+3 (one 16-byte load of X per k: the

@@ -21,33 +21,14 @@
 #include <stdlib.h>
 
 #include "common.h"
+#include "conv_x3.h"
+#include "device.h"
 
 using namespace hdiff;
 
 namespace {
 
 constexpr int THREADS = 256;
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ unsigned pack_hi16(float lo, float hi) {
-  return __builtin_amdgcn_perm(__builtin_bit_cast(unsigned, hi), __builtin_bit_cast(unsigned, lo), 0x07060302u);
-}
-__device__ __forceinline__ float top16(float x) {
-  return __builtin_bit_cast(float, __builtin_bit_cast(unsigned, x) & 0xffff0000u);
-}
-// (a, b) -> three packed bf16 pairs, a = a0 + a1 + a2 exactly (truncation split; plain VALU only, see attention_x3.hip)
-__device__ __forceinline__ void split3(float a, float b, unsigned& h0, unsigned& h1, unsigned& h2) {
-  h0 = pack_hi16(a, b);
-  const float ra = a - top16(a), rb = b - top16(b);
-  h1 = pack_hi16(ra, rb);
-  const float sa = ra - top16(ra), sb = rb - top16(rb);
-  h2 = pack_hi16(sa, sb);
-}
-__device__ __forceinline__ f32x16 mfma_bf16(u32x4 a, u32x4 b, f32x16 c) {
-  return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-}
 
 // split-product terms kept (piece of W, piece of X): all i + j <= 2, small ones first
 __device__ constexpr int TERM_W[6] = {2, 1, 0, 1, 0, 0};

@@ -35,6 +35,8 @@
 #include <type_traits>
 
 #include "common.h"
+#include "conv_x3.h"
+#include "device.h"
 
 using namespace hdiff;
 
@@ -48,46 +50,6 @@ constexpr int PIECE_WORDS = 2 * HALF_WORDS;           // 32-bit words of one pie
 constexpr int PSTRIDE = PIECE_WORDS + 8;              // plane stride: each plane is followed by a dump area ...
 constexpr int DUMP_WORD = PIECE_WORDS;                // ... where the unused staging slot of a thread stores (branch-free staging)
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ float swish_fast(float v) { return v * __builtin_amdgcn_rcpf(1.0f + __expf(-v)); }
-
-__device__ __forceinline__ unsigned pack_hi16(float lo, float hi) {
-  return __builtin_amdgcn_perm(__builtin_bit_cast(unsigned, hi), __builtin_bit_cast(unsigned, lo), 0x07060302u);
-}
-__device__ __forceinline__ float top16(float x) {
-  return __builtin_bit_cast(float, __builtin_bit_cast(unsigned, x) & 0xffff0000u);
-}
-// (a, b) -> three packed bf16 pairs, a = a0 + a1 + a2 exactly (plain VALU only: see attention_x3.hip)
-__device__ __forceinline__ void split3(float a, float b, unsigned& h0, unsigned& h1, unsigned& h2) {
-  h0 = pack_hi16(a, b);
-  const float ra = a - top16(a), rb = b - top16(b);
-  h1 = pack_hi16(ra, rb);
-  const float sa = ra - top16(ra), sb = rb - top16(rb);
-  h2 = pack_hi16(sa, sb);
-}
-
-__device__ __forceinline__ f32x16 mfma_bf16(u32x4 a, u32x4 b, f32x16 c) {
-  return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-}
-__device__ __forceinline__ f32x16 mfma_f16(u32x4 a, u32x4 b, f32x16 c) {
-  return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
-}
-// (a, b) -> two packed fp16 pairs with a = h0.lo + h1.lo up to 2^-23 |a| (or 2^-25 absolute), b likewise in the high halves
-// (attention_h2.hip).  `one` is 1.0f in a register the compiler cannot see through: fma(a, 1, -h) must stay an fma
-// (v_fma_mixlo / mixhi_f16: the residual is exact in fp32 and rounded once).
-__device__ __forceinline__ void split2(float a, float b, float one, unsigned& h0, unsigned& h1) {
-  const f16x2 p = {(_Float16)a, (_Float16)b};                 // v_cvt_pk_f16_f32: round to nearest even
-  unsigned u = __builtin_bit_cast(unsigned, p);
-  asm("" : "+v"(u));
-  const f16x2 q = __builtin_bit_cast(f16x2, u);
-  const f16x2 r = {(_Float16)__builtin_fmaf(a, one, -(float)q[0]), (_Float16)__builtin_fmaf(b, one, -(float)q[1])};
-  h0 = u;
-  h1 = __builtin_bit_cast(unsigned, r);
-}
 
 // split-product terms kept (piece of W, piece of X): all i + j <= 2, small ones first
 __device__ constexpr int TERM_W[6] = {2, 1, 0, 1, 0, 0};
@@ -238,7 +200,6 @@ __global__ __launch_bounds__(THREADS, OCC) void conv3x3_x3_kernel(const ConvX3K 
         else fetch_keep(0, c0 + 16 < p.Cin ? c0 + 16 : c0, tie);      // branch-free: the last chunk re-reads its own words, unused
       }
     }
-    typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
     if constexpr (PAIR) {
       unsigned a0, a1, c0w, c1w;
       split2(v[0] * xs, v[1] * xs, one, a0, a1);

@@ -15,6 +15,8 @@
 #include <stdlib.h>
 
 #include "common.h"
+#include "conv_x3.h"
+#include "device.h"
 
 using namespace hdiff;
 
@@ -48,10 +50,6 @@ struct ConvK {
   const unsigned* keep_bits;
   float inv_keep;
 };
-
-// Swish with the hardware reciprocal (1 ulp) instead of an IEEE division: the prologue runs once per staged element
-// and, on gfx950, every VALU instruction is issue time taken from the fp32 MFMA stream.
-__device__ __forceinline__ float swish_fast(float v) { return v * __builtin_amdgcn_rcpf(1.0f + __expf(-v)); }
 
 // Pipeline per CK-channel chunk (one LDS buffer, two barriers):
 //   [registers of chunk c hold the prefetched patch + weight slab]

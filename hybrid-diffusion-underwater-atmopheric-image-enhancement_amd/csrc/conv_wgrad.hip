@@ -14,6 +14,7 @@
 #include <stdlib.h>
 
 #include "common.h"
+#include "device.h"
 
 using namespace hdiff;
 
@@ -47,8 +48,6 @@ struct WgradK {
   const unsigned* keep_bits;
   float inv_keep;
 };
-
-__device__ __forceinline__ float swish_fast_w(float v) { return v * __builtin_amdgcn_rcpf(1.0f + __expf(-v)); }
 
 // ROWS = input stride (1 or 2) when the tile is 4 rows x 32 pixels (each wave then owns one tile row and every LDS operand
 // address in the pixel loop is base + immediate: no VALU between the MFMAs); ROWS = 0 is the generic tile shape.
@@ -162,7 +161,7 @@ __global__ __launch_bounds__(NTHREADS) void conv_wgrad_kernel(const WgradK p) {
     for (int i = 0; i < NXS; ++i) {
       if (x_pos[i] >= 0) {
         float v = xr[i];
-        if (has_gn && ((xlive >> i) & 1u)) v = swish_fast_w(fmaf(v, sG[x_pos[i] >> 20], sG[p.CKW + (x_pos[i] >> 20)]));
+        if (has_gn && ((xlive >> i) & 1u)) v = swish_fast(fmaf(v, sG[x_pos[i] >> 20], sG[p.CKW + (x_pos[i] >> 20)]));
         if constexpr (DROP) v = ((xkeep >> i) & 1u) ? v * p.inv_keep : 0.f;
         sX[(x_pos[i] >> 20) * p.PLANE + ((x_pos[i] >> 10) & 1023) * p.PWp + (x_pos[i] & 1023)] = v;
       }

@@ -21,6 +21,7 @@
 // Workgroups: (Cout / 128) x (Cin / 32) x nsplit, each walking tiles split, split + nsplit, ...; partial slabs
 // dwp[split][tap][ci][co] are summed in split order by hdiff_conv_wgrad_unpack -- no atomics, bitwise reproducible.
 #include "common.h"
+#include "device.h"
 
 using namespace hdiff;
 
@@ -53,8 +54,6 @@ struct WgradF {
   const unsigned* keep_bits;
   float inv_keep;
 };
-
-__device__ __forceinline__ float swish_w3(float v) { return v * __builtin_amdgcn_rcpf(1.0f + __expf(-v)); }
 
 // DROP: the recomputed activation is the forward's dropped one, kept ? swish(..) * inv_keep : 0 -- the keep bits of a thread's 17
 // patch elements are fetched with them (from the element index the activation is read at: padding elements read the bit of the
@@ -146,7 +145,7 @@ __global__ __launch_bounds__(FT) void conv_wgrad3x3_kernel(const WgradF p) {
 #pragma unroll
     for (int i = 0; i < NXE; ++i) {
       float v = xr[i];
-      if (GN) v = swish_w3(fmaf(v, gsc, gsh));
+      if (GN) v = swish_fast(fmaf(v, gsc, gsh));
       if constexpr (DROP) sX[xlds[i]] = (((xbad | ~xkeep) >> i) & 1u) ? 0.f : v * p.inv_keep;
       else sX[xlds[i]] = ((xbad >> i) & 1u) ? 0.f : v;             // the conv pads the ACTIVATED tensor with zeros
     }

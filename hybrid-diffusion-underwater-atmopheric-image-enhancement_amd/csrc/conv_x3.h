@@ -1,0 +1,52 @@
+// Kernel arguments of the split-operand convolutions, shared by the kernel files (conv3x3_x3.hip, conv1x1_x3.hip) and their
+// dispatcher (conv_igemm.hip), and included by those three only: a new field changes these kernels and no others.
+#pragma once
+#include <hip/hip_runtime.h>
+
+namespace hdiff {
+
+// conv3x3_x3.hip: split-bf16 convolution over the 3x3 neighbourhood (plain 3x3 / stride-1 convs and the four output-parity
+// phases of the transposed 5x5 / stride-2 conv: every tap offset lies in [-1, 1]^2)
+struct ConvX3K {
+  const float* x0;
+  const float* x1;
+  int C0, C1, Cin, H, W;
+  const unsigned* wp3;             // [Cin/16][ntaps][3][CoutPad][8] packed bf16 pairs
+  int CoutPad, Cout;
+  const float* bias;
+  const float* gn_scale;
+  const float* gn_shift;
+  const float* addvec;
+  const float* residual;
+  float* out;
+  int tiles_x;
+  int ntaps;                       // 9, 6 or 4
+  int tap_off[9];                  // LDS word offset of the tap inside the staged patch: ((dy + 1) * 34 + (dx + 1)) * 4
+  int OH, OW, out_sy, out_oy, out_sx, out_ox;     // output pixel (vy * out_sy + out_oy, vx * out_sx + out_ox) of an OH x OW plane
+  // fp16-pair form (plain 3x3 behind GroupNorm + Swish): wp3 then holds [Cin/16][9][2][CoutPad][8] words of w 2^t
+  const float* act_scale;          // device {2^s, 2^-s} of the staged activations (hdiff_gn_act_scale), NULL = bf16 triples
+  const float* w_scale;            // the pack's tail {bits of max |w|, 2^-t, 2^t, 0} (hdiff_pack_conv_weight_h2)
+  float one;                       // 1.0f, opaque to the compiler
+  // train-mode dropout between the prologue and the conv (hdiff_conv2d_fwd_dropout; the DROP instantiations only): the staged value
+  // is kept ? swish(..) * inv_keep : 0, bit (e & 31) of keep_bits[e >> 5] for the element's flat NCHW index e < 2^31 in x0
+  const unsigned* keep_bits;
+  float inv_keep;
+};
+void launch_conv3x3_x3(const ConvX3K& k, int B, hipStream_t stream);
+
+// conv1x1_x3.hip: the 1x1 / stride-1 convolution on bf16 triples (no LDS; operands split in registers)
+struct Conv1x1X3K {
+  const float* x0;
+  const float* x1;
+  int C0, Cin;
+  long HW;
+  const unsigned* wp3;             // [Cin/16][1][3][CoutPad][8] packed bf16 pairs (hdiff_pack_conv_weight_x3_taps, one tap)
+  int CoutPad, Cout;
+  const float* bias;
+  const float* addvec;
+  const float* residual;
+  float* out;
+};
+void launch_conv1x1_x3(const Conv1x1X3K& k, int B, hipStream_t stream);
+
+}  // namespace hdiff

@@ -2,6 +2,7 @@
 // (diffusion/Diffusion.py:217-269, diffusion/Model.py:110-168, 446-515).  HBM-bound streaming kernels; compiled with
 // -ffp-contract=off so that the update rounds like the reference's separate tensor ops.
 #include "common.h"
+#include "device.h"
 
 using namespace hdiff;
 

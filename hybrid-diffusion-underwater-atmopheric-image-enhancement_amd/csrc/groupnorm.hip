@@ -9,6 +9,7 @@
 // Each (sample, group) is split over `nsplit` workgroups; every workgroup produces (count, mean, M2) of its slice in one
 // pass over shifted data, and the partials are merged with Chan's formula.
 #include "common.h"
+#include "device.h"
 
 using namespace hdiff;
 

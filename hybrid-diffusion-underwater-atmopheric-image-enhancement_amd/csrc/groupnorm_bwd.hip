@@ -10,6 +10,7 @@
 // kept ? dA * inv_keep : 0 in passes 1 and 3 (bit (e & 31) of keep_bits[e >> 5] for the flat element index e) -- no masked copy
 // of dA is ever written.  A compile-time variant of the two streaming kernels.
 #include "common.h"
+#include "device.h"
 
 using namespace hdiff;
 

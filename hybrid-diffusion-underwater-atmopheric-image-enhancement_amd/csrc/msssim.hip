@@ -34,6 +34,7 @@
 // per-pixel formulas alone switch contraction off, so that identical images give l = cs = 1 and a loss of exactly 0: with fma,
 // 2 mu_x mu_y + C1 and mu_x^2 + mu_y^2 + C1 would round differently for mu_x == mu_y.
 #include "common.h"
+#include "device.h"
 
 using namespace hdiff;
 
@@ -193,16 +194,10 @@ __global__ __launch_bounds__(kThreads) void msssim_moments_kernel(const Params P
   else moments_job<16>(sA, sB, sRow, sw, dst, HW, P.H, P.W, ty0, tx0, l1);
 }
 
-__device__ __forceinline__ double wave_sum_d(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
 // Block-wide sum in a fixed order: wave sums, then thread 0 adds them in index order (valid in thread 0).
 __device__ double block_sum_d(double v) {
   __shared__ double part[kThreads / 64];
-  v = wave_sum_d(v);
+  v = wave_sum(v);
   if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = v;
   __syncthreads();
   double s = 0.0;

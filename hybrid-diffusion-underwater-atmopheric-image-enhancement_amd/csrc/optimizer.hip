@@ -9,6 +9,7 @@
 // 4-byte alignment (gradient views into a flat exchange buffer start anywhere).
 // Deterministic: every partial sum is formed in a fixed order (no float atomics), the final sum in float64.
 #include "common.h"
+#include "device.h"
 
 using namespace hdiff;
 

@@ -2,6 +2,7 @@
 // All HBM- or latency-bound; none of them shows up next to attention/conv at the target sizes, so they are written
 // for clarity: one wave per output of a GEMV, 16-byte grid-stride loops for the elementwise passes.
 #include "common.h"
+#include "device.h"
 
 // The DDPM elementwise steps must round exactly like the reference's separate mul / sub / add tensor ops:
 // fma contraction is forbidden in this file (hipcc defaults to -ffp-contract=fast for device code, and HIP's __fmul_rn

@@ -3,6 +3,7 @@
 // pool and the nearest resize.  All HBM-bound streaming kernels; compiled with -ffp-contract=off so that the forward rounds like
 // the reference's separate tensor ops.  Every reduction is a fixed-order two-stage sum (no float atomics): bitwise reproducible.
 #include "common.h"
+#include "device.h"
 
 using namespace hdiff;
 
@@ -27,16 +28,10 @@ inline int grid_for(int64_t n) {
 
 __device__ __forceinline__ int clamp_t(int64_t t, int T) { return t < 0 ? 0 : (t >= T ? T - 1 : (int)t); }
 
-__device__ __forceinline__ double wave_sum_d(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
 // Block-wide sum in a fixed order: wave sums, then wave 0 adds the four of them in index order.
 __device__ double block_sum_d(double v) {
   __shared__ double part[kTailThreads / 64];
-  v = wave_sum_d(v);
+  v = wave_sum(v);
   const int w = threadIdx.x >> 6;
   if ((threadIdx.x & 63) == 0) part[w] = v;
   __syncthreads();

@@ -1,5 +1,5 @@
 """The parity suite's own sensitivity, demonstrated: libraries that silently damage ONE low-order piece product per split-operand
-kernel (csrc/common.h lists the HDIFF_MUTANT bits; `make mutant mutant2`) must turn the float64 error-class tests RED --
+kernel (csrc/device.h lists the HDIFF_MUTANT bits; `make mutant mutant2`) must turn the float64 error-class tests RED --
 
   build/libhdiff_mutant.so   the term w0 x2 of the split-bf16 3x3 / 1x1 convolutions (fp16-pair 3x3: 2^-16 of every activation);
                              2^-17 of q in the score product of both attention forwards; in the attention backward the cross
@@ -12,6 +12,7 @@ DESIGN.md section 2) the default UNet at 128x128 differs from the real reference
 by 2.4e-5 in the split mode -- two fp32 implementations of this network differ that much through summation order alone -- and
 each forward mutant moves that figure to 2.5e-5 ... 2.9e-5.  No tolerance that the correct fp32 mode passes can see a 2^-16
 term at the model level; the per-kernel float64 comparison (error <= 1.25x the fp32 kernel's) sees it by an order of magnitude or two."""
+import glob
 import os
 import subprocess
 import sys
@@ -49,7 +50,7 @@ def _mutants():
     import hdiff_amd  # noqa: F401
     from hdiff_amd import _capi
     src = [os.path.join(_capi.CSRC, f) for f in ("conv3x3_x3.hip", "conv1x1_x3.hip", "attention_x3p.hip", "attention_h2.hip",
-                                                  "attention_bwd_h2.hip", "common.h")]
+                                                  "attention_bwd_h2.hip")] + glob.glob(os.path.join(_capi.CSRC, "*.h"))
     newest = max(os.path.getmtime(f) for f in src)
     if any(not os.path.isfile(m) or os.path.getmtime(m) < newest for m in (_capi.MUTANT_PATH, _capi.MUTANT2_PATH)):
         _capi.build_mutant()

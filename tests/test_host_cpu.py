@@ -296,6 +296,30 @@ def test_inline_asm_packed_math_keeps_the_trans_use_wait_state(tmp_path, source,
     assert n_pk > 100            # the packed instructions are really there (the check above is not vacuous)
 
 
+def test_counter_stamps_hash_every_header_that_can_change_their_kernels():
+    """profiles/roofline_traffic.json keeps a counter entry only while its `sources` hash as they did when it was measured.  That
+    is sound only if (a) common.h, which every file includes and no entry hashes, holds no device code, and (b) an entry's sources
+    name every other csrc header its .hip files reach through quoted #include lines."""
+    csrc = _capi.CSRC
+    common = open(os.path.join(csrc, "common.h")).read()
+    assert "__device__" not in common and "__global__" not in common
+
+    def reach(name, seen):
+        for inc in re.findall(r'^\s*#\s*include\s+"([^"]+)"', open(os.path.join(csrc, name)).read(), re.M):
+            if inc != "common.h" and inc not in seen and os.path.isfile(os.path.join(csrc, inc)) and os.sep not in inc:
+                seen.add(inc)
+                reach(inc, seen)
+        return seen
+    kernels = json.load(open(os.path.join(ROOT, "profiles", "roofline_traffic.json")))["_stamp"]["kernels"]
+    assert kernels
+    for key, meta in kernels.items():
+        hips = [n for n in meta["sources"] if n.endswith(".hip")]
+        assert hips, key
+        for hip in hips:
+            missing = reach(hip, set()) - set(meta["sources"])
+            assert not missing, (key, hip, sorted(missing))
+
+
 # ----------------------------------------------------------------------------------------------------------------------
 # The drop-in for the reference's own entry files (north_star: "so MainCondition.py is a drop-in")
 # ----------------------------------------------------------------------------------------------------------------------

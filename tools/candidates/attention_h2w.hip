@@ -35,6 +35,7 @@
 
 #include "attention_h2w_sched.h"
 #include "common.h"
+#include "device.h"
 
 using namespace hdiff;
 
@@ -49,25 +50,6 @@ namespace {
 constexpr int THREADS = 256;
 constexpr int BLKB = 5120;                        // bytes of one 32-key block: K 3 x 1 KiB, V 2 x 1 KiB
 constexpr int VOFF = 3072;                        // V steps inside a block
-constexpr float OVERFLOW_LIMIT = 1.2379400e27f;   // 2^90: only NaN / inf inputs get here
-constexpr float P_SHIFT = 8.0f;                   // the reference point enters as P = 2^8
-constexpr float P_TRIP = 32768.0f;                // per-lane sum of one stage's 16 P values that moves the reference
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) unsigned char lds_byte;
-
-__device__ __forceinline__ f32x16 mfma32(u32x4 a, u32x4 b, f32x16 c) {
-  return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-}
-__device__ __forceinline__ f32x16 mfma32h(u32x4 a, u32x4 b, f32x16 c) {
-  return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
-}
-
 // First MFMA of a score chain: D = A B + C with C (the splat -m of the query group) in a tuple of its own.  Written as asm
 // because the compiler only has the tied form (C = D) for 16-register accumulators in VGPRs and would copy the 16 registers of
 // -m into S in front of every chain.  Nothing reads D before the chain's next MFMA (same opcode, back to back: no wait states).
@@ -75,30 +57,6 @@ __device__ __forceinline__ f32x16 mfma32_start(u32x4 a, u32x4 b, const f32x16& c
   f32x16 d;
   asm volatile("v_mfma_f32_32x32x16_bf16 %0, %1, %2, %3" : "=&v"(d) : "v"(a), "v"(b), "v"(c));
   return d;
-}
-
-// bf16 triples by truncation (x = x0 + x1 + x2 exactly; attention_x3.hip) and fp16 pairs by rounding (attention_h2.hip)
-__device__ __forceinline__ unsigned pack_hi16(float lo, float hi) {
-  return __builtin_amdgcn_perm(__builtin_bit_cast(unsigned, hi), __builtin_bit_cast(unsigned, lo), 0x07060302u);
-}
-__device__ __forceinline__ float top16(float x) {
-  return __builtin_bit_cast(float, __builtin_bit_cast(unsigned, x) & 0xffff0000u);
-}
-__device__ __forceinline__ void split3(float a, float b, unsigned& h0, unsigned& h1, unsigned& h2) {
-  h0 = pack_hi16(a, b);
-  const float ra = a - top16(a), rb = b - top16(b);
-  h1 = pack_hi16(ra, rb);
-  const float sa = ra - top16(ra), sb = rb - top16(rb);
-  h2 = pack_hi16(sa, sb);
-}
-__device__ __forceinline__ void split2(float a, float b, float one, unsigned& h0, unsigned& h1) {
-  const f16x2 p = {(_Float16)a, (_Float16)b};                 // v_cvt_pk_f16_f32: round to nearest even
-  unsigned u = __builtin_bit_cast(unsigned, p);
-  asm("" : "+v"(u));
-  const f16x2 q = __builtin_bit_cast(f16x2, u);
-  const f16x2 r = {(_Float16)__builtin_fmaf(a, one, -(float)q[0]), (_Float16)__builtin_fmaf(b, one, -(float)q[1])};
-  h0 = u;
-  h1 = __builtin_bit_cast(unsigned, r);
 }
 
 // bytes of one (sample, head) pair in the workspace: Q pieces [3][L][16] bf16, the key blocks, 16 factors 2^-s
@@ -390,12 +348,12 @@ __global__ __launch_bounds__(THREADS, 2) void mha_flash_fwd_h2w_kernel(const uns
       if ((HDIFF_MUTANT & 8) && piece == 1)                        // (mutation test: the low five bits of every second piece of P dropped)
 #pragma unroll
         for (int w = 0; w < 4; ++w) pb[w] &= 0xffe0ffe0u;
-      O[G ^ 1] = mfma32h(vop[ks], pb, O[G ^ 1]);
+      O[G ^ 1] = mfma_f16(vop[ks], pb, O[G ^ 1]);
       if (G == 0 && piece == 0 && !(H2W_ABL & 2)) vop[ks] = lds_read(vcur_base, vcur_off + VOFF + ks * 1024);
     } else {
       const int kp = TERM_K[nq], qp = TERM_Q[nq];
       if (!((HDIFF_MUTANT & 4) && kp == 0 && qp == 2))             // (mutation test: the k0 q2 term dropped)
-        S[G ^ 1] = nq == 0 ? mfma32_start(kop[kp], qop[G ^ 1][qp], negm[G ^ 1]) : mfma32(kop[kp], qop[G ^ 1][qp], S[G ^ 1]);      // the chain starts from -m
+        S[G ^ 1] = nq == 0 ? mfma32_start(kop[kp], qop[G ^ 1][qp], negm[G ^ 1]) : mfma_bf16(kop[kp], qop[G ^ 1][qp], S[G ^ 1]);      // the chain starts from -m
       bool last = true;
       for (int k = nq + 1; k < 6; ++k) last = last && TERM_K[k] != kp;
       if (G == 0 && last && !(H2W_ABL & 2)) kop[kp] = lds_read(knext_base, knext_off + kp * 1024);
@@ -475,7 +433,7 @@ __global__ __launch_bounds__(THREADS, 2) void mha_flash_fwd_h2w_kernel(const uns
       // score chain of (0, 1) on K(0); K(1) is fetched afterwards; V(0) for the first P V
 #pragma unroll
       for (int nq = 0; nq < 6; ++nq)
-        if (!((HDIFF_MUTANT & 4) && TERM_K[nq] == 0 && TERM_Q[nq] == 2)) S[1] = mfma32(kop[TERM_K[nq]], qop[1][TERM_Q[nq]], nq == 0 ? negm[1] : S[1]);
+        if (!((HDIFF_MUTANT & 4) && TERM_K[nq] == 0 && TERM_Q[nq] == 2)) S[1] = mfma_bf16(kop[TERM_K[nq]], qop[1][TERM_Q[nq]], nq == 0 ? negm[1] : S[1]);
 #pragma unroll
       for (int p = 0; p < 3; ++p) kop[p] = lds_read(0, BLKB + p * 1024);
 #pragma unroll
@@ -484,11 +442,11 @@ __global__ __launch_bounds__(THREADS, 2) void mha_flash_fwd_h2w_kernel(const uns
       // score chain of (1, 0) on K(1) (its reference is final: group 0's first stage has run) and P V of (0, 0)
 #pragma unroll
       for (int nq = 0; nq < 6; ++nq)
-        if (!((HDIFF_MUTANT & 4) && TERM_K[nq] == 0 && TERM_Q[nq] == 2)) S[0] = mfma32(kop[TERM_K[nq]], qop[0][TERM_Q[nq]], nq == 0 ? negm[0] : S[0]);
+        if (!((HDIFF_MUTANT & 4) && TERM_K[nq] == 0 && TERM_Q[nq] == 2)) S[0] = mfma_bf16(kop[TERM_K[nq]], qop[0][TERM_Q[nq]], nq == 0 ? negm[0] : S[0]);
 #pragma unroll
       for (int ks = 0; ks < 2; ++ks) {
-        O[0] = mfma32h(vop[ks], pop[0][1][ks], O[0]);
-        O[0] = mfma32h(vop[ks], pop[0][0][ks], O[0]);
+        O[0] = mfma_f16(vop[ks], pop[0][1][ks], O[0]);
+        O[0] = mfma_f16(vop[ks], pop[0][0][ks], O[0]);
       }
     }
     float mx = S[G][0];
@@ -524,7 +482,7 @@ __global__ __launch_bounds__(THREADS, 2) void mha_flash_fwd_h2w_kernel(const uns
   for (int p = 0; p < 3; ++p) kop[p] = lds_read(0, p * 1024);
 #pragma unroll
   for (int nq = 0; nq < 6; ++nq)
-    if (!((HDIFF_MUTANT & 4) && TERM_K[nq] == 0 && TERM_Q[nq] == 2)) S[0] = mfma32(kop[TERM_K[nq]], qop[0][TERM_Q[nq]], nq == 0 ? negm[0] : S[0]);
+    if (!((HDIFF_MUTANT & 4) && TERM_K[nq] == 0 && TERM_Q[nq] == 2)) S[0] = mfma_bf16(kop[TERM_K[nq]], qop[0][TERM_Q[nq]], nq == 0 ? negm[0] : S[0]);
 
   // Tile t lives in buffer t % 3 (byte offset cur; nxt = tile t + 1's).  Stage s = 2 kb + G of tile t; block kb + 1 of the last
   // block is block 0 of tile t + 1.  The barrier sits in front of the first read of tile t + 1 (the K reload of stage
@@ -568,8 +526,8 @@ __global__ __launch_bounds__(THREADS, 2) void mha_flash_fwd_h2w_kernel(const uns
   // P V of the last stage (group 1 of the last block; vop still holds that block's V)
 #pragma unroll
   for (int ks = 0; ks < 2; ++ks) {
-    O[1] = mfma32h(vop[ks], pop[1][1][ks], O[1]);
-    O[1] = mfma32h(vop[ks], pop[1][0][ks], O[1]);
+    O[1] = mfma_f16(vop[ks], pop[1][1][ks], O[1]);
+    O[1] = mfma_f16(vop[ks], pop[1][0][ks], O[1]);
   }
 
   float* obase = out + ((size_t)b * C + (size_t)head * D) * L;
@@ -603,7 +561,7 @@ namespace hdiff {
 bool launch_mha_fwd_h2w(const float* qkv, float* o, float* lse2, int B, int C, int heads, int L, float qscale, void* ws,
                         int64_t ws_bytes, hipStream_t stream) {
   const int64_t need = mha_fwd_x3p_workspace(B, C, heads, L);
-  if (!mha_fwd_h2_enabled() || need == 0 || ws == nullptr || ws_bytes < need) return false;
+  if (need == 0 || ws == nullptr || ws_bytes < need) return false;
   if (C / heads != 16 || L % 256 != 0) return false;
   static const char* e = getenv("HDIFF_H2W");       // dev knob (A/B inside one gpurun call) while the kernel is being tuned: 1 = this kernel
   if (!(e && atoi(e) == 1)) return false;

@@ -4,8 +4,11 @@ hash of the kernel sources each entry belongs to (code only: comments and whites
 recomputes those hashes and drops an entry whose kernel has changed since (a stale counter is not a measurement of the run that prints it).
 
   python3 tools/traffic_json.py <prof dir of profile_round.sh> <commit> [--out profiles/roofline_traffic.json]
-  python3 tools/traffic_json.py --restamp <commit>      re-hash the sources for the EXISTING values (only when the
-                                                        kernels are byte-identical to the ones that were measured)
+  python3 tools/traffic_json.py --restamp <rev> [key ...]   re-hash the sources of the named entries (default: all) for the EXISTING
+                                                        values, and record <rev> in them: only for entries whose counted kernel
+                                                        `python tools/isa_diff.py <rev>` prints as `same`.  Other entries are left alone.
+The source lists name what decides an entry's instructions: its .hip files, device.h, and conv_x3.h for the convolutions -- not
+common.h, which is host-side only (tests/test_host_cpu.py checks both).
 Counters are KiB per dispatch.  gfx950 correction (MI355X_MICROARCH.md, HBM / rocprofv3 section): FETCH_SIZE reports half
 the bytes of wide (16-byte-per-lane) coalesced loads -> reads = 2 * FETCH_SIZE * 1024 for kernels that load that way
 (attention forward / backward, GroupNorm statistics; calibrated on gn_stats_kernel, which reads its tensor exactly once);
@@ -17,13 +20,13 @@ import bench
 
 # key in the table            kernel-name filter         pass dirs prefix   wide loads   kernel sources
 ENTRIES = (
-    ("mha_flash_fwd_L65536_B16_bf16x3", "mha_flash_fwd_h2_kernel", "x3", True, ["attention_h2.hip", "attention_x3p.hip", "common.h"]),
-    ("mha_flash_fwd_L65536_B16", "fast_kernel<16", "attn", True, ["attention.hip", "common.h"]),
-    ("conv3x3_128_256_B16", "igemm_kernel<2, 8, 12, 5, 1", "conv", False, ["conv_igemm.hip", "common.h"]),
-    ("gn_stats_128_256_B16", "gn_stats_kernel", "gn", True, ["groupnorm.hip", "common.h"]),
-    ("conv3x3_128_256_B16_pairs", "conv3x3_x3_kernel", "convh2", False, ["conv3x3_x3.hip", "conv_igemm.hip", "common.h"]),
-    ("mha_flash_bwd_L65536_B4_bf16x3", "mha_bwd_h2p_kernel", "bwd", True, ["attention_bwd_h2.hip", "attention_bwd.hip", "common.h"]),
-    ("mha_flash_bwd_L65536_B4", "bwd_fused", "bwdf32", True, ["attention_bwd.hip", "common.h"]),
+    ("mha_flash_fwd_L65536_B16_bf16x3", "mha_flash_fwd_h2_kernel", "x3", True, ["attention_h2.hip", "attention_x3p.hip", "device.h"]),
+    ("mha_flash_fwd_L65536_B16", "fast_kernel<16", "attn", True, ["attention.hip", "device.h"]),
+    ("conv3x3_128_256_B16", "igemm_kernel<2, 8, 12, 5, 1", "conv", False, ["conv_igemm.hip", "conv_x3.h", "device.h"]),
+    ("gn_stats_128_256_B16", "gn_stats_kernel", "gn", True, ["groupnorm.hip", "device.h"]),
+    ("conv3x3_128_256_B16_pairs", "conv3x3_x3_kernel", "convh2", False, ["conv3x3_x3.hip", "conv_igemm.hip", "conv_x3.h", "device.h"]),
+    ("mha_flash_bwd_L65536_B4_bf16x3", "mha_bwd_h2p_kernel", "bwd", True, ["attention_bwd_h2.hip", "attention_bwd.hip", "device.h"]),
+    ("mha_flash_bwd_L65536_B4", "bwd_fused", "bwdf32", True, ["attention_bwd.hip", "device.h"]),
 )
 ALGORITHMIC = {
     "mha_flash_fwd_L65536_B16_bf16x3": 16 * 128 * 65536 * (4 + 8 + 4 + 4),   # main kernel (round 5): q as two fp16 pieces (4 B per element), k as four (8 B), v as an fp16 pair (4 B) read, o written
@@ -53,7 +56,10 @@ def main():
         out = sys.argv[sys.argv.index("--out") + 1]
     if sys.argv[1] == "--restamp":
         tab = json.load(open(out))
-        tab["_stamp"] = stamp(sys.argv[2], "values kept; sources re-hashed (kernels byte-identical to the measured ones)")
+        rev, keys = sys.argv[2], [a for a in sys.argv[3:] if a != "--out" and a != out]
+        sources = {key: src for key, _, _, _, src in ENTRIES}
+        for key in keys or sources:
+            tab["_stamp"]["kernels"][key] = {"sources": sources[key], "sha256_16": bench.source_hash(sources[key]), "isa_identical_to": rev}
         json.dump(tab, open(out, "w"), indent=1)
         return
     prof, commit = sys.argv[1], sys.argv[2]
