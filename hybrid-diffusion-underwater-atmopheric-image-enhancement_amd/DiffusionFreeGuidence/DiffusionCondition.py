@@ -10,11 +10,15 @@ What differs underneath (reference lines in brackets):
     loop from a device flag (same ``AssertionError("nan in tensor.")``);
   * per-step noise is drawn in-kernel (Philox4x32-10 + Box-Muller) from a seed taken from torch's default generator,
     so ``torch.manual_seed`` still makes sampling reproducible.
+
+What is added to the reference's surface: ``GaussianDiffusionSampler.forward(..., ddim_steps=S)`` (or ``timesteps=[...]``) samples
+in S <= T model evaluations with the strided DDIM update (Song et al. 2021) under the same guidance, from the same captured 2B step
+with ``hdiff_cfg_ddim_step_loop`` as its one update kernel; ``ddim_timesteps`` and ``ddim_table`` are its schedule, usable on the CPU.
 """
 from __future__ import annotations
 
 import ctypes as C
-from typing import List, Optional
+from typing import List, Optional, Sequence, Tuple
 
 import torch
 import torch.nn as nn
@@ -25,13 +29,60 @@ from .. import _capi
 from .. import engine as E
 
 
-__all__ = ["extract", "GaussianDiffusionTrainer", "GaussianDiffusionSampler"]
+__all__ = ["extract", "GaussianDiffusionTrainer", "GaussianDiffusionSampler", "ddim_timesteps", "ddim_table"]
 
 
 def extract(v, t, x_shape):
     """Coefficients at the given timesteps, cast float64 -> fp32 AFTER the gather, shaped [B,1,1,...] (reference :9-16)."""
     out = torch.gather(v, index=t, dim=0).float().to(t.device)
     return out.view([t.shape[0]] + [1] * (len(x_shape) - 1))
+
+
+def ddim_timesteps(T: int, S: int) -> List[int]:
+    """The S time steps a strided sampler visits out of T: ``tau_k = ((k + 1) * T) // S - 1`` for k = 0 .. S-1 in integer
+    arithmetic -- strictly increasing for 1 <= S <= T, always ending at T - 1 (the step x_T belongs to); S = T gives 0 .. T-1,
+    (1000, 50) gives 19, 39, ..., 999.  ``ValueError`` for S outside [1, T] or not an integer."""
+    if int(S) != S or int(T) != T:
+        raise ValueError(f"ddim_steps and T must be integers, got {S!r} out of {T!r}")
+    T, S = int(T), int(S)
+    if not 1 <= S <= T:
+        raise ValueError(f"ddim_steps must lie in [1, T = {T}], got {S}")
+    return [((k + 1) * T) // S - 1 for k in range(S)]
+
+
+def _checked_timesteps(timesteps: Sequence[int], T: int) -> Tuple[int, ...]:
+    given = list(timesteps)                    # once: a generator is consumed by the first pass over it
+    tau = tuple(int(t) for t in given)
+    if len(tau) < 1 or any(a != b for a, b in zip(tau, given)):
+        raise ValueError("timesteps must be a non-empty list of integers")
+    if tau[0] < 0 or tau[-1] >= T or any(b <= a for a, b in zip(tau, tau[1:])):
+        raise ValueError(f"timesteps must be strictly increasing and lie in [0, T = {T}), got {list(tau)[:8]}"
+                         f"{' ...' if len(tau) > 8 else ''}")
+    return tau
+
+
+def ddim_table(betas: torch.Tensor, timesteps: Sequence[int], eta: float = 0.0) -> torch.Tensor:
+    """Coefficients of the strided DDIM update, float64 ``[S, 5]``, row k = ``(s1m, sa, san, c2, sigma)`` for the step from
+    ``tau_k`` to ``tau_(k-1)``.  With ``ab = cumprod(1 - betas)``, ``a = ab[tau_k]`` and ``a' = ab[tau_(k-1)]`` (``a' = 1`` at k = 0):
+
+        sigma = eta * sqrt((1 - a') / (1 - a)) * sqrt(1 - a / a')
+        s1m = sqrt(1 - a),  sa = sqrt(a),  san = sqrt(a'),  c2 = sqrt(max(1 - a' - sigma^2, 0))
+
+    and one step is ``x0 = (x - eps * s1m) / sa ; x' = san * x0 + c2 * eps + sigma * z``.  ``eta = 0`` is the deterministic DDIM;
+    ``eta = 1`` at stride 1 is the ancestral sampler with the POSTERIOR variance (``sigma^2 == posterior_var``,
+    ``san / sa == coeff1``, ``san * s1m / sa - c2 == coeff2``), not the reference's fixed-large variance.  Computed on the CPU."""
+    b = torch.as_tensor(betas).detach().to(device="cpu", dtype=torch.float64)
+    tau = _checked_timesteps(timesteps, int(b.numel()))
+    eta = float(eta)
+    if not eta >= 0.0:
+        raise ValueError(f"eta must be >= 0, got {eta}")
+    ab = torch.cumprod(1.0 - b, dim=0)
+    idx = torch.tensor(tau, dtype=torch.int64)
+    a = ab[idx]
+    a_prev = torch.cat([torch.ones(1, dtype=torch.float64), a[:-1]])
+    sigma = eta * torch.sqrt((1.0 - a_prev) / (1.0 - a)) * torch.sqrt(1.0 - a / a_prev)
+    c2 = torch.sqrt(torch.clamp(1.0 - a_prev - sigma * sigma, min=0.0))
+    return torch.stack([torch.sqrt(1.0 - a), torch.sqrt(a), torch.sqrt(a_prev), c2, sigma], dim=1)
 
 
 def _stream(device) -> int:
@@ -124,6 +175,31 @@ class _SamplerPlan:
         self._variants = {}
         self._sampler = sampler
 
+    def _build_ddim(self, inject_noise: bool, ddim) -> E.Plan:
+        """The strided step: the same 2B UNet launches + ONE fused DDIM update with the same bookkeeping
+        (hdiff_cfg_ddim_step_loop); the device-resident counter is the position k in ``timesteps``, the time vector tau_k."""
+        timesteps, eta, clip_x0 = ddim
+        up, n, dev = self.unet, self.n, self.x.device
+        tab = ddim_table(self._sampler.betas, timesteps, eta).float().contiguous().to(dev)   # f64 -> f32 once per entry
+        t_tab = torch.tensor(timesteps, dtype=torch.int64, device=dev)
+        p = E.Plan(dev)
+        p.ops.extend(up.plan.ops)
+        eps = up.out
+        d = _capi.CfgDdimLoopDesc()
+        d.x, d.eps_c, d.eps_u = self.x.data_ptr(), eps.data_ptr(), eps.data_ptr() + 4 * n
+        d.noise = self.noise.data_ptr() if inject_noise else None
+        d.x_next = self.x.data_ptr()
+        d.tab, d.t_tab = tab.data_ptr(), t_tab.data_ptr()
+        d.step_ptr, d.nsteps, d.clip_x0 = self.step.data_ptr(), len(timesteps), int(bool(clip_x0))
+        d.w, d.seed = float(self._sampler.w), self.seed
+        d.nan_flag, d.n = self.nan_flag.data_ptr(), n
+        d.x_dup0, d.x_dup1 = up.x.data_ptr(), up.x.data_ptr() + 4 * n
+        d.t_next, d.t_count = up.t.data_ptr(), 2 * self.B
+        d.done_counter = self.done.data_ptr()
+        p.keep((d, tab, t_tab))                    # the tables live exactly as long as the step that reads them
+        p.call("hdiff_cfg_ddim_step_loop", C.byref(d))
+        return p
+
     def _build(self, inject_noise: bool) -> E.Plan:
         """One denoising step = the 2B UNet launches + ONE fused update kernel.  The update also writes x_next into both
         halves of the UNet's input, decrements the device-resident step and refills the time vector (hdiff_ddpm_step_loop),
@@ -147,29 +223,30 @@ class _SamplerPlan:
         p.call("hdiff_ddpm_step_loop", C.byref(d))
         return p
 
-    def reset(self, x_T: torch.Tensor, labels: torch.Tensor, step: Optional[int] = None) -> None:
+    def reset(self, x_T: torch.Tensor, labels: torch.Tensor, step: Optional[int] = None, t: Optional[int] = None) -> None:
         """Loop state at its start: x = x_T (also in both halves of the UNet input), labels = [labels; 0] (reference :76-77),
-        the time vector and the device-resident step at T - 1 (or `step`), flags cleared."""
+        the time vector and the device-resident step at T - 1 (or `step`), flags cleared.  The strided loop counts positions:
+        `step` = S - 1 and the time vector at `t` = tau_(S-1)."""
         T = int(self._sampler.T)
         step = T - 1 if step is None else int(step)
         self.x.copy_(x_T)
         self.unet.x[:self.B].copy_(x_T)
         self.unet.x[self.B:].copy_(x_T)
         self.unet.labels.copy_(torch.cat([labels, torch.zeros_like(labels)], dim=0))
-        self.unet.t.fill_(step)
+        self.unet.t.fill_(step if t is None else int(t))
         self.step.fill_(step)
         self.nan_flag.zero_()
         self.done.zero_()
 
-    def variant(self, inject_noise: bool, seed: int) -> E.Plan:
+    def variant(self, inject_noise: bool, seed: int, ddim=None) -> E.Plan:
         # the guidance weight is a launch argument of the fused update: the reference reads self.w on every step (:78), so
-        # a changed sampler.w must rebuild the captured step
+        # a changed sampler.w must rebuild the captured step.  ddim = (timesteps, eta, clip_x0) selects the strided step.
         key = (inject_noise, seed if not inject_noise else 0, _capi.lib().hdiff_get_contraction_mode(),
-               float(self._sampler.w))
+               float(self._sampler.w), ddim)
         if key not in self._variants:
             self.seed = seed
             self._variants.clear()          # a graph bakes its seed (and the contraction mode): keep one live variant
-            self._variants[key] = self._build(inject_noise)
+            self._variants[key] = self._build(inject_noise) if ddim is None else self._build_ddim(inject_noise, ddim)
         return self._variants[key]
 
 
@@ -232,9 +309,19 @@ class GaussianDiffusionSampler(nn.Module):
         return self.predict_xt_prev_mean_from_eps(x_t, t, eps=eps), var
 
     # -- the loop -----------------------------------------------------------------------------------------------------
-    def forward(self, x_T, labels, *, noise_by_step=None, trajectory: Optional[List[torch.Tensor]] = None):
+    def forward(self, x_T, labels, *, ddim_steps: Optional[int] = None, eta: float = 0.0,
+                timesteps: Optional[Sequence[int]] = None, clip_x0: bool = False, noise_by_step=None,
+                trajectory: Optional[List[torch.Tensor]] = None):
         """``noise_by_step[time_step]`` injects the per-step z (parity tests); ``trajectory`` collects the pre-clip
-        x_t after every step.  Both default to the reference behaviour."""
+        x_t after every step.  Both default to the reference behaviour.
+
+        ``ddim_steps=S`` (the time steps of ``ddim_timesteps(T, S)``) or an explicit strictly increasing ``timesteps`` list
+        switches to the strided DDIM sampler: S model evaluations instead of T, same guidance, same 2B plan and graph replay.
+        ``eta`` scales the step noise (0: deterministic, no seed is drawn; 1: posterior-variance ancestral steps -- ``ddim_table``),
+        ``clip_x0`` clamps the predicted x_0 to [-1, 1] before it is used.  In this mode ``noise_by_step[k]`` is indexed by the
+        POSITION k in the time-step list (S entries, entry 0 unused) and ``trajectory`` receives S states.  Without
+        ``ddim_steps`` / ``timesteps`` the T-step ancestral loop of the reference runs."""
+        ddim = self._ddim_arguments(ddim_steps, eta, timesteps, clip_x0, noise_by_step)
         x_T, labels = _gpu_input(x_T, "x_T"), _gpu_input(labels, "labels")
         if torch.is_grad_enabled():
             # The reference runs here too (DiffusionCondition.py:82-98) and records an autograd graph through all 2T model
@@ -252,9 +339,26 @@ class GaussianDiffusionSampler(nn.Module):
                               "torch.no_grad() and returns a tensor without grad_fn (the reference would record a graph "
                               "through all 2T model evaluations)", RuntimeWarning, stacklevel=2)
         with torch.no_grad(), torch.cuda.device(x_T.device):
-            return self._forward(x_T, labels, noise_by_step, trajectory)
+            return self._forward(x_T, labels, noise_by_step, trajectory, ddim)
 
-    def _forward(self, x_T, labels, noise_by_step, trajectory):
+    def _ddim_arguments(self, ddim_steps, eta, timesteps, clip_x0, noise_by_step):
+        """None for the ancestral loop, else the validated (timesteps, eta, clip_x0) of the strided one (``ValueError`` otherwise)."""
+        if ddim_steps is None and timesteps is None:
+            if float(eta) != 0.0 or clip_x0:
+                raise ValueError("eta / clip_x0 belong to the strided sampler: give ddim_steps or timesteps with them")
+            return None
+        if ddim_steps is not None and timesteps is not None:
+            raise ValueError("give ddim_steps or timesteps, not both")
+        tau = tuple(ddim_timesteps(self.T, ddim_steps)) if timesteps is None else _checked_timesteps(timesteps, int(self.T))
+        eta = float(eta)
+        if not eta >= 0.0:
+            raise ValueError(f"eta must be >= 0, got {eta}")
+        if noise_by_step is not None and len(noise_by_step) != len(tau):
+            raise ValueError(f"noise_by_step has {len(noise_by_step)} entries for {len(tau)} time steps (one per position, "
+                             "entry 0 unused)")
+        return tau, eta, bool(clip_x0)
+
+    def _forward(self, x_T, labels, noise_by_step, trajectory, ddim=None):
         lib = _capi.lib()
         B, Cx, H, W = (int(v) for v in x_T.shape)
         dev = x_T.device
@@ -268,13 +372,22 @@ class GaussianDiffusionSampler(nn.Module):
         sp.unet.plan.pack_weights()
         self.model.check_indices(torch.zeros_like(labels), labels)
         inject = noise_by_step is not None
-        seed = 0 if inject else int(torch.empty((), dtype=torch.int64).random_().item())
-        plan = sp.variant(inject, seed)
-        sp.reset(x_T, labels)
+        if ddim is None:
+            seed = 0 if inject else int(torch.empty((), dtype=torch.int64).random_().item())
+            plan = sp.variant(inject, seed)
+            sp.reset(x_T, labels)
+            steps = self.T
+        else:
+            tau, eta, _ = ddim
+            # the deterministic sampler consumes no randomness: torch's generator is left where it was
+            seed = 0 if inject or eta == 0.0 else int(torch.empty((), dtype=torch.int64).random_().item())
+            plan = sp.variant(inject, seed, ddim)
+            steps = len(tau)
+            sp.reset(x_T, labels, step=steps - 1, t=tau[-1])
         graphed = self.use_graph and trajectory is None
         if graphed:
             plan.capture()
-        for time_step in reversed(range(self.T)):
+        for time_step in reversed(range(steps)):          # the strided loop counts positions k in its time-step list
             if inject and time_step > 0:
                 sp.noise.copy_(noise_by_step[time_step])
             if graphed:

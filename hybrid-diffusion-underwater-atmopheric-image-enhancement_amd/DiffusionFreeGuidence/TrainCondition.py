@@ -12,7 +12,8 @@ Differences: the data set.  The reference hard-codes torchvision CIFAR10; here `
 "folder" (``data_dir/<domain>/*.png``: clean image = x_0, domain index = label), "reference_sets" (the reference's own
 ``data/`` tree of underwater / atmospheric sets, ``hdiff_amd.datasets``), "synthetic", or "cifar10" (only if torchvision is
 installed).  Optional keys, all with reference-equivalent defaults: ``num_labels`` (10), ``num_workers`` (4),
-``max_steps_per_epoch``.  Under ``torch.distributed.run`` (WORLD_SIZE > 1) training is data-parallel: replicated weights,
+``max_steps_per_epoch``; for ``eval`` alone ``ddim_steps`` (absent / None: the reference's T-step ancestral loop; S: the strided DDIM
+sampler of ``GaussianDiffusionSampler.forward`` in S model evaluations), ``ddim_eta`` (0.0) and ``ddim_clip_x0`` (False).  Under ``torch.distributed.run`` (WORLD_SIZE > 1) training is data-parallel: replicated weights,
 per-rank shard of every epoch, ONE mean all-reduce of the gradients per step (hdiff_amd.parallel), rank-0 checkpoints.
 """
 import os
@@ -165,6 +166,10 @@ def eval(modelConfig: Dict) -> torch.Tensor:
         x_T = torch.randn(size=[batch, 3, side, side], device=device)
         save_image(torch.clamp(x_T * 0.5 + 0.5, 0, 1), os.path.join(cfg["sampled_dir"], cfg["sampledNoisyImgName"]),
                    nrow=cfg["nrow"])
-        images = sampler(x_T, labels) * 0.5 + 0.5                   # [-1, 1] -> [0, 1]
+        if cfg.get("ddim_steps") is None:
+            images = sampler(x_T, labels) * 0.5 + 0.5               # [-1, 1] -> [0, 1]
+        else:
+            images = sampler(x_T, labels, ddim_steps=int(cfg["ddim_steps"]), eta=float(cfg.get("ddim_eta", 0.0)),
+                             clip_x0=bool(cfg.get("ddim_clip_x0", False))) * 0.5 + 0.5
         save_image(images, os.path.join(cfg["sampled_dir"], cfg["sampledImgName"]), nrow=cfg["nrow"])
         return images

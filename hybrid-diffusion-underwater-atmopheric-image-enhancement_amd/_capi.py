@@ -34,6 +34,17 @@ class DdpmLoopDesc(C.Structure):
     ]
 
 
+class CfgDdimLoopDesc(C.Structure):
+    """hdiff_cfg_ddim_loop_desc (include/hdiff.h)."""
+    _fields_ = [
+        ("x", C.c_void_p), ("eps_c", C.c_void_p), ("eps_u", C.c_void_p), ("noise", C.c_void_p), ("x_next", C.c_void_p),
+        ("tab", C.c_void_p), ("t_tab", C.c_void_p), ("step_ptr", C.c_void_p), ("nsteps", C.c_int), ("clip_x0", C.c_int),
+        ("w", C.c_double), ("seed", C.c_uint64), ("nan_flag", C.c_void_p), ("n", C.c_int64),
+        ("x_dup0", C.c_void_p), ("x_dup1", C.c_void_p), ("t_next", C.c_void_p), ("t_count", C.c_int),
+        ("done_counter", C.c_void_p),
+    ]
+
+
 class ConvDesc(C.Structure):
     _fields_ = [
         ("x0", C.c_void_p), ("x1", C.c_void_p), ("C0", C.c_int), ("C1", C.c_int),
@@ -138,6 +149,9 @@ _PROTOS = {
     "hdiff_ddpm_step": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                   C.c_void_p, C.c_void_p, C.c_int, C.c_double, C.c_uint64, C.c_void_p, C.c_int64, C.c_void_p]),
     "hdiff_ddpm_step_loop": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "hdiff_cfg_ddim_step": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
+                                      C.c_double, C.c_int, C.c_uint64, C.c_void_p, C.c_int64, C.c_void_p]),
+    "hdiff_cfg_ddim_step_loop": (C.c_int, [C.c_void_p, C.c_void_p]),
     "hdiff_fill_t": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     "hdiff_step_decrement": (C.c_int, [C.c_void_p, C.c_void_p]),
     "hdiff_ddim_step": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int64,

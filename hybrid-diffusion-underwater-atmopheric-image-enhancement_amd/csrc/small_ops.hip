@@ -215,6 +215,79 @@ __global__ void ddpm_step_kernel(const DdpmStepK p) {
   }
 }
 
+// One strided DDIM step with classifier-free guidance (Song et al. 2021, eq. 12, on a sub-sequence tau of the T training steps):
+//   eps = (1+w)*eps_c - w*eps_u ; x0 = (x - eps*s1m) / sa ; [x0 = clamp(x0, -1, 1) ; eps = (x - sa*x0) / s1m]
+//   v = san*x0 + c2*eps (+ sigma*z when k > 0 and sigma > 0),   tab[k] = {s1m, sa, san, c2, sigma} of position k in tau
+// one rounding per written operation (contraction is off in this file), so a plain torch program of the same lines gives the same
+// bits.  The clamp is written with compares: a NaN stays a NaN (torch.clamp), fminf / fmaxf would swallow it.
+// The bookkeeping is ddpm_step_kernel's: x_next also goes to the two halves of the next UNet input, the workgroup that finishes
+// last decrements the device-resident position and writes the next time vector, here tau[k - 1] from t_tab.
+// x and x_next may be the same buffer: neither is __restrict__.
+struct CfgDdimStepK {
+  const float* x; const float* eps_c; const float* eps_u; const float* noise; float* x_next;
+  const float* tab; const int64_t* t_tab; int32_t* step_ptr; int nsteps; int clip_x0; float w1, w; uint64_t seed;
+  int32_t* nan_flag; int64_t n;
+  float* x_dup0; float* x_dup1; int64_t* t_next; int t_count; unsigned* done_counter;     // loop bookkeeping (all optional)
+};
+__global__ void cfg_ddim_step_kernel(const CfgDdimStepK p) {
+  int k = *p.step_ptr;
+  k = k < 0 ? 0 : (k >= p.nsteps ? p.nsteps - 1 : k);          // never index outside the tables, whatever the counter holds
+  const float* row = p.tab + 5 * (size_t)k;
+  const float s1m = row[0], sa = row[1], san = row[2], c2 = row[3], sg = row[4];
+  const bool add_noise = k > 0 && sg > 0.f;
+  const bool clip = p.clip_x0 != 0;
+  const float* x = p.x;
+  float* x_next = p.x_next;
+  bool bad = false;
+  const int64_t n = p.n, nq = (n + 3) >> 2;
+  for (int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; q < nq; q += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t i0 = q << 2;
+    float z[4] = {0.f, 0.f, 0.f, 0.f};
+    if (add_noise && p.noise == nullptr) {
+      const float4 zz = normal4(p.seed, (uint64_t)q, (uint64_t)(uint32_t)k);
+      z[0] = zz.x; z[1] = zz.y; z[2] = zz.z; z[3] = zz.w;
+    }
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const int64_t i = i0 + e;
+      if (i < n) {
+        if (add_noise && p.noise != nullptr) z[e] = p.noise[i];
+        const float xi = x[i];
+        float eps = p.w1 * p.eps_c[i] - p.w * p.eps_u[i];
+        float x0 = (xi - eps * s1m) / sa;
+        if (clip) {
+          x0 = x0 < -1.f ? -1.f : (x0 > 1.f ? 1.f : x0);
+          eps = (xi - sa * x0) / s1m;
+        }
+        float v = san * x0 + c2 * eps;
+        if (add_noise) v = v + sg * z[e];
+        bad |= (v != v);
+        x_next[i] = v;
+        if (p.x_dup0) p.x_dup0[i] = v;
+        if (p.x_dup1) p.x_dup1[i] = v;
+      }
+    }
+  }
+  if (__any(bad)) {
+    if ((threadIdx.x & 63) == 0) atomicOr(p.nan_flag, 1);
+  }
+  if (p.done_counter != nullptr) {
+    __shared__ int is_last;
+    __syncthreads();
+    if (threadIdx.x == 0) is_last = atomicInc(p.done_counter, gridDim.x - 1) == gridDim.x - 1;   // wraps back to 0 by itself
+    __syncthreads();
+    if (is_last) {
+      const int next = *p.step_ptr - 1;
+      const int kn = next < 0 ? 0 : (next >= p.nsteps ? p.nsteps - 1 : next);
+      if (p.t_count > 0) {
+        const int64_t t = p.t_tab[kn];
+        for (int i = threadIdx.x; i < p.t_count; i += blockDim.x) p.t_next[i] = t;
+      }
+      if (threadIdx.x == 0) *p.step_ptr = next;
+    }
+  }
+}
+
 __global__ void fill_t_kernel(int64_t* t, const int32_t* step_ptr, int B) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i < B) t[i] = (int64_t)(*step_ptr);
@@ -414,6 +487,33 @@ int hdiff_ddpm_step_loop(const hdiff_ddpm_loop_desc* d, hdiff_stream_t stream) {
               d->done_counter};
   hipLaunchKernelGGL(ddpm_step_kernel, dim3(grid_for(d->n, 4)), dim3(256), 0, (hipStream_t)stream, k);
   HDIFF_CHECK_LAUNCH("ddpm_step_kernel");
+  return HDIFF_OK;
+}
+
+int hdiff_cfg_ddim_step(const float* x, const float* eps_c, const float* eps_u, const float* noise, float* x_next,
+                        const float* tab, const int32_t* step_ptr, int nsteps, double w, int clip_x0, uint64_t seed,
+                        int32_t* nan_flag, int64_t n, hdiff_stream_t stream) {
+  HDIFF_CHECK_ARG(x && eps_c && eps_u && x_next && tab && step_ptr && nan_flag, "cfg_ddim_step: null pointer");
+  HDIFF_CHECK_ARG(nsteps > 0 && n > 0, "cfg_ddim_step: bad sizes nsteps=%d n=%lld", nsteps, (long long)n);
+  (void)hipGetLastError();  // drop any stale error left by another HIP user in this thread
+  CfgDdimStepK k{x, eps_c, eps_u, noise, x_next, tab, nullptr, const_cast<int32_t*>(step_ptr), nsteps, clip_x0 != 0,
+                 (float)(1.0 + w), (float)w, seed, nan_flag, n, nullptr, nullptr, nullptr, 0, nullptr};
+  hipLaunchKernelGGL(cfg_ddim_step_kernel, dim3(grid_for(n, 4)), dim3(256), 0, (hipStream_t)stream, k);
+  HDIFF_CHECK_LAUNCH("cfg_ddim_step_kernel");
+  return HDIFF_OK;
+}
+
+int hdiff_cfg_ddim_step_loop(const hdiff_cfg_ddim_loop_desc* d, hdiff_stream_t stream) {
+  HDIFF_CHECK_ARG(d && d->x && d->eps_c && d->eps_u && d->x_next && d->tab && d->step_ptr && d->nan_flag && d->done_counter,
+                  "cfg_ddim_step_loop: null pointer");
+  HDIFF_CHECK_ARG(d->nsteps > 0 && d->n > 0 && d->t_count >= 0 && (d->t_count == 0 || (d->t_next && d->t_tab)),
+                  "cfg_ddim_step_loop: bad sizes nsteps=%d n=%lld t_count=%d", d->nsteps, (long long)d->n, d->t_count);
+  (void)hipGetLastError();  // drop any stale error left by another HIP user in this thread
+  CfgDdimStepK k{d->x, d->eps_c, d->eps_u, d->noise, d->x_next, d->tab, d->t_tab, d->step_ptr, d->nsteps, d->clip_x0 != 0,
+                 (float)(1.0 + d->w), (float)d->w, d->seed, d->nan_flag, d->n, d->x_dup0, d->x_dup1, d->t_next, d->t_count,
+                 d->done_counter};
+  hipLaunchKernelGGL(cfg_ddim_step_kernel, dim3(grid_for(d->n, 4)), dim3(256), 0, (hipStream_t)stream, k);
+  HDIFF_CHECK_LAUNCH("cfg_ddim_step_kernel");
   return HDIFF_OK;
 }
 

@@ -346,6 +346,40 @@ typedef struct hdiff_ddpm_loop_desc {
   uint32_t* done_counter;
 } hdiff_ddpm_loop_desc;
 int hdiff_ddpm_step_loop(const hdiff_ddpm_loop_desc* d, hdiff_stream_t stream);
+/* One STRIDED DDIM step with classifier-free guidance for the same sampler (no call site in the reference, whose label-conditioned
+ * tree only has the T-step ancestral loop; Song et al. 2021, eq. 12 on a sub-sequence tau_0 < ... < tau_(S-1) of the time steps).
+ * k = *step_ptr (int32, device resident, clamped into [0, nsteps)) is the POSITION in tau; tab[k] = {sqrt(1 - a), sqrt(a),
+ * sqrt(a'), sqrt(max(1 - a' - sigma^2, 0)), sigma} in fp32 with a = alphas_bar[tau_k], a' = alphas_bar[tau_(k-1)] (1 at k = 0):
+ *   eps = (1+w)*eps_c - w*eps_u ; x0 = (x - eps*tab[k][0]) / tab[k][1]
+ *   clip_x0 != 0:  x0 = clamp(x0, -1, 1) (a NaN stays a NaN) ; eps = (x - tab[k][1]*x0) / tab[k][0]
+ *   x_next = tab[k][2]*x0 + tab[k][3]*eps  (+ tab[k][4]*z  when k > 0 and tab[k][4] > 0)
+ * each written operation rounded once, w cast as in hdiff_ddpm_step.  z: noise[i], or with noise == NULL the in-kernel Philox
+ * stream of hdiff_ddpm_step with counter (seed, k, element).  nan_flag is OR-ed with 1 on a NaN output.  x and x_next may alias. */
+int hdiff_cfg_ddim_step(const float* x, const float* eps_c, const float* eps_u, const float* noise, float* x_next,
+                        const float* tab /* [nsteps][5] */, const int32_t* step_ptr, int nsteps, double w, int clip_x0,
+                        uint64_t seed, int32_t* nan_flag, int64_t n, hdiff_stream_t stream);
+/* The same update with the loop's bookkeeping folded in, as hdiff_ddpm_step_loop does for the ancestral step: ONE launch per step.
+ * Every workgroup also stores x_next to x_dup0 / x_dup1 when given; the workgroup that finishes last writes *step_ptr - 1 to
+ * *step_ptr and t_tab[max(*step_ptr - 1, 0)] (t_tab[k] = tau_k, int64) to t_next[0 .. t_count).  done_counter: one uint32, zero
+ * before the first launch; it wraps back to zero by itself. */
+typedef struct hdiff_cfg_ddim_loop_desc {
+  const float* x; const float* eps_c; const float* eps_u;
+  const float* noise;                 /* NULL: in-kernel Philox noise */
+  float* x_next;
+  const float* tab;                   /* [nsteps][5] fp32 */
+  const int64_t* t_tab;               /* [nsteps]; may be NULL when t_count = 0 */
+  int32_t* step_ptr;
+  int nsteps;
+  int clip_x0;
+  double w;
+  uint64_t seed;
+  int32_t* nan_flag;
+  int64_t n;
+  float* x_dup0; float* x_dup1;       /* optional */
+  int64_t* t_next; int t_count;       /* optional (t_count = 0) */
+  uint32_t* done_counter;
+} hdiff_cfg_ddim_loop_desc;
+int hdiff_cfg_ddim_step_loop(const hdiff_cfg_ddim_loop_desc* d, hdiff_stream_t stream);
 /* step bookkeeping for the captured loop: t[b] = *step for all b (int64 vector for the embedding gather) */
 int hdiff_fill_t(int64_t* t, const int32_t* step_ptr, int B, hdiff_stream_t stream);
 int hdiff_step_decrement(int32_t* step_ptr, hdiff_stream_t stream);
