@@ -33,7 +33,8 @@ def set_contraction_mode(mode: str) -> None:
     and the product as a few piece products on the 16-bit MFMA, each exact in the fp32 accumulator.  As shipped: every operand of the
     attention contractions is an fp16 PAIR (x 2^s = h0 + h1: 22-23 of fp32's 24 bits) -- the scores with a balance per product term
     (four terms at d_head 16, three at d_head 32: attention_h2.hip / attention_x3p.hip), P.V three terms, the backward's five products
-    likewise (attention_bwd_h2.hip) -- and so are both operands of the 3x3 convolutions behind GroupNorm + Swish; 3x3 convolutions
+    likewise (attention_bwd_h2.hip) -- and so are both operands of the 3x3 convolutions behind GroupNorm + Swish and of UpSample's /
+    DownSample's convolutions (their range: one word per sample from the producing kernel's epilogue); 3x3 convolutions
     without a known input range and the 1x1 convolutions run on bf16 TRIPLES (x = x0 + x1 + x2 exactly, the six products with
     i + j <= 2).  fp32-class accuracy: the error against float64 is <= 1.25x (attention) / 1.5x (conv) the fp32 kernels' rms
     (tests/test_gpu_ops.py, tests/test_gpu_backward.py), the whole golden / oracle suite passes in this mode at the fp32 tolerances

@@ -60,6 +60,12 @@ class ConvDesc(C.Structure):
     ]
 
 
+class ConvRange(C.Structure):
+    """hdiff_conv_range (include/hdiff.h)."""
+    _fields_ = [("absmax_out", C.c_void_p), ("absmax_in", C.c_void_p), ("wp_h2_taps", C.c_void_p),
+                ("wp_h2_s2", C.c_void_p)]
+
+
 class MsssimDesc(C.Structure):
     """hdiff_msssim_desc (include/hdiff.h)."""
     MAX_PAIRS, MAX_SCALES, MAX_WINDOW = 15, 5, 33
@@ -100,6 +106,13 @@ _PROTOS = {
                                          C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "hdiff_conv2d_fwd": (C.c_int, [C.POINTER(ConvDesc), C.c_void_p]),
     "hdiff_conv2d_fwd_dropout": (C.c_int, [C.POINTER(ConvDesc), C.c_void_p, C.c_float, C.c_void_p]),
+    "hdiff_conv2d_fwd_range": (C.c_int, [C.POINTER(ConvDesc), C.POINTER(ConvRange), C.c_void_p]),
+    "hdiff_range_words_zero": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
+    "hdiff_pack_conv_weight_h2_taps_words": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int64)]),
+    "hdiff_pack_conv_weight_h2_taps": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                                 C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int, C.c_void_p]),
+    "hdiff_pack_conv_weight_h2_s2_words": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int64)]),
+    "hdiff_pack_conv_weight_h2_s2": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "hdiff_conv2d_fwd_workspace": (C.c_int, [C.POINTER(ConvDesc), C.POINTER(C.c_int64)]),
     "hdiff_gn_stats": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
                                  C.c_void_p]),

@@ -6,7 +6,9 @@
 //
 // Why triples and not the fp16 pairs of the 3x3 kernel: these inputs (a ResBlock's output, the attention output, a block's
 // input) have no range that is known before they are read, and a maximum pass per launch costs a fifth of what the pairs would
-// save (profiles/r04_rejected_candidates.txt).  bf16 has fp32's exponent range: no scale, no pass.
+// save (profiles/r04_rejected_candidates.txt).  bf16 has fp32's exponent range: no scale, no pass.  (A range CAN be had for
+// free from the producer's epilogue -- this kernel leaves one for its consumers, absmax_out below, as conv3x3_x3.hip does --
+// but here halving the MFMAs is worth about 1 ms per step: the ablations in the loop are additive, stores 34 %, MFMAs 25 %.)
 //
 // Why its own kernel (round 3 routed the 1x1 convs through the 3x3 kernel's centre tap and measured them SLOWER than the fp32
 // kernel, 61-84 against 76-86 TFLOP/s): there one tap gives the staging split nothing to hide behind -- a workgroup split a
@@ -184,6 +186,11 @@ __global__ __launch_bounds__(THREADS, 3) void conv1x1_x3_kernel(const Conv1x1X3K
   // accumulator register r of tile mt holds channel co0 + 32 mt + (r & 3) + 8 (r >> 2) + 4 h
   const size_t blk = ((size_t)b * p.Cout) * p.HW + px0;
   const bool full = co0 + 64 <= p.Cout;
+  // absmax_out: bits of the largest |v| this lane stores (conv3x3_x3.hip has the same epilogue), behind a workgroup-uniform test:
+  // the 128 extra vector instructions are 13 % of what a 128-channel launch executes, and only the out-projections in front of
+  // a DownSample want the word
+  const bool track = p.absmax_out != nullptr;
+  unsigned amax = 0u;
 #pragma unroll
   for (int mt = 0; mt < MT; ++mt) {
 #pragma unroll
@@ -211,8 +218,21 @@ __global__ __launch_bounds__(THREADS, 3) void conv1x1_x3_kernel(const Conv1x1X3K
         v += add[j];
         if (p.residual) v += res[j];
         if (ok[j]) *reinterpret_cast<f32x2*>(p.out + blk + (size_t)co * p.HW + 2u * l31) = v;
+        if (track && ok[j]) {
+          const unsigned v0 = __builtin_bit_cast(unsigned, v[0]) & 0x7fffffffu, v1 = __builtin_bit_cast(unsigned, v[1]) & 0x7fffffffu;
+          const unsigned vm = v0 > v1 ? v0 : v1;
+          amax = vm > amax ? vm : amax;
+        }
       }
     }
+  }
+  if (track) {       // one atomicMax per wave into the sample's word
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+      const unsigned other = (unsigned)__shfl_xor((int)amax, o, 64);
+      amax = other > amax ? other : amax;
+    }
+    if (lane == 0) atomicMax(&p.absmax_out[b], amax);
   }
 }
 

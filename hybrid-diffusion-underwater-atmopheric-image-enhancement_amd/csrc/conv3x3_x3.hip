@@ -30,6 +30,25 @@
 // channels and tap instead of 6, and measures a SMALLER error than the bf16 triples (tools/h2_sim_conv.py).  A caller whose
 // gn_scale / gn_shift are not GroupNorm statistics of x can break the bound: the fp16 conversion then yields inf and the
 // output NaN -- loud, never silently wrong.
+//
+// Range sources of the PAIR form: (1) the GroupNorm bound above (act_scale, evaluated at pack time); (2) absmax_in, one word per
+// sample with the bits of max |x[b]|, for convolutions WITHOUT a prologue: the workgroup forms 2^s from word blockIdx.z so that
+// absmax 2^s lies in [2^14, 2^15).  The word comes out of the epilogue of the kernel that produced x (absmax_out below: no pass
+// over memory -- a separate maximum pass costs a fifth of what the pairs save, profiles/r04_rejected_candidates.txt), so
+// UpSample's four transposed-conv phases (their input: a ResBlock's residual epilogue), its 3x3 (input: the four phases'
+// epilogues, all into the same words) and DownSample's 5x5 / stride 2 (input: the attention out-projection) run on pairs too.
+// A word below the true maximum overflows the fp16 conversion: NaN, loud again.  Per SAMPLE, never per launch: a sample's result
+// must not depend on what else is in the batch.
+// absmax_out (every instantiation): the epilogue takes the maximum of the bit patterns of |v| over what the wave stores,
+// reduces it in the wave and combines it into the sample's word by ONE unsigned atomicMax per wave -- order-independent, so
+// bitwise reproducible; NaN and inf compare above every finite value and end up in the word.
+//
+// Strided input (in_s = 2: the four parity planes of a 5x5 / stride-2 / pad-2 conv, out(y, x) = sum w(ky, kx) in(2y + ky - 2,
+// 2x + kx - 2)): the taps with ky % 2 == oy, kx % 2 == ox read plane (oy, ox) at (y + dy, x + dx), dy, dx in {-1, 0, 1} -- a
+// stride-1 conv of 9 / 6 / 6 / 4 taps over that plane.  Only the staging address changes: pixel (iy, ix) of the grid the kernel
+// walks is input element (iy in_s + in_oy, ix in_s + in_ox), bounds taken there.  The dispatcher (conv_igemm.hip) issues the four
+// launches inside one call; they accumulate through the residual epilogue (residual_first: the last one adds the bias behind
+// the partial sums, so the result is rounded once at its own size).
 #include <stdlib.h>
 
 #include <type_traits>
@@ -57,7 +76,7 @@ __device__ constexpr int TERM_X[6] = {0, 1, 2, 0, 1, 0};
 
 // NT: taps of the launch (9 = the 3x3 conv, 6 / 4 = transposed-conv phases with fewer taps); OUTMAP: the output pixel of
 // (vy, vx) is (vy * out_sy + out_oy, vx * out_sx + out_ox) of an OH x OW plane (transposed-conv phases) instead of (vy, vx).
-// PAIR: fp16 pairs and three products instead of bf16 triples and six (header).
+// PAIR: fp16 pairs and three products instead of bf16 triples and six (header); every (NT, OUTMAP) the launcher can ask for.
 // DROP: train-mode dropout behind the GroupNorm + Swish prologue (nn.Dropout between Swish and the conv, ModelCondition.py:185):
 // the keep words of a slot's four channels (one word per channel) are requested while the slot before it is staged, one tap of
 // MFMAs ahead (a padding slot fetches the word of its channel plane's first element and never looks at it), and the staged value
@@ -88,7 +107,23 @@ __global__ __launch_bounds__(THREADS, OCC) void conv3x3_x3_kernel(const ConvX3K 
   const int vy0 = tile_y * 8, vx0 = tile_x * 32;
   const bool has_gn = p.gn_scale != nullptr;
   const size_t HW = (size_t)p.H * p.W;
-  const float xs = PAIR ? p.act_scale[0] : 1.0f;       // 2^s of the staged activations
+  const size_t IHW = (size_t)p.IH * p.IW;      // channel stride of the input (= HW but for a strided input)
+  // 2^s of the staged activations and 2^-s: the GroupNorm bound (act_scale), or formed here from the sample's range word
+  // (absmax_in, a producer's epilogue maximum): max |x| 2^s in [2^14, 2^15).  The exponent is clamped as in v_split_h2_kernel so
+  // that 2^s and 2^-s are normal numbers: a zero or denormal word gives 2^114, a non-finite one 2^-113 (inf / NaN stay what they
+  // are in fp16, and a word below the true maximum overflows the conversion: NaN out, never finite wrong values).
+  float xs = 1.0f, xinv = 1.0f;
+  if constexpr (PAIR) {
+    if (p.absmax_in != nullptr) {
+      int e = (int)((p.absmax_in[b] >> 23) & 0xffu) - 127;
+      e = e < -100 ? -100 : (e > 127 ? 127 : e);
+      xs = __builtin_bit_cast(float, (unsigned)(14 - e + 127) << 23);
+      xinv = __builtin_bit_cast(float, (unsigned)(e - 14 + 127) << 23);
+    } else {
+      xs = p.act_scale[0];
+      xinv = p.act_scale[1];
+    }
+  }
   const float one = p.one;
 
   // LDS layout of a piece: two half-planes [h][pixel][4 words]; word w of half h holds the bf16 pieces of input channels
@@ -96,7 +131,7 @@ __global__ __launch_bounds__(THREADS, OCC) void conv3x3_x3_kernel(const ConvX3K 
   // consecutive 16-byte blocks: conflict-free.  (Round 2's [pixel][8 words] put lanes 8 words apart: the operand reads were
   // 2-way and the 4-byte staging stores 8-way bank-conflicted -- SQ_LDS_BANK_CONFLICT was 60 % of the LDS-active cycles.)
   // staging slots: slot e = (channel quad jq = e / 340: channels 4 jq .. 4 jq + 3, patch pixel e % 340); 8-byte stores
-  int s_goff[NSLOT];      // iy * W + ix of the pixel, or -1 (zero padding / unused slot)
+  int s_goff[NSLOT];      // offset of the pixel inside its channel plane (iy * W + ix; strided input: header), or -1 (zero padding / unused slot)
   int s_lds[NSLOT];       // word offset inside a piece, or the dump word (unused slot)
   int s_quad[NSLOT];
 #pragma unroll
@@ -108,7 +143,8 @@ __global__ __launch_bounds__(THREADS, OCC) void conv3x3_x3_kernel(const ConvX3K 
     const bool used = jq < 4;
     s_quad[i] = used ? jq : 3;
     s_lds[i] = used ? (jq >> 1) * HALF_WORDS + pos * 4 + (jq & 1) * 2 : DUMP_WORD;
-    s_goff[i] = (used && iy >= 0 && iy < p.H && ix >= 0 && ix < p.W) ? iy * p.W + ix : -1;
+    const int gy = iy * p.in_s + p.in_oy, gx = ix * p.in_s + p.in_ox;
+    s_goff[i] = (used && iy >= 0 && gy < p.IH && ix >= 0 && gx < p.IW) ? gy * p.IW + gx : -1;
   }
   if (has_gn) {
     for (int i = tid; i < 2 * p.Cin; i += THREADS)
@@ -141,7 +177,7 @@ __global__ __launch_bounds__(THREADS, OCC) void conv3x3_x3_kernel(const ConvX3K 
   unsigned ksh = 0;         // their four bit positions, five bits each
   auto fetch_keep = [&](int i, int c0, unsigned tie) {
     if constexpr (DROP) {
-      const unsigned hw = (unsigned)HW;
+      const unsigned hw = (unsigned)IHW;
       unsigned e = (unsigned)(b * p.Cin + c0 + 4 * s_quad[i]) * hw + (unsigned)(s_goff[i] >= 0 ? s_goff[i] : 0);
       asm("" : "+v"(e) : "v"(tie));
       ksh = 0;
@@ -154,23 +190,23 @@ __global__ __launch_bounds__(THREADS, OCC) void conv3x3_x3_kernel(const ConvX3K 
     }
   };
   auto issue_loads_to = [&](f32x4 (&dst)[XAHEAD ? NSLOT : 1], int c0) {
-    const float* xbase = (c0 < p.C0) ? p.x0 + ((size_t)b * p.C0 + c0) * HW : p.x1 + ((size_t)b * p.C1 + (c0 - p.C0)) * HW;
+    const float* xbase = (c0 < p.C0) ? p.x0 + ((size_t)b * p.C0 + c0) * IHW : p.x1 + ((size_t)b * p.C1 + (c0 - p.C0)) * IHW;
 #pragma unroll
     for (int i = 0; i < (XAHEAD ? NSLOT : 0); ++i) {
       const bool ok = s_goff[i] >= 0;
-      const float* src = xbase + (size_t)(4 * s_quad[i]) * HW + (ok ? s_goff[i] : 0);
-      const float v0 = src[0], v1 = src[HW], v2 = src[2 * HW], v3 = src[3 * HW];
+      const float* src = xbase + (size_t)(4 * s_quad[i]) * IHW + (ok ? s_goff[i] : 0);
+      const float v0 = src[0], v1 = src[IHW], v2 = src[2 * IHW], v3 = src[3 * IHW];
       dst[i] = f32x4{ok ? v0 : 0.f, ok ? v1 : 0.f, ok ? v2 : 0.f, ok ? v3 : 0.f};
     }
   };
   auto issue_loads = [&](int c0) {
     // a 16-channel chunk never straddles the concat seam (C0 % 16 == 0 is checked on the host)
-    const float* xbase = (c0 < p.C0) ? p.x0 + ((size_t)b * p.C0 + c0) * HW : p.x1 + ((size_t)b * p.C1 + (c0 - p.C0)) * HW;
+    const float* xbase = (c0 < p.C0) ? p.x0 + ((size_t)b * p.C0 + c0) * IHW : p.x1 + ((size_t)b * p.C1 + (c0 - p.C0)) * IHW;
 #pragma unroll
     for (int i = 0; i < NSLOT; ++i) {
       const bool ok = s_goff[i] >= 0;
-      const float* src = xbase + (size_t)(4 * s_quad[i]) * HW + (ok ? s_goff[i] : 0);
-      const float v0 = src[0], v1 = src[HW], v2 = src[2 * HW], v3 = src[3 * HW];   // unconditional: the address is always valid
+      const float* src = xbase + (size_t)(4 * s_quad[i]) * IHW + (ok ? s_goff[i] : 0);
+      const float v0 = src[0], v1 = src[IHW], v2 = src[2 * IHW], v3 = src[3 * IHW];   // unconditional: the address is always valid
       xv[i] = f32x4{ok ? v0 : 0.f, ok ? v1 : 0.f, ok ? v2 : 0.f, ok ? v3 : 0.f};
     }
   };
@@ -324,7 +360,7 @@ __global__ __launch_bounds__(THREADS, OCC) void conv3x3_x3_kernel(const ConvX3K 
   // flight before the first add -- with per-element tests every output waited for its own three loads in turn (64 dependent
   // round trips per lane: a quarter of the kernel's time at 128 channels).
   if constexpr (PAIR) {                    // out of the scaled domain: 2^-(s + t), exact
-    const float os = p.act_scale[1] * p.w_scale[1];
+    const float os = xinv * p.w_scale[1];
 #pragma unroll
     for (int nt = 0; nt < 4; ++nt)
 #pragma unroll
@@ -333,6 +369,20 @@ __global__ __launch_bounds__(THREADS, OCC) void conv3x3_x3_kernel(const ConvX3K 
   const size_t OHW = OUTMAP ? (size_t)p.OH * p.OW : HW;
   const int osy = OUTMAP ? p.out_sy : 1, ooy = OUTMAP ? p.out_oy : 0, osx = OUTMAP ? p.out_sx : 1, oox = OUTMAP ? p.out_ox : 0;
   const int OW = OUTMAP ? p.OW : p.W;
+  // absmax_out: the maximum of |v| over what this wave stores, as bits (non-negative floats order like unsigned integers, NaN
+  // above inf above every finite value), reduced over the wave and combined into the sample's word by ONE atomicMax
+  // (Behind a workgroup-uniform test: a launch without the word -- most of a step's -- executes none of it.)
+  const bool track = p.absmax_out != nullptr;
+  unsigned amax = 0u;
+  auto post_absmax = [&]() {
+    if (!track) return;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+      const unsigned other = (unsigned)__shfl_xor((int)amax, o, 64);
+      amax = other > amax ? other : amax;
+    }
+    if (lane == 0) atomicMax(&p.absmax_out[b], amax);
+  };
   if (co0 + 64 <= p.Cout && vy0 + 8 <= p.H && vx0 + 32 <= p.W) {
     float add[16];
 #pragma unroll
@@ -353,13 +403,27 @@ __global__ __launch_bounds__(THREADS, OCC) void conv3x3_x3_kernel(const ConvX3K 
 #pragma unroll
         for (int r = 0; r < 16; ++r) res[r] = p.residual[row + (size_t)((r & 3) + 8 * (r >> 2)) * OHW];
       }
+      float vv[16];
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        float v = acc[nt][r] + add[r];
-        if (p.residual) v += res[r];
+        float v;
+        if (p.residual_first) v = (acc[nt][r] + res[r]) + add[r];       // (only with a residual: the parity-plane launches)
+        else {
+          v = acc[nt][r] + add[r];
+          if (p.residual) v += res[r];
+        }
         p.out[row + (size_t)((r & 3) + 8 * (r >> 2)) * OHW] = v;
+        vv[r] = v;
+      }
+      if (track) {
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          const unsigned vb = __builtin_bit_cast(unsigned, vv[r]) & 0x7fffffffu;
+          amax = vb > amax ? vb : amax;
+        }
       }
     }
+    post_absmax();
     return;
   }
 #pragma unroll
@@ -374,13 +438,22 @@ __global__ __launch_bounds__(THREADS, OCC) void conv3x3_x3_kernel(const ConvX3K 
         float a = 0.f;                               // the same order of additions as the full-tile form
         if (p.bias) a += p.bias[co];
         if (p.addvec) a += p.addvec[b * p.Cout + co];
-        float v = acc[nt][r] + a;
         const size_t o = ((size_t)b * p.Cout + co) * OHW + pix;
-        if (p.residual) v += p.residual[o];
+        float v;
+        if (p.residual_first) v = (acc[nt][r] + p.residual[o]) + a;
+        else {
+          v = acc[nt][r] + a;
+          if (p.residual) v += p.residual[o];
+        }
         p.out[o] = v;
+        if (track) {
+          const unsigned vb = __builtin_bit_cast(unsigned, v) & 0x7fffffffu;
+          amax = vb > amax ? vb : amax;
+        }
       }
     }
   }
+  post_absmax();
 }
 
 // fp32 weights -> [Cin/16][tap][piece][CoutPad][8 words]: word j of a row = bf16 pieces of input channels 2j, 2j+1.  Tap t
@@ -388,6 +461,7 @@ __global__ __launch_bounds__(THREADS, OCC) void conv3x3_x3_kernel(const ConvX3K 
 // nn.ConvTranspose2d's layout, and the layout of a forward weight seen from its input-gradient convolution).
 struct PackX3K {
   int mode, Cout, Cin, KH, KW, ntaps, CoutPad;
+  int CinPad;        // mode 2 (fp16 pairs only): w is an fp32 pack [KH * KW][CinPad][CoutPad] of hdiff_pack_conv_weight
   int ky[9], kx[9];
 };
 __global__ void pack_conv_weight_x3_kernel(const float* __restrict__ w, unsigned* __restrict__ wp3, const PackX3K q) {
@@ -429,9 +503,9 @@ __global__ void conv_weight_absmax_kernel(const float* __restrict__ w, size_t n,
   for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
   if ((threadIdx.x & 63) == 0) atomicMax(tail, __builtin_bit_cast(unsigned, m));      // non-negative floats order like unsigned integers
 }
-__global__ void pack_conv_weight_h2_kernel(const float* __restrict__ w, unsigned* __restrict__ wp2, const PackX3K q, float one) {
+__global__ void pack_conv_weight_h2_kernel(const float* __restrict__ w, unsigned* __restrict__ wp2, unsigned* __restrict__ tail,
+                                           const PackX3K q, float one) {
   const size_t n = (size_t)(q.Cin / 16) * q.ntaps * q.CoutPad * 8;
-  unsigned* tail = wp2 + 2 * n;
   // 2^t with max |w| 2^t in [2^14, 2^15); an all-zero / denormal / non-finite tensor gets a fixed scale (inf and NaN stay what they are)
   int e = (int)((tail[0] >> 23) & 0xffu) - 127;
   e = e < -60 ? -60 : (e > 60 ? 60 : e);
@@ -447,8 +521,16 @@ __global__ void pack_conv_weight_h2_kernel(const float* __restrict__ w, unsigned
     if (co < q.Cout) {
       const int ci = chunk * 16 + 2 * j;
       const size_t k = (size_t)q.ky[tap] * q.KW + q.kx[tap], kk = (size_t)q.KH * q.KW;
-      a = w[((size_t)co * q.Cin + ci) * kk + k];
-      c = w[((size_t)co * q.Cin + ci + 1) * kk + k];
+      if (q.mode == 2) {
+        a = w[(k * q.CinPad + ci) * q.CoutPad + co];
+        c = w[(k * q.CinPad + ci + 1) * q.CoutPad + co];
+      } else if (q.mode == 1) {
+        a = w[((size_t)ci * q.Cout + co) * kk + k];
+        c = w[((size_t)(ci + 1) * q.Cout + co) * kk + k];
+      } else {
+        a = w[((size_t)co * q.Cin + ci) * kk + k];
+        c = w[((size_t)co * q.Cin + ci + 1) * kk + k];
+      }
     }
     unsigned h0, h1;
     split2(a * sc, c * sc, one, h0, h1);
@@ -456,7 +538,7 @@ __global__ void pack_conv_weight_h2_kernel(const float* __restrict__ w, unsigned
     wp2[base] = h0;
     wp2[base + (size_t)q.CoutPad * 8] = h1;
   }
-  if (blockIdx.x == 0 && threadIdx.x == 0) {
+  if (blockIdx.x == 0 && threadIdx.x == 0) {          // (the groups of a plane-grouped pack all write the same values)
     reinterpret_cast<float*>(tail)[1] = __builtin_bit_cast(float, (unsigned)(e - 14 + 127) << 23);
     reinterpret_cast<float*>(tail)[2] = sc;
     tail[3] = 0u;
@@ -497,8 +579,13 @@ void launch_conv3x3_x3(const ConvX3K& k, int B, hipStream_t stream) {
     else hipLaunchKernelGGL((conv3x3_x3_kernel<9, false, false, 2, true>), grid, dim3(THREADS), dyn, stream, k);
     return;
   }
-  if (k.act_scale != nullptr) {            // fp16 pairs: the plain 3x3 conv behind GroupNorm + Swish (the dispatcher checked the shape)
-    hipLaunchKernelGGL((conv3x3_x3_kernel<9, false, true>), grid, dim3(THREADS), dyn, stream, k);
+  if (k.act_scale != nullptr || k.absmax_in != nullptr) {      // fp16 pairs: the input's range is known (the dispatcher checked the shape)
+    if (k.ntaps == 9 && !outmap) hipLaunchKernelGGL((conv3x3_x3_kernel<9, false, true>), grid, dim3(THREADS), dyn, stream, k);
+    else if (k.ntaps == 9) hipLaunchKernelGGL((conv3x3_x3_kernel<9, true, true>), grid, dim3(THREADS), dyn, stream, k);
+    else if (k.ntaps == 6 && !outmap) hipLaunchKernelGGL((conv3x3_x3_kernel<6, false, true>), grid, dim3(THREADS), dyn, stream, k);   // (parity planes
+    else if (k.ntaps == 4 && !outmap) hipLaunchKernelGGL((conv3x3_x3_kernel<4, false, true>), grid, dim3(THREADS), dyn, stream, k);   //  of the 5x5 / s2)
+    else if (k.ntaps == 6) hipLaunchKernelGGL((conv3x3_x3_kernel<6, true, true>), grid, dim3(THREADS), dyn, stream, k);
+    else hipLaunchKernelGGL((conv3x3_x3_kernel<4, true, true>), grid, dim3(THREADS), dyn, stream, k);
     return;
   }
   if (k.ntaps == 9 && !outmap) hipLaunchKernelGGL((conv3x3_x3_kernel<9, false, false>), grid, dim3(THREADS), dyn, stream, k);
@@ -543,27 +630,111 @@ extern "C" int hdiff_pack_conv_weight_h2_words(int Cout, int Cin, int CoutPad, i
   return HDIFF_OK;
 }
 
-extern "C" int hdiff_pack_conv_weight_h2(const float* w, void* wp2, int Cout, int Cin, int CoutPad, hdiff_stream_t stream) {
-  HDIFF_CHECK_ARG(w && wp2, "pack_conv_weight_h2: null pointer");
-  HDIFF_CHECK_ARG(Cout > 0 && Cin > 0 && Cin % 16 == 0 && CoutPad >= Cout && CoutPad % 64 == 0,
-                  "pack_conv_weight_h2: needs Cin %% 16 == 0 and CoutPad %% 64 == 0 (Cin %d, Cout %d, CoutPad %d)", Cin, Cout, CoutPad);
+// the maximum over the WHOLE weight tensor, then the split of the listed taps: one 2^t per pack (the phases of one transposed
+// conv share it)
+static int pack_h2(const char* who, const float* w, void* wp2, int mode, int Cout, int Cin, int KH, int KW, int ntaps, const int* ky,
+                   const int* kx, int CoutPad, hipStream_t stream) {
   PackX3K q{};
-  q.mode = 0; q.Cout = Cout; q.Cin = Cin; q.KH = 3; q.KW = 3; q.ntaps = 9; q.CoutPad = CoutPad;
-  for (int t = 0; t < 9; ++t) { q.ky[t] = t / 3; q.kx[t] = t % 3; }
-  const size_t n = (size_t)(Cin / 16) * 9 * CoutPad * 8, nw = (size_t)Cout * Cin * 9;
+  q.mode = mode; q.Cout = Cout; q.Cin = Cin; q.KH = KH; q.KW = KW; q.ntaps = ntaps; q.CoutPad = CoutPad;
+  for (int t = 0; t < ntaps; ++t) { q.ky[t] = ky[t]; q.kx[t] = kx[t]; }
+  const size_t n = (size_t)(Cin / 16) * ntaps * CoutPad * 8, nw = (size_t)Cout * Cin * KH * KW;
   unsigned* tail = (unsigned*)wp2 + 2 * n;
   const int blocks = (int)((n + 255) / 256 < 4096 ? (n + 255) / 256 : 4096);
   const int mblocks = (int)((nw + 255) / 256 < 1024 ? (nw + 255) / 256 : 1024);
   (void)hipGetLastError();  // drop any stale error left by another HIP user in this thread
-  if (hipMemsetAsync(tail, 0, 16, (hipStream_t)stream) != hipSuccess) {
-    hdiff::set_error("pack_conv_weight_h2: hipMemsetAsync failed");
+  if (hipMemsetAsync(tail, 0, 16, stream) != hipSuccess) {
+    hdiff::set_error("%s: hipMemsetAsync failed", who);
     return HDIFF_ERR_LAUNCH;
   }
-  hipLaunchKernelGGL(conv_weight_absmax_kernel, dim3(mblocks), dim3(256), 0, (hipStream_t)stream, w, nw, tail);
+  hipLaunchKernelGGL(conv_weight_absmax_kernel, dim3(mblocks), dim3(256), 0, stream, w, nw, tail);
   HDIFF_CHECK_LAUNCH("conv_weight_absmax_kernel");
-  hipLaunchKernelGGL(pack_conv_weight_h2_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, w, (unsigned*)wp2, q, 1.0f);
+  hipLaunchKernelGGL(pack_conv_weight_h2_kernel, dim3(blocks), dim3(256), 0, stream, w, (unsigned*)wp2, tail, q, 1.0f);
   HDIFF_CHECK_LAUNCH("pack_conv_weight_h2_kernel");
   return HDIFF_OK;
+}
+
+// ---- the 5x5 / stride-2 conv as four stride-1 convs over the input's parity planes (conv_igemm.hip issues them): plane (oy, ox)
+//      holds the taps with ky % 2 == oy, kx % 2 == ox, which read plane pixel (y + dy, x + dx) with dy = (ky - 2 - oy) / 2 in
+//      {-1, 0, 1} (oy = 0) or {-1, 0} (oy = 1).  Pack: the groups (0,0), (0,1), (1,0), (1,1) with 9 / 6 / 6 / 4 taps one after the
+//      other, each [Cin/16][taps][2][CoutPad][8], then ONE tail: one 2^t for all four.
+namespace hdiff {
+int s2_plane_taps(int oy, int ox, int* ky, int* kx) {
+  int n = 0;
+  for (int y = oy; y < 5; y += 2)
+    for (int x = ox; x < 5; x += 2) { ky[n] = y; kx[n] = x; ++n; }
+  return n;
+}
+}  // namespace hdiff
+
+extern "C" int hdiff_pack_conv_weight_h2_s2_words(int Cout, int Cin, int CoutPad, int64_t* words_out) {
+  HDIFF_CHECK_ARG(words_out, "pack_conv_weight_h2_s2_words: null pointer");
+  HDIFF_CHECK_ARG(Cout > 0 && Cin > 0 && Cin % 16 == 0 && CoutPad >= Cout && CoutPad % 64 == 0,
+                  "pack_conv_weight_h2_s2_words: needs Cin %% 16 == 0 and CoutPad %% 64 == 0 (Cin %d, Cout %d, CoutPad %d)", Cin, Cout,
+                  CoutPad);
+  *words_out = (int64_t)(Cin / 16) * 25 * 2 * CoutPad * 8 + 4;
+  return HDIFF_OK;
+}
+
+extern "C" int hdiff_pack_conv_weight_h2_s2(const float* wp, void* wp2, int Cout, int Cin, int CinPad, int CoutPad, hdiff_stream_t stream) {
+  HDIFF_CHECK_ARG(wp && wp2, "pack_conv_weight_h2_s2: null pointer");
+  HDIFF_CHECK_ARG(Cout > 0 && Cin > 0 && Cin % 16 == 0 && CinPad >= Cin && CinPad % 8 == 0 && CoutPad >= Cout && CoutPad % 64 == 0,
+                  "pack_conv_weight_h2_s2: needs Cin %% 16 == 0, CinPad %% 8 == 0 and CoutPad %% 64 == 0 (Cin %d, CinPad %d, Cout %d, CoutPad %d)",
+                  Cin, CinPad, Cout, CoutPad);
+  const size_t per_tap = (size_t)(Cin / 16) * 2 * CoutPad * 8, nw = (size_t)25 * CinPad * CoutPad;
+  unsigned* tail = (unsigned*)wp2 + 25 * per_tap;
+  const int mblocks = (int)((nw + 255) / 256 < 1024 ? (nw + 255) / 256 : 1024);
+  (void)hipGetLastError();  // drop any stale error left by another HIP user in this thread
+  if (hipMemsetAsync(tail, 0, 16, (hipStream_t)stream) != hipSuccess) {
+    hdiff::set_error("pack_conv_weight_h2_s2: hipMemsetAsync failed");
+    return HDIFF_ERR_LAUNCH;
+  }
+  hipLaunchKernelGGL(conv_weight_absmax_kernel, dim3(mblocks), dim3(256), 0, (hipStream_t)stream, wp, nw, tail);      // (the padding is zero)
+  HDIFF_CHECK_LAUNCH("conv_weight_absmax_kernel");
+  size_t taps_before = 0;
+  for (int g = 0; g < 4; ++g) {
+    PackX3K q{};
+    q.mode = 2; q.Cout = Cout; q.Cin = Cin; q.KH = 5; q.KW = 5; q.CoutPad = CoutPad; q.CinPad = CinPad;
+    q.ntaps = hdiff::s2_plane_taps(g >> 1, g & 1, q.ky, q.kx);
+    const size_t n = per_tap / 2 * q.ntaps;
+    const int blocks = (int)((n + 255) / 256 < 4096 ? (n + 255) / 256 : 4096);
+    hipLaunchKernelGGL(pack_conv_weight_h2_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, wp, (unsigned*)wp2 + taps_before * per_tap,
+                       tail, q, 1.0f);
+    HDIFF_CHECK_LAUNCH("pack_conv_weight_h2_kernel");
+    taps_before += q.ntaps;
+  }
+  return HDIFF_OK;
+}
+
+extern "C" int hdiff_pack_conv_weight_h2(const float* w, void* wp2, int Cout, int Cin, int CoutPad, hdiff_stream_t stream) {
+  HDIFF_CHECK_ARG(w && wp2, "pack_conv_weight_h2: null pointer");
+  HDIFF_CHECK_ARG(Cout > 0 && Cin > 0 && Cin % 16 == 0 && CoutPad >= Cout && CoutPad % 64 == 0,
+                  "pack_conv_weight_h2: needs Cin %% 16 == 0 and CoutPad %% 64 == 0 (Cin %d, Cout %d, CoutPad %d)", Cin, Cout, CoutPad);
+  int ky[9], kx[9];
+  for (int t = 0; t < 9; ++t) { ky[t] = t / 3; kx[t] = t % 3; }
+  return pack_h2("pack_conv_weight_h2", w, wp2, 0, Cout, Cin, 3, 3, 9, ky, kx, CoutPad, (hipStream_t)stream);
+}
+
+extern "C" int hdiff_pack_conv_weight_h2_taps_words(int Cout, int Cin, int CoutPad, int ntaps, int64_t* words_out) {
+  HDIFF_CHECK_ARG(words_out, "pack_conv_weight_h2_taps_words: null pointer");
+  HDIFF_CHECK_ARG(Cout > 0 && Cin > 0 && Cin % 16 == 0 && CoutPad >= Cout && CoutPad % 64 == 0,
+                  "pack_conv_weight_h2_taps_words: needs Cin %% 16 == 0 and CoutPad %% 64 == 0 (Cin %d, Cout %d, CoutPad %d)", Cin, Cout,
+                  CoutPad);
+  HDIFF_CHECK_ARG(ntaps >= 1 && ntaps <= 9, "pack_conv_weight_h2_taps_words: ntaps %d out of range", ntaps);
+  *words_out = (int64_t)(Cin / 16) * ntaps * 2 * CoutPad * 8 + 4;
+  return HDIFF_OK;
+}
+
+extern "C" int hdiff_pack_conv_weight_h2_taps(const float* w, void* wp2, int mode, int Cout, int Cin, int KH, int KW, int ntaps,
+                                              const int* tap_ky, const int* tap_kx, int CoutPad, hdiff_stream_t stream) {
+  HDIFF_CHECK_ARG(w && wp2 && tap_ky && tap_kx, "pack_conv_weight_h2_taps: null pointer");
+  HDIFF_CHECK_ARG(Cout > 0 && Cin > 0 && Cin % 16 == 0 && CoutPad >= Cout && CoutPad % 64 == 0 && (mode == 0 || mode == 1),
+                  "pack_conv_weight_h2_taps: needs Cin %% 16 == 0, CoutPad %% 64 == 0, mode 0 / 1 (Cin %d, Cout %d, CoutPad %d, mode %d)",
+                  Cin, Cout, CoutPad, mode);
+  HDIFF_CHECK_ARG(ntaps >= 1 && ntaps <= 9 && KH > 0 && KW > 0, "pack_conv_weight_h2_taps: ntaps %d out of range", ntaps);
+  for (int t = 0; t < ntaps; ++t)
+    HDIFF_CHECK_ARG(tap_ky[t] >= 0 && tap_ky[t] < KH && tap_kx[t] >= 0 && tap_kx[t] < KW,
+                    "pack_conv_weight_h2_taps: tap %d reads kernel element (%d, %d) of a %d x %d kernel", t, tap_ky[t], tap_kx[t], KH, KW);
+  return pack_h2("pack_conv_weight_h2_taps", w, wp2, mode, Cout, Cin, KH, KW, ntaps, tap_ky, tap_kx, CoutPad, (hipStream_t)stream);
 }
 
 extern "C" int hdiff_gn_act_scale(const float* gamma, const float* beta, int C, int64_t group_elems, float gain, float* out2,

@@ -649,7 +649,7 @@ int configure(const hdiff_conv_desc* d, ConvCfg& c) {
 
 }  // namespace
 
-namespace { bool is_direct_1x1(const hdiff_conv_desc* d); bool is_x3_conv(const hdiff_conv_desc* d); bool is_x3_1x1(const hdiff_conv_desc* d); }
+namespace { bool is_direct_1x1(const hdiff_conv_desc* d); bool is_x3_conv(const hdiff_conv_desc* d, const hdiff_conv_range* r = nullptr); bool is_x3_1x1(const hdiff_conv_desc* d); }
 
 extern "C" int hdiff_conv2d_fwd_workspace(const hdiff_conv_desc* d, int64_t* floats_out) {
   HDIFF_CHECK_ARG(floats_out, "conv2d_fwd_workspace: null pointer");
@@ -687,8 +687,30 @@ namespace {
 bool is_h2_conv_shape(const hdiff_conv_desc* d, bool same) {
   return same && d->ntaps == 9 && d->wp_h2 != nullptr && d->act_scale != nullptr;
 }
-bool is_x3_conv(const hdiff_conv_desc* d) {
-  if ((d->wp_x3 == nullptr && d->wp_h2 == nullptr) || !hdiff::split_operands_on()) return false;
+// The second source of the pair form's range (hdiff_conv2d_fwd_range): a per-sample word of max |x| from the epilogue of the
+// kernel that produced x.  No prologue may stand between the word and the staged value.  The pair pack: wp_h2 for the plain 3x3
+// conv, the range struct's wp_h2_taps for a tap list (the transposed-conv phases).
+const void* h2_word_pack(const hdiff_conv_desc* d, const hdiff_conv_range* r, bool same) {
+  if (r == nullptr || r->absmax_in == nullptr || d->gn_scale != nullptr) return nullptr;
+  return same ? d->wp_h2 : r->wp_h2_taps;
+}
+// The 5x5 / stride-2 / pad-2 conv (DownSample with its 3x3 folded in) whose input carries a range word: four stride-1 pair
+// convolutions over the input's parity planes, accumulated through the residual epilogue (conv3x3_x3.hip, the plane pack).
+bool is_s2_pair_conv(const hdiff_conv_desc* d, const hdiff_conv_range* r) {
+  if (r == nullptr || r->absmax_in == nullptr || r->wp_h2_s2 == nullptr || !hdiff::split_operands_on()) return false;
+  if (d->ntaps != 25 || d->in_stride != 2 || d->gn_scale != nullptr || d->residual != nullptr) return false;
+  if (d->out_sy != 1 || d->out_oy != 0 || d->out_sx != 1 || d->out_ox != 0 || d->VH != d->OH || d->VW != d->OW) return false;
+  if (d->VH != (d->H - 1) / 2 + 1 || d->VW != (d->W - 1) / 2 + 1) return false;
+  for (int t = 0; t < 25; ++t)
+    if (d->tap_dy[t] != t / 5 - 2 || d->tap_dx[t] != t % 5 - 2) return false;
+  const int Cin = d->C0 + d->C1;
+  if (Cin % 16 != 0 || (d->C1 != 0 && d->C0 % 16 != 0) || Cin > 4096) return false;
+  if ((long)d->H * d->W >= (1L << 25)) return false;       // 32-bit pixel offsets inside a channel plane
+  return (long)cdiv(d->VW, 32) * cdiv(d->VH, 8) * cdiv(d->Cout, 64) * d->B >= 192;
+}
+bool is_x3_conv(const hdiff_conv_desc* d, const hdiff_conv_range* r) {
+  const bool word_pack = r != nullptr && r->absmax_in != nullptr && (d->wp_h2 != nullptr || r->wp_h2_taps != nullptr);
+  if ((d->wp_x3 == nullptr && d->wp_h2 == nullptr && !word_pack) || !hdiff::split_operands_on()) return false;
   if ((d->ntaps != 9 && d->ntaps != 6 && d->ntaps != 4) || d->in_stride != 1) return false;
   if (d->VH != d->H || d->VW != d->W) return false;
   const bool same = d->out_sy == 1 && d->out_oy == 0 && d->out_sx == 1 && d->out_ox == 0 && d->OH == d->H && d->OW == d->W;
@@ -713,7 +735,7 @@ bool is_x3_conv(const hdiff_conv_desc* d) {
   if (Cin % 16 != 0 || (d->C1 != 0 && d->C0 % 16 != 0) || Cin > 4096) return false;
   const long blocks = (long)cdiv(d->W, 32) * cdiv(d->H, 8) * cdiv(d->Cout, 64) * d->B;
   if (blocks < 192) return false;
-  return d->wp_x3 != nullptr || is_h2_conv_shape(d, same);
+  return d->wp_x3 != nullptr || is_h2_conv_shape(d, same) || h2_word_pack(d, r, same) != nullptr;
 }
 
 // A plain 1x1 / stride-1 conv over a full-size output with no GroupNorm prologue and enough pixels to fill the chip goes to
@@ -734,14 +756,51 @@ bool is_x3_1x1(const hdiff_conv_desc* d) {
 }  // namespace
 
 // keep_bits != NULL: the dropout form (hdiff_conv2d_fwd_dropout validated the descriptor; such a launch is never a 1x1)
-static int conv2d_fwd(const hdiff_conv_desc* d, const unsigned* keep_bits, float inv_keep, hdiff_stream_t stream) {
+// r != NULL: the range form (hdiff_conv2d_fwd_range validated it).  Its words matter in the split-operand mode only.
+static int conv2d_fwd_launch(const hdiff_conv_desc* d, const hdiff_conv_range* r, const unsigned* keep_bits, float inv_keep,
+                             hdiff_stream_t stream, bool* filled_absmax) {
   ConvCfg c;
   const int rc = configure(d, c);
   if (rc != HDIFF_OK) return rc;
   ConvK& k = c.k;
   k.keep_bits = keep_bits;
   k.inv_keep = inv_keep;
-  if (is_x3_conv(d)) {
+  if (!hdiff::split_operands_on()) r = nullptr;
+  if (is_s2_pair_conv(d, r)) {
+    hdiff::ConvX3K q{};
+    q.x0 = d->x0; q.x1 = d->x1; q.C0 = d->C0; q.C1 = d->C1; q.Cin = d->C0 + d->C1; q.H = d->VH; q.W = d->VW;
+    q.CoutPad = d->CoutPad; q.Cout = d->Cout; q.out = d->out; q.tiles_x = cdiv(d->VW, 32);
+    q.OH = d->OH; q.OW = d->OW; q.out_sy = 1; q.out_sx = 1;
+    q.absmax_in = r->absmax_in; q.one = 1.0f;
+    q.in_s = 2; q.IH = d->H; q.IW = d->W;
+    const size_t per_tap = (size_t)(q.Cin / 16) * 2 * d->CoutPad * 8;
+    const unsigned* pack = (const unsigned*)r->wp_h2_s2;
+    q.w_scale = reinterpret_cast<const float*>(pack + 25 * per_tap);
+    (void)hipGetLastError();  // drop any stale error left by another HIP user in this thread
+    size_t taps_before = 0;
+    for (int g = 0; g < 4; ++g) {          // plane (oy, ox) = (g >> 1, g & 1): 9, 6, 6, 4 taps
+      int ky[9], kx[9];
+      q.in_oy = g >> 1; q.in_ox = g & 1;
+      q.ntaps = hdiff::s2_plane_taps(q.in_oy, q.in_ox, ky, kx);
+      for (int t = 0; t < q.ntaps; ++t) q.tap_off[t] = (((ky[t] - 2 - q.in_oy) / 2 + 1) * 34 + ((kx[t] - 2 - q.in_ox) / 2 + 1)) * 4;
+      q.wp3 = pack + taps_before * per_tap;
+      // The LAST launch carries bias and addvec, behind the partial sums: out = (acc + partial) + bias is rounded once at the
+      // size of the result, like the one-launch kernel's acc + bias.  With the bias in the first launch every later launch rounds
+      // at the size of the bias again (four roundings: an input far below the bias measured 1.50x the fp32 kernel's rms error,
+      // over the gate of tests/test_gpu_conv_range.py).
+      q.bias = g == 3 ? d->bias : nullptr;
+      q.addvec = g == 3 ? d->addvec : nullptr;
+      q.residual = g == 0 ? nullptr : d->out;
+      q.residual_first = g != 0;
+      q.absmax_out = g == 3 ? r->absmax_out : nullptr;      // the last launch stores the finished sums
+      hdiff::launch_conv3x3_x3(q, d->B, (hipStream_t)stream);
+      HDIFF_CHECK_LAUNCH("conv3x3_x3_kernel");
+      taps_before += q.ntaps;
+    }
+    if (r->absmax_out != nullptr) *filled_absmax = true;
+    return HDIFF_OK;
+  }
+  if (is_x3_conv(d, r)) {
     hdiff::ConvX3K q{};
     q.x0 = d->x0; q.x1 = d->x1; q.C0 = d->C0; q.C1 = d->C1; q.Cin = d->C0 + d->C1; q.H = d->H; q.W = d->W;
     q.wp3 = (const unsigned*)d->wp_x3; q.CoutPad = d->CoutPad; q.Cout = d->Cout;
@@ -752,12 +811,22 @@ static int conv2d_fwd(const hdiff_conv_desc* d, const unsigned* keep_bits, float
         q.act_scale = d->act_scale;
         q.w_scale = reinterpret_cast<const float*>(q.wp3 + (size_t)(q.Cin / 16) * 9 * 2 * d->CoutPad * 8);
         q.one = 1.0f;
+      } else if (const void* wp2 = h2_word_pack(d, r, same)) {       // fp16 pairs staged by the sample's range word
+        q.wp3 = (const unsigned*)wp2;
+        q.absmax_in = r->absmax_in;
+        q.w_scale = reinterpret_cast<const float*>(q.wp3 + (size_t)(q.Cin / 16) * d->ntaps * 2 * d->CoutPad * 8);
+        q.one = 1.0f;
       }
+    }
+    if (r != nullptr && r->absmax_out != nullptr) {
+      q.absmax_out = r->absmax_out;
+      *filled_absmax = true;
     }
     q.bias = d->bias; q.gn_scale = d->gn_scale; q.gn_shift = d->gn_shift; q.addvec = d->addvec; q.residual = d->residual;
     q.out = d->out; q.tiles_x = cdiv(d->W, 32); q.ntaps = d->ntaps;
     for (int t = 0; t < d->ntaps; ++t) q.tap_off[t] = ((d->tap_dy[t] + 1) * 34 + (d->tap_dx[t] + 1)) * 4;
     q.OH = d->OH; q.OW = d->OW; q.out_sy = d->out_sy; q.out_oy = d->out_oy; q.out_sx = d->out_sx; q.out_ox = d->out_ox;
+    q.in_s = 1; q.IH = d->H; q.IW = d->W;
     q.keep_bits = keep_bits; q.inv_keep = inv_keep;
     (void)hipGetLastError();  // drop any stale error left by another HIP user in this thread
     hdiff::launch_conv3x3_x3(q, d->B, (hipStream_t)stream);
@@ -766,7 +835,11 @@ static int conv2d_fwd(const hdiff_conv_desc* d, const unsigned* keep_bits, float
   }
   if (is_direct_1x1(d) && is_x3_1x1(d)) {          // bf16x3 mode: the same GEMM on bf16 triples (conv1x1_x3.hip)
     hdiff::Conv1x1X3K q{d->x0, d->x1, d->C0, d->C0 + d->C1, (long)d->H * d->W, (const unsigned*)d->wp_x3, d->CoutPad, d->Cout,
-                        d->bias, d->addvec, d->residual, d->out};
+                        d->bias, d->addvec, d->residual, d->out, nullptr};
+    if (r != nullptr && r->absmax_out != nullptr) {
+      q.absmax_out = r->absmax_out;
+      *filled_absmax = true;
+    }
     (void)hipGetLastError();  // drop any stale error left by another HIP user in this thread
     hdiff::launch_conv1x1_x3(q, d->B, (hipStream_t)stream);
     HDIFF_CHECK_LAUNCH("conv1x1_x3_kernel");
@@ -801,7 +874,71 @@ static int conv2d_fwd(const hdiff_conv_desc* d, const unsigned* keep_bits, float
   return launch<1, 4, 20, 7, 0>(k, d->B, c.lds, s);
 }
 
-extern "C" int hdiff_conv2d_fwd(const hdiff_conv_desc* d, hdiff_stream_t stream) { return conv2d_fwd(d, nullptr, 1.0f, stream); }
+namespace {
+// max |out[b]| over the virtual grid of one launch into the sample's word, for the kernels whose epilogue does not do it (the
+// fp32-input kernel behind its split-K reduce, conv1x1_direct): small launches only, the full-resolution convs of the
+// split-operand mode all run conv3x3_x3.hip / conv1x1_x3.hip.
+struct OutAbsmaxK {
+  const float* out;
+  unsigned* words;
+  int Cout, VH, VW, OH, OW, sy, oy, sx, ox;
+};
+__global__ __launch_bounds__(256) void conv_out_absmax_kernel(const OutAbsmaxK q) {
+  const int b = blockIdx.y;
+  const long plane = (long)q.VH * q.VW, n = plane * q.Cout;
+  const float* base = q.out + (size_t)b * q.Cout * q.OH * q.OW;
+  unsigned m = 0u;
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
+    const long co = i / plane, pix = i - co * plane;
+    const int vy = (int)(pix / q.VW), vx = (int)(pix - (long)vy * q.VW);
+    const float v = base[((size_t)co * q.OH + (size_t)(vy * q.sy + q.oy)) * q.OW + (size_t)(vx * q.sx + q.ox)];
+    const unsigned vb = __builtin_bit_cast(unsigned, v) & 0x7fffffffu;
+    m = vb > m ? vb : m;
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const unsigned other = (unsigned)__shfl_xor((int)m, o, 64);
+    m = other > m ? other : m;
+  }
+  if ((threadIdx.x & 63) == 0) atomicMax(&q.words[b], m);
+}
+}  // namespace
+
+static int conv2d_fwd(const hdiff_conv_desc* d, const hdiff_conv_range* r, const unsigned* keep_bits, float inv_keep,
+                      hdiff_stream_t stream) {
+  bool filled = false;
+  const int rc = conv2d_fwd_launch(d, r, keep_bits, inv_keep, stream, &filled);
+  if (rc != HDIFF_OK || r == nullptr || r->absmax_out == nullptr || filled || !hdiff::split_operands_on()) return rc;
+  const OutAbsmaxK q{d->out, r->absmax_out, d->Cout, d->VH, d->VW, d->OH, d->OW, d->out_sy, d->out_oy, d->out_sx, d->out_ox};
+  const long n = (long)d->Cout * d->VH * d->VW;
+  const int blocks = (int)((n + 1023) / 1024 < 256 ? (n + 1023) / 1024 : 256);
+  hipLaunchKernelGGL(conv_out_absmax_kernel, dim3(blocks, d->B), dim3(256), 0, (hipStream_t)stream, q);
+  HDIFF_CHECK_LAUNCH("conv_out_absmax_kernel");
+  return HDIFF_OK;
+}
+
+extern "C" int hdiff_conv2d_fwd(const hdiff_conv_desc* d, hdiff_stream_t stream) { return conv2d_fwd(d, nullptr, nullptr, 1.0f, stream); }
+
+// hdiff_conv2d_fwd with per-sample range words (include/hdiff.h).  The words are zeroed by a small kernel, not by
+// hipMemsetAsync: captured into a hipGraph, the memset node left non-zero words behind from the second replay on
+// (tests/test_gpu_conv_range.py, test_replay_starts_from_zeroed_words, caught it).
+extern "C" int hdiff_conv2d_fwd_range(const hdiff_conv_desc* d, const hdiff_conv_range* r, hdiff_stream_t stream) {
+  HDIFF_CHECK_ARG(d && r, "conv2d_fwd_range: null pointer");
+  HDIFF_CHECK_ARG(((uintptr_t)r->absmax_out & 3u) == 0 && ((uintptr_t)r->absmax_in & 3u) == 0,
+                  "conv2d_fwd_range: absmax_out / absmax_in are not aligned to 32-bit words");
+  HDIFF_CHECK_ARG(r->absmax_in == nullptr || (const void*)r->absmax_in != (const void*)r->absmax_out,
+                  "conv2d_fwd_range: absmax_in and absmax_out are the same words (a launch cannot read the range it is writing)");
+  HDIFF_CHECK_ARG(r->absmax_in == nullptr || d->gn_scale == nullptr,
+                  "conv2d_fwd_range: absmax_in describes x0 / x1 as stored, not the output of the GroupNorm + Swish prologue "
+                  "(use act_scale)");
+  HDIFF_CHECK_ARG(r->wp_h2_taps == nullptr || r->absmax_in != nullptr, "conv2d_fwd_range: wp_h2_taps without absmax_in (the pair form needs the range)");
+  HDIFF_CHECK_ARG(r->wp_h2_taps == nullptr || (d->ntaps >= 1 && d->ntaps <= 9),
+                  "conv2d_fwd_range: wp_h2_taps holds a tap list of at most 9 taps (ntaps %d)", d->ntaps);
+  HDIFF_CHECK_ARG(r->wp_h2_s2 == nullptr || r->absmax_in != nullptr, "conv2d_fwd_range: wp_h2_s2 without absmax_in (the pair form needs the range)");
+  HDIFF_CHECK_ARG(r->wp_h2_s2 == nullptr || (d->ntaps == 25 && d->in_stride == 2),
+                  "conv2d_fwd_range: wp_h2_s2 is the pack of a 25-tap stride-2 conv (ntaps %d, in_stride %d)", d->ntaps, d->in_stride);
+  return conv2d_fwd(d, r, nullptr, 1.0f, stream);
+}
 
 // conv(dropout(swish(GroupNorm(x)))) in one launch (nn.Dropout between Swish and block2's conv, ModelCondition.py:184-186)
 extern "C" int hdiff_conv2d_fwd_dropout(const hdiff_conv_desc* d, const uint32_t* keep_bits, float inv_keep, hdiff_stream_t stream) {
@@ -817,5 +954,19 @@ extern "C" int hdiff_conv2d_fwd_dropout(const hdiff_conv_desc* d, const uint32_t
   HDIFF_CHECK_ARG(d->C0 > 0 && d->C0 % 8 == 0, "conv2d_fwd_dropout: C0 = %d is not a multiple of 8", d->C0);
   HDIFF_CHECK_ARG(d->B > 0 && d->H > 0 && d->W > 0 && (long long)d->B * d->C0 * d->H * d->W < (1ll << 31),
                   "conv2d_fwd_dropout: inputs of 2^31 elements or more are not supported (32-bit bit indices)");
-  return conv2d_fwd(d, keep_bits, inv_keep, stream);
+  return conv2d_fwd(d, nullptr, keep_bits, inv_keep, stream);
+}
+
+namespace {
+__global__ void range_words_zero_kernel(unsigned* __restrict__ words, int n) {
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) words[i] = 0u;
+}
+}  // namespace
+
+extern "C" int hdiff_range_words_zero(uint32_t* words, int n, hdiff_stream_t stream) {
+  HDIFF_CHECK_ARG(words && n > 0, "range_words_zero: null pointer or n = %d", n);
+  (void)hipGetLastError();  // drop any stale error left by another HIP user in this thread
+  hipLaunchKernelGGL(range_words_zero_kernel, dim3(n < 4096 ? (n + 255) / 256 : 16), dim3(256), 0, (hipStream_t)stream, words, n);
+  HDIFF_CHECK_LAUNCH("range_words_zero_kernel");
+  return HDIFF_OK;
 }

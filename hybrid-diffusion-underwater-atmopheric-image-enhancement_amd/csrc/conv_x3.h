@@ -5,8 +5,9 @@
 
 namespace hdiff {
 
-// conv3x3_x3.hip: split-bf16 convolution over the 3x3 neighbourhood (plain 3x3 / stride-1 convs and the four output-parity
-// phases of the transposed 5x5 / stride-2 conv: every tap offset lies in [-1, 1]^2)
+// conv3x3_x3.hip: split-bf16 convolution over the 3x3 neighbourhood (plain 3x3 / stride-1 convs, the four output-parity
+// phases of the transposed 5x5 / stride-2 conv and the four input-parity planes of the 5x5 / stride-2 conv: every tap offset
+// lies in [-1, 1]^2)
 struct ConvX3K {
   const float* x0;
   const float* x1;
@@ -31,8 +32,21 @@ struct ConvX3K {
   // is kept ? swish(..) * inv_keep : 0, bit (e & 31) of keep_bits[e >> 5] for the element's flat NCHW index e < 2^31 in x0
   const unsigned* keep_bits;
   float inv_keep;
+  // per-sample output range (hdiff_conv2d_fwd_range): word b takes max(word, bits of max |out[b]| over what this launch writes)
+  // by one unsigned atomicMax per wave; NULL = not wanted
+  unsigned* absmax_out;
+  // second source of the fp16-pair form's staging scale: word b = bits of max |x[b]| (a producer's absmax_out); with it the
+  // workgroup forms 2^s itself (act_scale is then not read), wp3 is a pair pack of ntaps taps and w_scale its tail
+  const unsigned* absmax_in;
+  // strided input (the parity planes of a stride-2 conv): pixel (iy, ix) of the H x W grid the kernel walks is element
+  // (iy * in_s + in_oy, ix * in_s + in_ox) of an IH x IW plane, zero outside it; the plain case is in_s = 1, offsets 0, IH x IW = H x W
+  int in_s, in_oy, in_ox, IH, IW;
+  int residual_first;              // != 0: out = (acc + residual) + (bias + addvec) instead of (acc + (bias + addvec)) + residual
 };
 void launch_conv3x3_x3(const ConvX3K& k, int B, hipStream_t stream);
+// taps (ky, kx) of the 5x5 kernel that read input parity plane (oy, ox) of a stride-2 conv, in the order of the plane-grouped
+// pair pack (hdiff_pack_conv_weight_h2_s2); returns their number: 9, 6, 6 or 4
+int s2_plane_taps(int oy, int ox, int* ky, int* kx);
 
 // conv1x1_x3.hip: the 1x1 / stride-1 convolution on bf16 triples (no LDS; operands split in registers)
 struct Conv1x1X3K {
@@ -46,6 +60,7 @@ struct Conv1x1X3K {
   const float* addvec;
   const float* residual;
   float* out;
+  unsigned* absmax_out;            // as ConvX3K::absmax_out
 };
 void launch_conv1x1_x3(const Conv1x1X3K& k, int B, hipStream_t stream);
 

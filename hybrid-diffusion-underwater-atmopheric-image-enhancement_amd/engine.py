@@ -101,6 +101,8 @@ class PackedConv:
         self.act_scale: Optional[torch.Tensor] = None
         self._h2_src: Optional[torch.Tensor] = None
         self._h2_gn: Optional[Tuple[torch.Tensor, torch.Tensor, int, float]] = None
+        self.wp2t: Optional[torch.Tensor] = None     # fp16-pair copy of a tap list (transposed-conv phases), see enable_h2_taps
+        self.wp2s: Optional[torch.Tensor] = None     # fp16-pair copy of a 5x5 / stride-2 pack grouped by input parity plane, see enable_h2_s2
 
     def enable_h2(self, w: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, group_elems: int, gain: float = 1.0) -> None:
         """Also keep the weights as two fp16 pieces (conv3x3_x3.hip, PAIR) for a plain 3x3 conv whose input is the output of
@@ -108,6 +110,8 @@ class PackedConv:
         that output is bounded by sqrt(n - 1) max|gamma| + max|beta|, which fixes the power of two the activations are staged
         with (hdiff_gn_act_scale, evaluated at pack time like the weights)."""
         ident = (gamma.data_ptr(), beta.data_ptr(), int(group_elems), float(gain))
+        if self.wp2 is not None and self._h2_gn is None:
+            raise RuntimeError("PackedConv.enable_h2: this pack already serves a conv that takes its range from a word")
         if self.wp2 is not None:
             # one pack = one staging scale: a second conv behind another GroupNorm (or another gain) must not inherit it silently
             have = (self._h2_gn[0].data_ptr(), self._h2_gn[1].data_ptr(), self._h2_gn[2], self._h2_gn[3])
@@ -123,6 +127,40 @@ class PackedConv:
             self.act_scale = torch.empty(2, dtype=torch.float32, device=self.wp.device)
             self._h2_src = w
             self._h2_gn = (gamma, beta, int(group_elems), float(gain))
+
+    def enable_h2_words(self) -> None:
+        """The fp16-pair copy for a plain 3x3 conv WITHOUT a GroupNorm prologue, whose input range arrives at run time as one
+        word per sample from the epilogue of the kernel that produced the input (Plan.conv, ``absmax_in``): weights only, the
+        kernel forms the staging scale itself."""
+        if self.wp2 is not None:
+            if self._h2_gn is not None:
+                raise RuntimeError("PackedConv.enable_h2_words: this pack already stages activations behind a GroupNorm")
+            return
+        if self.wp3 is not None and self._x3_taps is None and not self._x3_transposed:
+            words = C.c_int64(0)
+            _capi.check(_capi.lib().hdiff_pack_conv_weight_h2_words(self.cout, self.cin, self.cout_pad, C.byref(words)),
+                        "pack_conv_weight_h2_words")
+            self.wp2 = torch.empty(words.value, dtype=torch.int32, device=self.wp.device)
+            self._h2_src = self._x3_src
+
+    def enable_h2_taps(self) -> None:
+        """The fp16-pair copy of a tap-list pack (enable_x3_taps with 4 / 6 / 9 taps: the transposed-conv phases), used when
+        the launch is given its input's range word."""
+        if self.wp2t is None and self.wp3 is not None and self._x3_taps is not None and self.ntaps in (4, 6, 9):
+            words = C.c_int64(0)
+            _capi.check(_capi.lib().hdiff_pack_conv_weight_h2_taps_words(self.cout, self.cin, self.cout_pad, self.ntaps,
+                                                                         C.byref(words)), "pack_conv_weight_h2_taps_words")
+            self.wp2t = torch.empty(words.value, dtype=torch.int32, device=self.wp.device)
+
+    def enable_h2_s2(self) -> None:
+        """The fp16-pair copy of a 25-tap 5x5 pack (DownSample's folded weights), made from ``wp`` itself once its sources are
+        packed: the stride-2 conv then runs as four parity-plane pair convolutions when it is given its input's range word."""
+        if self.wp2s is None and self.ntaps == 25 and self.cin % 16 == 0 and \
+                all(dy == t // 5 - 2 and dx == t % 5 - 2 for t, (dy, dx) in enumerate(zip(self.taps.dy, self.taps.dx))):
+            words = C.c_int64(0)
+            _capi.check(_capi.lib().hdiff_pack_conv_weight_h2_s2_words(self.cout, self.cin, self.cout_pad, C.byref(words)),
+                        "pack_conv_weight_h2_s2_words")
+            self.wp2s = torch.empty(words.value, dtype=torch.int32, device=self.wp.device)
 
     def enable_x3(self, w: torch.Tensor, transposed: bool = False) -> None:
         """Also keep the weights as three bf16 pieces (conv3x3_x3.hip) -- used when the contraction mode is bf16x3.
@@ -164,10 +202,20 @@ class PackedConv:
         elif self.wp3 is not None:
             _capi.check(lib.hdiff_pack_conv_weight_x3(self._x3_src.data_ptr(), self.wp3.data_ptr(), self.cout, self.cin,
                                                       self.cout_pad, int(self._x3_transposed), stream), "pack_conv_weight_x3")
+        if self.wp2s is not None:
+            _capi.check(lib.hdiff_pack_conv_weight_h2_s2(self.wp.data_ptr(), self.wp2s.data_ptr(), self.cout, self.cin, self.cin_pad,
+                                                         self.cout_pad, stream), "pack_conv_weight_h2_s2")
+        if self.wp2t is not None:
+            mode, kh, kw = self._x3_taps
+            a_ky, a_kx = (C.c_int * self.ntaps)(*self.taps.ky), (C.c_int * self.ntaps)(*self.taps.kx)
+            _capi.check(lib.hdiff_pack_conv_weight_h2_taps(self._x3_src.data_ptr(), self.wp2t.data_ptr(), mode, self.cout, self.cin,
+                                                           kh, kw, self.ntaps, a_ky, a_kx, self.cout_pad, stream),
+                        "pack_conv_weight_h2_taps")
         if self.wp2 is not None:
-            gamma, beta, group_elems, gain = self._h2_gn
             _capi.check(lib.hdiff_pack_conv_weight_h2(self._h2_src.data_ptr(), self.wp2.data_ptr(), self.cout, self.cin,
                                                       self.cout_pad, stream), "pack_conv_weight_h2")
+        if self.wp2 is not None and self._h2_gn is not None:
+            gamma, beta, group_elems, gain = self._h2_gn
             _capi.check(lib.hdiff_gn_act_scale(gamma.data_ptr(), beta.data_ptr(), int(gamma.numel()), C.c_int64(group_elems),
                                                C.c_float(gain), self.act_scale.data_ptr(), stream), "gn_act_scale")
 
@@ -193,6 +241,8 @@ class Plan:
         self._graph_stream: Optional[torch.cuda.Stream] = None
         self.flops = 0.0          # algorithmic FLOPs of the MFMA-bound launches (convolutions, attention) of one run
         self._vec_jobs: List[tuple] = []          # per-block embedding projections, emitted as ONE launch (flush_block_vecs)
+        self._words: Optional[torch.Tensor] = None     # per-sample range words of the plan's tensors (range_words)
+        self._words_used = 0
 
     # -- memory -------------------------------------------------------------------------------------------------------
     def buf(self, *shape: int, dtype=torch.float32) -> torch.Tensor:
@@ -209,6 +259,21 @@ class Plan:
         t = base.view(dtype)[:n].view(*shape) if dtype != torch.float32 else base[:n].view(*shape)
         t._hdiff_base = base  # type: ignore[attr-defined]
         return t
+
+    RANGE_WORDS = 4096
+
+    def range_words(self, B: int) -> torch.Tensor:
+        """B words for the per-sample range of one tensor (Plan.conv: a producer's ``absmax_out`` is its consumer's ``absmax_in``).
+        All of a plan's words live in one small buffer, zeroed by ONE op emitted where the first of them is asked for -- before
+        any producer -- so every run and every graph replay starts from zeros."""
+        if self._words is None:
+            self._words = torch.zeros(self.RANGE_WORDS, dtype=torch.int32, device=self.device)
+            self.call("hdiff_range_words_zero", self._words.data_ptr(), self.RANGE_WORDS)
+        if self._words_used + B > self.RANGE_WORDS:
+            raise RuntimeError(f"hdiff: a plan holds at most {self.RANGE_WORDS} range words")
+        w = self._words[self._words_used:self._words_used + B]
+        self._words_used += B
+        return w
 
     def free(self, t: torch.Tensor) -> None:
         base = getattr(t, "_hdiff_base", None)
@@ -276,12 +341,15 @@ class Plan:
              out_map: Tuple[int, int, int, int] = (1, 0, 1, 0), gn: Optional[Tuple[torch.Tensor, torch.Tensor]] = None,
              addvec: Optional[torch.Tensor] = None, residual: Optional[torch.Tensor] = None,
              act_range: Optional[Tuple[torch.Tensor, torch.Tensor, int, float]] = None,
-             dropout: Optional[Tuple[torch.Tensor, float]] = None) -> None:
+             dropout: Optional[Tuple[torch.Tensor, float]] = None,
+             absmax_out: Optional[torch.Tensor] = None, absmax_in: Optional[torch.Tensor] = None) -> None:
         """act_range = (gamma, beta, group_elems, gain): the input tensor itself is gain * swish(GroupNorm(gamma, beta)(.)) of
         groups of group_elems elements (an activation materialised by the caller, or the prologue's output behind a dropout
         scaled by gain) -- what the fp16-pair 3x3 kernel needs to know about its range; with ``gn`` from gn_scale_shift() the
         plan knows it already.  dropout = (keep bits, fp32 1 / keep): train-mode dropout between the prologue and the conv
-        (hdiff_conv2d_fwd_dropout; a plain 3x3 conv with ``gn``)."""
+        (hdiff_conv2d_fwd_dropout; a plain 3x3 conv with ``gn``).  absmax_out / absmax_in = range_words(B): the launch leaves
+        max |out[b]| in the one, and takes max |x[b]| from the other -- which puts a plain 3x3 conv or a transposed-conv phase
+        WITHOUT a prologue onto the fp16-pair kernel in the split-operand mode (hdiff_conv2d_fwd_range; ignored in the f32 mode)."""
         d = _capi.ConvDesc()
         C0 = int(x0.shape[1])
         C1 = int(x1.shape[1]) if x1 is not None else 0
@@ -305,6 +373,20 @@ class Plan:
             pk.enable_h2(pk._x3_src, *act_range)
         if act_range is not None:      # only calls that carry the range take the fp16-pair form (a pack reused without one runs the triples)
             d.wp_h2, d.act_scale = _ptr(pk.wp2), _ptr(pk.act_scale)
+        r = None
+        if absmax_out is not None or absmax_in is not None:
+            assert dropout is None and (absmax_in is None or gn is None)
+            r = _capi.ConvRange()
+            r.absmax_out, r.absmax_in = _ptr(absmax_out), _ptr(absmax_in)
+            if absmax_in is not None and in_stride == 1 and pk._x3_taps is not None:
+                pk.enable_h2_taps()
+                r.wp_h2_taps = _ptr(pk.wp2t)
+            elif absmax_in is not None and in_stride == 1 and out_map == (1, 0, 1, 0):
+                pk.enable_h2_words()
+                d.wp_h2 = _ptr(pk.wp2)
+            elif absmax_in is not None and in_stride == 2 and pk.ntaps == 25:
+                pk.enable_h2_s2()
+                r.wp_h2_s2 = _ptr(pk.wp2s)
         for i in range(pk.ntaps):
             d.tap_dy[i], d.tap_dx[i] = pk.taps.dy[i], pk.taps.dx[i]
         need = C.c_int64(0)
@@ -313,10 +395,12 @@ class Plan:
         if need.value > 0:               # small grid, long channel loop: split-K partial sums + ordered reduce
             ws = self.buf(need.value)
             d.splitk_ws, d.splitk_floats = ws.data_ptr(), need.value
-        self.keep((d, x0, x1, pk, bias, out, gn, addvec, residual, ws, dropout))
+        self.keep((d, x0, x1, pk, bias, out, gn, addvec, residual, ws, dropout, r, absmax_out, absmax_in))
         self.flops += 2.0 * pk.ntaps * pk.cin * pk.cout * VH * VW * B
         if dropout is not None:
             self.call("hdiff_conv2d_fwd_dropout", C.byref(d), dropout[0].data_ptr(), C.c_float(dropout[1]))
+        elif r is not None:
+            self.call("hdiff_conv2d_fwd_range", C.byref(d), C.byref(r))
         else:
             self.call("hdiff_conv2d_fwd", C.byref(d))
         if ws is not None:
@@ -442,8 +526,10 @@ def emit_embed_mlp(plan: Plan, P: Dict[str, torch.Tensor], prefix: str, idx: tor
     return out
 
 
-def emit_mha(plan: Plan, P: Dict[str, torch.Tensor], p: str, h: torch.Tensor, B: int, Cc: int, H: int, W: int) -> torch.Tensor:
-    """nn.MultiheadAttention(C, 8) as attn(h,h,h) on (L,B,C): no pre-norm, no residual (ModelCondition.py:204-208)."""
+def emit_mha(plan: Plan, P: Dict[str, torch.Tensor], p: str, h: torch.Tensor, B: int, Cc: int, H: int, W: int,
+             absmax_out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """nn.MultiheadAttention(C, 8) as attn(h,h,h) on (L,B,C): no pre-norm, no residual (ModelCondition.py:204-208).
+    absmax_out: range words for the result (filled by the out-projection)."""
     if Cc % NUM_HEADS != 0:
         raise AssertionError("embed_dim must be divisible by num_heads")
     w_in = P[f"{p}.attn.in_proj_weight"].view(3 * Cc, Cc, 1, 1)
@@ -461,7 +547,7 @@ def emit_mha(plan: Plan, P: Dict[str, torch.Tensor], p: str, h: torch.Tensor, B:
     if ws is not None:
         plan.free(ws)
     y = plan.buf(B, Cc, H, W)
-    plan.conv(o, None, pk_out, P[f"{p}.attn.out_proj.bias"], y, B=B, H=H, W=W, VH=H, VW=W)
+    plan.conv(o, None, pk_out, P[f"{p}.attn.out_proj.bias"], y, B=B, H=H, W=W, VH=H, VW=W, absmax_out=absmax_out)
     plan.free(o)
     return y
 
@@ -504,8 +590,10 @@ def emit_attn_block(plan: Plan, P: Dict[str, torch.Tensor], p: str, x: torch.Ten
 
 
 def emit_resblock(plan: Plan, P: Dict[str, torch.Tensor], p: str, xa: torch.Tensor, xb: Optional[torch.Tensor],
-                  temb: torch.Tensor, cemb: Optional[torch.Tensor], cout: int, B: int, H: int, W: int, attn: bool) -> torch.Tensor:
-    """ResBlock.forward (ModelCondition.py:196-211) on the virtual concat [xa | xb]."""
+                  temb: torch.Tensor, cemb: Optional[torch.Tensor], cout: int, B: int, H: int, W: int, attn: bool,
+                  absmax_out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """ResBlock.forward (ModelCondition.py:196-211) on the virtual concat [xa | xb].  absmax_out: range words for the result
+    (filled by the block's last launch)."""
     sc1 = plan.gn_scale_shift(xa, xb, P[f"{p}.block1.0.weight"], P[f"{p}.block1.0.bias"], B, H * W)
     vec = plan.block_vec(temb, cemb, P, p, B, cout)
     pk1 = _std_pack(plan, P[f"{p}.block1.2.weight"], 3, 1)
@@ -524,19 +612,23 @@ def emit_resblock(plan: Plan, P: Dict[str, torch.Tensor], p: str, xa: torch.Tens
         res, res_owned = xa, False
     pk2 = _std_pack(plan, P[f"{p}.block2.3.weight"], 3, 1)
     h2 = plan.buf(B, cout, H, W)
-    plan.conv(h1, None, pk2, P[f"{p}.block2.3.bias"], h2, B=B, H=H, W=W, VH=H, VW=W, gn=sc2, residual=res)
+    plan.conv(h1, None, pk2, P[f"{p}.block2.3.bias"], h2, B=B, H=H, W=W, VH=H, VW=W, gn=sc2, residual=res,
+              absmax_out=None if attn else absmax_out)
     plan.free(sc2[0]); plan.free(sc2[1]); plan.free(h1)
     if res_owned:
         plan.free(res)
     if attn:
-        y = emit_mha(plan, P, p, h2, B, cout, H, W)
+        y = emit_mha(plan, P, p, h2, B, cout, H, W, absmax_out=absmax_out)
         plan.free(h2)
         return y
     return h2
 
 
-def emit_downsample(plan: Plan, P: Dict[str, torch.Tensor], p: str, x: torch.Tensor, B: int, Cc: int, H: int, W: int) -> torch.Tensor:
-    """DownSample.forward (ModelCondition.py:74-76): c1(x) + c2(x) as one 5x5/s2 conv with folded weights and biases."""
+def emit_downsample(plan: Plan, P: Dict[str, torch.Tensor], p: str, x: torch.Tensor, B: int, Cc: int, H: int, W: int,
+                    x_absmax: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """DownSample.forward (ModelCondition.py:74-76): c1(x) + c2(x) as one 5x5/s2 conv with folded weights and biases.
+    x_absmax: the range words of x (from its producer's epilogue): in the split-operand mode the conv then runs as four
+    parity-plane convolutions on fp16 pairs inside its one call."""
     taps = conv_taps(5, 2)
     pk = _new_pack(plan, Cc, Cc, taps)
     pk.add_source(P[f"{p}.c2.weight"], 0, taps.ky, taps.kx, 0)
@@ -549,25 +641,30 @@ def emit_downsample(plan: Plan, P: Dict[str, torch.Tensor], p: str, x: torch.Ten
               bias.data_ptr(), Cc)
     plan.keep((P[f"{p}.c1.bias"], P[f"{p}.c2.bias"]))
     y = plan.buf(B, Cc, OH, OW)
-    plan.conv(x, None, pk, bias, y, B=B, H=H, W=W, VH=OH, VW=OW, in_stride=2)
+    plan.conv(x, None, pk, bias, y, B=B, H=H, W=W, VH=OH, VW=OW, in_stride=2, absmax_in=x_absmax)
     plan.free(bias)
     return y
 
 
-def emit_upsample(plan: Plan, P: Dict[str, torch.Tensor], p: str, x: torch.Tensor, B: int, Cc: int, H: int, W: int) -> torch.Tensor:
-    """UpSample.forward (ModelCondition.py:85-89): ConvTranspose2d(5,2,2,1) as 4 parity phases, then Conv3x3."""
+def emit_upsample(plan: Plan, P: Dict[str, torch.Tensor], p: str, x: torch.Tensor, B: int, Cc: int, H: int, W: int,
+                  x_absmax: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """UpSample.forward (ModelCondition.py:85-89): ConvTranspose2d(5,2,2,1) as 4 parity phases, then Conv3x3.
+    x_absmax: the range words of x (from its producer's epilogue): the phases then run on fp16 pairs in the split-operand mode.
+    The words of u are always made here (the four phases max into them), so the 3x3 always does."""
     wt = P[f"{p}.t.weight"]                      # [Cin][Cout][5][5]
     u = plan.buf(B, Cc, 2 * H, 2 * W)
+    u_absmax = plan.range_words(B)
     for py in (0, 1):
         for px in (0, 1):
             taps = tconv_phase_taps(py, px)
             pk = _new_pack(plan, Cc, Cc, taps)
             pk.add_source(wt, 1, taps.ky, taps.kx, 0)
             pk.enable_x3_taps(wt, 1)             # every phase's taps lie in the 3x3 neighbourhood: the split-bf16 kernel serves them
-            plan.conv(x, None, pk, P[f"{p}.t.bias"], u, B=B, H=H, W=W, VH=H, VW=W, out_map=(2, py, 2, px))
+            plan.conv(x, None, pk, P[f"{p}.t.bias"], u, B=B, H=H, W=W, VH=H, VW=W, out_map=(2, py, 2, px),
+                      absmax_out=u_absmax, absmax_in=x_absmax)
     pkc = _std_pack(plan, P[f"{p}.c.weight"], 3, 1)
     y = plan.buf(B, Cc, 2 * H, 2 * W)
-    plan.conv(u, None, pkc, P[f"{p}.c.bias"], y, B=B, H=2 * H, W=2 * W, VH=2 * H, VW=2 * W)
+    plan.conv(u, None, pkc, P[f"{p}.c.bias"], y, B=B, H=2 * H, W=2 * W, VH=2 * H, VW=2 * W, absmax_in=u_absmax)
     plan.free(u)
     return y
 
@@ -598,13 +695,17 @@ class UNetPlan:
         n_down = 0
         for i, mult in enumerate(shape.ch_mult):
             out = ch * mult
-            for _ in range(shape.num_res_blocks):
-                h = emit_resblock(plan, P, f"downblocks.{n_down}", h, None, temb, cemb, out, B, cH, cW, attn=True)
+            h_absmax = None
+            for j in range(shape.num_res_blocks):
+                if i != len(shape.ch_mult) - 1 and j == shape.num_res_blocks - 1:     # the DownSample's input: its range comes
+                    h_absmax = plan.range_words(B)                                     # out of this block's last epilogue
+                h = emit_resblock(plan, P, f"downblocks.{n_down}", h, None, temb, cemb, out, B, cH, cW, attn=True,
+                                  absmax_out=h_absmax)
                 n_down += 1
                 now = out
                 hs.append((h, now, cH, cW))
             if i != len(shape.ch_mult) - 1:
-                h = emit_downsample(plan, P, f"downblocks.{n_down}", h, B, now, cH, cW)
+                h = emit_downsample(plan, P, f"downblocks.{n_down}", h, B, now, cH, cW, x_absmax=h_absmax)
                 n_down += 1
                 cH, cW = (cH - 1) // 2 + 1, (cW - 1) // 2 + 1
                 hs.append((h, now, cH, cW))
@@ -614,15 +715,19 @@ class UNetPlan:
         n_up = 0
         for i, mult in reversed(list(enumerate(shape.ch_mult))):
             out = ch * mult
-            for _ in range(shape.num_res_blocks + 1):
+            h_absmax = None
+            for j in range(shape.num_res_blocks + 1):
                 skip, sc, sH, sW = hs.pop()
                 assert (sH, sW) == (cH, cW)
-                y = emit_resblock(plan, P, f"upblocks.{n_up}", h, skip, temb, cemb, out, B, cH, cW, attn=False)
+                if i != 0 and j == shape.num_res_blocks:       # the UpSample's input: its range comes out of this block's epilogue
+                    h_absmax = plan.range_words(B)
+                y = emit_resblock(plan, P, f"upblocks.{n_up}", h, skip, temb, cemb, out, B, cH, cW, attn=False,
+                                  absmax_out=h_absmax)
                 n_up += 1
                 plan.free(h); plan.free(skip)
                 h, now = y, out
             if i != 0:
-                y = emit_upsample(plan, P, f"upblocks.{n_up}", h, B, now, cH, cW)
+                y = emit_upsample(plan, P, f"upblocks.{n_up}", h, B, now, cH, cW, x_absmax=h_absmax)
                 n_up += 1
                 plan.free(h)
                 h, cH, cW = y, 2 * cH, 2 * cW

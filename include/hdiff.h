@@ -92,6 +92,20 @@ int hdiff_pack_conv_weight_x3_taps(const float* w, void* wp3, int mode, int Cout
  * split-operand 3x3 kernel (hdiff_conv_desc.wp_h2; replaces the weight operand of F.conv2d at ModelCondition.py:172, 186). */
 int hdiff_pack_conv_weight_h2_words(int Cout, int Cin, int CoutPad, int64_t* words_out);
 int hdiff_pack_conv_weight_h2(const float* w, void* wp2, int Cout, int Cin, int CoutPad, hdiff_stream_t stream);
+/* The fp16-pair pack for a tap LIST, the counterpart of hdiff_pack_conv_weight_x3_taps (same arguments, same tap rules):
+ * [Cin/16][ntaps][2 pieces][CoutPad][16] of w * 2^t followed by the 4-word tail {scratch, 2^-t, 2^t, 0}.  t comes from the
+ * maximum over the WHOLE tensor w, so the packs of the four phases of one transposed conv share it.  For
+ * hdiff_conv_range.wp_h2_taps; the descriptor lists the taps in the order of the list given here. */
+int hdiff_pack_conv_weight_h2_taps_words(int Cout, int Cin, int CoutPad, int ntaps, int64_t* words_out);
+int hdiff_pack_conv_weight_h2_taps(const float* w, void* wp2, int mode, int Cout, int Cin, int KH, int KW, int ntaps,
+                                   const int* tap_ky, const int* tap_kx, int CoutPad, hdiff_stream_t stream);
+/* The fp16-pair pack of a 5x5 / stride-2 / pad-2 conv, made from its fp32 pack wp[25][CinPad][CoutPad] (hdiff_pack_conv_weight
+ * with tap t = (t / 5, t % 5); DownSample's folded c2 + c1, exactly what the fp32 kernel multiplies by).  The conv runs as four
+ * stride-1 convs over the parity planes of its input (taps with ky % 2 == oy, kx % 2 == ox read plane (oy, ox): 9 / 6 / 6 / 4
+ * taps, all within the plane's 3x3 neighbourhood); the pack holds the four groups (0,0), (0,1), (1,0), (1,1) one after the
+ * other, each [Cin/16][taps][2 pieces][CoutPad][16], and ONE tail {scratch, 2^-t, 2^t, 0}.  For hdiff_conv_range.wp_h2_s2. */
+int hdiff_pack_conv_weight_h2_s2_words(int Cout, int Cin, int CoutPad, int64_t* words_out);
+int hdiff_pack_conv_weight_h2_s2(const float* wp, void* wp2, int Cout, int Cin, int CinPad, int CoutPad, hdiff_stream_t stream);
 /* (ABI 5) Range of a GroupNorm + Swish output from the GroupNorm weights alone: |swish(gamma * xhat + beta)| <=
  * sqrt(n - 1) * max |gamma| + max |beta| =: A for groups of n = group_elems elements (a normalised value cannot leave
  * [-sqrt(n - 1), sqrt(n - 1)]).  out2[0] = 2^s, out2[1] = 2^-s with gain * A * 2^s in [2^13, 2^14): the power of two by which
@@ -163,6 +177,37 @@ int hdiff_conv2d_fwd(const hdiff_conv_desc* d, hdiff_stream_t stream);
  * act_scale, when set, must have been computed with gain = 1 / keep.  Anything else is HDIFF_ERR_INVALID, nothing is launched.
  * Padding positions stage 0 and use no keep bit; no word outside the ceil(B*C0*H*W / 32) words is read. */
 int hdiff_conv2d_fwd_dropout(const hdiff_conv_desc* d, const uint32_t* keep_bits, float inv_keep, hdiff_stream_t stream);
+
+/* Per-sample range words: how a convolution WITHOUT the GroupNorm prologue gets onto the fp16-pair form of the split-operand
+ * kernel.  The kernel that produces a tensor leaves max |out[b]| of every sample b in a 32-bit word (its epilogue: no pass over
+ * memory), the kernel that consumes the tensor forms its staging scale 2^s from that word.
+ *   absmax_out  uint32_t[B] or NULL.  After the call word b holds max(word b before, bits of max |out[b, :, :, :]| over what this
+ *               call wrote for sample b) -- an unsigned maximum of fp32 bit patterns, so NaN and inf end up in the word and the
+ *               result does not depend on order.  The caller zeroes the words before the first producer of a tensor (the four
+ *               phases of a transposed conv all max into the same words).  Filled on every path of the split-operand mode:
+ *               in the epilogue of the split-operand kernels, by one small extra launch behind the others.
+ *   absmax_in   uint32_t[B] or NULL: word b = bits of (a bound of) max |x[b]| of the input as stored.  With it, a launch that
+ *               qualifies for the split-operand 3x3 kernel runs its fp16-pair form: weights from hdiff_conv_desc.wp_h2 (the
+ *               plain 3x3 conv) or from wp_h2_taps below (a tap list: the transposed-conv phases), activations staged times 2^s
+ *               with absmax 2^s in [2^14, 2^15).  A zero, denormal or non-finite word gives a fixed finite scale.  A word below
+ *               the true maximum overflows the fp16 conversion: that sample's output is NaN, never a finite wrong value.
+ *               Not allowed together with gn_scale / gn_shift (the word describes x, not the prologue's output).
+ *   wp_h2_taps  hdiff_pack_conv_weight_h2_taps of the descriptor's tap list, or NULL; needs absmax_in.
+ *   wp_h2_s2    hdiff_pack_conv_weight_h2_s2 of the descriptor's wp, or NULL; needs absmax_in, ntaps = 25 and in_stride = 2.
+ *               With it the 5x5 / stride-2 / pad-2 conv (taps in row-major order, no prologue, no residual, Cin % 16 == 0, a
+ *               launch large enough to fill the chip) runs as four parity-plane pair convolutions inside this one call: the
+ *               first carries bias / addvec, the others add to out.  Any other descriptor keeps the fp32 kernel.
+ * Sample b of the output depends on word b alone.  In every contraction mode but HDIFF_CONTRACT_BF16X3 the call IS
+ * hdiff_conv2d_fwd(d): the struct is ignored, the words are neither read nor written.  Same workspace query. */
+typedef struct hdiff_conv_range {
+  uint32_t* absmax_out;
+  const uint32_t* absmax_in;
+  const void* wp_h2_taps;
+  const void* wp_h2_s2;
+} hdiff_conv_range;
+int hdiff_conv2d_fwd_range(const hdiff_conv_desc* d, const hdiff_conv_range* r, hdiff_stream_t stream);
+/* Zeroes n range words (one tiny launch: captured into a graph, every replay starts from zeros). */
+int hdiff_range_words_zero(uint32_t* words, int n, hdiff_stream_t stream);
 
 /* Weight gradient of hdiff_conv2d_fwd (autograd of the conv weights, TrainCondition.py:60).  Same geometry fields as the
  * forward descriptor; dy is the gradient of the forward's `out`.  The kernel writes `nsplit` packed partial slabs
