@@ -108,6 +108,7 @@ _PROTOS = {
     "hdiff_conv2d_fwd_dropout": (C.c_int, [C.POINTER(ConvDesc), C.c_void_p, C.c_float, C.c_void_p]),
     "hdiff_conv2d_fwd_range": (C.c_int, [C.POINTER(ConvDesc), C.POINTER(ConvRange), C.c_void_p]),
     "hdiff_range_words_zero": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
+    "hdiff_conv2d_fwd_route": (C.c_int, [C.POINTER(ConvDesc), C.POINTER(ConvRange), C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "hdiff_pack_conv_weight_h2_taps_words": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int64)]),
     "hdiff_pack_conv_weight_h2_taps": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                                  C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int, C.c_void_p]),

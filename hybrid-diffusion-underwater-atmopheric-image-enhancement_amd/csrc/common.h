@@ -1,5 +1,5 @@
 // Host side of the library: error reporting, launch checks and the launchers / workspace queries that one source file offers to
-// another.  No device code: what can change a kernel's instructions is in device.h (and conv_x3.h for the split-operand convolutions).
+// another.  No device code: what can change a kernel's instructions is in device.h (and conv_x3.h for the split-operand convolutions and the direct 1x1).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

@@ -13,24 +13,10 @@
 #include <stdlib.h>
 
 #include "common.h"
+#include "conv_x3.h"
 #include "device.h"
 
 using namespace hdiff;
-
-namespace hdiff {
-struct Conv1x1K {
-  const float* x0;
-  const float* x1;
-  int C0, Cin;
-  long HW;
-  const float* wp;
-  int CoutPad, Cout;
-  const float* bias;
-  const float* addvec;
-  const float* residual;
-  float* out;
-};
-}  // namespace hdiff
 
 namespace {
 

@@ -649,71 +649,33 @@ int configure(const hdiff_conv_desc* d, ConvCfg& c) {
 
 }  // namespace
 
-namespace { bool is_direct_1x1(const hdiff_conv_desc* d); bool is_x3_conv(const hdiff_conv_desc* d, const hdiff_conv_range* r = nullptr); bool is_x3_1x1(const hdiff_conv_desc* d); }
-
-extern "C" int hdiff_conv2d_fwd_workspace(const hdiff_conv_desc* d, int64_t* floats_out) {
-  HDIFF_CHECK_ARG(floats_out, "conv2d_fwd_workspace: null pointer");
-  ConvCfg c;
-  const int rc = configure(d, c);
-  if (rc != HDIFF_OK) return rc;
-  *floats_out = (is_direct_1x1(d) || is_x3_conv(d)) ? 0 : c.splitk_floats;
-  return HDIFF_OK;
-}
-
-namespace hdiff {
-struct Conv1x1K {
-  const float* x0;
-  const float* x1;
-  int C0, Cin;
-  long HW;
-  const float* wp;
-  int CoutPad, Cout;
-  const float* bias;
-  const float* addvec;
-  const float* residual;
-  float* out;
-};
-void launch_conv1x1_direct(const Conv1x1K& k, int B, hipStream_t stream);   // conv1x1_direct.hip
-}  // namespace hdiff
-
+// ---- the forward conv's route: which kernel serves a descriptor, decided once (conv_route) -------------------------------------
 namespace {
-// Split-bf16 mode: a stride-1 conv whose taps all lie in the 3x3 neighbourhood -- the plain 3x3 / pad-1 conv (9 taps, output
-// grid = input grid) and the output-parity phases of ConvTranspose2d(5, stride 2) (9 / 6 / 6 / 4 taps, output pixel
-// (2y + py, 2x + px)) -- with 16-channel-aligned inputs and a launch large enough to fill the chip (small ones keep the
-// split-K path of the fp32 kernel).
-// The fp16-pair form of that kernel (conv3x3_x3.hip, PAIR): the plain 3x3 conv whose input range the caller knows -- behind the
-// GroupNorm + Swish prologue (or an activation tensor made from it), bounded by the GroupNorm weights (act_scale from
-// hdiff_gn_act_scale, weights from hdiff_pack_conv_weight_h2).
-bool is_h2_conv_shape(const hdiff_conv_desc* d, bool same) {
-  return same && d->ntaps == 9 && d->wp_h2 != nullptr && d->act_scale != nullptr;
-}
-// The second source of the pair form's range (hdiff_conv2d_fwd_range): a per-sample word of max |x| from the epilogue of the
-// kernel that produced x.  No prologue may stand between the word and the staged value.  The pair pack: wp_h2 for the plain 3x3
-// conv, the range struct's wp_h2_taps for a tap list (the transposed-conv phases).
-const void* h2_word_pack(const hdiff_conv_desc* d, const hdiff_conv_range* r, bool same) {
-  if (r == nullptr || r->absmax_in == nullptr || d->gn_scale != nullptr) return nullptr;
-  return same ? d->wp_h2 : r->wp_h2_taps;
-}
-// The 5x5 / stride-2 / pad-2 conv (DownSample with its 3x3 folded in) whose input carries a range word: four stride-1 pair
-// convolutions over the input's parity planes, accumulated through the residual epilogue (conv3x3_x3.hip, the plane pack).
-bool is_s2_pair_conv(const hdiff_conv_desc* d, const hdiff_conv_range* r) {
-  if (r == nullptr || r->absmax_in == nullptr || r->wp_h2_s2 == nullptr || !hdiff::split_operands_on()) return false;
+
+struct ConvRoute {
+  int route;                        // HDIFF_CONV_ROUTE_* (include/hdiff.h)
+  const hdiff_conv_range* range;    // the range struct as the launch sees it: NULL when the mode (or the dropout form) ignores it
+  const unsigned* pair_pack;        // the fp16-pair pack of the three PAIRS routes, NULL otherwise ...
+  int pair_taps;                    // ... and its tap count: the tail {bits of max |w|, 2^-t, 2^t, 0} follows the taps' words
+  bool absmax_tail;                 // conv_out_absmax_kernel follows: no epilogue of this route fills range->absmax_out
+};
+
+// The 5x5 / stride-2 / pad-2 conv (DownSample with its 3x3 folded in): 25 taps in row-major order over the whole output, no
+// prologue and no residual (the four plane launches accumulate through the residual epilogue themselves).
+bool s2_5x5_geometry(const hdiff_conv_desc* d, bool identity) {
   if (d->ntaps != 25 || d->in_stride != 2 || d->gn_scale != nullptr || d->residual != nullptr) return false;
-  if (d->out_sy != 1 || d->out_oy != 0 || d->out_sx != 1 || d->out_ox != 0 || d->VH != d->OH || d->VW != d->OW) return false;
+  if (!identity || d->VH != d->OH || d->VW != d->OW) return false;
   if (d->VH != (d->H - 1) / 2 + 1 || d->VW != (d->W - 1) / 2 + 1) return false;
   for (int t = 0; t < 25; ++t)
     if (d->tap_dy[t] != t / 5 - 2 || d->tap_dx[t] != t % 5 - 2) return false;
-  const int Cin = d->C0 + d->C1;
-  if (Cin % 16 != 0 || (d->C1 != 0 && d->C0 % 16 != 0) || Cin > 4096) return false;
-  if ((long)d->H * d->W >= (1L << 25)) return false;       // 32-bit pixel offsets inside a channel plane
-  return (long)cdiv(d->VW, 32) * cdiv(d->VH, 8) * cdiv(d->Cout, 64) * d->B >= 192;
+  return (long)d->H * d->W < (1L << 25);                   // 32-bit pixel offsets inside a channel plane
 }
-bool is_x3_conv(const hdiff_conv_desc* d, const hdiff_conv_range* r) {
-  const bool word_pack = r != nullptr && r->absmax_in != nullptr && (d->wp_h2 != nullptr || r->wp_h2_taps != nullptr);
-  if ((d->wp_x3 == nullptr && d->wp_h2 == nullptr && !word_pack) || !hdiff::split_operands_on()) return false;
+
+// A stride-1 conv whose taps all lie in the 3x3 neighbourhood -- the plain 3x3 / pad-1 conv (9 taps, output grid = input grid:
+// `same`) and the output-parity phases of ConvTranspose2d(5, stride 2) (9 / 6 / 6 / 4 taps, output pixel (2y + py, 2x + px)).
+bool x3_geometry(const hdiff_conv_desc* d, bool same) {
   if ((d->ntaps != 9 && d->ntaps != 6 && d->ntaps != 4) || d->in_stride != 1) return false;
   if (d->VH != d->H || d->VW != d->W) return false;
-  const bool same = d->out_sy == 1 && d->out_oy == 0 && d->out_sx == 1 && d->out_ox == 0 && d->OH == d->H && d->OW == d->W;
   const bool phase = d->out_sy == 2 && d->out_sx == 2 && (d->out_oy == 0 || d->out_oy == 1) && (d->out_ox == 0 || d->out_ox == 1) &&
                      d->OH == 2 * d->H && d->OW == 2 * d->W && d->residual == nullptr;
   if (!same && !phase) return false;
@@ -731,128 +693,158 @@ bool is_x3_conv(const hdiff_conv_desc* d, const hdiff_conv_range* r) {
   if (same)
     for (int t = 0; t < 9; ++t)
       if (d->ntaps != 9 || d->tap_dy[t] != t / 3 - 1 || d->tap_dx[t] != t % 3 - 1) return false;
-  const int Cin = d->C0 + d->C1;
-  if (Cin % 16 != 0 || (d->C1 != 0 && d->C0 % 16 != 0) || Cin > 4096) return false;
-  const long blocks = (long)cdiv(d->W, 32) * cdiv(d->H, 8) * cdiv(d->Cout, 64) * d->B;
-  if (blocks < 192) return false;
-  return d->wp_x3 != nullptr || is_h2_conv_shape(d, same) || h2_word_pack(d, r, same) != nullptr;
+  return true;
 }
 
 // A plain 1x1 / stride-1 conv over a full-size output with no GroupNorm prologue and enough pixels to fill the chip goes to
 // the LDS-free GEMM kernel (small grids keep the split-K path of the implicit-GEMM kernel).
-bool is_direct_1x1(const hdiff_conv_desc* d) {
-  return d->ntaps == 1 && d->tap_dy[0] == 0 && d->tap_dx[0] == 0 && d->in_stride == 1 && d->gn_scale == nullptr &&
-         d->out_sy == 1 && d->out_oy == 0 && d->out_sx == 1 && d->out_ox == 0 && d->VH == d->H && d->VW == d->W &&
-         d->OH == d->H && d->OW == d->W && (long)d->B * d->H * d->W >= 32768 && ((long)d->H * d->W) % 128 == 0 &&
+bool direct_1x1_geometry(const hdiff_conv_desc* d, bool same) {
+  return d->ntaps == 1 && d->tap_dy[0] == 0 && d->tap_dx[0] == 0 && d->in_stride == 1 && d->gn_scale == nullptr && same &&
+         d->VH == d->H && d->VW == d->W && (long)d->B * d->H * d->W >= 32768 && ((long)d->H * d->W) % 128 == 0 &&
          d->C0 % 2 == 0 && (long)(d->C0 + d->C1) * d->H * d->W < (1L << 30) && d->CinPad * d->CoutPad < (1 << 30);
 }
-// ... and in the split-bf16 mode, with a one-tap bf16-triple pack (hdiff_pack_conv_weight_x3_taps, ntaps = 1) and 16-channel-aligned
-// inputs, the same GEMM runs on the bf16 MFMA (conv1x1_x3.hip).
-bool is_x3_1x1(const hdiff_conv_desc* d) {
+
+// The one place that decides which kernel runs a (validated) descriptor; the launcher below switches over the answer, the
+// workspace query and hdiff_conv2d_fwd_route read it.  Touches no device.  Order: stride-2 pairs, the 3x3-neighbourhood kernel
+// (pairs by GroupNorm, pairs by word, triples), the 1x1 on triples, the direct 1x1, the fp32-input implicit GEMM.
+// dropout: the dropout form (hdiff_conv2d_fwd_dropout) carries no range struct.
+ConvRoute conv_route(const hdiff_conv_desc* d, const hdiff_conv_range* r, bool dropout) {
+  const bool split = hdiff::split_operands_on();
+  if (!split || dropout) r = nullptr;            // the words matter in the split-operand mode only
+  // the split-operand kernels fill range->absmax_out in their epilogue; behind the two others a small launch does
+  auto take = [&](int route, const void* pack = nullptr, int taps = 0) {
+    const bool tail = r != nullptr && r->absmax_out != nullptr && (route == HDIFF_CONV_ROUTE_IGEMM || route == HDIFF_CONV_ROUTE_DIRECT_1X1);
+    return ConvRoute{route, r, (const unsigned*)pack, taps, tail};
+  };
+  const bool identity = d->out_sy == 1 && d->out_oy == 0 && d->out_sx == 1 && d->out_ox == 0;
+  const bool same = identity && d->OH == d->H && d->OW == d->W;          // output grid = input grid
+  // a per-sample word of max |x| from the epilogue of the kernel that produced x: the second source of the pair form's range.
+  // No prologue may stand between the word and the staged value.
+  const bool word = r != nullptr && r->absmax_in != nullptr && d->gn_scale == nullptr;
+  // the split-operand kernels want 16-channel-aligned inputs (each tensor of a concat) ...
   const int Cin = d->C0 + d->C1;
-  return d->wp_x3 != nullptr && hdiff::split_operands_on() && Cin % 16 == 0 &&
-         (d->C1 == 0 || d->C0 % 16 == 0) && ((long)d->H * d->W) % 256 == 0 && d->CoutPad % 64 == 0;
+  const bool ch16 = Cin % 16 == 0 && (d->C1 == 0 || d->C0 % 16 == 0);
+  // ... and conv3x3_x3.hip (32x8 pixels x 64 output channels per workgroup) a launch large enough to fill the chip: small ones keep
+  // the split-K path of the fp32 kernel
+  const bool x3_fills = split && ch16 && Cin <= 4096 && (long)cdiv(d->VW, 32) * cdiv(d->VH, 8) * cdiv(d->Cout, 64) * d->B >= 192;
+
+  // four stride-1 pair convolutions over the input's parity planes (conv3x3_x3.hip, the plane pack)
+  if (x3_fills && word && r->wp_h2_s2 != nullptr && s2_5x5_geometry(d, identity)) return take(HDIFF_CONV_ROUTE_S2_PAIRS_WORD, r->wp_h2_s2, 25);
+  if (x3_fills && x3_geometry(d, same)) {
+    // fp16 pairs (three products) instead of bf16 triples (six) for the plain 3x3 conv whose input range the caller knows:
+    // behind the GroupNorm + Swish prologue (or an activation tensor made from it), bounded by the GroupNorm weights (act_scale
+    // from hdiff_gn_act_scale, weights from hdiff_pack_conv_weight_h2) ...
+    if (same && d->wp_h2 != nullptr && d->act_scale != nullptr) return take(HDIFF_CONV_ROUTE_X3_PAIRS_GN, d->wp_h2, 9);
+    // ... or staged by the sample's range word: wp_h2 for the plain 3x3 conv, the range struct's wp_h2_taps for a tap list
+    const void* by_word = !word ? nullptr : same ? d->wp_h2 : r->wp_h2_taps;
+    if (by_word != nullptr) return take(HDIFF_CONV_ROUTE_X3_PAIRS_WORD, by_word, d->ntaps);
+    if (d->wp_x3 != nullptr) return take(HDIFF_CONV_ROUTE_X3_TRIPLES);
+  }
+  if (direct_1x1_geometry(d, same)) {
+    // with a one-tap bf16-triple pack (hdiff_pack_conv_weight_x3_taps, ntaps = 1) and 16-channel-aligned inputs the same GEMM
+    // runs on the bf16 MFMA (conv1x1_x3.hip)
+    if (d->wp_x3 != nullptr && split && ch16 && ((long)d->H * d->W) % 256 == 0 && d->CoutPad % 64 == 0) return take(HDIFF_CONV_ROUTE_X3_1X1);
+    return take(HDIFF_CONV_ROUTE_DIRECT_1X1);
+  }
+  return take(HDIFF_CONV_ROUTE_IGEMM);      // split-K or not, as configure() decided
+}
+
+}  // namespace
+
+// Asked without a range struct, whatever entry will run the conv: a conv that hdiff_conv2d_fwd_range then runs as S2_PAIRS_WORD
+// (or a phase that only a word puts onto the x3 kernel) is told the split-K floats of the fp32 kernel it does not run.  Known,
+// harmless (the workspace goes unused), and deliberately left as it is.
+extern "C" int hdiff_conv2d_fwd_workspace(const hdiff_conv_desc* d, int64_t* floats_out) {
+  HDIFF_CHECK_ARG(floats_out, "conv2d_fwd_workspace: null pointer");
+  ConvCfg c;
+  const int rc = configure(d, c);
+  if (rc != HDIFF_OK) return rc;
+  *floats_out = conv_route(d, nullptr, false).route == HDIFF_CONV_ROUTE_IGEMM ? c.splitk_floats : 0;
+  return HDIFF_OK;
+}
+
+namespace {
+// the ConvX3K fields that the plain launch and the four plane launches of the stride-2 form share
+hdiff::ConvX3K x3_args(const hdiff_conv_desc* d, const ConvRoute& rt) {
+  hdiff::ConvX3K q{};
+  q.x0 = d->x0; q.x1 = d->x1; q.C0 = d->C0; q.C1 = d->C1; q.Cin = d->C0 + d->C1; q.H = d->VH; q.W = d->VW;
+  q.wp3 = (const unsigned*)d->wp_x3; q.CoutPad = d->CoutPad; q.Cout = d->Cout; q.out = d->out; q.tiles_x = cdiv(d->VW, 32);
+  q.OH = d->OH; q.OW = d->OW; q.out_sy = d->out_sy; q.out_oy = d->out_oy; q.out_sx = d->out_sx; q.out_ox = d->out_ox;
+  q.in_s = d->in_stride; q.IH = d->H; q.IW = d->W;
+  if (rt.pair_pack != nullptr) {
+    q.wp3 = rt.pair_pack;
+    q.w_scale = reinterpret_cast<const float*>(rt.pair_pack + (size_t)(q.Cin / 16) * rt.pair_taps * 2 * d->CoutPad * 8);
+    q.one = 1.0f;
+    if (rt.route == HDIFF_CONV_ROUTE_X3_PAIRS_GN) q.act_scale = d->act_scale;
+    else q.absmax_in = rt.range->absmax_in;
+  }
+  return q;
 }
 }  // namespace
 
 // keep_bits != NULL: the dropout form (hdiff_conv2d_fwd_dropout validated the descriptor; such a launch is never a 1x1)
-// r != NULL: the range form (hdiff_conv2d_fwd_range validated it).  Its words matter in the split-operand mode only.
-static int conv2d_fwd_launch(const hdiff_conv_desc* d, const hdiff_conv_range* r, const unsigned* keep_bits, float inv_keep,
-                             hdiff_stream_t stream, bool* filled_absmax) {
-  ConvCfg c;
-  const int rc = configure(d, c);
-  if (rc != HDIFF_OK) return rc;
+static int conv2d_fwd_launch(const hdiff_conv_desc* d, ConvCfg& c, const ConvRoute& rt, const unsigned* keep_bits, float inv_keep,
+                             hipStream_t s) {
+  unsigned* const absmax_out = rt.range != nullptr ? rt.range->absmax_out : nullptr;
+  (void)hipGetLastError();  // drop any stale error left by another HIP user in this thread
+  switch (rt.route) {
+    case HDIFF_CONV_ROUTE_S2_PAIRS_WORD: {
+      hdiff::ConvX3K q = x3_args(d, rt);
+      const size_t per_tap = (size_t)(q.Cin / 16) * 2 * d->CoutPad * 8;
+      size_t taps_before = 0;
+      for (int g = 0; g < 4; ++g) {          // plane (oy, ox) = (g >> 1, g & 1): 9, 6, 6, 4 taps
+        int ky[9], kx[9];
+        q.in_oy = g >> 1; q.in_ox = g & 1;
+        q.ntaps = hdiff::s2_plane_taps(q.in_oy, q.in_ox, ky, kx);
+        for (int t = 0; t < q.ntaps; ++t) q.tap_off[t] = (((ky[t] - 2 - q.in_oy) / 2 + 1) * 34 + ((kx[t] - 2 - q.in_ox) / 2 + 1)) * 4;
+        q.wp3 = rt.pair_pack + taps_before * per_tap;
+        // The LAST launch carries bias and addvec, behind the partial sums: out = (acc + partial) + bias is rounded once at the
+        // size of the result, like the one-launch kernel's acc + bias.  With the bias in the first launch every later launch rounds
+        // at the size of the bias again (four roundings: an input far below the bias measured 1.50x the fp32 kernel's rms error,
+        // over the gate of tests/test_gpu_conv_range.py).
+        q.bias = g == 3 ? d->bias : nullptr;
+        q.addvec = g == 3 ? d->addvec : nullptr;
+        q.residual = g == 0 ? nullptr : d->out;
+        q.residual_first = g != 0;
+        q.absmax_out = g == 3 ? absmax_out : nullptr;      // the last launch stores the finished sums
+        hdiff::launch_conv3x3_x3(q, d->B, s);
+        HDIFF_CHECK_LAUNCH("conv3x3_x3_kernel");
+        taps_before += q.ntaps;
+      }
+      return HDIFF_OK;
+    }
+    case HDIFF_CONV_ROUTE_X3_TRIPLES:
+    case HDIFF_CONV_ROUTE_X3_PAIRS_GN:
+    case HDIFF_CONV_ROUTE_X3_PAIRS_WORD: {
+      hdiff::ConvX3K q = x3_args(d, rt);
+      q.absmax_out = absmax_out;
+      q.bias = d->bias; q.gn_scale = d->gn_scale; q.gn_shift = d->gn_shift; q.addvec = d->addvec; q.residual = d->residual;
+      q.ntaps = d->ntaps;
+      for (int t = 0; t < d->ntaps; ++t) q.tap_off[t] = ((d->tap_dy[t] + 1) * 34 + (d->tap_dx[t] + 1)) * 4;
+      q.keep_bits = keep_bits; q.inv_keep = inv_keep;
+      hdiff::launch_conv3x3_x3(q, d->B, s);
+      HDIFF_CHECK_LAUNCH("conv3x3_x3_kernel");
+      return HDIFF_OK;
+    }
+    case HDIFF_CONV_ROUTE_X3_1X1: {
+      const hdiff::Conv1x1X3K q{d->x0, d->x1, d->C0, d->C0 + d->C1, (long)d->H * d->W, (const unsigned*)d->wp_x3, d->CoutPad, d->Cout,
+                                d->bias, d->addvec, d->residual, d->out, absmax_out};
+      hdiff::launch_conv1x1_x3(q, d->B, s);
+      HDIFF_CHECK_LAUNCH("conv1x1_x3_kernel");
+      return HDIFF_OK;
+    }
+    case HDIFF_CONV_ROUTE_DIRECT_1X1: {
+      const hdiff::Conv1x1K q{d->x0, d->x1, d->C0, d->C0 + d->C1, (long)d->H * d->W, d->wp, d->CoutPad, d->Cout, d->bias, d->addvec,
+                              d->residual, d->out};
+      hdiff::launch_conv1x1_direct(q, d->B, s);
+      HDIFF_CHECK_LAUNCH("conv1x1_direct_kernel");
+      return HDIFF_OK;
+    }
+    default: break;      // HDIFF_CONV_ROUTE_IGEMM
+  }
   ConvK& k = c.k;
   k.keep_bits = keep_bits;
   k.inv_keep = inv_keep;
-  if (!hdiff::split_operands_on()) r = nullptr;
-  if (is_s2_pair_conv(d, r)) {
-    hdiff::ConvX3K q{};
-    q.x0 = d->x0; q.x1 = d->x1; q.C0 = d->C0; q.C1 = d->C1; q.Cin = d->C0 + d->C1; q.H = d->VH; q.W = d->VW;
-    q.CoutPad = d->CoutPad; q.Cout = d->Cout; q.out = d->out; q.tiles_x = cdiv(d->VW, 32);
-    q.OH = d->OH; q.OW = d->OW; q.out_sy = 1; q.out_sx = 1;
-    q.absmax_in = r->absmax_in; q.one = 1.0f;
-    q.in_s = 2; q.IH = d->H; q.IW = d->W;
-    const size_t per_tap = (size_t)(q.Cin / 16) * 2 * d->CoutPad * 8;
-    const unsigned* pack = (const unsigned*)r->wp_h2_s2;
-    q.w_scale = reinterpret_cast<const float*>(pack + 25 * per_tap);
-    (void)hipGetLastError();  // drop any stale error left by another HIP user in this thread
-    size_t taps_before = 0;
-    for (int g = 0; g < 4; ++g) {          // plane (oy, ox) = (g >> 1, g & 1): 9, 6, 6, 4 taps
-      int ky[9], kx[9];
-      q.in_oy = g >> 1; q.in_ox = g & 1;
-      q.ntaps = hdiff::s2_plane_taps(q.in_oy, q.in_ox, ky, kx);
-      for (int t = 0; t < q.ntaps; ++t) q.tap_off[t] = (((ky[t] - 2 - q.in_oy) / 2 + 1) * 34 + ((kx[t] - 2 - q.in_ox) / 2 + 1)) * 4;
-      q.wp3 = pack + taps_before * per_tap;
-      // The LAST launch carries bias and addvec, behind the partial sums: out = (acc + partial) + bias is rounded once at the
-      // size of the result, like the one-launch kernel's acc + bias.  With the bias in the first launch every later launch rounds
-      // at the size of the bias again (four roundings: an input far below the bias measured 1.50x the fp32 kernel's rms error,
-      // over the gate of tests/test_gpu_conv_range.py).
-      q.bias = g == 3 ? d->bias : nullptr;
-      q.addvec = g == 3 ? d->addvec : nullptr;
-      q.residual = g == 0 ? nullptr : d->out;
-      q.residual_first = g != 0;
-      q.absmax_out = g == 3 ? r->absmax_out : nullptr;      // the last launch stores the finished sums
-      hdiff::launch_conv3x3_x3(q, d->B, (hipStream_t)stream);
-      HDIFF_CHECK_LAUNCH("conv3x3_x3_kernel");
-      taps_before += q.ntaps;
-    }
-    if (r->absmax_out != nullptr) *filled_absmax = true;
-    return HDIFF_OK;
-  }
-  if (is_x3_conv(d, r)) {
-    hdiff::ConvX3K q{};
-    q.x0 = d->x0; q.x1 = d->x1; q.C0 = d->C0; q.C1 = d->C1; q.Cin = d->C0 + d->C1; q.H = d->H; q.W = d->W;
-    q.wp3 = (const unsigned*)d->wp_x3; q.CoutPad = d->CoutPad; q.Cout = d->Cout;
-    {
-      const bool same = d->out_sy == 1 && d->out_oy == 0 && d->out_sx == 1 && d->out_ox == 0 && d->OH == d->H && d->OW == d->W;
-      if (is_h2_conv_shape(d, same)) {         // fp16 pairs (three products) instead of bf16 triples (six)
-        q.wp3 = (const unsigned*)d->wp_h2;
-        q.act_scale = d->act_scale;
-        q.w_scale = reinterpret_cast<const float*>(q.wp3 + (size_t)(q.Cin / 16) * 9 * 2 * d->CoutPad * 8);
-        q.one = 1.0f;
-      } else if (const void* wp2 = h2_word_pack(d, r, same)) {       // fp16 pairs staged by the sample's range word
-        q.wp3 = (const unsigned*)wp2;
-        q.absmax_in = r->absmax_in;
-        q.w_scale = reinterpret_cast<const float*>(q.wp3 + (size_t)(q.Cin / 16) * d->ntaps * 2 * d->CoutPad * 8);
-        q.one = 1.0f;
-      }
-    }
-    if (r != nullptr && r->absmax_out != nullptr) {
-      q.absmax_out = r->absmax_out;
-      *filled_absmax = true;
-    }
-    q.bias = d->bias; q.gn_scale = d->gn_scale; q.gn_shift = d->gn_shift; q.addvec = d->addvec; q.residual = d->residual;
-    q.out = d->out; q.tiles_x = cdiv(d->W, 32); q.ntaps = d->ntaps;
-    for (int t = 0; t < d->ntaps; ++t) q.tap_off[t] = ((d->tap_dy[t] + 1) * 34 + (d->tap_dx[t] + 1)) * 4;
-    q.OH = d->OH; q.OW = d->OW; q.out_sy = d->out_sy; q.out_oy = d->out_oy; q.out_sx = d->out_sx; q.out_ox = d->out_ox;
-    q.in_s = 1; q.IH = d->H; q.IW = d->W;
-    q.keep_bits = keep_bits; q.inv_keep = inv_keep;
-    (void)hipGetLastError();  // drop any stale error left by another HIP user in this thread
-    hdiff::launch_conv3x3_x3(q, d->B, (hipStream_t)stream);
-    HDIFF_CHECK_LAUNCH("conv3x3_x3_kernel");
-    return HDIFF_OK;
-  }
-  if (is_direct_1x1(d) && is_x3_1x1(d)) {          // bf16x3 mode: the same GEMM on bf16 triples (conv1x1_x3.hip)
-    hdiff::Conv1x1X3K q{d->x0, d->x1, d->C0, d->C0 + d->C1, (long)d->H * d->W, (const unsigned*)d->wp_x3, d->CoutPad, d->Cout,
-                        d->bias, d->addvec, d->residual, d->out, nullptr};
-    if (r != nullptr && r->absmax_out != nullptr) {
-      q.absmax_out = r->absmax_out;
-      *filled_absmax = true;
-    }
-    (void)hipGetLastError();  // drop any stale error left by another HIP user in this thread
-    hdiff::launch_conv1x1_x3(q, d->B, (hipStream_t)stream);
-    HDIFF_CHECK_LAUNCH("conv1x1_x3_kernel");
-    return HDIFF_OK;
-  }
-  if (is_direct_1x1(d)) {
-    hdiff::Conv1x1K q{d->x0, d->x1, d->C0, d->C0 + d->C1, (long)d->H * d->W, d->wp, d->CoutPad, d->Cout, d->bias, d->addvec,
-                      d->residual, d->out};
-    (void)hipGetLastError();  // drop any stale error left by another HIP user in this thread
-    hdiff::launch_conv1x1_direct(q, d->B, (hipStream_t)stream);
-    HDIFF_CHECK_LAUNCH("conv1x1_direct_kernel");
-    return HDIFF_OK;
-  }
   if (k.ksplit > 1 && d->splitk_ws != nullptr && d->splitk_floats >= c.splitk_floats) {
     k.partial = d->splitk_ws;
   } else {            // no (or too small a) workspace: one slice, the plain epilogue
@@ -860,7 +852,6 @@ static int conv2d_fwd_launch(const hdiff_conv_desc* d, const hdiff_conv_range* r
     k.chunks_per_split = d->CinPad / c.CK;
     k.partial = nullptr;
   }
-  hipStream_t s = (hipStream_t)stream;
   // the specialised 3x3 path: standard taps in row-major order, stride 1, 8x32 tile (patch stride 35, plane 350)
   bool spec = c.WN == 2 && c.CK == 8 && d->ntaps == 9 && d->in_stride == 1 && k.tw_log2 == 5 && k.PWp == 35 && k.PLANE == 350;
   for (int t = 0; spec && t < 9; ++t) spec = k.tap_off[t] == (t / 3) * 35 + (t % 3);
@@ -904,25 +895,8 @@ __global__ __launch_bounds__(256) void conv_out_absmax_kernel(const OutAbsmaxK q
 }
 }  // namespace
 
-static int conv2d_fwd(const hdiff_conv_desc* d, const hdiff_conv_range* r, const unsigned* keep_bits, float inv_keep,
-                      hdiff_stream_t stream) {
-  bool filled = false;
-  const int rc = conv2d_fwd_launch(d, r, keep_bits, inv_keep, stream, &filled);
-  if (rc != HDIFF_OK || r == nullptr || r->absmax_out == nullptr || filled || !hdiff::split_operands_on()) return rc;
-  const OutAbsmaxK q{d->out, r->absmax_out, d->Cout, d->VH, d->VW, d->OH, d->OW, d->out_sy, d->out_oy, d->out_sx, d->out_ox};
-  const long n = (long)d->Cout * d->VH * d->VW;
-  const int blocks = (int)((n + 1023) / 1024 < 256 ? (n + 1023) / 1024 : 256);
-  hipLaunchKernelGGL(conv_out_absmax_kernel, dim3(blocks, d->B), dim3(256), 0, (hipStream_t)stream, q);
-  HDIFF_CHECK_LAUNCH("conv_out_absmax_kernel");
-  return HDIFF_OK;
-}
-
-extern "C" int hdiff_conv2d_fwd(const hdiff_conv_desc* d, hdiff_stream_t stream) { return conv2d_fwd(d, nullptr, nullptr, 1.0f, stream); }
-
-// hdiff_conv2d_fwd with per-sample range words (include/hdiff.h).  The words are zeroed by a small kernel, not by
-// hipMemsetAsync: captured into a hipGraph, the memset node left non-zero words behind from the second replay on
-// (tests/test_gpu_conv_range.py, test_replay_starts_from_zeroed_words, caught it).
-extern "C" int hdiff_conv2d_fwd_range(const hdiff_conv_desc* d, const hdiff_conv_range* r, hdiff_stream_t stream) {
+// the rules of hdiff_conv2d_fwd_range (include/hdiff.h) on top of configure()'s
+static int check_range(const hdiff_conv_desc* d, const hdiff_conv_range* r) {
   HDIFF_CHECK_ARG(d && r, "conv2d_fwd_range: null pointer");
   HDIFF_CHECK_ARG(((uintptr_t)r->absmax_out & 3u) == 0 && ((uintptr_t)r->absmax_in & 3u) == 0,
                   "conv2d_fwd_range: absmax_out / absmax_in are not aligned to 32-bit words");
@@ -937,14 +911,11 @@ extern "C" int hdiff_conv2d_fwd_range(const hdiff_conv_desc* d, const hdiff_conv
   HDIFF_CHECK_ARG(r->wp_h2_s2 == nullptr || r->absmax_in != nullptr, "conv2d_fwd_range: wp_h2_s2 without absmax_in (the pair form needs the range)");
   HDIFF_CHECK_ARG(r->wp_h2_s2 == nullptr || (d->ntaps == 25 && d->in_stride == 2),
                   "conv2d_fwd_range: wp_h2_s2 is the pack of a 25-tap stride-2 conv (ntaps %d, in_stride %d)", d->ntaps, d->in_stride);
-  return conv2d_fwd(d, r, nullptr, 1.0f, stream);
+  return HDIFF_OK;
 }
 
-// conv(dropout(swish(GroupNorm(x)))) in one launch (nn.Dropout between Swish and block2's conv, ModelCondition.py:184-186)
-extern "C" int hdiff_conv2d_fwd_dropout(const hdiff_conv_desc* d, const uint32_t* keep_bits, float inv_keep, hdiff_stream_t stream) {
-  HDIFF_CHECK_ARG(d && keep_bits, "conv2d_fwd_dropout: null pointer");
-  HDIFF_CHECK_ARG(inv_keep >= 1.0f && inv_keep <= 3.0e38f, "conv2d_fwd_dropout: inv_keep = %g is not a finite 1 / keep with keep in (0, 1]",
-                  (double)inv_keep);
+// the descriptor rules of hdiff_conv2d_fwd_dropout (include/hdiff.h) on top of configure()'s
+static int check_dropout(const hdiff_conv_desc* d) {
   HDIFF_CHECK_ARG(d->x1 == nullptr && d->C1 == 0, "conv2d_fwd_dropout: a concat input (x1) is not supported");
   HDIFF_CHECK_ARG(d->gn_scale != nullptr && d->gn_shift != nullptr, "conv2d_fwd_dropout: needs the GroupNorm + Swish prologue (gn_scale / gn_shift)");
   bool plain = d->ntaps == 9 && d->in_stride == 1 && d->VH == d->H && d->VW == d->W && d->OH == d->H && d->OW == d->W &&
@@ -954,7 +925,58 @@ extern "C" int hdiff_conv2d_fwd_dropout(const hdiff_conv_desc* d, const uint32_t
   HDIFF_CHECK_ARG(d->C0 > 0 && d->C0 % 8 == 0, "conv2d_fwd_dropout: C0 = %d is not a multiple of 8", d->C0);
   HDIFF_CHECK_ARG(d->B > 0 && d->H > 0 && d->W > 0 && (long long)d->B * d->C0 * d->H * d->W < (1ll << 31),
                   "conv2d_fwd_dropout: inputs of 2^31 elements or more are not supported (32-bit bit indices)");
-  return conv2d_fwd(d, nullptr, keep_bits, inv_keep, stream);
+  return HDIFF_OK;
+}
+
+// r != NULL: the range form, keep_bits != NULL: the dropout form (both validated by their entries)
+static int conv2d_fwd(const hdiff_conv_desc* d, const hdiff_conv_range* r, const unsigned* keep_bits, float inv_keep,
+                      hdiff_stream_t stream) {
+  ConvCfg c;
+  int rc = configure(d, c);
+  if (rc != HDIFF_OK) return rc;
+  const ConvRoute rt = conv_route(d, r, keep_bits != nullptr);
+  rc = conv2d_fwd_launch(d, c, rt, keep_bits, inv_keep, (hipStream_t)stream);
+  if (rc != HDIFF_OK || !rt.absmax_tail) return rc;
+  const OutAbsmaxK q{d->out, rt.range->absmax_out, d->Cout, d->VH, d->VW, d->OH, d->OW, d->out_sy, d->out_oy, d->out_sx, d->out_ox};
+  const long n = (long)d->Cout * d->VH * d->VW;
+  const int blocks = (int)((n + 1023) / 1024 < 256 ? (n + 1023) / 1024 : 256);
+  hipLaunchKernelGGL(conv_out_absmax_kernel, dim3(blocks, d->B), dim3(256), 0, (hipStream_t)stream, q);
+  HDIFF_CHECK_LAUNCH("conv_out_absmax_kernel");
+  return HDIFF_OK;
+}
+
+extern "C" int hdiff_conv2d_fwd(const hdiff_conv_desc* d, hdiff_stream_t stream) { return conv2d_fwd(d, nullptr, nullptr, 1.0f, stream); }
+
+// hdiff_conv2d_fwd with per-sample range words (include/hdiff.h).  The words are zeroed by a small kernel, not by
+// hipMemsetAsync: captured into a hipGraph, the memset node left non-zero words behind from the second replay on
+// (tests/test_gpu_conv_range.py, test_replay_starts_from_zeroed_words, caught it).
+extern "C" int hdiff_conv2d_fwd_range(const hdiff_conv_desc* d, const hdiff_conv_range* r, hdiff_stream_t stream) {
+  const int rc = check_range(d, r);
+  return rc != HDIFF_OK ? rc : conv2d_fwd(d, r, nullptr, 1.0f, stream);
+}
+
+// conv(dropout(swish(GroupNorm(x)))) in one launch (nn.Dropout between Swish and block2's conv, ModelCondition.py:184-186)
+extern "C" int hdiff_conv2d_fwd_dropout(const hdiff_conv_desc* d, const uint32_t* keep_bits, float inv_keep, hdiff_stream_t stream) {
+  HDIFF_CHECK_ARG(d && keep_bits, "conv2d_fwd_dropout: null pointer");
+  HDIFF_CHECK_ARG(inv_keep >= 1.0f && inv_keep <= 3.0e38f, "conv2d_fwd_dropout: inv_keep = %g is not a finite 1 / keep with keep in (0, 1]",
+                  (double)inv_keep);
+  const int rc = check_dropout(d);
+  return rc != HDIFF_OK ? rc : conv2d_fwd(d, nullptr, keep_bits, inv_keep, stream);
+}
+
+// The route of a descriptor as one of the three entries above would run it (include/hdiff.h): their validation, no launch, no device.
+extern "C" int hdiff_conv2d_fwd_route(const hdiff_conv_desc* d, const hdiff_conv_range* r, int dropout, int* route_out,
+                                      int* absmax_tail_out) {
+  HDIFF_CHECK_ARG(d && route_out && absmax_tail_out, "conv2d_fwd_route: null pointer");
+  HDIFF_CHECK_ARG(!(dropout && r), "conv2d_fwd_route: the dropout form takes no range struct");
+  ConvCfg c;
+  int rc = r != nullptr ? check_range(d, r) : dropout ? check_dropout(d) : HDIFF_OK;
+  if (rc == HDIFF_OK) rc = configure(d, c);
+  if (rc != HDIFF_OK) return rc;
+  const ConvRoute rt = conv_route(d, r, dropout != 0);
+  *route_out = rt.route;
+  *absmax_tail_out = rt.absmax_tail;
+  return HDIFF_OK;
 }
 
 namespace {

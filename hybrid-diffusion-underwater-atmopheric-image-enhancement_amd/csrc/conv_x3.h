@@ -1,5 +1,6 @@
-// Kernel arguments of the split-operand convolutions, shared by the kernel files (conv3x3_x3.hip, conv1x1_x3.hip) and their
-// dispatcher (conv_igemm.hip), and included by those three only: a new field changes these kernels and no others.
+// Kernel arguments of the convolutions that live outside their dispatcher's file (conv_igemm.hip): the split-operand kernels
+// (conv3x3_x3.hip, conv1x1_x3.hip) and the direct 1x1 (conv1x1_direct.hip).  Each struct is defined here ONCE and passed by value
+// to a kernel; the header is included by those four files only: a new field changes these kernels and no others.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -63,5 +64,20 @@ struct Conv1x1X3K {
   unsigned* absmax_out;            // as ConvX3K::absmax_out
 };
 void launch_conv1x1_x3(const Conv1x1X3K& k, int B, hipStream_t stream);
+
+// conv1x1_direct.hip: the 1x1 / stride-1 convolution on the fp32-input MFMA (no LDS)
+struct Conv1x1K {
+  const float* x0;
+  const float* x1;
+  int C0, Cin;
+  long HW;
+  const float* wp;                 // [CinPad][CoutPad] (hdiff_pack_conv_weight, one tap)
+  int CoutPad, Cout;
+  const float* bias;
+  const float* addvec;
+  const float* residual;
+  float* out;
+};
+void launch_conv1x1_direct(const Conv1x1K& k, int B, hipStream_t stream);
 
 }  // namespace hdiff

@@ -1,5 +1,5 @@
 // Device-side helpers shared by the gfx950 kernels: everything here can change a kernel's instructions, and nothing else in a
-// header can (common.h is host-side only; conv_x3.h holds the argument structs of the split-operand convolutions).  Every helper is
+// header can (common.h is host-side only; conv_x3.h holds the argument structs of the split-operand convolutions and the direct 1x1).  Every helper is
 // __device__ __forceinline__ and leaves no symbol behind.  The per-file tile constants (KT, THREADS, KROW ...) are NOT here: they
 // coincide in value, not in meaning.
 #pragma once

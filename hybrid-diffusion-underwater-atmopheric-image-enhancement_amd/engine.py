@@ -84,8 +84,18 @@ def tconv_phase_taps(py: int, px: int) -> TapSet:
     return t
 
 
+# Geometry class of a pack: which launches beyond the fp32 kernel its weights can serve.  Every class but OTHER has Cin % 16 == 0.
+PLAIN_3X3 = "plain 3x3"                  # hdiff_pack_conv_weight_x3; pairs behind a GroupNorm or by a range word (wp_h2)
+PLAIN_3X3_T = "plain 3x3 transposed"     # its input-gradient twin: triples only
+TAPS_3X3 = "3x3-neighbourhood tap list"  # 4 / 6 / 9 taps (transposed-conv phases): pairs by a range word (wp_h2_taps)
+ONE_TAP = "one tap"                      # the 1x1 GEMM on triples
+S2_5X5 = "row-major 5x5"                 # DownSample's folded weights: at stride 2, pairs by a range word (wp_h2_s2)
+OTHER = "other"
+
+
 class PackedConv:
-    """Device-side packed weights wp[tap][CinPad][CoutPad] for one convolution launch (conv_igemm.hip)."""
+    """Device-side packed weights wp[tap][CinPad][CoutPad] for one convolution launch (conv_igemm.hip), and the copies the
+    split-operand kernels read: ``wp3`` (bf16 triples) and ``wp2`` (fp16 pairs, in the layout of the pack's class)."""
 
     def __init__(self, device, cout: int, cin: int, taps: TapSet):
         self.cout, self.cin, self.taps = cout, cin, taps
@@ -93,74 +103,69 @@ class PackedConv:
         self.ntaps = len(taps.dy)
         self.wp = torch.empty(self.ntaps * self.cin_pad * self.cout_pad, dtype=torch.float32, device=device)
         self.sources: List[Tuple[torch.Tensor, int, int, int, List[int], List[int], int]] = []
-        self.wp3: Optional[torch.Tensor] = None      # split-bf16 copy (standard 3x3 convs with Cin % 16 == 0), see enable_x3
-        self._x3_src: Optional[torch.Tensor] = None
-        self._x3_transposed = False
-        self._x3_taps: Optional[Tuple[int, int, int]] = None
-        self.wp2: Optional[torch.Tensor] = None      # fp16-pair copy + the staged activations' power of two, see enable_h2
+        row_major_5x5 = self.ntaps == 25 and all(dy == t // 5 - 2 and dx == t % 5 - 2 for t, (dy, dx) in enumerate(zip(taps.dy, taps.dx)))
+        self.kind = S2_5X5 if row_major_5x5 and cin % 16 == 0 else OTHER      # enable_x3 / enable_x3_taps set the other classes
+        self.wp3: Optional[torch.Tensor] = None      # split-bf16 copy, see enable_x3 / enable_x3_taps
+        self._x3_src: Optional[torch.Tensor] = None  # the weight tensor wp3 and a plain or tap-list wp2 are packed from ...
+        self._x3_layout: Optional[Tuple[int, int, int]] = None      # ... and, for a tap list, its (mode, KH, KW)
+        # fp16-pair copy, allocated by the first launch that may use it (launch_ptrs) -- made from the x3 source (PLAIN_3X3: + the
+        # staged activations' power of two; TAPS_3X3) or, once its sources are packed, from ``wp`` itself (S2_5X5, grouped by
+        # input parity plane)
+        self.wp2: Optional[torch.Tensor] = None
         self.act_scale: Optional[torch.Tensor] = None
-        self._h2_src: Optional[torch.Tensor] = None
-        self._h2_gn: Optional[Tuple[torch.Tensor, torch.Tensor, int, float]] = None
-        self.wp2t: Optional[torch.Tensor] = None     # fp16-pair copy of a tap list (transposed-conv phases), see enable_h2_taps
-        self.wp2s: Optional[torch.Tensor] = None     # fp16-pair copy of a 5x5 / stride-2 pack grouped by input parity plane, see enable_h2_s2
+        self._gn: Optional[Tuple[torch.Tensor, torch.Tensor, int, float]] = None      # PLAIN_3X3 with wp2: None = it serves a range word
 
-    def enable_h2(self, w: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, group_elems: int, gain: float = 1.0) -> None:
-        """Also keep the weights as two fp16 pieces (conv3x3_x3.hip, PAIR) for a plain 3x3 conv whose input is the output of
-        GroupNorm(gamma, beta) + Swish over groups of ``group_elems`` elements, times ``gain`` (1 / keep behind a dropout):
-        that output is bounded by sqrt(n - 1) max|gamma| + max|beta|, which fixes the power of two the activations are staged
-        with (hdiff_gn_act_scale, evaluated at pack time like the weights)."""
-        ident = (gamma.data_ptr(), beta.data_ptr(), int(group_elems), float(gain))
-        if self.wp2 is not None and self._h2_gn is None:
-            raise RuntimeError("PackedConv.enable_h2: this pack already serves a conv that takes its range from a word")
-        if self.wp2 is not None:
-            # one pack = one staging scale: a second conv behind another GroupNorm (or another gain) must not inherit it silently
-            have = (self._h2_gn[0].data_ptr(), self._h2_gn[1].data_ptr(), self._h2_gn[2], self._h2_gn[3])
-            if have != ident:
-                raise RuntimeError("PackedConv.enable_h2: this pack already stages activations for another GroupNorm / gain; "
-                                   "use one PackedConv per (convolution, GroupNorm) pair")
-            return
-        if self.ntaps == 9 and self.cin % 16 == 0 and tuple(w.shape[2:]) == (3, 3):
-            words = C.c_int64(0)
-            _capi.check(_capi.lib().hdiff_pack_conv_weight_h2_words(self.cout, self.cin, self.cout_pad, C.byref(words)),
-                        "pack_conv_weight_h2_words")
-            self.wp2 = torch.empty(words.value, dtype=torch.int32, device=self.wp.device)
-            self.act_scale = torch.empty(2, dtype=torch.float32, device=self.wp.device)
-            self._h2_src = w
-            self._h2_gn = (gamma, beta, int(group_elems), float(gain))
+    def _pair_buffer(self, size_query: str, *args) -> torch.Tensor:
+        words = C.c_int64(0)
+        _capi.check(getattr(_capi.lib(), size_query)(self.cout, self.cin, self.cout_pad, *args, C.byref(words)),
+                    size_query[len("hdiff_"):])
+        return torch.empty(words.value, dtype=torch.int32, device=self.wp.device)
 
-    def enable_h2_words(self) -> None:
-        """The fp16-pair copy for a plain 3x3 conv WITHOUT a GroupNorm prologue, whose input range arrives at run time as one
-        word per sample from the epilogue of the kernel that produced the input (Plan.conv, ``absmax_in``): weights only, the
-        kernel forms the staging scale itself."""
-        if self.wp2 is not None:
-            if self._h2_gn is not None:
+    def launch_ptrs(self, act_range: Optional[Tuple[torch.Tensor, torch.Tensor, int, float]], has_absmax_in: bool, in_stride: int,
+                    out_map: Tuple[int, int, int, int]) -> Tuple[Optional[int], ...]:
+        """(wp_x3, wp_h2, act_scale, wp_h2_taps, wp_h2_s2) for one launch of this pack (hdiff_conv_desc / hdiff_conv_range), after
+        allocating the fp16-pair copy that launch may use.  One pack serves ONE source of the pair form's range:
+        ``act_range`` = (gamma, beta, group_elems, gain) -- a plain 3x3 conv whose input is gain * swish(GroupNorm(gamma, beta)) over
+        groups of group_elems elements, bounded by sqrt(n - 1) max|gamma| + max|beta|, which fixes the power of two the activations
+        are staged with (hdiff_gn_act_scale, evaluated at pack time like the weights) -- or ``has_absmax_in``: no prologue, the range
+        arrives at run time as one word per sample from the epilogue of the kernel that produced the input, and the kernel forms
+        the staging scale itself (a plain 3x3 conv, a transposed-conv phase, the 5x5 at stride 2 as four parity-plane convolutions)."""
+        same = in_stride == 1 and out_map == (1, 0, 1, 0)
+        wp_h2 = act_scale = wp_h2_taps = wp_h2_s2 = None
+        if act_range is not None and self.kind == PLAIN_3X3:
+            if same:
+                self._serve_gn(*act_range)
+            # only calls that carry the range take the fp16-pair form (a pack reused without one runs the triples)
+            wp_h2, act_scale = _ptr(self.wp2), _ptr(self.act_scale)
+        if has_absmax_in and in_stride == 1 and self.kind in (TAPS_3X3, ONE_TAP):
+            if self.wp2 is None and self.kind == TAPS_3X3:
+                self.wp2 = self._pair_buffer("hdiff_pack_conv_weight_h2_taps_words", self.ntaps)
+            wp_h2_taps = _ptr(self.wp2)
+        elif has_absmax_in and same and self.kind == PLAIN_3X3:
+            if self._gn is not None:
                 raise RuntimeError("PackedConv.enable_h2_words: this pack already stages activations behind a GroupNorm")
-            return
-        if self.wp3 is not None and self._x3_taps is None and not self._x3_transposed:
-            words = C.c_int64(0)
-            _capi.check(_capi.lib().hdiff_pack_conv_weight_h2_words(self.cout, self.cin, self.cout_pad, C.byref(words)),
-                        "pack_conv_weight_h2_words")
-            self.wp2 = torch.empty(words.value, dtype=torch.int32, device=self.wp.device)
-            self._h2_src = self._x3_src
+            if self.wp2 is None:
+                self.wp2 = self._pair_buffer("hdiff_pack_conv_weight_h2_words")
+            wp_h2 = _ptr(self.wp2)
+        elif has_absmax_in and in_stride == 2 and self.kind == S2_5X5:
+            if self.wp2 is None:
+                self.wp2 = self._pair_buffer("hdiff_pack_conv_weight_h2_s2_words")
+            wp_h2_s2 = _ptr(self.wp2)
+        return _ptr(self.wp3), wp_h2, act_scale, wp_h2_taps, wp_h2_s2
 
-    def enable_h2_taps(self) -> None:
-        """The fp16-pair copy of a tap-list pack (enable_x3_taps with 4 / 6 / 9 taps: the transposed-conv phases), used when
-        the launch is given its input's range word."""
-        if self.wp2t is None and self.wp3 is not None and self._x3_taps is not None and self.ntaps in (4, 6, 9):
-            words = C.c_int64(0)
-            _capi.check(_capi.lib().hdiff_pack_conv_weight_h2_taps_words(self.cout, self.cin, self.cout_pad, self.ntaps,
-                                                                         C.byref(words)), "pack_conv_weight_h2_taps_words")
-            self.wp2t = torch.empty(words.value, dtype=torch.int32, device=self.wp.device)
-
-    def enable_h2_s2(self) -> None:
-        """The fp16-pair copy of a 25-tap 5x5 pack (DownSample's folded weights), made from ``wp`` itself once its sources are
-        packed: the stride-2 conv then runs as four parity-plane pair convolutions when it is given its input's range word."""
-        if self.wp2s is None and self.ntaps == 25 and self.cin % 16 == 0 and \
-                all(dy == t // 5 - 2 and dx == t % 5 - 2 for t, (dy, dx) in enumerate(zip(self.taps.dy, self.taps.dx))):
-            words = C.c_int64(0)
-            _capi.check(_capi.lib().hdiff_pack_conv_weight_h2_s2_words(self.cout, self.cin, self.cout_pad, C.byref(words)),
-                        "pack_conv_weight_h2_s2_words")
-            self.wp2s = torch.empty(words.value, dtype=torch.int32, device=self.wp.device)
+    def _serve_gn(self, gamma: torch.Tensor, beta: torch.Tensor, group_elems: int, gain: float = 1.0) -> None:
+        gn = (gamma, beta, int(group_elems), float(gain))
+        ident = lambda g: (g[0].data_ptr(), g[1].data_ptr(), g[2], g[3])
+        if self.wp2 is None:
+            self.wp2 = self._pair_buffer("hdiff_pack_conv_weight_h2_words")
+            self.act_scale = torch.empty(2, dtype=torch.float32, device=self.wp.device)
+            self._gn = gn
+        elif self._gn is None:
+            raise RuntimeError("PackedConv.enable_h2: this pack already serves a conv that takes its range from a word")
+        elif ident(self._gn) != ident(gn):
+            # one pack = one staging scale: a second conv behind another GroupNorm (or another gain) must not inherit it silently
+            raise RuntimeError("PackedConv.enable_h2: this pack already stages activations for another GroupNorm / gain; "
+                               "use one PackedConv per (convolution, GroupNorm) pair")
 
     def enable_x3(self, w: torch.Tensor, transposed: bool = False) -> None:
         """Also keep the weights as three bf16 pieces (conv3x3_x3.hip) -- used when the contraction mode is bf16x3.
@@ -169,8 +174,7 @@ class PackedConv:
         if self.ntaps == 9 and self.cin % 16 == 0 and tuple(w.shape[2:]) == (3, 3):
             self.wp3 = torch.empty((self.cin // 16) * 9 * 3 * self.cout_pad * 8, dtype=torch.int32, device=self.wp.device)
             self._x3_src = w
-            self._x3_transposed = bool(transposed)
-            self._x3_taps = None
+            self.kind = PLAIN_3X3_T if transposed else PLAIN_3X3
 
     def enable_x3_taps(self, w: torch.Tensor, mode: int) -> None:
         """The split-bf16 copy for a launch whose taps are a subset of the 3x3 neighbourhood reading elements (ky, kx) of a
@@ -178,7 +182,8 @@ class PackedConv:
         if self.ntaps in (1, 4, 6, 9) and self.cin % 16 == 0 and all(-1 <= v <= 1 for v in self.taps.dy + self.taps.dx):
             self.wp3 = torch.empty((self.cin // 16) * self.ntaps * 3 * self.cout_pad * 8, dtype=torch.int32, device=self.wp.device)
             self._x3_src = w
-            self._x3_taps = (int(mode), int(w.shape[2]), int(w.shape[3]))
+            self._x3_layout = (int(mode), int(w.shape[2]), int(w.shape[3]))
+            self.kind = ONE_TAP if self.ntaps == 1 else TAPS_3X3
 
     def add_source(self, w: torch.Tensor, mode: int, ky: Sequence[int], kx: Sequence[int], accumulate: int) -> None:
         kh, kw = int(w.shape[2]), int(w.shape[3])
@@ -186,38 +191,31 @@ class PackedConv:
 
     def pack(self, stream: int) -> None:
         lib = _capi.lib()
+        taps = lambda ky, kx: ((C.c_int * self.ntaps)(*ky), (C.c_int * self.ntaps)(*kx))
         for w, mode, kh, kw, ky, kx, acc in self.sources:
             require_gpu_tensor(w, "conv weight")
-            a_ky = (C.c_int * self.ntaps)(*ky)
-            a_kx = (C.c_int * self.ntaps)(*kx)
             _capi.check(lib.hdiff_pack_conv_weight(w.data_ptr(), self.wp.data_ptr(), mode, self.cout, self.cin, kh, kw,
-                                                   self.ntaps, a_ky, a_kx, self.cin_pad, self.cout_pad, acc, stream),
+                                                   self.ntaps, *taps(ky, kx), self.cin_pad, self.cout_pad, acc, stream),
                         "pack_conv_weight")
-        if self.wp3 is not None and self._x3_taps is not None:
-            mode, kh, kw = self._x3_taps
-            a_ky, a_kx = (C.c_int * self.ntaps)(*self.taps.ky), (C.c_int * self.ntaps)(*self.taps.kx)
-            _capi.check(lib.hdiff_pack_conv_weight_x3_taps(self._x3_src.data_ptr(), self.wp3.data_ptr(), mode, self.cout, self.cin,
-                                                           kh, kw, self.ntaps, a_ky, a_kx, self.cout_pad, stream),
-                        "pack_conv_weight_x3_taps")
-        elif self.wp3 is not None:
+        if self.kind in (TAPS_3X3, ONE_TAP):
+            mode, kh, kw = self._x3_layout
+            tail = (mode, self.cout, self.cin, kh, kw, self.ntaps, *taps(self.taps.ky, self.taps.kx), self.cout_pad, stream)
+            _capi.check(lib.hdiff_pack_conv_weight_x3_taps(self._x3_src.data_ptr(), self.wp3.data_ptr(), *tail), "pack_conv_weight_x3_taps")
+            if self.wp2 is not None:
+                _capi.check(lib.hdiff_pack_conv_weight_h2_taps(self._x3_src.data_ptr(), self.wp2.data_ptr(), *tail), "pack_conv_weight_h2_taps")
+        elif self.kind in (PLAIN_3X3, PLAIN_3X3_T):
             _capi.check(lib.hdiff_pack_conv_weight_x3(self._x3_src.data_ptr(), self.wp3.data_ptr(), self.cout, self.cin,
-                                                      self.cout_pad, int(self._x3_transposed), stream), "pack_conv_weight_x3")
-        if self.wp2s is not None:
-            _capi.check(lib.hdiff_pack_conv_weight_h2_s2(self.wp.data_ptr(), self.wp2s.data_ptr(), self.cout, self.cin, self.cin_pad,
+                                                      self.cout_pad, int(self.kind == PLAIN_3X3_T), stream), "pack_conv_weight_x3")
+            if self.wp2 is not None:
+                _capi.check(lib.hdiff_pack_conv_weight_h2(self._x3_src.data_ptr(), self.wp2.data_ptr(), self.cout, self.cin,
+                                                          self.cout_pad, stream), "pack_conv_weight_h2")
+            if self._gn is not None:
+                gamma, beta, group_elems, gain = self._gn
+                _capi.check(lib.hdiff_gn_act_scale(gamma.data_ptr(), beta.data_ptr(), int(gamma.numel()), C.c_int64(group_elems),
+                                                   C.c_float(gain), self.act_scale.data_ptr(), stream), "gn_act_scale")
+        elif self.wp2 is not None:           # S2_5X5
+            _capi.check(lib.hdiff_pack_conv_weight_h2_s2(self.wp.data_ptr(), self.wp2.data_ptr(), self.cout, self.cin, self.cin_pad,
                                                          self.cout_pad, stream), "pack_conv_weight_h2_s2")
-        if self.wp2t is not None:
-            mode, kh, kw = self._x3_taps
-            a_ky, a_kx = (C.c_int * self.ntaps)(*self.taps.ky), (C.c_int * self.ntaps)(*self.taps.kx)
-            _capi.check(lib.hdiff_pack_conv_weight_h2_taps(self._x3_src.data_ptr(), self.wp2t.data_ptr(), mode, self.cout, self.cin,
-                                                           kh, kw, self.ntaps, a_ky, a_kx, self.cout_pad, stream),
-                        "pack_conv_weight_h2_taps")
-        if self.wp2 is not None:
-            _capi.check(lib.hdiff_pack_conv_weight_h2(self._h2_src.data_ptr(), self.wp2.data_ptr(), self.cout, self.cin,
-                                                      self.cout_pad, stream), "pack_conv_weight_h2")
-        if self.wp2 is not None and self._h2_gn is not None:
-            gamma, beta, group_elems, gain = self._h2_gn
-            _capi.check(lib.hdiff_gn_act_scale(gamma.data_ptr(), beta.data_ptr(), int(gamma.numel()), C.c_int64(group_elems),
-                                               C.c_float(gain), self.act_scale.data_ptr(), stream), "gn_act_scale")
 
 
 # ----------------------------------------------------------------------------------------------------------------------
@@ -364,29 +362,14 @@ class Plan:
         d.VH, d.VW, d.in_stride = VH, VW, in_stride
         d.out_sy, d.out_oy, d.out_sx, d.out_ox = out_map
         d.ntaps = pk.ntaps
-        d.wp_x3 = _ptr(pk.wp3)
         if act_range is None and gn is not None:
             act_range = self._gn_src.get(id(gn[0]))
-        if act_range is not None and pk.wp3 is not None and pk._x3_taps is None and not pk._x3_transposed and in_stride == 1 \
-                and out_map == (1, 0, 1, 0):
-            # a plain 3x3 conv behind GroupNorm + Swish: the fp16-pair form of the split-operand kernel (its input range is known)
-            pk.enable_h2(pk._x3_src, *act_range)
-        if act_range is not None:      # only calls that carry the range take the fp16-pair form (a pack reused without one runs the triples)
-            d.wp_h2, d.act_scale = _ptr(pk.wp2), _ptr(pk.act_scale)
+        assert (absmax_out is None and absmax_in is None) or (dropout is None and (absmax_in is None or gn is None))
+        d.wp_x3, d.wp_h2, d.act_scale, wp_h2_taps, wp_h2_s2 = pk.launch_ptrs(act_range, absmax_in is not None, in_stride, out_map)
         r = None
         if absmax_out is not None or absmax_in is not None:
-            assert dropout is None and (absmax_in is None or gn is None)
             r = _capi.ConvRange()
-            r.absmax_out, r.absmax_in = _ptr(absmax_out), _ptr(absmax_in)
-            if absmax_in is not None and in_stride == 1 and pk._x3_taps is not None:
-                pk.enable_h2_taps()
-                r.wp_h2_taps = _ptr(pk.wp2t)
-            elif absmax_in is not None and in_stride == 1 and out_map == (1, 0, 1, 0):
-                pk.enable_h2_words()
-                d.wp_h2 = _ptr(pk.wp2)
-            elif absmax_in is not None and in_stride == 2 and pk.ntaps == 25:
-                pk.enable_h2_s2()
-                r.wp_h2_s2 = _ptr(pk.wp2s)
+            r.absmax_out, r.absmax_in, r.wp_h2_taps, r.wp_h2_s2 = _ptr(absmax_out), _ptr(absmax_in), wp_h2_taps, wp_h2_s2
         for i in range(pk.ntaps):
             d.tap_dy[i], d.tap_dx[i] = pk.taps.dy[i], pk.taps.dx[i]
         need = C.c_int64(0)

@@ -195,10 +195,12 @@ int hdiff_conv2d_fwd_dropout(const hdiff_conv_desc* d, const uint32_t* keep_bits
  *   wp_h2_taps  hdiff_pack_conv_weight_h2_taps of the descriptor's tap list, or NULL; needs absmax_in.
  *   wp_h2_s2    hdiff_pack_conv_weight_h2_s2 of the descriptor's wp, or NULL; needs absmax_in, ntaps = 25 and in_stride = 2.
  *               With it the 5x5 / stride-2 / pad-2 conv (taps in row-major order, no prologue, no residual, Cin % 16 == 0, a
- *               launch large enough to fill the chip) runs as four parity-plane pair convolutions inside this one call: the
- *               first carries bias / addvec, the others add to out.  Any other descriptor keeps the fp32 kernel.
- * Sample b of the output depends on word b alone.  In every contraction mode but HDIFF_CONTRACT_BF16X3 the call IS
- * hdiff_conv2d_fwd(d): the struct is ignored, the words are neither read nor written.  Same workspace query. */
+ *               launch large enough to fill the chip) runs as four parity-plane pair convolutions inside this one call: each
+ *               adds to what the ones before left in out, the LAST carries bias / addvec (one rounding at the size of the
+ *               result).  Any other descriptor keeps the fp32 kernel.
+ * Sample b of the output depends on word b alone.  Outside the split-operand modes (HDIFF_CONTRACT_BF16X3 and
+ * HDIFF_CONTRACT_F16), that is in HDIFF_CONTRACT_F32, the call IS hdiff_conv2d_fwd(d): the struct is ignored, the words are
+ * neither read nor written.  Same workspace query. */
 typedef struct hdiff_conv_range {
   uint32_t* absmax_out;
   const uint32_t* absmax_in;
@@ -208,6 +210,22 @@ typedef struct hdiff_conv_range {
 int hdiff_conv2d_fwd_range(const hdiff_conv_desc* d, const hdiff_conv_range* r, hdiff_stream_t stream);
 /* Zeroes n range words (one tiny launch: captured into a graph, every replay starts from zeros). */
 int hdiff_range_words_zero(uint32_t* words, int n, hdiff_stream_t stream);
+
+/* Which kernel the three forward entries run a descriptor on, in the contraction mode of the moment.  Host only: nothing is
+ * launched, no device is needed, no pointer of the descriptor is dereferenced.  r may be NULL (hdiff_conv2d_fwd); dropout != 0
+ * asks for hdiff_conv2d_fwd_dropout (then r must be NULL).  The validation of the entry asked for applies, with its messages.
+ * *absmax_tail_out = 1 when the small conv_out_absmax_kernel launch follows the conv (r->absmax_out set in a split-operand mode
+ * on a route whose epilogue does not fill the words: IGEMM and DIRECT_1X1), else 0. */
+enum {
+  HDIFF_CONV_ROUTE_IGEMM = 0,         /* conv_igemm_kernel on wp (fp32-input MFMA), split-K when the workspace query asked for it */
+  HDIFF_CONV_ROUTE_DIRECT_1X1 = 1,    /* conv1x1_direct_kernel on wp */
+  HDIFF_CONV_ROUTE_X3_1X1 = 2,        /* conv1x1_x3_kernel on the one-tap wp_x3 (bf16 triples) */
+  HDIFF_CONV_ROUTE_X3_TRIPLES = 3,    /* conv3x3_x3_kernel on wp_x3 (bf16 triples) */
+  HDIFF_CONV_ROUTE_X3_PAIRS_GN = 4,   /* conv3x3_x3_kernel on wp_h2 (fp16 pairs), staging scale from act_scale */
+  HDIFF_CONV_ROUTE_X3_PAIRS_WORD = 5, /* conv3x3_x3_kernel on wp_h2 or r->wp_h2_taps (fp16 pairs), staging scale from r->absmax_in */
+  HDIFF_CONV_ROUTE_S2_PAIRS_WORD = 6  /* four parity-plane launches of conv3x3_x3_kernel on r->wp_h2_s2, scale from r->absmax_in */
+};
+int hdiff_conv2d_fwd_route(const hdiff_conv_desc* d, const hdiff_conv_range* r, int dropout, int* route_out, int* absmax_tail_out);
 
 /* Weight gradient of hdiff_conv2d_fwd (autograd of the conv weights, TrainCondition.py:60).  Same geometry fields as the
  * forward descriptor; dy is the gradient of the forward's `out`.  The kernel writes `nsplit` packed partial slabs

@@ -369,3 +369,37 @@ def test_f32_mode_ignores_the_words():
 
     with_words, without = in_f32_mode(lambda: run(True)), in_f32_mode(lambda: run(False))
     assert all(torch.equal(a, b) for a, b in zip(with_words, without))
+
+
+def test_default_plan_route_histogram():
+    """Which kernel each conv of the default model's plan runs on, asked of hdiff_conv2d_fwd_route for every kept descriptor -- the
+    plan is built, not run.  128 x 128 with B = 2 is the smallest shape at which level 0 passes 192 workgroups (3x3: 64 tiles x
+    2 channel blocks x 2 samples = 256; 1x1: 32 768 pixels) while every deeper level, the tail (one channel block: 128) and every
+    Up / DownSample but the last UpSample's 3x3 (512) stay below.  The literals are what the predicate cascade of the commit before
+    the route function answers for these same descriptors (profiles/conv_route_refactor.txt, section 5), that is per kernel:
+    conv_igemm_kernel 77, conv3x3_x3_kernel<.., PAIR> 11, conv1x1_x3_kernel 7, conv_out_absmax_kernel 17; f32 mode:
+    conv_igemm_kernel 88, conv1x1_direct_kernel 7.  Of the 11 pair launches one takes its range from a word (UpSample's 3x3 at
+    level 0), ten from a GroupNorm (the 3x3 convs of level 0's two down and three up blocks)."""
+    import collections
+    import ctypes as C
+    from hdiff_amd import _capi
+    from hdiff_amd.DiffusionFreeGuidence.ModelCondition import UNet, _params_of
+    m = UNet(T=500, num_labels=10, ch=128, ch_mult=[1, 2, 2, 2], num_res_blocks=2, dropout=0.15).to(DEV).eval()
+    plan = E.UNetPlan(_params_of(m), m._shape, 2, 128, 128, torch.device(DEV)).plan
+    convs = [k for k in plan._keep if isinstance(k, tuple) and k and isinstance(k[0], _capi.ConvDesc)]
+    assert len(convs) == sum(name.startswith("hdiff_conv2d_fwd") for name, _, _ in plan.ops) == 95
+
+    def histogram():
+        hist, tails = collections.Counter(), 0
+        for kept in convs:
+            r = next((v for v in kept if isinstance(v, _capi.ConvRange)), None)
+            route, tail = C.c_int(-1), C.c_int(-1)
+            _capi.check(plan.lib.hdiff_conv2d_fwd_route(C.byref(kept[0]), None if r is None else C.byref(r), 0, C.byref(route),
+                                                        C.byref(tail)), "conv2d_fwd_route")
+            hist[route.value] += 1
+            tails += tail.value
+        return dict(hist), tails
+
+    IGEMM, DIRECT_1X1, X3_1X1, X3_PAIRS_GN, X3_PAIRS_WORD = 0, 1, 2, 4, 5
+    assert histogram() == ({IGEMM: 77, X3_1X1: 7, X3_PAIRS_GN: 10, X3_PAIRS_WORD: 1}, 17)
+    assert in_f32_mode(histogram) == ({IGEMM: 88, DIRECT_1X1: 7}, 0)
