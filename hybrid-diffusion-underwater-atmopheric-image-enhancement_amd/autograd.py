@@ -498,7 +498,7 @@ class _SingleHeadFn(Function):
         B, C3, H, W = (int(v) for v in qkv.shape)
         Cc, L = C3 // 3, H * W
         o = torch.empty(B, Cc, H, W, device=qkv.device)
-        if Cc <= 64:
+        if Cc <= E.FLASH_MAX_HEAD:
             _capi.check(lib.hdiff_mha_flash_fwd(qkv.data_ptr(), o.data_ptr(), None, B, Cc, 1, L, _stream(qkv.device)), "mha_flash_fwd")
         else:
             _capi.check(lib.hdiff_mha_wide_fwd(qkv.data_ptr(), o.data_ptr(), B, Cc, L, _stream(qkv.device)), "mha_wide_fwd")

@@ -534,61 +534,74 @@ void launch_v(const float* qkv, float* o, float* lse2, int B, int C, int heads, 
   hipLaunchKernelGGL((mha_flash_fwd_kernel<D, NQ>), grid, dim3(ATT_THREADS), 0, stream, qkv, o, lse2, C, L, qscale, check);
 }
 
-template <int D>
-int launch_d(const float* qkv, float* o, float* lse2, int B, int C, int heads, int L, void* ws, int64_t ws_bytes,
-             hipStream_t stream) {
-  const float qscale = 1.4426950408889634f / sqrtf((float)D);
-  (void)hipGetLastError();  // drop any stale error left by another HIP user in this thread
-  if constexpr (D >= 48) {
-    // d_head 48 / 64 (ch_mult containing 3 or 4 at ch = 128: C = 384 / 512): the running-max kernel with one query tile per
-    // wave -- the register budget of the wider tiles does not stretch to 12-16 k-steps; not shapes of the default model
-    launch_v<D, 1>(qkv, o, lse2, B, C, heads, L, qscale, 0, stream);
-  } else {
-    int nq = (L >= 512) ? 4 : 1;   // 4 query tiles per wave: 3 waves per SIMD at d_head 16, 2 at d_head 32 (8 tiles measured no faster)
+// Which program runs a forward call (HDIFF_MHA_FWD_ROUTE_*, include/hdiff.h), decided once: mha_flash_fwd_any switches over it
+// and hdiff_mha_flash_fwd_route reports it.  Touches no device.  nq: query tiles per wave of mha_flash_fwd_kernel, as main
+// kernel or as check pass; check: it runs in check mode behind the route's fixed-reference kernel.
+struct MhaFwdRoute { int route, nq, check; };
+MhaFwdRoute mha_fwd_route(int B, int C, int heads, int L, bool want_lse, int64_t ws_bytes, int mode) {
+  const int D = C / heads;
+  // d_head 48 / 64 (ch_mult containing 3 or 4 at ch = 128: C = 384 / 512): the running-max kernel with one query tile per
+  // wave -- the register budget of the wider tiles does not stretch to 12-16 k-steps; not shapes of the default model
+  if (D >= 48 || L < 512) return {HDIFF_MHA_FWD_ROUTE_RUNNING_MAX, 1, 0};
+  // from here on 4 query tiles per wave: 3 waves per SIMD at d_head 16, 2 at d_head 32 (8 tiles measured no faster)
+  if (mode != HDIFF_CONTRACT_F32) {
+    const int64_t need = mha_fwd_x3p_workspace(B, C, heads, L);
+    const bool ws_ok = need != 0 && ws_bytes >= need;
+    if (mode == HDIFF_CONTRACT_F16 && !want_lse && ws_ok) return {HDIFF_MHA_FWD_ROUTE_F16_SINGLE, 4, 1};
+    if (ws_ok && D == 16) return {HDIFF_MHA_FWD_ROUTE_H2_PAIRS, 4, 1};
     // d_head 32 on the fixed-reference kernel: 134 TFLOP/s against 120 on the running-max kernel (L = 16 384, batch 16)
-    if (nq == 4 && split_operands_on() &&
-        ((contraction_mode() == HDIFF_CONTRACT_F16 &&
-          launch_mha_fwd_f16(qkv, o, lse2, B, C, heads, L, qscale, ws, ws_bytes, stream)) ||     // f16 mode, no lse: single fp16 pieces
-         launch_mha_fwd_h2(qkv, o, lse2, B, C, heads, L, qscale, ws, ws_bytes, stream) ||       // d_head 16, fp16 pairs (needs the workspace)
-         launch_mha_fwd_x3p(qkv, o, lse2, B, C, heads, L, qscale, ws, ws_bytes, stream) ||      // d_head 32, fp16 pairs (needs the workspace)
-         launch_mha_fwd_x3(qkv, o, lse2, B, C, heads, L, qscale, stream))) {                    // bf16 triples split in the loop
-      // split-bf16 kernel (attention_x3.hip), same fixed-reference protocol: overflow-proof fp32 kernel in check mode behind it
-      static const bool skip_check = getenv("HDIFF_NO_CHECK_PASS") != nullptr;      // dev knob: look at the poisoned rows
-      if (!skip_check) launch_v<D, 4>(qkv, o, lse2, B, C, heads, L, qscale, 1, stream);
-    } else if (nq == 4 && L % KT == 0) {
-      // fixed-reference fast kernel, then the overflow-proof kernel in check mode (exits at once unless flagged)
-      dim3 grid(cdiv(L, 256), heads, B);
-      hipLaunchKernelGGL((mha_flash_fwd_fast_kernel<D, 4>), grid, dim3(ATT_THREADS), 0, stream, qkv, o, lse2, C, L, qscale);
-      launch_v<D, 4>(qkv, o, lse2, B, C, heads, L, qscale, 1, stream);
-    } else if (nq >= 8) launch_v<D, 8>(qkv, o, lse2, B, C, heads, L, qscale, 0, stream);
-    else if (nq >= 4) launch_v<D, 4>(qkv, o, lse2, B, C, heads, L, qscale, 0, stream);
-    else launch_v<D, 1>(qkv, o, lse2, B, C, heads, L, qscale, 0, stream);
+    if (ws_ok && D == 32) return {HDIFF_MHA_FWD_ROUTE_X3P_PAIRS, 4, 1};
+    if (L % KT == 0 && (D == 16 || D == 32)) return {HDIFF_MHA_FWD_ROUTE_X3_TRIPLES, 4, 1};
   }
-  HDIFF_CHECK_LAUNCH("mha_flash_fwd_kernel");
-  return HDIFF_OK;
+  if (L % KT == 0) return {HDIFF_MHA_FWD_ROUTE_FAST_F32, 4, 1};
+  return {HDIFF_MHA_FWD_ROUTE_RUNNING_MAX, 4, 0};
+}
+
+template <int D>
+void launch_d(const float* qkv, float* o, float* lse2, int B, int C, int heads, int L, void* ws, const MhaFwdRoute& rt,
+              hipStream_t stream) {
+  const float qscale = 1.4426950408889634f / sqrtf((float)D);
+  // mha_flash_fwd_kernel follows: alone, or in check mode behind a fixed-reference kernel (it exits at once unless flagged).
+  // Dev knob: look at the rows a split-operand kernel poisoned (the check pass behind it is not launched)
+  static const bool skip_check = getenv("HDIFF_NO_CHECK_PASS") != nullptr;
+  const bool tail = !skip_check || rt.route == HDIFF_MHA_FWD_ROUTE_RUNNING_MAX || rt.route == HDIFF_MHA_FWD_ROUTE_FAST_F32;
+  if constexpr (D < 48) {      // mha_fwd_route sends d_head 48 / 64 to RUNNING_MAX with nq 1
+    switch (rt.route) {
+      case HDIFF_MHA_FWD_ROUTE_F16_SINGLE: launch_mha_fwd_f16(qkv, o, B, C, heads, L, qscale, ws, stream); break;
+      case HDIFF_MHA_FWD_ROUTE_H2_PAIRS: launch_mha_fwd_h2(qkv, o, lse2, B, C, heads, L, qscale, ws, stream); break;
+      case HDIFF_MHA_FWD_ROUTE_X3P_PAIRS: launch_mha_fwd_x3p(qkv, o, lse2, B, C, heads, L, qscale, ws, stream); break;
+      case HDIFF_MHA_FWD_ROUTE_X3_TRIPLES: launch_mha_fwd_x3(qkv, o, lse2, B, C, heads, L, qscale, stream); break;
+      case HDIFF_MHA_FWD_ROUTE_FAST_F32:
+        hipLaunchKernelGGL((mha_flash_fwd_fast_kernel<D, 4>), dim3(cdiv(L, 256), heads, B), dim3(ATT_THREADS), 0, stream, qkv, o, lse2, C, L, qscale);
+        break;
+      default: break;      // RUNNING_MAX
+    }
+    if (tail && rt.nq == 4) launch_v<D, 4>(qkv, o, lse2, B, C, heads, L, qscale, rt.check, stream);
+  }
+  if (tail && rt.nq == 1) launch_v<D, 1>(qkv, o, lse2, B, C, heads, L, qscale, rt.check, stream);
 }
 
 }  // namespace
 
+// the checks of the launching entries behind their pointer checks, shared with the route query
+static int mha_fwd_check_shape(int B, int C, int heads, int L) {
+  HDIFF_CHECK_ARG(B > 0 && L > 0 && heads > 0 && C % heads == 0, "mha_flash_fwd: bad sizes B=%d C=%d heads=%d L=%d", B, C,
+                  heads, L);
+  HDIFF_CHECK_ARG(mha_head_dim_ok(C / heads), "mha_flash_fwd: head dim %d not in {4, 8, 12, 16, 24, 32, 48, 64}", C / heads);
+  return HDIFF_OK;
+}
+
 static int mha_flash_fwd_any(const float* qkv, float* o, float* lse2, int B, int C, int heads, int L, void* ws,
                              int64_t ws_bytes, hipStream_t s) {
   HDIFF_CHECK_ARG(qkv && o, "mha_flash_fwd: null pointer");
-  HDIFF_CHECK_ARG(B > 0 && L > 0 && heads > 0 && C % heads == 0, "mha_flash_fwd: bad sizes B=%d C=%d heads=%d L=%d", B, C,
-                  heads, L);
-  const int D = C / heads;
-  switch (D) {
-    case 4: return launch_d<4>(qkv, o, lse2, B, C, heads, L, ws, ws_bytes, s);
-    case 8: return launch_d<8>(qkv, o, lse2, B, C, heads, L, ws, ws_bytes, s);
-    case 12: return launch_d<12>(qkv, o, lse2, B, C, heads, L, ws, ws_bytes, s);
-    case 16: return launch_d<16>(qkv, o, lse2, B, C, heads, L, ws, ws_bytes, s);
-    case 24: return launch_d<24>(qkv, o, lse2, B, C, heads, L, ws, ws_bytes, s);
-    case 32: return launch_d<32>(qkv, o, lse2, B, C, heads, L, ws, ws_bytes, s);
-    case 48: return launch_d<48>(qkv, o, lse2, B, C, heads, L, ws, ws_bytes, s);
-    case 64: return launch_d<64>(qkv, o, lse2, B, C, heads, L, ws, ws_bytes, s);
-    default: break;
-  }
-  hdiff::set_error("mha_flash_fwd: head dim %d not in {4, 8, 12, 16, 24, 32, 48, 64}", D);
-  return HDIFF_ERR_INVALID;
+  const int rc = mha_fwd_check_shape(B, C, heads, L);
+  if (rc != HDIFF_OK) return rc;
+  // (a NULL ws comes with ws_bytes = 0: hdiff_mha_flash_fwd passes that, hdiff_mha_flash_fwd_ws checks it)
+  const MhaFwdRoute rt = mha_fwd_route(B, C, heads, L, lse2 != nullptr, ws_bytes, contraction_mode());
+  (void)hipGetLastError();  // drop any stale error left by another HIP user in this thread
+  with_head_dim(C / heads, [&](auto d) { launch_d<decltype(d)::value>(qkv, o, lse2, B, C, heads, L, ws, rt, s); });
+  HDIFF_CHECK_LAUNCH("mha_flash_fwd_kernel");
+  return HDIFF_OK;
 }
 
 extern "C" int hdiff_mha_flash_fwd(const float* qkv, float* o, float* lse2, int B, int C, int heads, int L,
@@ -608,4 +621,17 @@ extern "C" int hdiff_mha_flash_fwd_ws(const float* qkv, float* o, float* lse2, i
                                       int64_t ws_bytes, hdiff_stream_t stream) {
   HDIFF_CHECK_ARG(ws_bytes >= 0 && (ws != nullptr || ws_bytes == 0), "mha_flash_fwd_ws: workspace pointer / size mismatch");
   return mha_flash_fwd_any(qkv, o, lse2, B, C, heads, L, ws, ws_bytes, (hipStream_t)stream);
+}
+
+extern "C" int hdiff_mha_flash_fwd_route(int B, int C, int heads, int L, int want_lse, int64_t ws_bytes, int* route_out,
+                                         int* nq_out, int* check_out) {
+  HDIFF_CHECK_ARG(route_out && nq_out && check_out, "mha_flash_fwd_route: null pointer");
+  HDIFF_CHECK_ARG(ws_bytes >= 0, "mha_flash_fwd_ws: workspace pointer / size mismatch");
+  const int rc = mha_fwd_check_shape(B, C, heads, L);
+  if (rc != HDIFF_OK) return rc;
+  const MhaFwdRoute rt = mha_fwd_route(B, C, heads, L, want_lse != 0, ws_bytes, contraction_mode());
+  *route_out = rt.route;
+  *nq_out = rt.nq;
+  *check_out = rt.check;
+  return HDIFF_OK;
 }

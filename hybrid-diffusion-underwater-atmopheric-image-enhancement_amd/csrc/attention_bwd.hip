@@ -481,120 +481,114 @@ __global__ __launch_bounds__(ATT_THREADS, (D >= 48 ? 1 : 2)) void mha_bwd_fused_
   }
 }
 
-// Geometry shared by the workspace query and the launch.
-struct BwdGeom { int nk, nkb_total, per, nsplit; };
-static BwdGeom bwd_geometry(int B, int heads, int L, int D) {
-  BwdGeom g;
-  g.nk = (L <= 4096 || D >= 48) ? 1 : (D > 16 ? 2 : 4);   // short sequences: 64-key blocks for enough workgroups
-  if (L % (64 * g.nk) != 0) g.nk = 1;                      // ragged sequences: the generic (bounds-checked) kernel, 64-key blocks
-  const int KB = 64 * g.nk;
-  g.nkb_total = cdiv(L, KB);
-  const int pairs = B * heads;
-  int want = cdiv(1024, pairs);                          // ~2 rounds of 2 workgroups per CU on 256 CUs
-  if (want > g.nkb_total) want = g.nkb_total;
-  if (want < 1) want = 1;
-  g.per = cdiv(g.nkb_total, want);
-  g.nsplit = cdiv(g.nkb_total, g.per);                   // no empty key range
-  return g;
+// key tiles (of 16) per wave that the registers hold at this head dim; the instantiations of mha_bwd_fused_kernel stop here
+constexpr int max_nk(int D) { return D >= 48 ? 1 : (D > 16 ? 2 : 4); }
+
+// Which kernels run a backward call (HDIFF_MHA_BWD_ROUTE_*, include/hdiff.h) and on what geometry, decided once: the launch, the
+// workspace query and hdiff_mha_flash_bwd_route read it.  Touches no device.  nk: key tiles per wave of mha_bwd_fused_kernel (0 on
+// H2_PAIRS); aligned = 0: its bounds-checked <D, 1, false> form; kr: key blocks per range and ranges; ws_floats: what ws must hold.
+struct MhaBwdRoute { int route, nk, aligned; KeyRanges kr; int64_t ws_floats; };
+MhaBwdRoute mha_bwd_route(int B, int C, int heads, int L, int mode) {
+  const int D = C / heads;
+  if (mode != HDIFF_CONTRACT_F32 && mha_bwd_x3_shape_ok(B, C, heads, L))      // all five products on the 16-bit matrix core
+    return {HDIFF_MHA_BWD_ROUTE_H2_PAIRS, 0, 1, mha_bwd_h2_key_ranges(B, heads, L, D), mha_bwd_x3_workspace_floats(B, C, heads, L)};
+  int nk = L <= 4096 ? 1 : max_nk(D);                   // short sequences: 64-key blocks for enough workgroups
+  // ragged / unaligned sequences: the generic (bounds-checked) kernel exists for 64-key blocks only (with more key tiles per
+  // wave its bounds handling spills registers in the MFMA loop)
+  if (L % (64 * nk) != 0) nk = 1;
+  const KeyRanges kr = key_ranges(cdiv(L, 64 * nk), cdiv(1024, B * heads));      // ~2 rounds of 2 workgroups per CU on 256 CUs
+  return {HDIFF_MHA_BWD_ROUTE_FUSED_F32, nk, L % (64 * nk) == 0, kr, kr.nsplit > 1 ? (int64_t)kr.nsplit * B * C * L : 0};
 }
 
-template <int D, int NK>
-void launch_fused(const BwdArgs& a, const BwdGeom& g, int B, int heads, hipStream_t stream) {
-  if (a.L % (64 * NK) == 0) {
-    hipLaunchKernelGGL((mha_bwd_fused_kernel<D, NK, true>), dim3(g.nsplit, heads, B), dim3(ATT_THREADS), 0, stream, a);
-  } else if constexpr (NK == 1) {
-    // ragged / unaligned sequences: the generic instantiation exists for 64-key blocks only (bwd_geometry picks NK = 1 for
-    // them: with more key tiles per wave its bounds handling spills registers in the MFMA loop)
-    hipLaunchKernelGGL((mha_bwd_fused_kernel<D, 1, false>), dim3(g.nsplit, heads, B), dim3(ATT_THREADS), 0, stream, a);
-  }
+template <int D, int NK, bool ALIGNED>
+void launch_fused(const BwdArgs& a, int nsplit, int B, int heads, hipStream_t stream) {
+  if constexpr (NK <= max_nk(D))
+    hipLaunchKernelGGL((mha_bwd_fused_kernel<D, NK, ALIGNED>), dim3(nsplit, heads, B), dim3(ATT_THREADS), 0, stream, a);
 }
 
+// HDIFF_MHA_BWD_ROUTE_FUSED_F32 behind mha_delta_kernel
 template <int D>
-int launch_bwd(const float* qkv, const float* o, const float* d_o, const float* lse2, float* delta, float* dqkv, float* ws,
-               int B, int C, int heads, int L, hipStream_t stream) {
-  if constexpr (D == 16 || D == 32) {
-    if (mha_bwd_x3_applicable(B, C, heads, L)) {       // bf16x3 mode: all five products on the bf16 matrix core
-      HDIFF_CHECK_ARG(ws != nullptr, "mha_flash_bwd: this shape needs a workspace (hdiff_mha_flash_bwd_workspace)");
-      const int total = B * heads * L;
-      (void)hipGetLastError();
-      hipLaunchKernelGGL(mha_delta_kernel, dim3(cdiv(total, 256)), dim3(256), 0, stream, o, d_o, delta, C, D, L, total);
-      if (launch_mha_bwd_h2(qkv, d_o, lse2, delta, dqkv, ws, B, C, heads, L, stream)) {
-        HDIFF_CHECK_LAUNCH("mha_bwd (split-bf16) kernels");
-        return HDIFF_OK;
-      }
-      // the device refused the split kernel's LDS size (nothing of it was launched): the fp32-input backward below takes the call -- its
-      // workspace need is never larger (hdiff_mha_flash_bwd_workspace reports the maximum of the two)
-    }
-  }
-  const BwdGeom g = bwd_geometry(B, heads, L, D);
-  HDIFF_CHECK_ARG(g.nsplit == 1 || ws != nullptr, "mha_flash_bwd: this shape needs a workspace (hdiff_mha_flash_bwd_workspace)");
+void launch_bwd_fused(const float* qkv, const float* d_o, const float* lse2, const float* delta, float* dqkv, float* ws, int B,
+                      int C, int heads, int L, const MhaBwdRoute& rt, hipStream_t stream) {
+  const int nsplit = rt.kr.nsplit;
   BwdArgs a;
   a.qkv = qkv; a.d_o = d_o; a.lse2 = lse2; a.delta = delta; a.dqkv = dqkv;
-  a.C = C; a.L = L; a.kb_per_split = g.per;
+  a.C = C; a.L = L; a.kb_per_split = rt.kr.per;
   a.inv_sqrt_d = 1.0f / sqrtf((float)D);
   a.qscale = 1.4426950408889634f * a.inv_sqrt_d;
   const size_t per_sample = (size_t)C * L;
-  if (g.nsplit == 1) {           // one key range: its slab is the Q third of the output itself
+  if (nsplit == 1) {           // one key range: its slab is the Q third of the output itself
     a.dq_part = dqkv; a.split_stride = 0; a.batch_stride = 3 * per_sample;
   } else {
     a.dq_part = ws; a.split_stride = (size_t)B * per_sample; a.batch_stride = per_sample;
   }
-  const int total = B * heads * L;
-  (void)hipGetLastError();  // drop any stale error left by another HIP user in this thread
-  hipLaunchKernelGGL(mha_delta_kernel, dim3(cdiv(total, 256)), dim3(256), 0, stream, o, d_o, delta, C, D, L, total);
-  if constexpr (D >= 48) {
-    launch_fused<D, 1>(a, g, B, heads, stream);             // d_head 48 / 64: 16 keys per wave is what the registers hold
-  } else {
-    if (g.nk == 1) launch_fused<D, 1>(a, g, B, heads, stream);
-    else if (g.nk == 2) launch_fused<D, 2>(a, g, B, heads, stream);
-    else launch_fused<D, (D > 16 ? 2 : 4)>(a, g, B, heads, stream);
-  }
-  if (g.nsplit > 1) {
+  if (!rt.aligned) launch_fused<D, 1, false>(a, nsplit, B, heads, stream);
+  else if (rt.nk == 1) launch_fused<D, 1, true>(a, nsplit, B, heads, stream);
+  else if (rt.nk == 2) launch_fused<D, 2, true>(a, nsplit, B, heads, stream);
+  else launch_fused<D, 4, true>(a, nsplit, B, heads, stream);
+  if (nsplit > 1) {
     const size_t n4 = per_sample / 4 + 1;
     const int bx = (int)((n4 + 255) / 256 < 2048 ? (n4 + 255) / 256 : 2048);
-    hipLaunchKernelGGL(mha_dq_reduce_kernel, dim3(bx, B), dim3(256), 0, stream, ws, dqkv, g.nsplit, C, L, a.split_stride,
-                       per_sample);
+    hipLaunchKernelGGL(mha_dq_reduce_kernel, dim3(bx, B), dim3(256), 0, stream, ws, dqkv, nsplit, C, L, a.split_stride, per_sample);
   }
-  HDIFF_CHECK_LAUNCH("mha_bwd kernels");
-  return HDIFF_OK;
 }
 
 }  // namespace
+
+// the checks of hdiff_mha_flash_bwd behind its pointer check, shared with the route query
+static int mha_bwd_check_shape(int B, int C, int heads, int L) {
+  HDIFF_CHECK_ARG(B > 0 && L > 0 && heads > 0 && C % heads == 0, "mha_flash_bwd: bad sizes B=%d C=%d heads=%d L=%d", B, C,
+                  heads, L);
+  HDIFF_CHECK_ARG(B <= 65535 && heads <= 65535, "mha_flash_bwd: B=%d / heads=%d exceed the grid limits", B, heads);
+  HDIFF_CHECK_ARG(mha_head_dim_ok(C / heads), "mha_flash_bwd: head dim %d not in {4, 8, 12, 16, 24, 32, 48, 64}", C / heads);
+  return HDIFF_OK;
+}
 
 extern "C" int hdiff_mha_flash_bwd_workspace(int B, int C, int heads, int L, int64_t* n_floats) {
   HDIFF_CHECK_ARG(n_floats, "mha_flash_bwd_workspace: null pointer");
   HDIFF_CHECK_ARG(B > 0 && L > 0 && heads > 0 && C % heads == 0, "mha_flash_bwd_workspace: bad sizes B=%d C=%d heads=%d L=%d",
                   B, C, heads, L);
-  const BwdGeom g = bwd_geometry(B, heads, L, C / heads);
-  *n_floats = (g.nsplit > 1) ? (int64_t)g.nsplit * B * C * L : 0;
   // The answer does not depend on the contraction mode: a caller that sizes the buffer, switches the mode and then calls
-  // must not overrun it (the call takes no size).  Shapes the split-bf16 kernel covers get the larger of the two needs.
-  if (mha_bwd_x3_shape_ok(B, C, heads, L)) {
-    const int64_t x3 = mha_bwd_x3_workspace_floats(B, C, heads, L);
-    if (x3 > *n_floats) *n_floats = x3;
-  }
+  // must not overrun it (the call takes no size).  The larger of the two needs (f16 routes as bf16x3 does).
+  const int64_t f32 = mha_bwd_route(B, C, heads, L, HDIFF_CONTRACT_F32).ws_floats;
+  const int64_t split = mha_bwd_route(B, C, heads, L, HDIFF_CONTRACT_BF16X3).ws_floats;
+  *n_floats = f32 > split ? f32 : split;
+  return HDIFF_OK;
+}
+
+extern "C" int hdiff_mha_flash_bwd_route(int B, int C, int heads, int L, int* route_out, int* nk_out, int* aligned_out,
+                                         int* nsplit_out) {
+  HDIFF_CHECK_ARG(route_out && nk_out && aligned_out && nsplit_out, "mha_flash_bwd_route: null pointer");
+  const int rc = mha_bwd_check_shape(B, C, heads, L);
+  if (rc != HDIFF_OK) return rc;
+  const MhaBwdRoute rt = mha_bwd_route(B, C, heads, L, contraction_mode());
+  *route_out = rt.route;
+  *nk_out = rt.nk;
+  *aligned_out = rt.aligned;
+  *nsplit_out = rt.kr.nsplit;
   return HDIFF_OK;
 }
 
 extern "C" int hdiff_mha_flash_bwd(const float* qkv, const float* o, const float* d_o, const float* lse2, float* delta,
                                    float* dqkv, float* ws, int B, int C, int heads, int L, hdiff_stream_t stream) {
   HDIFF_CHECK_ARG(qkv && o && d_o && lse2 && delta && dqkv, "mha_flash_bwd: null pointer");
-  HDIFF_CHECK_ARG(B > 0 && L > 0 && heads > 0 && C % heads == 0, "mha_flash_bwd: bad sizes B=%d C=%d heads=%d L=%d", B, C,
-                  heads, L);
-  HDIFF_CHECK_ARG(B <= 65535 && heads <= 65535, "mha_flash_bwd: B=%d / heads=%d exceed the grid limits", B, heads);
-  const int D = C / heads;
+  const int rc = mha_bwd_check_shape(B, C, heads, L);
+  if (rc != HDIFF_OK) return rc;
+  MhaBwdRoute rt = mha_bwd_route(B, C, heads, L, contraction_mode());
+  // A device that refuses the pair kernels' LDS size is asked before anything is enqueued: the fp32-input backward takes the
+  // call -- its workspace need is never larger (hdiff_mha_flash_bwd_workspace reports the maximum of the two)
+  if (rt.route == HDIFF_MHA_BWD_ROUTE_H2_PAIRS && !mha_bwd_h2_lds_granted()) rt = mha_bwd_route(B, C, heads, L, HDIFF_CONTRACT_F32);
+  HDIFF_CHECK_ARG(rt.ws_floats == 0 || ws != nullptr, "mha_flash_bwd: this shape needs a workspace (hdiff_mha_flash_bwd_workspace)");
+  const int D = C / heads, total = B * heads * L;
   hipStream_t s = (hipStream_t)stream;
-  switch (D) {
-    case 4: return launch_bwd<4>(qkv, o, d_o, lse2, delta, dqkv, ws, B, C, heads, L, s);
-    case 8: return launch_bwd<8>(qkv, o, d_o, lse2, delta, dqkv, ws, B, C, heads, L, s);
-    case 12: return launch_bwd<12>(qkv, o, d_o, lse2, delta, dqkv, ws, B, C, heads, L, s);
-    case 16: return launch_bwd<16>(qkv, o, d_o, lse2, delta, dqkv, ws, B, C, heads, L, s);
-    case 24: return launch_bwd<24>(qkv, o, d_o, lse2, delta, dqkv, ws, B, C, heads, L, s);
-    case 32: return launch_bwd<32>(qkv, o, d_o, lse2, delta, dqkv, ws, B, C, heads, L, s);
-    case 48: return launch_bwd<48>(qkv, o, d_o, lse2, delta, dqkv, ws, B, C, heads, L, s);
-    case 64: return launch_bwd<64>(qkv, o, d_o, lse2, delta, dqkv, ws, B, C, heads, L, s);
-    default: break;
+  (void)hipGetLastError();  // drop any stale error left by another HIP user in this thread
+  hipLaunchKernelGGL(mha_delta_kernel, dim3(cdiv(total, 256)), dim3(256), 0, s, o, d_o, delta, C, D, L, total);
+  if (rt.route == HDIFF_MHA_BWD_ROUTE_H2_PAIRS) {
+    launch_mha_bwd_h2(qkv, d_o, lse2, delta, dqkv, ws, B, C, heads, L, rt.kr, s);
+    HDIFF_CHECK_LAUNCH("mha_bwd (split-bf16) kernels");
+    return HDIFF_OK;
   }
-  hdiff::set_error("mha_flash_bwd: head dim %d not in {4, 8, 12, 16, 24, 32, 48, 64}", D);
-  return HDIFF_ERR_INVALID;
+  with_head_dim(D, [&](auto d) { launch_bwd_fused<decltype(d)::value>(qkv, d_o, lse2, delta, dqkv, ws, B, C, heads, L, rt, s); });
+  HDIFF_CHECK_LAUNCH("mha_bwd kernels");
+  return HDIFF_OK;
 }

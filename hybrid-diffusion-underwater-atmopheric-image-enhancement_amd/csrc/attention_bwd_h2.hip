@@ -1013,27 +1013,6 @@ __global__ void mha_dq_reduce_h2p_kernel(const float* __restrict__ part, const _
   }
 }
 
-struct H2Geom { int nkb_total, per, nsplit; };
-H2Geom h2_geometry(int B, int heads, int L, int D) {
-  H2Geom g;
-  g.nkb_total = L / KB;
-  int want = cdiv(1024, B * heads);                  // workgroups wanted in all: four rounds of one per CU on 256 CUs
-  // At larger batches that leaves few key ranges per (sample, head) pair, and the workgroups of a pair are the ones that share
-  // its Q / dO tile stream in their XCD's L2: up to 16 ranges per pair (batch 16: 567 -> 553 ms per launch; 32: 547) as
-  // long as the slabs stay below the cap (16 GiB, or HDIFF_BWD_SLAB_GIB: mha_bwd_slab_cap_bytes).
-  {
-    const long long per_range = (long long)B * heads * D * L * 4;
-    int cap = (int)(hdiff::mha_bwd_slab_cap_bytes() / per_range);
-    int more = 16 < cap ? 16 : cap;
-    if (more > want) want = more;
-  }
-  if (want > g.nkb_total) want = g.nkb_total;
-  if (want < 1) want = 1;
-  g.per = cdiv(g.nkb_total, want);
-  g.nsplit = cdiv(g.nkb_total, g.per);
-  return g;
-}
-
 }  // namespace
 
 namespace hdiff {
@@ -1057,21 +1036,31 @@ bool mha_bwd_x3_shape_ok(int B, int C, int heads, int L) {
   const int D = C / heads;
   return C % heads == 0 && (D == 16 || D == 32) && L % 256 == 0 && L >= 512 && (int64_t)B * heads * (L / 128) >= 256;
 }
-bool mha_bwd_x3_applicable(int B, int C, int heads, int L) {
-  return split_operands_on() && mha_bwd_x3_shape_ok(B, C, heads, L);
+
+// key blocks per range and ranges of a (sample, head) pair
+KeyRanges mha_bwd_h2_key_ranges(int B, int heads, int L, int D) {
+  int want = cdiv(1024, B * heads);                  // workgroups wanted in all: four rounds of one per CU on 256 CUs
+  // At larger batches that leaves few key ranges per (sample, head) pair, and the workgroups of a pair are the ones that share
+  // its Q / dO tile stream in their XCD's L2: up to 16 ranges per pair (batch 16: 567 -> 553 ms per launch; 32: 547) as
+  // long as the slabs stay below the cap (16 GiB, or HDIFF_BWD_SLAB_GIB: mha_bwd_slab_cap_bytes).
+  const long long per_range = (long long)B * heads * D * L * 4;
+  const int cap = (int)(mha_bwd_slab_cap_bytes() / per_range);
+  const int more = 16 < cap ? 16 : cap;
+  if (more > want) want = more;
+  return key_ranges(L / KB, want);
 }
 
 // slabs (tile-major, one per key range: even a single range goes through the reduce kernel, which restores the [C][L] layout)
 // followed by the piece tensors (S_COUNT = 17 two-byte piece slots per element: the enum above) and the B * heads * 4 tensor maxima, in floats
 int64_t mha_bwd_x3_workspace_floats(int B, int C, int heads, int L) {
-  const H2Geom g = h2_geometry(B, heads, L, C / heads);
+  const KeyRanges g = mha_bwd_h2_key_ranges(B, heads, L, C / heads);
   const int64_t pieces_bytes = (int64_t)B * C * L * S_COUNT * 2;
   return (int64_t)g.nsplit * B * C * L + (pieces_bytes + 3) / 4 + 4 + (int64_t)B * heads * M_COUNT + 4;
 }
 
 // More than 64 KB of LDS per workgroup has to be asked for -- per DEVICE (the attribute belongs to the device's copy of the kernel): asked
 // once per device of this process, remembered, and a refusal is reported to the caller BEFORE anything is launched.
-static bool big_lds_granted() {
+bool mha_bwd_h2_lds_granted() {
   constexpr int MAXDEV = 64;
   static std::atomic<signed char> state[MAXDEV];      // 0: not asked yet, 1: granted, -1: refused
   int dev = -1;
@@ -1088,11 +1077,11 @@ static bool big_lds_granted() {
   return st > 0;
 }
 
-// delta has been computed by the caller (mha_delta_kernel).  false: the device refused the kernel's LDS size, nothing was launched
-bool launch_mha_bwd_h2(const float* qkv, const float* d_o, const float* lse2, const float* delta, float* dqkv, float* ws,
-                       int B, int C, int heads, int L, hipStream_t stream) {
+// HDIFF_MHA_BWD_ROUTE_H2_PAIRS.  Preconditions: mha_bwd_x3_shape_ok, mha_bwd_h2_lds_granted, g = mha_bwd_h2_key_ranges, ws holds
+// mha_bwd_x3_workspace_floats, delta has been computed by the caller (mha_delta_kernel).
+void launch_mha_bwd_h2(const float* qkv, const float* d_o, const float* lse2, const float* delta, float* dqkv, float* ws,
+                       int B, int C, int heads, int L, KeyRanges g, hipStream_t stream) {
   const int D = C / heads;
-  const H2Geom g = h2_geometry(B, heads, L, D);
   const size_t per_sample = (size_t)C * L;
   const int64_t slab = (int64_t)g.nsplit * B * C * L;
   uintptr_t pw = reinterpret_cast<uintptr_t>(ws + slab);
@@ -1110,7 +1099,6 @@ bool launch_mha_bwd_h2(const float* qkv, const float* d_o, const float* lse2, co
   const dim3 mgrid(cdiv(L, 4096), M_COUNT * heads, B), sgrid(cdiv(L, THREADS), 4 * heads, B), grid(g.nsplit, heads, B);
   const size_t n4 = per_sample / 4;
   const int bx = (int)((n4 + 255) / 256 < 2048 ? (n4 + 255) / 256 : 2048);
-  if (!big_lds_granted()) return false;      // nothing has been enqueued yet: the caller runs the fp32-input backward instead
   (void)hipMemsetAsync(absmax, 0, (size_t)B * heads * M_COUNT * sizeof(unsigned), stream);
   if (D == 16) {
     hipLaunchKernelGGL(mha_bwd_absmax_kernel<16>, mgrid, dim3(THREADS), 0, stream, qkv, d_o, absmax, C, L);
@@ -1123,7 +1111,6 @@ bool launch_mha_bwd_h2(const float* qkv, const float* d_o, const float* lse2, co
     hipLaunchKernelGGL(mha_bwd_h2_kernel<32>, grid, dim3(MTHREADS), Geo::LDS_BYTES, stream, a);
     hipLaunchKernelGGL(mha_dq_reduce_h2_kernel<32>, dim3(bx, B), dim3(256), 0, stream, ws, dqkv, g.nsplit, C, L, a.split_stride);
   }
-  return true;
 }
 
 }  // namespace hdiff

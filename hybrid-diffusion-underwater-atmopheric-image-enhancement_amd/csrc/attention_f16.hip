@@ -479,14 +479,10 @@ __global__ __launch_bounds__(THREADS, 2) void mha_flash_fwd_f16_d32_kernel(const
 
 namespace hdiff {
 
-// The inference forward of the f16 mode.  Returns false (and launches nothing) when the call is not the one the mode acts on:
-// a log-sum-exp is asked for, the shape is not covered or the workspace is missing -- the caller then runs the pair kernels.
-bool launch_mha_fwd_f16(const float* qkv, float* o, float* lse2, int B, int C, int heads, int L, float qscale, void* ws,
-                        int64_t ws_bytes, hipStream_t stream) {
-  const int64_t need = mha_fwd_x3p_workspace(B, C, heads, L);      // the pair kernels' size: plans are pooled by it; a third is used
-  if (lse2 != nullptr || need == 0 || ws == nullptr || ws_bytes < need) return false;
+// The inference forward of the f16 mode: it writes no log-sum-exp.  Precondition (HDIFF_MHA_FWD_ROUTE_F16_SINGLE): d_head 16 or 32
+// and ws holds mha_fwd_x3p_workspace bytes, non-zero for this shape (the pair kernels' size: plans are pooled by it; a third is used).
+void launch_mha_fwd_f16(const float* qkv, float* o, int B, int C, int heads, int L, float qscale, void* ws, hipStream_t stream) {
   const int D = C / heads;
-  if (D != 16 && D != 32) return false;
   const int64_t pieces = (int64_t)B * 3 * C * L * 2;               // B * heads * 3 pieces of L * D fp16
   // the 3 C row maxima per sample sit right behind the pieces: pieces + 12 B C bytes is far below need = 3 * pieces + tail
   float* rowmax = reinterpret_cast<float*>(reinterpret_cast<unsigned char*>(ws) + pieces);
@@ -500,7 +496,6 @@ bool launch_mha_fwd_f16(const float* qkv, float* o, float* lse2, int B, int C, i
     hipLaunchKernelGGL((f16_split_kernel<32>), sgrid, dim3(THREADS), 0, stream, qkv, rowmax, wsh, C, L, qscale);
     hipLaunchKernelGGL(mha_flash_fwd_f16_d32_kernel, grid, dim3(THREADS), 0, stream, wsh, rowmax, o, C, L);
   }
-  return true;
 }
 
 }  // namespace hdiff

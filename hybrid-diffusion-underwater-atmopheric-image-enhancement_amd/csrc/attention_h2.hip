@@ -581,18 +581,13 @@ void launch_qk_split_h2(const float* qkv, void* ws, int B, int C, int heads, int
 }
 
 // The d_head 16 forward on fp16 pairs (scores: four balanced products; P.V: three) on its own operand layout in the workspace.
-// Returns false when the shape is not covered or the workspace is missing (the caller then runs the bf16-triple kernels).
-bool launch_mha_fwd_h2(const float* qkv, float* o, float* lse2, int B, int C, int heads, int L, float qscale, void* ws,
-                       int64_t ws_bytes, hipStream_t stream) {
-  const int64_t need = mha_fwd_x3p_workspace(B, C, heads, L);
-  if (need == 0 || ws == nullptr || ws_bytes < need) return false;
-  const int D = C / heads;
-  if (D != 16) return false;
+// Precondition (HDIFF_MHA_FWD_ROUTE_H2_PAIRS): d_head 16 and ws holds mha_fwd_x3p_workspace bytes, non-zero for this shape.
+void launch_mha_fwd_h2(const float* qkv, float* o, float* lse2, int B, int C, int heads, int L, float qscale, void* ws,
+                       hipStream_t stream) {
   launch_qk_split_h2(qkv, ws, B, C, heads, L, qscale, stream);
   launch_v_split_h2(qkv, ws, B, C, heads, L, stream);
   hipLaunchKernelGGL((mha_flash_fwd_h2_kernel<16, 4>), dim3(L / 256, heads, B), dim3(THREADS), 0, stream, (const __bf16*)ws, o, lse2,
                      C, L, 1.0f);
-  return true;
 }
 
 }  // namespace hdiff

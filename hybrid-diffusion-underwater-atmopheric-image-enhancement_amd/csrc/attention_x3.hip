@@ -307,19 +307,13 @@ __global__ __launch_bounds__(THREADS, 2) void mha_flash_fwd_x3_kernel(const floa
 
 namespace hdiff {
 
-// Launches the split-bf16 kernel for (d_head, L) it supports; returns false if this shape is not covered.
-bool launch_mha_fwd_x3(const float* qkv, float* o, float* lse2, int B, int C, int heads, int L, float qscale, hipStream_t stream) {
-  const int D = C / heads;
-  if (L % KT != 0 || L < 512) return false;
-  if (D == 16) {
+// The kernel that splits into bf16 triples in its loop.  Precondition (HDIFF_MHA_FWD_ROUTE_X3_TRIPLES): d_head 16 or 32, L a
+// multiple of 64 and at least 512.
+void launch_mha_fwd_x3(const float* qkv, float* o, float* lse2, int B, int C, int heads, int L, float qscale, hipStream_t stream) {
+  if (C / heads == 16)
     hipLaunchKernelGGL((mha_flash_fwd_x3_kernel<16, 4>), dim3(cdiv(L, 256), heads, B), dim3(THREADS), 0, stream, qkv, nullptr, o, lse2, C, L, qscale);
-    return true;
-  }
-  if (D == 32) {
+  else
     hipLaunchKernelGGL((mha_flash_fwd_x3_kernel<32, 2>), dim3(cdiv(L, 128), heads, B), dim3(THREADS), 0, stream, qkv, nullptr, o, lse2, C, L, qscale);
-    return true;
-  }
-  return false;
 }
 
 }  // namespace hdiff

@@ -310,15 +310,13 @@ int64_t mha_fwd_x3p_workspace(int B, int C, int heads, int L) {
   return (int64_t)B * C * L * F_COUNT * 2 + mha_fwd_h2_tail_bytes(B, C);      // F_COUNT fp16 slots of L * D per (sample, head)
 }
 
-// The d_head 32 forward on the pre-split fp16 operands.  Returns false when the shape is not covered or the workspace is missing.
-bool launch_mha_fwd_x3p(const float* qkv, float* o, float* lse2, int B, int C, int heads, int L, float qscale, void* ws,
-                        int64_t ws_bytes, hipStream_t stream) {
-  const int64_t need = mha_fwd_x3p_workspace(B, C, heads, L);
-  if (need == 0 || ws == nullptr || ws_bytes < need || C / heads != 32) return false;
+// The d_head 32 forward on the pre-split fp16 operands.
+// Precondition (HDIFF_MHA_FWD_ROUTE_X3P_PAIRS): d_head 32 and ws holds mha_fwd_x3p_workspace bytes, non-zero for this shape.
+void launch_mha_fwd_x3p(const float* qkv, float* o, float* lse2, int B, int C, int heads, int L, float qscale, void* ws,
+                        hipStream_t stream) {
   launch_qk_split_h2(qkv, ws, B, C, heads, L, qscale, stream);
   launch_v_split_h2(qkv, ws, B, C, heads, L, stream);
   hipLaunchKernelGGL(mha_flash_fwd_x3p_kernel, dim3(L / 256, heads, B), dim3(THREADS), 0, stream, (const __bf16*)ws, o, lse2, C, L, 1.0f);
-  return true;
 }
 
 }  // namespace hdiff

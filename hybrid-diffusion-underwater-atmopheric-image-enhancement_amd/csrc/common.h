@@ -6,6 +6,8 @@
 #include <stdio.h>
 #include <string.h>
 
+#include <type_traits>
+
 #include "../../include/hdiff.h"
 
 namespace hdiff {
@@ -55,28 +57,51 @@ int contraction_mode();   // HDIFF_CONTRACT_*
 // the split-operand family is on (bf16x3, and f16, which is bf16x3 everywhere but in one attention-forward dispatch)
 inline bool split_operands_on() { return contraction_mode() != HDIFF_CONTRACT_F32; }
 
-// attention_bwd_h2.hip: the attention backward at d_head 16 / 32 in the split-operand mode (dispatched from attention_bwd.hip)
+// The head dims the attention kernels are instantiated for, and f(std::integral_constant<int, D>) for one of them
+static inline bool mha_head_dim_ok(int D) { return D == 4 || D == 8 || D == 12 || D == 16 || D == 24 || D == 32 || D == 48 || D == 64; }
+template <class F>
+static inline void with_head_dim(int D, F&& f) {
+  switch (D) {
+    case 4: return f(std::integral_constant<int, 4>{});
+    case 8: return f(std::integral_constant<int, 8>{});
+    case 12: return f(std::integral_constant<int, 12>{});
+    case 16: return f(std::integral_constant<int, 16>{});
+    case 24: return f(std::integral_constant<int, 24>{});
+    case 32: return f(std::integral_constant<int, 32>{});
+    case 48: return f(std::integral_constant<int, 48>{});
+    case 64: return f(std::integral_constant<int, 64>{});
+  }
+}
+
+// Attention backward: the key blocks of a (sample, head) pair cut into `want` ranges at most: blocks per range, and ranges (none empty)
+struct KeyRanges { int per, nsplit; };
+static inline KeyRanges key_ranges(int nkb_total, int want) {
+  if (want > nkb_total) want = nkb_total;
+  if (want < 1) want = 1;
+  const int per = cdiv(nkb_total, want);
+  return {per, cdiv(nkb_total, per)};
+}
+// attention_bwd_h2.hip: the attention backward at d_head 16 / 32 in the split-operand mode.  mha_bwd_route (attention_bwd.hip) decides
+// whether it runs; nothing here looks at the contraction mode.
 long long mha_bwd_slab_cap_bytes();                          // upper bound on the dQ partial slabs (HDIFF_BWD_SLAB_GIB)
-bool mha_bwd_x3_shape_ok(int B, int C, int heads, int L);     // the shape alone (mode-independent)
-bool mha_bwd_x3_applicable(int B, int C, int heads, int L);   // shape AND the bf16x3 contraction mode
+bool mha_bwd_x3_shape_ok(int B, int C, int heads, int L);     // the shapes it covers
+KeyRanges mha_bwd_h2_key_ranges(int B, int heads, int L, int D);
 int64_t mha_bwd_x3_workspace_floats(int B, int C, int heads, int L);   // dQ slabs + piece tensors + maxima
-bool launch_mha_bwd_h2(const float* qkv, const float* d_o, const float* lse2, const float* delta, float* dqkv, float* ws, int B,
-                       int C, int heads, int L, hipStream_t stream);
+bool mha_bwd_h2_lds_granted();                                // asks the current device for the kernels' LDS size (once per device)
+void launch_mha_bwd_h2(const float* qkv, const float* d_o, const float* lse2, const float* delta, float* dqkv, float* ws, int B,
+                       int C, int heads, int L, KeyRanges g, hipStream_t stream);
 // Attention forward in the split-operand mode.  attention_x3p.hip: d_head 32 on operands split ONCE into a workspace (fp16 pairs;
 // 0 bytes = shape not covered); attention_h2.hip: d_head 16 likewise, and the split passes of both; attention_x3.hip: the kernel that
-// splits in its loop (bf16 triples), for calls without a workspace.  Each returns false when the shape is not covered / no workspace.
+// splits in its loop (bf16 triples), for calls without a workspace; attention_f16.hip: the inference forward of the f16 mode, every
+// operand ONE fp16 piece, inside the same workspace.  mha_fwd_route (attention.hip) decides which one runs: the launchers check
+// nothing, each names its precondition where it is defined.
 int64_t mha_fwd_x3p_workspace(int B, int C, int heads, int L);
 int64_t mha_fwd_h2_tail_bytes(int B, int C);      // bytes behind the pairs of the workspace (Q / K row maxima)
-bool launch_mha_fwd_x3p(const float* qkv, float* o, float* lse2, int B, int C, int heads, int L, float qscale, void* ws,
-                        int64_t ws_bytes, hipStream_t stream);
-bool launch_mha_fwd_h2(const float* qkv, float* o, float* lse2, int B, int C, int heads, int L, float qscale, void* ws,
-                       int64_t ws_bytes, hipStream_t stream);
+void launch_mha_fwd_x3p(const float* qkv, float* o, float* lse2, int B, int C, int heads, int L, float qscale, void* ws, hipStream_t stream);
+void launch_mha_fwd_h2(const float* qkv, float* o, float* lse2, int B, int C, int heads, int L, float qscale, void* ws, hipStream_t stream);
 void launch_qk_split_h2(const float* qkv, void* ws, int B, int C, int heads, int L, float qscale, hipStream_t stream);   // Q, K as fp16 score operands
 void launch_v_split_h2(const float* qkv, void* ws, int B, int C, int heads, int L, hipStream_t stream);                  // V as fp16 pairs, d_head 16 / 32
-bool launch_mha_fwd_x3(const float* qkv, float* o, float* lse2, int B, int C, int heads, int L, float qscale, hipStream_t stream);
-// attention_f16.hip: the inference forward of the f16 mode, d_head 16 / 32, every operand ONE fp16 piece, inside the same workspace.
-// Returns false (nothing launched) unless lse2 == NULL, the shape is covered and the workspace is there.
-bool launch_mha_fwd_f16(const float* qkv, float* o, float* lse2, int B, int C, int heads, int L, float qscale, void* ws,
-                        int64_t ws_bytes, hipStream_t stream);
+void launch_mha_fwd_x3(const float* qkv, float* o, float* lse2, int B, int C, int heads, int L, float qscale, hipStream_t stream);
+void launch_mha_fwd_f16(const float* qkv, float* o, int B, int C, int heads, int L, float qscale, void* ws, hipStream_t stream);
 
 }  // namespace hdiff

@@ -29,6 +29,7 @@ from . import _capi
 GN_GROUPS = 32      # ModelCondition.py:170,184,249
 GN_EPS = 1e-5
 NUM_HEADS = 8       # ModelCondition.py:189
+FLASH_MAX_HEAD = 64 # widest head of hdiff_mha_flash_fwd; AttnBlock's single head of width C beyond it runs hdiff_mha_wide_fwd
 
 
 RESERVE_SPLIT_WORKSPACE = True      # plans reserve the split-operand attention scratch (Plan.attention_workspace); hdiff_amd.reserve_split_workspace
@@ -404,6 +405,15 @@ class Plan:
         _capi.check(self.lib.hdiff_mha_flash_fwd_workspace(B, Cc, heads, L, C.byref(need)), "mha_flash_fwd_workspace")
         return self.buf((need.value + 3) // 4) if need.value > 0 else None
 
+    def flash_attention(self, qkv: torch.Tensor, o: torch.Tensor, B: int, Cc: int, heads: int, L: int) -> None:
+        """hdiff_mha_flash_fwd_ws without a log-sum-exp, on scratch that goes back to the pool behind the call."""
+        ws = self.attention_workspace(B, Cc, heads, L)
+        self.call("hdiff_mha_flash_fwd_ws", qkv.data_ptr(), o.data_ptr(), None, B, Cc, heads, L, _ptr(ws),
+                  C.c_int64(0 if ws is None else ws.numel() * 4))
+        self.keep(ws)
+        if ws is not None:
+            self.free(ws)
+
     def gn_scale_shift(self, x0: torch.Tensor, x1: Optional[torch.Tensor], gamma: torch.Tensor, beta: torch.Tensor,
                        B: int, HW: int) -> Tuple[torch.Tensor, torch.Tensor]:
         C0 = int(x0.shape[1])
@@ -521,14 +531,10 @@ def emit_mha(plan: Plan, P: Dict[str, torch.Tensor], p: str, h: torch.Tensor, B:
     qkv = plan.buf(B, 3 * Cc, H, W)
     plan.conv(h, None, pk_in, P[f"{p}.attn.in_proj_bias"], qkv, B=B, H=H, W=W, VH=H, VW=W)
     o = plan.buf(B, Cc, H, W)
-    ws = plan.attention_workspace(B, Cc, NUM_HEADS, H * W)
-    plan.call("hdiff_mha_flash_fwd_ws", qkv.data_ptr(), o.data_ptr(), None, B, Cc, NUM_HEADS, H * W, _ptr(ws),
-              C.c_int64(0 if ws is None else ws.numel() * 4))
+    plan.flash_attention(qkv, o, B, Cc, NUM_HEADS, H * W)
     plan.flops += 4.0 * (H * W) ** 2 * Cc * B
-    plan.keep((qkv, o, ws))
+    plan.keep((qkv, o))
     plan.free(qkv)
-    if ws is not None:
-        plan.free(ws)
     y = plan.buf(B, Cc, H, W)
     plan.conv(o, None, pk_out, P[f"{p}.attn.out_proj.bias"], y, B=B, H=H, W=W, VH=H, VW=W, absmax_out=absmax_out)
     plan.free(o)
@@ -553,13 +559,8 @@ def emit_attn_block(plan: Plan, P: Dict[str, torch.Tensor], p: str, x: torch.Ten
     plan.conv(hn, None, pk_in, b_qkv, qkv, B=B, H=H, W=W, VH=H, VW=W)
     plan.free(hn)
     o = plan.buf(B, Cc, H, W)
-    if Cc <= 64:
-        ws = plan.attention_workspace(B, Cc, 1, L)
-        plan.call("hdiff_mha_flash_fwd_ws", qkv.data_ptr(), o.data_ptr(), None, B, Cc, 1, L, _ptr(ws),     # one head of width C
-                  C.c_int64(0 if ws is None else ws.numel() * 4))
-        plan.keep(ws)
-        if ws is not None:
-            plan.free(ws)
+    if Cc <= FLASH_MAX_HEAD:
+        plan.flash_attention(qkv, o, B, Cc, 1, L)      # one head of width C
     else:
         plan.call("hdiff_mha_wide_fwd", qkv.data_ptr(), o.data_ptr(), B, Cc, L)
     plan.flops += 4.0 * L * L * Cc * B

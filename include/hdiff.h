@@ -319,6 +319,21 @@ int hdiff_mha_flash_fwd(const float* qkv, float* o, float* lse2 /*[B][heads][L] 
 int hdiff_mha_flash_fwd_workspace(int B, int C, int heads, int L, int64_t* bytes_out);
 int hdiff_mha_flash_fwd_ws(const float* qkv, float* o, float* lse2 /*[B][heads][L] or NULL*/, int B, int C, int heads, int L,
                            void* ws, int64_t ws_bytes, hdiff_stream_t stream);
+/* Which program the two forward entries run a call on, in the contraction mode of the moment (hdiff_mha_flash_fwd: ws_bytes = 0).
+ * Host only: nothing is launched, no device is needed.  The validation of the launching entries applies, with their messages; a
+ * refused call writes nothing.  *nq_out: query tiles of 16 per wave of mha_flash_fwd_kernel wherever it runs, as main kernel or
+ * as check pass (1 or 4); *check_out = 1: it follows the route's kernel in check mode and redoes the query blocks that kernel
+ * flagged (the HDIFF_NO_CHECK_PASS developer knob suppresses that launch, not this answer). */
+enum {
+  HDIFF_MHA_FWD_ROUTE_RUNNING_MAX = 0, /* mha_flash_fwd_kernel<D, nq> alone (check = 0) */
+  HDIFF_MHA_FWD_ROUTE_FAST_F32 = 1,    /* mha_flash_fwd_fast_kernel<D, 4>, then the check pass */
+  HDIFF_MHA_FWD_ROUTE_X3_TRIPLES = 2,  /* mha_flash_fwd_x3_kernel (splits in its loop), then the check pass */
+  HDIFF_MHA_FWD_ROUTE_H2_PAIRS = 3,    /* d_head 16 on the pre-split workspace, then the check pass */
+  HDIFF_MHA_FWD_ROUTE_X3P_PAIRS = 4,   /* d_head 32 on the pre-split workspace, then the check pass */
+  HDIFF_MHA_FWD_ROUTE_F16_SINGLE = 5   /* f16 mode, no log-sum-exp, single fp16 pieces, then the check pass */
+};
+int hdiff_mha_flash_fwd_route(int B, int C, int heads, int L, int want_lse, int64_t ws_bytes, int* route_out, int* nq_out,
+                              int* check_out);
 /* Single-head attention with a head wider than 64 channels: softmax(q k^T * C^-1/2) v with d_head = C, the core of the
  * reference's AttnBlock (ModelCondition.py:109-116; dead code there, built for completeness: one workgroup per query row,
  * L + C floats of LDS).  qkv [B][3C][L] rows [q | k | v], o [B][C][L].  Heads of width <= 64: hdiff_mha_flash_fwd, heads = 1. */
@@ -338,6 +353,16 @@ int hdiff_mha_wide_bwd(const float* qkv, const float* d_o, float* dqkv, float* w
 int hdiff_mha_flash_bwd_workspace(int B, int C, int heads, int L, int64_t* n_floats);
 int hdiff_mha_flash_bwd(const float* qkv, const float* o, const float* d_o, const float* lse2, float* delta, float* dqkv,
                         float* ws, int B, int C, int heads, int L, hdiff_stream_t stream);
+/* Which kernels hdiff_mha_flash_bwd runs a call on, in the contraction mode of the moment.  Host only, validated like that entry;
+ * a refused call writes nothing.  *nk_out: key tiles of 16 per wave (1, 2 or 4; 0 on H2_PAIRS); *aligned_out = 0: the
+ * bounds-checked <D, 1, false> kernel; *nsplit_out: key ranges per (sample, head) pair (HDIFF_BWD_SLAB_GIB bounds it on H2_PAIRS).
+ * Not modelled: a device that refuses the H2_PAIRS kernels' 70 KB of LDS (no MI355X does) runs FUSED_F32 on the answer the
+ * fp32 mode gets. */
+enum {
+  HDIFF_MHA_BWD_ROUTE_FUSED_F32 = 0,   /* mha_bwd_fused_kernel<D, nk, aligned> (+ mha_dq_reduce_kernel when nsplit > 1) */
+  HDIFF_MHA_BWD_ROUTE_H2_PAIRS = 1     /* absmax + split + mha_bwd_h2p_kernel (d 16) / mha_bwd_h2_kernel<32> (d 32) + its reduce */
+};
+int hdiff_mha_flash_bwd_route(int B, int C, int heads, int L, int* route_out, int* nk_out, int* aligned_out, int* nsplit_out);
 
 /* ------------------------------------------------------------------------------------------------------------------
  * Small dense layers (K6, K10).  y[b][j] (+)= bias[j] + sum_k W[j][k] * f(x_row(b)[k]),  f = identity or Swish.

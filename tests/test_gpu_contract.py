@@ -315,3 +315,46 @@ def test_reserve_split_workspace_opt_out():
         hdiff_amd.reserve_split_workspace(True)
         hdiff_amd.set_contraction_mode(before)
         assert engine.RESERVE_SPLIT_WORKSPACE is True
+
+
+def test_attention_routes_of_a_plan_with_and_without_the_workspace():
+    """Which kernel each recorded attention call of the opt-out test's model runs, asked of the library (hdiff_mha_flash_fwd_route) with the
+    call's own (B, C, heads, L, no log-sum-exp, bytes) in each contraction mode.  The model has one attention at 32 x 32 (L = 1024, heads
+    of 16 channels) and two at 16 x 16 (L = 256: the running-max kernel in every mode).  With the workspace the L = 1024 call runs the
+    fp16-pair kernel (the single-piece one in the f16 mode); in the plan built after reserve_split_workspace(False) it runs the kernel that
+    splits in its loop.  Source of the expected routes: the predicate cascade that hdiff_mha_flash_fwd_route replaced, copied from the
+    commit before it into a one-off harness and run on these arguments (tests/test_attention_route_cpu.py holds the same rows)."""
+    import collections
+    import hdiff_amd
+    from hdiff_amd.DiffusionFreeGuidence.ModelCondition import UNet
+    RUNNING_MAX, FAST_F32, X3_TRIPLES, H2_PAIRS, X3P_PAIRS, F16_SINGLE = range(6)
+    cfg = dict(T=4, num_labels=2, ch=128, ch_mult=[1, 1], num_res_blocks=1, dropout=0.0)
+    lib = _capi.lib()
+
+    def histogram(plan, mode):
+        hdiff_amd.set_contraction_mode(mode)
+        seen = collections.Counter()
+        for name, _, a in plan.ops:
+            if name != "hdiff_mha_flash_fwd_ws":
+                continue
+            route, nq, check = C.c_int(-1), C.c_int(-1), C.c_int(-1)
+            _capi.check(lib.hdiff_mha_flash_fwd_route(a[3], a[4], a[5], a[6], 0, a[8].value, C.byref(route), C.byref(nq), C.byref(check)))
+            assert (nq.value, check.value) == ((1, 0) if route.value == RUNNING_MAX else (4, 1))
+            seen[route.value] += 1
+        return dict(seen)
+
+    before = hdiff_amd.get_contraction_mode()
+    try:
+        torch.manual_seed(0)
+        with_ws = UNet(**cfg).eval().to(DEV).plan_for(2, 32, 32, torch.device(DEV)).plan
+        assert histogram(with_ws, "bf16x3") == {H2_PAIRS: 1, RUNNING_MAX: 2}
+        assert histogram(with_ws, "f16") == {F16_SINGLE: 1, RUNNING_MAX: 2}
+        assert histogram(with_ws, "f32") == {FAST_F32: 1, RUNNING_MAX: 2}
+        hdiff_amd.reserve_split_workspace(False)
+        lean = UNet(**cfg).eval().to(DEV).plan_for(2, 32, 32, torch.device(DEV)).plan
+        assert histogram(lean, "bf16x3") == {X3_TRIPLES: 1, RUNNING_MAX: 2}
+        assert histogram(lean, "f16") == {X3_TRIPLES: 1, RUNNING_MAX: 2}
+        assert histogram(lean, "f32") == {FAST_F32: 1, RUNNING_MAX: 2}
+    finally:
+        hdiff_amd.reserve_split_workspace(True)
+        hdiff_amd.set_contraction_mode(before)

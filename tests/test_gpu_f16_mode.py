@@ -21,7 +21,7 @@ sys.path.insert(0, HERE)
 import hdiff_amd  # noqa: E402
 from hdiff_amd import _capi  # noqa: E402
 import _f16_attention_emul as EM  # noqa: E402
-from test_gpu_ops import _flash, _h2_case, run_conv  # noqa: E402
+from test_gpu_ops import MHA_H2_PAIRS, MHA_X3P_PAIRS, _flash, _flash_route, _h2_case, run_conv  # noqa: E402
 
 DEV = "cuda:0"
 GOLDEN = os.path.join(HERE, "golden")
@@ -133,6 +133,7 @@ def test_f16_is_another_program(d, f16_mode):
     o16, _ = _flash(lib, qkv, 8, workspace=True)
     ox3, _ = _in_mode("bf16x3", lambda: _flash(lib, qkv, 8, workspace=True))
     assert hdiff_amd.get_contraction_mode() == "f16"
+    assert _flash_route(lib, qkv, 8, workspace=True) == 5      # HDIFF_MHA_FWD_ROUTE_F16_SINGLE
     assert not torch.equal(o16, ox3)
     ref = EM.exact(qkv.to(DEV), 8)
     e16, ex3 = EM.errors(o16, ref)[0], EM.errors(ox3, ref)[0]
@@ -148,6 +149,7 @@ def test_f16_forward_with_lse_is_the_default_forward(d, f16_mode):
     o16, l16 = _flash(lib, qkv, 8, want_lse=True, workspace=True)
     ox3, lx3 = _in_mode("bf16x3", lambda: _flash(lib, qkv, 8, want_lse=True, workspace=True))
     assert torch.equal(o16, ox3) and torch.equal(l16, lx3)
+    assert _flash_route(lib, qkv, 8, want_lse=True, workspace=True) == (MHA_H2_PAIRS if d == 16 else MHA_X3P_PAIRS)
     assert not torch.equal(o16, _flash(lib, qkv, 8, workspace=True)[0])          # ... and without the lse the mode does act
 
 

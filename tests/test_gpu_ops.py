@@ -319,6 +319,20 @@ def _flash(lib, qkv, heads, want_lse=False, workspace=False):
     return o, lse
 
 
+def _flash_route(lib, qkv, heads, want_lse=False, workspace=False):
+    """HDIFF_MHA_FWD_ROUTE_* of the call _flash makes with these arguments, in the mode of the moment."""
+    B, C3, L = qkv.shape
+    need = C.c_int64(0)
+    if workspace:
+        _capi.check(lib.hdiff_mha_flash_fwd_workspace(B, C3 // 3, heads, L, C.byref(need)), "mha ws query")
+    route, nq, check = C.c_int(-1), C.c_int(-1), C.c_int(-1)
+    _capi.check(lib.hdiff_mha_flash_fwd_route(B, C3 // 3, heads, L, int(want_lse), need.value, C.byref(route), C.byref(nq), C.byref(check)), "mha route")
+    return route.value
+
+
+MHA_FAST_F32, MHA_X3_TRIPLES, MHA_H2_PAIRS, MHA_X3P_PAIRS = 1, 2, 3, 4      # HDIFF_MHA_FWD_ROUTE_* (include/hdiff.h)
+
+
 @pytest.mark.parametrize("workspace", [False, True], ids=["split-in-loop", "pre-split"])
 @pytest.mark.parametrize("d,L,B,scale", [(16, 1024, 2, 1.0), (16, 4096, 1, 3.0), (32, 2048, 1, 1.0), (32, 512, 2, 2.0)])
 def test_flash_attention_split_bf16_is_fp32_class(d, L, B, scale, workspace, bf16x3_mode):
@@ -335,9 +349,12 @@ def test_flash_attention_split_bf16_is_fp32_class(d, L, B, scale, workspace, bf1
         # with a workspace other programs run: d_head 32 the 32x32x16 kernel on pre-split bf16 triples, d_head 16 the
         # fp16-pair P.V kernel (attention_h2.hip) -- other pieces, other summation order, so other bits
         assert not torch.equal(o_x3, _flash(lib, qkv, heads)[0]), "the workspace path did not run its own kernel"
+        assert _flash_route(lib, qkv, heads, workspace=True) == (MHA_H2_PAIRS if d == 16 else MHA_X3P_PAIRS)
+    assert _flash_route(lib, qkv, heads) == MHA_X3_TRIPLES
     assert lib.hdiff_get_contraction_mode() == 1
     _capi.check(lib.hdiff_set_contraction_mode(0))
     o_f32, _ = _flash(lib, qkv, heads)
+    assert _flash_route(lib, qkv, heads) == MHA_FAST_F32 and _flash_route(lib, qkv, heads, workspace=True) == MHA_FAST_F32
     _capi.check(lib.hdiff_set_contraction_mode(1))
     assert not torch.equal(o_x3, o_f32), "the split-bf16 kernel did not run"
     close(o_x3, ref.float(), rel=2e-5, abs_=2e-6, what=f"split-bf16 d={d} L={L}")
@@ -383,6 +400,7 @@ def test_flash_attention_fp16_pairs_moving_reference_and_ranges(name, d, bf16x3_
     g = torch.Generator().manual_seed({"ramp": 1, "peaked": 2, "late-spikes": 3, "wide-v": 4, "tiny-v": 5, "quiet-neighbour": 6}[name])
     qkv = _h2_case(name, d, L, g)
     assert not torch.equal(_flash(lib, qkv, heads, workspace=True)[0], _flash(lib, qkv, heads)[0]), "the workspace path did not run its own kernel"
+    assert _flash_route(lib, qkv, heads, want_lse=True, workspace=True) == (MHA_H2_PAIRS if d == 16 else MHA_X3P_PAIRS)
     ref = attention_core_ref(qkv, heads).double()
     o_h2, lse = _flash(lib, qkv, heads, want_lse=True, workspace=True)
     _capi.check(lib.hdiff_set_contraction_mode(0))
