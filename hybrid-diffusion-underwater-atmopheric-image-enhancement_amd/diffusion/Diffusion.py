@@ -13,6 +13,11 @@ Kept as written in the reference, on purpose:
   * DDIM lays its time steps over a literal 1000 and reads ``alphas_bar[t + 1]`` (:243-251); ``eta = 0`` makes the
     per-step ``c1 * randn`` term an exact zero (:260-263).
 
+Added to the reference's surface: ``forward(..., tile=, tile_overlap=, tile_batch=)`` samples an image of any size through
+overlapping model-sized windows (``tile_origins`` / ``tile_weights`` give the layout): every window is denoised at every step,
+the noise estimates are blended where they overlap and ONE DDIM update is applied to the full image
+(``csrc/tile_ops.hip``).  Without ``tile`` nothing changes.
+
 Trainer underneath: q_sample and the 3 + 3 channel concat are HIP launches, the DynamicUNet runs its autograd path
 (``autograd.dyn_unet_forward_with_grad``) and the loss tail -- the squared error, ``y_0_pred`` and the angular-colour term,
 and their joint backward -- is one fused kernel pair (``csrc/train_b_ops.hip``).  The reference's two further terms are passed in as
@@ -35,7 +40,7 @@ from .. import _capi
 from .. import engine as E
 from ..DiffusionFreeGuidence.DiffusionCondition import _gpu_input, _timesteps
 
-__all__ = ["extract", "GaussianDiffusionTrainer", "GaussianDiffusionSampler"]
+__all__ = ["extract", "GaussianDiffusionTrainer", "GaussianDiffusionSampler", "tile_origins", "tile_weights"]
 
 
 def extract(v, t, x_shape):
@@ -143,6 +148,84 @@ class GaussianDiffusionTrainer(nn.Module):
         return [loss, mse_loss, perceptual_dino, msssim, col_loss]
 
 
+def _int_arg(name: str, v, lo: int) -> int:
+    if isinstance(v, bool) or not isinstance(v, int):
+        raise ValueError(f"{name} must be an integer, got {v!r}")
+    if v < lo:
+        raise ValueError(f"{name} must be >= {lo}, got {v}")
+    return int(v)
+
+
+def _tile_args(size, tile, overlap):
+    size, tile, overlap = _int_arg("size", size, 1), _int_arg("tile", tile, 1), _int_arg("tile_overlap", overlap, 0)
+    if overlap > tile // 2:
+        raise ValueError(f"tile_overlap must be in [0, tile // 2] = [0, {tile // 2}], got {overlap}")
+    return size, tile, overlap
+
+
+def tile_origins(size: int, tile: int, overlap: int) -> List[int]:
+    """Origins of the windows of length ``min(tile, size)`` along an axis of ``size`` positions: ``[0]`` if one window covers
+    the axis, else ``0, s, 2s, ...`` with ``s = tile - overlap`` while the window ends before the axis does, then a last window
+    flush with the end, at ``size - tile``.  Strictly increasing; at most 3 windows cover a position."""
+    size, tile, overlap = _tile_args(size, tile, overlap)
+    if size <= tile:
+        return [0]
+    s, origins, o = tile - overlap, [], 0
+    while o + tile < size:
+        origins.append(o)
+        o += s
+    origins.append(size - tile)
+    return origins
+
+
+def tile_weights(size: int, tile: int, overlap: int):
+    """-> (first[int32, size], count[int32, size], weight[float64, size, 3]): position p is covered by the consecutive windows
+    ``first[p] .. first[p] + count[p] - 1`` of ``tile_origins`` with the weights ``weight[p, :count[p]]`` (the rest is 0), which
+    sum to 1.  The profile over a window of length t is ``w(i) = min(i + 1, t - i, max(overlap, 1))`` -- a linear cross-fade
+    across a regular overlap -- normalised over the covering windows in float64 (the sampler casts it to fp32 once)."""
+    origins = tile_origins(size, tile, overlap)
+    size, tile, overlap = _tile_args(size, tile, overlap)
+    t = min(tile, size)
+    cap = max(overlap, 1)
+    first = torch.zeros(size, dtype=torch.int32)
+    count = torch.zeros(size, dtype=torch.int32)
+    weight = torch.zeros(size, 3, dtype=torch.float64)
+    lo = 0
+    for p in range(size):
+        while origins[lo] + t <= p:                      # origins increase: the first covering window only moves forward
+            lo += 1
+        ws = []
+        k = lo
+        while k < len(origins) and origins[k] <= p:
+            i = p - origins[k]
+            ws.append(min(i + 1, t - i, cap))
+            k += 1
+        if not 1 <= len(ws) <= 3:
+            raise AssertionError(f"position {p} of {size} is covered by {len(ws)} windows (tile {tile}, overlap {overlap})")
+        w = torch.tensor(ws, dtype=torch.float64)
+        first[p], count[p] = lo, len(ws)
+        weight[p, :len(ws)] = w / w.sum()
+    return first, count, weight
+
+
+def _ddim_tables(sampler: "GaussianDiffusionSampler", ddim_step: int, device):
+    """-> (tab[n, 4] fp32, t_tab[n] int32), indexed by the down-counting step counter k (k = n - 1 first): the same fp32 ops as
+    the reference's :250-262."""
+    step = int(1000 / ddim_step)                                                           # :243-247
+    seq = list(range(0, 1000, step))
+    seq_next = [-1] + seq[:-1]
+    ab = sampler.alphas_bar
+    if seq[-1] + 1 >= ab.shape[0]:
+        raise RuntimeError(f"index {seq[-1] + 1} is out of bounds for dimension 0 with size {ab.shape[0]}")
+    ab = ab.to(device)
+    at = ab[torch.tensor(seq, device=device) + 1].float()
+    at_next = ab[torch.tensor(seq_next, device=device) + 1].float()
+    c1 = 0 * ((1 - at / at_next) * (1 - at_next) / (1 - at)).sqrt()
+    c2 = ((1 - at_next) - c1 ** 2).sqrt()
+    tab = torch.stack([(1 - at).sqrt(), at.sqrt(), at_next.sqrt(), c2], dim=1).contiguous()
+    return tab, torch.tensor(seq, dtype=torch.int32, device=device)
+
+
 class _StepPlan:
     """One captured sampling step for a fixed (B, H, W) and mode: fill t -> DynamicUNet -> update -> advance the counter."""
 
@@ -174,21 +257,8 @@ class _StepPlan:
                    self.sigma.data_ptr(), self.step.data_ptr(), int(sampler.T), C.c_double(0.0), C.c_uint64(seed),
                    self.nan_flag.data_ptr(), n)
         else:
-            step = int(1000 / ddim_step)                                                           # :243-247
-            seq = list(range(0, 1000, step))
-            seq_next = [-1] + seq[:-1]
-            ab = sampler.alphas_bar
-            if seq[-1] + 1 >= ab.shape[0]:
-                raise RuntimeError(f"index {seq[-1] + 1} is out of bounds for dimension 0 with size {ab.shape[0]}")
-            ab = ab.to(device)
-            # tables indexed by the down-counting step counter k (k = len-1 first): same fp32 ops as :250-262
-            at = ab[torch.tensor(seq, device=device) + 1].float()
-            at_next = ab[torch.tensor(seq_next, device=device) + 1].float()
-            c1 = 0 * ((1 - at / at_next) * (1 - at_next) / (1 - at)).sqrt()
-            c2 = ((1 - at_next) - c1 ** 2).sqrt()
-            self.tab = torch.stack([(1 - at).sqrt(), at.sqrt(), at_next.sqrt(), c2], dim=1).contiguous()
-            self.t_tab = torch.tensor(seq, dtype=torch.int32, device=device)
-            self.n_steps = len(seq)
+            self.tab, self.t_tab = _ddim_tables(sampler, ddim_step, device)
+            self.n_steps = int(self.t_tab.numel())
             p.call("hdiff_fill_from_table", up.t.data_ptr(), self.t_tab.data_ptr(), self.step.data_ptr(), self.n_steps, B)
             p.ops.extend(up.plan.ops)
             p.call("hdiff_ddim_step", up.y.data_ptr(), up.out.data_ptr(), up.y.data_ptr(), self.tab.data_ptr(),
@@ -197,9 +267,65 @@ class _StepPlan:
         self.plan = p
 
 
+class _TiledStepPlan:
+    """One captured DDIM step over overlapping windows for a fixed (B, H, W, tile, overlap, tile_batch): fill t -> per chunk of
+    windows [gather cond, gather y, DynamicUNet, store eps] -> blend + update on the full image -> advance the counter.
+
+    Every chunk runs the SAME window plan at batch ``n_slots``; a short final chunk is padded with repeats of the last window,
+    whose estimates are not stored.  With a single chunk the blend reads the plan's output directly."""
+
+    def __init__(self, sampler: "GaussianDiffusionSampler", B: int, H: int, W: int, device, ddim_step: int, tile: int,
+                 overlap: int, tile_batch: Optional[int]):
+        th, tw = min(tile, H), min(tile, W)
+        oy, ox = tile_origins(H, tile, overlap), tile_origins(W, tile, overlap)
+        ny, nx = len(oy), len(ox)
+        n_windows = B * ny * nx
+        n_slots = n_windows if tile_batch is None else min(tile_batch, n_windows)
+        self.unet = sampler.model.plan_for(n_slots, th, tw, device, True)
+        up = self.unet
+        if up.out_hw != (th, tw):
+            raise RuntimeError(f"The size of tensor a ({tw}) must match the size of tensor b ({up.out_hw[1]}) at non-singleton "
+                               "dimension 3")
+        self.B, self.n = B, B * 3 * H * W
+        self.ny, self.nx, self.th, self.tw, self.n_windows, self.n_slots = ny, nx, th, tw, n_windows, n_slots
+        self.chunks = [(w0, min(n_slots, n_windows - w0)) for w0 in range(0, n_windows, n_slots)]
+        self.step = torch.zeros(1, dtype=torch.int32, device=device)
+        self.nan_flag = torch.zeros(1, dtype=torch.int32, device=device)
+        self.y = torch.empty(B, 3, H, W, device=device)
+        self.cond = torch.empty(B, 3, H, W, device=device)
+        self.eps = up.out if len(self.chunks) == 1 else torch.empty(n_windows, 3, th, tw, device=device)
+        i32 = dict(dtype=torch.int32, device=device)
+        self.oy, self.ox, self.zero = torch.tensor(oy, **i32), torch.tensor(ox, **i32), torch.zeros(1, **i32)
+        fy, cy, wy = tile_weights(H, tile, overlap)
+        fx, cx, wx = tile_weights(W, tile, overlap)
+        self.fy, self.cy, self.wy = fy.to(device), cy.to(device), wy.float().to(device).contiguous()    # fp32 cast: once, here
+        self.fx, self.cx, self.wx = fx.to(device), cx.to(device), wx.float().to(device).contiguous()
+        self.tab, self.t_tab = _ddim_tables(sampler, ddim_step, device)
+        self.n_steps = int(self.t_tab.numel())
+        p = E.Plan(device)
+        p.call("hdiff_fill_from_table", up.t.data_ptr(), self.t_tab.data_ptr(), self.step.data_ptr(), self.n_steps, n_slots)
+        for w0, valid in self.chunks:
+            for src, dst in ((self.cond, up.cond), (self.y, up.y)):
+                p.call("hdiff_tile_gather", src.data_ptr(), dst.data_ptr(), self.oy.data_ptr(), self.ox.data_ptr(), B, 3, H, W,
+                       ny, nx, th, tw, w0, n_slots)
+            p.ops.extend(up.plan.ops)
+            if self.eps is not up.out:
+                # the plan's output is reused by the next chunk: keep this chunk's estimates (a gather whose windows are whole
+                # samples is a copy; the padding slots are left behind)
+                p.call("hdiff_tile_gather", up.out.data_ptr(), self.eps[w0].data_ptr(), self.zero.data_ptr(),
+                       self.zero.data_ptr(), n_slots, 3, th, tw, 1, 1, th, tw, 0, valid)
+        p.call("hdiff_tile_ddim_step", self.y.data_ptr(), self.eps.data_ptr(), self.fy.data_ptr(), self.cy.data_ptr(),
+               self.wy.data_ptr(), self.oy.data_ptr(), self.fx.data_ptr(), self.cx.data_ptr(), self.wx.data_ptr(),
+               self.ox.data_ptr(), self.tab.data_ptr(), self.step.data_ptr(), self.n_steps, self.nan_flag.data_ptr(), B, 3, H, W,
+               ny, nx, th, tw)
+        p.call("hdiff_step_decrement", self.step.data_ptr())
+        self.plan = p
+
+
 class GaussianDiffusionSampler(nn.Module):
     """forward(input_image, ddim=False, unconditional_guidance_scale=1, ddim_step=None) -> enhanced image clipped to [-1, 1]
-    (reference diffusion/Diffusion.py:182-269).  ``input_image`` is in [0, 255] (divided by 255 here, as there)."""
+    (reference diffusion/Diffusion.py:182-269).  ``input_image`` is in [0, 255] (divided by 255 here, as there).
+    ``tile=`` (not in the reference) samples an image of any size through overlapping model-sized windows: see ``forward``."""
 
     GRAPH_MIN_STEPS = 4
 
@@ -241,12 +367,35 @@ class GaussianDiffusionSampler(nn.Module):
         return self.predict_xt_prev_mean_from_eps(t, eps, y_t), var
 
     def forward(self, input_image, ddim=False, unconditional_guidance_scale=1, ddim_step=None, *, y_T=None,
-                noise_by_step: Optional[List[torch.Tensor]] = None, trajectory: Optional[List[torch.Tensor]] = None):
+                noise_by_step: Optional[List[torch.Tensor]] = None, trajectory: Optional[List[torch.Tensor]] = None,
+                tile: Optional[int] = None, tile_overlap: Optional[int] = None, tile_batch: Optional[int] = None):
         """``y_T`` / ``noise_by_step`` inject the random draws (parity runs; ``noise_by_step[k]`` is the k-th per-step draw of
         the ancestral loop, in call order); by default they come from torch's generator exactly where the reference draws
         them.  ``trajectory`` collects the pre-clip y_t after every step.  Called with autograd enabled (the reference would
         record a graph through every model evaluation, diffusion/Diffusion.py:217-269) the loop still runs without one and
-        returns a detached tensor, with one RuntimeWarning per sampler instance; an input that requires grad is refused."""
+        returns a detached tensor, with one RuntimeWarning per sampler instance; an input that requires grad is refused.
+
+        Overlapping-window sampling (an addition to the reference's surface; DDIM only):
+          * ``tile``: integer >= 1, the side of the square window handed to the model (``min(tile, size)`` on each axis); every
+            window is denoised at every step, the noise estimates are averaged where windows overlap (``tile_weights``) and one
+            DDIM update is applied to the full image.  ``None``: the whole image goes through the model in one piece, as in the
+            reference.  A window size the model cannot take raises the same ``RuntimeError`` as such an image does.
+          * ``tile_overlap``: integer in ``[0, tile // 2]``, the overlap of neighbouring windows; default ``tile // 8``.
+          * ``tile_batch``: integer >= 1, the most windows per model evaluation (bounds memory); ``None`` evaluates all
+            ``B * n_windows`` at once.
+        ``y_T`` and ``trajectory`` are full-size ``[B, 3, H, W]``; ``dynamic_forward`` sees the full image."""
+        if tile is None:
+            if tile_overlap is not None or tile_batch is not None:
+                raise ValueError("tile_overlap / tile_batch were given without tile")
+        else:
+            tile = _int_arg("tile", tile, 1)
+            if not ddim:
+                raise ValueError("tile needs ddim=True: the ancestral loop is not run over windows")
+            tile_overlap = tile // 8 if tile_overlap is None else _int_arg("tile_overlap", tile_overlap, 0)
+            if tile_overlap > tile // 2:
+                raise ValueError(f"tile_overlap must be in [0, tile // 2] = [0, {tile // 2}], got {tile_overlap}")
+            if tile_batch is not None:
+                tile_batch = _int_arg("tile_batch", tile_batch, 1)
         if torch.is_grad_enabled():
             if input_image.requires_grad or (y_T is not None and torch.is_tensor(y_T) and y_T.requires_grad):
                 raise RuntimeError("GaussianDiffusionSampler.forward: an input requires grad, but the sampling loop runs under "
@@ -256,7 +405,50 @@ class GaussianDiffusionSampler(nn.Module):
                 warnings.warn("GaussianDiffusionSampler.forward was called with autograd enabled: the sampling loop runs under "
                               "torch.no_grad() and returns a tensor without grad_fn", RuntimeWarning, stacklevel=2)
         with torch.no_grad():
+            if tile is not None:
+                return self._forward_tiled(input_image, ddim_step, y_T, trajectory, tile, tile_overlap, tile_batch)
             return self._forward(input_image, ddim, unconditional_guidance_scale, ddim_step, y_T, noise_by_step, trajectory)
+
+    def _forward_tiled(self, input_image, ddim_step, y_T, trajectory, tile, overlap, tile_batch):
+        """The DDIM loop over overlapping windows.  ``unconditional_guidance_scale`` needs no handling: as in ``_forward`` its
+        two evaluations are the same function, so the combine is eps exactly and one evaluation is issued."""
+        if input_image.is_cuda and not input_image.is_contiguous():
+            input_image = input_image.contiguous()
+        E.require_gpu_tensor(input_image, "input_image")
+        lib = _capi.lib()
+        dev = input_image.device
+        img = input_image.float() / 255.0                                                          # :220
+        B, Cx, H, W = (int(v) for v in img.shape)
+        if Cx != 3:
+            raise RuntimeError(f"expected input[{B}, {Cx + 3}, {H}, {W}] to have 6 channels")
+        if ddim_step is None:
+            raise TypeError("unsupported operand type(s) for /: 'int' and 'NoneType'")             # :243 with ddim_step=None
+        key = (B, H, W, str(dev), int(ddim_step), False, 0, lib.hdiff_get_contraction_mode(), tile, overlap, tile_batch)
+        sp = self._plans.get(key)
+        if sp is None or sp.unet is not self.model.plan_for(sp.n_slots, sp.th, sp.tw, dev, True):
+            sp = _TiledStepPlan(self, B, H, W, dev, int(ddim_step), tile, overlap, tile_batch)
+            self._plans = {key: sp}
+        sp.unet.plan.pack_weights()     # once per call, as in _forward
+        self.model.dynamic_forward(torch.cat([img, img], dim=1))    # on the full image
+        y = torch.randn_like(img) if y_T is None else y_T            # :239
+        sp.cond.copy_(img)
+        sp.y.copy_(y)
+        sp.step.fill_(sp.n_steps - 1)
+        sp.nan_flag.zero_()
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        eager = trajectory is not None or sp.n_steps < self.GRAPH_MIN_STEPS
+        if not eager:
+            sp.plan.capture()
+        for _ in range(sp.n_steps):
+            if eager:
+                sp.plan.run(stream)
+            else:
+                sp.plan.replay(stream)
+            if trajectory is not None:
+                trajectory.append(sp.y.clone())
+        out = torch.empty_like(img)
+        _capi.check(lib.hdiff_clip(sp.y.data_ptr(), out.data_ptr(), C.c_float(-1.0), C.c_float(1.0), sp.n, stream), "clip")
+        return out
 
     def _forward(self, input_image, ddim, unconditional_guidance_scale, ddim_step, y_T, noise_by_step, trajectory):
         if input_image.is_cuda and not input_image.is_contiguous():
@@ -272,7 +464,8 @@ class GaussianDiffusionSampler(nn.Module):
             raise TypeError("unsupported operand type(s) for /: 'int' and 'NoneType'")             # :243 with ddim_step=None
         inject = (not ddim) and noise_by_step is not None
         seed = 0 if (ddim or inject) else int(torch.empty((), dtype=torch.int64).random_().item())
-        key = (B, H, W, str(dev), int(ddim_step) if ddim else None, inject, seed, lib.hdiff_get_contraction_mode())
+        key = (B, H, W, str(dev), int(ddim_step) if ddim else None, inject, seed, lib.hdiff_get_contraction_mode(), None, None,
+               None)                                                  # the last three: tile, tile_overlap, tile_batch
         sp = self._plans.get(key)
         if sp is None or sp.unet is not self.model.plan_for(B, H, W, dev, True):
             sp = _StepPlan(self, B, H, W, dev, int(ddim_step) if ddim else None, inject, seed)

@@ -492,6 +492,30 @@ int hdiff_resize_nearest(const float* x, float* y, int BC, int H, int W, int OH,
 int hdiff_avgpool_global(const float* x, float* y, int BC, int HW, hdiff_stream_t stream);
 int hdiff_concat2(const float* a, const float* b, float* out, int B, int64_t n0, int64_t n1, hdiff_stream_t stream);
 /* ------------------------------------------------------------------------------------------------------------------
+ * Overlapping-window DDIM sampling of the second tree's sampler (the `tile=` argument; an addition to the reference).
+ * Layout: per axis a table of window origins (origin_y[ny], origin_x[nx]); window (b, iy, ix) has index (b*ny + iy)*nx + ix
+ * and covers rows origin_y[iy] .. + th - 1 and columns origin_x[ix] .. + tw - 1 of a [B][C][H][W] tensor (th <= H, tw <= W).
+ * The windows covering row py are the consecutive run first_y[py] .. first_y[py] + count_y[py] - 1 (count <= 3) with the
+ * normalised fp32 weights weight_y[py][0..2]; columns likewise.  The weight of window (iy, ix) at a pixel is ay * ax.
+ *   hdiff_tile_gather      out[slot] = the [C][th][tw] crop of window min(w0 + slot, B*ny*nx - 1) for slot < n_slots (slots past
+ *                          the last window repeat it: the padding of a short final chunk); origins are clamped into the
+ *                          tensor in the kernel.  With ny = nx = 1, th = H, tw = W it is a copy of samples w0 .. w0 + n_slots - 1
+ *   hdiff_tile_ddim_step   one DDIM step on the full image y [B][C][H][W], in place, from the windows' noise estimates
+ *                          eps_w [B*ny*nx][C][th][tw]: eps = sum over jy (outer), jx (inner), ascending, of
+ *                          (ay * ax) * eps_w[window][c][py - oy][px - ox], the first product initialising the sum; then
+ *                          hdiff_ddim_step's update with the same tab / step_ptr / nsteps / nan_flag (one atomicOr per wave).
+ *                          fp32, no contraction, no atomics on y: bitwise repeatable; one window of weight 1.0 gives
+ *                          hdiff_ddim_step bit for bit.  Table entries are clamped: no access leaves eps_w
+ * ------------------------------------------------------------------------------------------------------------------ */
+int hdiff_tile_gather(const float* x, float* out, const int32_t* origin_y, const int32_t* origin_x, int B, int C, int H, int W,
+                      int ny, int nx, int th, int tw, int w0 /* first window, 0 <= w0 < B*ny*nx */, int n_slots,
+                      hdiff_stream_t stream);
+int hdiff_tile_ddim_step(float* y, const float* eps_w, const int32_t* first_y, const int32_t* count_y,
+                         const float* weight_y /* [H][3] */, const int32_t* origin_y, const int32_t* first_x,
+                         const int32_t* count_x, const float* weight_x /* [W][3] */, const int32_t* origin_x, const float* tab,
+                         const int32_t* step_ptr, int nsteps, int32_t* nan_flag, int B, int C, int H, int W, int ny, int nx,
+                         int th, int tw, hdiff_stream_t stream);
+/* ------------------------------------------------------------------------------------------------------------------
  * Trainer of the second tree (diffusion/Diffusion.py:26-180) and the backward passes of its image encoder / skip resize.
  *   hdiff_train_b_loss_fwd   from noise_pred, noise, y_t, gt [B][3][HW] and t: mse = (noise_pred - noise)^2,
  *                            y0_pred = ((1 / sqrt_ab[t]) * (y_t - sqrt_1mab[t] * noise_pred)) / 255 (the reference's trailing
