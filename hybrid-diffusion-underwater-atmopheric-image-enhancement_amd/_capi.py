@@ -183,6 +183,9 @@ _PROTOS = {
     "hdiff_msssim_l1_workspace": (C.c_int, [C.POINTER(MsssimDesc), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "hdiff_msssim_l1_fwd": (C.c_int, [C.POINTER(MsssimDesc)] + [C.c_void_p] * 6),
     "hdiff_msssim_l1_bwd": (C.c_int, [C.POINTER(MsssimDesc)] + [C.c_void_p] * 7),
+    "hdiff_quality_workspace": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int64)]),
+    "hdiff_psnr_ssim": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "hdiff_uiqm": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "hdiff_avgpool_global_bwd": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "hdiff_resize_nearest_bwd": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "hdiff_concat2": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.c_void_p]),

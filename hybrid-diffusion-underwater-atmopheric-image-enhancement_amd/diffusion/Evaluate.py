@@ -1,0 +1,150 @@
+"""The evaluation loop of the reference's second tree (``utils/rotinas.py:839-1085`` ``test``, which ``Main.py --state inference``
+runs): sample a test set with the image-conditioned DDIM sampler and score every result with PSNR, SSIM and UIQM.  Here the scores
+are taken on the device, where the sampler leaves its output (``hdiff_amd.quality``); nothing is copied to the host per batch unless
+the images are to be saved.
+
+Deliberate deviations from the reference:
+  * the target is scaled by 1 / 255.  ``rotinas.py:919`` clips the 0-255 target to [0, 1] and so compares against a binary image; that
+    is not copied.
+  * FID, LPIPS and ``nmetrics`` / UCIQE are not computed: the first two need pretrained networks, the last stays on the unpinned host
+    path in ``uw_metrics``.  ``res.txt`` holds the reference's keys for what was measured and no others.
+  * UIQM's parts are ``getUIQM``'s own (``quality.uiqm``); the reference reports the parts of ``nmetrics`` beside ``getUIQM``'s total.
+  * images are written with Pillow, rounded to the nearest integer (``cv2.imwrite`` of a float image in the reference, which also
+    swaps the red and blue channels on the way).
+  * ``test`` scores every image of a set: the reference's loader drops the last incomplete batch.  Its file names are those of the
+    degraded images.
+"""
+from __future__ import annotations
+
+import os
+from typing import Dict, Iterable, Iterator, List, Optional, Sequence
+
+import torch
+
+from .. import quality
+
+__all__ = ["evaluate", "test", "RES_KEYS"]
+
+# res.txt: the reference's key for each measured score, in the reference's order (rotinas.py:967-982)
+RES_KEYS = (("psnr_orgin_avg:", "psnr"), ("ssim_orgin_avg:", "ssim"), ("uiqm_orgin_avg:", "uiqm"), ("uism_orgin_avg:", "uism"),
+            ("uicm_orgin_avg:", "uicm"), ("uiconm_orgin_avg:", "uiconm"))
+
+
+def _device_of(sampler) -> Optional[torch.device]:
+    """Where the sampler's tensors live; None (batches stay where they are) for a callable that holds none."""
+    if isinstance(sampler, torch.nn.Module):
+        for t in list(sampler.buffers()) + list(sampler.parameters()):
+            return t.device
+    return None
+
+
+def _save_batch(images01: torch.Tensor, names: Sequence[str], save_dir: str) -> None:
+    from PIL import Image
+    arr = (images01.detach().float().clamp(0, 1) * 255.0).round().to(torch.uint8).permute(0, 2, 3, 1).cpu().numpy()
+    for img, name in zip(arr, names):
+        Image.fromarray(img).save(os.path.join(save_dir, name))
+
+
+def write_res(path: str, result: Dict[str, object]) -> None:
+    with open(path, "w+") as f:
+        for key, k in RES_KEYS:
+            f.write("\n" + key)
+            f.write(str(result[k]))
+
+
+def evaluate(sampler, batches: Iterable, *, ddim_step: int, tile: Optional[int] = None, tile_overlap: Optional[int] = None,
+             tile_batch: Optional[int] = None, save_dir: Optional[str] = None, collect: Optional[List[torch.Tensor]] = None,
+             meter=None) -> Dict[str, object]:
+    """Samples and scores a set.  ``batches`` yields ``(input, target)`` or ``(input, target, names)``: CHW images in [0, 255] as
+    ``Underwater_Dataset`` / ``Atmospheric_Dataset`` produce them, batched.  Per batch: ``out = sampler(input, ddim=True,
+    unconditional_guidance_scale=1, ddim_step=ddim_step, tile=...)`` (rotinas.py:907), then ``(out + 1) / 2`` is scored against
+    ``target / 255``.  ``collect``, a list, receives every ``out``.  With ``save_dir`` each result is written under its name
+    (``<running index>.png`` without one) as uint8, and ``res.txt`` beside them.  ``meter``: a ``quality.QualityMeter`` to go on
+    filling (a new one by default).  Returns ``QualityMeter.compute()``'s dict."""
+    meter = quality.QualityMeter() if meter is None else meter
+    dev = _device_of(sampler)
+    if save_dir is not None:
+        os.makedirs(save_dir, exist_ok=True)
+    tile_kw = {} if tile is None else dict(tile=tile, tile_overlap=tile_overlap, tile_batch=tile_batch)
+    done = 0
+    with torch.no_grad():
+        for batch in batches:
+            inp, target = batch[0], batch[1]
+            names = list(batch[2]) if len(batch) > 2 else [f"{done + i:05d}.png" for i in range(int(inp.shape[0]))]
+            inp = (inp if dev is None else inp.to(dev)).float()
+            target = (target if dev is None else target.to(dev)).float()
+            out = sampler(inp, ddim=True, unconditional_guidance_scale=1, ddim_step=ddim_step, **tile_kw)
+            pred01 = (out + 1) / 2                                                        # :912
+            meter.update(pred01, target / 255)
+            if collect is not None:
+                collect.append(out)
+            if save_dir is not None:
+                _save_batch(pred01, names, save_dir)
+            done += int(inp.shape[0])
+    result = meter.compute()
+    if save_dir is not None:
+        write_res(os.path.join(save_dir, "res.txt"), result)
+    return result
+
+
+def _cfg(config, key: str, *default):
+    if isinstance(config, dict):
+        if key in config:
+            return config[key]
+    elif hasattr(config, key):
+        return getattr(config, key)
+    if default:
+        return default[0]
+    raise KeyError(f"the configuration has no '{key}'")
+
+
+def _batched(dataset, batch_size: int) -> Iterator:
+    """(input [B,3,H,W], target [B,3,H,W], file names of the degraded images) in order, the last batch as short as it comes."""
+    for start in range(0, len(dataset), batch_size):
+        idx = range(start, min(start + batch_size, len(dataset)))
+        items = [dataset[i] for i in idx]
+        yield (torch.stack([it[0] for it in items]), torch.stack([it[1] for it in items]),
+               [os.path.basename(dataset.paths_a[i]) for i in idx])
+
+
+def test(config, epoch=None) -> Dict[str, Dict[str, object]]:
+    """``rotinas.test(config, epoch)``: the test split of ``config.underwater_data_name`` and of ``config.atmospheric_data_name``
+    through ``DynamicUNet`` (``config.T / channel / channel_mult / num_res_blocks``) loaded from ``config.pretrained_path`` (a
+    state dict; ``module.`` prefixes are stripped), ``config.ddim_step`` DDIM steps, results under
+    ``output/result/<checkpoint file>/<set>/`` (``config.result_root`` replaces ``output/result``).  Optional keys: ``tile``,
+    ``tile_overlap``, ``tile_batch`` (overlapping-window sampling), ``dataset_root`` (one root for both sets, or a dict by set
+    name), ``transforms`` (the sets' ``transforms=``; default: their 256 x 256 resize), ``device_list`` (the first entry is used; default ``cuda:0``).  ``epoch`` is accepted and unused, as in the reference.
+    Returns ``{set name: evaluate()'s dict}``."""
+    from ..datasets import Atmospheric_Dataset, Underwater_Dataset
+    from .Diffusion import GaussianDiffusionSampler
+    from .Model import DynamicUNet
+
+    u_name, a_name = _cfg(config, "underwater_data_name"), _cfg(config, "atmospheric_data_name")
+    root = _cfg(config, "dataset_root", None)
+
+    def root_of(name):
+        return root.get(name) if isinstance(root, dict) else root
+
+    transforms = _cfg(config, "transforms", None)
+    sets = ((u_name, Underwater_Dataset(u_name, transforms=transforms, task="test", root=root_of(u_name))),
+            (a_name, Atmospheric_Dataset(a_name, transforms=transforms, task="test", root=root_of(a_name))))
+    devices = _cfg(config, "device_list", None)
+    device = torch.device(devices[0] if devices else "cuda:0")
+    if device.type == "cuda" and device.index is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+
+    model = DynamicUNet(T=_cfg(config, "T"), ch=_cfg(config, "channel"), ch_mult=_cfg(config, "channel_mult"),
+                        num_res_blocks=_cfg(config, "num_res_blocks"), dropout=0.)
+    path = _cfg(config, "pretrained_path")
+    ckpt = torch.load(path, map_location="cpu")
+    model.load_state_dict({k.replace("module.", ""): v for k, v in ckpt.items()})
+    model.eval()
+    sampler = GaussianDiffusionSampler(model, _cfg(config, "beta_1"), _cfg(config, "beta_T"), _cfg(config, "T")).to(device)
+
+    base = os.path.join(_cfg(config, "result_root", os.path.join("output", "result")), os.path.basename(path))
+    results = {}
+    for name, data in sets:
+        results[name] = evaluate(sampler, _batched(data, int(_cfg(config, "batch_size"))), ddim_step=_cfg(config, "ddim_step"),
+                                 tile=_cfg(config, "tile", None), tile_overlap=_cfg(config, "tile_overlap", None),
+                                 tile_batch=_cfg(config, "tile_batch", None), save_dir=os.path.join(base, name))
+    return results

@@ -8,6 +8,7 @@ published definitions with skimage's defaults; PARITY UNPINNED by the reference 
   SSIM (Wang et al. 2004): 7x7 uniform window, K1 = 0.01, K2 = 0.03, sample covariance (N/(N-1)), borders of
   (win-1)//2 pixels cropped before averaging, channels averaged.
 CPU / numpy: these are evaluation-side metrics, not part of the device hot path.
+``hdiff_amd.quality.psnr_ssim`` computes the same two scores per image on the device (``csrc/quality.hip``).
 """
 from __future__ import annotations
 

@@ -1,6 +1,7 @@
 """Underwater image-quality measures used by the reference's evaluation (``utils/rotinas.py:923-928`` calls ``nmetrics`` and
 ``getUIQM`` of ``metrics/metrics.py``): UIQM = c1*UICM + c2*UISM + c3*UIConM, UCIQE, EME and logAMEE.  CPU / numpy: this is
 reporting code, not part of the GPU hot path.
+``hdiff_amd.quality.uiqm`` computes ``getUIQM`` and its three parts per image on the device (``csrc/quality.hip``).
 
 Parity:
   * ``getUIQM`` and its parts, ``eme`` and ``logamee`` are PINNED by golden vectors produced by the reference's own functions

@@ -572,6 +572,18 @@ int hdiff_msssim_l1_fwd(const hdiff_msssim_desc* d, const float* x, const float*
                         hdiff_stream_t stream);
 int hdiff_msssim_l1_bwd(const hdiff_msssim_desc* d, const float* x, const float* y, const float* d_loss, const void* saved,
                         void* scratch, float* dx, hdiff_stream_t stream);
+/* Per-image quality scores of the evaluation (csrc/quality.hip; the reference's utils/rotinas.py:916-928).  a, b: fp32 [N][3][H][W],
+ * nominal range [0, 1]; every score is taken on v = min(max(x, 0), 1) * 255 in fp32.  Outputs are float64 device rows.
+ *   hdiff_quality_workspace  bytes of `scratch` for either call at (N, H, W)
+ *   hdiff_psnr_ssim          out[n] = {PSNR (dB, range 255; +inf for identical images), SSIM (7x7 uniform window, interior positions,
+ *                            sample covariance, channels averaged)}; H, W >= 7; two launches
+ *   hdiff_uiqm               out[n] = {UICM, UISM, UIConM, UIQM = 0.0282 UICM + 0.2953 UISM + 3.5753 UIConM}; H, W >= 8; twelve launches;
+ *                            an image with a constant channel has UISM = UIQM = NaN (the definition divides by the largest gradient)
+ * N in [1, 65535], H * W <= 2^30.  A non-finite input value makes the scores of ITS image NaN.  No allocation, no synchronisation, no
+ * float atomics: legal under stream capture, bitwise repeatable, and an image's scores do not depend on N or its place in the batch. */
+int hdiff_quality_workspace(int N, int H, int W, int64_t* bytes);
+int hdiff_psnr_ssim(const float* a, const float* b, int N, int H, int W, double* out, void* scratch, hdiff_stream_t stream);
+int hdiff_uiqm(const float* a, int N, int H, int W, double* out, void* scratch, hdiff_stream_t stream);
 /* final clip (:98) */
 int hdiff_clip(const float* x, float* y, float lo, float hi, int64_t n, hdiff_stream_t stream);
 /* out = a*x + b*y (y may be NULL): bias merges and other weight-preparation arithmetic */

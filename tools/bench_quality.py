@@ -1,0 +1,97 @@
+"""Scoring one batch of 8 images at 256x256 two ways, ALTERNATELY inside one process, engine clock and board power sampled beside
+each timing (bench.ClockSampler):
+
+  (a) device: ``quality.QualityMeter.update(pred, target)`` -- PSNR, SSIM and UIQM with its parts for the whole batch, timed by device
+      events around ``--reps`` consecutive updates (nothing synchronises in between);
+  (b) host: what it replaces -- copy the batch to the host, then ``metrics.psnr`` / ``metrics.ssim`` and ``uw_metrics.getUIQM`` per
+      image in one Python thread.
+
+    python tools/bench_quality.py [--batch 8] [--size 256] [--alternate 3] [--reps 50] [--warmup 5]
+
+Prints one line per timing and one JSON summary line.  The one condition checked (exit status 1 otherwise): the device arm for the
+WHOLE batch takes less than the host arm for ONE image in the same run -- any sound kernel clears that by an order of magnitude; it
+is there to catch a hidden per-image synchronisation or host fallback."""
+import argparse
+import json
+import os
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+import hdiff_amd  # noqa: E402,F401
+import bench  # noqa: E402
+from hdiff_amd import metrics, quality, uw_metrics  # noqa: E402
+
+ap = argparse.ArgumentParser()
+ap.add_argument("--batch", type=int, default=8)
+ap.add_argument("--size", type=int, default=256)
+ap.add_argument("--alternate", type=int, default=3)
+ap.add_argument("--reps", type=int, default=50)
+ap.add_argument("--warmup", type=int, default=5)
+a = ap.parse_args()
+dev = torch.device("cuda", 0)
+torch.cuda.set_device(0)
+g = torch.Generator().manual_seed(0)
+# image-like content: smooth colour fields plus noise, the prediction a perturbed target
+yy, xx = torch.meshgrid(torch.arange(a.size, dtype=torch.float32), torch.arange(a.size, dtype=torch.float32), indexing="ij")
+base = torch.stack([0.5 + 0.4 * torch.sin(xx / 25 + c) * torch.cos(yy / 35 - c) for c in range(3)])
+target = (base[None] + 0.05 * torch.randn(a.batch, 3, a.size, a.size, generator=g)).clamp(0, 1)
+pred = (target + 0.03 * torch.randn(a.batch, 3, a.size, a.size, generator=g)).clamp(0, 1)
+pred_d, target_d = pred.to(dev), target.to(dev)
+
+
+def device_arm():
+    meter = quality.QualityMeter(capacity=a.batch * (a.reps + a.warmup))
+    for _ in range(a.warmup):
+        meter.update(pred_d, target_d)
+    torch.cuda.synchronize(dev)
+    start, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    start.record()
+    for _ in range(a.reps):
+        meter.update(pred_d, target_d)
+    end.record()
+    end.synchronize()
+    return start.elapsed_time(end) / a.reps, meter.compute()
+
+
+def host_arm():
+    t0 = time.perf_counter()
+    p = pred_d.cpu().numpy().transpose(0, 2, 3, 1)
+    t = target_d.cpu().numpy().transpose(0, 2, 3, 1)
+    rows = []
+    for i in range(a.batch):
+        pi, ti = np.clip(p[i], 0, 1) * 255, np.clip(t[i], 0, 1) * 255
+        rows.append((metrics.psnr(ti, pi, 255.0), metrics.ssim(ti, pi, 255.0, channel_axis=2), uw_metrics.getUIQM(pi)))
+    return (time.perf_counter() - t0) * 1e3, rows
+
+
+times = {"device_batch_ms": [], "host_batch_ms": []}
+for rep in range(a.alternate):
+    clock = bench.ClockSampler(0)
+    with clock:
+        ms, res = device_arm()
+    c = clock.summary()
+    times["device_batch_ms"].append(ms)
+    print(f"device  rep {rep}: {ms:.4f} ms per batch of {a.batch} ({a.reps} updates between two events)  sclk {c.get('sclk_mhz_mean')} MHz  "
+          f"board {c.get('board_power_w_mean')} W", flush=True)
+    clock = bench.ClockSampler(0)
+    with clock:
+        ms, rows = host_arm()
+    c = clock.summary()
+    times["host_batch_ms"].append(ms)
+    print(f"host    rep {rep}: {ms:.2f} ms per batch of {a.batch} = {ms / a.batch:.2f} ms per image  sclk {c.get('sclk_mhz_mean')} MHz  "
+          f"board {c.get('board_power_w_mean')} W", flush=True)
+    gaps = [abs(res["per_image"][i, 0] - rows[i][0]) for i in range(a.batch)], [abs(res["per_image"][i, 1] - rows[i][1]) for i in range(a.batch)], \
+        [abs(res["per_image"][i, 2] - rows[i][2]) / abs(rows[i][2]) for i in range(a.batch)]
+    print(f"        device against host on this batch: |dPSNR| {max(gaps[0]):.1e} dB  |dSSIM| {max(gaps[1]):.1e}  UIQM rel {max(gaps[2]):.1e}",
+          flush=True)
+dev_worst, host_image_best = max(times["device_batch_ms"]), min(times["host_batch_ms"]) / a.batch
+summary = {k: {"mean": sum(v) / len(v), "min": min(v), "max": max(v), "repetitions": len(v)} for k, v in times.items()}
+ok = dev_worst < host_image_best
+print(json.dumps({"metric": f"PSNR + SSIM + UIQM of one batch of {a.batch} at {a.size}x{a.size}, device against host, alternating",
+                  "unit": "ms/batch", "arms": summary, "host_ms_per_image_min": host_image_best,
+                  "device_batch_below_one_host_image": ok}))
+sys.exit(0 if ok else 1)
