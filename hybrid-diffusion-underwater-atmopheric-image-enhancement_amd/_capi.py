@@ -141,6 +141,7 @@ _PROTOS = {
     "hdiff_conv2d_wgrad_workspace": (C.c_int, [C.POINTER(WgradDesc), C.POINTER(C.c_int), C.POINTER(C.c_int64)]),
     "hdiff_conv2d_wgrad": (C.c_int, [C.POINTER(WgradDesc), C.c_void_p, C.c_int, C.c_void_p]),
     "hdiff_conv2d_wgrad_dropout": (C.c_int, [C.POINTER(WgradDesc), C.c_void_p, C.c_float, C.c_void_p, C.c_int, C.c_void_p]),
+    "hdiff_conv2d_wgrad_route": (C.c_int, [C.POINTER(WgradDesc), C.c_int, C.POINTER(C.c_int)]),
     "hdiff_conv_wgrad_unpack": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                           C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "hdiff_gn_swish_bwd": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,

@@ -280,53 +280,63 @@ int ceil_log2w(int v) {
 
 }  // namespace
 
-extern "C" int hdiff_conv2d_wgrad_workspace(const hdiff_conv_wgrad_desc* d, int* nsplit_out, int64_t* floats_out) {
-  HDIFF_CHECK_ARG(d && nsplit_out && floats_out, "conv2d_wgrad_workspace: null pointer");
-  if (wgrad1x1_applicable(d)) {
-    *nsplit_out = wgrad1x1_nsplit(d);
-    *floats_out = (int64_t)*nsplit_out * d->ntaps * d->CinPad * d->CoutPad;
-    return HDIFF_OK;
-  }
-  if (wgrad3x3_applicable(d)) {
-    *nsplit_out = wgrad3x3_nsplit(d);
-    *floats_out = (int64_t)*nsplit_out * d->ntaps * d->CinPad * d->CoutPad;
-    return HDIFF_OK;
-  }
-  const int ckw = d->ntaps == 1 ? 32 : (d->ntaps > 9 ? 4 : 16);
-  const int base = cdiv(d->Cout, BM) * cdiv(d->CinPad, ckw);
-  int twl = ceil_log2w(d->VW);
-  if (twl > 5) twl = 5;
-  const int TW = 1 << twl, TH = BNP / TW;
-  const int total = d->B * cdiv(d->VW, TW) * cdiv(d->VH, TH);
-  int ns = cdiv(768, base);
-  if (ns > total) ns = total;
-  if (ns < 1) ns = 1;
-  *nsplit_out = ns;
-  *floats_out = (int64_t)ns * d->ntaps * d->CinPad * d->CoutPad;
-  return HDIFF_OK;
-}
+// ---- the weight gradient's route: which kernel serves a descriptor, decided once (wgrad_route) ---------------------------------
+namespace {
 
-// keep_bits != NULL: the dropout form (hdiff_conv2d_wgrad_dropout validated the descriptor: a plain 3x3 with prologue, never a 1x1)
-static int conv2d_wgrad(const hdiff_conv_wgrad_desc* d, float* dwp, int nsplit, const unsigned* keep_bits, float inv_keep,
-                        hdiff_stream_t stream) {
-  HDIFF_CHECK_ARG(d && d->x0 && d->dy && dwp, "conv2d_wgrad: null pointer");
+// the descriptor rules of hdiff_conv2d_wgrad (include/hdiff.h)
+int check_wgrad_desc(const hdiff_conv_wgrad_desc* d) {
+  HDIFF_CHECK_ARG(d && d->x0 && d->dy, "conv2d_wgrad: null pointer");
   HDIFF_CHECK_ARG(d->C1 == 0 || d->x1, "conv2d_wgrad: C1 > 0 without x1");
   HDIFF_CHECK_ARG(d->ntaps >= 1 && d->ntaps <= HDIFF_MAX_TAPS, "conv2d_wgrad: ntaps %d out of range", d->ntaps);
   HDIFF_CHECK_ARG(d->CinPad >= d->C0 + d->C1 && d->CinPad % 8 == 0 && d->CoutPad >= d->Cout && d->CoutPad % 64 == 0,
                   "conv2d_wgrad: padded channel counts invalid");
-  HDIFF_CHECK_ARG(d->B > 0 && d->VH > 0 && d->VW > 0 && d->in_stride >= 1 && d->in_stride <= 2 && nsplit >= 1,
-                  "conv2d_wgrad: bad geometry");
+  HDIFF_CHECK_ARG(d->B > 0 && d->VH > 0 && d->VW > 0 && d->in_stride >= 1 && d->in_stride <= 2, "conv2d_wgrad: bad geometry");
   HDIFF_CHECK_ARG((d->gn_scale == nullptr) == (d->gn_shift == nullptr), "conv2d_wgrad: gn_scale/gn_shift must come together");
-  if (wgrad1x1_applicable(d)) return launch_wgrad1x1(d, dwp, nsplit, (hipStream_t)stream);
-  if (wgrad3x3_applicable(d)) return launch_wgrad3x3(d, dwp, nsplit, (hipStream_t)stream, keep_bits, inv_keep);
+  return HDIFF_OK;
+}
 
-  WgradK k{};
-  k.keep_bits = keep_bits; k.inv_keep = inv_keep;
+// the descriptor rules of hdiff_conv2d_wgrad_dropout on top of those: a plain 3x3 with prologue, never a 1x1, always stride 1
+int check_wgrad_dropout(const hdiff_conv_wgrad_desc* d) {
+  HDIFF_CHECK_ARG(d->x1 == nullptr && d->C1 == 0, "conv2d_wgrad_dropout: a concat input (x1) is not supported");
+  HDIFF_CHECK_ARG(d->gn_scale != nullptr && d->gn_shift != nullptr, "conv2d_wgrad_dropout: needs the GroupNorm + Swish prologue (gn_scale / gn_shift)");
+  bool plain = d->ntaps == 9 && d->in_stride == 1 && d->VH == d->H && d->VW == d->W && d->OH == d->H && d->OW == d->W &&
+               d->out_sy == 1 && d->out_oy == 0 && d->out_sx == 1 && d->out_ox == 0;
+  for (int t = 0; plain && t < 9; ++t) plain = d->tap_dy[t] == t / 3 - 1 && d->tap_dx[t] == t % 3 - 1;
+  HDIFF_CHECK_ARG(plain, "conv2d_wgrad_dropout: not a plain 3x3 / stride-1 / pad-1 convolution (nine taps in row-major order, output grid = input grid)");
+  HDIFF_CHECK_ARG(d->B > 0 && d->C0 > 0 && d->H > 0 && d->W > 0 && (long long)d->B * d->C0 * d->H * d->W < (1ll << 31),
+                  "conv2d_wgrad_dropout: inputs of 2^31 elements or more are not supported (32-bit bit indices)");
+  return HDIFF_OK;
+}
+
+// pixel tile of the generic kernel: 2^tw_log2 columns (the plane's width rounded up to a power of two, 32 at most) x 128 >> tw_log2 rows
+int wgrad_tw_log2(const hdiff_conv_wgrad_desc* d) {
+  const int twl = ceil_log2w(d->VW);
+  return twl > 5 ? 5 : twl;
+}
+
+// The one place that decides which kernel runs a (validated) descriptor; the launcher switches over the answer, the workspace
+// query and hdiff_conv2d_wgrad_route read it.  Touches no device.  Order: the 1x1 fast kernel, the 3x3 fast kernel, the generic one.
+// The generic kernel's ROWS > 0 instantiations (4 x 32 tile, wave w reads patch rows from w * in_stride on, no clamp) want all
+// four tile rows staged: the plane at least as tall as the tile, VH >= TH = 4.  On a shorter plane the staged patch ends below
+// wave 3 (or 2, 1): their reads would run into the next channel's plane and, for the chunk's last channel, past the kernel's LDS
+// -- multiplied by dY = 0, but 0 x NaN is NaN.  Such planes take ROWS = 0, which clamps the row.
+// dropout: the dropout form (a stride-1 conv, check_wgrad_dropout); the answer is the same, the launcher picks the DROP instantiation.
+int wgrad_route(const hdiff_conv_wgrad_desc* d, bool dropout) {
+  if (wgrad1x1_applicable(d)) return HDIFF_WGRAD_ROUTE_FAST_1X1;
+  if (wgrad3x3_applicable(d)) return HDIFF_WGRAD_ROUTE_FAST_3X3;
+  const int twl = wgrad_tw_log2(d);
+  const int TH = BNP >> twl;
+  if (twl != 5 || d->VH < TH) return HDIFF_WGRAD_ROUTE_GENERIC;
+  return (dropout || d->in_stride == 1) ? HDIFF_WGRAD_ROUTE_GENERIC_ROWS1 : HDIFF_WGRAD_ROUTE_GENERIC_ROWS2;
+}
+
+// geometry of the generic kernel's launch, and whether it fits
+int wgrad_configure(const hdiff_conv_wgrad_desc* d, WgradK& k) {
   k.x0 = d->x0; k.x1 = d->x1; k.C0 = d->C0; k.C1 = d->C1; k.Cin = d->C0 + d->C1; k.H = d->H; k.W = d->W;
   k.gn_scale = d->gn_scale; k.gn_shift = d->gn_shift; k.dy = d->dy; k.Cout = d->Cout; k.OH = d->OH; k.OW = d->OW;
   k.VH = d->VH; k.VW = d->VW; k.in_stride = d->in_stride;
   k.out_sy = d->out_sy; k.out_oy = d->out_oy; k.out_sx = d->out_sx; k.out_ox = d->out_ox;
-  k.ntaps = d->ntaps; k.CinPad = d->CinPad; k.CoutPad = d->CoutPad; k.nsplit = nsplit; k.dwp = dwp;
+  k.ntaps = d->ntaps; k.CinPad = d->CinPad; k.CoutPad = d->CoutPad;
 
   int dy_min = d->tap_dy[0], dy_max = d->tap_dy[0], dx_min = d->tap_dx[0], dx_max = d->tap_dx[0];
   for (int t = 1; t < d->ntaps; ++t) {
@@ -336,10 +346,8 @@ static int conv2d_wgrad(const hdiff_conv_wgrad_desc* d, float* dwp, int nsplit, 
     dx_max = d->tap_dx[t] > dx_max ? d->tap_dx[t] : dx_max;
   }
   k.dy_min = dy_min; k.dx_min = dx_min;
-  int twl = ceil_log2w(d->VW);
-  if (twl > 5) twl = 5;
-  k.tw_log2 = twl;
-  const int TW = 1 << twl;
+  k.tw_log2 = wgrad_tw_log2(d);
+  const int TW = 1 << k.tw_log2;
   k.TH = BNP / TW;
   k.tiles_x = cdiv(d->VW, TW);
   k.tiles_per_image = k.tiles_x * cdiv(d->VH, k.TH);
@@ -362,9 +370,53 @@ static int conv2d_wgrad(const hdiff_conv_wgrad_desc* d, float* dwp, int nsplit, 
   k.nx = cdiv(k.CKW * k.PH * k.PW, NTHREADS);
   HDIFF_CHECK_ARG(k.nt_used <= MAXNT && k.nx <= NXS && k.PH < 1024 && k.PW < 1024,
                   "conv2d_wgrad: configuration does not fit (columns %d, slots %d)", k.ncol, k.nx);
-  HDIFF_CHECK_ARG(nsplit <= k.total_tiles, "conv2d_wgrad: nsplit %d exceeds the %d tiles", nsplit, k.total_tiles);
   const size_t lds = (size_t)(BM * DYROW + k.CKW * k.PLANE + 2 * k.CKW) * sizeof(float);
   HDIFF_CHECK_ARG(lds <= 160 * 1024, "conv2d_wgrad: tile needs %zu bytes of LDS", lds);
+  return HDIFF_OK;
+}
+
+}  // namespace
+
+// (no dropout flag: the route's fast / generic answer, all the split count depends on, is the same in the dropout form)
+extern "C" int hdiff_conv2d_wgrad_workspace(const hdiff_conv_wgrad_desc* d, int* nsplit_out, int64_t* floats_out) {
+  HDIFF_CHECK_ARG(d && nsplit_out && floats_out, "conv2d_wgrad_workspace: null pointer");
+  int ns;
+  switch (wgrad_route(d, false)) {
+    case HDIFF_WGRAD_ROUTE_FAST_1X1: ns = wgrad1x1_nsplit(d); break;
+    case HDIFF_WGRAD_ROUTE_FAST_3X3: ns = wgrad3x3_nsplit(d); break;
+    default: {
+      const int ckw = d->ntaps == 1 ? 32 : (d->ntaps > 9 ? 4 : 16);
+      const int base = cdiv(d->Cout, BM) * cdiv(d->CinPad, ckw);
+      const int TW = 1 << wgrad_tw_log2(d), TH = BNP / TW;
+      const int total = d->B * cdiv(d->VW, TW) * cdiv(d->VH, TH);
+      ns = cdiv(768, base);
+      if (ns > total) ns = total;
+      if (ns < 1) ns = 1;
+    }
+  }
+  *nsplit_out = ns;
+  *floats_out = (int64_t)ns * d->ntaps * d->CinPad * d->CoutPad;
+  return HDIFF_OK;
+}
+
+// keep_bits != NULL: the dropout form (hdiff_conv2d_wgrad_dropout validated the descriptor)
+static int conv2d_wgrad(const hdiff_conv_wgrad_desc* d, float* dwp, int nsplit, const unsigned* keep_bits, float inv_keep,
+                        hdiff_stream_t stream) {
+  int rc = check_wgrad_desc(d);
+  if (rc != HDIFF_OK) return rc;
+  HDIFF_CHECK_ARG(dwp, "conv2d_wgrad: null pointer");
+  HDIFF_CHECK_ARG(nsplit >= 1, "conv2d_wgrad: bad geometry");
+  const int route = wgrad_route(d, keep_bits != nullptr);
+  if (route == HDIFF_WGRAD_ROUTE_FAST_1X1) return launch_wgrad1x1(d, dwp, nsplit, (hipStream_t)stream);
+  if (route == HDIFF_WGRAD_ROUTE_FAST_3X3) return launch_wgrad3x3(d, dwp, nsplit, (hipStream_t)stream, keep_bits, inv_keep);
+
+  WgradK k{};
+  rc = wgrad_configure(d, k);
+  if (rc != HDIFF_OK) return rc;
+  k.keep_bits = keep_bits; k.inv_keep = inv_keep;
+  k.nsplit = nsplit; k.dwp = dwp;
+  HDIFF_CHECK_ARG(nsplit <= k.total_tiles, "conv2d_wgrad: nsplit %d exceeds the %d tiles", nsplit, k.total_tiles);
+  const size_t lds = (size_t)(BM * DYROW + k.CKW * k.PLANE + 2 * k.CKW) * sizeof(float);
 
   static uint64_t attr_mask = 0;
   if (first_use_on_device(attr_mask)) {
@@ -376,17 +428,37 @@ static int conv2d_wgrad(const hdiff_conv_wgrad_desc* d, float* dwp, int nsplit, 
   }
   dim3 grid(cdiv(d->Cout, BM), cdiv(d->CinPad, k.CKW), nsplit);
   (void)hipGetLastError();  // drop any stale error left by another HIP user in this thread
-  if (keep_bits != nullptr && k.tw_log2 == 5)          // (stride 1: checked by the dropout entry)
-    hipLaunchKernelGGL((conv_wgrad_kernel<1, true>), grid, dim3(NTHREADS), lds, (hipStream_t)stream, k);
-  else if (keep_bits != nullptr)
-    hipLaunchKernelGGL((conv_wgrad_kernel<0, true>), grid, dim3(NTHREADS), lds, (hipStream_t)stream, k);
-  else if (k.tw_log2 == 5 && d->in_stride == 1)
-    hipLaunchKernelGGL(conv_wgrad_kernel<1>, grid, dim3(NTHREADS), lds, (hipStream_t)stream, k);
-  else if (k.tw_log2 == 5 && d->in_stride == 2)
-    hipLaunchKernelGGL(conv_wgrad_kernel<2>, grid, dim3(NTHREADS), lds, (hipStream_t)stream, k);
-  else
-    hipLaunchKernelGGL(conv_wgrad_kernel<0>, grid, dim3(NTHREADS), lds, (hipStream_t)stream, k);
+  const bool drop = keep_bits != nullptr;
+  switch (route) {
+    case HDIFF_WGRAD_ROUTE_GENERIC_ROWS1:
+      if (drop) hipLaunchKernelGGL((conv_wgrad_kernel<1, true>), grid, dim3(NTHREADS), lds, (hipStream_t)stream, k);
+      else hipLaunchKernelGGL(conv_wgrad_kernel<1>, grid, dim3(NTHREADS), lds, (hipStream_t)stream, k);
+      break;
+    case HDIFF_WGRAD_ROUTE_GENERIC_ROWS2:      // never the dropout form (stride 1: wgrad_route)
+      hipLaunchKernelGGL(conv_wgrad_kernel<2>, grid, dim3(NTHREADS), lds, (hipStream_t)stream, k);
+      break;
+    default:                                   // HDIFF_WGRAD_ROUTE_GENERIC
+      if (drop) hipLaunchKernelGGL((conv_wgrad_kernel<0, true>), grid, dim3(NTHREADS), lds, (hipStream_t)stream, k);
+      else hipLaunchKernelGGL(conv_wgrad_kernel<0>, grid, dim3(NTHREADS), lds, (hipStream_t)stream, k);
+  }
   HDIFF_CHECK_LAUNCH("conv_wgrad_kernel");
+  return HDIFF_OK;
+}
+
+// The route of a descriptor as hdiff_conv2d_wgrad (dropout != 0: hdiff_conv2d_wgrad_dropout) would run it (include/hdiff.h):
+// their validation, the generic kernel's fit, no launch, no device.
+extern "C" int hdiff_conv2d_wgrad_route(const hdiff_conv_wgrad_desc* d, int dropout, int* route_out) {
+  HDIFF_CHECK_ARG(d && route_out, "conv2d_wgrad_route: null pointer");
+  int rc = check_wgrad_desc(d);
+  if (rc == HDIFF_OK && dropout) rc = check_wgrad_dropout(d);
+  if (rc != HDIFF_OK) return rc;
+  const int route = wgrad_route(d, dropout != 0);
+  if (route >= HDIFF_WGRAD_ROUTE_GENERIC) {
+    WgradK k{};
+    rc = wgrad_configure(d, k);
+    if (rc != HDIFF_OK) return rc;
+  }
+  *route_out = route;
   return HDIFF_OK;
 }
 
@@ -401,14 +473,8 @@ extern "C" int hdiff_conv2d_wgrad_dropout(const hdiff_conv_wgrad_desc* d, const 
   HDIFF_CHECK_ARG(d && keep_bits && dwp, "conv2d_wgrad_dropout: null pointer");
   HDIFF_CHECK_ARG(inv_keep >= 1.0f && inv_keep <= 3.0e38f, "conv2d_wgrad_dropout: inv_keep = %g is not a finite 1 / keep with keep in (0, 1]",
                   (double)inv_keep);
-  HDIFF_CHECK_ARG(d->x1 == nullptr && d->C1 == 0, "conv2d_wgrad_dropout: a concat input (x1) is not supported");
-  HDIFF_CHECK_ARG(d->gn_scale != nullptr && d->gn_shift != nullptr, "conv2d_wgrad_dropout: needs the GroupNorm + Swish prologue (gn_scale / gn_shift)");
-  bool plain = d->ntaps == 9 && d->in_stride == 1 && d->VH == d->H && d->VW == d->W && d->OH == d->H && d->OW == d->W &&
-               d->out_sy == 1 && d->out_oy == 0 && d->out_sx == 1 && d->out_ox == 0;
-  for (int t = 0; plain && t < 9; ++t) plain = d->tap_dy[t] == t / 3 - 1 && d->tap_dx[t] == t % 3 - 1;
-  HDIFF_CHECK_ARG(plain, "conv2d_wgrad_dropout: not a plain 3x3 / stride-1 / pad-1 convolution (nine taps in row-major order, output grid = input grid)");
-  HDIFF_CHECK_ARG(d->B > 0 && d->C0 > 0 && d->H > 0 && d->W > 0 && (long long)d->B * d->C0 * d->H * d->W < (1ll << 31),
-                  "conv2d_wgrad_dropout: inputs of 2^31 elements or more are not supported (32-bit bit indices)");
+  const int rc = check_wgrad_dropout(d);
+  if (rc != HDIFF_OK) return rc;
   return conv2d_wgrad(d, dwp, nsplit, keep_bits, inv_keep, stream);
 }
 

@@ -255,6 +255,20 @@ int hdiff_conv2d_wgrad(const hdiff_conv_wgrad_desc* d, float* dwp, int nsplit, h
  * the same ordered reduce (hdiff_conv_wgrad_unpack): no atomics, bitwise repeatable. */
 int hdiff_conv2d_wgrad_dropout(const hdiff_conv_wgrad_desc* d, const uint32_t* keep_bits, float inv_keep, float* dwp, int nsplit,
                                hdiff_stream_t stream);
+/* Which kernel hdiff_conv2d_wgrad (dropout != 0: hdiff_conv2d_wgrad_dropout) runs a descriptor on.  Host only: nothing is
+ * launched, no device is needed, no pointer of the descriptor is dereferenced.  The validation of the entry asked for applies,
+ * with its messages, and for the generic kernel the check that its tile fits.  hdiff_conv2d_wgrad_workspace reads the same
+ * answer: the fast kernels have their own split counts.  The generic kernel's tile is 2^t columns x 128 / 2^t rows of the
+ * virtual output grid, 2^t = VW rounded up to a power of two, 32 at most; at 32 columns each of the four waves owns one tile row
+ * (ROWS1 / ROWS2, by in_stride) -- on planes at least as tall as the tile, VH >= 4, only. */
+enum {
+  HDIFF_WGRAD_ROUTE_FAST_1X1 = 0,       /* conv_wgrad1x1_kernel: plain 1x1 without prologue, H * W and the channel counts aligned */
+  HDIFF_WGRAD_ROUTE_FAST_3X3 = 1,       /* conv_wgrad3x3_kernel: plain 3x3 / stride 1, W % 32 == 0, H even, channel counts aligned */
+  HDIFF_WGRAD_ROUTE_GENERIC = 2,        /* conv_wgrad_kernel<0>: any tap list, stride and output map; tiles narrower than 32 or taller than the plane */
+  HDIFF_WGRAD_ROUTE_GENERIC_ROWS1 = 3,  /* conv_wgrad_kernel<1>: 4 x 32 tile, in_stride 1 */
+  HDIFF_WGRAD_ROUTE_GENERIC_ROWS2 = 4   /* conv_wgrad_kernel<2>: 4 x 32 tile, in_stride 2 */
+};
+int hdiff_conv2d_wgrad_route(const hdiff_conv_wgrad_desc* d, int dropout, int* route_out);
 int hdiff_conv_wgrad_unpack(const float* dwp, int nsplit, float* dw, int mode, int Cout, int Cin, int KH, int KW, int ntaps,
                             const int* tap_ky, const int* tap_kx, int CinPad, int CoutPad, int accumulate,
                             hdiff_stream_t stream);
