@@ -14,6 +14,9 @@ What differs underneath (reference lines in brackets):
 What is added to the reference's surface: ``GaussianDiffusionSampler.forward(..., ddim_steps=S)`` (or ``timesteps=[...]``) samples
 in S <= T model evaluations with the strided DDIM update (Song et al. 2021) under the same guidance, from the same captured 2B step
 with ``hdiff_cfg_ddim_step_loop`` as its one update kernel; ``ddim_timesteps`` and ``ddim_table`` are its schedule, usable on the CPU.
+``solver="dpmpp2m"`` replaces that first-order update by DPM-Solver++(2M) (Lu et al. 2022: data prediction, multistep) -- still one
+model evaluation and ONE update kernel per step (``hdiff_cfg_dpmpp_step_loop``), one more state tensor -- on the logSNR-uniform time
+steps of ``logsnr_timesteps``, with the coefficients of ``dpmpp_table``; both are shared with the image-conditioned sampler.
 """
 from __future__ import annotations
 
@@ -29,7 +32,11 @@ from .. import _capi
 from .. import engine as E
 
 
-__all__ = ["extract", "GaussianDiffusionTrainer", "GaussianDiffusionSampler", "ddim_timesteps", "ddim_table"]
+__all__ = ["extract", "GaussianDiffusionTrainer", "GaussianDiffusionSampler", "ddim_timesteps", "ddim_table", "logsnr_timesteps",
+           "dpmpp_table"]
+
+SOLVERS = ("ddim", "dpmpp2m")
+SPACINGS = ("uniform", "logsnr")
 
 
 def extract(v, t, x_shape):
@@ -83,6 +90,92 @@ def ddim_table(betas: torch.Tensor, timesteps: Sequence[int], eta: float = 0.0) 
     sigma = eta * torch.sqrt((1.0 - a_prev) / (1.0 - a)) * torch.sqrt(1.0 - a / a_prev)
     c2 = torch.sqrt(torch.clamp(1.0 - a_prev - sigma * sigma, min=0.0))
     return torch.stack([torch.sqrt(1.0 - a), torch.sqrt(a), torch.sqrt(a_prev), c2, sigma], dim=1)
+
+
+def _alphas_bar(betas) -> torch.Tensor:
+    return torch.cumprod(1.0 - torch.as_tensor(betas).detach().to(device="cpu", dtype=torch.float64).reshape(-1), dim=0)
+
+
+def _int_shift(shift) -> int:
+    if isinstance(shift, bool) or int(shift) != shift or int(shift) < 0:
+        raise ValueError(f"shift must be an integer >= 0, got {shift!r}")
+    return int(shift)
+
+
+def logsnr_timesteps(betas, S: int, shift: int = 0) -> List[int]:
+    """S time steps spaced uniformly in the half log signal-to-noise ratio ``lam[t] = 0.5 * log(ab / (1 - ab))`` at
+    ``ab = cumprod(1 - betas)[t + shift]``, t = 0 .. hi = T - 1 - shift (``shift = 1``: the image-conditioned sampler, which reads
+    ``alphas_bar[t + 1]``): the index nearest to each of the S targets between ``lam[0]`` and ``lam[hi]`` (the lowest on a tie), then
+    made strictly increasing by a forward pass ``idx_k >= idx_(k-1) + 1``, a cap of the last at hi and a backward pass
+    ``idx_k <= idx_(k+1) - 1``.  Always S entries, from 0 to hi; ``S = 1`` gives ``[hi]``.  A multistep solver needs such steps: on
+    index-uniform ones the last logSNR interval of a linear-beta schedule is several times the one before it.  ``ValueError`` for S
+    outside [1, hi + 1] or not an integer.  Computed on the CPU in float64."""
+    shift = _int_shift(shift)
+    ab = _alphas_bar(betas)
+    hi = int(ab.numel()) - 1 - shift
+    if isinstance(S, bool) or int(S) != S:
+        raise ValueError(f"the number of steps must be an integer, got {S!r}")
+    S = int(S)
+    if hi < 0 or not 1 <= S <= hi + 1:
+        raise ValueError(f"the number of steps must lie in [1, {hi + 1}], got {S}")
+    if S == 1:
+        return [hi]
+    v = ab[shift:]
+    lam = 0.5 * torch.log(v / (1.0 - v))
+    idx = []
+    for k in range(S):
+        d = (lam - (lam[0] + (lam[hi] - lam[0]) * k / (S - 1))).abs()
+        idx.append(int((d == d.min()).nonzero()[0]))
+    for k in range(1, S):
+        idx[k] = max(idx[k], idx[k - 1] + 1)
+    idx[S - 1] = min(idx[S - 1], hi)
+    for k in range(S - 2, -1, -1):
+        idx[k] = min(idx[k], idx[k + 1] - 1)
+    return idx
+
+
+def dpmpp_table(betas, timesteps: Sequence[int], shift: int = 0, final_alpha_bar: float = 1.0) -> torch.Tensor:
+    """Coefficients of DPM-Solver++(2M), float64 ``[S, 5]``, row k = ``(s1m, sa, A, B, C)`` for the step from ``tau_k`` to
+    ``tau_(k-1)`` (the loop runs k = S-1 down to 0).  With ``a = ab[tau_k + shift]``, ``a' = ab[tau_(k-1) + shift]`` (``a' =
+    final_alpha_bar`` at k = 0), ``lam(v) = 0.5 * log(v / (1 - v))`` and ``h = lam(a') - lam(a)``:
+
+        s1m = sqrt(1 - a),  sa = sqrt(a),  A = sqrt(1 - a') / sqrt(1 - a),  g = -sqrt(a') * expm1(-h)
+        first order (k = S-1: no history yet; k = 0: the closing step):   B = g,  C = 0
+        else, with r = h_(k+1) / h:                                        B = g * (1 + 1 / (2r)),  C = -g / (2r)
+
+    and one step is ``x0 = (x - eps * s1m) / sa ; x' = A * x + B * x0 + C * x0_prev`` (``x0_prev``: the x0 of the step before).  A
+    first-order row is the deterministic DDIM update written in x and x0.  Where ``a' = 1`` the row is exactly ``A = 0, B = 1, C = 0``
+    (h is infinite and is not formed).  Computed on the CPU; the samplers cast each entry to fp32 once."""
+    shift = _int_shift(shift)
+    ab = _alphas_bar(betas)
+    tau = _checked_timesteps(timesteps, int(ab.numel()) - shift)
+    final = torch.tensor(float(final_alpha_bar), dtype=torch.float64)
+    if not 0.0 < float(final) <= 1.0:
+        raise ValueError(f"final_alpha_bar must lie in (0, 1], got {final_alpha_bar}")
+
+    def lam(v):
+        return 0.5 * torch.log(v / (1.0 - v))
+
+    S = len(tau)
+    rows, h_prev = [None] * S, None
+    zero, one = torch.zeros((), dtype=torch.float64), torch.ones((), dtype=torch.float64)
+    for k in range(S - 1, -1, -1):
+        a = ab[tau[k] + shift]
+        a_next = ab[tau[k - 1] + shift] if k > 0 else final
+        if float(a_next) == 1.0:
+            A, B, Cc, h = zero, one, zero, None
+        else:
+            h = lam(a_next) - lam(a)
+            A = torch.sqrt(1.0 - a_next) / torch.sqrt(1.0 - a)
+            g = -torch.sqrt(a_next) * torch.expm1(-h)
+            if k == S - 1 or k == 0:
+                B, Cc = g, zero
+            else:
+                r = h_prev / h
+                B, Cc = g * (1.0 + 1.0 / (2.0 * r)), -g / (2.0 * r)
+        rows[k] = torch.stack([torch.sqrt(1.0 - a), torch.sqrt(a), A, B, Cc])
+        h_prev = h
+    return torch.stack(rows)
 
 
 def _stream(device) -> int:
@@ -163,6 +256,7 @@ class _SamplerPlan:
         dev = device
         self.x = torch.empty(B, 3, H, W, device=dev)
         self.noise = torch.empty(B, 3, H, W, device=dev)
+        self.x0_prev = None                                              # the x0 history of solver="dpmpp2m", allocated on first use
         self.step = torch.zeros(1, dtype=torch.int32, device=dev)
         self.nan_flag = torch.zeros(1, dtype=torch.int32, device=dev)
         self.done = torch.zeros(1, dtype=torch.int32, device=dev)       # finished-workgroup counter of the fused update
@@ -198,6 +292,32 @@ class _SamplerPlan:
         d.done_counter = self.done.data_ptr()
         p.keep((d, tab, t_tab))                    # the tables live exactly as long as the step that reads them
         p.call("hdiff_cfg_ddim_step_loop", C.byref(d))
+        return p
+
+    def _build_dpmpp(self, ddim) -> E.Plan:
+        """The DPM-Solver++(2M) step: the strided step's launches with hdiff_cfg_dpmpp_step_loop as the ONE update -- same counter,
+        same time vector; the plan owns the x0 history the update reads (from the second step on) and writes."""
+        timesteps, _, clip_x0 = ddim
+        up, n, dev = self.unet, self.n, self.x.device
+        tab = dpmpp_table(self._sampler.betas, timesteps).float().contiguous().to(dev)       # f64 -> f32 once per entry
+        t_tab = torch.tensor(timesteps, dtype=torch.int64, device=dev)
+        if self.x0_prev is None:
+            self.x0_prev = torch.empty_like(self.x)
+        p = E.Plan(dev)
+        p.ops.extend(up.plan.ops)
+        eps = up.out
+        d = _capi.CfgDpmppLoopDesc()
+        d.x, d.eps_c, d.eps_u = self.x.data_ptr(), eps.data_ptr(), eps.data_ptr() + 4 * n
+        d.x_next, d.x0_prev = self.x.data_ptr(), self.x0_prev.data_ptr()
+        d.tab, d.t_tab = tab.data_ptr(), t_tab.data_ptr()
+        d.step_ptr, d.nsteps, d.clip_x0 = self.step.data_ptr(), len(timesteps), int(bool(clip_x0))
+        d.w = float(self._sampler.w)
+        d.nan_flag, d.n = self.nan_flag.data_ptr(), n
+        d.x_dup0, d.x_dup1 = up.x.data_ptr(), up.x.data_ptr() + 4 * n
+        d.t_next, d.t_count = up.t.data_ptr(), 2 * self.B
+        d.done_counter = self.done.data_ptr()
+        p.keep((d, tab, t_tab))
+        p.call("hdiff_cfg_dpmpp_step_loop", C.byref(d))
         return p
 
     def _build(self, inject_noise: bool) -> E.Plan:
@@ -238,15 +358,21 @@ class _SamplerPlan:
         self.nan_flag.zero_()
         self.done.zero_()
 
-    def variant(self, inject_noise: bool, seed: int, ddim=None) -> E.Plan:
+    def variant(self, inject_noise: bool, seed: int, ddim=None, solver: str = "ddim") -> E.Plan:
         # the guidance weight is a launch argument of the fused update: the reference reads self.w on every step (:78), so
-        # a changed sampler.w must rebuild the captured step.  ddim = (timesteps, eta, clip_x0) selects the strided step.
+        # a changed sampler.w must rebuild the captured step.  ddim = (timesteps, eta, clip_x0) selects the strided step, solver
+        # its update.
         key = (inject_noise, seed if not inject_noise else 0, _capi.lib().hdiff_get_contraction_mode(),
-               float(self._sampler.w), ddim)
+               float(self._sampler.w), ddim, solver)
         if key not in self._variants:
             self.seed = seed
             self._variants.clear()          # a graph bakes its seed (and the contraction mode): keep one live variant
-            self._variants[key] = self._build(inject_noise) if ddim is None else self._build_ddim(inject_noise, ddim)
+            if ddim is None:
+                self._variants[key] = self._build(inject_noise)
+            elif solver == "dpmpp2m":
+                self._variants[key] = self._build_dpmpp(ddim)
+            else:
+                self._variants[key] = self._build_ddim(inject_noise, ddim)
         return self._variants[key]
 
 
@@ -311,7 +437,7 @@ class GaussianDiffusionSampler(nn.Module):
     # -- the loop -----------------------------------------------------------------------------------------------------
     def forward(self, x_T, labels, *, ddim_steps: Optional[int] = None, eta: float = 0.0,
                 timesteps: Optional[Sequence[int]] = None, clip_x0: bool = False, noise_by_step=None,
-                trajectory: Optional[List[torch.Tensor]] = None):
+                trajectory: Optional[List[torch.Tensor]] = None, solver: str = "ddim", spacing: Optional[str] = None):
         """``noise_by_step[time_step]`` injects the per-step z (parity tests); ``trajectory`` collects the pre-clip
         x_t after every step.  Both default to the reference behaviour.
 
@@ -320,8 +446,14 @@ class GaussianDiffusionSampler(nn.Module):
         ``eta`` scales the step noise (0: deterministic, no seed is drawn; 1: posterior-variance ancestral steps -- ``ddim_table``),
         ``clip_x0`` clamps the predicted x_0 to [-1, 1] before it is used.  In this mode ``noise_by_step[k]`` is indexed by the
         POSITION k in the time-step list (S entries, entry 0 unused) and ``trajectory`` receives S states.  Without
-        ``ddim_steps`` / ``timesteps`` the T-step ancestral loop of the reference runs."""
-        ddim = self._ddim_arguments(ddim_steps, eta, timesteps, clip_x0, noise_by_step)
+        ``ddim_steps`` / ``timesteps`` the T-step ancestral loop of the reference runs.
+
+        ``solver`` ("ddim" or "dpmpp2m") chooses the update of the strided sampler: "dpmpp2m" is DPM-Solver++(2M) (``dpmpp_table``),
+        second order at the same one model evaluation per step; it is the deterministic solver, so it takes neither ``eta != 0``
+        nor ``noise_by_step``.  ``spacing`` ("uniform": ``ddim_timesteps``; "logsnr": ``logsnr_timesteps(betas, S)``) chooses the
+        time steps of ``ddim_steps=S``; ``None`` is uniform for "ddim" and logsnr for "dpmpp2m".  It does not go with an explicit
+        ``timesteps`` list, and neither argument goes without ``ddim_steps`` / ``timesteps``."""
+        ddim, solver = self._ddim_arguments(ddim_steps, eta, timesteps, clip_x0, noise_by_step, solver, spacing)
         x_T, labels = _gpu_input(x_T, "x_T"), _gpu_input(labels, "labels")
         if torch.is_grad_enabled():
             # The reference runs here too (DiffusionCondition.py:82-98) and records an autograd graph through all 2T model
@@ -339,26 +471,42 @@ class GaussianDiffusionSampler(nn.Module):
                               "torch.no_grad() and returns a tensor without grad_fn (the reference would record a graph "
                               "through all 2T model evaluations)", RuntimeWarning, stacklevel=2)
         with torch.no_grad(), torch.cuda.device(x_T.device):
-            return self._forward(x_T, labels, noise_by_step, trajectory, ddim)
+            return self._forward(x_T, labels, noise_by_step, trajectory, ddim, solver)
 
-    def _ddim_arguments(self, ddim_steps, eta, timesteps, clip_x0, noise_by_step):
-        """None for the ancestral loop, else the validated (timesteps, eta, clip_x0) of the strided one (``ValueError`` otherwise)."""
+    def _ddim_arguments(self, ddim_steps, eta, timesteps, clip_x0, noise_by_step, solver="ddim", spacing=None):
+        """-> (None for the ancestral loop, else the validated (timesteps, eta, clip_x0) of the strided one; its solver);
+        ``ValueError`` otherwise.  Looks at no device."""
+        if solver not in SOLVERS:
+            raise ValueError(f"solver must be one of {SOLVERS}, got {solver!r}")
+        if spacing is not None and spacing not in SPACINGS:
+            raise ValueError(f"spacing must be None or one of {SPACINGS}, got {spacing!r}")
         if ddim_steps is None and timesteps is None:
             if float(eta) != 0.0 or clip_x0:
                 raise ValueError("eta / clip_x0 belong to the strided sampler: give ddim_steps or timesteps with them")
-            return None
+            if solver != "ddim" or spacing is not None:
+                raise ValueError("solver / spacing belong to the strided sampler: give ddim_steps or timesteps with them")
+            return None, solver
         if ddim_steps is not None and timesteps is not None:
             raise ValueError("give ddim_steps or timesteps, not both")
-        tau = tuple(ddim_timesteps(self.T, ddim_steps)) if timesteps is None else _checked_timesteps(timesteps, int(self.T))
+        if timesteps is not None:
+            if spacing is not None:
+                raise ValueError("spacing chooses the time steps of ddim_steps: it does not go with an explicit timesteps list")
+            tau = _checked_timesteps(timesteps, int(self.T))
+        elif (spacing or ("logsnr" if solver == "dpmpp2m" else "uniform")) == "logsnr":
+            tau = tuple(logsnr_timesteps(self.betas, ddim_steps))
+        else:
+            tau = tuple(ddim_timesteps(self.T, ddim_steps))
         eta = float(eta)
         if not eta >= 0.0:
             raise ValueError(f"eta must be >= 0, got {eta}")
+        if solver == "dpmpp2m" and (eta != 0.0 or noise_by_step is not None):
+            raise ValueError("solver='dpmpp2m' is the deterministic solver: it takes neither eta != 0 nor noise_by_step")
         if noise_by_step is not None and len(noise_by_step) != len(tau):
             raise ValueError(f"noise_by_step has {len(noise_by_step)} entries for {len(tau)} time steps (one per position, "
                              "entry 0 unused)")
-        return tau, eta, bool(clip_x0)
+        return (tau, eta, bool(clip_x0)), solver
 
-    def _forward(self, x_T, labels, noise_by_step, trajectory, ddim=None):
+    def _forward(self, x_T, labels, noise_by_step, trajectory, ddim=None, solver="ddim"):
         lib = _capi.lib()
         B, Cx, H, W = (int(v) for v in x_T.shape)
         dev = x_T.device
@@ -381,7 +529,7 @@ class GaussianDiffusionSampler(nn.Module):
             tau, eta, _ = ddim
             # the deterministic sampler consumes no randomness: torch's generator is left where it was
             seed = 0 if inject or eta == 0.0 else int(torch.empty((), dtype=torch.int64).random_().item())
-            plan = sp.variant(inject, seed, ddim)
+            plan = sp.variant(inject, seed, ddim, solver)
             steps = len(tau)
             sp.reset(x_T, labels, step=steps - 1, t=tau[-1])
         graphed = self.use_graph and trajectory is None

@@ -13,7 +13,8 @@ Differences: the data set.  The reference hard-codes torchvision CIFAR10; here `
 ``data/`` tree of underwater / atmospheric sets, ``hdiff_amd.datasets``), "synthetic", or "cifar10" (only if torchvision is
 installed).  Optional keys, all with reference-equivalent defaults: ``num_labels`` (10), ``num_workers`` (4),
 ``max_steps_per_epoch``; for ``eval`` alone ``ddim_steps`` (absent / None: the reference's T-step ancestral loop; S: the strided DDIM
-sampler of ``GaussianDiffusionSampler.forward`` in S model evaluations), ``ddim_eta`` (0.0) and ``ddim_clip_x0`` (False).  Under ``torch.distributed.run`` (WORLD_SIZE > 1) training is data-parallel: replicated weights,
+sampler of ``GaussianDiffusionSampler.forward`` in S model evaluations), ``ddim_eta`` (0.0), ``ddim_clip_x0`` (False), and with ``ddim_steps`` ``ddim_solver`` ("ddim" / "dpmpp2m": DPM-Solver++(2M)) and
+``ddim_spacing`` ("uniform" / "logsnr"), passed on as ``solver=`` / ``spacing=`` only when present.  Under ``torch.distributed.run`` (WORLD_SIZE > 1) training is data-parallel: replicated weights,
 per-rank shard of every epoch, ONE mean all-reduce of the gradients per step (hdiff_amd.parallel), rank-0 checkpoints.
 """
 import os
@@ -169,7 +170,9 @@ def eval(modelConfig: Dict) -> torch.Tensor:
         if cfg.get("ddim_steps") is None:
             images = sampler(x_T, labels) * 0.5 + 0.5               # [-1, 1] -> [0, 1]
         else:
+            solver_kw = {kw: cfg[key] for kw, key in (("solver", "ddim_solver"), ("spacing", "ddim_spacing"))
+                         if cfg.get(key) is not None}
             images = sampler(x_T, labels, ddim_steps=int(cfg["ddim_steps"]), eta=float(cfg.get("ddim_eta", 0.0)),
-                             clip_x0=bool(cfg.get("ddim_clip_x0", False))) * 0.5 + 0.5
+                             clip_x0=bool(cfg.get("ddim_clip_x0", False)), **solver_kw) * 0.5 + 0.5
         save_image(images, os.path.join(cfg["sampled_dir"], cfg["sampledImgName"]), nrow=cfg["nrow"])
         return images

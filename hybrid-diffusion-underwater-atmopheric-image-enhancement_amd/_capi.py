@@ -45,6 +45,17 @@ class CfgDdimLoopDesc(C.Structure):
     ]
 
 
+class CfgDpmppLoopDesc(C.Structure):
+    """hdiff_cfg_dpmpp_loop_desc (include/hdiff.h)."""
+    _fields_ = [
+        ("x", C.c_void_p), ("eps_c", C.c_void_p), ("eps_u", C.c_void_p), ("x_next", C.c_void_p), ("x0_prev", C.c_void_p),
+        ("tab", C.c_void_p), ("t_tab", C.c_void_p), ("step_ptr", C.c_void_p), ("nsteps", C.c_int), ("clip_x0", C.c_int),
+        ("w", C.c_double), ("nan_flag", C.c_void_p), ("n", C.c_int64),
+        ("x_dup0", C.c_void_p), ("x_dup1", C.c_void_p), ("t_next", C.c_void_p), ("t_count", C.c_int),
+        ("done_counter", C.c_void_p),
+    ]
+
+
 class ConvDesc(C.Structure):
     _fields_ = [
         ("x0", C.c_void_p), ("x1", C.c_void_p), ("C0", C.c_int), ("C1", C.c_int),
@@ -169,6 +180,9 @@ _PROTOS = {
     "hdiff_cfg_ddim_step": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
                                       C.c_double, C.c_int, C.c_uint64, C.c_void_p, C.c_int64, C.c_void_p]),
     "hdiff_cfg_ddim_step_loop": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "hdiff_cfg_dpmpp_step": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
+                                       C.c_double, C.c_int, C.c_void_p, C.c_int64, C.c_void_p]),
+    "hdiff_cfg_dpmpp_step_loop": (C.c_int, [C.c_void_p, C.c_void_p]),
     "hdiff_fill_t": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     "hdiff_step_decrement": (C.c_int, [C.c_void_p, C.c_void_p]),
     "hdiff_ddim_step": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int64,
@@ -176,6 +190,8 @@ _PROTOS = {
     "hdiff_fill_from_table": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "hdiff_tile_gather": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 10 + [C.c_void_p]),
     "hdiff_tile_ddim_step": (C.c_int, [C.c_void_p] * 12 + [C.c_int, C.c_void_p] + [C.c_int] * 8 + [C.c_void_p]),
+    "hdiff_dpmpp_step": (C.c_int, [C.c_void_p] * 6 + [C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_void_p]),
+    "hdiff_tile_dpmpp_step": (C.c_int, [C.c_void_p] * 13 + [C.c_int, C.c_int, C.c_void_p] + [C.c_int] * 8 + [C.c_void_p]),
     "hdiff_resize_nearest": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "hdiff_avgpool_global": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "hdiff_train_b_loss_workspace": (C.c_int, [C.c_int64, C.POINTER(C.c_int64)]),

@@ -16,7 +16,10 @@ Kept as written in the reference, on purpose:
 Added to the reference's surface: ``forward(..., tile=, tile_overlap=, tile_batch=)`` samples an image of any size through
 overlapping model-sized windows (``tile_origins`` / ``tile_weights`` give the layout): every window is denoised at every step,
 the noise estimates are blended where they overlap and ONE DDIM update is applied to the full image
-(``csrc/tile_ops.hip``).  Without ``tile`` nothing changes.
+(``csrc/tile_ops.hip``).  Without ``tile`` nothing changes.  ``forward(..., solver="dpmpp2m", spacing=, timesteps=)`` replaces the
+first-order DDIM update by DPM-Solver++(2M) on logSNR-uniform time steps (``dpmpp_table`` / ``logsnr_timesteps`` of
+``DiffusionFreeGuidence.DiffusionCondition`` with ``shift=1``: this sampler reads ``alphas_bar[t + 1]``) -- still one model
+evaluation and one update kernel per step (``csrc/dpmpp_ops.hip``), untiled and over windows.  Without ``solver`` nothing changes.
 
 Trainer underneath: q_sample and the 3 + 3 channel concat are HIP launches, the DynamicUNet runs its autograd path
 (``autograd.dyn_unet_forward_with_grad``) and the loss tail -- the squared error, ``y_0_pred`` and the angular-colour term,
@@ -38,9 +41,11 @@ import torch.nn.functional as F
 
 from .. import _capi
 from .. import engine as E
-from ..DiffusionFreeGuidence.DiffusionCondition import _gpu_input, _timesteps
+from ..DiffusionFreeGuidence.DiffusionCondition import (SOLVERS, SPACINGS, _checked_timesteps, _gpu_input, _timesteps, dpmpp_table,
+                                                         logsnr_timesteps)
 
-__all__ = ["extract", "GaussianDiffusionTrainer", "GaussianDiffusionSampler", "tile_origins", "tile_weights"]
+__all__ = ["extract", "GaussianDiffusionTrainer", "GaussianDiffusionSampler", "tile_origins", "tile_weights", "logsnr_timesteps",
+           "dpmpp_table"]
 
 
 def extract(v, t, x_shape):
@@ -208,11 +213,22 @@ def tile_weights(size: int, tile: int, overlap: int):
     return first, count, weight
 
 
-def _ddim_tables(sampler: "GaussianDiffusionSampler", ddim_step: int, device):
+def _uniform_sequence(ddim_step: int) -> List[int]:
+    return list(range(0, 1000, int(1000 / ddim_step)))                                     # :243-247 (the 1000 is literal there)
+
+
+def _dpmpp_tables(sampler: "GaussianDiffusionSampler", seq, device):
+    """-> (tab[n, 5] fp32, t_tab[n] int32) of DPM-Solver++(2M) on the increasing time steps ``seq``: ``a = alphas_bar[t + 1]`` and
+    the last step lands on ``alphas_bar[0]``, as the DDIM loop's does; float64 -> fp32 once per entry."""
+    seq = list(seq)
+    tab = dpmpp_table(sampler.betas, seq, shift=1, final_alpha_bar=float(sampler.alphas_bar[0]))
+    return tab.float().contiguous().to(device), torch.tensor(seq, dtype=torch.int32, device=device)
+
+
+def _ddim_tables(sampler: "GaussianDiffusionSampler", ddim_step: Optional[int], device, seq: Optional[List[int]] = None):
     """-> (tab[n, 4] fp32, t_tab[n] int32), indexed by the down-counting step counter k (k = n - 1 first): the same fp32 ops as
-    the reference's :250-262."""
-    step = int(1000 / ddim_step)                                                           # :243-247
-    seq = list(range(0, 1000, step))
+    the reference's :250-262, on the reference's time steps or on the increasing list ``seq``."""
+    seq = _uniform_sequence(ddim_step) if seq is None else list(seq)
     seq_next = [-1] + seq[:-1]
     ab = sampler.alphas_bar
     if seq[-1] + 1 >= ab.shape[0]:
@@ -230,7 +246,8 @@ class _StepPlan:
     """One captured sampling step for a fixed (B, H, W) and mode: fill t -> DynamicUNet -> update -> advance the counter."""
 
     def __init__(self, sampler: "GaussianDiffusionSampler", B: int, H: int, W: int, device, ddim_step: Optional[int],
-                 inject_noise: bool = False, seed: int = 0):
+                 inject_noise: bool = False, seed: int = 0, solver: str = "ddim", seq: Optional[List[int]] = None):
+        """``seq``: the increasing time steps of the DDIM / DPM-Solver++(2M) loop (None: the reference's, from ``ddim_step``)."""
         self.unet = sampler.model.plan_for(B, H, W, device, True)
         up = self.unet
         if up.out_hw != (H, W):
@@ -242,7 +259,7 @@ class _StepPlan:
         self.nan_flag = torch.zeros(1, dtype=torch.int32, device=device)
         self.noise = torch.empty(B, 3, H, W, device=device)
         p = E.Plan(device)
-        if ddim_step is None:
+        if ddim_step is None and seq is None:
             # ancestral (:224-236): t = the step counter itself; the first tree's fused update with w = 0 (eps_u := eps)
             var = torch.cat([sampler.posterior_var[1:2], sampler.betas[1:]])                      # :210
             self.c1 = sampler.coeff1.float().contiguous()
@@ -256,8 +273,17 @@ class _StepPlan:
                    self.noise.data_ptr() if inject_noise else None, up.y.data_ptr(), self.c1.data_ptr(), self.c2.data_ptr(),
                    self.sigma.data_ptr(), self.step.data_ptr(), int(sampler.T), C.c_double(0.0), C.c_uint64(seed),
                    self.nan_flag.data_ptr(), n)
+        elif solver == "dpmpp2m":
+            # the same step with the second-order update; the plan owns the x0 history it reads (from the second step on) and writes
+            self.tab, self.t_tab = _dpmpp_tables(sampler, _uniform_sequence(ddim_step) if seq is None else seq, device)
+            self.n_steps = int(self.t_tab.numel())
+            self.x0_prev = torch.empty(B, 3, H, W, device=device)
+            p.call("hdiff_fill_from_table", up.t.data_ptr(), self.t_tab.data_ptr(), self.step.data_ptr(), self.n_steps, B)
+            p.ops.extend(up.plan.ops)
+            p.call("hdiff_dpmpp_step", up.y.data_ptr(), up.out.data_ptr(), up.y.data_ptr(), self.x0_prev.data_ptr(),
+                   self.tab.data_ptr(), self.step.data_ptr(), self.n_steps, 0, self.nan_flag.data_ptr(), n)
         else:
-            self.tab, self.t_tab = _ddim_tables(sampler, ddim_step, device)
+            self.tab, self.t_tab = _ddim_tables(sampler, ddim_step, device, seq)
             self.n_steps = int(self.t_tab.numel())
             p.call("hdiff_fill_from_table", up.t.data_ptr(), self.t_tab.data_ptr(), self.step.data_ptr(), self.n_steps, B)
             p.ops.extend(up.plan.ops)
@@ -274,8 +300,8 @@ class _TiledStepPlan:
     Every chunk runs the SAME window plan at batch ``n_slots``; a short final chunk is padded with repeats of the last window,
     whose estimates are not stored.  With a single chunk the blend reads the plan's output directly."""
 
-    def __init__(self, sampler: "GaussianDiffusionSampler", B: int, H: int, W: int, device, ddim_step: int, tile: int,
-                 overlap: int, tile_batch: Optional[int]):
+    def __init__(self, sampler: "GaussianDiffusionSampler", B: int, H: int, W: int, device, ddim_step: Optional[int], tile: int,
+                 overlap: int, tile_batch: Optional[int], solver: str = "ddim", seq: Optional[List[int]] = None):
         th, tw = min(tile, H), min(tile, W)
         oy, ox = tile_origins(H, tile, overlap), tile_origins(W, tile, overlap)
         ny, nx = len(oy), len(ox)
@@ -300,7 +326,11 @@ class _TiledStepPlan:
         fx, cx, wx = tile_weights(W, tile, overlap)
         self.fy, self.cy, self.wy = fy.to(device), cy.to(device), wy.float().to(device).contiguous()    # fp32 cast: once, here
         self.fx, self.cx, self.wx = fx.to(device), cx.to(device), wx.float().to(device).contiguous()
-        self.tab, self.t_tab = _ddim_tables(sampler, ddim_step, device)
+        if solver == "dpmpp2m":
+            self.tab, self.t_tab = _dpmpp_tables(sampler, _uniform_sequence(ddim_step) if seq is None else seq, device)
+            self.x0_prev = torch.empty(B, 3, H, W, device=device)          # full-size history, like y
+        else:
+            self.tab, self.t_tab = _ddim_tables(sampler, ddim_step, device, seq)
         self.n_steps = int(self.t_tab.numel())
         p = E.Plan(device)
         p.call("hdiff_fill_from_table", up.t.data_ptr(), self.t_tab.data_ptr(), self.step.data_ptr(), self.n_steps, n_slots)
@@ -314,10 +344,16 @@ class _TiledStepPlan:
                 # samples is a copy; the padding slots are left behind)
                 p.call("hdiff_tile_gather", up.out.data_ptr(), self.eps[w0].data_ptr(), self.zero.data_ptr(),
                        self.zero.data_ptr(), n_slots, 3, th, tw, 1, 1, th, tw, 0, valid)
-        p.call("hdiff_tile_ddim_step", self.y.data_ptr(), self.eps.data_ptr(), self.fy.data_ptr(), self.cy.data_ptr(),
-               self.wy.data_ptr(), self.oy.data_ptr(), self.fx.data_ptr(), self.cx.data_ptr(), self.wx.data_ptr(),
-               self.ox.data_ptr(), self.tab.data_ptr(), self.step.data_ptr(), self.n_steps, self.nan_flag.data_ptr(), B, 3, H, W,
-               ny, nx, th, tw)
+        if solver == "dpmpp2m":
+            p.call("hdiff_tile_dpmpp_step", self.y.data_ptr(), self.eps.data_ptr(), self.x0_prev.data_ptr(), self.fy.data_ptr(),
+                   self.cy.data_ptr(), self.wy.data_ptr(), self.oy.data_ptr(), self.fx.data_ptr(), self.cx.data_ptr(),
+                   self.wx.data_ptr(), self.ox.data_ptr(), self.tab.data_ptr(), self.step.data_ptr(), self.n_steps, 0,
+                   self.nan_flag.data_ptr(), B, 3, H, W, ny, nx, th, tw)
+        else:
+            p.call("hdiff_tile_ddim_step", self.y.data_ptr(), self.eps.data_ptr(), self.fy.data_ptr(), self.cy.data_ptr(),
+                   self.wy.data_ptr(), self.oy.data_ptr(), self.fx.data_ptr(), self.cx.data_ptr(), self.wx.data_ptr(),
+                   self.ox.data_ptr(), self.tab.data_ptr(), self.step.data_ptr(), self.n_steps, self.nan_flag.data_ptr(), B, 3, H,
+                   W, ny, nx, th, tw)
         p.call("hdiff_step_decrement", self.step.data_ptr())
         self.plan = p
 
@@ -368,7 +404,8 @@ class GaussianDiffusionSampler(nn.Module):
 
     def forward(self, input_image, ddim=False, unconditional_guidance_scale=1, ddim_step=None, *, y_T=None,
                 noise_by_step: Optional[List[torch.Tensor]] = None, trajectory: Optional[List[torch.Tensor]] = None,
-                tile: Optional[int] = None, tile_overlap: Optional[int] = None, tile_batch: Optional[int] = None):
+                tile: Optional[int] = None, tile_overlap: Optional[int] = None, tile_batch: Optional[int] = None,
+                solver: str = "ddim", spacing: Optional[str] = None, timesteps=None):
         """``y_T`` / ``noise_by_step`` inject the random draws (parity runs; ``noise_by_step[k]`` is the k-th per-step draw of
         the ancestral loop, in call order); by default they come from torch's generator exactly where the reference draws
         them.  ``trajectory`` collects the pre-clip y_t after every step.  Called with autograd enabled (the reference would
@@ -383,7 +420,16 @@ class GaussianDiffusionSampler(nn.Module):
           * ``tile_overlap``: integer in ``[0, tile // 2]``, the overlap of neighbouring windows; default ``tile // 8``.
           * ``tile_batch``: integer >= 1, the most windows per model evaluation (bounds memory); ``None`` evaluates all
             ``B * n_windows`` at once.
-        ``y_T`` and ``trajectory`` are full-size ``[B, 3, H, W]``; ``dynamic_forward`` sees the full image."""
+        ``y_T`` and ``trajectory`` are full-size ``[B, 3, H, W]``; ``dynamic_forward`` sees the full image.
+
+        The solver of the DDIM loop (additions as well; ``ddim=True`` only, untiled and with ``tile``):
+          * ``solver``: "ddim" (the reference's update) or "dpmpp2m", DPM-Solver++(2M) -- second order at the same one model
+            evaluation per step (``dpmpp_table(betas, tau, shift=1, final_alpha_bar=alphas_bar[0])``).
+          * ``spacing``: the ``ddim_step`` time steps tau -- "uniform", the reference's ``range(0, 1000, int(1000 / ddim_step))``, or
+            "logsnr", ``logsnr_timesteps(betas, ddim_step, shift=1)``; ``None`` is uniform for "ddim" and logsnr for "dpmpp2m".
+          * ``timesteps``: an explicit strictly increasing list in ``[0, T - 2]`` in place of ``ddim_step`` (and of ``spacing``).
+        The model's time input at step k is ``tau_k``, as in the reference's loop."""
+        seq = self._solver_arguments(ddim, ddim_step, solver, spacing, timesteps)
         if tile is None:
             if tile_overlap is not None or tile_batch is not None:
                 raise ValueError("tile_overlap / tile_batch were given without tile")
@@ -406,10 +452,36 @@ class GaussianDiffusionSampler(nn.Module):
                               "torch.no_grad() and returns a tensor without grad_fn", RuntimeWarning, stacklevel=2)
         with torch.no_grad():
             if tile is not None:
-                return self._forward_tiled(input_image, ddim_step, y_T, trajectory, tile, tile_overlap, tile_batch)
-            return self._forward(input_image, ddim, unconditional_guidance_scale, ddim_step, y_T, noise_by_step, trajectory)
+                return self._forward_tiled(input_image, ddim_step, y_T, trajectory, tile, tile_overlap, tile_batch, solver, spacing,
+                                           seq)
+            return self._forward(input_image, ddim, unconditional_guidance_scale, ddim_step, y_T, noise_by_step, trajectory, solver,
+                                 spacing, seq)
 
-    def _forward_tiled(self, input_image, ddim_step, y_T, trajectory, tile, overlap, tile_batch):
+    def _solver_arguments(self, ddim, ddim_step, solver, spacing, timesteps):
+        """-> the time steps of the loop as a tuple, or None for the reference's own (``ValueError`` otherwise).  Looks at no
+        device.  Plain ``ddim=True, ddim_step=n`` gives None: that call runs exactly what it ran before these arguments existed."""
+        if solver not in SOLVERS:
+            raise ValueError(f"solver must be one of {SOLVERS}, got {solver!r}")
+        if spacing is not None and spacing not in SPACINGS:
+            raise ValueError(f"spacing must be None or one of {SPACINGS}, got {spacing!r}")
+        if not ddim:
+            if solver != "ddim" or spacing is not None or timesteps is not None:
+                raise ValueError("solver / spacing / timesteps need ddim=True: they choose the update and the steps of the DDIM loop")
+            return None
+        if timesteps is not None:
+            if ddim_step is not None or spacing is not None:
+                raise ValueError("an explicit timesteps list replaces ddim_step and spacing: give one or the other")
+            return _checked_timesteps(timesteps, int(self.T) - 1)
+        if (spacing or ("logsnr" if solver == "dpmpp2m" else "uniform")) == "uniform":
+            if ddim_step is None and solver != "ddim":
+                raise ValueError("solver='dpmpp2m' needs ddim_step or timesteps")
+            return None                                       # (ddim_step=None: the reference's TypeError, raised where it was)
+        if ddim_step is None:
+            raise ValueError("spacing='logsnr' needs ddim_step")
+        return tuple(logsnr_timesteps(self.betas, ddim_step, shift=1))
+
+    def _forward_tiled(self, input_image, ddim_step, y_T, trajectory, tile, overlap, tile_batch, solver="ddim", spacing=None,
+                       seq=None):
         """The DDIM loop over overlapping windows.  ``unconditional_guidance_scale`` needs no handling: as in ``_forward`` its
         two evaluations are the same function, so the combine is eps exactly and one evaluation is issued."""
         if input_image.is_cuda and not input_image.is_contiguous():
@@ -421,12 +493,14 @@ class GaussianDiffusionSampler(nn.Module):
         B, Cx, H, W = (int(v) for v in img.shape)
         if Cx != 3:
             raise RuntimeError(f"expected input[{B}, {Cx + 3}, {H}, {W}] to have 6 channels")
-        if ddim_step is None:
+        if ddim_step is None and seq is None:
             raise TypeError("unsupported operand type(s) for /: 'int' and 'NoneType'")             # :243 with ddim_step=None
-        key = (B, H, W, str(dev), int(ddim_step), False, 0, lib.hdiff_get_contraction_mode(), tile, overlap, tile_batch)
+        ddim_step = None if seq is not None else int(ddim_step)
+        key = (B, H, W, str(dev), ddim_step, False, 0, lib.hdiff_get_contraction_mode(), tile, overlap, tile_batch, solver, spacing,
+               seq)
         sp = self._plans.get(key)
         if sp is None or sp.unet is not self.model.plan_for(sp.n_slots, sp.th, sp.tw, dev, True):
-            sp = _TiledStepPlan(self, B, H, W, dev, int(ddim_step), tile, overlap, tile_batch)
+            sp = _TiledStepPlan(self, B, H, W, dev, ddim_step, tile, overlap, tile_batch, solver, seq)
             self._plans = {key: sp}
         sp.unet.plan.pack_weights()     # once per call, as in _forward
         self.model.dynamic_forward(torch.cat([img, img], dim=1))    # on the full image
@@ -450,7 +524,8 @@ class GaussianDiffusionSampler(nn.Module):
         _capi.check(lib.hdiff_clip(sp.y.data_ptr(), out.data_ptr(), C.c_float(-1.0), C.c_float(1.0), sp.n, stream), "clip")
         return out
 
-    def _forward(self, input_image, ddim, unconditional_guidance_scale, ddim_step, y_T, noise_by_step, trajectory):
+    def _forward(self, input_image, ddim, unconditional_guidance_scale, ddim_step, y_T, noise_by_step, trajectory, solver="ddim",
+                 spacing=None, seq=None):
         if input_image.is_cuda and not input_image.is_contiguous():
             input_image = input_image.contiguous()
         E.require_gpu_tensor(input_image, "input_image")
@@ -460,15 +535,16 @@ class GaussianDiffusionSampler(nn.Module):
         B, Cx, H, W = (int(v) for v in img.shape)
         if Cx != 3:
             raise RuntimeError(f"expected input[{B}, {Cx + 3}, {H}, {W}] to have 6 channels")
-        if ddim and ddim_step is None:
+        if ddim and ddim_step is None and seq is None:
             raise TypeError("unsupported operand type(s) for /: 'int' and 'NoneType'")             # :243 with ddim_step=None
         inject = (not ddim) and noise_by_step is not None
         seed = 0 if (ddim or inject) else int(torch.empty((), dtype=torch.int64).random_().item())
-        key = (B, H, W, str(dev), int(ddim_step) if ddim else None, inject, seed, lib.hdiff_get_contraction_mode(), None, None,
-               None)                                                  # the last three: tile, tile_overlap, tile_batch
+        ddim_step = int(ddim_step) if ddim and seq is None else None
+        key = (B, H, W, str(dev), ddim_step, inject, seed, lib.hdiff_get_contraction_mode(), None, None, None, solver, spacing,
+               seq)                                    # the three None: tile, tile_overlap, tile_batch
         sp = self._plans.get(key)
         if sp is None or sp.unet is not self.model.plan_for(B, H, W, dev, True):
-            sp = _StepPlan(self, B, H, W, dev, int(ddim_step) if ddim else None, inject, seed)
+            sp = _StepPlan(self, B, H, W, dev, ddim_step, inject, seed, solver, seq)
             self._plans = {key: sp}                                  # a graph bakes its seed and contraction mode: keep one live plan
         sp.unet.plan.pack_weights()     # once per call: also catches writes through p.data, which p._version does not see
         self.model.dynamic_forward(torch.cat([img, img], dim=1))    # the reference runs it on every call (requires_grad only)

@@ -54,18 +54,20 @@ def write_res(path: str, result: Dict[str, object]) -> None:
 
 def evaluate(sampler, batches: Iterable, *, ddim_step: int, tile: Optional[int] = None, tile_overlap: Optional[int] = None,
              tile_batch: Optional[int] = None, save_dir: Optional[str] = None, collect: Optional[List[torch.Tensor]] = None,
-             meter=None) -> Dict[str, object]:
+             meter=None, solver: Optional[str] = None, spacing: Optional[str] = None) -> Dict[str, object]:
     """Samples and scores a set.  ``batches`` yields ``(input, target)`` or ``(input, target, names)``: CHW images in [0, 255] as
     ``Underwater_Dataset`` / ``Atmospheric_Dataset`` produce them, batched.  Per batch: ``out = sampler(input, ddim=True,
     unconditional_guidance_scale=1, ddim_step=ddim_step, tile=...)`` (rotinas.py:907), then ``(out + 1) / 2`` is scored against
     ``target / 255``.  ``collect``, a list, receives every ``out``.  With ``save_dir`` each result is written under its name
     (``<running index>.png`` without one) as uint8, and ``res.txt`` beside them.  ``meter``: a ``quality.QualityMeter`` to go on
-    filling (a new one by default).  Returns ``QualityMeter.compute()``'s dict."""
+    filling (a new one by default).  ``solver`` / ``spacing`` are the sampler's (``solver="dpmpp2m"``: DPM-Solver++(2M) on logSNR
+    time steps); ``None`` leaves the argument out of the call.  Returns ``QualityMeter.compute()``'s dict."""
     meter = quality.QualityMeter() if meter is None else meter
     dev = _device_of(sampler)
     if save_dir is not None:
         os.makedirs(save_dir, exist_ok=True)
     tile_kw = {} if tile is None else dict(tile=tile, tile_overlap=tile_overlap, tile_batch=tile_batch)
+    tile_kw.update({k: v for k, v in (("solver", solver), ("spacing", spacing)) if v is not None})
     done = 0
     with torch.no_grad():
         for batch in batches:
@@ -112,7 +114,7 @@ def test(config, epoch=None) -> Dict[str, Dict[str, object]]:
     through ``DynamicUNet`` (``config.T / channel / channel_mult / num_res_blocks``) loaded from ``config.pretrained_path`` (a
     state dict; ``module.`` prefixes are stripped), ``config.ddim_step`` DDIM steps, results under
     ``output/result/<checkpoint file>/<set>/`` (``config.result_root`` replaces ``output/result``).  Optional keys: ``tile``,
-    ``tile_overlap``, ``tile_batch`` (overlapping-window sampling), ``dataset_root`` (one root for both sets, or a dict by set
+    ``tile_overlap``, ``tile_batch`` (overlapping-window sampling), ``solver``, ``spacing`` (the sampler's; absent: the reference's DDIM), ``dataset_root`` (one root for both sets, or a dict by set
     name), ``transforms`` (the sets' ``transforms=``; default: their 256 x 256 resize), ``device_list`` (the first entry is used; default ``cuda:0``).  ``epoch`` is accepted and unused, as in the reference.
     Returns ``{set name: evaluate()'s dict}``."""
     from ..datasets import Atmospheric_Dataset, Underwater_Dataset
@@ -146,5 +148,6 @@ def test(config, epoch=None) -> Dict[str, Dict[str, object]]:
     for name, data in sets:
         results[name] = evaluate(sampler, _batched(data, int(_cfg(config, "batch_size"))), ddim_step=_cfg(config, "ddim_step"),
                                  tile=_cfg(config, "tile", None), tile_overlap=_cfg(config, "tile_overlap", None),
-                                 tile_batch=_cfg(config, "tile_batch", None), save_dir=os.path.join(base, name))
+                                 tile_batch=_cfg(config, "tile_batch", None), save_dir=os.path.join(base, name),
+                                 solver=_cfg(config, "solver", None), spacing=_cfg(config, "spacing", None))
     return results

@@ -482,6 +482,39 @@ typedef struct hdiff_cfg_ddim_loop_desc {
   uint32_t* done_counter;
 } hdiff_cfg_ddim_loop_desc;
 int hdiff_cfg_ddim_step_loop(const hdiff_cfg_ddim_loop_desc* d, hdiff_stream_t stream);
+/* One DPM-Solver++(2M) step (Lu et al. 2022, data-prediction form, multistep) with classifier-free guidance for the same sampler:
+ * one model evaluation per step like DDIM, second order through one history tensor.  k = *step_ptr (clamped into [0, nsteps)) is
+ * the POSITION in tau; tab[k] = {s1m, sa, A, B, C} in fp32 (DiffusionCondition.py: dpmpp_table -- s1m = sqrt(1 - a), sa = sqrt(a),
+ * A = sqrt(1 - a') / sqrt(1 - a), B and C the data-prediction weights of x0 and of the previous x0; C = 0 on first-order rows):
+ *   eps = (1+w)*eps_c - w*eps_u ; x0 = (x - eps*tab[k][0]) / tab[k][1]
+ *   clip_x0 != 0:  x0 = clamp(x0, -1, 1) (a NaN stays a NaN)
+ *   v = tab[k][2]*x + tab[k][3]*x0 ; tab[k][4] != 0:  v = v + tab[k][4]*x0_prev ; x0_prev = x0 ; x_next = v
+ * each written operation rounded once, w cast as in hdiff_ddpm_step.  x0_prev [n] is the caller's persistent history: it is NOT
+ * read when tab[k][4] == 0 (the first step of a loop, where it holds whatever the last call left, and the closing one) and always
+ * written.  Deterministic: no noise, no seed.  nan_flag is OR-ed with 1 on a NaN output.  x and x_next may alias.  Buffers that are
+ * all 16-byte aligned are accessed four floats at a time, with the same result. */
+int hdiff_cfg_dpmpp_step(const float* x, const float* eps_c, const float* eps_u, float* x_next, float* x0_prev,
+                         const float* tab /* [nsteps][5] */, const int32_t* step_ptr, int nsteps, double w, int clip_x0,
+                         int32_t* nan_flag, int64_t n, hdiff_stream_t stream);
+/* The same update with hdiff_cfg_ddim_step_loop's bookkeeping folded in (x_dup0 / x_dup1, the last workgroup's decrement of
+ * *step_ptr, t_tab[max(*step_ptr - 1, 0)] to t_next, the self-wrapping done_counter): ONE launch per step. */
+typedef struct hdiff_cfg_dpmpp_loop_desc {
+  const float* x; const float* eps_c; const float* eps_u;
+  float* x_next;
+  float* x0_prev;                     /* [n] fp32 history, read only when tab[k][4] != 0 */
+  const float* tab;                   /* [nsteps][5] fp32 */
+  const int64_t* t_tab;               /* [nsteps]; may be NULL when t_count = 0 */
+  int32_t* step_ptr;
+  int nsteps;
+  int clip_x0;
+  double w;
+  int32_t* nan_flag;
+  int64_t n;
+  float* x_dup0; float* x_dup1;       /* optional */
+  int64_t* t_next; int t_count;       /* optional (t_count = 0) */
+  uint32_t* done_counter;
+} hdiff_cfg_dpmpp_loop_desc;
+int hdiff_cfg_dpmpp_step_loop(const hdiff_cfg_dpmpp_loop_desc* d, hdiff_stream_t stream);
 /* step bookkeeping for the captured loop: t[b] = *step for all b (int64 vector for the embedding gather) */
 int hdiff_fill_t(int64_t* t, const int32_t* step_ptr, int B, hdiff_stream_t stream);
 int hdiff_step_decrement(int32_t* step_ptr, hdiff_stream_t stream);
@@ -505,6 +538,14 @@ int hdiff_fill_from_table(int64_t* dst, const int32_t* table, const int32_t* idx
 int hdiff_resize_nearest(const float* x, float* y, int BC, int H, int W, int OH, int OW, hdiff_stream_t stream);
 int hdiff_avgpool_global(const float* x, float* y, int BC, int HW, hdiff_stream_t stream);
 int hdiff_concat2(const float* a, const float* b, float* out, int B, int64_t n0, int64_t n1, hdiff_stream_t stream);
+/* One DPM-Solver++(2M) update of the same sampler (an addition to the reference; hdiff_cfg_dpmpp_step's update with eps as the model
+ * gives it): y0 = (y - eps*tab[k][0]) / tab[k][1] ; clip_x0 != 0: y0 = clamp(y0, -1, 1) ; v = tab[k][2]*y + tab[k][3]*y0 ;
+ * tab[k][4] != 0: v = v + tab[k][4]*x0_prev ; x0_prev = y0 ; y_next = v, with k = *step_ptr clamped into [0, nsteps) and
+ * tab[k] = {s1m, sa, A, B, C} in fp32 (dpmpp_table with shift = 1, final_alpha_bar = alphas_bar[0]).  x0_prev [n] is the caller's
+ * persistent history, not read when tab[k][4] == 0 and always written; nan_flag is OR-ed with 1 on a NaN output; y and y_next may
+ * alias. */
+int hdiff_dpmpp_step(const float* y, const float* eps, float* y_next, float* x0_prev, const float* tab /* [nsteps][5] */,
+                     const int32_t* step_ptr, int nsteps, int clip_x0, int32_t* nan_flag, int64_t n, hdiff_stream_t stream);
 /* ------------------------------------------------------------------------------------------------------------------
  * Overlapping-window DDIM sampling of the second tree's sampler (the `tile=` argument; an addition to the reference).
  * Layout: per axis a table of window origins (origin_y[ny], origin_x[nx]); window (b, iy, ix) has index (b*ny + iy)*nx + ix
@@ -529,6 +570,14 @@ int hdiff_tile_ddim_step(float* y, const float* eps_w, const int32_t* first_y, c
                          const int32_t* count_x, const float* weight_x /* [W][3] */, const int32_t* origin_x, const float* tab,
                          const int32_t* step_ptr, int nsteps, int32_t* nan_flag, int B, int C, int H, int W, int ny, int nx,
                          int th, int tw, hdiff_stream_t stream);
+/* hdiff_tile_ddim_step's blend of the windows' noise estimates, in its fixed order, followed by hdiff_dpmpp_step's update on the full
+ * image y [B][C][H][W], in place, with a full-size history x0_prev [B][C][H][W] (every pixel is read and written by one thread).
+ * Same tables, clamping and repeatability; one window of weight 1.0 gives hdiff_dpmpp_step bit for bit. */
+int hdiff_tile_dpmpp_step(float* y, const float* eps_w, float* x0_prev, const int32_t* first_y, const int32_t* count_y,
+                          const float* weight_y /* [H][3] */, const int32_t* origin_y, const int32_t* first_x,
+                          const int32_t* count_x, const float* weight_x /* [W][3] */, const int32_t* origin_x,
+                          const float* tab /* [nsteps][5] */, const int32_t* step_ptr, int nsteps, int clip_x0, int32_t* nan_flag,
+                          int B, int C, int H, int W, int ny, int nx, int th, int tw, hdiff_stream_t stream);
 /* ------------------------------------------------------------------------------------------------------------------
  * Trainer of the second tree (diffusion/Diffusion.py:26-180) and the backward passes of its image encoder / skip resize.
  *   hdiff_train_b_loss_fwd   from noise_pred, noise, y_t, gt [B][3][HW] and t: mse = (noise_pred - noise)^2,

@@ -3,10 +3,11 @@ T-step ancestral loop against the strided DDIM sampler, ALTERNATELY inside one p
 each timing (bench.ClockSampler).
 
     python tools/bench_sample_a.py [--ddim-steps 50] [--eta 0] [--T 1000] [--size 256] [--batch 8] [--contract bf16x3|f32|f16]
-                                   [--alternate 2] [--no-ancestral]
+                                   [--alternate 2] [--no-ancestral] [--solver ddim|dpmpp2m|both] [--spacing uniform|logsnr]
 
 One call = everything a user waits for: weight pack, loop state reset, S (or T) graph replays, the NaN check and the final clip;
-the first call of each arm (plan build + graph capture) is printed as a warm-up and not counted.  --T is the length of the sampler's
+--solver chooses the update of the strided arm (dpmpp2m: DPM-Solver++(2M); both: one arm each, alternating), --spacing its time steps
+(default: the solver's own).  The first call of each arm (plan build + graph capture) is printed as a warm-up and not counted.  --T is the length of the sampler's
 schedule, i.e. the number of steps of the ancestral arm (the model keeps bench.py's T = 1000 embedding table; a shorter schedule
 makes the ancestral arm affordable, its time per step is the same).  Prints one line per timing and one JSON summary line."""
 import argparse
@@ -30,7 +31,9 @@ ap.add_argument("--size", type=int, default=256)
 ap.add_argument("--batch", type=int, default=8)
 ap.add_argument("--contract", choices=["f32", "bf16x3", "f16"], default="bf16x3")
 ap.add_argument("--alternate", type=int, default=2)
-ap.add_argument("--no-ancestral", action="store_true", help="time the DDIM arm alone")
+ap.add_argument("--no-ancestral", action="store_true", help="time the strided arm(s) alone")
+ap.add_argument("--solver", choices=["ddim", "dpmpp2m", "both"], default="ddim")
+ap.add_argument("--spacing", choices=["uniform", "logsnr"], default=None)
 a = ap.parse_args()
 assert 1 <= a.T <= bench.MODEL["T"], "--T cannot exceed the model's time-embedding table"
 dev = torch.device("cuda", 0)
@@ -45,8 +48,12 @@ labels = (torch.arange(a.batch) % 2 + 1).to(dev)
 arms = {}
 if not a.no_ancestral:
     arms["ancestral"] = (GaussianDiffusionSampler(model, *bench.BETA, a.T, w=bench.GUIDANCE_W).to(dev), {}, a.T)
-arms[f"ddim{a.ddim_steps}"] = (GaussianDiffusionSampler(model, *bench.BETA, a.T, w=bench.GUIDANCE_W).to(dev),
-                               dict(ddim_steps=a.ddim_steps, eta=a.eta), len(ddim_timesteps(a.T, a.ddim_steps)))
+for solver in (("ddim", "dpmpp2m") if a.solver == "both" else (a.solver,)):
+    kw = dict(ddim_steps=a.ddim_steps, eta=a.eta if solver == "ddim" else 0.0)            # dpmpp2m is deterministic
+    if solver != "ddim" or a.spacing is not None:                                         # the plain DDIM arm is called as before
+        kw.update(solver=solver, spacing=a.spacing)
+    arms[f"{solver}{a.ddim_steps}"] = (GaussianDiffusionSampler(model, *bench.BETA, a.T, w=bench.GUIDANCE_W).to(dev), kw,
+                                       len(ddim_timesteps(a.T, a.ddim_steps)))
 times = {name: [] for name in arms}
 clocks = {name: [] for name in arms}
 try:
@@ -80,5 +87,5 @@ for name, (sampler, kw, steps) in arms.items():
         summary[name] = {"steps": steps, "s_per_batch_mean": mean, "s_per_batch_min": min(t), "s_per_batch_max": max(t),
                          "ms_per_step_mean": mean / steps * 1e3, "images_per_s": a.batch / mean, "repetitions": len(t),
                          "sclk_mhz_board_w": clocks[name]}
-print(json.dumps({"metric": f"whole sampler forward, ancestral against strided DDIM, alternating ({a.size}x{a.size}, batch {a.batch}, "
-                            f"schedule T = {a.T}, {a.contract}, hipGraph replay)", "unit": "s/batch", "eta": a.eta, "arms": summary}))
+print(json.dumps({"metric": f"whole sampler forward, {'' if a.no_ancestral else 'ancestral against '}strided {' and '.join(n for n in arms if n != 'ancestral')}, alternating ({a.size}x{a.size}, batch {a.batch}, "
+                            f"schedule T = {a.T}, {a.contract}, hipGraph replay)", "unit": "s/batch", "eta": a.eta, "spacing": a.spacing, "arms": summary}))
