@@ -16,7 +16,9 @@ in S <= T model evaluations with the strided DDIM update (Song et al. 2021) unde
 with ``hdiff_cfg_ddim_step_loop`` as its one update kernel; ``ddim_timesteps`` and ``ddim_table`` are its schedule, usable on the CPU.
 ``solver="dpmpp2m"`` replaces that first-order update by DPM-Solver++(2M) (Lu et al. 2022: data prediction, multistep) -- still one
 model evaluation and ONE update kernel per step (``hdiff_cfg_dpmpp_step_loop``), one more state tensor -- on the logSNR-uniform time
-steps of ``logsnr_timesteps``, with the coefficients of ``dpmpp_table``; both are shared with the image-conditioned sampler.
+steps of ``logsnr_timesteps``, with the coefficients of ``dpmpp_table``.  The four schedule functions live in ``schedules.py``
+(CPU-only, shared with the image-conditioned sampler) and are re-exported here; every update kernel of both samplers is in
+``csrc/sampler_step.hip``.
 """
 from __future__ import annotations
 
@@ -30,14 +32,13 @@ import warnings
 
 from .. import _capi
 from .. import engine as E
+from ..engine import gpu_input as _gpu_input, index_vector as _timesteps
+from ..schedules import (_checked_timesteps, check_solver_spacing, ddim_table, ddim_timesteps, dpmpp_table, logsnr_timesteps,
+                         spacing_of)
 
 
 __all__ = ["extract", "GaussianDiffusionTrainer", "GaussianDiffusionSampler", "ddim_timesteps", "ddim_table", "logsnr_timesteps",
            "dpmpp_table"]
-
-SOLVERS = ("ddim", "dpmpp2m")
-SPACINGS = ("uniform", "logsnr")
-
 
 def extract(v, t, x_shape):
     """Coefficients at the given timesteps, cast float64 -> fp32 AFTER the gather, shaped [B,1,1,...] (reference :9-16)."""
@@ -45,163 +46,8 @@ def extract(v, t, x_shape):
     return out.view([t.shape[0]] + [1] * (len(x_shape) - 1))
 
 
-def ddim_timesteps(T: int, S: int) -> List[int]:
-    """The S time steps a strided sampler visits out of T: ``tau_k = ((k + 1) * T) // S - 1`` for k = 0 .. S-1 in integer
-    arithmetic -- strictly increasing for 1 <= S <= T, always ending at T - 1 (the step x_T belongs to); S = T gives 0 .. T-1,
-    (1000, 50) gives 19, 39, ..., 999.  ``ValueError`` for S outside [1, T] or not an integer."""
-    if int(S) != S or int(T) != T:
-        raise ValueError(f"ddim_steps and T must be integers, got {S!r} out of {T!r}")
-    T, S = int(T), int(S)
-    if not 1 <= S <= T:
-        raise ValueError(f"ddim_steps must lie in [1, T = {T}], got {S}")
-    return [((k + 1) * T) // S - 1 for k in range(S)]
-
-
-def _checked_timesteps(timesteps: Sequence[int], T: int) -> Tuple[int, ...]:
-    given = list(timesteps)                    # once: a generator is consumed by the first pass over it
-    tau = tuple(int(t) for t in given)
-    if len(tau) < 1 or any(a != b for a, b in zip(tau, given)):
-        raise ValueError("timesteps must be a non-empty list of integers")
-    if tau[0] < 0 or tau[-1] >= T or any(b <= a for a, b in zip(tau, tau[1:])):
-        raise ValueError(f"timesteps must be strictly increasing and lie in [0, T = {T}), got {list(tau)[:8]}"
-                         f"{' ...' if len(tau) > 8 else ''}")
-    return tau
-
-
-def ddim_table(betas: torch.Tensor, timesteps: Sequence[int], eta: float = 0.0) -> torch.Tensor:
-    """Coefficients of the strided DDIM update, float64 ``[S, 5]``, row k = ``(s1m, sa, san, c2, sigma)`` for the step from
-    ``tau_k`` to ``tau_(k-1)``.  With ``ab = cumprod(1 - betas)``, ``a = ab[tau_k]`` and ``a' = ab[tau_(k-1)]`` (``a' = 1`` at k = 0):
-
-        sigma = eta * sqrt((1 - a') / (1 - a)) * sqrt(1 - a / a')
-        s1m = sqrt(1 - a),  sa = sqrt(a),  san = sqrt(a'),  c2 = sqrt(max(1 - a' - sigma^2, 0))
-
-    and one step is ``x0 = (x - eps * s1m) / sa ; x' = san * x0 + c2 * eps + sigma * z``.  ``eta = 0`` is the deterministic DDIM;
-    ``eta = 1`` at stride 1 is the ancestral sampler with the POSTERIOR variance (``sigma^2 == posterior_var``,
-    ``san / sa == coeff1``, ``san * s1m / sa - c2 == coeff2``), not the reference's fixed-large variance.  Computed on the CPU."""
-    b = torch.as_tensor(betas).detach().to(device="cpu", dtype=torch.float64)
-    tau = _checked_timesteps(timesteps, int(b.numel()))
-    eta = float(eta)
-    if not eta >= 0.0:
-        raise ValueError(f"eta must be >= 0, got {eta}")
-    ab = torch.cumprod(1.0 - b, dim=0)
-    idx = torch.tensor(tau, dtype=torch.int64)
-    a = ab[idx]
-    a_prev = torch.cat([torch.ones(1, dtype=torch.float64), a[:-1]])
-    sigma = eta * torch.sqrt((1.0 - a_prev) / (1.0 - a)) * torch.sqrt(1.0 - a / a_prev)
-    c2 = torch.sqrt(torch.clamp(1.0 - a_prev - sigma * sigma, min=0.0))
-    return torch.stack([torch.sqrt(1.0 - a), torch.sqrt(a), torch.sqrt(a_prev), c2, sigma], dim=1)
-
-
-def _alphas_bar(betas) -> torch.Tensor:
-    return torch.cumprod(1.0 - torch.as_tensor(betas).detach().to(device="cpu", dtype=torch.float64).reshape(-1), dim=0)
-
-
-def _int_shift(shift) -> int:
-    if isinstance(shift, bool) or int(shift) != shift or int(shift) < 0:
-        raise ValueError(f"shift must be an integer >= 0, got {shift!r}")
-    return int(shift)
-
-
-def logsnr_timesteps(betas, S: int, shift: int = 0) -> List[int]:
-    """S time steps spaced uniformly in the half log signal-to-noise ratio ``lam[t] = 0.5 * log(ab / (1 - ab))`` at
-    ``ab = cumprod(1 - betas)[t + shift]``, t = 0 .. hi = T - 1 - shift (``shift = 1``: the image-conditioned sampler, which reads
-    ``alphas_bar[t + 1]``): the index nearest to each of the S targets between ``lam[0]`` and ``lam[hi]`` (the lowest on a tie), then
-    made strictly increasing by a forward pass ``idx_k >= idx_(k-1) + 1``, a cap of the last at hi and a backward pass
-    ``idx_k <= idx_(k+1) - 1``.  Always S entries, from 0 to hi; ``S = 1`` gives ``[hi]``.  A multistep solver needs such steps: on
-    index-uniform ones the last logSNR interval of a linear-beta schedule is several times the one before it.  ``ValueError`` for S
-    outside [1, hi + 1] or not an integer.  Computed on the CPU in float64."""
-    shift = _int_shift(shift)
-    ab = _alphas_bar(betas)
-    hi = int(ab.numel()) - 1 - shift
-    if isinstance(S, bool) or int(S) != S:
-        raise ValueError(f"the number of steps must be an integer, got {S!r}")
-    S = int(S)
-    if hi < 0 or not 1 <= S <= hi + 1:
-        raise ValueError(f"the number of steps must lie in [1, {hi + 1}], got {S}")
-    if S == 1:
-        return [hi]
-    v = ab[shift:]
-    lam = 0.5 * torch.log(v / (1.0 - v))
-    idx = []
-    for k in range(S):
-        d = (lam - (lam[0] + (lam[hi] - lam[0]) * k / (S - 1))).abs()
-        idx.append(int((d == d.min()).nonzero()[0]))
-    for k in range(1, S):
-        idx[k] = max(idx[k], idx[k - 1] + 1)
-    idx[S - 1] = min(idx[S - 1], hi)
-    for k in range(S - 2, -1, -1):
-        idx[k] = min(idx[k], idx[k + 1] - 1)
-    return idx
-
-
-def dpmpp_table(betas, timesteps: Sequence[int], shift: int = 0, final_alpha_bar: float = 1.0) -> torch.Tensor:
-    """Coefficients of DPM-Solver++(2M), float64 ``[S, 5]``, row k = ``(s1m, sa, A, B, C)`` for the step from ``tau_k`` to
-    ``tau_(k-1)`` (the loop runs k = S-1 down to 0).  With ``a = ab[tau_k + shift]``, ``a' = ab[tau_(k-1) + shift]`` (``a' =
-    final_alpha_bar`` at k = 0), ``lam(v) = 0.5 * log(v / (1 - v))`` and ``h = lam(a') - lam(a)``:
-
-        s1m = sqrt(1 - a),  sa = sqrt(a),  A = sqrt(1 - a') / sqrt(1 - a),  g = -sqrt(a') * expm1(-h)
-        first order (k = S-1: no history yet; k = 0: the closing step):   B = g,  C = 0
-        else, with r = h_(k+1) / h:                                        B = g * (1 + 1 / (2r)),  C = -g / (2r)
-
-    and one step is ``x0 = (x - eps * s1m) / sa ; x' = A * x + B * x0 + C * x0_prev`` (``x0_prev``: the x0 of the step before).  A
-    first-order row is the deterministic DDIM update written in x and x0.  Where ``a' = 1`` the row is exactly ``A = 0, B = 1, C = 0``
-    (h is infinite and is not formed).  Computed on the CPU; the samplers cast each entry to fp32 once."""
-    shift = _int_shift(shift)
-    ab = _alphas_bar(betas)
-    tau = _checked_timesteps(timesteps, int(ab.numel()) - shift)
-    final = torch.tensor(float(final_alpha_bar), dtype=torch.float64)
-    if not 0.0 < float(final) <= 1.0:
-        raise ValueError(f"final_alpha_bar must lie in (0, 1], got {final_alpha_bar}")
-
-    def lam(v):
-        return 0.5 * torch.log(v / (1.0 - v))
-
-    S = len(tau)
-    rows, h_prev = [None] * S, None
-    zero, one = torch.zeros((), dtype=torch.float64), torch.ones((), dtype=torch.float64)
-    for k in range(S - 1, -1, -1):
-        a = ab[tau[k] + shift]
-        a_next = ab[tau[k - 1] + shift] if k > 0 else final
-        if float(a_next) == 1.0:
-            A, B, Cc, h = zero, one, zero, None
-        else:
-            h = lam(a_next) - lam(a)
-            A = torch.sqrt(1.0 - a_next) / torch.sqrt(1.0 - a)
-            g = -torch.sqrt(a_next) * torch.expm1(-h)
-            if k == S - 1 or k == 0:
-                B, Cc = g, zero
-            else:
-                r = h_prev / h
-                B, Cc = g * (1.0 + 1.0 / (2.0 * r)), -g / (2.0 * r)
-        rows[k] = torch.stack([torch.sqrt(1.0 - a), torch.sqrt(a), A, B, Cc])
-        h_prev = h
-    return torch.stack(rows)
-
-
 def _stream(device) -> int:
     return torch.cuda.current_stream(device).cuda_stream
-
-
-def _gpu_input(x, name):
-    """A caller's tensor as the kernels need it: on the GPU (no CPU fallback), fp32 / integer, contiguous NCHW."""
-    if x.is_cuda and not x.is_contiguous():
-        x = x.contiguous()              # the reference accepts strided views; the kernels read dense NCHW
-    E.require_gpu_tensor(x, name)
-    return x
-
-
-def _timesteps(t, T: int, device):
-    """The index vector of ``extract`` (reference :9-16) as the kernels read it: int64, contiguous, on ``device``, and in
-    range -- ``torch.gather`` raises for an index outside [0, T), so does this (the kernels clamp on top: a bad index can
-    never fault the GPU)."""
-    if not torch.is_tensor(t) or t.dtype not in (torch.int64, torch.int32):
-        raise RuntimeError("gather(): Expected dtype int64 for index")
-    t = t.to(device=device, dtype=torch.int64).contiguous()
-    if t.numel():
-        lo, hi = torch.stack([t.min(), t.max()]).tolist()
-        if lo < 0 or hi >= T:
-            raise RuntimeError(f"index {hi if hi >= T else lo} is out of bounds for dimension 0 with size {T}")
-    return t
 
 
 class GaussianDiffusionTrainer(nn.Module):
@@ -269,78 +115,58 @@ class _SamplerPlan:
         self._variants = {}
         self._sampler = sampler
 
-    def _build_ddim(self, inject_noise: bool, ddim) -> E.Plan:
-        """The strided step: the same 2B UNet launches + ONE fused DDIM update with the same bookkeeping
-        (hdiff_cfg_ddim_step_loop); the device-resident counter is the position k in ``timesteps``, the time vector tau_k."""
-        timesteps, eta, clip_x0 = ddim
-        up, n, dev = self.unet, self.n, self.x.device
-        tab = ddim_table(self._sampler.betas, timesteps, eta).float().contiguous().to(dev)   # f64 -> f32 once per entry
-        t_tab = torch.tensor(timesteps, dtype=torch.int64, device=dev)
-        p = E.Plan(dev)
-        p.ops.extend(up.plan.ops)
+    def _loop_fields(self, d):
+        """What the three loop descriptors share: the state and the two eps halves, guidance, the flags, and the bookkeeping --
+        x_next into both halves of the UNet's input, the device-resident step, the next time vector."""
+        up, n = self.unet, self.n
         eps = up.out
-        d = _capi.CfgDdimLoopDesc()
         d.x, d.eps_c, d.eps_u = self.x.data_ptr(), eps.data_ptr(), eps.data_ptr() + 4 * n
-        d.noise = self.noise.data_ptr() if inject_noise else None
         d.x_next = self.x.data_ptr()
-        d.tab, d.t_tab = tab.data_ptr(), t_tab.data_ptr()
-        d.step_ptr, d.nsteps, d.clip_x0 = self.step.data_ptr(), len(timesteps), int(bool(clip_x0))
-        d.w, d.seed = float(self._sampler.w), self.seed
+        d.step_ptr, d.w = self.step.data_ptr(), float(self._sampler.w)
         d.nan_flag, d.n = self.nan_flag.data_ptr(), n
         d.x_dup0, d.x_dup1 = up.x.data_ptr(), up.x.data_ptr() + 4 * n
         d.t_next, d.t_count = up.t.data_ptr(), 2 * self.B
         d.done_counter = self.done.data_ptr()
-        p.keep((d, tab, t_tab))                    # the tables live exactly as long as the step that reads them
-        p.call("hdiff_cfg_ddim_step_loop", C.byref(d))
-        return p
+        return d
 
-    def _build_dpmpp(self, ddim) -> E.Plan:
-        """The DPM-Solver++(2M) step: the strided step's launches with hdiff_cfg_dpmpp_step_loop as the ONE update -- same counter,
-        same time vector; the plan owns the x0 history the update reads (from the second step on) and writes."""
-        timesteps, _, clip_x0 = ddim
-        up, n, dev = self.unet, self.n, self.x.device
-        tab = dpmpp_table(self._sampler.betas, timesteps).float().contiguous().to(dev)       # f64 -> f32 once per entry
-        t_tab = torch.tensor(timesteps, dtype=torch.int64, device=dev)
-        if self.x0_prev is None:
-            self.x0_prev = torch.empty_like(self.x)
-        p = E.Plan(dev)
-        p.ops.extend(up.plan.ops)
-        eps = up.out
-        d = _capi.CfgDpmppLoopDesc()
-        d.x, d.eps_c, d.eps_u = self.x.data_ptr(), eps.data_ptr(), eps.data_ptr() + 4 * n
-        d.x_next, d.x0_prev = self.x.data_ptr(), self.x0_prev.data_ptr()
-        d.tab, d.t_tab = tab.data_ptr(), t_tab.data_ptr()
-        d.step_ptr, d.nsteps, d.clip_x0 = self.step.data_ptr(), len(timesteps), int(bool(clip_x0))
-        d.w = float(self._sampler.w)
-        d.nan_flag, d.n = self.nan_flag.data_ptr(), n
-        d.x_dup0, d.x_dup1 = up.x.data_ptr(), up.x.data_ptr() + 4 * n
-        d.t_next, d.t_count = up.t.data_ptr(), 2 * self.B
-        d.done_counter = self.done.data_ptr()
-        p.keep((d, tab, t_tab))
-        p.call("hdiff_cfg_dpmpp_step_loop", C.byref(d))
-        return p
+    def _noise_fields(self, d, inject_noise: bool):
+        """The injected noise buffer (else the kernel draws its own from the seed) of the two descriptors that add noise."""
+        d.noise, d.seed = (self.noise.data_ptr() if inject_noise else None), self.seed
+        return d
 
-    def _build(self, inject_noise: bool) -> E.Plan:
+    def _build(self, inject_noise: bool, ddim=None, solver: str = "ddim") -> E.Plan:
         """One denoising step = the 2B UNet launches + ONE fused update kernel.  The update also writes x_next into both
-        halves of the UNet's input, decrements the device-resident step and refills the time vector (hdiff_ddpm_step_loop),
-        so nothing else has to run between two replays; `reset()` puts the loop state at its start."""
-        up, B, n = self.unet, self.B, self.n
-        p = E.Plan(self.x.device)
-        p.ops.extend(up.plan.ops)
-        eps = up.out
-        d = _capi.DdpmLoopDesc()
-        d.x, d.eps_c, d.eps_u = self.x.data_ptr(), eps.data_ptr(), eps.data_ptr() + 4 * n
-        d.noise = self.noise.data_ptr() if inject_noise else None
-        d.x_next = self.x.data_ptr()
-        d.coeff1, d.coeff2, d.sigma = self.c1.data_ptr(), self.c2.data_ptr(), self.sigma.data_ptr()
-        d.step_ptr, d.T = self.step.data_ptr(), int(self._sampler.T)
-        d.w, d.seed = float(self._sampler.w), self.seed
-        d.nan_flag, d.n = self.nan_flag.data_ptr(), n
-        d.x_dup0, d.x_dup1 = up.x.data_ptr(), up.x.data_ptr() + 4 * n
-        d.t_next, d.t_count = up.t.data_ptr(), 2 * B
-        d.done_counter = self.done.data_ptr()
-        p.keep(d)
-        p.call("hdiff_ddpm_step_loop", C.byref(d))
+        halves of the UNet's input, decrements the device-resident step and refills the time vector, so nothing else has to run
+        between two replays; `reset()` puts the loop state at its start.  Without ``ddim`` the ancestral step
+        (hdiff_ddpm_step_loop: the counter is the time step).  With ``ddim = (timesteps, eta, clip_x0)`` the strided step: the
+        counter is the position k in ``timesteps``, the time vector tau_k, the update hdiff_cfg_ddim_step_loop or, for
+        ``solver="dpmpp2m"``, hdiff_cfg_dpmpp_step_loop -- whose x0 history (read from the second step on, and written) the plan owns."""
+        dev = self.x.device
+        p = E.Plan(dev)
+        p.ops.extend(self.unet.plan.ops)
+        if ddim is None:
+            d = self._noise_fields(self._loop_fields(_capi.DdpmLoopDesc()), inject_noise)
+            d.coeff1, d.coeff2, d.sigma = self.c1.data_ptr(), self.c2.data_ptr(), self.sigma.data_ptr()
+            d.T = int(self._sampler.T)
+            p.keep(d)
+            p.call("hdiff_ddpm_step_loop", C.byref(d))
+            return p
+        timesteps, eta, clip_x0 = ddim
+        dpmpp = solver == "dpmpp2m"
+        tab = dpmpp_table(self._sampler.betas, timesteps) if dpmpp else ddim_table(self._sampler.betas, timesteps, eta)
+        tab = tab.float().contiguous().to(dev)                          # f64 -> f32 once per entry
+        t_tab = torch.tensor(timesteps, dtype=torch.int64, device=dev)
+        if dpmpp:
+            if self.x0_prev is None:
+                self.x0_prev = torch.empty_like(self.x)
+            d = self._loop_fields(_capi.CfgDpmppLoopDesc())
+            d.x0_prev = self.x0_prev.data_ptr()
+        else:
+            d = self._noise_fields(self._loop_fields(_capi.CfgDdimLoopDesc()), inject_noise)
+        d.tab, d.t_tab = tab.data_ptr(), t_tab.data_ptr()
+        d.nsteps, d.clip_x0 = len(timesteps), int(bool(clip_x0))
+        p.keep((d, tab, t_tab))                    # the tables live exactly as long as the step that reads them
+        p.call("hdiff_cfg_dpmpp_step_loop" if dpmpp else "hdiff_cfg_ddim_step_loop", C.byref(d))
         return p
 
     def reset(self, x_T: torch.Tensor, labels: torch.Tensor, step: Optional[int] = None, t: Optional[int] = None) -> None:
@@ -367,12 +193,7 @@ class _SamplerPlan:
         if key not in self._variants:
             self.seed = seed
             self._variants.clear()          # a graph bakes its seed (and the contraction mode): keep one live variant
-            if ddim is None:
-                self._variants[key] = self._build(inject_noise)
-            elif solver == "dpmpp2m":
-                self._variants[key] = self._build_dpmpp(ddim)
-            else:
-                self._variants[key] = self._build_ddim(inject_noise, ddim)
+            self._variants[key] = self._build(inject_noise, ddim, solver)
         return self._variants[key]
 
 
@@ -476,10 +297,7 @@ class GaussianDiffusionSampler(nn.Module):
     def _ddim_arguments(self, ddim_steps, eta, timesteps, clip_x0, noise_by_step, solver="ddim", spacing=None):
         """-> (None for the ancestral loop, else the validated (timesteps, eta, clip_x0) of the strided one; its solver);
         ``ValueError`` otherwise.  Looks at no device."""
-        if solver not in SOLVERS:
-            raise ValueError(f"solver must be one of {SOLVERS}, got {solver!r}")
-        if spacing is not None and spacing not in SPACINGS:
-            raise ValueError(f"spacing must be None or one of {SPACINGS}, got {spacing!r}")
+        check_solver_spacing(solver, spacing)
         if ddim_steps is None and timesteps is None:
             if float(eta) != 0.0 or clip_x0:
                 raise ValueError("eta / clip_x0 belong to the strided sampler: give ddim_steps or timesteps with them")
@@ -492,7 +310,7 @@ class GaussianDiffusionSampler(nn.Module):
             if spacing is not None:
                 raise ValueError("spacing chooses the time steps of ddim_steps: it does not go with an explicit timesteps list")
             tau = _checked_timesteps(timesteps, int(self.T))
-        elif (spacing or ("logsnr" if solver == "dpmpp2m" else "uniform")) == "logsnr":
+        elif spacing_of(solver, spacing) == "logsnr":
             tau = tuple(logsnr_timesteps(self.betas, ddim_steps))
         else:
             tau = tuple(ddim_timesteps(self.T, ddim_steps))

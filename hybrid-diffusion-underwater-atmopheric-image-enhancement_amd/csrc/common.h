@@ -33,6 +33,23 @@ void set_error(const char* fmt, ...);
 
 static inline int cdiv(int a, int b) { return (a + b - 1) / b; }
 
+// Workgroups of 256 threads for a grid-stride loop over n elements, per_thread of them at a time.  Two formulas are in use; they
+// differ in cap and rounding and give different grids above about 2 M elements, so each launcher names the one it was measured with.
+// floor(n / per_thread) rounded up to workgroups, at most 2048: small_ops.hip, and the DDPM / CFG-DDIM steps of sampler_step.hip
+static inline int grid_floor_2k(int64_t n, int per_thread = 1) {
+  int64_t blocks = (n / per_thread + 255) / 256;
+  if (blocks < 1) blocks = 1;
+  if (blocks > 2048) blocks = 2048;
+  return (int)blocks;
+}
+// ceil(n / (256 * per_thread)), at most 8192: model_b_ops.hip and every other kernel of sampler_step.hip
+static inline int grid_ceil_8k(int64_t n, int per_thread = 1) {
+  int64_t blocks = (n + (int64_t)256 * per_thread - 1) / ((int64_t)256 * per_thread);
+  if (blocks > 256 * 32) blocks = 256 * 32;
+  if (blocks < 1) blocks = 1;
+  return (int)blocks;
+}
+
 // hipFuncSetAttribute is per DEVICE: true the first time the calling site (one `static uint64_t` mask each) runs with the
 // current device, so that a process using several GPUs raises the dynamic-LDS limit on each of them.
 static inline bool first_use_on_device(uint64_t& mask) {

@@ -1,10 +1,12 @@
-// Small dense layers, the DDPM elementwise steps and the in-graph normal generator (gfx950).
+// Small dense layers, the elementwise ops around the model (q_sample, squared error, clip, axpby, dropout masks) and the in-graph
+// normal generator (gfx950).  The samplers' per-step update kernels are in sampler_step.hip.
 // All HBM- or latency-bound; none of them shows up next to attention/conv at the target sizes, so they are written
 // for clarity: one wave per output of a GEMV, 16-byte grid-stride loops for the elementwise passes.
 #include "common.h"
 #include "device.h"
+#include "philox.h"
 
-// The DDPM elementwise steps must round exactly like the reference's separate mul / sub / add tensor ops:
+// q_sample and axpby must round exactly like the reference's separate mul / sub / add tensor ops:
 // fma contraction is forbidden in this file (hipcc defaults to -ffp-contract=fast for device code, and HIP's __fmul_rn
 // is a plain, contractible '*'): the Makefile compiles it with -ffp-contract=off and the pragma repeats it.
 #pragma clang fp contract(off)
@@ -78,46 +80,7 @@ __global__ void linear_rows_multi_kernel(const float* __restrict__ x0, const flo
   }
 }
 
-// ---------------------------------------------------------------------------------------------------------------------
-// Philox4x32-10 counter-based generator + Box-Muller: 4 normals per counter.
-// ---------------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ void philox_round(uint32_t (&c)[4], uint32_t k0, uint32_t k1) {
-  const uint64_t p0 = (uint64_t)0xD2511F53u * c[0];
-  const uint64_t p1 = (uint64_t)0xCD9E8D57u * c[2];
-  const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c[1] ^ k0;
-  const uint32_t n1 = (uint32_t)p1;
-  const uint32_t n2 = (uint32_t)(p0 >> 32) ^ c[3] ^ k1;
-  const uint32_t n3 = (uint32_t)p0;
-  c[0] = n0; c[1] = n1; c[2] = n2; c[3] = n3;
-}
-
-__device__ __forceinline__ void philox4x32_10(uint64_t seed, uint64_t ctr_lo, uint64_t ctr_hi, uint32_t (&out)[4]) {
-  uint32_t c[4] = {(uint32_t)ctr_lo, (uint32_t)(ctr_lo >> 32), (uint32_t)ctr_hi, (uint32_t)(ctr_hi >> 32)};
-  uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    philox_round(c, k0, k1);
-    k0 += 0x9E3779B9u;
-    k1 += 0xBB67AE85u;
-  }
-  out[0] = c[0]; out[1] = c[1]; out[2] = c[2]; out[3] = c[3];
-}
-
-__device__ __forceinline__ float4 normal4(uint64_t seed, uint64_t ctr_lo, uint64_t ctr_hi) {
-  uint32_t r[4];
-  philox4x32_10(seed, ctr_lo, ctr_hi, r);
-  // u in (0,1]: (r + 1) * 2^-32 ; Box-Muller on two pairs
-  const float u0 = ((float)(r[0] >> 8) + 1.0f) * (1.0f / 16777216.0f);
-  const float u1 = ((float)(r[1] >> 8) + 0.5f) * (1.0f / 16777216.0f);
-  const float u2 = ((float)(r[2] >> 8) + 1.0f) * (1.0f / 16777216.0f);
-  const float u3 = ((float)(r[3] >> 8) + 0.5f) * (1.0f / 16777216.0f);
-  const float ra = sqrtf(-2.0f * logf(u0)), rb = sqrtf(-2.0f * logf(u2));
-  float s0, c0, s1, c1;
-  sincosf(6.283185307179586f * u1, &s0, &c0);
-  sincosf(6.283185307179586f * u3, &s1, &c1);
-  return make_float4(ra * c0, ra * s0, rb * c1, rb * s1);
-}
-
+// The in-graph normal generator: Philox4x32-10 + Box-Muller (philox.h), 4 normals per counter.
 __global__ void randn_kernel(float* __restrict__ out, int64_t n, uint64_t seed, uint64_t offset) {
   const int64_t nq = (n + 3) >> 2;
   for (int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; q < nq; q += (int64_t)gridDim.x * blockDim.x) {
@@ -133,7 +96,7 @@ __global__ void randn_kernel(float* __restrict__ out, int64_t n, uint64_t seed, 
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
-// Diffusion elementwise steps (DiffusionCondition.py)
+// Diffusion elementwise ops (DiffusionCondition.py)
 // ---------------------------------------------------------------------------------------------------------------------
 __global__ void q_sample_kernel(const float* __restrict__ x0, const float* __restrict__ noise,
                                 const int64_t* __restrict__ t, const float* __restrict__ sa,
@@ -155,146 +118,6 @@ __global__ void sq_err_kernel(const float* __restrict__ a, const float* __restri
   }
 }
 
-// x_next = coeff1[t]*x - coeff2[t]*((1+w)*eps_c - w*eps_u) + sigma[t]*z   (DiffusionCondition.py:78-79, 95)
-// Written with separate multiplies/adds in the reference's order (no fma contraction across terms) so that the CPU
-// oracle and this kernel round identically given identical eps.
-// x and x_next may be the same buffer (the sampler updates in place): neither is __restrict__.
-struct DdpmStepK {
-  const float* x; const float* eps_c; const float* eps_u; const float* noise; float* x_next;
-  const float* coeff1; const float* coeff2; const float* sigma;
-  int32_t* step_ptr; int T; float w1, w; uint64_t seed; int32_t* nan_flag; int64_t n;
-  float* x_dup0; float* x_dup1; int64_t* t_next; int t_count; unsigned* done_counter;     // loop bookkeeping (all optional)
-};
-__global__ void ddpm_step_kernel(const DdpmStepK p) {
-  int step = *p.step_ptr;
-  step = step < 0 ? 0 : (step >= p.T ? p.T - 1 : step);        // never index outside the schedule tables, whatever the counter holds
-  const float c1 = p.coeff1[step], c2 = p.coeff2[step], sg = p.sigma[step];
-  const bool add_noise = step > 0;
-  const float* x = p.x;
-  float* x_next = p.x_next;
-  bool bad = false;
-  const int64_t n = p.n, nq = (n + 3) >> 2;
-  for (int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; q < nq; q += (int64_t)gridDim.x * blockDim.x) {
-    const int64_t i0 = q << 2;
-    float z[4] = {0.f, 0.f, 0.f, 0.f};
-    if (add_noise && p.noise == nullptr) {
-      const float4 zz = normal4(p.seed, (uint64_t)q, (uint64_t)(uint32_t)step);
-      z[0] = zz.x; z[1] = zz.y; z[2] = zz.z; z[3] = zz.w;
-    }
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      const int64_t i = i0 + e;
-      if (i < n) {
-        if (add_noise && p.noise != nullptr) z[e] = p.noise[i];
-        const float eps = p.w1 * p.eps_c[i] - p.w * p.eps_u[i];
-        const float mean = c1 * x[i] - c2 * eps;
-        const float v = add_noise ? mean + sg * z[e] : mean;
-        bad |= (v != v);
-        x_next[i] = v;
-        if (p.x_dup0) p.x_dup0[i] = v;
-        if (p.x_dup1) p.x_dup1[i] = v;
-      }
-    }
-  }
-  if (__any(bad)) {
-    if ((threadIdx.x & 63) == 0) atomicOr(p.nan_flag, 1);
-  }
-  // Loop bookkeeping of the captured sampler step (DiffusionCondition.py:87-89: `for time_step in reversed(range(T))`,
-  // `t = x_t.new_ones([B]) * time_step`): the workgroup that finishes LAST -- every other one has read *step_ptr by then --
-  // decrements the device-resident step and writes the next step's time vector.  The counter wraps back to 0 by itself.
-  if (p.done_counter != nullptr) {
-    __shared__ int is_last;
-    __syncthreads();
-    if (threadIdx.x == 0) is_last = atomicInc(p.done_counter, gridDim.x - 1) == gridDim.x - 1;
-    __syncthreads();
-    if (is_last) {
-      const int next = *p.step_ptr - 1;
-      for (int i = threadIdx.x; i < p.t_count; i += blockDim.x) p.t_next[i] = (int64_t)(next < 0 ? 0 : next);
-      if (threadIdx.x == 0) *p.step_ptr = next;
-    }
-  }
-}
-
-// One strided DDIM step with classifier-free guidance (Song et al. 2021, eq. 12, on a sub-sequence tau of the T training steps):
-//   eps = (1+w)*eps_c - w*eps_u ; x0 = (x - eps*s1m) / sa ; [x0 = clamp(x0, -1, 1) ; eps = (x - sa*x0) / s1m]
-//   v = san*x0 + c2*eps (+ sigma*z when k > 0 and sigma > 0),   tab[k] = {s1m, sa, san, c2, sigma} of position k in tau
-// one rounding per written operation (contraction is off in this file), so a plain torch program of the same lines gives the same
-// bits.  The clamp is written with compares: a NaN stays a NaN (torch.clamp), fminf / fmaxf would swallow it.
-// The bookkeeping is ddpm_step_kernel's: x_next also goes to the two halves of the next UNet input, the workgroup that finishes
-// last decrements the device-resident position and writes the next time vector, here tau[k - 1] from t_tab.
-// x and x_next may be the same buffer: neither is __restrict__.
-struct CfgDdimStepK {
-  const float* x; const float* eps_c; const float* eps_u; const float* noise; float* x_next;
-  const float* tab; const int64_t* t_tab; int32_t* step_ptr; int nsteps; int clip_x0; float w1, w; uint64_t seed;
-  int32_t* nan_flag; int64_t n;
-  float* x_dup0; float* x_dup1; int64_t* t_next; int t_count; unsigned* done_counter;     // loop bookkeeping (all optional)
-};
-__global__ void cfg_ddim_step_kernel(const CfgDdimStepK p) {
-  int k = *p.step_ptr;
-  k = k < 0 ? 0 : (k >= p.nsteps ? p.nsteps - 1 : k);          // never index outside the tables, whatever the counter holds
-  const float* row = p.tab + 5 * (size_t)k;
-  const float s1m = row[0], sa = row[1], san = row[2], c2 = row[3], sg = row[4];
-  const bool add_noise = k > 0 && sg > 0.f;
-  const bool clip = p.clip_x0 != 0;
-  const float* x = p.x;
-  float* x_next = p.x_next;
-  bool bad = false;
-  const int64_t n = p.n, nq = (n + 3) >> 2;
-  for (int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; q < nq; q += (int64_t)gridDim.x * blockDim.x) {
-    const int64_t i0 = q << 2;
-    float z[4] = {0.f, 0.f, 0.f, 0.f};
-    if (add_noise && p.noise == nullptr) {
-      const float4 zz = normal4(p.seed, (uint64_t)q, (uint64_t)(uint32_t)k);
-      z[0] = zz.x; z[1] = zz.y; z[2] = zz.z; z[3] = zz.w;
-    }
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      const int64_t i = i0 + e;
-      if (i < n) {
-        if (add_noise && p.noise != nullptr) z[e] = p.noise[i];
-        const float xi = x[i];
-        float eps = p.w1 * p.eps_c[i] - p.w * p.eps_u[i];
-        float x0 = (xi - eps * s1m) / sa;
-        if (clip) {
-          x0 = x0 < -1.f ? -1.f : (x0 > 1.f ? 1.f : x0);
-          eps = (xi - sa * x0) / s1m;
-        }
-        float v = san * x0 + c2 * eps;
-        if (add_noise) v = v + sg * z[e];
-        bad |= (v != v);
-        x_next[i] = v;
-        if (p.x_dup0) p.x_dup0[i] = v;
-        if (p.x_dup1) p.x_dup1[i] = v;
-      }
-    }
-  }
-  if (__any(bad)) {
-    if ((threadIdx.x & 63) == 0) atomicOr(p.nan_flag, 1);
-  }
-  if (p.done_counter != nullptr) {
-    __shared__ int is_last;
-    __syncthreads();
-    if (threadIdx.x == 0) is_last = atomicInc(p.done_counter, gridDim.x - 1) == gridDim.x - 1;   // wraps back to 0 by itself
-    __syncthreads();
-    if (is_last) {
-      const int next = *p.step_ptr - 1;
-      const int kn = next < 0 ? 0 : (next >= p.nsteps ? p.nsteps - 1 : next);
-      if (p.t_count > 0) {
-        const int64_t t = p.t_tab[kn];
-        for (int i = threadIdx.x; i < p.t_count; i += blockDim.x) p.t_next[i] = t;
-      }
-      if (threadIdx.x == 0) *p.step_ptr = next;
-    }
-  }
-}
-
-__global__ void fill_t_kernel(int64_t* t, const int32_t* step_ptr, int B) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < B) t[i] = (int64_t)(*step_ptr);
-}
-__global__ void step_decrement_kernel(int32_t* step_ptr) {
-  if (threadIdx.x == 0 && blockIdx.x == 0) *step_ptr = *step_ptr - 1;
-}
 __global__ void clip_kernel(const float* __restrict__ x, float* __restrict__ y, float lo, float hi, int64_t n) {
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
     y[i] = fminf(fmaxf(x[i], lo), hi);
@@ -418,13 +241,6 @@ __global__ void mul_kernel(const float* __restrict__ a, const float* __restrict_
     out[i] = a[i] * b[i];
 }
 
-inline int grid_for(int64_t n, int per_thread = 1) {
-  int64_t blocks = (n / per_thread + 255) / 256;
-  if (blocks < 1) blocks = 1;
-  if (blocks > 2048) blocks = 2048;
-  return (int)blocks;
-}
-
 }  // namespace
 
 extern "C" {
@@ -456,64 +272,8 @@ int hdiff_q_sample(const float* x0, const float* noise, const int64_t* t, const 
 int hdiff_sq_err(const float* a, const float* b, float* out, int64_t n, hdiff_stream_t stream) {
   HDIFF_CHECK_ARG(a && b && out, "sq_err: null pointer");
   (void)hipGetLastError();  // drop any stale error left by another HIP user in this thread
-  hipLaunchKernelGGL(sq_err_kernel, dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream, a, b, out, n);
+  hipLaunchKernelGGL(sq_err_kernel, dim3(grid_floor_2k(n)), dim3(256), 0, (hipStream_t)stream, a, b, out, n);
   HDIFF_CHECK_LAUNCH("sq_err_kernel");
-  return HDIFF_OK;
-}
-
-int hdiff_ddpm_step(const float* x, const float* eps_c, const float* eps_u, const float* noise, float* x_next,
-                    const float* coeff1, const float* coeff2, const float* sigma, const int32_t* step_ptr, int T, double w,
-                    uint64_t seed, int32_t* nan_flag, int64_t n, hdiff_stream_t stream) {
-  HDIFF_CHECK_ARG(x && eps_c && eps_u && x_next && coeff1 && coeff2 && sigma && step_ptr && nan_flag,
-                  "ddpm_step: null pointer");
-  HDIFF_CHECK_ARG(T > 0 && n > 0, "ddpm_step: bad sizes T=%d n=%lld", T, (long long)n);
-  (void)hipGetLastError();  // drop any stale error left by another HIP user in this thread
-  DdpmStepK k{x, eps_c, eps_u, noise, x_next, coeff1, coeff2, sigma, const_cast<int32_t*>(step_ptr), T, (float)(1.0 + w),
-              (float)w, seed, nan_flag, n, nullptr, nullptr, nullptr, 0, nullptr};
-  hipLaunchKernelGGL(ddpm_step_kernel, dim3(grid_for(n, 4)), dim3(256), 0, (hipStream_t)stream, k);
-  HDIFF_CHECK_LAUNCH("ddpm_step_kernel");
-  return HDIFF_OK;
-}
-
-int hdiff_ddpm_step_loop(const hdiff_ddpm_loop_desc* d, hdiff_stream_t stream) {
-  HDIFF_CHECK_ARG(d && d->x && d->eps_c && d->eps_u && d->x_next && d->coeff1 && d->coeff2 && d->sigma && d->step_ptr &&
-                      d->nan_flag && d->done_counter,
-                  "ddpm_step_loop: null pointer");
-  HDIFF_CHECK_ARG(d->T > 0 && d->n > 0 && d->t_count >= 0 && (d->t_count == 0 || d->t_next),
-                  "ddpm_step_loop: bad sizes T=%d n=%lld t_count=%d", d->T, (long long)d->n, d->t_count);
-  (void)hipGetLastError();  // drop any stale error left by another HIP user in this thread
-  DdpmStepK k{d->x, d->eps_c, d->eps_u, d->noise, d->x_next, d->coeff1, d->coeff2, d->sigma, d->step_ptr, d->T,
-              (float)(1.0 + d->w), (float)d->w, d->seed, d->nan_flag, d->n, d->x_dup0, d->x_dup1, d->t_next, d->t_count,
-              d->done_counter};
-  hipLaunchKernelGGL(ddpm_step_kernel, dim3(grid_for(d->n, 4)), dim3(256), 0, (hipStream_t)stream, k);
-  HDIFF_CHECK_LAUNCH("ddpm_step_kernel");
-  return HDIFF_OK;
-}
-
-int hdiff_cfg_ddim_step(const float* x, const float* eps_c, const float* eps_u, const float* noise, float* x_next,
-                        const float* tab, const int32_t* step_ptr, int nsteps, double w, int clip_x0, uint64_t seed,
-                        int32_t* nan_flag, int64_t n, hdiff_stream_t stream) {
-  HDIFF_CHECK_ARG(x && eps_c && eps_u && x_next && tab && step_ptr && nan_flag, "cfg_ddim_step: null pointer");
-  HDIFF_CHECK_ARG(nsteps > 0 && n > 0, "cfg_ddim_step: bad sizes nsteps=%d n=%lld", nsteps, (long long)n);
-  (void)hipGetLastError();  // drop any stale error left by another HIP user in this thread
-  CfgDdimStepK k{x, eps_c, eps_u, noise, x_next, tab, nullptr, const_cast<int32_t*>(step_ptr), nsteps, clip_x0 != 0,
-                 (float)(1.0 + w), (float)w, seed, nan_flag, n, nullptr, nullptr, nullptr, 0, nullptr};
-  hipLaunchKernelGGL(cfg_ddim_step_kernel, dim3(grid_for(n, 4)), dim3(256), 0, (hipStream_t)stream, k);
-  HDIFF_CHECK_LAUNCH("cfg_ddim_step_kernel");
-  return HDIFF_OK;
-}
-
-int hdiff_cfg_ddim_step_loop(const hdiff_cfg_ddim_loop_desc* d, hdiff_stream_t stream) {
-  HDIFF_CHECK_ARG(d && d->x && d->eps_c && d->eps_u && d->x_next && d->tab && d->step_ptr && d->nan_flag && d->done_counter,
-                  "cfg_ddim_step_loop: null pointer");
-  HDIFF_CHECK_ARG(d->nsteps > 0 && d->n > 0 && d->t_count >= 0 && (d->t_count == 0 || (d->t_next && d->t_tab)),
-                  "cfg_ddim_step_loop: bad sizes nsteps=%d n=%lld t_count=%d", d->nsteps, (long long)d->n, d->t_count);
-  (void)hipGetLastError();  // drop any stale error left by another HIP user in this thread
-  CfgDdimStepK k{d->x, d->eps_c, d->eps_u, d->noise, d->x_next, d->tab, d->t_tab, d->step_ptr, d->nsteps, d->clip_x0 != 0,
-                 (float)(1.0 + d->w), (float)d->w, d->seed, d->nan_flag, d->n, d->x_dup0, d->x_dup1, d->t_next, d->t_count,
-                 d->done_counter};
-  hipLaunchKernelGGL(cfg_ddim_step_kernel, dim3(grid_for(d->n, 4)), dim3(256), 0, (hipStream_t)stream, k);
-  HDIFF_CHECK_LAUNCH("cfg_ddim_step_kernel");
   return HDIFF_OK;
 }
 
@@ -528,26 +288,10 @@ int hdiff_linear_rows_multi(const float* x0, const float* x1, const hdiff_linear
   return HDIFF_OK;
 }
 
-int hdiff_fill_t(int64_t* t, const int32_t* step_ptr, int B, hdiff_stream_t stream) {
-  HDIFF_CHECK_ARG(t && step_ptr && B > 0, "fill_t: bad arguments");
-  (void)hipGetLastError();  // drop any stale error left by another HIP user in this thread
-  hipLaunchKernelGGL(fill_t_kernel, dim3(cdiv(B, 64)), dim3(64), 0, (hipStream_t)stream, t, step_ptr, B);
-  HDIFF_CHECK_LAUNCH("fill_t_kernel");
-  return HDIFF_OK;
-}
-
-int hdiff_step_decrement(int32_t* step_ptr, hdiff_stream_t stream) {
-  HDIFF_CHECK_ARG(step_ptr, "step_decrement: null pointer");
-  (void)hipGetLastError();  // drop any stale error left by another HIP user in this thread
-  hipLaunchKernelGGL(step_decrement_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, step_ptr);
-  HDIFF_CHECK_LAUNCH("step_decrement_kernel");
-  return HDIFF_OK;
-}
-
 int hdiff_clip(const float* x, float* y, float lo, float hi, int64_t n, hdiff_stream_t stream) {
   HDIFF_CHECK_ARG(x && y, "clip: null pointer");
   (void)hipGetLastError();  // drop any stale error left by another HIP user in this thread
-  hipLaunchKernelGGL(clip_kernel, dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream, x, y, lo, hi, n);
+  hipLaunchKernelGGL(clip_kernel, dim3(grid_floor_2k(n)), dim3(256), 0, (hipStream_t)stream, x, y, lo, hi, n);
   HDIFF_CHECK_LAUNCH("clip_kernel");
   return HDIFF_OK;
 }
@@ -555,7 +299,7 @@ int hdiff_clip(const float* x, float* y, float lo, float hi, int64_t n, hdiff_st
 int hdiff_randn(float* out, int64_t n, uint64_t seed, uint64_t offset, hdiff_stream_t stream) {
   HDIFF_CHECK_ARG(out, "randn: null pointer");
   (void)hipGetLastError();  // drop any stale error left by another HIP user in this thread
-  hipLaunchKernelGGL(randn_kernel, dim3(grid_for(n, 4)), dim3(256), 0, (hipStream_t)stream, out, n, seed, offset);
+  hipLaunchKernelGGL(randn_kernel, dim3(grid_floor_2k(n, 4)), dim3(256), 0, (hipStream_t)stream, out, n, seed, offset);
   HDIFF_CHECK_LAUNCH("randn_kernel");
   return HDIFF_OK;
 }
@@ -563,7 +307,7 @@ int hdiff_randn(float* out, int64_t n, uint64_t seed, uint64_t offset, hdiff_str
 int hdiff_axpby(float a, const float* x, float b, const float* y, float* out, int64_t n, hdiff_stream_t stream) {
   HDIFF_CHECK_ARG(x && out, "axpby: null pointer");
   (void)hipGetLastError();  // drop any stale error left by another HIP user in this thread
-  hipLaunchKernelGGL(axpby_kernel, dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream, a, x, b, y, out, n);
+  hipLaunchKernelGGL(axpby_kernel, dim3(grid_floor_2k(n)), dim3(256), 0, (hipStream_t)stream, a, x, b, y, out, n);
   HDIFF_CHECK_LAUNCH("axpby_kernel");
   return HDIFF_OK;
 }
@@ -587,7 +331,7 @@ int hdiff_linear_rows_bwd(const float* x, const int64_t* idx, int n_rows, const 
 int hdiff_sq_err_bwd(const float* a, const float* b, const float* dloss, float* da, int64_t n, hdiff_stream_t stream) {
   HDIFF_CHECK_ARG(a && b && dloss && da, "sq_err_bwd: null pointer");
   (void)hipGetLastError();  // drop any stale error left by another HIP user in this thread
-  hipLaunchKernelGGL(sq_err_bwd_kernel, dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream, a, b, dloss, da, n);
+  hipLaunchKernelGGL(sq_err_bwd_kernel, dim3(grid_floor_2k(n)), dim3(256), 0, (hipStream_t)stream, a, b, dloss, da, n);
   HDIFF_CHECK_LAUNCH("sq_err_bwd_kernel");
   return HDIFF_OK;
 }
@@ -595,7 +339,7 @@ int hdiff_sq_err_bwd(const float* a, const float* b, const float* dloss, float* 
 int hdiff_dropout_mask(float* out, int64_t n, float keep, uint64_t seed, uint64_t offset, hdiff_stream_t stream) {
   HDIFF_CHECK_ARG(out && keep > 0.f && keep <= 1.f, "dropout_mask: bad arguments");
   (void)hipGetLastError();  // drop any stale error left by another HIP user in this thread
-  hipLaunchKernelGGL(dropout_mask_kernel, dim3(grid_for(n, 4)), dim3(256), 0, (hipStream_t)stream, out, n, keep, seed, offset);
+  hipLaunchKernelGGL(dropout_mask_kernel, dim3(grid_floor_2k(n, 4)), dim3(256), 0, (hipStream_t)stream, out, n, keep, seed, offset);
   HDIFF_CHECK_LAUNCH("dropout_mask_kernel");
   return HDIFF_OK;
 }
@@ -605,7 +349,7 @@ int hdiff_dropout_keep_bits(uint32_t* bits, int64_t n, float keep, uint64_t seed
   HDIFF_CHECK_ARG(n > 0, "dropout_keep_bits: n = %lld is not positive", (long long)n);
   HDIFF_CHECK_ARG(keep > 0.f && keep <= 1.f, "dropout_keep_bits: keep = %g is outside (0, 1]", (double)keep);
   (void)hipGetLastError();  // drop any stale error left by another HIP user in this thread
-  hipLaunchKernelGGL(dropout_keep_bits_kernel, dim3(grid_for((n + 31) >> 5)), dim3(256), 0, (hipStream_t)stream, bits, n, keep, seed,
+  hipLaunchKernelGGL(dropout_keep_bits_kernel, dim3(grid_floor_2k((n + 31) >> 5)), dim3(256), 0, (hipStream_t)stream, bits, n, keep, seed,
                      offset);
   HDIFF_CHECK_LAUNCH("dropout_keep_bits_kernel");
   return HDIFF_OK;
@@ -614,7 +358,7 @@ int hdiff_dropout_keep_bits(uint32_t* bits, int64_t n, float keep, uint64_t seed
 int hdiff_mul(const float* a, const float* b, float* out, int64_t n, hdiff_stream_t stream) {
   HDIFF_CHECK_ARG(a && b && out, "mul: null pointer");
   (void)hipGetLastError();  // drop any stale error left by another HIP user in this thread
-  hipLaunchKernelGGL(mul_kernel, dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream, a, b, out, n);
+  hipLaunchKernelGGL(mul_kernel, dim3(grid_floor_2k(n)), dim3(256), 0, (hipStream_t)stream, a, b, out, n);
   HDIFF_CHECK_LAUNCH("mul_kernel");
   return HDIFF_OK;
 }

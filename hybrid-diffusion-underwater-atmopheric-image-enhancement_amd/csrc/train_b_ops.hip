@@ -156,7 +156,7 @@ __global__ void avgpool_global_bwd_kernel(const float* __restrict__ dy, float* _
     dx[i] = dy[i / HW] / (float)HW;
 }
 
-// The forward's source index (ddim_ops.hip resize_nearest_kernel): min(floor(o * s), in - 1), s = (float)in / out.
+// The forward's source index (model_b_ops.hip resize_nearest_kernel): min(floor(o * s), in - 1), s = (float)in / out.
 __device__ __forceinline__ int nearest_src(int o, float s, int in) { return min((int)floorf(o * s), in - 1); }
 
 // First output index o in [0, out) with nearest_src(o) >= i (out if none): the source map is non-decreasing in o.

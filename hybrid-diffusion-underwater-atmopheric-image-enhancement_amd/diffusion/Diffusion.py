@@ -16,10 +16,10 @@ Kept as written in the reference, on purpose:
 Added to the reference's surface: ``forward(..., tile=, tile_overlap=, tile_batch=)`` samples an image of any size through
 overlapping model-sized windows (``tile_origins`` / ``tile_weights`` give the layout): every window is denoised at every step,
 the noise estimates are blended where they overlap and ONE DDIM update is applied to the full image
-(``csrc/tile_ops.hip``).  Without ``tile`` nothing changes.  ``forward(..., solver="dpmpp2m", spacing=, timesteps=)`` replaces the
+(``csrc/sampler_step.hip``).  Without ``tile`` nothing changes.  ``forward(..., solver="dpmpp2m", spacing=, timesteps=)`` replaces the
 first-order DDIM update by DPM-Solver++(2M) on logSNR-uniform time steps (``dpmpp_table`` / ``logsnr_timesteps`` of
-``DiffusionFreeGuidence.DiffusionCondition`` with ``shift=1``: this sampler reads ``alphas_bar[t + 1]``) -- still one model
-evaluation and one update kernel per step (``csrc/dpmpp_ops.hip``), untiled and over windows.  Without ``solver`` nothing changes.
+``schedules`` with ``shift=1``: this sampler reads ``alphas_bar[t + 1]``) -- still one model evaluation and one update kernel per
+step (the same file), untiled and over windows.  Without ``solver`` nothing changes.
 
 Trainer underneath: q_sample and the 3 + 3 channel concat are HIP launches, the DynamicUNet runs its autograd path
 (``autograd.dyn_unet_forward_with_grad``) and the loss tail -- the squared error, ``y_0_pred`` and the angular-colour term,
@@ -41,8 +41,8 @@ import torch.nn.functional as F
 
 from .. import _capi
 from .. import engine as E
-from ..DiffusionFreeGuidence.DiffusionCondition import (SOLVERS, SPACINGS, _checked_timesteps, _gpu_input, _timesteps, dpmpp_table,
-                                                         logsnr_timesteps)
+from ..engine import gpu_input as _gpu_input, index_vector as _timesteps
+from ..schedules import _checked_timesteps, check_solver_spacing, dpmpp_table, logsnr_timesteps, spacing_of
 
 __all__ = ["extract", "GaussianDiffusionTrainer", "GaussianDiffusionSampler", "tile_origins", "tile_weights", "logsnr_timesteps",
            "dpmpp_table"]
@@ -242,6 +242,15 @@ def _ddim_tables(sampler: "GaussianDiffusionSampler", ddim_step: Optional[int], 
     return tab, torch.tensor(seq, dtype=torch.int32, device=device)
 
 
+def _loop_tables(sampler: "GaussianDiffusionSampler", B: int, H: int, W: int, device, ddim_step: Optional[int], seq, solver: str):
+    """-> (tab, t_tab, x0_prev) of the DDIM loop on the increasing time steps ``seq`` (None: the reference's, from ``ddim_step``).
+    ``x0_prev`` is the full-size history solver="dpmpp2m" reads (from the second step on) and writes, else None."""
+    if solver == "dpmpp2m":
+        tab, t_tab = _dpmpp_tables(sampler, _uniform_sequence(ddim_step) if seq is None else seq, device)
+        return tab, t_tab, torch.empty(B, 3, H, W, device=device)
+    return _ddim_tables(sampler, ddim_step, device, seq) + (None,)
+
+
 class _StepPlan:
     """One captured sampling step for a fixed (B, H, W) and mode: fill t -> DynamicUNet -> update -> advance the counter."""
 
@@ -255,6 +264,7 @@ class _StepPlan:
                                "dimension 3")
         n = B * 3 * H * W
         self.B, self.n = B, n
+        self.n_slots, self.th, self.tw = B, H, W          # what the UNet plan was made for (the names of _TiledStepPlan)
         self.step = torch.zeros(1, dtype=torch.int32, device=device)
         self.nan_flag = torch.zeros(1, dtype=torch.int32, device=device)
         self.noise = torch.empty(B, 3, H, W, device=device)
@@ -273,22 +283,17 @@ class _StepPlan:
                    self.noise.data_ptr() if inject_noise else None, up.y.data_ptr(), self.c1.data_ptr(), self.c2.data_ptr(),
                    self.sigma.data_ptr(), self.step.data_ptr(), int(sampler.T), C.c_double(0.0), C.c_uint64(seed),
                    self.nan_flag.data_ptr(), n)
-        elif solver == "dpmpp2m":
-            # the same step with the second-order update; the plan owns the x0 history it reads (from the second step on) and writes
-            self.tab, self.t_tab = _dpmpp_tables(sampler, _uniform_sequence(ddim_step) if seq is None else seq, device)
-            self.n_steps = int(self.t_tab.numel())
-            self.x0_prev = torch.empty(B, 3, H, W, device=device)
-            p.call("hdiff_fill_from_table", up.t.data_ptr(), self.t_tab.data_ptr(), self.step.data_ptr(), self.n_steps, B)
-            p.ops.extend(up.plan.ops)
-            p.call("hdiff_dpmpp_step", up.y.data_ptr(), up.out.data_ptr(), up.y.data_ptr(), self.x0_prev.data_ptr(),
-                   self.tab.data_ptr(), self.step.data_ptr(), self.n_steps, 0, self.nan_flag.data_ptr(), n)
         else:
-            self.tab, self.t_tab = _ddim_tables(sampler, ddim_step, device, seq)
+            self.tab, self.t_tab, self.x0_prev = _loop_tables(sampler, B, H, W, device, ddim_step, seq, solver)
             self.n_steps = int(self.t_tab.numel())
             p.call("hdiff_fill_from_table", up.t.data_ptr(), self.t_tab.data_ptr(), self.step.data_ptr(), self.n_steps, B)
             p.ops.extend(up.plan.ops)
-            p.call("hdiff_ddim_step", up.y.data_ptr(), up.out.data_ptr(), up.y.data_ptr(), self.tab.data_ptr(),
-                   self.step.data_ptr(), self.n_steps, self.nan_flag.data_ptr(), n)
+            if solver == "dpmpp2m":         # the same step with the second-order update; the plan owns the x0 history
+                p.call("hdiff_dpmpp_step", up.y.data_ptr(), up.out.data_ptr(), up.y.data_ptr(), self.x0_prev.data_ptr(),
+                       self.tab.data_ptr(), self.step.data_ptr(), self.n_steps, 0, self.nan_flag.data_ptr(), n)
+            else:
+                p.call("hdiff_ddim_step", up.y.data_ptr(), up.out.data_ptr(), up.y.data_ptr(), self.tab.data_ptr(),
+                       self.step.data_ptr(), self.n_steps, self.nan_flag.data_ptr(), n)
         p.call("hdiff_step_decrement", self.step.data_ptr())
         self.plan = p
 
@@ -326,11 +331,7 @@ class _TiledStepPlan:
         fx, cx, wx = tile_weights(W, tile, overlap)
         self.fy, self.cy, self.wy = fy.to(device), cy.to(device), wy.float().to(device).contiguous()    # fp32 cast: once, here
         self.fx, self.cx, self.wx = fx.to(device), cx.to(device), wx.float().to(device).contiguous()
-        if solver == "dpmpp2m":
-            self.tab, self.t_tab = _dpmpp_tables(sampler, _uniform_sequence(ddim_step) if seq is None else seq, device)
-            self.x0_prev = torch.empty(B, 3, H, W, device=device)          # full-size history, like y
-        else:
-            self.tab, self.t_tab = _ddim_tables(sampler, ddim_step, device, seq)
+        self.tab, self.t_tab, self.x0_prev = _loop_tables(sampler, B, H, W, device, ddim_step, seq, solver)   # history: full-size, like y
         self.n_steps = int(self.t_tab.numel())
         p = E.Plan(device)
         p.call("hdiff_fill_from_table", up.t.data_ptr(), self.t_tab.data_ptr(), self.step.data_ptr(), self.n_steps, n_slots)
@@ -460,10 +461,7 @@ class GaussianDiffusionSampler(nn.Module):
     def _solver_arguments(self, ddim, ddim_step, solver, spacing, timesteps):
         """-> the time steps of the loop as a tuple, or None for the reference's own (``ValueError`` otherwise).  Looks at no
         device.  Plain ``ddim=True, ddim_step=n`` gives None: that call runs exactly what it ran before these arguments existed."""
-        if solver not in SOLVERS:
-            raise ValueError(f"solver must be one of {SOLVERS}, got {solver!r}")
-        if spacing is not None and spacing not in SPACINGS:
-            raise ValueError(f"spacing must be None or one of {SPACINGS}, got {spacing!r}")
+        check_solver_spacing(solver, spacing)
         if not ddim:
             if solver != "ddim" or spacing is not None or timesteps is not None:
                 raise ValueError("solver / spacing / timesteps need ddim=True: they choose the update and the steps of the DDIM loop")
@@ -472,7 +470,7 @@ class GaussianDiffusionSampler(nn.Module):
             if ddim_step is not None or spacing is not None:
                 raise ValueError("an explicit timesteps list replaces ddim_step and spacing: give one or the other")
             return _checked_timesteps(timesteps, int(self.T) - 1)
-        if (spacing or ("logsnr" if solver == "dpmpp2m" else "uniform")) == "uniform":
+        if spacing_of(solver, spacing) == "uniform":
             if ddim_step is None and solver != "ddim":
                 raise ValueError("solver='dpmpp2m' needs ddim_step or timesteps")
             return None                                       # (ddim_step=None: the reference's TypeError, raised where it was)
@@ -480,93 +478,79 @@ class GaussianDiffusionSampler(nn.Module):
             raise ValueError("spacing='logsnr' needs ddim_step")
         return tuple(logsnr_timesteps(self.betas, ddim_step, shift=1))
 
-    def _forward_tiled(self, input_image, ddim_step, y_T, trajectory, tile, overlap, tile_batch, solver="ddim", spacing=None,
-                       seq=None):
-        """The DDIM loop over overlapping windows.  ``unconditional_guidance_scale`` needs no handling: as in ``_forward`` its
-        two evaluations are the same function, so the combine is eps exactly and one evaluation is issued."""
-        if input_image.is_cuda and not input_image.is_contiguous():
-            input_image = input_image.contiguous()
-        E.require_gpu_tensor(input_image, "input_image")
-        lib = _capi.lib()
-        dev = input_image.device
-        img = input_image.float() / 255.0                                                          # :220
-        B, Cx, H, W = (int(v) for v in img.shape)
-        if Cx != 3:
-            raise RuntimeError(f"expected input[{B}, {Cx + 3}, {H}, {W}] to have 6 channels")
-        if ddim_step is None and seq is None:
-            raise TypeError("unsupported operand type(s) for /: 'int' and 'NoneType'")             # :243 with ddim_step=None
-        ddim_step = None if seq is not None else int(ddim_step)
-        key = (B, H, W, str(dev), ddim_step, False, 0, lib.hdiff_get_contraction_mode(), tile, overlap, tile_batch, solver, spacing,
-               seq)
-        sp = self._plans.get(key)
-        if sp is None or sp.unet is not self.model.plan_for(sp.n_slots, sp.th, sp.tw, dev, True):
-            sp = _TiledStepPlan(self, B, H, W, dev, ddim_step, tile, overlap, tile_batch, solver, seq)
-            self._plans = {key: sp}
-        sp.unet.plan.pack_weights()     # once per call, as in _forward
-        self.model.dynamic_forward(torch.cat([img, img], dim=1))    # on the full image
-        y = torch.randn_like(img) if y_T is None else y_T            # :239
-        sp.cond.copy_(img)
-        sp.y.copy_(y)
-        sp.step.fill_(sp.n_steps - 1)
-        sp.nan_flag.zero_()
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        eager = trajectory is not None or sp.n_steps < self.GRAPH_MIN_STEPS
-        if not eager:
-            sp.plan.capture()
-        for _ in range(sp.n_steps):
-            if eager:
-                sp.plan.run(stream)
-            else:
-                sp.plan.replay(stream)
-            if trajectory is not None:
-                trajectory.append(sp.y.clone())
-        out = torch.empty_like(img)
-        _capi.check(lib.hdiff_clip(sp.y.data_ptr(), out.data_ptr(), C.c_float(-1.0), C.c_float(1.0), sp.n, stream), "clip")
-        return out
-
-    def _forward(self, input_image, ddim, unconditional_guidance_scale, ddim_step, y_T, noise_by_step, trajectory, solver="ddim",
-                 spacing=None, seq=None):
-        if input_image.is_cuda and not input_image.is_contiguous():
-            input_image = input_image.contiguous()
-        E.require_gpu_tensor(input_image, "input_image")
-        lib = _capi.lib()
-        dev = input_image.device
-        img = input_image.float() / 255.0                                                          # :220
+    def _input(self, input_image, ddim, ddim_step, seq):
+        """-> (the image in [0, 1] as the kernels need it, ``ddim_step`` as a plan key holds it: an int for the reference's own
+        time steps of the DDIM loop, else None)."""
+        img = _gpu_input(input_image, "input_image").float() / 255.0                               # :220
         B, Cx, H, W = (int(v) for v in img.shape)
         if Cx != 3:
             raise RuntimeError(f"expected input[{B}, {Cx + 3}, {H}, {W}] to have 6 channels")
         if ddim and ddim_step is None and seq is None:
             raise TypeError("unsupported operand type(s) for /: 'int' and 'NoneType'")             # :243 with ddim_step=None
-        inject = (not ddim) and noise_by_step is not None
-        seed = 0 if (ddim or inject) else int(torch.empty((), dtype=torch.int64).random_().item())
-        ddim_step = int(ddim_step) if ddim and seq is None else None
-        key = (B, H, W, str(dev), ddim_step, inject, seed, lib.hdiff_get_contraction_mode(), None, None, None, solver, spacing,
-               seq)                                    # the three None: tile, tile_overlap, tile_batch
+        return img, (int(ddim_step) if ddim and seq is None else None)
+
+    def _plan(self, key, device, make):
+        """The one live step plan: a graph bakes its seed and contraction mode, and a rebuilt UNet plan retires it."""
         sp = self._plans.get(key)
-        if sp is None or sp.unet is not self.model.plan_for(B, H, W, dev, True):
-            sp = _StepPlan(self, B, H, W, dev, ddim_step, inject, seed, solver, seq)
-            self._plans = {key: sp}                                  # a graph bakes its seed and contraction mode: keep one live plan
+        if sp is None or sp.unet is not self.model.plan_for(sp.n_slots, sp.th, sp.tw, device, True):
+            sp = make()
+            self._plans = {key: sp}
         sp.unet.plan.pack_weights()     # once per call: also catches writes through p.data, which p._version does not see
-        self.model.dynamic_forward(torch.cat([img, img], dim=1))    # the reference runs it on every call (requires_grad only)
-        y = torch.randn_like(img) if y_T is None else y_T            # :226 / :239
-        up = sp.unet
-        up.cond.copy_(img)
-        up.y.copy_(y)
-        sp.step.fill_(sp.n_steps - 1)
+        return sp
+
+    def _run(self, sp, y_buffer, n_steps, eager, noise_by_step, trajectory):
+        """``n_steps`` runs (eager) or replays of the captured step on the state in ``y_buffer``, then the clip.
+        ``noise_by_step[k]`` goes into the plan's noise buffer before step k (the last step adds none)."""
+        sp.step.fill_(n_steps - 1)
         sp.nan_flag.zero_()
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        eager = inject or trajectory is not None or sp.n_steps < self.GRAPH_MIN_STEPS
+        stream = torch.cuda.current_stream(y_buffer.device).cuda_stream
         if not eager:
             sp.plan.capture()
-        for k in range(sp.n_steps):
-            if inject and k < sp.n_steps - 1:
+        for k in range(n_steps):
+            if noise_by_step is not None and k < n_steps - 1:
                 sp.noise.copy_(noise_by_step[k])
             if eager:
                 sp.plan.run(stream)
             else:
                 sp.plan.replay(stream)
             if trajectory is not None:
-                trajectory.append(up.y.clone())
-        out = torch.empty_like(img)
-        _capi.check(lib.hdiff_clip(up.y.data_ptr(), out.data_ptr(), C.c_float(-1.0), C.c_float(1.0), sp.n, stream), "clip")
+                trajectory.append(y_buffer.clone())
+        out = torch.empty_like(y_buffer)
+        _capi.check(_capi.lib().hdiff_clip(y_buffer.data_ptr(), out.data_ptr(), C.c_float(-1.0), C.c_float(1.0), sp.n, stream),
+                    "clip")
         return out
+
+    def _forward_tiled(self, input_image, ddim_step, y_T, trajectory, tile, overlap, tile_batch, solver="ddim", spacing=None,
+                       seq=None):
+        """The DDIM loop over overlapping windows.  ``unconditional_guidance_scale`` needs no handling: as in ``_forward`` its
+        two evaluations are the same function, so the combine is eps exactly and one evaluation is issued."""
+        img, ddim_step = self._input(input_image, True, ddim_step, seq)
+        B, _, H, W = (int(v) for v in img.shape)
+        dev = img.device
+        mode = _capi.lib().hdiff_get_contraction_mode()
+        sp = self._plan((B, H, W, str(dev), ddim_step, False, 0, mode, tile, overlap, tile_batch, solver, spacing, seq), dev,
+                        lambda: _TiledStepPlan(self, B, H, W, dev, ddim_step, tile, overlap, tile_batch, solver, seq))
+        self.model.dynamic_forward(torch.cat([img, img], dim=1))    # on the full image
+        y = torch.randn_like(img) if y_T is None else y_T            # :239
+        sp.cond.copy_(img)
+        sp.y.copy_(y)
+        eager = trajectory is not None or sp.n_steps < self.GRAPH_MIN_STEPS
+        return self._run(sp, sp.y, sp.n_steps, eager, None, trajectory)
+
+    def _forward(self, input_image, ddim, unconditional_guidance_scale, ddim_step, y_T, noise_by_step, trajectory, solver="ddim",
+                 spacing=None, seq=None):
+        img, ddim_step = self._input(input_image, ddim, ddim_step, seq)
+        B, _, H, W = (int(v) for v in img.shape)
+        dev = img.device
+        inject = (not ddim) and noise_by_step is not None
+        seed = 0 if (ddim or inject) else int(torch.empty((), dtype=torch.int64).random_().item())
+        mode = _capi.lib().hdiff_get_contraction_mode()
+        sp = self._plan((B, H, W, str(dev), ddim_step, inject, seed, mode, None, None, None, solver, spacing, seq), dev,
+                        lambda: _StepPlan(self, B, H, W, dev, ddim_step, inject, seed, solver, seq))     # the three None: tile, ...
+        self.model.dynamic_forward(torch.cat([img, img], dim=1))    # the reference runs it on every call (requires_grad only)
+        y = torch.randn_like(img) if y_T is None else y_T            # :226 / :239
+        up = sp.unet
+        up.cond.copy_(img)
+        up.y.copy_(y)
+        eager = inject or trajectory is not None or sp.n_steps < self.GRAPH_MIN_STEPS
+        return self._run(sp, up.y, sp.n_steps, eager, noise_by_step if inject else None, trajectory)

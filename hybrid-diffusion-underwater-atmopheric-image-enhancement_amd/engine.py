@@ -53,6 +53,28 @@ def require_gpu_tensor(t: torch.Tensor, name: str) -> None:
         raise RuntimeError(f"hdiff: '{name}' must be contiguous (NCHW)")
 
 
+def gpu_input(x, name):
+    """A caller's tensor as the kernels need it: on the GPU (no CPU fallback), fp32 / integer, contiguous NCHW."""
+    if x.is_cuda and not x.is_contiguous():
+        x = x.contiguous()              # the reference accepts strided views; the kernels read dense NCHW
+    require_gpu_tensor(x, name)
+    return x
+
+
+def index_vector(t, T: int, device):
+    """The index vector of ``extract`` (reference :9-16) as the kernels read it: int64, contiguous, on ``device``, and in
+    range -- ``torch.gather`` raises for an index outside [0, T), so does this (the kernels clamp on top: a bad index can
+    never fault the GPU)."""
+    if not torch.is_tensor(t) or t.dtype not in (torch.int64, torch.int32):
+        raise RuntimeError("gather(): Expected dtype int64 for index")
+    t = t.to(device=device, dtype=torch.int64).contiguous()
+    if t.numel():
+        lo, hi = torch.stack([t.min(), t.max()]).tolist()
+        if lo < 0 or hi >= T:
+            raise RuntimeError(f"index {hi if hi >= T else lo} is out of bounds for dimension 0 with size {T}")
+    return t
+
+
 # ----------------------------------------------------------------------------------------------------------------------
 # Packed convolution weights
 # ----------------------------------------------------------------------------------------------------------------------

@@ -32,6 +32,23 @@ def test_one_implementation_in_both_trees():
     assert {"logsnr_timesteps", "dpmpp_table"} <= set(DC.__all__) and {"logsnr_timesteps", "dpmpp_table"} <= set(DD.__all__)
 
 
+def test_schedules_module_is_cpu_only_and_shared():
+    """``hdiff_amd.schedules`` is the one home of the schedule functions: both sampler modules re-export its objects, and importing
+    it (in a fresh interpreter) loads neither the native library nor the engine."""
+    from hdiff_amd import schedules
+    for name in ("ddim_timesteps", "ddim_table", "logsnr_timesteps", "dpmpp_table"):
+        assert getattr(DC, name) is getattr(schedules, name), name
+    for name in ("logsnr_timesteps", "dpmpp_table"):
+        assert getattr(DD, name) is getattr(schedules, name), name
+    code = ("import sys; import hdiff_amd.schedules as S; from hdiff_amd import _capi; "
+            "assert _capi._lib is None, 'libhdiff.so was loaded'; "
+            "assert 'hdiff_amd.engine' not in sys.modules, 'engine was imported'; "
+            "print(S.ddim_timesteps(1000, 4))")
+    res = subprocess.run([os.sys.executable, "-c", code], capture_output=True, text=True, cwd=ROOT, timeout=300)
+    assert res.returncode == 0, res.stderr
+    assert res.stdout.strip() == "[249, 499, 749, 999]"
+
+
 def test_logsnr_prefixes():
     assert DC.logsnr_timesteps(BETAS, 10)[:5] == [0, 5, 22, 73, 202]
     assert DC.logsnr_timesteps(BETAS, 10, shift=1)[:5] == [0, 7, 31, 94, 240]

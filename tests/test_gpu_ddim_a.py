@@ -121,6 +121,56 @@ def test_own_noise_moments_and_determinism():
     assert flag.item() == 0
 
 
+def test_own_noise_is_the_randn_stream():
+    """The step kernels draw element i of step k from the Philox counter that ``hdiff_randn(n, seed, offset=k)`` gives element i:
+    with x = eps_c = eps_u = 0 and no injected noise each update is exactly ``0 + sigma_k * z``, bit for bit (the product formed by
+    torch in fp32 on the device).  n = 4099: several workgroups, n % 4 == 3, so the tail quad is taken."""
+    n, T, S, w, seed = 4099, 50, 10, 1.8, 42
+    lib = _capi.lib()
+    zero = torch.zeros(n, device=DEV)
+    flag = torch.zeros(1, dtype=torch.int32, device=DEV)
+
+    def randn(k):
+        z = torch.empty(n, device=DEV)
+        _capi.check(lib.hdiff_randn(z.data_ptr(), n, C.c_uint64(seed), C.c_uint64(k), _stream()), "randn")
+        return z
+
+    # the ancestral step: the sampler's own tables (DiffusionCondition.py: _SamplerPlan)
+    betas = torch.linspace(1e-4, 0.028, T).double()
+    alphas = 1. - betas
+    alphas_bar = torch.cumprod(alphas, dim=0)
+    alphas_bar_prev = torch.cat([torch.ones(1, dtype=torch.float64), alphas_bar[:-1]])
+    coeff1 = torch.sqrt(1. / alphas)
+    coeff2 = coeff1 * (1. - alphas) / torch.sqrt(1. - alphas_bar)
+    var = torch.cat([(betas * (1. - alphas_bar_prev) / (1. - alphas_bar))[1:2], betas[1:]])
+    c1, c2, sg = coeff1.float().to(DEV), coeff2.float().to(DEV), torch.sqrt(var.float()).to(DEV)
+
+    def ddpm(step):
+        out = torch.empty(n, device=DEV)
+        ctr = torch.tensor([step], dtype=torch.int32, device=DEV)
+        _capi.check(lib.hdiff_ddpm_step(zero.data_ptr(), zero.data_ptr(), zero.data_ptr(), None, out.data_ptr(), c1.data_ptr(),
+                                        c2.data_ptr(), sg.data_ptr(), ctr.data_ptr(), T, C.c_double(w), C.c_uint64(seed),
+                                        flag.data_ptr(), n, _stream()), "ddpm_step")
+        return out
+
+    assert torch.equal(ddpm(5), sg[5] * randn(5)), "ddpm_step: not sigma_5 * randn(seed, offset=5)"
+    assert bool((ddpm(0) == 0).all())                           # no noise at step 0
+
+    # the strided DDIM step with eta = 1
+    dtab = D.table(betas, D.timesteps(T, S), 1.0).float().to(DEV).contiguous()
+
+    def ddim(k):
+        out = torch.empty(n, device=DEV)
+        ctr = torch.tensor([k], dtype=torch.int32, device=DEV)
+        _step(lib, zero, zero, zero, None, out, dtab, ctr, S, w, False, seed, flag, n)
+        return out
+
+    assert float(dtab[6, D.SIGMA]) > 0
+    assert torch.equal(ddim(6), dtab[6, D.SIGMA] * randn(6)), "cfg_ddim_step: not sigma_6 * randn(seed, offset=6)"
+    assert bool((ddim(0) == 0).all())                           # no noise at k = 0
+    assert flag.item() == 0
+
+
 # ----------------------------------------------------------------------------------------------------------------------
 # c. the loop's bookkeeping
 # ----------------------------------------------------------------------------------------------------------------------

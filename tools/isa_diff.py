@@ -5,8 +5,10 @@
 
 Exports csrc/ and include/ of <rev> with `git archive` into a temporary directory, runs `make asm` there and here (every source with
 its own Makefile flags, the mutant sources also with the two mutant masks), cuts each .s into its kernels and compares them with
-local labels renumbered and comments stripped.  One line per kernel: same / DIFF / only in <rev> / only here.  Exit status 1 on any
-DIFF or `only in <rev>` (a kernel that only exists here is new code, not changed code).  A revision whose Makefile has no asm target
+local labels renumbered and comments stripped.  One line per kernel: same / DIFF / only in <rev> / only here.  A kernel missing from
+the same-named .s of the other tree but present under the same symbol in exactly one other .s there is compared with that one and
+printed with both file names, marked (moved).  Exit status 1 on any DIFF or `only in <rev>` (a kernel that only exists here is new
+code, not changed code).  A revision whose Makefile has no asm target
 is given this tree's csrc/asm.mk next to its own Makefile, so each side is compiled with its own flags.
 """
 import argparse
@@ -49,13 +51,29 @@ def compare(asm_rev, asm_here, rev, out=sys.stdout):
     """prints the verdict lines for build/asm of the two trees; True when nothing differs and nothing of <rev> is missing"""
     ok = True
     files = sorted({p.relative_to(d) for d in (asm_rev, asm_here) for p in d.rglob("*.s")})
+    a_all = {rel: kernels(asm_rev / rel) if (asm_rev / rel).exists() else {} for rel in files}
+    b_all = {rel: kernels(asm_here / rel) if (asm_here / rel).exists() else {} for rel in files}
+    moved = {}                                  # (file here, symbol) -> file of <rev>: the symbol left its file for exactly one other
     for rel in files:
-        a = kernels(asm_rev / rel) if (asm_rev / rel).exists() else {}
-        b = kernels(asm_here / rel) if (asm_here / rel).exists() else {}
+        for sym in a_all[rel].keys() - b_all[rel].keys():
+            homes = [r for r in files if sym in b_all[r]]
+            if len(homes) == 1:
+                moved[(homes[0], sym)] = rel
+    home_of = {(rel, sym): home for (home, sym), rel in moved.items()}
+    for rel in files:
+        a, b = a_all[rel], b_all[rel]
         for sym in sorted(a.keys() | b.keys()):
-            verdict = f"only in {rev}" if sym not in b else "only here" if sym not in a else "same" if a[sym] == b[sym] else "DIFF"
+            if (rel, sym) in moved and sym not in a:
+                continue                        # printed with the file it came from
+            if (rel, sym) in home_of:
+                home = home_of[(rel, sym)]
+                verdict = "same" if a[sym] == b_all[home][sym] else "DIFF"
+                where = f"{rel} -> {home} (moved)"
+            else:
+                verdict = f"only in {rev}" if sym not in b else "only here" if sym not in a else "same" if a[sym] == b[sym] else "DIFF"
+                where = str(rel)
             ok &= verdict in ("same", "only here")
-            print(f"{verdict:<8}  {rel}  {sym}", file=out)
+            print(f"{verdict:<8}  {where}  {sym}", file=out)
     return ok
 
 
