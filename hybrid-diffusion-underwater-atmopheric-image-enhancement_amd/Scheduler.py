@@ -5,6 +5,10 @@ Every base learning rate ramps linearly from ``base`` (epoch 0) to ``base * mult
 base rates re-based to ``base * multiplier`` at the hand-over and its epoch counter starting there.  The resulting
 learning-rate sequence is pinned against the reference's (tests/golden/lr_schedule.json, equal to 1e-12).
 
+``warm_epoch = 0`` (the reference's drivers pass ``epochs // 10``, so any run shorter than 10 epochs) divides by zero in the
+reference; here a warm-up of no epochs is over at epoch 0: the rate starts at ``base * multiplier`` and ``after_scheduler`` takes
+over from epoch 1, as it does after a warm-up of any other length.
+
 Public attributes keep the reference's names: ``multiplier``, ``total_epoch``, ``after_scheduler``, ``finished``.
 """
 from torch.optim.lr_scheduler import LRScheduler
@@ -20,6 +24,8 @@ class GradualWarmupScheduler(LRScheduler):
 
     def _ramp(self) -> float:
         """Factor on the base rate during warm-up: 1 at epoch 0, ``multiplier`` at ``total_epoch``."""
+        if self.total_epoch == 0:
+            return float(self.multiplier)
         return 1.0 + (self.multiplier - 1.0) * self.last_epoch / self.total_epoch
 
     def _peak(self):

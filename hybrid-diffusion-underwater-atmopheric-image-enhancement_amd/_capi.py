@@ -212,6 +212,7 @@ _PROTOS = {
     "hdiff_grad_norm_clip_coef": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p]),
     "hdiff_adamw_step": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double,
                                    C.c_int64, C.c_void_p]),
+    "hdiff_ema_update": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_double, C.c_void_p]),
     "hdiff_randn": (C.c_int, [C.c_void_p, C.c_int64, C.c_uint64, C.c_uint64, C.c_void_p]),
     "hdiff_graph_begin": (C.c_int, [C.c_void_p]),
     "hdiff_graph_end": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p)]),

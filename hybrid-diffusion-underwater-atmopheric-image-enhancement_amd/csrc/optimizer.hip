@@ -94,6 +94,32 @@ __global__ __launch_bounds__(OT) void opt_adamw_kernel(const OptTensor* __restri
   }
 }
 
+struct EmaTensor {
+  float* avg;
+  const float* p;
+  long long n;
+};
+static_assert(sizeof(EmaTensor) == sizeof(hdiff_ema_tensor), "host and device table layouts");
+
+// The weight average a diffusion run samples from: avg += (p - avg) w with w = 1 - decay, three separately rounded fp32 operations
+// (this file is compiled with -ffp-contract=off).  p and avg read, avg written once: 3 x 4 bytes per parameter.  w == 0 returns avg
+// exactly where p - avg is finite.
+__global__ __launch_bounds__(OT) void opt_ema_kernel(const EmaTensor* __restrict__ tab, const int2* __restrict__ chunks, const float w) {
+  const int2 c = chunks[blockIdx.x];
+  const EmaTensor t = tab[c.x];
+  const long long base = (long long)c.y * CHUNK;
+#pragma unroll 4
+  for (int i = threadIdx.x; i < CHUNK; i += OT) {
+    const long long e = base + i;
+    if (e < t.n) {
+      const float a = t.avg[e];
+      const float d = t.p[e] - a;
+      const float u = d * w;
+      t.avg[e] = a + u;
+    }
+  }
+}
+
 }  // namespace
 
 extern "C" int hdiff_opt_chunk(void) { return CHUNK; }
@@ -124,5 +150,17 @@ extern "C" int hdiff_adamw_step(const hdiff_opt_tensor* table, const int* chunks
   hipLaunchKernelGGL(opt_adamw_kernel, dim3(nchunks), dim3(OT), 0, (hipStream_t)stream, reinterpret_cast<const OptTensor*>(table),
                      reinterpret_cast<const int2*>(chunks), norm_coef, a);
   HDIFF_CHECK_LAUNCH("adamw kernel");
+  return HDIFF_OK;
+}
+
+extern "C" int hdiff_ema_update(const hdiff_ema_tensor* table, const int* chunks, int nchunks, double decay, hdiff_stream_t stream) {
+  HDIFF_CHECK_ARG(table && chunks, "ema_update: null pointer");
+  HDIFF_CHECK_ARG(nchunks > 0, "ema_update: bad sizes (nchunks %d)", nchunks);
+  HDIFF_CHECK_ARG(decay >= 0. && decay <= 1., "ema_update: decay %g is outside [0, 1]", decay);
+  if (decay == 1.) return HDIFF_OK;      // avg stays bit for bit, also where p - avg is not finite
+  (void)hipGetLastError();
+  hipLaunchKernelGGL(opt_ema_kernel, dim3(nchunks), dim3(OT), 0, (hipStream_t)stream, reinterpret_cast<const EmaTensor*>(table),
+                     reinterpret_cast<const int2*>(chunks), (float)(1.0 - decay));
+  HDIFF_CHECK_LAUNCH("ema kernel");
   return HDIFF_OK;
 }

@@ -1,0 +1,329 @@
+"""The training driver of the reference's second tree (``utils/rotinas.py:571-732`` ``train``, which ``Main.py --state train`` runs):
+two stages over the image-conditioned ``DynamicUNet`` -- stage 0 "Atmosferic" on the atmospheric set for ``epochs_stage_1`` epochs,
+stage 1 "Underwater" on the underwater set for ``epochs_stage_2`` -- each with a NEW ``AdamW(lr, weight_decay=1e-4)`` and a new
+``CosineAnnealingLR(T_max=epochs)`` behind ``GradualWarmupScheduler(multiplier, warm_epoch=epochs // 10)`` stepped once per epoch.
+Per batch (``rotinas.py:427-448``): ``loss = trainer(input, label, stage_number)[0]; loss.mean().backward()``, then the clip and the
+step, here ``opt.step(max_grad_norm=grad_clip)`` of ``hdiff_amd.optim.AdamW``.  Weights-only checkpoints go to
+``<output_path>/ckpt/ckpt_<global epoch>_<stage name>_<u_name><a_name>.pt`` and, at the end, ``ckpt_<total>_final_<u_name><a_name>.pt``:
+plain state dicts that the reference and ``Evaluate.test(pretrained_path=...)`` load.
+
+Keys read as the reference reads them: ``underwater_data_name``, ``atmospheric_data_name``, ``T``, ``channel``, ``channel_mult``,
+``num_res_blocks``, ``dropout``, ``lr``, ``multiplier``, ``beta_1``, ``beta_T``, ``grad_clip``, ``batch_size``, ``epochs_stage_1``,
+``epochs_stage_2``, ``save_checkpoint``, ``output_path``, ``pretrained_path``, ``device_list``.
+
+Deliberate deviations from the reference:
+  * checkpoints: the reference's second condition compares the GLOBAL epoch with the stage's length (``rotinas.py:700``); here a
+    checkpoint is written when ``global_epoch % save_checkpoint == 0`` and also at the last epoch of each stage.
+  * validation: the reference's is unreachable (it names an undefined ``dataloaders_test``, ``:712``) and would step the optimizer
+    (``process_batch``).  Here it is the five loss terms of the trainer on the stage's test loader, under ``no_grad`` with the model in
+    ``eval()``, no optimizer involved, at most ``max_val_batches`` batches, inside ``torch.random.fork_rng`` with a fixed seed: it
+    draws the same ``t`` / noise at every checkpoint and does not move the training stream.
+  * a stage shorter than 10 epochs has ``warm_epoch = 0``, at which the reference's scheduler divides by zero; here such a stage
+    starts at ``lr * multiplier`` (``Scheduler.GradualWarmupScheduler``: a warm-up of no epochs is over at epoch 0).
+  * wandb is not wired: ``wandb=True`` warns once.
+  * data-parallel training is out of scope: ``WORLD_SIZE > 1`` or ``DDP=True`` raises (the per-batch gating of the middle blocks does
+    not fit ``parallel.FlatGradients`` as it stands); of ``device_list`` the first entry is used.
+  * ``msssim_loss`` defaults to the package's ``Loss.loss.MSSSIMLoss()``; ``dino_loss`` is an optional callable (the DINOv2 weights are
+    not part of the package) and the trainer's warning stands when it is absent.
+
+Additions, all optional (with none of them set the run is the loop above): ``dataset_root`` (one root for both sets, or a dict by
+set name), ``transforms`` (the sets' ``transforms=``), ``num_workers`` (4), ``seed`` (``torch.manual_seed`` before the model is
+built), ``max_steps_per_epoch``, ``max_val_batches``, ``max_epochs`` (stop after this many global epochs, having written the state
+file: a clean interruption), ``ema_decay`` (``None``: no EMA), ``resume`` (a state file to continue from), ``on_step`` (a callable
+``(step number, model)`` run after every optimizer step, for logging).
+
+With ``ema_decay`` an ``optim.EMA`` of all weights is updated after every optimizer step and lives across the stage boundary (the
+optimizer does not); every checkpoint gets a sibling ``..._ema.pt`` (``EMA.shadow_state_dict``: the same keys, so ``Evaluate.test``
+evaluates it unchanged) and validation reports the raw and the averaged weights.
+
+Whenever a checkpoint is written so is ``<output_path>/ckpt/state_last.pt``: model, EMA, optimizer and both schedulers' state
+dicts, stage index, epoch within the stage, step counter, the torch CPU and device RNG states and the records so far.  ``resume``
+restores all of it and continues at the next epoch; across a stage boundary it begins stage 1 with a fresh optimizer, as the
+uninterrupted run does.
+
+Returns ``{"losses": {term: [mean per epoch]}, "lr": [per epoch], "validation": [records], "files": [paths written], "steps": n,
+"epochs": global epochs done, "finished": bool}``.
+"""
+from __future__ import annotations
+
+import os
+import warnings
+from typing import Dict, List, Optional, Tuple
+
+import torch
+
+from .Evaluate import _cfg
+
+__all__ = ["train", "stage_plan", "checkpoint_epochs", "checkpoint_name", "final_name", "expected_files", "lr_sequence", "TERMS",
+           "STATE_FILE"]
+
+TERMS = ("loss", "mse_loss", "perceptual_dino", "msssim", "col_loss")       # the trainer's return order (rotinas.py:439)
+WEIGHT_DECAY = 1e-4                                                          # rotinas.py:660
+STATE_FILE = "state_last.pt"
+VALIDATION_SEED = 0x5eed
+
+
+# -- host-only pieces: the stage plan, which epochs checkpoint, the file names, the LR sequence ----------------------------------
+def stage_plan(config) -> List[Dict[str, object]]:
+    """rotinas.py:643-646, with the set each stage trains on (:668-673)."""
+    lr = _cfg(config, "lr")
+    return [{"name": "Atmosferic", "lr": lr, "epochs": int(_cfg(config, "epochs_stage_1")), "number": 0, "data": "atmospheric"},
+            {"name": "Underwater", "lr": lr, "epochs": int(_cfg(config, "epochs_stage_2")), "number": 1, "data": "underwater"}]
+
+
+def checkpoint_epochs(epochs_stage_1: int, epochs_stage_2: int, save_checkpoint: int) -> List[Tuple[int, int, int]]:
+    """[(global epoch, stage index, epoch within the stage)] of every checkpoint but the final one: ``global % save_checkpoint == 0``
+    or the last epoch of a stage."""
+    out, start = [], 0
+    for si, epochs in enumerate((int(epochs_stage_1), int(epochs_stage_2))):
+        for e in range(epochs):
+            if (start + e) % int(save_checkpoint) == 0 or e == epochs - 1:
+                out.append((start + e, si, e))
+        start += epochs
+    return out
+
+
+def checkpoint_name(global_epoch: int, stage_name: str, u_name: str, a_name: str, ema: bool = False) -> str:
+    """rotinas.py:559 with ``dataset_name = u_name + a_name`` (:706); ``ema``: the averaged weights' sibling."""
+    return f"ckpt_{global_epoch}_{stage_name}_{u_name}{a_name}{'_ema' if ema else ''}.pt"
+
+
+def final_name(total_epochs: int, u_name: str, a_name: str, ema: bool = False) -> str:
+    return checkpoint_name(total_epochs, "final", u_name, a_name, ema)
+
+
+def expected_files(config) -> List[str]:
+    """Every file name a complete run leaves under ``<output_path>/ckpt``, sorted."""
+    u, a = _cfg(config, "underwater_data_name"), _cfg(config, "atmospheric_data_name")
+    plan = stage_plan(config)
+    kinds = (False, True) if _cfg(config, "ema_decay", None) is not None else (False,)
+    names = [checkpoint_name(g, plan[si]["name"], u, a, k)
+             for g, si, _ in checkpoint_epochs(plan[0]["epochs"], plan[1]["epochs"], _cfg(config, "save_checkpoint")) for k in kinds]
+    names += [final_name(plan[0]["epochs"] + plan[1]["epochs"], u, a, k) for k in kinds]
+    return sorted(names + [STATE_FILE])
+
+
+def _schedulers(optimizer, multiplier: float, epochs: int):
+    from ..Scheduler import GradualWarmupScheduler
+    cosine = torch.optim.lr_scheduler.CosineAnnealingLR(optimizer=optimizer, T_max=epochs, eta_min=0, last_epoch=-1)      # :661-662
+    warm = GradualWarmupScheduler(optimizer=optimizer, multiplier=multiplier, warm_epoch=epochs // 10, after_scheduler=cosine)
+    return warm, cosine
+
+
+def lr_sequence(lr: float, multiplier: float, epochs: int) -> List[float]:
+    """The learning rate of every epoch of one stage: the driver's schedulers on a dummy CPU optimizer, stepped once per epoch."""
+    opt = torch.optim.SGD([torch.nn.Parameter(torch.zeros(1))], lr=lr)
+    warm, _ = _schedulers(opt, multiplier, epochs)
+    out = []
+    for _ in range(epochs):
+        out.append(opt.param_groups[0]["lr"])
+        opt.step()
+        warm.step()
+    return out
+
+
+def _refuse_data_parallel(config) -> None:
+    if int(os.environ.get("WORLD_SIZE", "1")) > 1 or bool(_cfg(config, "DDP", False)):
+        raise RuntimeError("hdiff_amd.diffusion.Train.train: data-parallel training of the image-conditioned tree is out of scope "
+                           "(WORLD_SIZE > 1 or DDP=True): run one process on one GPU")
+
+
+def _device(config) -> torch.device:
+    devices = _cfg(config, "device_list", None)
+    first = devices[0] if devices else "cuda:0"
+    device = torch.device("cuda", first) if isinstance(first, int) else torch.device(first)
+    if device.type != "cuda":
+        raise RuntimeError(f"hdiff_amd.diffusion.Train.train runs on the GPU in fp32 only (there is no CPU path), got device '{device}'")
+    if device.index is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    return device
+
+
+def _sched_state(warm, cosine) -> Dict[str, dict]:
+    return {"warmup": {k: v for k, v in warm.state_dict().items() if k != "after_scheduler"}, "cosine": cosine.state_dict()}
+
+
+# -- the driver ----------------------------------------------------------------------------------------------------------------
+def _validate(trainer, model, loader, device, stage_number: int, max_batches: Optional[int], ema) -> Dict[str, Dict[str, float]]:
+    """Mean of the five loss terms over the stage's test loader, for the raw weights and, with an EMA, the averaged ones.  The
+    caller's RNG streams (CPU and device) are the same after the call as before it."""
+    def one_pass() -> Dict[str, float]:
+        torch.manual_seed(VALIDATION_SEED)
+        total, n = torch.zeros(len(TERMS), dtype=torch.float64, device=device), 0
+        for it, (inp, label) in enumerate(loader):
+            if max_batches is not None and it >= max_batches:
+                break
+            terms = trainer(inp.to(device), label.to(device), stage_number)
+            total += torch.stack([v.detach().double().mean() for v in terms])
+            n += 1
+        vals = (total / max(n, 1)).tolist()
+        return {"batches": n, **{k: (v if n else float("nan")) for k, v in zip(TERMS, vals)}}
+
+    was_training = model.training
+    model.eval()
+    try:
+        with torch.random.fork_rng(devices=[device]), torch.no_grad():
+            out = {"raw": one_pass()}
+            if ema is not None:
+                with ema.average_parameters():
+                    out["ema"] = one_pass()
+    finally:
+        model.train(was_training)
+    return out
+
+
+def train(config) -> Dict[str, object]:
+    from torch.utils.data import DataLoader
+    from .. import optim as hdiff_optim
+    from ..datasets import Atmospheric_Dataset, Underwater_Dataset
+    from .Diffusion import GaussianDiffusionTrainer
+    from .Model import DynamicUNet
+
+    _refuse_data_parallel(config)
+    device = _device(config)
+    if _cfg(config, "wandb", False):
+        warnings.warn("hdiff_amd.diffusion.Train.train: wandb is not wired; nothing is logged there", RuntimeWarning, stacklevel=2)
+
+    u_name, a_name = _cfg(config, "underwater_data_name"), _cfg(config, "atmospheric_data_name")
+    root = _cfg(config, "dataset_root", None)
+
+    def root_of(name):
+        return root.get(name) if isinstance(root, dict) else root
+
+    transforms = _cfg(config, "transforms", None)
+    batch_size, workers = int(_cfg(config, "batch_size")), int(_cfg(config, "num_workers", 4))
+
+    def loader(data):                                                                               # :602-605
+        return DataLoader(data, batch_size=batch_size, num_workers=workers, drop_last=True, pin_memory=True)
+
+    loaders = {(kind, task): loader(cls(name, transforms=transforms, task=task, root=root_of(name)))
+               for kind, cls, name in (("underwater", Underwater_Dataset, u_name), ("atmospheric", Atmospheric_Dataset, a_name))
+               for task in ("train", "test")}
+
+    seed = _cfg(config, "seed", None)
+    if seed is not None:
+        torch.manual_seed(int(seed))
+    model = DynamicUNet(T=_cfg(config, "T"), ch=_cfg(config, "channel"), ch_mult=_cfg(config, "channel_mult"),
+                        num_res_blocks=_cfg(config, "num_res_blocks"), dropout=_cfg(config, "dropout"))          # :611-612
+    pretrained = _cfg(config, "pretrained_path", None)
+    if pretrained is not None:
+        ckpt = torch.load(pretrained, map_location="cpu")
+        model.load_state_dict({k.replace("module.", ""): v for k, v in ckpt.items()})                           # :614-616
+    model.to(device).train()
+    msssim_loss = _cfg(config, "msssim_loss", None)
+    if msssim_loss is None:
+        from ..Loss.loss import MSSSIMLoss
+        msssim_loss = MSSSIMLoss()
+    trainer = GaussianDiffusionTrainer(model, _cfg(config, "beta_1"), _cfg(config, "beta_T"), _cfg(config, "T"),
+                                       dino_loss=_cfg(config, "dino_loss", None), msssim_loss=msssim_loss).to(device)   # :629
+    ema_decay = _cfg(config, "ema_decay", None)
+    ema = hdiff_optim.EMA(model.parameters(), decay=ema_decay) if ema_decay is not None else None
+
+    ckpt_dir = os.path.join(_cfg(config, "output_path"), "ckpt")
+    os.makedirs(os.path.join(_cfg(config, "output_path"), "logs"), exist_ok=True)                               # :631-635
+    os.makedirs(ckpt_dir, exist_ok=True)
+    state_path = os.path.join(ckpt_dir, STATE_FILE)
+
+    stages = stage_plan(config)
+    total_epochs = sum(s["epochs"] for s in stages)
+    save_every, grad_clip = int(_cfg(config, "save_checkpoint")), _cfg(config, "grad_clip")
+    multiplier = _cfg(config, "multiplier")
+    step_cap, val_cap = _cfg(config, "max_steps_per_epoch", None), _cfg(config, "max_val_batches", None)
+    max_epochs, on_step = _cfg(config, "max_epochs", None), _cfg(config, "on_step", None)
+
+    record = {"losses": {k: [] for k in TERMS}, "lr": [], "validation": [], "files": []}
+    num, first_stage, first_epoch, resumed = 0, 0, 0, None
+    resume = _cfg(config, "resume", None)
+    if resume is not None:
+        resumed = torch.load(resume, map_location="cpu", weights_only=False)
+        model.load_state_dict(resumed["model"])
+        if (ema is None) != (resumed["ema"] is None):
+            raise RuntimeError("hdiff_amd.diffusion.Train.train: the state file and the configuration disagree about ema_decay")
+        if ema is not None:
+            ema.load_state_dict(resumed["ema"])
+        num, record = int(resumed["num"]), resumed["record"]
+        first_stage, first_epoch = int(resumed["stage"]), int(resumed["epoch"]) + 1
+        if first_stage < len(stages) and first_epoch >= stages[first_stage]["epochs"]:
+            first_stage, first_epoch = first_stage + 1, 0          # the next stage starts with a fresh optimizer, as it would have
+
+    def write(name: str, obj) -> None:
+        path = os.path.join(ckpt_dir, name)
+        torch.save(obj, path)
+        if path not in record["files"]:
+            record["files"].append(path)
+
+    def write_weights(global_epoch: int, stage_name: str) -> None:
+        write(checkpoint_name(global_epoch, stage_name, u_name, a_name), model.state_dict())                    # :555-564
+        if ema is not None:
+            write(checkpoint_name(global_epoch, stage_name, u_name, a_name, ema=True), ema.shadow_state_dict(model))
+
+    def write_state(si: int, e: int, opt, warm, cosine) -> None:
+        if state_path not in record["files"]:
+            record["files"].append(state_path)
+        torch.cuda.synchronize(device)
+        torch.save({"model": model.state_dict(), "ema": None if ema is None else ema.state_dict(),
+                    "optimizer": None if opt is None else opt.state_dict(),
+                    "schedulers": None if opt is None else _sched_state(warm, cosine),
+                    "stage": si, "epoch": e, "num": num, "record": record,
+                    "rng_cpu": torch.get_rng_state(), "rng_device": torch.cuda.get_rng_state(device)}, state_path)
+
+    done_epochs = sum(s["epochs"] for s in stages[:first_stage]) + first_epoch
+    stopped, opt, warm, cosine = False, None, None, None
+    for si in range(first_stage, len(stages)):
+        stage = stages[si]
+        start = sum(s["epochs"] for s in stages[:si])
+        opt = hdiff_optim.AdamW(model.parameters(), lr=stage["lr"], weight_decay=WEIGHT_DECAY)                  # :660
+        warm, cosine = _schedulers(opt, multiplier, stage["epochs"])                                            # :661-665
+        e0 = 0
+        if resumed is not None and si == first_stage:
+            if first_epoch > 0:
+                opt.load_state_dict(resumed["optimizer"])
+                cosine.load_state_dict(resumed["schedulers"]["cosine"])
+                warm.load_state_dict(resumed["schedulers"]["warmup"])
+                e0 = first_epoch
+            torch.set_rng_state(resumed["rng_cpu"])
+            torch.cuda.set_rng_state(resumed["rng_device"], device)
+            resumed = None
+        train_loader, test_loader = loaders[(stage["data"], "train")], loaders[(stage["data"], "test")]
+        for e in range(e0, stage["epochs"]):
+            current = start + e
+            record["lr"].append(opt.param_groups[0]["lr"])
+            sums, steps = torch.zeros(len(TERMS), dtype=torch.float64, device=device), 0
+            for it, (inp, label) in enumerate(train_loader):
+                if step_cap is not None and it >= step_cap:
+                    break
+                inp, label = inp.to(device), label.to(device)
+                opt.zero_grad()
+                terms = trainer(inp, label, stage["number"])                                                     # :439
+                terms[0].mean().backward()                                                                       # :443
+                opt.step(max_grad_norm=grad_clip)                                                                # :444-445
+                if ema is not None:
+                    ema.update()
+                sums += torch.stack([v.detach().double().mean() for v in terms])
+                steps += 1
+                num += 1
+                if on_step is not None:
+                    on_step(num, model)
+            means = (sums / max(steps, 1)).tolist()
+            for k, v in zip(TERMS, means):
+                record["losses"][k].append(v if steps else float("nan"))
+            warm.step()                                                                                          # :697
+            done_epochs = current + 1
+            wrote = False
+            if current % save_every == 0 or e == stage["epochs"] - 1:
+                write_weights(current, stage["name"])
+                val = _validate(trainer, model, test_loader, device, stage["number"], val_cap, ema)
+                record["validation"].append({"epoch": current, "stage": stage["name"], **val})
+                write_state(si, e, opt, warm, cosine)
+                wrote = True
+            if max_epochs is not None and done_epochs >= int(max_epochs) and done_epochs < total_epochs:
+                if not wrote:
+                    write_state(si, e, opt, warm, cosine)
+                stopped = True
+                break
+        if stopped:
+            break
+    if not stopped:
+        write_weights(total_epochs, "final")                                                                     # :731
+        write_state(len(stages), -1, opt, warm, cosine)
+    return {**record, "steps": num, "epochs": done_epochs, "finished": not stopped}

@@ -14,11 +14,20 @@ It is a ``torch.optim.Optimizer`` (param groups, ``zero_grad``, LR schedulers --
 ``exp_avg_sq``, the moments being views into one flat buffer per group).  The arithmetic is torch's single-tensor AdamW in its order of
 operations (``csrc/optimizer.hip``); the norm is ONE sum over all elements (fixed order, float64 final sum) instead of torch's norm of
 per-tensor norms: the same number to fp32 rounding.  No CPU path: CPU parameters raise.
+
+``step`` writes the parameters from a raw kernel, which autograd does not see; it then bumps their version counters (host only, no
+launch), so a weight pack cached on ``p._version`` (``DynamicUNet.plan_for``, ``UNet.plan_for``) is rebuilt by the next forward.
+``load_state_dict`` takes a state dict of this class or of ``torch.optim.AdamW`` (per-parameter ``step`` tensors on the CPU), copies the
+moments into fresh flat buffers and drops the cached device tables, so a resumed run goes on exactly where the saved one stopped.
+
+``EMA`` is the exponential moving average of the weights that a diffusion run samples from: the shadows are views into one flat fp32
+buffer, ``update()`` is ONE ``hdiff_ema_update`` launch over all tensors.
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
-from typing import Iterable, List, Optional, Tuple
+from typing import Dict, Iterable, List, Optional, Tuple
 
 import numpy as np
 import torch
@@ -56,6 +65,34 @@ class AdamW(torch.optim.Optimizer):
             st["exp_avg_sq"] = v_flat[off:off + p.numel()].view_as(p)
             off += p.numel()
 
+    def load_state_dict(self, state_dict) -> None:
+        """A state dict of this class or of ``torch.optim.AdamW``.  The moments are copied into fresh flat buffers (torch's loader
+        hands back the caller's own tensors where device and dtype already match), step counters become CPU tensors of their own
+        -- those that were one object stay one object -- and the cached device tables are dropped."""
+        super().load_state_dict(state_dict)
+        self._tables.clear()
+        self._chunk_cache.clear()
+        counters: dict = {}
+        for group in self.param_groups:
+            have = [p for p in group["params"] if "exp_avg" in self.state.get(p, {})]
+            if not have:
+                continue
+            n = sum(p.numel() for p in have)
+            m_flat = torch.empty(n, dtype=torch.float32, device=have[0].device)
+            v_flat = torch.empty(n, dtype=torch.float32, device=have[0].device)
+            off = 0
+            for p in have:
+                st = self.state[p]
+                for key, flat in (("exp_avg", m_flat), ("exp_avg_sq", v_flat)):
+                    view = flat[off:off + p.numel()].view_as(p)
+                    view.copy_(st[key])
+                    st[key] = view
+                off += p.numel()
+                c = st["step"]
+                if id(c) not in counters:
+                    counters[id(c)] = (c, torch.tensor(float(c.item() if torch.is_tensor(c) else c)))
+                st["step"] = counters[id(c)][1]
+
     def _table(self, gi: int, group: dict):
         ps = [p for p in group["params"] if p.grad is not None]
         for p in ps:
@@ -63,7 +100,8 @@ class AdamW(torch.optim.Optimizer):
                 raise RuntimeError("hdiff_amd.optim.AdamW runs on the GPU in fp32 only (there is no CPU path)")
             if not (p.is_contiguous() and p.grad.is_contiguous()):
                 raise RuntimeError("hdiff_amd.optim.AdamW: parameters and gradients must be contiguous")
-        sig = tuple((p.data_ptr(), p.grad.data_ptr(), self.state[p]["exp_avg"].data_ptr()) for p in ps)
+        sig = tuple((p.data_ptr(), p.grad.data_ptr(), self.state[p]["exp_avg"].data_ptr(), self.state[p]["exp_avg_sq"].data_ptr(),
+                     p.numel()) for p in ps)
         hit = self._tables.get(gi)
         if hit is not None and hit[0] == sig:
             return hit
@@ -169,6 +207,127 @@ class AdamW(torch.optim.Optimizer):
                         fresh = torch.tensor(float(step))
                         for i in cidx:
                             self.state[ps[i]]["step"] = fresh
+            torch.autograd.graph.increment_version(ps)      # the kernel wrote p behind autograd's back: caches keyed on p._version see it
         if max_grad_norm is not None:
             return self._norm_coef[0].clone()
         return loss
+
+
+class EMA:
+    """Exponential moving average of a list of parameters: ``shadow = shadow + (p - shadow) * (1 - decay)`` per ``update()``.
+
+        ema = EMA(model.parameters(), decay=0.9999)    # shadow = a copy of the weights now
+        ema.update()                                   # after every optimizer step; update(decay=d) overrides for this call
+        with ema.average_parameters():                 # weights <- shadow inside, restored on exit (also on an exception)
+            out = sampler(...)
+        ema.copy_to()                                  # weights <- shadow, for good
+
+    It covers ALL parameters handed in, whatever ``requires_grad`` says at that moment (``DynamicUNet`` flips it per batch).  GPU and
+    fp32 only.  The weights are swapped with copies autograd sees, so weight packs cached on ``p._version`` are rebuilt."""
+
+    def __init__(self, params: Iterable, decay: float = 0.9999):
+        self.params: List[torch.Tensor] = [p for p in params]
+        if not self.params:
+            raise ValueError("hdiff_amd.optim.EMA: no parameters")
+        self.decay = self._checked(decay)
+        self.num_updates = 0
+        self._check_params()
+        self._lib = _capi.lib()
+        self._chunk = int(self._lib.hdiff_opt_chunk())
+        dev = self.params[0].device
+        self._flat = torch.empty(sum(p.numel() for p in self.params), dtype=torch.float32, device=dev)
+        self.shadow: List[torch.Tensor] = []
+        off = 0
+        for p in self.params:
+            self.shadow.append(self._flat[off:off + p.numel()].view(p.shape))
+            off += p.numel()
+        with torch.no_grad():
+            torch._foreach_copy_(self.shadow, [p.detach() for p in self.params])
+        self._table = None            # (signature, table tensor, chunk tensor, nchunks)
+
+    @staticmethod
+    def _checked(decay) -> float:
+        decay = float(decay)
+        if not 0.0 <= decay <= 1.0:
+            raise ValueError(f"hdiff_amd.optim.EMA: decay must be in [0, 1], got {decay}")
+        return decay
+
+    def _check_params(self) -> None:
+        for p in self.params:
+            if not p.is_cuda or p.dtype != torch.float32:
+                raise RuntimeError("hdiff_amd.optim.EMA runs on the GPU in fp32 only (there is no CPU path)")
+            if not p.is_contiguous():
+                raise RuntimeError("hdiff_amd.optim.EMA: parameters must be contiguous")
+            if p.device != self.params[0].device:
+                raise RuntimeError("hdiff_amd.optim.EMA: parameters must be on one device")
+
+    def _tables(self):
+        sig = tuple((p.data_ptr(), s.data_ptr(), p.numel()) for p, s in zip(self.params, self.shadow))
+        if self._table is not None and self._table[0] == sig:
+            return self._table
+        self._check_params()
+        ps = [(p, s) for p, s in zip(self.params, self.shadow) if p.numel()]
+        tab = np.array([(s.data_ptr(), p.data_ptr(), p.numel()) for p, s in ps], dtype=np.int64).reshape(len(ps), 3)
+        chunks = [(i, c) for i, (p, _) in enumerate(ps) for c in range((p.numel() + self._chunk - 1) // self._chunk)]
+        dev = self._flat.device
+        self._table = (sig, torch.from_numpy(tab).to(dev), torch.tensor(chunks, dtype=torch.int32).reshape(len(chunks), 2).to(dev),
+                       len(chunks))
+        return self._table
+
+    @torch.no_grad()
+    def update(self, decay: Optional[float] = None) -> None:
+        """One ``hdiff_ema_update`` launch over all tensors, on the current stream of the parameters' device."""
+        d = self.decay if decay is None else self._checked(decay)
+        _, t_dev, c_dev, n = self._tables()
+        if n:
+            stream = torch.cuda.current_stream(self._flat.device).cuda_stream
+            with torch.cuda.device(self._flat.device):
+                _capi.check(self._lib.hdiff_ema_update(t_dev.data_ptr(), c_dev.data_ptr(), n, C.c_double(d), stream), "ema_update")
+        self.num_updates += 1
+
+    @torch.no_grad()
+    def copy_to(self, params: Optional[Iterable] = None) -> None:
+        """weights <- shadow (``params``: another list of the same shapes, default the averaged parameters themselves)."""
+        dst = self.params if params is None else [p for p in params]
+        if len(dst) != len(self.shadow):
+            raise ValueError(f"hdiff_amd.optim.EMA.copy_to: {len(dst)} parameters for {len(self.shadow)} shadows")
+        torch._foreach_copy_([p for p in dst], self.shadow)      # in-place writes autograd sees: p._version moves
+
+    @contextlib.contextmanager
+    def average_parameters(self):
+        """Inside: the parameters hold the shadow values.  On exit, also through an exception, they hold what they held before."""
+        with torch.no_grad():
+            flat, backup, off = torch.empty_like(self._flat), [], 0
+            for p in self.params:
+                backup.append(flat[off:off + p.numel()].view(p.shape))
+                off += p.numel()
+            torch._foreach_copy_(backup, [p.detach() for p in self.params])
+            torch._foreach_copy_(self.params, self.shadow)
+        try:
+            yield self
+        finally:
+            with torch.no_grad():
+                torch._foreach_copy_(self.params, backup)
+
+    def state_dict(self) -> dict:
+        return {"decay": self.decay, "num_updates": self.num_updates, "shadow": [s.clone() for s in self.shadow]}
+
+    @torch.no_grad()
+    def load_state_dict(self, sd: dict) -> None:
+        shadow = list(sd["shadow"])
+        if len(shadow) != len(self.shadow) or any(tuple(a.shape) != tuple(b.shape) for a, b in zip(shadow, self.shadow)):
+            raise ValueError("hdiff_amd.optim.EMA.load_state_dict: the shadows do not match the parameters")
+        self.decay = self._checked(sd["decay"])
+        self.num_updates = int(sd["num_updates"])
+        for dst, src in zip(self.shadow, shadow):
+            dst.copy_(src)
+        self._table = None
+
+    def shadow_state_dict(self, model: torch.nn.Module) -> Dict[str, torch.Tensor]:
+        """``model.state_dict()`` with every averaged parameter replaced by its shadow (clones; buffers and parameters that are not
+        averaged are copied through): what a checkpoint file of the averaged weights holds."""
+        by_id = {id(p): s for p, s in zip(self.params, self.shadow)}
+        names = {name: by_id[id(p)] for name, p in model.named_parameters(remove_duplicate=False) if id(p) in by_id}
+        if len({id(s) for s in names.values()}) != len(self.shadow):
+            raise ValueError("hdiff_amd.optim.EMA.shadow_state_dict: the model does not hold every averaged parameter")
+        return {k: (names[k] if k in names else v).detach().clone() for k, v in model.state_dict().items()}

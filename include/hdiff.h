@@ -667,6 +667,15 @@ int hdiff_grad_norm_clip_coef(const hdiff_opt_tensor* table, const int* chunks, 
                               float* norm_coef, hdiff_stream_t stream);
 int hdiff_adamw_step(const hdiff_opt_tensor* table, const int* chunks, int nchunks, const float* norm_coef, double lr, double beta1,
                      double beta2, double eps, double weight_decay, int64_t step, hdiff_stream_t stream);
+/* The exponential moving average of the weights that a diffusion run samples from, over a LIST of tensors in one launch:
+ *   avg = avg + (p - avg) * w,  w = (float)(1.0 - decay)
+ * in fp32, as three separately rounded operations (no contraction).  `table` (device) holds one entry per tensor, `chunks` (device) is cut
+ * as for hdiff_adamw_step: 2 ints per chunk (tensor index, chunk index inside the tensor), hdiff_opt_chunk() elements each, both built once
+ * by the host (hdiff_amd.optim.EMA).  Pointers need 4-byte alignment only; avg and p of one entry must not overlap.  decay in [0, 1];
+ * decay == 1 leaves avg bit for bit (nothing is launched).  No atomics, no reduction, no synchronisation, no allocation: legal under
+ * stream capture.  An addition to ABI 6. */
+typedef struct { float* avg; const float* p; long long n; } hdiff_ema_tensor;
+int hdiff_ema_update(const hdiff_ema_tensor* table, const int* chunks, int nchunks, double decay, hdiff_stream_t stream);
 /* nn.Dropout (train mode, ModelCondition.py:185) in its unfused form: keep-mask scaled by 1/keep from the Philox stream, and out = a*b
  * (the training path uses the keep bits below; these two remain for callers that want the tensors) */
 int hdiff_dropout_mask(float* out, int64_t n, float keep, uint64_t seed, uint64_t offset, hdiff_stream_t stream);
