@@ -34,7 +34,8 @@ using namespace hdiff;
 
 namespace {
 
-constexpr int kThreads = 256;
+#include "quality_common.h"
+
 constexpr int kTile = 32;
 constexpr int kWin = 7;
 constexpr int kSsimIn = kTile + kWin - 1;      // 38
@@ -49,7 +50,6 @@ constexpr int kPixPerBlock = kThreads * 16;
 struct Select { unsigned prefix, rank, less, eq; };
 
 __device__ __forceinline__ float scaled(float x) { return fminf(fmaxf(x, 0.0f), 1.0f) * 255.0f; }
-__device__ __forceinline__ bool non_finite(float x) { return !(fabsf(x) <= 3.402823466e+38f); }
 
 // order-preserving key of a finite fp32 value; -0 and +0 share a key
 __device__ __forceinline__ unsigned key_of(float f) {
@@ -59,30 +59,6 @@ __device__ __forceinline__ unsigned key_of(float f) {
 }
 __device__ __forceinline__ float value_of(unsigned k) {
   return __builtin_bit_cast(float, (k & 0x80000000u) ? (k & 0x7fffffffu) : ~k);
-}
-
-// Block-wide sum in a fixed order (wave sums, then in index order), returned to every thread; ends with a barrier.
-__device__ double block_sum_all(double v) {
-  __shared__ double part[kThreads / 64];
-  __shared__ double total;
-  v = wave_sum(v);
-  if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = v;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    double s = 0.0;
-    for (int i = 0; i < kThreads / 64; ++i) s += part[i];
-    total = s;
-  }
-  __syncthreads();
-  const double r = total;
-  __syncthreads();
-  return r;
-}
-
-__device__ double sum_partials(const double* __restrict__ p, int n, int stride) {
-  double acc = 0.0;
-  for (int i = threadIdx.x; i < n; i += kThreads) acc += p[(int64_t)i * stride];
-  return block_sum_all(acc);
 }
 
 // ---------------------------------------------------------------------------------------------------------------- PSNR / SSIM
@@ -515,18 +491,9 @@ __global__ __launch_bounds__(kThreads) void uiqm_finalize_kernel(const UiqmParam
 }
 
 // ---------------------------------------------------------------------------------------------------------------- host side
-inline int64_t align256(int64_t v) { return (v + 255) / 256 * 256; }
-
 int pix_blocks(int64_t K) {
   const int64_t b = (K + kPixPerBlock - 1) / kPixPerBlock;
   return b > kMaxPixBlocks ? kMaxPixBlocks : (int)b;
-}
-
-int check_sizes(const char* who, int N, int H, int W, int min_side) {
-  HDIFF_CHECK_ARG(N >= 1 && N <= 65535, "%s: N = %d; between 1 and 65535 images", who, N);
-  HDIFF_CHECK_ARG(H >= min_side && W >= min_side, "%s: H = %d, W = %d; both sides must be at least %d", who, H, W, min_side);
-  HDIFF_CHECK_ARG((int64_t)H * W <= (1ll << 30), "%s: H * W = %lld is too large; at most 2^30 pixels", who, (long long)H * W);
-  return HDIFF_OK;
 }
 
 int64_t ssim_bytes(int N, int tiles) { return align256((int64_t)N * 3 * tiles * 3 * (int64_t)sizeof(double)); }

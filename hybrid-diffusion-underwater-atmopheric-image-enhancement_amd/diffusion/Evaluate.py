@@ -1,18 +1,22 @@
-"""The evaluation loop of the reference's second tree (``utils/rotinas.py:839-1085`` ``test``, which ``Main.py --state inference``
-runs): sample a test set with the image-conditioned DDIM sampler and score every result with PSNR, SSIM and UIQM.  Here the scores
-are taken on the device, where the sampler leaves its output (``hdiff_amd.quality``); nothing is copied to the host per batch unless
-the images are to be saved.
+"""The evaluation loops of the reference's second tree (``utils/rotinas.py:839-1085`` ``test``, which ``Main.py --state inference``
+runs, and ``:1086`` ``inference``, which ``--state eval`` runs on the validation split): sample a set with the image-conditioned DDIM
+sampler and score every result with PSNR, SSIM, UIQM and, when asked for, UCIQE.  Here the scores are taken on the device, where the
+sampler leaves its output (``hdiff_amd.quality``); nothing is copied to the host per batch unless the images are to be saved.
 
 Deliberate deviations from the reference:
   * the target is scaled by 1 / 255.  ``rotinas.py:919`` clips the 0-255 target to [0, 1] and so compares against a binary image; that
     is not copied.
-  * FID, LPIPS and ``nmetrics`` / UCIQE are not computed: the first two need pretrained networks, the last stays on the unpinned host
-    path in ``uw_metrics``.  ``res.txt`` holds the reference's keys for what was measured and no others.
+  * FID and LPIPS are not computed: they need pretrained networks.  ``res.txt`` holds the reference's keys for what was measured and
+    no others.
+  * UCIQE (``uciqe=True``; the UCIQE part of ``nmetrics``, ``rotinas.py:923, 975-976``) is taken on the image's colour range by
+    default.  The reference hands ``nmetrics`` a float image in [0, 255] (``:916``), which the colour conversion inside takes as being
+    in [0, 1] already: ``uciqe_scale=255`` evaluates that, for comparing a ``res.txt`` with one of a reference run.
   * UIQM's parts are ``getUIQM``'s own (``quality.uiqm``); the reference reports the parts of ``nmetrics`` beside ``getUIQM``'s total.
   * images are written with Pillow, rounded to the nearest integer (``cv2.imwrite`` of a float image in the reference, which also
     swaps the red and blue channels on the way).
   * ``test`` scores every image of a set: the reference's loader drops the last incomplete batch.  Its file names are those of the
-    degraded images.
+    degraded images.  ``inference`` does the same on the validation split, and its means are ``sum / len``: the reference's
+    ``(sum + 1) / (len + 1)`` (``:1204-1211``) is not copied.
 """
 from __future__ import annotations
 
@@ -23,11 +27,13 @@ import torch
 
 from .. import quality
 
-__all__ = ["evaluate", "test", "RES_KEYS"]
+__all__ = ["evaluate", "test", "inference", "RES_KEYS", "RES_KEYS_UCIQE"]
 
 # res.txt: the reference's key for each measured score, in the reference's order (rotinas.py:967-982)
 RES_KEYS = (("psnr_orgin_avg:", "psnr"), ("ssim_orgin_avg:", "ssim"), ("uiqm_orgin_avg:", "uiqm"), ("uism_orgin_avg:", "uism"),
             ("uicm_orgin_avg:", "uicm"), ("uiconm_orgin_avg:", "uiconm"))
+# with UCIQE: its line directly after UIQM's, the reference's position (rotinas.py:973-976)
+RES_KEYS_UCIQE = RES_KEYS[:3] + (("uciqe_orgin_avg:", "uciqe"),) + RES_KEYS[3:]
 
 
 def _device_of(sampler) -> Optional[torch.device]:
@@ -45,24 +51,28 @@ def _save_batch(images01: torch.Tensor, names: Sequence[str], save_dir: str) -> 
         Image.fromarray(img).save(os.path.join(save_dir, name))
 
 
-def write_res(path: str, result: Dict[str, object]) -> None:
+def write_res(path: str, result: Dict[str, object], keys=RES_KEYS) -> None:
     with open(path, "w+") as f:
-        for key, k in RES_KEYS:
+        for key, k in keys:
             f.write("\n" + key)
             f.write(str(result[k]))
 
 
 def evaluate(sampler, batches: Iterable, *, ddim_step: int, tile: Optional[int] = None, tile_overlap: Optional[int] = None,
              tile_batch: Optional[int] = None, save_dir: Optional[str] = None, collect: Optional[List[torch.Tensor]] = None,
-             meter=None, solver: Optional[str] = None, spacing: Optional[str] = None) -> Dict[str, object]:
+             meter=None, solver: Optional[str] = None, spacing: Optional[str] = None, uciqe: bool = False,
+             uciqe_scale: float = 1.0) -> Dict[str, object]:
     """Samples and scores a set.  ``batches`` yields ``(input, target)`` or ``(input, target, names)``: CHW images in [0, 255] as
     ``Underwater_Dataset`` / ``Atmospheric_Dataset`` produce them, batched.  Per batch: ``out = sampler(input, ddim=True,
     unconditional_guidance_scale=1, ddim_step=ddim_step, tile=...)`` (rotinas.py:907), then ``(out + 1) / 2`` is scored against
     ``target / 255``.  ``collect``, a list, receives every ``out``.  With ``save_dir`` each result is written under its name
     (``<running index>.png`` without one) as uint8, and ``res.txt`` beside them.  ``meter``: a ``quality.QualityMeter`` to go on
     filling (a new one by default).  ``solver`` / ``spacing`` are the sampler's (``solver="dpmpp2m"``: DPM-Solver++(2M) on logSNR
-    time steps); ``None`` leaves the argument out of the call.  Returns ``QualityMeter.compute()``'s dict."""
-    meter = quality.QualityMeter() if meter is None else meter
+    time steps); ``None`` leaves the argument out of the call.  ``uciqe=True``: the default meter also scores UCIQE of
+    ``clip((out + 1) / 2, 0, 1) * uciqe_scale`` (``quality.QualityMeter(uciqe=True)``; a ``meter`` passed in must report "uciqe"
+    itself) and ``res.txt`` gets ``uciqe_orgin_avg:`` after UIQM's line.  Returns ``QualityMeter.compute()``'s dict."""
+    if meter is None:
+        meter = quality.QualityMeter(uciqe=True, uciqe_scale=uciqe_scale) if uciqe else quality.QualityMeter()
     dev = _device_of(sampler)
     if save_dir is not None:
         os.makedirs(save_dir, exist_ok=True)
@@ -85,7 +95,7 @@ def evaluate(sampler, batches: Iterable, *, ddim_step: int, tile: Optional[int] 
             done += int(inp.shape[0])
     result = meter.compute()
     if save_dir is not None:
-        write_res(os.path.join(save_dir, "res.txt"), result)
+        write_res(os.path.join(save_dir, "res.txt"), result, RES_KEYS_UCIQE if uciqe else RES_KEYS)
     return result
 
 
@@ -109,14 +119,8 @@ def _batched(dataset, batch_size: int) -> Iterator:
                [os.path.basename(dataset.paths_a[i]) for i in idx])
 
 
-def test(config, epoch=None) -> Dict[str, Dict[str, object]]:
-    """``rotinas.test(config, epoch)``: the test split of ``config.underwater_data_name`` and of ``config.atmospheric_data_name``
-    through ``DynamicUNet`` (``config.T / channel / channel_mult / num_res_blocks``) loaded from ``config.pretrained_path`` (a
-    state dict; ``module.`` prefixes are stripped), ``config.ddim_step`` DDIM steps, results under
-    ``output/result/<checkpoint file>/<set>/`` (``config.result_root`` replaces ``output/result``).  Optional keys: ``tile``,
-    ``tile_overlap``, ``tile_batch`` (overlapping-window sampling), ``solver``, ``spacing`` (the sampler's; absent: the reference's DDIM), ``dataset_root`` (one root for both sets, or a dict by set
-    name), ``transforms`` (the sets' ``transforms=``; default: their 256 x 256 resize), ``device_list`` (the first entry is used; default ``cuda:0``).  ``epoch`` is accepted and unused, as in the reference.
-    Returns ``{set name: evaluate()'s dict}``."""
+def _run_sets(config, task: str) -> Dict[str, Dict[str, object]]:
+    """The body ``test`` and ``inference`` share; ``task`` is the split both sets are opened with."""
     from ..datasets import Atmospheric_Dataset, Underwater_Dataset
     from .Diffusion import GaussianDiffusionSampler
     from .Model import DynamicUNet
@@ -128,8 +132,8 @@ def test(config, epoch=None) -> Dict[str, Dict[str, object]]:
         return root.get(name) if isinstance(root, dict) else root
 
     transforms = _cfg(config, "transforms", None)
-    sets = ((u_name, Underwater_Dataset(u_name, transforms=transforms, task="test", root=root_of(u_name))),
-            (a_name, Atmospheric_Dataset(a_name, transforms=transforms, task="test", root=root_of(a_name))))
+    sets = ((u_name, Underwater_Dataset(u_name, transforms=transforms, task=task, root=root_of(u_name))),
+            (a_name, Atmospheric_Dataset(a_name, transforms=transforms, task=task, root=root_of(a_name))))
     devices = _cfg(config, "device_list", None)
     device = torch.device(devices[0] if devices else "cuda:0")
     if device.type == "cuda" and device.index is None:
@@ -144,10 +148,32 @@ def test(config, epoch=None) -> Dict[str, Dict[str, object]]:
     sampler = GaussianDiffusionSampler(model, _cfg(config, "beta_1"), _cfg(config, "beta_T"), _cfg(config, "T")).to(device)
 
     base = os.path.join(_cfg(config, "result_root", os.path.join("output", "result")), os.path.basename(path))
+    extra = {}
+    if _cfg(config, "uciqe", False):
+        extra = dict(uciqe=True, uciqe_scale=float(_cfg(config, "uciqe_scale", 1.0)))
     results = {}
     for name, data in sets:
         results[name] = evaluate(sampler, _batched(data, int(_cfg(config, "batch_size"))), ddim_step=_cfg(config, "ddim_step"),
                                  tile=_cfg(config, "tile", None), tile_overlap=_cfg(config, "tile_overlap", None),
                                  tile_batch=_cfg(config, "tile_batch", None), save_dir=os.path.join(base, name),
-                                 solver=_cfg(config, "solver", None), spacing=_cfg(config, "spacing", None))
+                                 solver=_cfg(config, "solver", None), spacing=_cfg(config, "spacing", None), **extra)
     return results
+
+
+def test(config, epoch=None) -> Dict[str, Dict[str, object]]:
+    """``rotinas.test(config, epoch)``: the test split of ``config.underwater_data_name`` and of ``config.atmospheric_data_name``
+    through ``DynamicUNet`` (``config.T / channel / channel_mult / num_res_blocks``) loaded from ``config.pretrained_path`` (a
+    state dict; ``module.`` prefixes are stripped), ``config.ddim_step`` DDIM steps, results under
+    ``output/result/<checkpoint file>/<set>/`` (``config.result_root`` replaces ``output/result``).  Optional keys: ``tile``,
+    ``tile_overlap``, ``tile_batch`` (overlapping-window sampling), ``solver``, ``spacing`` (the sampler's; absent: the reference's DDIM), ``dataset_root`` (one root for both sets, or a dict by set
+    name), ``transforms`` (the sets' ``transforms=``; default: their 256 x 256 resize), ``device_list`` (the first entry is used; default ``cuda:0``),
+    ``uciqe``, ``uciqe_scale`` (``evaluate``'s; absent: no UCIQE, ``res.txt`` as before).
+    ``epoch`` is accepted and unused, as in the reference.  Returns ``{set name: evaluate()'s dict}``."""
+    return _run_sets(config, "test")
+
+
+def inference(config, epoch=None) -> Dict[str, Dict[str, object]]:
+    """``rotinas.inference(config, epoch)`` (``:1086``, ``Main.py --state eval``): the same loop on the validation split
+    (``task="val"``) of both sets, with ``test``'s keys, results under the same ``<result_root>/<checkpoint file>/<set>/``.  Every image
+    is scored, under the file name of its degraded image, and the means are ``sum / len``."""
+    return _run_sets(config, "val")

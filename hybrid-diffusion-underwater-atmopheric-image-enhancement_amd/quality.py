@@ -1,5 +1,5 @@
-"""PSNR / SSIM / UIQM on the device (``csrc/quality.hip``): the per-image scores of the reference's evaluation
-(``utils/rotinas.py:916-928``) taken where the sampler leaves its output, without a copy to the host per batch.
+"""PSNR / SSIM / UIQM (``csrc/quality.hip``) and UCIQE (``csrc/uciqe.hip``) on the device: the per-image scores of the reference's
+evaluation (``utils/rotinas.py:916-931``) taken where the sampler leaves its output, without a copy to the host per batch.
 
 Inputs are ``[N, 3, H, W]`` device tensors with nominal range [0, 1]; the kernels score ``clip(x, 0, 1) * 255`` as an fp32 image,
 which is what ``np.clip(img, 0, 1) * 255`` hands the reference's metric calls.  Definitions:
@@ -8,10 +8,14 @@ which is what ``np.clip(img, 0, 1) * 255`` hands the reference's metric calls.  
   * ``uiqm`` is ``uw_metrics.getUIQM`` with its parts (pinned to the reference's functions by ``tests/golden/uw_metrics.npz``), with
     ONE deliberate difference: the trimmed means of UICM add the kept samples in double, not in an fp32 running sum.  An image with a
     constant channel has ``uism = uiqm = NaN``, as on the host.
+  * ``uciqe`` is the UCIQE part of ``uw_metrics.nmetrics`` (CIE L*a*b* from sRGB in double; ``tests/_uciqe_def.py`` is the definition the
+    kernels are held to) of ``clip(x, 0, 1) * scale``.  ``scale=1`` scores the image on its colour range; ``scale=255`` evaluates what
+    the reference's call evaluates (a float image in [0, 255] handed to a conversion that takes floats as [0, 1]).  An image of fewer
+    than 50 pixels has ``conl = uciqe = NaN``, as on the host.
 
 A non-finite input value makes the scores of its image NaN and leaves the rest of the batch alone.  Results are bitwise repeatable
-and do not depend on the batch an image is scored in.  The scikit-image / OpenCV dependent ``nmetrics`` / ``uciqe`` stay on the
-host (``uw_metrics``).  There is no CPU fallback: CPU tensors are refused.
+and do not depend on the batch an image is scored in.  The other parts of ``nmetrics`` (its own UIQM variant) and the 8-bit OpenCV
+``uw_metrics.uciqe``, which the reference never calls, stay on the host.  There is no CPU fallback: CPU tensors are refused.
 """
 from __future__ import annotations
 
@@ -24,9 +28,10 @@ import torch
 from . import _capi
 from . import engine as E
 
-__all__ = ["psnr_ssim", "uiqm", "QualityMeter"]
+__all__ = ["psnr_ssim", "uiqm", "uciqe", "QualityMeter"]
 
 COLUMNS = ("psnr", "ssim", "uiqm", "uicm", "uism", "uiconm")      # the columns of QualityMeter's per-image rows
+UCIQE_COLUMNS = ("uciqe", "uciqe_sc", "uciqe_conl", "uciqe_us")   # the four more of QualityMeter(uciqe=True)
 
 
 def _image_batch(t: torch.Tensor, name: str) -> torch.Tensor:
@@ -51,6 +56,12 @@ def _scratch(N: int, H: int, W: int, dev) -> torch.Tensor:
     return torch.empty(need.value, dtype=torch.uint8, device=dev)
 
 
+def _uciqe_scratch(N: int, H: int, W: int, dev) -> torch.Tensor:
+    need = C.c_int64(0)
+    _capi.check(_capi.lib().hdiff_uciqe_workspace(N, H, W, C.byref(need)), "uciqe_workspace")
+    return torch.empty(need.value, dtype=torch.uint8, device=dev)
+
+
 def _stream(dev) -> int:
     return torch.cuda.current_stream(dev).cuda_stream
 
@@ -64,6 +75,12 @@ def _psnr_ssim_into(pred: torch.Tensor, target: torch.Tensor, out: torch.Tensor,
 def _uiqm_into(img: torch.Tensor, out: torch.Tensor, scratch: torch.Tensor) -> None:
     N, _, H, W = (int(v) for v in img.shape)
     _capi.check(_capi.lib().hdiff_uiqm(img.data_ptr(), N, H, W, out.data_ptr(), scratch.data_ptr(), _stream(img.device)), "uiqm")
+
+
+def _uciqe_into(img: torch.Tensor, scale: float, out: torch.Tensor, scratch: torch.Tensor) -> None:
+    N, _, H, W = (int(v) for v in img.shape)
+    _capi.check(_capi.lib().hdiff_uciqe(img.data_ptr(), N, H, W, float(scale), out.data_ptr(), scratch.data_ptr(),
+                                        _stream(img.device)), "uciqe")
 
 
 def psnr_ssim(pred01: torch.Tensor, target01: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
@@ -88,15 +105,30 @@ def uiqm(img01: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor,
     return out[:, 0], out[:, 1], out[:, 2], out[:, 3]
 
 
+def uciqe(img01: torch.Tensor, *, scale: float = 1.0) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """-> (sc[N], conl[N], us[N], uciqe[N]), float64 device tensors: chroma spread, luminance contrast (mean of the 1 % largest L minus
+    mean of the 1 % smallest), mean saturation, and ``0.4680 sc + 0.2745 conl + 0.2576 us``, of ``clip(img01, 0, 1) * scale``."""
+    img = _image_batch(img01, "img01")
+    N, _, H, W = (int(v) for v in img.shape)
+    out = torch.empty(N, 4, dtype=torch.float64, device=img.device)
+    with torch.cuda.device(img.device):
+        _uciqe_into(img, scale, out, _uciqe_scratch(N, H, W, img.device))
+    return out[:, 0], out[:, 1], out[:, 2], out[:, 3]
+
+
 class QualityMeter:
     """Accumulates per-image scores on the device: ``update`` per batch (never synchronises), ``compute`` once at the end (one copy).
 
     Rows are ``COLUMNS`` = (psnr, ssim, uiqm, uicm, uism, uiconm); psnr / ssim are NaN for the images of an ``update`` without a
-    target, and the means of those two are taken over the images that had one."""
+    target, and the means of those two are taken over the images that had one.  With ``uciqe=True`` every row gains
+    ``UCIQE_COLUMNS`` = (uciqe, uciqe_sc, uciqe_conl, uciqe_us) of ``clip(pred, 0, 1) * uciqe_scale`` (``quality.uciqe``); without it
+    the rows, the launches and ``compute``'s dict are those of the six columns alone."""
 
-    def __init__(self, capacity: int = 64):
+    def __init__(self, capacity: int = 64, *, uciqe: bool = False, uciqe_scale: float = 1.0):
         self._capacity = max(1, int(capacity))
-        self._rows: Optional[torch.Tensor] = None      # [capacity, 6] float64 on the device of the first update
+        self._uciqe, self._uciqe_scale = bool(uciqe), float(uciqe_scale)
+        self.columns = COLUMNS + UCIQE_COLUMNS if self._uciqe else COLUMNS
+        self._rows: Optional[torch.Tensor] = None      # [capacity, 6 or 10] float64 on the device of the first update
         self._n = 0
         self._updates = []                             # (first row, rows, had a target): host bookkeeping
 
@@ -107,14 +139,14 @@ class QualityMeter:
         if self._rows is None:
             while self._capacity < extra:
                 self._capacity *= 2
-            self._rows = torch.empty(self._capacity, len(COLUMNS), dtype=torch.float64, device=dev)
+            self._rows = torch.empty(self._capacity, len(self.columns), dtype=torch.float64, device=dev)
             return
         if self._rows.device != dev:
             raise RuntimeError(f"hdiff: QualityMeter holds rows on {self._rows.device}, the update is on {dev}")
         if self._n + extra > self._capacity:
             while self._capacity < self._n + extra:
                 self._capacity *= 2
-            grown = torch.empty(self._capacity, len(COLUMNS), dtype=torch.float64, device=dev)
+            grown = torch.empty(self._capacity, len(self.columns), dtype=torch.float64, device=dev)
             grown[:self._n].copy_(self._rows[:self._n])
             self._rows = grown
 
@@ -139,18 +171,23 @@ class QualityMeter:
             _uiqm_into(pred, four, scratch)             # same stream: the scratch is reused in order
             rows[:, 2].copy_(four[:, 3])
             rows[:, 3:6].copy_(four[:, 0:3])
+            if self._uciqe:
+                _uciqe_into(pred, self._uciqe_scale, four, _uciqe_scratch(N, H, W, dev))
+                rows[:, 6].copy_(four[:, 3])
+                rows[:, 7:10].copy_(four[:, 0:3])
         self._updates.append((self._n, N, target is not None))
         self._n += N
 
     def compute(self) -> Dict[str, object]:
         """{"n", "psnr", "ssim", "uiqm", "uicm", "uism", "uiconm"} as float means over the images (an infinite PSNR makes the mean
-        infinite, as the reference's ``sum(list) / len(list)`` does) and "per_image", the ``[n, 6]`` float64 rows."""
-        per = np.empty((0, len(COLUMNS))) if self._rows is None else self._rows[:self._n].cpu().numpy()
+        infinite, as the reference's ``sum(list) / len(list)`` does) and "per_image", the ``[n, 6]`` float64 rows; with ``uciqe=True``
+        also the means of ``UCIQE_COLUMNS``, and "per_image" is ``[n, 10]``."""
+        per = np.empty((0, len(self.columns))) if self._rows is None else self._rows[:self._n].cpu().numpy()
         paired = np.zeros(self._n, dtype=bool)
         for start, count, has_target in self._updates:
             paired[start:start + count] = has_target
         res: Dict[str, object] = {"n": int(self._n)}
-        for j, k in enumerate(COLUMNS):
+        for j, k in enumerate(self.columns):
             col = per[paired, j] if k in ("psnr", "ssim") else per[:, j]
             res[k] = float(np.sum(col) / col.size) if col.size else float("nan")
         res["per_image"] = per

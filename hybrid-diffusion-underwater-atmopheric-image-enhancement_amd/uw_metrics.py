@@ -1,7 +1,8 @@
 """Underwater image-quality measures used by the reference's evaluation (``utils/rotinas.py:923-928`` calls ``nmetrics`` and
 ``getUIQM`` of ``metrics/metrics.py``): UIQM = c1*UICM + c2*UISM + c3*UIConM, UCIQE, EME and logAMEE.  CPU / numpy: this is
 reporting code, not part of the GPU hot path.
-``hdiff_amd.quality.uiqm`` computes ``getUIQM`` and its three parts per image on the device (``csrc/quality.hip``).
+``hdiff_amd.quality.uiqm`` computes ``getUIQM`` and its three parts per image on the device (``csrc/quality.hip``), and
+``hdiff_amd.quality.uciqe`` the UCIQE part of ``nmetrics`` (``csrc/uciqe.hip``; definition: ``tests/_uciqe_def.py``).
 
 Parity:
   * ``getUIQM`` and its parts, ``eme`` and ``logamee`` are PINNED by golden vectors produced by the reference's own functions
@@ -11,6 +12,7 @@ Parity:
     ceil-sized edge blocks, zero extrema bumped to 1 -- is the one ``_uism`` ends up calling;
   * ``nmetrics`` and ``uciqe`` additionally need scikit-image / OpenCV colour conversions and edge filters, absent here:
     those are restated from the published definitions (CIE Lab D65, ITU-R 709 luma, 3x3 Sobel) and are UNPINNED.
+    ``_srgb_to_lab`` is anchored to the published CIE values of the sRGB primaries (``tests/test_uciqe_cpu.py``).
 """
 from __future__ import annotations
 

@@ -647,6 +647,20 @@ int hdiff_msssim_l1_bwd(const hdiff_msssim_desc* d, const float* x, const float*
 int hdiff_quality_workspace(int N, int H, int W, int64_t* bytes);
 int hdiff_psnr_ssim(const float* a, const float* b, int N, int H, int W, double* out, void* scratch, hdiff_stream_t stream);
 int hdiff_uiqm(const float* a, int N, int H, int W, double* out, void* scratch, hdiff_stream_t stream);
+/* UCIQE per image (csrc/uciqe.hip; the UCIQE part of the reference's `nmetrics`, metrics/metrics.py:301-337, called at
+ * utils/rotinas.py:923 and :1171).  a: fp32 [N][3][H][W]; rgb = double(min(max(x, 0), 1)) * scale is converted to CIE L*a*b* (D65) in
+ * double.  scale = 1 scores the image on its colour range; scale = 255 evaluates what the reference's call evaluates (it hands
+ * skimage.color.rgb2lab a float image in [0, 255], which takes floats as being in [0, 1] already).
+ *   hdiff_uciqe_workspace    bytes of `scratch` for hdiff_uciqe at (N, H, W) (two double planes per image and the partials; NOT
+ *                            covered by hdiff_quality_workspace, which returns what it always did)
+ *   hdiff_uciqe              out[n] = {sc = sqrt(mean((chroma - mean chroma)^2)), conl = mean(top largest L) - mean(top smallest L) with
+ *                            top = round_half_even(0.01 H W), us = mean(chroma / L, 0 where either is 0),
+ *                            UCIQE = 0.4680 sc + 0.2745 conl + 0.2576 us}; top == 0 (H W < 50): conl = UCIQE = NaN; sixteen launches
+ * N in [1, 65535], H, W >= 1, H * W <= 2^30, scale finite and > 0.  The cut values of L are selected on the 64-bit key of the double and
+ * ties at a cut are counted exactly.  A non-finite input value makes the four scores of ITS image NaN.  No allocation, no
+ * synchronisation, no float atomics: legal under stream capture, bitwise repeatable, independent of N and of the place in the batch. */
+int hdiff_uciqe_workspace(int N, int H, int W, int64_t* bytes);
+int hdiff_uciqe(const float* a, int N, int H, int W, double scale, double* out, void* scratch, hdiff_stream_t stream);
 /* final clip (:98) */
 int hdiff_clip(const float* x, float* y, float lo, float hi, int64_t n, hdiff_stream_t stream);
 /* out = a*x + b*y (y may be NULL): bias merges and other weight-preparation arithmetic */

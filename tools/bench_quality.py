@@ -10,7 +10,12 @@ each timing (bench.ClockSampler):
 
 Prints one line per timing and one JSON summary line.  The one condition checked (exit status 1 otherwise): the device arm for the
 WHOLE batch takes less than the host arm for ONE image in the same run -- any sound kernel clears that by an order of magnitude; it
-is there to catch a hidden per-image synchronisation or host fallback."""
+is there to catch a hidden per-image synchronisation or host fallback.
+
+With ``--uciqe`` three arms alternate instead: ``QualityMeter.update`` without UCIQE, ``QualityMeter(uciqe=True).update``, and the host
+path the latter replaces (copy the batch, then ``uw_metrics.nmetrics`` per image in one Python thread).  The JSON line holds what
+UCIQE adds per update (the difference of the two device arms), its ratio to the host path and to one 29.4 ms DDIM step; the
+condition checked is that the added device time for the whole batch stays below the host time for one image."""
 import argparse
 import json
 import os
@@ -31,6 +36,7 @@ ap.add_argument("--size", type=int, default=256)
 ap.add_argument("--alternate", type=int, default=3)
 ap.add_argument("--reps", type=int, default=50)
 ap.add_argument("--warmup", type=int, default=5)
+ap.add_argument("--uciqe", action="store_true", help="time QualityMeter.update without / with UCIQE against uw_metrics.nmetrics on the host")
 a = ap.parse_args()
 dev = torch.device("cuda", 0)
 torch.cuda.set_device(0)
@@ -43,8 +49,8 @@ pred = (target + 0.03 * torch.randn(a.batch, 3, a.size, a.size, generator=g)).cl
 pred_d, target_d = pred.to(dev), target.to(dev)
 
 
-def device_arm():
-    meter = quality.QualityMeter(capacity=a.batch * (a.reps + a.warmup))
+def device_arm(uciqe=False):
+    meter = quality.QualityMeter(capacity=a.batch * (a.reps + a.warmup), uciqe=uciqe)
     for _ in range(a.warmup):
         meter.update(pred_d, target_d)
     torch.cuda.synchronize(dev)
@@ -67,6 +73,47 @@ def host_arm():
         rows.append((metrics.psnr(ti, pi, 255.0), metrics.ssim(ti, pi, 255.0, channel_axis=2), uw_metrics.getUIQM(pi)))
     return (time.perf_counter() - t0) * 1e3, rows
 
+
+def timed(arm, label, fmt):
+    """One arm under the clock sampler: prints its line, returns (ms, what the arm returned)."""
+    clock = bench.ClockSampler(0)
+    with clock:
+        ms, res = arm()
+    c = clock.summary()
+    print(f"{label} {fmt(ms)}  sclk {c.get('sclk_mhz_mean')} MHz  board {c.get('board_power_w_mean')} W", flush=True)
+    return ms, res
+
+
+def uciqe_host_arm():
+    t0 = time.perf_counter()
+    p = pred_d.cpu().numpy().transpose(0, 2, 3, 1)
+    rows = [uw_metrics.nmetrics(np.clip(p[i], 0, 1).astype(np.float64))[1] for i in range(a.batch)]
+    return (time.perf_counter() - t0) * 1e3, rows
+
+
+if a.uciqe:
+    times = {"meter_ms": [], "meter_with_uciqe_ms": [], "host_nmetrics_batch_ms": []}
+    for rep in range(a.alternate):
+        per_update = lambda ms: f"{ms:.4f} ms per update of {a.batch} ({a.reps} updates between two events)"      # noqa: E731
+        ms0, _ = timed(device_arm, f"meter            rep {rep}:", per_update)
+        ms1, res = timed(lambda: device_arm(uciqe=True), f"meter with UCIQE rep {rep}:", per_update)
+        ms2, rows = timed(uciqe_host_arm, f"host nmetrics    rep {rep}:",
+                          lambda ms: f"{ms:.2f} ms per batch of {a.batch} = {ms / a.batch:.2f} ms per image")
+        for k, ms in zip(times, (ms0, ms1, ms2)):
+            times[k].append(ms)
+        gap = max(abs(res["per_image"][i, 6] - rows[i]) / abs(rows[i]) for i in range(a.batch))
+        print(f"                 device against host on this batch: UCIQE rel {gap:.1e}", flush=True)
+    summary = {k: {"mean": sum(v) / len(v), "min": min(v), "max": max(v), "repetitions": len(v)} for k, v in times.items()}
+    added = [w - p for w, p in zip(times["meter_with_uciqe_ms"], times["meter_ms"])]
+    added_worst, host_image_best = max(added), min(times["host_nmetrics_batch_ms"]) / a.batch
+    ok = added_worst < host_image_best
+    print(json.dumps({"metric": f"QualityMeter.update of one batch of {a.batch} at {a.size}x{a.size} without / with UCIQE, against "
+                                f"uw_metrics.nmetrics per image on the host, alternating",
+                      "unit": "ms/batch", "arms": summary, "uciqe_added_ms_per_update": {"mean": sum(added) / len(added), "max": added_worst},
+                      "host_over_added_device": summary["host_nmetrics_batch_ms"]["mean"] / (sum(added) / len(added)),
+                      "added_ms_over_29.4_ms_ddim_step": (sum(added) / len(added)) / 29.4,
+                      "host_ms_per_image_min": host_image_best, "added_device_batch_below_one_host_image": ok}))
+    sys.exit(0 if ok else 1)
 
 times = {"device_batch_ms": [], "host_batch_ms": []}
 for rep in range(a.alternate):
