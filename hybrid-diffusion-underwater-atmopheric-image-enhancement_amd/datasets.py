@@ -92,7 +92,7 @@ class _PairedSet(Dataset):
             raise ValueError(f"Dataset {name} not found. Choose between {sorted(self._SETS)}")
         default_root, load_a, load_b = self._SETS[name]
         self.root = root if root is not None else default_root
-        self.task, self.supervised = task, supervised
+        self.task, self.supervised, self.transforms = task, supervised, transforms
         self.transform = (lambda image: transforms(image=image)) if transforms is not None else _default_transform
         a, b = load_a(self.root), load_b(self.root)
         which = {"train": 0, "test": 1}.get(task, 2)

@@ -30,7 +30,17 @@ Additions, all optional (with none of them set the run is the loop above): ``dat
 set name), ``transforms`` (the sets' ``transforms=``), ``num_workers`` (4), ``seed`` (``torch.manual_seed`` before the model is
 built), ``max_steps_per_epoch``, ``max_val_batches``, ``max_epochs`` (stop after this many global epochs, having written the state
 file: a clean interruption), ``ema_decay`` (``None``: no EMA), ``resume`` (a state file to continue from), ``on_step`` (a callable
-``(step number, model)`` run after every optimizer step, for logging).
+``(step number, model)`` run after every optimizer step, for logging), and the data keys ``device_cache``, ``cache_dir``, ``augment``,
+``shuffle``, ``data_seed`` (below).
+
+With ``device_cache=True`` each of the four splits is decoded once (``device_data.build_cache``, stored under ``cache_dir``, default
+``<output_path>/cache``, and reused while the files' fingerprint holds), kept on the device as ``uint8``, and every batch is assembled
+there by one kernel (``device_data.DeviceLoader``).  Without ``augment`` and ``shuffle`` such a run computes what the host-loader run
+computes, bit for bit.  ``augment`` (an ``Augment`` or a dict of its arguments: ``hflip``, ``vflip``, ``rot90``, ``crop``, ``crop_min``)
+gives each training pair ONE geometric transform, drawn from ``(data_seed, global epoch, sample index)``; ``shuffle`` permutes the
+training set per epoch from the same key.  ``data_seed`` defaults to ``seed or 0``.  Test loaders never shuffle or augment.  Before
+every training epoch the driver calls ``set_epoch(global epoch)``, so a resumed run draws what the uninterrupted one draws.
+``augment`` or ``shuffle`` without ``device_cache`` raises: the sets' host ``transforms`` run once per image and cannot be paired.
 
 With ``ema_decay`` an ``optim.EMA`` of all weights is updated after every optimizer step and lives across the stage boundary (the
 optimizer does not); every checkpoint gets a sibling ``..._ema.pt`` (``EMA.shadow_state_dict``: the same keys, so ``Evaluate.test``
@@ -54,8 +64,8 @@ import torch
 
 from .Evaluate import _cfg
 
-__all__ = ["train", "stage_plan", "checkpoint_epochs", "checkpoint_name", "final_name", "expected_files", "lr_sequence", "TERMS",
-           "STATE_FILE"]
+__all__ = ["train", "data_plan", "stage_plan", "checkpoint_epochs", "checkpoint_name", "final_name", "expected_files", "lr_sequence",
+           "TERMS", "STATE_FILE"]
 
 TERMS = ("loss", "mse_loss", "perceptual_dino", "msssim", "col_loss")       # the trainer's return order (rotinas.py:439)
 WEIGHT_DECAY = 1e-4                                                          # rotinas.py:660
@@ -101,6 +111,31 @@ def expected_files(config) -> List[str]:
              for g, si, _ in checkpoint_epochs(plan[0]["epochs"], plan[1]["epochs"], _cfg(config, "save_checkpoint")) for k in kinds]
     names += [final_name(plan[0]["epochs"] + plan[1]["epochs"], u, a, k) for k in kinds]
     return sorted(names + [STATE_FILE])
+
+
+def data_plan(config) -> Dict[str, object]:
+    """What feeds the run, validated on the host: ``{"device_cache", "cache_dir", "augment" (an ``Augment`` or None), "shuffle",
+    "data_seed"}``.  With none of the keys set this is the reference's plan: host ``DataLoader``s, in order, no augmentation."""
+    from ..device_data import Augment
+    device_cache = bool(_cfg(config, "device_cache", False))
+    augment = _cfg(config, "augment", None)
+    if isinstance(augment, dict):
+        augment = Augment(**augment)
+    elif augment is not None and not isinstance(augment, Augment):
+        raise TypeError(f"hdiff_amd.diffusion.Train: augment must be an Augment or a dict of its arguments, got {type(augment).__name__}")
+    shuffle = bool(_cfg(config, "shuffle", False))
+    if (augment is not None or shuffle) and not device_cache:
+        raise ValueError("hdiff_amd.diffusion.Train: augment / shuffle need device_cache=True: host transforms cannot be paired (the "
+                         "sets call `transforms` once per image, so the two images of a pair would be flipped or cropped independently)")
+    data_seed = _cfg(config, "data_seed", None)
+    if data_seed is None:
+        data_seed = _cfg(config, "seed", None) or 0
+    if isinstance(data_seed, bool) or not isinstance(data_seed, int) or not 0 <= data_seed < 2 ** 64:
+        raise ValueError(f"hdiff_amd.diffusion.Train: data_seed = {data_seed!r}; an integer in [0, 2^64)")
+    cache_dir = _cfg(config, "cache_dir", None)
+    if cache_dir is None:
+        cache_dir = os.path.join(str(_cfg(config, "output_path")), "cache")
+    return {"device_cache": device_cache, "cache_dir": str(cache_dir), "augment": augment, "shuffle": shuffle, "data_seed": data_seed}
 
 
 def _schedulers(optimizer, multiplier: float, epochs: int):
@@ -180,6 +215,7 @@ def train(config) -> Dict[str, object]:
     from .Model import DynamicUNet
 
     _refuse_data_parallel(config)
+    plan = data_plan(config)
     device = _device(config)
     if _cfg(config, "wandb", False):
         warnings.warn("hdiff_amd.diffusion.Train.train: wandb is not wired; nothing is logged there", RuntimeWarning, stacklevel=2)
@@ -193,10 +229,16 @@ def train(config) -> Dict[str, object]:
     transforms = _cfg(config, "transforms", None)
     batch_size, workers = int(_cfg(config, "batch_size")), int(_cfg(config, "num_workers", 4))
 
-    def loader(data):                                                                               # :602-605
-        return DataLoader(data, batch_size=batch_size, num_workers=workers, drop_last=True, pin_memory=True)
+    def loader(data, name, task):                                                                   # :602-605
+        if not plan["device_cache"]:
+            return DataLoader(data, batch_size=batch_size, num_workers=workers, drop_last=True, pin_memory=True)
+        from ..device_data import DeviceLoader, build_cache
+        cache = build_cache(data, os.path.join(plan["cache_dir"], f"{name}_{task}.pt"), num_workers=workers).to(device)
+        train_side = task == "train"
+        return DeviceLoader(cache, batch_size, shuffle=plan["shuffle"] and train_side, drop_last=True,
+                            augment=plan["augment"] if train_side else None, seed=plan["data_seed"])
 
-    loaders = {(kind, task): loader(cls(name, transforms=transforms, task=task, root=root_of(name)))
+    loaders = {(kind, task): loader(cls(name, transforms=transforms, task=task, root=root_of(name)), name, task)
                for kind, cls, name in (("underwater", Underwater_Dataset, u_name), ("atmospheric", Atmospheric_Dataset, a_name))
                for task in ("train", "test")}
 
@@ -287,6 +329,8 @@ def train(config) -> Dict[str, object]:
         train_loader, test_loader = loaders[(stage["data"], "train")], loaders[(stage["data"], "test")]
         for e in range(e0, stage["epochs"]):
             current = start + e
+            if plan["device_cache"]:
+                train_loader.set_epoch(current)
             record["lr"].append(opt.param_groups[0]["lr"])
             sums, steps = torch.zeros(len(TERMS), dtype=torch.float64, device=device), 0
             for it, (inp, label) in enumerate(train_loader):

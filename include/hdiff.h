@@ -703,6 +703,25 @@ int hdiff_dropout_keep_bits(uint32_t* bits, int64_t n, float keep, uint64_t seed
 int hdiff_randn(float* out, int64_t n, uint64_t seed, uint64_t offset, hdiff_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------------------------
+ * One batch of image pairs gathered from a device-resident uint8 cache, with one geometric transform per pair (csrc/batch_assemble.hip;
+ * tests/_augment_def.py is the definition, matched bit for bit; hdiff_amd/device_data.py is the caller).  a, b: [N][3][H][W] (b may
+ * equal a), idx: B int64 sample indices on the device, each in [0, N) -- NOT checked on the device; out_a, out_b: [B][3][H][W].
+ * Sample i at `epoch` draws A = philox4x32_10(seed, i, 2 epoch) and R = philox4x32_10(seed, i, 2 epoch + 1) (the generator of
+ * hdiff_randn: key = the halves of seed, counter = the two 64-bit words).  An event happens iff its word is < its threshold, a
+ * probability scaled to [0, 2^32]: hflip A[0] < th_hflip, vflip A[1] < th_vflip, cropped A[3] < th_crop; k = A[2] >> 30 quarter turns if
+ * rot90.  A crop box has height ch = crop_lo_h + ((R[0] (H - crop_lo_h + 1)) >> 32), width cw = clamp((2 ch W + H) / (2 H), 1, W), origin
+ * y0 = (R[1] (H - ch + 1)) >> 32, x0 = (R[2] (W - cw + 1)) >> 32, and is magnified back to H x W bilinearly with half-pixel centres in
+ * integer arithmetic (taps clamped to the box, round half up).  Output = rot90(vflip(hflip(resize(box))), k), the same for all three
+ * channels and both images.  With all thresholds 0 and rot90 = 0 the output is a[idx], b[idx] byte for byte.
+ * Refused: null pointers; B < 1; N < 1; H or W outside [1, 4096]; a threshold above 2^32; crop_lo_h outside [1, H]; rot90 with H != W;
+ * epoch >= 2^31.  One launch, no atomics, no scratch, no allocation, no synchronisation: legal under stream capture; the bytes of
+ * sample j depend on (a, b, idx[j], seed, epoch, settings) alone.  An addition to ABI 6.
+ * ------------------------------------------------------------------------------------------------------------------ */
+int hdiff_batch_assemble(const uint8_t* a, const uint8_t* b, const int64_t* idx, int B, int64_t N, int H, int W, uint64_t seed,
+                         uint32_t epoch, uint64_t th_hflip, uint64_t th_vflip, int rot90, uint64_t th_crop, int crop_lo_h,
+                         uint8_t* out_a, uint8_t* out_b, hdiff_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------------------------
  * hipGraph helpers: capture everything enqueued on `stream` between begin/end, replay it later.
  * ------------------------------------------------------------------------------------------------------------------ */
 int hdiff_graph_begin(hdiff_stream_t stream);
