@@ -8,6 +8,11 @@
 // straddle the seam (384 channels / 32 groups = 12 per group, seam at 256), so sources are chosen per channel.
 // Each (sample, group) is split over `nsplit` workgroups; every workgroup produces (count, mean, M2) of its slice in one
 // pass over shifted data, and the partials are merged with Chan's formula.
+// A partial's mean is one fp32 number: its rounding enters the merge as 2 n_s (mean_s - mean) * rounding, about
+// (|mean| / std) * 2^-24 / sqrt(n_s) of the variance for partials of n_s elements -- 2e-4 in rstd for partials of 4 elements
+// of data whose mean is 1e4 std from zero, 3e-6 for 4096 per channel (both measured).  So a slice is never shorter than
+// GN_MIN_SLICE = 4096 elements of a plane, the shortest the planner makes (nsplit = HW / 4096): a caller of the C ABI that
+// asks for more splits than that gets empty ones (count = 0), which the merge skips.
 #include "common.h"
 #include "device.h"
 
@@ -16,6 +21,7 @@ using namespace hdiff;
 namespace {
 
 constexpr int GN_THREADS = 512;
+constexpr int GN_MIN_SLICE = 4096;      // elements of one channel plane
 
 __device__ __forceinline__ float block_sum(float v, float* red) {
   v = wave_sum(v);
@@ -75,19 +81,40 @@ __global__ __launch_bounds__(GN_THREADS) void gn_stats_kernel(const float* __res
   // slice of every channel plane handled by this split, in float4 units when HW % 4 == 0
   const bool vec = (HW & 3) == 0;
   const int units = vec ? HW >> 2 : HW;
-  const int per = (units + nsplit - 1) / nsplit;
+  // no slice shorter than GN_MIN_SLICE elements of a plane (the header comment says why): the splits a short plane does not
+  // fill are empty and write count = 0.  The planner's nsplit = HW / 4096 never meets the floor.
+  const int per = max((units + nsplit - 1) / nsplit, vec ? GN_MIN_SLICE / 4 : GN_MIN_SLICE);
   const int lo = split * per, hi = min(units, lo + per);
   const int cnt_units = max(0, hi - lo);
   const float count = (float)cnt_units * (vec ? 4.f : 1.f) * (float)cpg;
 
-  // ONE pass: sums of d = x - K and of d^2 with K = the slice's first element (a value near the mean keeps the
-  // subtraction mean^2 - mean(x^2)-style cancellation out of fp32: d is O(std), so M2 = S2 - S1^2/n loses nothing)
-  float K = 0.f;
-  if (cnt_units > 0) {
+  // ONE pass: sums of d = x - K and of d^2 with a pivot K near the mean, which keeps the mean^2 - mean(x^2)-style
+  // cancellation out of fp32: d is O(std), so M2 = S2 - S1^2/n loses nothing.  The slice's first element F is the pivot while
+  // it is typical of the slice, which is checked against up to GN_THREADS elements spread evenly over the slice, one per thread
+  // (all of them when the slice is that short): with u = sample - F, F stays if mean(u)^2 <= 24 var(u), i.e. the cancellation
+  // costs a factor of at most 25 on fp32's 6e-8.  Otherwise -- F is the top-left corner pixel of a plane, where zero-padded
+  // conv stacks put their outliers -- K = F + mean(u), the mean of the samples, which no single element can drag away: that
+  // would take an outlier worth more than m^2 of the n elements' variance for m samples.  K depends on this (sample, group,
+  // split)'s data alone, and block_sum hands every thread the same bits.
+  const int slice_el = cnt_units * (vec ? 4 : 1);            // elements of one channel plane inside the slice
+  const int total_el = slice_el * cpg;                       // <= cpg * HW: the tensor itself is indexed with int elsewhere
+  const int nsamp = min(GN_THREADS, total_el);
+  float F = 0.f, u = 0.f;
+  if (nsamp > 0) {
     const int c = g * cpg;
     const float* plane = (c < C0) ? x0 + ((size_t)b * C0 + c) * HW : x1 + ((size_t)b * C1 + (c - C0)) * HW;
-    K = plane[vec ? 4 * lo : lo];
+    F = plane[vec ? 4 * lo : lo];
   }
+  if ((int)threadIdx.x < nsamp) {
+    const int j = (int)(((long long)threadIdx.x * total_el) / nsamp);      // < total_el
+    const int cc = j / slice_el, c = g * cpg + cc;
+    const float* plane = (c < C0) ? x0 + ((size_t)b * C0 + c) * HW : x1 + ((size_t)b * C1 + (c - C0)) * HW;
+    u = plane[(vec ? 4 * lo : lo) + (j - cc * slice_el)] - F;
+  }
+  const float su = block_sum(u, red), su2 = block_sum(u * u, red);     // every thread reaches them, also those without a sample
+  const float mu = nsamp > 0 ? su / (float)nsamp : 0.f;
+  const float var_u = nsamp > 0 ? su2 / (float)nsamp - mu * mu : 0.f;
+  const float K = (mu * mu <= 24.f * var_u) ? F : F + mu;               // (a NaN or an overflow compares false: the samples' mean)
   float s1 = 0.f, s2 = 0.f;
   for (int cc = 0; cc < cpg; ++cc) {
     const int c = g * cpg + cc;

@@ -278,7 +278,8 @@ int hdiff_conv_wgrad_unpack(const float* dwp, int nsplit, float* dw, int mode, i
  * and the Swish at :22-24 are applied inside the consuming convolution's prologue).
  *   hdiff_gn_stats:    partial (count, mean, M2) per (sample, group, split) over the virtual concat input
  *   hdiff_gn_finalize: combines the partials (Chan) and writes scale[b][c] = rstd*gamma[c], shift[b][c] = beta[c]-mean*scale
- * ws must hold B*G*nsplit*3 floats.
+ * ws must hold B*G*nsplit*3 floats.  A split covers at least 4096 elements of a plane; with more splits than that
+ * allows the rest are empty (count 0) and the merge skips them.
  * ------------------------------------------------------------------------------------------------------------------ */
 int hdiff_gn_stats(const float* x0, const float* x1, int C0, int C1, int B, int HW, int G, int nsplit, float* ws,
                    hdiff_stream_t stream);
