@@ -10,12 +10,27 @@ form, every channel at every scale.  The kornia layout was written from memory o
 is unpinned; what the tests pin is the definition.
 
 Use with the trainer: ``GaussianDiffusionTrainer(model, beta_1, beta_T, T, msssim_loss=MSSSIMLoss())``.
+
+``PerceptualLoss_vgg`` (reference ``:159-241``) and ``CharbonnierLoss`` (``:286-300``) are here too, on ``hdiff_amd.perceptual``: the VGG
+trunk's convs are the package's conv kernels, ReLU / pooling / the L1 mean / the Charbonnier map are ``csrc/perceptual.hip``.  No
+pretrained weights ship and none are fetched: the caller hands ``PerceptualLoss_vgg`` a torchvision state dict (``weights=``); without
+one the trunk is randomly initialised and says so.  Deliberate deviations: the target's features are taken under ``no_grad`` (the
+target is a constant, as for ``MSSSIMLoss``); the ``*_bn``, ``squeeze`` and ``alex`` trunks are not provided.  The Charbonnier formula
+``sqrt(d^2 + 1) - 1`` was written from memory of kornia's ``charbonnier_loss``: agreement with kornia itself is unpinned.  Pass either
+to the trainer through ``extra_losses=[(name, weight, loss), ...]``.
 """
 from __future__ import annotations
 
+import warnings
+
+import torch
 import torch.nn as nn
 
-__all__ = ["MSSSIMLoss"]
+__all__ = ["MSSSIMLoss", "PerceptualLoss_vgg", "CharbonnierLoss"]
+
+_UNSUPPORTED = ("Unsupported perceptual model type. Choose from ['vgg11', 'vgg11_bn', 'vgg13', 'vgg13_bn', 'vgg16', 'vgg16_bn', "
+                "'vgg19', 'vgg19_bn', 'squeeze', 'alex']")
+_NOT_PROVIDED = ("vgg11_bn", "vgg13_bn", "vgg16_bn", "vgg19_bn", "squeeze", "alex")
 
 
 class MSSSIMLoss(nn.Module):
@@ -42,3 +57,97 @@ class MSSSIMLoss(nn.Module):
     def forward(self, input, target):
         from ..autograd import msssim_l1_loss
         return msssim_l1_loss(input, target, config=self._cfg)
+
+
+class PerceptualLoss_vgg(nn.Module):
+    """forward(x, y) -> 0-dim tensor: the sum over the tapped layers of ``mean |feat(x) - feat(y)|`` (reference ``:217-233``; no input
+    normalisation, it is commented out there).  ``x`` is differentiated; ``y``'s features are taken under ``no_grad``.
+
+    ``weights``: a torchvision state dict of ``model`` (or the path of a file ``torch.load`` reads one from).  Without it the trunk
+    keeps its random initialisation and one ``RuntimeWarning`` says so.  ``.perceptual`` is the ``hdiff_amd.perceptual.VGGFeatures``;
+    move the loss to the device of the images (``.to(device)``) like any module."""
+
+    def __init__(self, id: int = None, model='vgg16', layer_indices=None, *, weights=None):
+        super().__init__()
+        from ..perceptual import VGG_CFGS, VGGFeatures
+        self._id = id
+        if model in _NOT_PROVIDED:
+            raise ValueError(f"perceptual model '{model}' is not provided: the HIP path has the plain VGG trunks {sorted(VGG_CFGS)} "
+                             "(no batch norm, no SqueezeNet, no AlexNet)")
+        if model not in VGG_CFGS:
+            raise ValueError(_UNSUPPORTED)
+        self.perceptual = VGGFeatures(model)
+        self._model = model
+        if weights is None:
+            warnings.warn(f"PerceptualLoss_vgg: no weights were given; the {model} trunk is randomly initialised (pass weights=, a "
+                          "torchvision state dict or its path)", RuntimeWarning, stacklevel=2)
+        else:
+            if not isinstance(weights, dict):
+                weights = torch.load(weights, map_location="cpu")
+            self.perceptual.load_torchvision(weights)
+        self.layer_indices = {
+            'squeeze':  [3, 7, 12],
+            'vgg11':    [3, 8, 15, 22],
+            'vgg11_bn': [3, 8, 15, 22],
+            'vgg13':    [3, 8, 15, 22],
+            'vgg13_bn': [3, 8, 15, 22],
+            'vgg16':    [3, 8, 15, 22],
+            'vgg16_bn': [3, 8, 15, 22],
+            'vgg19':    [3, 8, 17, 26, 35],
+            'vgg19_bn': [3, 8, 17, 26, 35],
+            'alex':     [3, 6, 8, 10, 12],
+        }
+        if layer_indices is not None:
+            self.layer_indices[model] = layer_indices
+
+    @property
+    def name(self):
+        return self.__class__.__name__ + '_' + self._model
+
+    @property
+    def id(self):
+        return self._id
+
+    def extract_features(self, x):
+        return self.perceptual(x, self.layer_indices[self._model])
+
+    def forward(self, x, y):
+        from ..perceptual import l1_mean
+        x_features = self.extract_features(x)
+        with torch.no_grad():
+            y_features = self.extract_features(y)
+        loss = None
+        for xf, yf in zip(x_features, y_features):
+            term = l1_mean(xf, yf).double()          # the handful of per-layer means are added in double and rounded once
+            loss = term if loss is None else loss + term
+        if loss is not None:
+            loss = loss.float()
+        if loss is None:
+            raise RuntimeError(f"PerceptualLoss_vgg: none of the layer indices {self.layer_indices[self._model]} is a layer of "
+                               f"{self._model}")
+        return loss
+
+
+class CharbonnierLoss(nn.Module):
+    """forward(input, target) -> ``sqrt((input - target)^2 + 1) - 1`` (reference ``:286-300``, kornia's ``charbonnier_loss`` with its
+    default ``reduction='none'``: an elementwise map); ``reduction='mean'`` / ``'sum'`` reduce it in a fixed order.  ``input`` is
+    differentiated, ``target`` is not."""
+
+    def __init__(self, id: int = None, *, reduction: str = 'none'):
+        super().__init__()
+        if reduction not in ("none", "mean", "sum"):
+            raise ValueError(f"Invalid reduction mode: {reduction}. Expected one of 'none', 'mean', 'sum'.")
+        self._id = id
+        self.reduction = reduction
+
+    @property
+    def name(self):
+        return self.__class__.__name__
+
+    @property
+    def id(self):
+        return self._id
+
+    def forward(self, input, target):
+        from ..perceptual import charbonnier
+        return charbonnier(input, target, self.reduction)

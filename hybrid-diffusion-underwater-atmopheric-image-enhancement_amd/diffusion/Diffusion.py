@@ -55,8 +55,38 @@ def extract(v, t, x_shape):
     return out.view([t.shape[0]] + [1] * (len(x_shape) - 1))
 
 
+def _checked_extra_losses(extra_losses):
+    """-> a tuple of ``(name, weight, callable)``; ``ValueError`` / ``TypeError`` for anything else.  Looks at no device."""
+    if extra_losses is None:
+        return ()
+    if isinstance(extra_losses, (str, bytes, dict)) or not hasattr(extra_losses, "__iter__"):
+        raise TypeError("extra_losses must be a sequence of (name, weight, callable)")
+    out, names = [], set()
+    for entry in extra_losses:
+        if not isinstance(entry, (tuple, list)) or len(entry) != 3:
+            raise ValueError(f"extra_losses: every entry is (name, weight, callable), got {entry!r}")
+        name, weight, fn = entry
+        if not isinstance(name, str) or not name:
+            raise ValueError(f"extra_losses: a term's name must be a non-empty string, got {name!r}")
+        if name in names:
+            raise ValueError(f"extra_losses: the name {name!r} appears twice")
+        if isinstance(weight, bool) or not isinstance(weight, (int, float)) or weight != weight or weight in (float("inf"), -float("inf")):
+            raise ValueError(f"extra_losses: the weight of {name!r} must be a finite number, got {weight!r}")
+        if not callable(fn):
+            raise TypeError(f"extra_losses: the term {name!r} is not callable")
+        names.add(name)
+        out.append((name, float(weight), fn))
+    return tuple(out)
+
+
 class GaussianDiffusionTrainer(nn.Module):
     """forward(gt_images, input_image, stage) -> [loss, mse_loss, perceptual_dino, msssim, col_loss] (reference :26-180).
+
+    ``extra_losses``: a sequence of ``(name, weight, callable)``; each ``callable(y_0_pred, gt_images) * weight`` is added to ``loss``
+    (an elementwise map broadcasts into it as it would in the reference's commented-out recipes, :111-136).  The returned list stays
+    the reference's five entries; the detached weighted values of the last call are in ``trainer.extra_terms``, a dict by name.
+    ``Loss.loss.PerceptualLoss_vgg`` and ``CharbonnierLoss`` are the package's own terms for it.  ``None`` or empty runs what ran
+    before, bit for bit.
 
     ``perceptual_vgg`` / ``perceptual_dino`` are the reference's model names; they are recorded but never loaded (no
     ``torch.hub``, no kornia).  ``dino_loss`` / ``msssim_loss`` are callables ``(y_0_pred, gt) -> scalar tensor`` for those two
@@ -66,8 +96,18 @@ class GaussianDiffusionTrainer(nn.Module):
     DINO_WEIGHT, MSSSIM_WEIGHT, COL_WEIGHT = 0.5, 0.0045, 1.0          # reference :165
 
     def __init__(self, model, beta_1, beta_T, T, perceptual_vgg: str = "vgg16", perceptual_dino: str = "dinov2_vits14", *,
-                 dino_loss=None, msssim_loss=None):
+                 dino_loss=None, msssim_loss=None, **more):
         super().__init__()
+        # extra_losses arrives through **more: the NAMED keyword-only arguments stay the two callables of the reference's own terms
+        # (tests/test_train_b_cpu.py holds the signature to that)
+        extra_losses = more.pop("extra_losses", None)
+        if more:
+            raise TypeError(f"GaussianDiffusionTrainer.__init__() got an unexpected keyword argument '{next(iter(more))}'")
+        self.extra_losses = _checked_extra_losses(extra_losses)
+        self.extra_terms = {}
+        held = [fn for _, _, fn in self.extra_losses if isinstance(fn, nn.Module)]
+        if held:      # terms that are modules travel with the trainer's .to(device), as dino_loss / msssim_loss do by being attributes
+            self.extra_loss_modules = nn.ModuleList(held)
         self.model = model
         self.T = T
         self.register_buffer('betas', torch.linspace(beta_1, beta_T, T).double())
@@ -150,6 +190,13 @@ class GaussianDiffusionTrainer(nn.Module):
             loss = loss + msssim
         col_loss = col * self.COL_WEIGHT                                                                   # :174-175
         loss = loss + col_loss
+        if self.extra_losses:
+            terms = {}
+            for name, weight, fn in self.extra_losses:
+                term = fn(y_0_pred, gt_images) * weight
+                loss = loss + term
+                terms[name] = term.detach()
+            self.extra_terms = terms
         return [loss, mse_loss, perceptual_dino, msssim, col_loss]
 
 

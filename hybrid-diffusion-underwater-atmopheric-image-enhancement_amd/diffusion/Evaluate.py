@@ -6,8 +6,10 @@ sampler leaves its output (``hdiff_amd.quality``); nothing is copied to the host
 Deliberate deviations from the reference:
   * the target is scaled by 1 / 255.  ``rotinas.py:919`` clips the 0-255 target to [0, 1] and so compares against a binary image; that
     is not copied.
-  * FID and LPIPS are not computed: they need pretrained networks.  ``res.txt`` holds the reference's keys for what was measured and
-    no others.
+  * FID is not computed: it needs a pretrained Inception.  LPIPS (``rotinas.py`` imports ``lpips``) is computed when the caller brings
+    the weights: ``lpips=`` a ``quality.LPIPS`` (config key ``lpips``, or ``lpips_weights``, the path of a file holding
+    ``{"vgg": <torchvision vgg16 state dict>, "lin": <the five lin weights>}``); ``res.txt`` then ends with ``lpips_orgin_avg:``.  Without
+    it ``res.txt`` holds the reference's keys for what was measured and no others.
   * UCIQE (``uciqe=True``; the UCIQE part of ``nmetrics``, ``rotinas.py:923, 975-976``) is taken on the image's colour range by
     default.  The reference hands ``nmetrics`` a float image in [0, 255] (``:916``), which the colour conversion inside takes as being
     in [0, 1] already: ``uciqe_scale=255`` evaluates that, for comparing a ``res.txt`` with one of a reference run.
@@ -27,13 +29,15 @@ import torch
 
 from .. import quality
 
-__all__ = ["evaluate", "test", "inference", "RES_KEYS", "RES_KEYS_UCIQE"]
+__all__ = ["evaluate", "test", "inference", "RES_KEYS", "RES_KEYS_UCIQE", "RES_KEY_LPIPS"]
 
 # res.txt: the reference's key for each measured score, in the reference's order (rotinas.py:967-982)
 RES_KEYS = (("psnr_orgin_avg:", "psnr"), ("ssim_orgin_avg:", "ssim"), ("uiqm_orgin_avg:", "uiqm"), ("uism_orgin_avg:", "uism"),
             ("uicm_orgin_avg:", "uicm"), ("uiconm_orgin_avg:", "uiconm"))
 # with UCIQE: its line directly after UIQM's, the reference's position (rotinas.py:973-976)
 RES_KEYS_UCIQE = RES_KEYS[:3] + (("uciqe_orgin_avg:", "uciqe"),) + RES_KEYS[3:]
+# with LPIPS: one last line, behind whichever list is in use
+RES_KEY_LPIPS = ("lpips_orgin_avg:", "lpips")
 
 
 def _device_of(sampler) -> Optional[torch.device]:
@@ -61,7 +65,7 @@ def write_res(path: str, result: Dict[str, object], keys=RES_KEYS) -> None:
 def evaluate(sampler, batches: Iterable, *, ddim_step: int, tile: Optional[int] = None, tile_overlap: Optional[int] = None,
              tile_batch: Optional[int] = None, save_dir: Optional[str] = None, collect: Optional[List[torch.Tensor]] = None,
              meter=None, solver: Optional[str] = None, spacing: Optional[str] = None, uciqe: bool = False,
-             uciqe_scale: float = 1.0) -> Dict[str, object]:
+             uciqe_scale: float = 1.0, lpips=None) -> Dict[str, object]:
     """Samples and scores a set.  ``batches`` yields ``(input, target)`` or ``(input, target, names)``: CHW images in [0, 255] as
     ``Underwater_Dataset`` / ``Atmospheric_Dataset`` produce them, batched.  Per batch: ``out = sampler(input, ddim=True,
     unconditional_guidance_scale=1, ddim_step=ddim_step, tile=...)`` (rotinas.py:907), then ``(out + 1) / 2`` is scored against
@@ -70,9 +74,14 @@ def evaluate(sampler, batches: Iterable, *, ddim_step: int, tile: Optional[int] 
     filling (a new one by default).  ``solver`` / ``spacing`` are the sampler's (``solver="dpmpp2m"``: DPM-Solver++(2M) on logSNR
     time steps); ``None`` leaves the argument out of the call.  ``uciqe=True``: the default meter also scores UCIQE of
     ``clip((out + 1) / 2, 0, 1) * uciqe_scale`` (``quality.QualityMeter(uciqe=True)``; a ``meter`` passed in must report "uciqe"
-    itself) and ``res.txt`` gets ``uciqe_orgin_avg:`` after UIQM's line.  Returns ``QualityMeter.compute()``'s dict."""
+    itself) and ``res.txt`` gets ``uciqe_orgin_avg:`` after UIQM's line.  ``lpips``: a ``quality.LPIPS``; the default meter also scores the
+    LPIPS distance of ``(out + 1) / 2`` from ``target / 255`` (a ``meter`` passed in must report "lpips" itself), the result gains
+    ``"lpips"`` and ``res.txt`` a last line ``lpips_orgin_avg:``.  Returns ``QualityMeter.compute()``'s dict."""
     if meter is None:
-        meter = quality.QualityMeter(uciqe=True, uciqe_scale=uciqe_scale) if uciqe else quality.QualityMeter()
+        if lpips is not None:
+            meter = quality.QualityMeter(uciqe=bool(uciqe), uciqe_scale=uciqe_scale, lpips=lpips)
+        else:
+            meter = quality.QualityMeter(uciqe=True, uciqe_scale=uciqe_scale) if uciqe else quality.QualityMeter()
     dev = _device_of(sampler)
     if save_dir is not None:
         os.makedirs(save_dir, exist_ok=True)
@@ -95,7 +104,8 @@ def evaluate(sampler, batches: Iterable, *, ddim_step: int, tile: Optional[int] 
             done += int(inp.shape[0])
     result = meter.compute()
     if save_dir is not None:
-        write_res(os.path.join(save_dir, "res.txt"), result, RES_KEYS_UCIQE if uciqe else RES_KEYS)
+        keys = RES_KEYS_UCIQE if uciqe else RES_KEYS
+        write_res(os.path.join(save_dir, "res.txt"), result, keys + (RES_KEY_LPIPS,) if lpips is not None else keys)
     return result
 
 
@@ -151,6 +161,12 @@ def _run_sets(config, task: str) -> Dict[str, Dict[str, object]]:
     extra = {}
     if _cfg(config, "uciqe", False):
         extra = dict(uciqe=True, uciqe_scale=float(_cfg(config, "uciqe_scale", 1.0)))
+    lpips = _cfg(config, "lpips", None)
+    if lpips is None and _cfg(config, "lpips_weights", None) is not None:
+        held = torch.load(_cfg(config, "lpips_weights"), map_location="cpu")
+        lpips = quality.LPIPS(held["vgg"], held["lin"])
+    if lpips is not None:
+        extra["lpips"] = lpips.to(device)
     results = {}
     for name, data in sets:
         results[name] = evaluate(sampler, _batched(data, int(_cfg(config, "batch_size"))), ddim_step=_cfg(config, "ddim_step"),
@@ -167,7 +183,8 @@ def test(config, epoch=None) -> Dict[str, Dict[str, object]]:
     ``output/result/<checkpoint file>/<set>/`` (``config.result_root`` replaces ``output/result``).  Optional keys: ``tile``,
     ``tile_overlap``, ``tile_batch`` (overlapping-window sampling), ``solver``, ``spacing`` (the sampler's; absent: the reference's DDIM), ``dataset_root`` (one root for both sets, or a dict by set
     name), ``transforms`` (the sets' ``transforms=``; default: their 256 x 256 resize), ``device_list`` (the first entry is used; default ``cuda:0``),
-    ``uciqe``, ``uciqe_scale`` (``evaluate``'s; absent: no UCIQE, ``res.txt`` as before).
+    ``uciqe``, ``uciqe_scale`` (``evaluate``'s; absent: no UCIQE, ``res.txt`` as before), ``lpips`` (a ``quality.LPIPS``) or
+    ``lpips_weights`` (the path of a file holding ``{"vgg": ..., "lin": ...}``; absent: no LPIPS, ``res.txt`` as before).
     ``epoch`` is accepted and unused, as in the reference.  Returns ``{set name: evaluate()'s dict}``."""
     return _run_sets(config, "test")
 

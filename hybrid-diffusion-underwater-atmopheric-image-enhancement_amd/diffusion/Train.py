@@ -30,7 +30,9 @@ Additions, all optional (with none of them set the run is the loop above): ``dat
 set name), ``transforms`` (the sets' ``transforms=``), ``num_workers`` (4), ``seed`` (``torch.manual_seed`` before the model is
 built), ``max_steps_per_epoch``, ``max_val_batches``, ``max_epochs`` (stop after this many global epochs, having written the state
 file: a clean interruption), ``ema_decay`` (``None``: no EMA), ``resume`` (a state file to continue from), ``on_step`` (a callable
-``(step number, model)`` run after every optimizer step, for logging), and the data keys ``device_cache``, ``cache_dir``, ``augment``,
+``(step number, model)`` run after every optimizer step, for logging), ``extra_losses`` (handed to the trainer unchanged: a sequence
+of ``(name, weight, callable)`` added to ``loss``, e.g. ``Loss.loss.PerceptualLoss_vgg`` / ``CharbonnierLoss``; ``TERMS``, the records
+and the checkpoints are the same with and without it), and the data keys ``device_cache``, ``cache_dir``, ``augment``,
 ``shuffle``, ``data_seed`` (below).
 
 With ``device_cache=True`` each of the four splits is decoded once (``device_data.build_cache``, stored under ``cache_dir``, default
@@ -257,7 +259,8 @@ def train(config) -> Dict[str, object]:
         from ..Loss.loss import MSSSIMLoss
         msssim_loss = MSSSIMLoss()
     trainer = GaussianDiffusionTrainer(model, _cfg(config, "beta_1"), _cfg(config, "beta_T"), _cfg(config, "T"),
-                                       dino_loss=_cfg(config, "dino_loss", None), msssim_loss=msssim_loss).to(device)   # :629
+                                       dino_loss=_cfg(config, "dino_loss", None), msssim_loss=msssim_loss,
+                                       extra_losses=_cfg(config, "extra_losses", None)).to(device)              # :629
     ema_decay = _cfg(config, "ema_decay", None)
     ema = hdiff_optim.EMA(model.parameters(), decay=ema_decay) if ema_decay is not None else None
 

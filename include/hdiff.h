@@ -662,6 +662,47 @@ int hdiff_uiqm(const float* a, int N, int H, int W, double* out, void* scratch, 
  * synchronisation, no float atomics: legal under stream capture, bitwise repeatable, independent of N and of the place in the batch. */
 int hdiff_uciqe_workspace(int N, int H, int W, int64_t* bytes);
 int hdiff_uciqe(const float* a, int N, int H, int W, double scale, double* out, void* scratch, hdiff_stream_t stream);
+/* What a VGG feature trunk, the losses on its taps and the LPIPS score need beside the conv kernels (csrc/perceptual.hip;
+ * hdiff_amd/perceptual.py is the caller, tests/_perceptual_def.py the definitions).  fp32 tensors, dense; every written operation
+ * rounds once (no contraction).  n and planes * H * W in [1, 2^40].
+ *   hdiff_relu_fwd           y = x > 0 ? x : 0, and a NaN stays a NaN (as torch.relu); y may alias x
+ *   hdiff_relu_bwd           dx = y > 0 ? dy : 0: reads the forward OUTPUT, so the forward can run in place; dx aliases neither input
+ *   hdiff_maxpool2_fwd       2x2 window, stride 2, floor mode over [planes][H][W] -> [planes][H / 2][W / 2]; H, W >= 2; a last odd row /
+ *                            column is dropped; the maximum is the first element in row-major order that no later one exceeds (a NaN counts as
+ *                            maximal: a window that holds one gives NaN)
+ *   hdiff_maxpool2_bwd       a gather from the forward INPUT x: dx = dy of the window where the element is that first maximal one, else 0
+ *                            (0 for the dropped row / column); no index tensor exists
+ *   hdiff_l1_mean_workspace  bytes of `scratch` for hdiff_l1_mean_fwd at n
+ *   hdiff_l1_mean_fwd        out[0] = (float)(sum_i double(fabsf(a[i] - b[i])) / n): each term rounded to fp32, summed in double in a
+ *                            fixed order (per-workgroup partials, then one workgroup), divided once.  b == NULL: mean |a|.  Two launches
+ *   hdiff_l1_mean_bwd        da = a > b ? c : a < b ? -c : 0 with c = g[0] / (float)n, g a device scalar (b == NULL: compared with 0);
+ *                            b receives no gradient
+ *   hdiff_charbonnier_fwd    y = sqrtf(d * d + 1) - 1, d = a - b
+ *   hdiff_charbonnier_bwd    da = (dy / divisor) * d / sqrtf(d * d + 1); dy_is_scalar = 1 reads dy[0] for every element (a reduced
+ *                            loss: divisor = n for the mean, 1 for the sum); divisor >= 1, and 1 leaves an elementwise dy as it is
+ *   hdiff_lpips_layer_workspace   bytes of `scratch` for hdiff_lpips_layer at (N, C, H, W)
+ *   hdiff_lpips_layer        f0, f1: [N][C][H][W], w: [C].  out[n] += mean over pixels of sum_c w[c] (f0[c] / (|f0| + 1e-10) -
+ *                            f1[c] / (|f1| + 1e-10))^2, |f| the L2 norm over the channels at the pixel; norms, sums and the mean in double,
+ *                            fixed order.  out is float64 [N] and is ADDED to: the caller zeroes it, five calls accumulate in call order.
+ *                            A non-finite feature makes out[n] of ITS image NaN.  N in [1, 65535], C in [1, 65536], H * W <= 2^30.  Two launches
+ *   hdiff_scale_input        y = ((x * mul + add) - shift[c]) / scale[c] over [N][C][H][W] (LPIPS: mul 2, add -1, then its shift / scale)
+ * No allocation, no synchronisation, no float atomics: legal under stream capture, bitwise repeatable; a reduction's grid depends on
+ * n (per image: on H * W) alone.  Additions to ABI 6. */
+int hdiff_relu_fwd(const float* x, float* y, int64_t n, hdiff_stream_t stream);
+int hdiff_relu_bwd(const float* y, const float* dy, float* dx, int64_t n, hdiff_stream_t stream);
+int hdiff_maxpool2_fwd(const float* x, float* y, int64_t planes, int H, int W, hdiff_stream_t stream);
+int hdiff_maxpool2_bwd(const float* x, const float* dy, float* dx, int64_t planes, int H, int W, hdiff_stream_t stream);
+int hdiff_l1_mean_workspace(int64_t n, int64_t* bytes);
+int hdiff_l1_mean_fwd(const float* a, const float* b, int64_t n, float* out, void* scratch, hdiff_stream_t stream);
+int hdiff_l1_mean_bwd(const float* a, const float* b, const float* g, int64_t n, float* da, hdiff_stream_t stream);
+int hdiff_charbonnier_fwd(const float* a, const float* b, float* y, int64_t n, hdiff_stream_t stream);
+int hdiff_charbonnier_bwd(const float* a, const float* b, const float* dy, int dy_is_scalar, float divisor, float* da, int64_t n,
+                          hdiff_stream_t stream);
+int hdiff_lpips_layer_workspace(int N, int C, int H, int W, int64_t* bytes);
+int hdiff_lpips_layer(const float* f0, const float* f1, const float* w, int N, int C, int H, int W, double* out, void* scratch,
+                      hdiff_stream_t stream);
+int hdiff_scale_input(const float* x, const float* shift, const float* scale, float mul, float add, float* y, int N, int C, int H,
+                      int W, hdiff_stream_t stream);
 /* final clip (:98) */
 int hdiff_clip(const float* x, float* y, float lo, float hi, int64_t n, hdiff_stream_t stream);
 /* out = a*x + b*y (y may be NULL): bias merges and other weight-preparation arithmetic */
