@@ -18,6 +18,12 @@ one the trunk is randomly initialised and says so.  Deliberate deviations: the t
 target is a constant, as for ``MSSSIMLoss``); the ``*_bn``, ``squeeze`` and ``alex`` trunks are not provided.  The Charbonnier formula
 ``sqrt(d^2 + 1) - 1`` was written from memory of kornia's ``charbonnier_loss``: agreement with kornia itself is unpinned.  Pass either
 to the trainer through ``extra_losses=[(name, weight, loss), ...]``.
+
+``PerceptualLoss_dino`` (reference ``:244-266``) is the term the reference trains with: smooth-L1 over every hooked module output of a
+frozen DINOv2 ViT, on ``hdiff_amd.dino`` (``csrc/dino.hip`` plus the package's dense-layer and attention kernels).  As for the VGG loss
+no weights ship: ``weights=`` takes the hub checkpoint's state dict.  The tap list, the position-embedding rule and the
+initialisation were written from memory of dinov2: agreement with the hub model is unpinned.  The trainer builds it itself with
+``GaussianDiffusionTrainer(..., dino_loss="native", dino_weights=...)``.
 """
 from __future__ import annotations
 
@@ -26,7 +32,7 @@ import warnings
 import torch
 import torch.nn as nn
 
-__all__ = ["MSSSIMLoss", "PerceptualLoss_vgg", "CharbonnierLoss"]
+__all__ = ["MSSSIMLoss", "PerceptualLoss_vgg", "PerceptualLoss_dino", "CharbonnierLoss"]
 
 _UNSUPPORTED = ("Unsupported perceptual model type. Choose from ['vgg11', 'vgg11_bn', 'vgg13', 'vgg13_bn', 'vgg16', 'vgg16_bn', "
                 "'vgg19', 'vgg19_bn', 'squeeze', 'alex']")
@@ -125,6 +131,49 @@ class PerceptualLoss_vgg(nn.Module):
         if loss is None:
             raise RuntimeError(f"PerceptualLoss_vgg: none of the layer indices {self.layer_indices[self._model]} is a layer of "
                                f"{self._model}")
+        return loss
+
+
+class PerceptualLoss_dino(nn.Module):
+    """forward(input, target) -> 0-dim fp32 tensor: the sum over the hooked modules of
+    ``smooth_l1_loss(feature(input), feature(target), 'mean')`` (reference ``:244-266``; ``layers=None`` hooks every module, which is
+    what the trainer constructs).  ``input`` is differentiated; ``target``'s features are taken without a graph.  The images go to the
+    trunk as they are: no normalisation and no rescaling (the reference hands it ``y_0_pred / 255`` and a ``[-1, 1]`` target), 2
+    pixels come off every edge, and ``H - 4`` / ``W - 4`` must be multiples of 14.
+
+    ``weights``: the hub checkpoint's state dict of ``model`` (or the path of a file ``torch.load`` reads one from).  Without it the
+    trunk keeps its random initialisation and one ``RuntimeWarning`` says so.  ``.perceptual`` is the ``hdiff_amd.dino.DinoV2Features``,
+    ``.taps`` the ``(module names, tensor, multiplicity)`` list in use, ``.last_per_image`` the ``(B,)`` shares of the last call.  The
+    attention probabilities (``attn.attn_drop``) are not hooked (``hdiff_amd.dino`` says why).  ``normalize_inputs=True`` is not
+    provided; ``version='dino'``, ``dinov2_vitg14`` and the ``_reg`` models raise ``ValueError``."""
+
+    def __init__(self, model="dinov2_vits14", version="dinov2", layers=None, normalize_inputs=False, *, weights=None, trunk=None):
+        super().__init__()
+        from ..dino import DinoV2Features, check_model_name, select_taps
+        if normalize_inputs:
+            raise NotImplementedError("PerceptualLoss_dino: normalize_inputs=True is not provided (the trainer never sets it; the "
+                                      "images go to the trunk as they are)")
+        if trunk is None:
+            check_model_name(model, version)
+            trunk = DinoV2Features(model)
+        elif not isinstance(trunk, DinoV2Features):
+            raise TypeError("PerceptualLoss_dino: trunk= must be a hdiff_amd.dino.DinoV2Features")
+        self.perceptual = trunk
+        self._model, self.version, self.layers = model, version, layers
+        self.taps = select_taps(trunk.depth, layers)
+        self.last_per_image = None
+        if weights is not None:
+            if not isinstance(weights, dict):
+                weights = torch.load(weights, map_location="cpu")
+            self.perceptual.load_dinov2(weights)
+
+    @property
+    def name(self):
+        return self.__class__.__name__ + '_' + str(self._model)
+
+    def forward(self, input, target):
+        from ..dino import dino_perceptual
+        loss, self.last_per_image = dino_perceptual(self.perceptual, input, target, self.taps, return_per_image=True)
         return loss
 
 

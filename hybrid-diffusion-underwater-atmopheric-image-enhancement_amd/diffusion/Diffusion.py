@@ -24,9 +24,10 @@ step (the same file), untiled and over windows.  Without ``solver`` nothing chan
 Trainer underneath: q_sample and the 3 + 3 channel concat are HIP launches, the DynamicUNet runs its autograd path
 (``autograd.dyn_unet_forward_with_grad``) and the loss tail -- the squared error, ``y_0_pred`` and the angular-colour term,
 and their joint backward -- is one fused kernel pair (``csrc/train_b_ops.hip``).  The reference's two further terms are passed in as
-callables (``dino_loss=``, ``msssim_loss=``); a term without one is returned as zero and left out of ``loss``.  The pretrained
-DINOv2 perceptual loss is not part of this package.  The MS-SSIM term is: ``Loss.loss.MSSSIMLoss()`` (hand-written kernels,
-``csrc/msssim.hip``) is what to pass as ``msssim_loss=``; nothing here imports kornia.
+callables (``dino_loss=``, ``msssim_loss=``); a term without one is returned as zero and left out of ``loss``.  Both have a native
+form: ``dino_loss="native"`` builds ``Loss.loss.PerceptualLoss_dino`` (a frozen DINOv2 ViT on ``csrc/dino.hip`` and the package's
+dense-layer and attention kernels; ``dino_weights=`` is the hub checkpoint's state dict, nothing is fetched), and
+``Loss.loss.MSSSIMLoss()`` (``csrc/msssim.hip``) is what to pass as ``msssim_loss=``; nothing here imports torch.hub or kornia.
 """
 from __future__ import annotations
 
@@ -91,7 +92,10 @@ class GaussianDiffusionTrainer(nn.Module):
     ``perceptual_vgg`` / ``perceptual_dino`` are the reference's model names; they are recorded but never loaded (no
     ``torch.hub``, no kornia).  ``dino_loss`` / ``msssim_loss`` are callables ``(y_0_pred, gt) -> scalar tensor`` for those two
     terms; their gradient reaches the model through ``y_0_pred``.  ``msssim_loss=Loss.loss.MSSSIMLoss()`` is the package's own
-    MS-SSIM + L1 loss on the HIP path; any other callable runs under torch autograd."""
+    MS-SSIM + L1 loss on the HIP path; any other callable runs under torch autograd.  ``dino_loss="native"`` builds
+    ``Loss.loss.PerceptualLoss_dino(perceptual_dino, weights=dino_weights)``, the package's own DINOv2 term (``dino_weights``: the hub
+    checkpoint's state dict or its path; without it the trunk is random and warns).  The trunk is frozen and belongs to the trainer,
+    not to ``model``: it is in no checkpoint, no EMA and no optimizer."""
 
     DINO_WEIGHT, MSSSIM_WEIGHT, COL_WEIGHT = 0.5, 0.0045, 1.0          # reference :165
 
@@ -101,6 +105,7 @@ class GaussianDiffusionTrainer(nn.Module):
         # extra_losses arrives through **more: the NAMED keyword-only arguments stay the two callables of the reference's own terms
         # (tests/test_train_b_cpu.py holds the signature to that)
         extra_losses = more.pop("extra_losses", None)
+        dino_weights = more.pop("dino_weights", None)
         if more:
             raise TypeError(f"GaussianDiffusionTrainer.__init__() got an unexpected keyword argument '{next(iter(more))}'")
         self.extra_losses = _checked_extra_losses(extra_losses)
@@ -117,6 +122,13 @@ class GaussianDiffusionTrainer(nn.Module):
         self.num = 0
         self.stage = 0
         self.perceptual_vgg, self.perceptual_dino = perceptual_vgg, perceptual_dino
+        if isinstance(dino_loss, str):
+            if dino_loss != "native":
+                raise ValueError(f"GaussianDiffusionTrainer: dino_loss is a callable, None or 'native', got {dino_loss!r}")
+            from ..Loss.loss import PerceptualLoss_dino
+            dino_loss = PerceptualLoss_dino(perceptual_dino, weights=dino_weights)
+        elif dino_weights is not None:
+            raise ValueError("GaussianDiffusionTrainer: dino_weights goes with dino_loss='native'")
         self.loss_perceptual_dino = dino_loss
         self.ms_ssim_loss = msssim_loss
         self._warned_missing = False

@@ -23,8 +23,10 @@ Deliberate deviations from the reference:
   * wandb is not wired: ``wandb=True`` warns once.
   * data-parallel training is out of scope: ``WORLD_SIZE > 1`` or ``DDP=True`` raises (the per-batch gating of the middle blocks does
     not fit ``parallel.FlatGradients`` as it stands); of ``device_list`` the first entry is used.
-  * ``msssim_loss`` defaults to the package's ``Loss.loss.MSSSIMLoss()``; ``dino_loss`` is an optional callable (the DINOv2 weights are
-    not part of the package) and the trainer's warning stands when it is absent.
+  * ``msssim_loss`` defaults to the package's ``Loss.loss.MSSSIMLoss()``; ``dino_loss`` is optional -- a callable, or ``"native"`` for
+    the package's own ``Loss.loss.PerceptualLoss_dino`` with ``dino_weights`` (the hub checkpoint's state dict or its path; no weights
+    ship and none are fetched) -- and the trainer's warning stands when it is absent.  The trunk is frozen and belongs to the trainer:
+    ``TERMS``, the records, the checkpoints, the EMA and the optimizer are the same with and without it.
 
 Additions, all optional (with none of them set the run is the loop above): ``dataset_root`` (one root for both sets, or a dict by
 set name), ``transforms`` (the sets' ``transforms=``), ``num_workers`` (4), ``seed`` (``torch.manual_seed`` before the model is
@@ -260,7 +262,8 @@ def train(config) -> Dict[str, object]:
         msssim_loss = MSSSIMLoss()
     trainer = GaussianDiffusionTrainer(model, _cfg(config, "beta_1"), _cfg(config, "beta_T"), _cfg(config, "T"),
                                        dino_loss=_cfg(config, "dino_loss", None), msssim_loss=msssim_loss,
-                                       extra_losses=_cfg(config, "extra_losses", None)).to(device)              # :629
+                                       extra_losses=_cfg(config, "extra_losses", None),
+                                       dino_weights=_cfg(config, "dino_weights", None)).to(device)              # :629
     ema_decay = _cfg(config, "ema_decay", None)
     ema = hdiff_optim.EMA(model.parameters(), decay=ema_decay) if ema_decay is not None else None
 

@@ -703,6 +703,49 @@ int hdiff_lpips_layer(const float* f0, const float* f1, const float* w, int N, i
                       hdiff_stream_t stream);
 int hdiff_scale_input(const float* x, const float* shift, const float* scale, float mul, float add, float* y, int N, int C, int H,
                       int W, hdiff_stream_t stream);
+/* ------------------------------------------------------------------------------------------------------------------
+ * The pieces of a frozen DINOv2 ViT trunk around the dense layers (hdiff_conv2d_fwd, one tap) and the attention core
+ * (hdiff_mha_flash_*), and the smooth-L1 sums on its taps (csrc/dino.hip; tests/_dino_def.py is the definition; hdiff_amd/dino.py is
+ * the caller).  Activations are fp32 [B][C][L], class token at position 0.  No float atomics, fixed summation orders, no allocation,
+ * no synchronisation: legal under stream capture; an image's numbers do not depend on the batch.  Additions to ABI 6.
+ *   hdiff_dino_unfold      x [B][3][H][W] -> cols [B][588][h*w], h = (H-4)/14, w = (W-4)/14: the 14x14 patches of the window that
+ *                          starts 2 pixels in from each edge, rows in Conv2d(3, C, 14, 14).weight order (c, ky, kx).  H - 4 and W - 4
+ *                          must be positive multiples of 14.
+ *   hdiff_dino_fold        its adjoint as a gather: dx [B][3][H][W] from dcols, zeros on the 2-pixel border.
+ *   hdiff_dino_tokens_fwd  tok[b][c][0] = cls[c] + pos[c][0]; tok[b][c][l] = patch[b][c][l-1] + pos[c][l]; pos is [C][L].
+ *   hdiff_dino_tokens_bwd  dpatch[b][c][l] = dtok[b][c][l+1].
+ *   hdiff_layernorm_fwd    y = (x - mean) * rstd * gamma[c] + beta[c] over C per token; mean / rstd [B][L] in double (both NULL: not
+ *                          kept).  Two passes in double: exact at mean = 1e3 x spread; a constant row gives beta exactly.
+ *   hdiff_layernorm_bwd    dx = add + rstd * (g - mean_c(g) - xhat * mean_c(g xhat)), g = dy * gamma; add may be NULL or dx itself.
+ *   hdiff_gelu_fwd / _bwd  x * Phi(x) and dy * (Phi(x) + x phi(x)), evaluated in double (erfc), rounded once; dx may be dy.
+ *   hdiff_layerscale_fwd   s = gamma[c] * x (s may be NULL), y = res + s.   hdiff_layerscale_bwd: dx = gamma[c] * ds (dx may be ds).
+ *   hdiff_smooth_l1_tap_*  a tap is B images of n_img elements, element j of image b at [b * img_stride + j * stride].  _fwd writes
+ *                          slot[b] = weight / (B n_img) * sum_j smooth_l1(a - t) (beta = 1; double, fixed order; scratch of
+ *                          _workspace bytes); _total adds the [ntaps][B] slots per image in slot order, then the images in order, and
+ *                          rounds once: out[0], and per_image[B] when not NULL; _bwd writes da_out = da_in + ((g[0] * weight) /
+ *                          (float)(B n_img)) * clamp(a - t, -1, 1) in fp32 in that order (da_in NULL: 0; da_in may be da_out).
+ *                          At most 256 images per call.
+ * ------------------------------------------------------------------------------------------------------------------ */
+int hdiff_dino_unfold(const float* x, float* cols, int B, int H, int W, hdiff_stream_t stream);
+int hdiff_dino_fold(const float* dcols, float* dx, int B, int H, int W, hdiff_stream_t stream);
+int hdiff_dino_tokens_fwd(const float* patch, const float* cls, const float* pos, float* tok, int B, int C, int L,
+                          hdiff_stream_t stream);
+int hdiff_dino_tokens_bwd(const float* dtok, float* dpatch, int B, int C, int L, hdiff_stream_t stream);
+int hdiff_layernorm_fwd(const float* x, const float* gamma, const float* beta, float eps, float* y, double* mean, double* rstd, int B,
+                        int C, int L, hdiff_stream_t stream);
+int hdiff_layernorm_bwd(const float* x, const float* gamma, const double* mean, const double* rstd, const float* dy, const float* add,
+                        float* dx, int B, int C, int L, hdiff_stream_t stream);
+int hdiff_gelu_fwd(const float* x, float* y, int64_t n, hdiff_stream_t stream);
+int hdiff_gelu_bwd(const float* x, const float* dy, float* dx, int64_t n, hdiff_stream_t stream);
+int hdiff_layerscale_fwd(const float* x, const float* gamma, const float* res, float* s, float* y, int B, int C, int L,
+                         hdiff_stream_t stream);
+int hdiff_layerscale_bwd(const float* ds, const float* gamma, float* dx, int B, int C, int L, hdiff_stream_t stream);
+int hdiff_smooth_l1_tap_workspace(int B, int64_t n_img, int64_t* bytes);
+int hdiff_smooth_l1_tap_fwd(const float* a, const float* t, int B, int64_t n_img, int64_t stride, int64_t img_stride, double weight,
+                            double* slot, void* scratch, hdiff_stream_t stream);
+int hdiff_smooth_l1_tap_total(const double* slots, int ntaps, int B, float* out, float* per_image, hdiff_stream_t stream);
+int hdiff_smooth_l1_tap_bwd(const float* a, const float* t, const float* g, int B, int64_t n_img, int64_t stride, int64_t img_stride,
+                            float weight, const float* da_in, float* da_out, hdiff_stream_t stream);
 /* final clip (:98) */
 int hdiff_clip(const float* x, float* y, float lo, float hi, int64_t n, hdiff_stream_t stream);
 /* out = a*x + b*y (y may be NULL): bias merges and other weight-preparation arithmetic */
