@@ -59,14 +59,25 @@ def ref64(qkv, d_o, b, h, d, Cc, chunk=4096):
     return {"dQ": dQ.t(), "dK": dK.t(), "dV": dV.t()}
 
 
-def error_stats(lib, qkv, d_o, heads, pairs=None):
-    """{name: {"pair": [(b, h, rms_h2, rms_f32, worst_h2, worst_f32, mag)], "rms": (h2, f32) over all pairs, "worst": (h2, f32), "mag"}}"""
+def error_stats(lib, qkv, d_o, heads, pairs=None, yard=False):
+    """{name: {"pair": [(b, h, rms_h2, rms_f32, worst_h2, worst_f32, mag)], "rms": (h2, f32) over all pairs, "worst": (h2, f32), "mag"}}
+    yard: also "yard": (rms, worst) of the fp32 CPU definition (_attn_f32_cases.definition in torch float32) over the same pairs --
+    what the fp32 kernel, the denominator of every ratio here, is itself held to (tests/test_gpu_attention_f32.py)"""
     B, C3, L = qkv.shape; Cc = C3 // 3; d = Cc // heads
     g32, gh2 = run_bwd(lib, qkv, d_o, heads, 0), run_bwd(lib, qkv, d_o, heads, 1)
     assert torch.isfinite(gh2).all() and not torch.equal(gh2, g32), "the split-operand backward did not run"
-    out = {n: {"pair": [], "sq": [0.0, 0.0], "worst": [0.0, 0.0], "mag": 0.0, "n": 0} for n in ("dQ", "dK", "dV")}
+    out = {n: {"pair": [], "sq": [0.0, 0.0], "worst": [0.0, 0.0], "mag": 0.0, "n": 0, "ysq": 0.0, "yworst": 0.0} for n in ("dQ", "dK", "dV")}
+    if yard:
+        import _attn_f32_cases as F32
+        qkv_cpu, d_o_cpu = qkv.cpu(), d_o.cpu()
     for b, h in (pairs if pairs is not None else [(b, h) for b in range(B) for h in range(heads)]):
         ref = ref64(qkv, d_o, b, h, d, Cc)
+        if yard:
+            rows = [slice(i * Cc + h * d, i * Cc + (h + 1) * d) for i in range(3)]
+            y32 = F32.definition(qkv_cpu[b, rows[0]], qkv_cpu[b, rows[1]], qkv_cpu[b, rows[2]], d_o_cpu[b, rows[0]], torch.float32)
+            for n in out:
+                ey = y32[n].double() - ref[n].cpu()
+                out[n]["ysq"] += ey.pow(2).sum().item(); out[n]["yworst"] = max(out[n]["yworst"], ey.abs().max().item())
         for i, n in enumerate(("dQ", "dK", "dV")):
             rows = slice(i * Cc + h * d, i * Cc + (h + 1) * d)
             e2, e0 = gh2[b, rows].double() - ref[n], g32[b, rows].double() - ref[n]
@@ -78,4 +89,6 @@ def error_stats(lib, qkv, d_o, heads, pairs=None):
             st["mag"] = max(st["mag"], ref[n].abs().max().item())
     for st in out.values():
         st["rms"] = tuple(math.sqrt(v / st["n"]) for v in st["sq"])
+        if yard:
+            st["yard"] = (math.sqrt(st["ysq"] / st["n"]), st["yworst"])
     return out
