@@ -6,7 +6,13 @@ sampler leaves its output (``hdiff_amd.quality``); nothing is copied to the host
 Deliberate deviations from the reference:
   * the target is scaled by 1 / 255.  ``rotinas.py:919`` clips the 0-255 target to [0, 1] and so compares against a binary image; that
     is not copied.
-  * FID is not computed: it needs a pretrained Inception.  LPIPS (``rotinas.py`` imports ``lpips``) is computed when the caller brings
+  * the reference's FID (``rotinas.py:879, 914, 962-972``: an Inception distance between the 16 images of a batch, averaged over the
+    batches) is not copied: there is no Inception trunk here, and a covariance of 16 samples in 2048 dimensions is singular.  In its
+    place ``distribution=`` (a ``quality.DistributionMeter``, or a feature callable such as ``quality.DinoFeatures``; config keys
+    ``distribution``, or ``fd_model`` with ``fd_weights``) scores the WHOLE set of outputs against the whole set of targets: the
+    Frechet distance and KID over the features, on DINOv2 class tokens by default.  ``res.txt`` then ends with ``fd_orgin_avg:`` and
+    ``kid_orgin_avg:`` -- deliberately not ``fid_orgin_avg:``, it is a different quantity.
+  * LPIPS (``rotinas.py`` imports ``lpips``) is computed when the caller brings
     the weights: ``lpips=`` a ``quality.LPIPS`` (config key ``lpips``, or ``lpips_weights``, the path of a file holding
     ``{"vgg": <torchvision vgg16 state dict>, "lin": <the five lin weights>}``); ``res.txt`` then ends with ``lpips_orgin_avg:``.  Without
     it ``res.txt`` holds the reference's keys for what was measured and no others.
@@ -29,7 +35,7 @@ import torch
 
 from .. import quality
 
-__all__ = ["evaluate", "test", "inference", "RES_KEYS", "RES_KEYS_UCIQE", "RES_KEY_LPIPS"]
+__all__ = ["evaluate", "test", "inference", "RES_KEYS", "RES_KEYS_UCIQE", "RES_KEY_LPIPS", "RES_KEYS_DISTRIBUTION"]
 
 # res.txt: the reference's key for each measured score, in the reference's order (rotinas.py:967-982)
 RES_KEYS = (("psnr_orgin_avg:", "psnr"), ("ssim_orgin_avg:", "ssim"), ("uiqm_orgin_avg:", "uiqm"), ("uism_orgin_avg:", "uism"),
@@ -38,6 +44,8 @@ RES_KEYS = (("psnr_orgin_avg:", "psnr"), ("ssim_orgin_avg:", "ssim"), ("uiqm_org
 RES_KEYS_UCIQE = RES_KEYS[:3] + (("uciqe_orgin_avg:", "uciqe"),) + RES_KEYS[3:]
 # with LPIPS: one last line, behind whichever list is in use
 RES_KEY_LPIPS = ("lpips_orgin_avg:", "lpips")
+# with the set-level scores: two last lines, behind LPIPS's where both are on
+RES_KEYS_DISTRIBUTION = (("fd_orgin_avg:", "fd"), ("kid_orgin_avg:", "kid"))
 
 
 def _device_of(sampler) -> Optional[torch.device]:
@@ -65,7 +73,7 @@ def write_res(path: str, result: Dict[str, object], keys=RES_KEYS) -> None:
 def evaluate(sampler, batches: Iterable, *, ddim_step: int, tile: Optional[int] = None, tile_overlap: Optional[int] = None,
              tile_batch: Optional[int] = None, save_dir: Optional[str] = None, collect: Optional[List[torch.Tensor]] = None,
              meter=None, solver: Optional[str] = None, spacing: Optional[str] = None, uciqe: bool = False,
-             uciqe_scale: float = 1.0, lpips=None) -> Dict[str, object]:
+             uciqe_scale: float = 1.0, lpips=None, distribution=None) -> Dict[str, object]:
     """Samples and scores a set.  ``batches`` yields ``(input, target)`` or ``(input, target, names)``: CHW images in [0, 255] as
     ``Underwater_Dataset`` / ``Atmospheric_Dataset`` produce them, batched.  Per batch: ``out = sampler(input, ddim=True,
     unconditional_guidance_scale=1, ddim_step=ddim_step, tile=...)`` (rotinas.py:907), then ``(out + 1) / 2`` is scored against
@@ -76,7 +84,13 @@ def evaluate(sampler, batches: Iterable, *, ddim_step: int, tile: Optional[int] 
     ``clip((out + 1) / 2, 0, 1) * uciqe_scale`` (``quality.QualityMeter(uciqe=True)``; a ``meter`` passed in must report "uciqe"
     itself) and ``res.txt`` gets ``uciqe_orgin_avg:`` after UIQM's line.  ``lpips``: a ``quality.LPIPS``; the default meter also scores the
     LPIPS distance of ``(out + 1) / 2`` from ``target / 255`` (a ``meter`` passed in must report "lpips" itself), the result gains
-    ``"lpips"`` and ``res.txt`` a last line ``lpips_orgin_avg:``.  Returns ``QualityMeter.compute()``'s dict."""
+    ``"lpips"`` and ``res.txt`` a last line ``lpips_orgin_avg:``.  ``distribution``: a ``quality.DistributionMeter`` to go on filling, or
+    a feature callable (``quality.DinoFeatures``) from which one is made; it is updated beside the quality meter with the same
+    ``(out + 1) / 2`` and ``target / 255``, the result gains ``"fd"`` and ``"kid"`` (of ALL the images the meter holds) and ``res.txt``
+    two last lines, ``fd_orgin_avg:`` and ``kid_orgin_avg:``.  Without it nothing of that is constructed, launched or written.
+    Returns ``QualityMeter.compute()``'s dict."""
+    if distribution is not None and not isinstance(distribution, quality.DistributionMeter):
+        distribution = quality.DistributionMeter(distribution)
     if meter is None:
         if lpips is not None:
             meter = quality.QualityMeter(uciqe=bool(uciqe), uciqe_scale=uciqe_scale, lpips=lpips)
@@ -97,15 +111,24 @@ def evaluate(sampler, batches: Iterable, *, ddim_step: int, tile: Optional[int] 
             out = sampler(inp, ddim=True, unconditional_guidance_scale=1, ddim_step=ddim_step, **tile_kw)
             pred01 = (out + 1) / 2                                                        # :912
             meter.update(pred01, target / 255)
+            if distribution is not None:
+                distribution.update(pred01, target / 255)
             if collect is not None:
                 collect.append(out)
             if save_dir is not None:
                 _save_batch(pred01, names, save_dir)
             done += int(inp.shape[0])
     result = meter.compute()
+    if distribution is not None:
+        scores = distribution.compute()
+        result["fd"], result["kid"] = scores["fd"], scores["kid"]
     if save_dir is not None:
         keys = RES_KEYS_UCIQE if uciqe else RES_KEYS
-        write_res(os.path.join(save_dir, "res.txt"), result, keys + (RES_KEY_LPIPS,) if lpips is not None else keys)
+        if lpips is not None:
+            keys = keys + (RES_KEY_LPIPS,)
+        if distribution is not None:
+            keys = keys + RES_KEYS_DISTRIBUTION
+        write_res(os.path.join(save_dir, "res.txt"), result, keys)
     return result
 
 
@@ -167,8 +190,17 @@ def _run_sets(config, task: str) -> Dict[str, Dict[str, object]]:
         lpips = quality.LPIPS(held["vgg"], held["lin"])
     if lpips is not None:
         extra["lpips"] = lpips.to(device)
+    features = _cfg(config, "distribution", None)
+    if features is None and _cfg(config, "fd_model", None) is not None:
+        from ..dino import DinoV2Features
+        trunk = DinoV2Features(_cfg(config, "fd_model"))
+        if _cfg(config, "fd_weights", None) is not None:
+            trunk.load_dinov2(torch.load(_cfg(config, "fd_weights"), map_location="cpu"))
+        features = quality.DinoFeatures(trunk).to(device)
     results = {}
     for name, data in sets:
+        if features is not None:      # one meter per set; a DistributionMeter from the configuration goes on filling across both
+            extra["distribution"] = features if isinstance(features, quality.DistributionMeter) else quality.DistributionMeter(features)
         results[name] = evaluate(sampler, _batched(data, int(_cfg(config, "batch_size"))), ddim_step=_cfg(config, "ddim_step"),
                                  tile=_cfg(config, "tile", None), tile_overlap=_cfg(config, "tile_overlap", None),
                                  tile_batch=_cfg(config, "tile_batch", None), save_dir=os.path.join(base, name),
@@ -184,7 +216,10 @@ def test(config, epoch=None) -> Dict[str, Dict[str, object]]:
     ``tile_overlap``, ``tile_batch`` (overlapping-window sampling), ``solver``, ``spacing`` (the sampler's; absent: the reference's DDIM), ``dataset_root`` (one root for both sets, or a dict by set
     name), ``transforms`` (the sets' ``transforms=``; default: their 256 x 256 resize), ``device_list`` (the first entry is used; default ``cuda:0``),
     ``uciqe``, ``uciqe_scale`` (``evaluate``'s; absent: no UCIQE, ``res.txt`` as before), ``lpips`` (a ``quality.LPIPS``) or
-    ``lpips_weights`` (the path of a file holding ``{"vgg": ..., "lin": ...}``; absent: no LPIPS, ``res.txt`` as before).
+    ``lpips_weights`` (the path of a file holding ``{"vgg": ..., "lin": ...}``; absent: no LPIPS, ``res.txt`` as before),
+    ``distribution`` (a feature callable such as ``quality.DinoFeatures``, or a ``quality.DistributionMeter``) or ``fd_model``
+    (``"dinov2_vits14"`` / ``vitb14`` / ``vitl14``) with ``fd_weights`` (the path of the hub state dict, loaded with ``load_dinov2``;
+    the images must fit the trunk: ``H - 4`` and ``W - 4`` multiples of 14; absent: no set-level scores, ``res.txt`` as before).
     ``epoch`` is accepted and unused, as in the reference.  Returns ``{set name: evaluate()'s dict}``."""
     return _run_sets(config, "test")
 

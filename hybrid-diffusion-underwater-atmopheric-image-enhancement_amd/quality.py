@@ -22,6 +22,16 @@ the pixels of the weighted squared difference of the channel-normalised features
 from the caller -- a torchvision ``vgg16`` state dict and the five ``lin`` layers of the ``lpips`` package; none ship, none are fetched.
 Scaling constants, taps and formula were written from memory of that package: agreement with it is unpinned.  The other parts of ``nmetrics`` (its own UIQM variant) and the 8-bit OpenCV
 ``uw_metrics.uciqe``, which the reference never calls, stay on the host.  There is no CPU fallback: CPU tensors are refused.
+
+The scores above are per image.  ``DistributionMeter`` scores a SET of outputs against a set of targets (``csrc/distribution.hip``): the
+Frechet distance between the Gaussians fitted to the two sets' features, and KID, the unbiased estimate of the squared maximum mean
+discrepancy under the kernel ``(x.y / d + 1)^3`` (Binkowski et al. 2018, "Demystifying MMD GANs").  With ``DinoFeatures`` the features
+are the normalised class token of a DINOv2 trunk (``hdiff_amd.dino``), which makes the first one FD-DINOv2 (Stein et al. 2023,
+"Exposing flaws of generative model evaluation metrics", who recommend it over the Inception FID).  This is NOT the reference's
+``fid_orgin_avg`` (``utils/rotinas.py:879, 914, 962-972``): that one averages, over batches, a distance between 16 images in 2048
+Inception dimensions.  The Frechet distance is strongly biased on sets smaller than the feature width -- the normal case for a test
+set of a few hundred images -- and KID is the score that stays meaningful there.  No value of either has been measured on hub weights
+or on trained models.
 """
 from __future__ import annotations
 
@@ -34,7 +44,8 @@ import torch
 from . import _capi
 from . import engine as E
 
-__all__ = ["psnr_ssim", "uiqm", "uciqe", "LPIPS", "QualityMeter"]
+__all__ = ["psnr_ssim", "uiqm", "uciqe", "LPIPS", "QualityMeter", "moments", "kid_sums", "kid", "frechet_from_moments", "DinoFeatures",
+           "DistributionMeter"]
 
 COLUMNS = ("psnr", "ssim", "uiqm", "uicm", "uism", "uiconm")      # the columns of QualityMeter's per-image rows
 UCIQE_COLUMNS = ("uciqe", "uciqe_sc", "uciqe_conl", "uciqe_us")   # the four more of QualityMeter(uciqe=True)
@@ -306,4 +317,211 @@ class QualityMeter:
             col = per[paired, j] if k in ("psnr", "ssim", "lpips") else per[:, j]
             res[k] = float(np.sum(col) / col.size) if col.size else float("nan")
         res["per_image"] = per
+        return res
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# set-level scores: feature moments, the Frechet distance, KID (csrc/distribution.hip)
+# ----------------------------------------------------------------------------------------------------------------------
+def _feature_rows(t: torch.Tensor, name: str) -> torch.Tensor:
+    """``[n, d]`` fp32 on the device, addressed in place by its two strides where they are positive."""
+    if not torch.is_tensor(t):
+        raise TypeError(f"hdiff: '{name}' must be a tensor, got {type(t).__name__}")
+    if t.is_cuda and t.is_floating_point() and t.dtype != torch.float32:
+        t = t.float()
+    if not t.is_cuda:                               # engine.require_gpu_tensor's refusal; its contiguity rule does not apply to a view
+        raise RuntimeError(f"hdiff: '{name}' lives on {t.device}; the HIP path needs an MI355X device tensor "
+                           "(there is deliberately no CPU fallback)")
+    if t.dtype != torch.float32 or t.dim() != 2 or t.shape[0] < 1 or t.shape[1] < 1:
+        raise RuntimeError(f"hdiff: '{name}' has dtype {t.dtype} and shape {tuple(t.shape)}; features are floating-point [n, d] rows")
+    if min(t.stride()) < 1:
+        t = t.contiguous()
+    return t.detach()
+
+
+def moments(feats: torch.Tensor) -> Tuple[int, torch.Tensor, torch.Tensor]:
+    """-> (n, mean[d], cov[d, d]), float64 device tensors, of ``feats`` ``[n, d]`` (any positive strides: a class-token view is read in
+    place).  ``cov`` is the unbiased sample covariance (divided by ``n - 1``; NaN for ``n = 1``), two passes in double, symmetric bit
+    for bit.  The raw kernel call: a non-finite feature spoils what it touches and raises nothing."""
+    f = _feature_rows(feats, "feats")
+    n, d = int(f.shape[0]), int(f.shape[1])
+    mean = torch.empty(d, dtype=torch.float64, device=f.device)
+    cov = torch.empty(d, d, dtype=torch.float64, device=f.device)
+    with torch.cuda.device(f.device):
+        _capi.check(_capi.lib().hdiff_feat_moments(f.data_ptr(), n, d, f.stride(0), f.stride(1), mean.data_ptr(), cov.data_ptr(),
+                                                   _stream(f.device)), "feat_moments")
+    return n, mean, cov
+
+
+def kid_sums(feats_a: torch.Tensor, feats_b: torch.Tensor) -> torch.Tensor:
+    """-> float64 ``[3]`` on the device: the sum of ``k(a_i, a_j)`` over ``i != j``, the same over ``b``, and the sum of ``k(a_i, b_j)``
+    over all pairs, ``k(x, y) = (x.y / d + 1)^3`` in double.  Swapping the arguments swaps the first two sums, bit for bit."""
+    a, b = _feature_rows(feats_a, "feats_a"), _feature_rows(feats_b, "feats_b")
+    if a.shape[1] != b.shape[1] or a.device != b.device:
+        raise ValueError(f"kid: the two sets must share their feature width and device, got {tuple(a.shape)} on {a.device} and "
+                         f"{tuple(b.shape)} on {b.device}")
+    n, m, d = int(a.shape[0]), int(b.shape[0]), int(a.shape[1])
+    need = C.c_int64(0)
+    _capi.check(_capi.lib().hdiff_kid_workspace(n, m, C.byref(need)), "kid_workspace")
+    out = torch.empty(3, dtype=torch.float64, device=a.device)
+    with torch.cuda.device(a.device):
+        scratch = torch.empty(need.value, dtype=torch.uint8, device=a.device)
+        _capi.check(_capi.lib().hdiff_kid_sums(a.data_ptr(), n, b.data_ptr(), m, d, a.stride(0), a.stride(1), b.stride(0), b.stride(1),
+                                               out.data_ptr(), scratch.data_ptr(), _stream(a.device)), "kid_sums")
+    return out
+
+
+def _kid_from_sums(sums, n: int, m: int) -> float:
+    s = [float(v) for v in sums]
+    if n < 2 or m < 2 or not np.isfinite(s).all():
+        return float("nan")
+    return s[0] / (n * (n - 1)) + s[1] / (m * (m - 1)) - 2 * s[2] / (n * m)
+
+
+def kid(feats_a: torch.Tensor, feats_b: torch.Tensor) -> float:
+    """The unbiased estimate of the squared MMD between the two sets under ``k(x, y) = (x.y / d + 1)^3``:
+    ``sum_{i != j} k(a_i, a_j) / (n (n - 1)) + sum_{i != j} k(b_i, b_j) / (m (m - 1)) - 2 sum_{i, j} k(a_i, b_j) / (n m)`` over the WHOLE
+    sets.  There is no subset resampling: the customary mean over 100 subsets of 1000 bounds the cost on sets of tens of thousands,
+    and on sets of a few hundred images the full estimate is the one with the lower variance.  It can come out slightly negative for
+    two samples of one distribution.  NaN if ``n < 2`` or ``m < 2`` or a feature is not finite."""
+    sums = kid_sums(feats_a, feats_b).cpu().numpy()
+    return _kid_from_sums(sums, int(feats_a.shape[0]), int(feats_b.shape[0]))
+
+
+def _host64(v) -> np.ndarray:
+    if torch.is_tensor(v):
+        v = v.detach().cpu().numpy()
+    return np.asarray(v, dtype=np.float64)
+
+
+def frechet_from_moments(mean_a, cov_a, mean_b, cov_b) -> float:
+    """``|mu_a - mu_b|^2 + tr S_a + tr S_b - 2 tr (S_a^1/2 S_b S_a^1/2)^1/2`` on the host in float64 (tensors are copied once; ``d`` is at
+    most a thousand or so, once per set).  ``R = S_a^1/2`` comes from ``eigh(S_a)`` with negative eigenvalues clamped to 0, the last
+    trace is the sum of the square roots of the eigenvalues of the symmetrised ``R S_b R``, clamped to 0 likewise.  No ``sqrtm``: the
+    route stays real on rank-deficient covariances (fewer rows than dimensions), which the reference patches with a ``1e-6`` offset.
+    NaN if a moment is not finite."""
+    ma, ca, mb, cb = _host64(mean_a), _host64(cov_a), _host64(mean_b), _host64(cov_b)
+    d = ma.shape[0]
+    if ma.shape != (d,) or mb.shape != (d,) or ca.shape != (d, d) or cb.shape != (d, d):
+        raise ValueError(f"frechet_from_moments: shapes {ma.shape}, {ca.shape}, {mb.shape}, {cb.shape}; means [d] and covariances [d, d]")
+    if not (np.isfinite(ma).all() and np.isfinite(mb).all() and np.isfinite(ca).all() and np.isfinite(cb).all()):
+        return float("nan")
+    lam_a, vec = np.linalg.eigh(ca)
+    root = (vec * np.sqrt(np.maximum(lam_a, 0.0))) @ vec.T
+    inner = root @ cb @ root
+    lam = np.maximum(np.linalg.eigvalsh((inner + inner.T) / 2), 0.0)
+    diff = ma - mb
+    return float(diff @ diff + np.trace(ca) + np.trace(cb) - 2.0 * np.sqrt(lam).sum())
+
+
+class DinoFeatures:
+    """``features(images01)`` -> the class-token features ``[N, d]`` of images in [0, 1], ``[N, 3, H, W]``: the ``head`` tap of a
+    ``dino.DinoV2Features`` (the class token behind the last LayerNorm), returned as the strided view ``nf[:, :, 0]`` of the trunk's
+    ``(N, d, L)`` output.  With ``normalize`` the images first get ImageNet's mean and std (``hdiff_scale_input``, one kernel).  The
+    trunk's own size rule applies: 2 pixels come off every edge and the rest must be whole 14 x 14 patches (256 -> 252).  Runs under
+    ``no_grad``.  A trunk without loaded weights warns once (the trunk's own ``RuntimeWarning``): its scores are not FD-DINOv2."""
+
+    MEAN = (0.485, 0.456, 0.406)
+    STD = (0.229, 0.224, 0.225)
+
+    def __init__(self, trunk, *, normalize: bool = True):
+        from .dino import DinoV2Features
+        if not isinstance(trunk, DinoV2Features):
+            raise TypeError(f"DinoFeatures: trunk must be a dino.DinoV2Features, got {type(trunk).__name__}")
+        self.trunk, self.normalize = trunk, bool(normalize)
+        self.name = str(trunk.model_name)
+        self.shift = torch.tensor(self.MEAN, dtype=torch.float32)
+        self.scale = torch.tensor(self.STD, dtype=torch.float32)
+
+    def to(self, device) -> "DinoFeatures":
+        self.trunk.to(device)
+        self.shift, self.scale = self.shift.to(device), self.scale.to(device)
+        return self
+
+    def scaled(self, images01: torch.Tensor) -> torch.Tensor:
+        """``(x - mean[c]) / std[c]`` in fp32: what the trunk is fed when ``normalize`` is on."""
+        img = _image_batch(images01, "images01")
+        if self.shift.device != img.device:
+            self.shift, self.scale = self.shift.to(img.device), self.scale.to(img.device)
+        N, _, H, W = (int(v) for v in img.shape)
+        out = torch.empty_like(img)
+        with torch.cuda.device(img.device):
+            _capi.check(_capi.lib().hdiff_scale_input(img.data_ptr(), self.shift.data_ptr(), self.scale.data_ptr(), C.c_float(1.0),
+                                                      C.c_float(0.0), out.data_ptr(), N, 3, H, W, _stream(img.device)), "scale_input")
+        return out
+
+    def __call__(self, images01: torch.Tensor) -> torch.Tensor:
+        img = _image_batch(images01, "images01")
+        with torch.no_grad():
+            return self.trunk(self.scaled(img) if self.normalize else img, ["head"])[0]
+
+
+class DistributionMeter:
+    """Collects the features of two image sets on the device and scores one set against the other: ``update`` per batch (never
+    synchronises), ``compute`` once at the end.
+
+    ``features``: a callable that maps ``[N, 3, H, W]`` images in [0, 1] to ``[N, d]`` fp32 features on the device -- a
+    ``DinoFeatures``, or any other extractor (a caller who has an Inception trunk gets an FID out of the same machinery).
+    ``update(pred01, target01)`` appends the features of both batches to two growing fp32 banks (they double from ``capacity`` rows,
+    as ``QualityMeter``'s rows do); ``update(pred01)`` fills the prediction bank only and ``add_reference(images01)`` the other one, so
+    the two sets need neither pairing nor equal sizes.  ``compute()`` -> ``{"n_pred", "n_ref", "fd", "kid", "features"}``: the Frechet
+    distance between the two banks' moments (``moments``, ``frechet_from_moments``), ``kid`` over the whole banks, and the extractor's
+    name.  A non-finite feature in either bank makes BOTH scores NaN; so does an empty bank, and a bank of one row (no covariance, no
+    off-diagonal pair)."""
+
+    def __init__(self, features, capacity: int = 64):
+        if not callable(features):
+            raise TypeError(f"DistributionMeter: features must be callable, got {type(features).__name__}")
+        self.features = features
+        self.name = str(getattr(features, "name", None) or getattr(features, "__name__", type(features).__name__))
+        self._capacity = [max(1, int(capacity))] * 2
+        self._bank = [None, None]                      # [capacity, d] fp32: predictions, references
+        self._n = [0, 0]
+
+    def _append(self, which: int, images01: torch.Tensor, name: str) -> None:
+        img = _image_batch(images01, name)
+        N = int(img.shape[0])
+        f = self.features(img)
+        if not torch.is_tensor(f) or not f.is_cuda or f.dim() != 2 or int(f.shape[0]) != N or f.device != img.device:
+            raise RuntimeError(f"DistributionMeter: the feature extractor must return [N, d] device tensors; got "
+                               f"{tuple(f.shape) if torch.is_tensor(f) else type(f).__name__} for {N} images")
+        d = int(f.shape[1])
+        other = self._bank[1 - which]
+        if other is not None and (int(other.shape[1]) != d or other.device != f.device):
+            raise RuntimeError(f"DistributionMeter: features of width {d} on {f.device}; the other set holds width "
+                               f"{int(other.shape[1])} on {other.device}")
+        bank, n = self._bank[which], self._n[which]
+        if bank is not None and (int(bank.shape[1]) != d or bank.device != f.device):
+            raise RuntimeError(f"DistributionMeter: features of width {d} on {f.device}; the bank holds width {int(bank.shape[1])} on "
+                               f"{bank.device}")
+        if bank is None or n + N > self._capacity[which]:
+            while self._capacity[which] < n + N:
+                self._capacity[which] *= 2
+            grown = torch.empty(self._capacity[which], d, dtype=torch.float32, device=f.device)
+            if bank is not None:
+                grown[:n].copy_(bank[:n])
+            self._bank[which] = bank = grown
+        bank[n:n + N].copy_(f.detach())
+        self._n[which] = n + N
+
+    def update(self, pred01: torch.Tensor, target01: Optional[torch.Tensor] = None) -> None:
+        self._append(0, pred01, "pred01")
+        if target01 is not None:
+            self._append(1, target01, "target01")
+
+    def add_reference(self, images01: torch.Tensor) -> None:
+        self._append(1, images01, "images01")
+
+    def compute(self) -> Dict[str, object]:
+        n, m = self._n
+        res: Dict[str, object] = {"n_pred": int(n), "n_ref": int(m), "fd": float("nan"), "kid": float("nan"), "features": self.name}
+        if n < 1 or m < 1:
+            return res
+        a, b = self._bank[0][:n], self._bank[1][:m]
+        _, mean_a, cov_a = moments(a)
+        _, mean_b, cov_b = moments(b)
+        sums = kid_sums(a, b).cpu().numpy()
+        fd = frechet_from_moments(mean_a, cov_a, mean_b, cov_b)        # NaN moments (a non-finite feature, a bank of one row) -> NaN
+        if np.isfinite(sums).all() and np.isfinite(fd):
+            res["fd"], res["kid"] = fd, _kid_from_sums(sums, n, m)
         return res

@@ -662,6 +662,25 @@ int hdiff_uiqm(const float* a, int N, int H, int W, double* out, void* scratch, 
  * synchronisation, no float atomics: legal under stream capture, bitwise repeatable, independent of N and of the place in the batch. */
 int hdiff_uciqe_workspace(int N, int H, int W, int64_t* bytes);
 int hdiff_uciqe(const float* a, int N, int H, int W, double scale, double* out, void* scratch, hdiff_stream_t stream);
+/* Set-level statistics of feature rows (csrc/distribution.hip; tests/_distribution_def.py is the definition): what a Frechet distance
+ * and a KID over a feature extractor need.  Features are fp32, n rows of d values, value (r, i) at feats[r * row_stride + i * ch_stride]
+ * (strides in elements, both >= 1), so the class-token view of a channel-major (B, C, L) tensor is read in place.  Outputs are double.
+ *   hdiff_feat_moments       mean[i] = (sum over r = 0 .. n-1, in that order, of (double)x[r][i]) / n; cov[i][j] = (sum over r in that
+ *                            order of (x[r][i] - mean[i]) * (x[r][j] - mean[j])) / (n - 1), difference, product and sum rounded apart;
+ *                            cov is [d][d], both halves written, bit for bit symmetric; n = 1 gives a NaN cov and no error.  Two launches
+ *   hdiff_kid_workspace      bytes of `scratch` for hdiff_kid_sums at (n, m)
+ *   hdiff_kid_sums           with k(x, y) = (x.y / d + 1)^3, x.y summed over the channels 0 .. d-1 in order, the cube as (t * t) * t:
+ *                            out[0] = sum of k(a_i, a_j) over i != j, out[1] = the same over b, out[2] = sum of k(a_i, b_j) over all
+ *                            pairs; one partial per workgroup in a slot of its own, added in a fixed order.  A call with a and b
+ *                            swapped returns out[1], out[0], out[2] bit for bit.  Four launches
+ * n, m in [1, 32768], d in [1, 8192].  A non-finite feature spoils what it touches (the mean and the cov entries of its channel; all
+ * three sums a row of its set enters) and raises nothing.  No allocation, no synchronisation, no float atomics: legal under stream
+ * capture, bitwise repeatable.  Additions to ABI 6. */
+int hdiff_feat_moments(const float* feats, int n, int d, int64_t row_stride, int64_t ch_stride, double* mean, double* cov,
+                       hdiff_stream_t stream);
+int hdiff_kid_workspace(int n, int m, int64_t* bytes);
+int hdiff_kid_sums(const float* a, int n, const float* b, int m, int d, int64_t a_row_stride, int64_t a_ch_stride,
+                   int64_t b_row_stride, int64_t b_ch_stride, double* out, void* scratch, hdiff_stream_t stream);
 /* What a VGG feature trunk, the losses on its taps and the LPIPS score need beside the conv kernels (csrc/perceptual.hip;
  * hdiff_amd/perceptual.py is the caller, tests/_perceptual_def.py the definitions).  fp32 tensors, dense; every written operation
  * rounds once (no contraction).  n and planes * H * W in [1, 2^40].

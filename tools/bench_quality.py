@@ -15,7 +15,12 @@ is there to catch a hidden per-image synchronisation or host fallback.
 With ``--uciqe`` three arms alternate instead: ``QualityMeter.update`` without UCIQE, ``QualityMeter(uciqe=True).update``, and the host
 path the latter replaces (copy the batch, then ``uw_metrics.nmetrics`` per image in one Python thread).  The JSON line holds what
 UCIQE adds per update (the difference of the two device arms), its ratio to the host path and to one 29.4 ms DDIM step; the
-condition checked is that the added device time for the whole batch stays below the host time for one image."""
+condition checked is that the added device time for the whole batch stays below the host time for one image.
+
+With ``--distribution`` four arms alternate: the device part of ``DistributionMeter.compute`` (``quality.moments`` of two banks of
+``--rows`` x ``--width`` features and ``quality.kid_sums``), the host path it stands in for (copy the features, ``np.cov`` and three
+float64 Gram products), ``frechet_from_moments`` on the host, and one ``DistributionMeter.update`` of the batch (predictions and
+targets) through ``dinov2_vits14`` with random weights.  No condition is checked: the figures are reported as they come."""
 import argparse
 import json
 import os
@@ -37,6 +42,10 @@ ap.add_argument("--alternate", type=int, default=3)
 ap.add_argument("--reps", type=int, default=50)
 ap.add_argument("--warmup", type=int, default=5)
 ap.add_argument("--uciqe", action="store_true", help="time QualityMeter.update without / with UCIQE against uw_metrics.nmetrics on the host")
+ap.add_argument("--distribution", action="store_true", help="time the set-level scores: moments + KID sums against numpy on the host, "
+                "frechet_from_moments, and one DistributionMeter.update through dinov2_vits14")
+ap.add_argument("--rows", type=int, default=1024, help="--distribution: rows per feature bank")
+ap.add_argument("--width", type=int, default=384, help="--distribution: feature width")
 a = ap.parse_args()
 dev = torch.device("cuda", 0)
 torch.cuda.set_device(0)
@@ -114,6 +123,84 @@ if a.uciqe:
                       "added_ms_over_29.4_ms_ddim_step": (sum(added) / len(added)) / 29.4,
                       "host_ms_per_image_min": host_image_best, "added_device_batch_below_one_host_image": ok}))
     sys.exit(0 if ok else 1)
+
+if a.distribution:
+    import warnings
+    from hdiff_amd.dino import DinoV2Features
+    rows, width = a.rows, a.width
+    passes = 25 * a.reps                     # a pass is well under a millisecond: enough of them for a window of a few tenths of a second
+    fa = (torch.randn(rows, width, generator=g) * 0.05 + torch.randn(width, generator=g)).to(dev)
+    fb = (torch.randn(rows, width, generator=g) * 0.06 + torch.randn(width, generator=g) + 0.01).to(dev)
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore", RuntimeWarning)                  # random weights: this times the trunk, it scores nothing
+        features = quality.DinoFeatures(DinoV2Features("dinov2_vits14").to(dev))
+        features(pred_d)
+
+    def sums_arm():
+        """The device part of ``DistributionMeter.compute``: the moments of both banks and the three kernel sums."""
+        for _ in range(a.warmup):
+            quality.moments(fa), quality.moments(fb), quality.kid_sums(fa, fb)
+        torch.cuda.synchronize(dev)
+        start, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        start.record()
+        for _ in range(passes):
+            ma, mb, sums = quality.moments(fa), quality.moments(fb), quality.kid_sums(fa, fb)
+        end.record()
+        end.synchronize()
+        return start.elapsed_time(end) / passes, (ma, mb, sums)
+
+    def sums_host_arm():
+        """Copy the features, then ``np.cov`` of each set and the three float64 Gram products of KID."""
+        t0 = time.perf_counter()
+        xa, xb = fa.cpu().numpy().astype(np.float64), fb.cpu().numpy().astype(np.float64)
+        ma, mb = (xa.mean(axis=0), np.cov(xa, rowvar=False)), (xb.mean(axis=0), np.cov(xb, rowvar=False))
+        kaa, kbb, kab = (xa @ xa.T / width + 1) ** 3, (xb @ xb.T / width + 1) ** 3, (xa @ xb.T / width + 1) ** 3
+        sums = (kaa.sum() - np.trace(kaa), kbb.sum() - np.trace(kbb), kab.sum())
+        return (time.perf_counter() - t0) * 1e3, (ma, mb, sums)
+
+    def frechet_arm():
+        """The host part of ``compute``: two copies and ``frechet_from_moments`` (two symmetric eigensolves)."""
+        (_, mean_a, cov_a), (_, mean_b, cov_b) = quality.moments(fa), quality.moments(fb)
+        torch.cuda.synchronize(dev)
+        t0 = time.perf_counter()
+        fd = quality.frechet_from_moments(mean_a, cov_a, mean_b, cov_b)
+        return (time.perf_counter() - t0) * 1e3, fd
+
+    def update_arm():
+        meter = quality.DistributionMeter(features, capacity=a.batch * (a.reps + a.warmup))
+        for _ in range(a.warmup):
+            meter.update(pred_d, target_d)
+        torch.cuda.synchronize(dev)
+        start, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        start.record()
+        for _ in range(a.reps):
+            meter.update(pred_d, target_d)
+        end.record()
+        end.synchronize()
+        return start.elapsed_time(end) / a.reps, len(meter._bank[0])
+
+    times = {"device_moments_and_kid_sums_ms": [], "host_cov_and_gram_ms": [], "host_frechet_ms": [], "update_ms": []}
+    for rep in range(a.alternate):
+        ms0, dev_res = timed(sums_arm, f"device moments + KID sums rep {rep}:",
+                             lambda ms: f"{ms:.4f} ms per pass over {rows} + {rows} rows of {width} ({passes} passes between two events)")
+        ms1, host_res = timed(sums_host_arm, f"host np.cov + Gram        rep {rep}:", lambda ms: f"{ms:.2f} ms (copy included)")
+        ms2, fd = timed(frechet_arm, f"host frechet_from_moments rep {rep}:", lambda ms: f"{ms:.2f} ms (copy included)")
+        ms3, _ = timed(update_arm, f"update through vits14     rep {rep}:",
+                       lambda ms: f"{ms:.4f} ms per update of {a.batch} + {a.batch} images at {a.size}x{a.size} ({a.reps} updates between "
+                                  "two events)")
+        for k, ms in zip(times, (ms0, ms1, ms2, ms3)):
+            times[k].append(ms)
+        cov_gap = max(float(np.abs(d[2].cpu().numpy() - h[1]).max() / np.abs(h[1]).max()) for d, h in zip(dev_res[:2], host_res[:2]))
+        sum_gap = max(abs(float(x) - float(y)) / abs(float(y)) for x, y in zip(dev_res[2].cpu().numpy(), host_res[2]))
+        print(f"                          device against host: cov {cov_gap:.1e} of the largest entry, KID sums rel {sum_gap:.1e}; "
+              f"fd {fd:.6g}", flush=True)
+    summary = {k: {"mean": sum(v) / len(v), "min": min(v), "max": max(v), "repetitions": len(v)} for k, v in times.items()}
+    print(json.dumps({"metric": f"set-level scores: moments + KID sums of {rows} + {rows} rows of {width} on the device against np.cov + "
+                                f"float64 Gram products on the host; frechet_from_moments on the host; one DistributionMeter.update of "
+                                f"{a.batch} + {a.batch} images at {a.size}x{a.size} through dinov2_vits14 (random weights); alternating",
+                      "unit": "ms", "arms": summary,
+                      "host_over_device": summary["host_cov_and_gram_ms"]["mean"] / summary["device_moments_and_kid_sums_ms"]["mean"]}))
+    sys.exit(0)
 
 times = {"device_batch_ms": [], "host_batch_ms": []}
 for rep in range(a.alternate):
