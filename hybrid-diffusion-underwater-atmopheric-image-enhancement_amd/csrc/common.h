@@ -1,5 +1,6 @@
 // Host side of the library: error reporting, launch checks and the launchers / workspace queries that one source file offers to
-// another.  No device code: what can change a kernel's instructions is in device.h (and conv_x3.h for the split-operand convolutions and the direct 1x1).
+// another.  No device code: what can change a kernel's instructions is in device.h (and conv_x3.h for the split-operand convolutions
+// and the direct 1x1; reduce.h and radix_select.h for the score and loss kernels).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -42,12 +43,45 @@ static inline int grid_floor_2k(int64_t n, int per_thread = 1) {
   if (blocks > 2048) blocks = 2048;
   return (int)blocks;
 }
-// ceil(n / (256 * per_thread)), at most 8192: model_b_ops.hip and every other kernel of sampler_step.hip
+// ceil(n / (256 * per_thread)), at most 8192: model_b_ops.hip, train_b_ops.hip and every other kernel of sampler_step.hip
 static inline int grid_ceil_8k(int64_t n, int per_thread = 1) {
   int64_t blocks = (n + (int64_t)256 * per_thread - 1) / ((int64_t)256 * per_thread);
   if (blocks > 256 * 32) blocks = 256 * 32;
   if (blocks < 1) blocks = 1;
   return (int)blocks;
+}
+
+// ceil(n / per_block) workgroups, each leaving one partial sum, between 1 and cap: the grids of the score and loss reductions.  They
+// are functions of the per-image (or per-call) element count alone, which is what makes a result independent of the batch.
+static inline int parts_for(int64_t n, int64_t per_block, int cap) {
+  int64_t b = (n + per_block - 1) / per_block;
+  if (b > cap) b = cap;
+  return b < 1 ? 1 : (int)b;
+}
+
+static inline int64_t align256(int64_t v) { return (v + 255) / 256 * 256; }
+
+// Cuts a caller's workspace into regions that each start on a 256-byte boundary, in the order of the take() calls.  Over a null base it
+// only measures (every take() returns null): a workspace query and its launcher run the same layout function.
+struct Carver {
+  char* base;
+  int64_t end = 0;                                              // bytes up to the end of the last region
+  explicit Carver(void* p) : base((char*)p) {}
+  template <class T>
+  T* take(int64_t count) {
+    const int64_t at = align256(end);
+    end = at + count * (int64_t)sizeof(T);
+    return base ? (T*)(base + at) : nullptr;
+  }
+  int64_t total() const { return align256(end); }               // the workspace size: the last region padded like the others
+};
+
+// the image sizes the per-image score kernels take: images on blockIdx.z, pixel indices of one plane in 32 bits
+static inline int check_sizes(const char* who, int N, int H, int W, int min_side) {
+  HDIFF_CHECK_ARG(N >= 1 && N <= 65535, "%s: N = %d; between 1 and 65535 images", who, N);
+  HDIFF_CHECK_ARG(H >= min_side && W >= min_side, "%s: H = %d, W = %d; both sides must be at least %d", who, H, W, min_side);
+  HDIFF_CHECK_ARG((int64_t)H * W <= (1ll << 30), "%s: H * W = %lld is too large; at most 2^30 pixels", who, (long long)H * W);
+  return HDIFF_OK;
 }
 
 // hipFuncSetAttribute is per DEVICE: true the first time the calling site (one `static uint64_t` mask each) runs with the

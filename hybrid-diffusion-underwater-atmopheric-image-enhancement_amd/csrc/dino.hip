@@ -20,14 +20,13 @@
 #include <math.h>
 
 #include "common.h"
-#include "device.h"
+#include "reduce.h"
 
 using namespace hdiff;
 
 namespace {
 
-#include "quality_common.h"
-
+constexpr int kThreads = 256;
 constexpr int kPatch = 14;               // DINOv2's patch side
 constexpr int kCrop = 2;                 // pixels removed from every edge before the patches are cut
 constexpr int kTok = 64;                 // tokens per LayerNorm workgroup: one wave along L ...
@@ -231,11 +230,6 @@ __global__ __launch_bounds__(kThreads) void layerscale_bwd_kernel(const float* d
 // ---------------------------------------------------------------------------------------------------------- smooth-L1 taps
 // a tap is B images of n_img elements, element j of image b at a[b * img_stride + j * stride] (stride = L picks the class token
 // of a [B][C][L] tensor).  grid (parts, B): part[b][p] = sum over the block's elements of smooth_l1(a - b), in double
-int tap_parts(int64_t n_img) {
-  const int64_t b = (n_img + (int64_t)kThreads * 8 - 1) / ((int64_t)kThreads * 8);
-  return b > kMaxParts ? kMaxParts : (int)b;
-}
-
 __global__ __launch_bounds__(kThreads) void tap_partial_kernel(const float* __restrict__ a, const float* __restrict__ t, int64_t n_img,
                                                                 int64_t stride, int64_t img_stride, double* __restrict__ part) {
   const float* pa = a + (int64_t)blockIdx.y * img_stride;
@@ -246,7 +240,7 @@ __global__ __launch_bounds__(kThreads) void tap_partial_kernel(const float* __re
     const double m = fabs(d);
     acc += m < 1.0 ? 0.5 * d * d : m - 0.5;        // a NaN difference takes the second branch and stays a NaN
   }
-  const double s = block_sum_all(acc);
+  const double s = block_sum_all<kThreads>(acc);
   if (threadIdx.x == 0) part[(int64_t)blockIdx.y * gridDim.x + blockIdx.x] = s;
 }
 
@@ -452,7 +446,7 @@ int hdiff_smooth_l1_tap_workspace(int B, int64_t n_img, int64_t* bytes) {
   const int rc = check_tap("smooth_l1_tap_workspace", B, n_img, 1, n_img);
   if (rc != HDIFF_OK) return rc;
   HDIFF_CHECK_ARG(bytes, "smooth_l1_tap_workspace: null pointer");
-  *bytes = align256((int64_t)B * tap_parts(n_img) * (int64_t)sizeof(double));
+  *bytes = align256((int64_t)B * parts_for(n_img, kThreads * 8, kMaxParts) * (int64_t)sizeof(double));
   return HDIFF_OK;
 }
 
@@ -463,7 +457,7 @@ int hdiff_smooth_l1_tap_fwd(const float* a, const float* t, int B, int64_t n_img
   HDIFF_CHECK_ARG(a && t && slot && scratch, "smooth_l1_tap_fwd: null pointer");
   HDIFF_CHECK_ARG(weight >= 0.0 && weight <= 1e30, "smooth_l1_tap_fwd: weight = %g; finite and not negative", weight);
   (void)hipGetLastError();
-  const int parts = tap_parts(n_img);
+  const int parts = parts_for(n_img, kThreads * 8, kMaxParts);
   hipLaunchKernelGGL(tap_partial_kernel, dim3(parts, B), dim3(kThreads), 0, (hipStream_t)stream, a, t, n_img, stride, img_stride,
                      (double*)scratch);
   hipLaunchKernelGGL(tap_slot_kernel, dim3(B), dim3(64), 0, (hipStream_t)stream, (const double*)scratch, parts,

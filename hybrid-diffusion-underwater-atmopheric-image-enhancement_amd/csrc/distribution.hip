@@ -29,14 +29,13 @@
 #include <math.h>
 
 #include "common.h"
-#include "device.h"
+#include "reduce.h"
 
 using namespace hdiff;
 
 namespace {
 
-#include "quality_common.h"
-
+constexpr int kThreads = 256;
 constexpr int kTile = 32;               // outputs per tile side; a thread holds (ty, ty + 16) x (tx, tx + 16)
 constexpr int kChunk = 32;              // rows (moments) or channels (pairs) staged at a time
 constexpr int kPad = kTile + 1;
@@ -167,7 +166,7 @@ __global__ __launch_bounds__(kThreads) void kid_pairs_kernel(const Rows X, const
     }
     sum += v;
   }
-  const double total = block_sum_all(sum);
+  const double total = block_sum_all<kThreads>(sum);
   if (threadIdx.x == 0) slots[blockIdx.x] = total;
 }
 
@@ -178,7 +177,7 @@ __global__ __launch_bounds__(kThreads) void kid_total_kernel(const double* __res
   const int b = blockIdx.x;
   int first = 0;
   for (int q = 0; q < b; ++q) first += K.tiles[q];
-  const double s = sum_partials(slots + first, K.tiles[b], 1);
+  const double s = sum_partials<kThreads>(slots + first, K.tiles[b], 1);
   if (threadIdx.x == 0) out[b] = s;
 }
 

@@ -34,7 +34,7 @@
 // per-pixel formulas alone switch contraction off, so that identical images give l = cs = 1 and a loss of exactly 0: with fma,
 // 2 mu_x mu_y + C1 and mu_x^2 + mu_y^2 + C1 would round differently for mu_x == mu_y.
 #include "common.h"
-#include "device.h"
+#include "reduce.h"
 
 using namespace hdiff;
 
@@ -194,18 +194,6 @@ __global__ __launch_bounds__(kThreads) void msssim_moments_kernel(const Params P
   else moments_job<16>(sA, sB, sRow, sw, dst, HW, P.H, P.W, ty0, tx0, l1);
 }
 
-// Block-wide sum in a fixed order: wave sums, then thread 0 adds them in index order (valid in thread 0).
-__device__ double block_sum_d(double v) {
-  __shared__ double part[kThreads / 64];
-  v = wave_sum(v);
-  if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = v;
-  __syncthreads();
-  double s = 0.0;
-  if (threadIdx.x == 0)
-    for (int i = 0; i < kThreads / 64; ++i) s += part[i];
-  return s;
-}
-
 __device__ __forceinline__ float powi(float v, int n) {
   float r = 1.0f;
   for (int i = 0; i < n; ++i) r *= v;
@@ -282,16 +270,14 @@ __global__ __launch_bounds__(kThreads) void msssim_pixel_kernel(const Params P, 
     }
   }
   if (!BWD) {
-    const double s = block_sum_d(acc);
+    const double s = block_sum_to0<kThreads>(acc);
     if (threadIdx.x == 0) partial[blockIdx.x] = s;
   }
 }
 
 __global__ __launch_bounds__(kThreads) void msssim_finalize_kernel(const double* __restrict__ partial, int nparts, double scale,
                                                                     float* __restrict__ loss) {
-  double acc = 0.0;
-  for (int i = threadIdx.x; i < nparts; i += kThreads) acc += partial[i];
-  const double s = block_sum_d(acc);
+  const double s = sum_partials_to0<kThreads>(partial, nparts, 1);
   if (threadIdx.x == 0) loss[0] = (float)(s * scale);
 }
 
@@ -367,13 +353,17 @@ __global__ __launch_bounds__(kThreads) void msssim_adjoint_kernel(const Params P
   }
 }
 
-int pix_blocks(int64_t n) {
-  int64_t b = (n + kThreads - 1) / kThreads;
-  if (b > kPixMaxBlocks) b = kPixMaxBlocks;
-  return b < 1 ? 1 : (int)b;
-}
+// workgroups of the pixel kernel, forward and backward
+int pix_blocks(int64_t N) { return parts_for(N, kThreads, kPixMaxBlocks); }
 
-inline int64_t align256(int64_t v) { return (v + 255) / 256 * 256; }
+// the forward's scratch: the per-pixel L1 planes, then one partial sum per workgroup of the pixel kernel; returns its size
+struct FwdScratch { float* l1f; double* part; };
+int64_t fwd_layout(void* base, int64_t N, FwdScratch* f) {
+  Carver c(base);
+  f->l1f = c.take<float>(N * 3);
+  f->part = c.take<double>(pix_blocks(N));
+  return c.end;      // NOT c.total(): this size has never been padded, and callers' records hold it
+}
 
 // Host-side validation and the kernels' parameter block; no HIP call.
 int make_params(const hdiff_msssim_desc* d, Params* P, const char* who) {
@@ -428,7 +418,8 @@ int hdiff_msssim_l1_workspace(const hdiff_msssim_desc* d, int64_t* saved_bytes, 
   HDIFF_CHECK_ARG(saved_bytes && scratch_bytes, "msssim_l1_workspace: null pointer");
   const int64_t N = (int64_t)d->B * d->H * d->W;
   *saved_bytes = N * d->npairs * 5 * (int64_t)sizeof(float);
-  const int64_t fwd = align256(N * 3 * (int64_t)sizeof(float)) + (int64_t)pix_blocks(N) * (int64_t)sizeof(double);
+  FwdScratch f;
+  const int64_t fwd = fwd_layout(nullptr, N, &f);
   const int64_t bwd = N * d->npairs * 3 * (int64_t)sizeof(float);
   *scratch_bytes = fwd > bwd ? fwd : bwd;
   return HDIFF_OK;
@@ -443,13 +434,14 @@ int hdiff_msssim_l1_fwd(const hdiff_msssim_desc* d, const float* x, const float*
   (void)hipGetLastError();
   const int64_t N = (int64_t)P.B * P.H * P.W;
   float* mom = (float*)saved;
-  float* l1f = (float*)scratch;
-  double* part = (double*)((char*)scratch + align256(N * 3 * (int64_t)sizeof(float)));
+  FwdScratch f;
+  fwd_layout(scratch, N, &f);
   const int tiles = P.tiles_x * cdiv(P.H, kTile), nb = pix_blocks(N);
-  hipLaunchKernelGGL(msssim_moments_kernel, dim3(tiles, P.npairs + 3, P.B), dim3(kThreads), 0, (hipStream_t)stream, P, x, y, mom, l1f);
+  hipLaunchKernelGGL(msssim_moments_kernel, dim3(tiles, P.npairs + 3, P.B), dim3(kThreads), 0, (hipStream_t)stream, P, x, y, mom,
+                     f.l1f);
   hipLaunchKernelGGL(msssim_pixel_kernel<false>, dim3(nb), dim3(kThreads), 0, (hipStream_t)stream, P, (const float*)mom,
-                     (const float*)l1f, (const float*)nullptr, part, (float*)nullptr);
-  hipLaunchKernelGGL(msssim_finalize_kernel, dim3(1), dim3(kThreads), 0, (hipStream_t)stream, (const double*)part, nb, P.red_scale,
+                     (const float*)f.l1f, (const float*)nullptr, f.part, (float*)nullptr);
+  hipLaunchKernelGGL(msssim_finalize_kernel, dim3(1), dim3(kThreads), 0, (hipStream_t)stream, (const double*)f.part, nb, P.red_scale,
                      loss);
   HDIFF_CHECK_LAUNCH("msssim_l1_fwd kernels");
   return HDIFF_OK;

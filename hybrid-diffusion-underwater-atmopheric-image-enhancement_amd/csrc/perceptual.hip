@@ -12,14 +12,13 @@
 #include <math.h>
 
 #include "common.h"
-#include "device.h"
+#include "reduce.h"
 
 using namespace hdiff;
 
 namespace {
 
-#include "quality_common.h"
-
+constexpr int kThreads = 256;
 constexpr int kMaxParts = 256;            // partial sums per reduction (per image for the LPIPS layer)
 constexpr int64_t kMaxElems = 1ll << 40;
 
@@ -89,11 +88,6 @@ __global__ __launch_bounds__(kThreads) void maxpool2_bwd_kernel(const float* __r
 }
 
 // --------------------------------------------------------------------------------------------------------------- L1 mean
-int l1_parts(int64_t n) {
-  const int64_t b = (n + (int64_t)kThreads * 8 - 1) / ((int64_t)kThreads * 8);
-  return b > kMaxParts ? kMaxParts : (int)b;
-}
-
 __global__ __launch_bounds__(kThreads) void l1_partial_kernel(const float* __restrict__ a, const float* __restrict__ b, int64_t n,
                                                                double* __restrict__ part) {
   double acc = 0.0;
@@ -101,13 +95,13 @@ __global__ __launch_bounds__(kThreads) void l1_partial_kernel(const float* __res
     const float d = b ? a[i] - b[i] : a[i];
     acc += (double)fabsf(d);
   }
-  const double s = block_sum_all(acc);
+  const double s = block_sum_all<kThreads>(acc);
   if (threadIdx.x == 0) part[blockIdx.x] = s;
 }
 
 __global__ __launch_bounds__(kThreads) void l1_finalize_kernel(const double* __restrict__ part, int parts, int64_t n,
                                                                 float* __restrict__ out) {
-  const double s = sum_partials(part, parts, 1);
+  const double s = sum_partials<kThreads>(part, parts, 1);
   if (threadIdx.x == 0) out[0] = (float)(s / (double)n);
 }
 
@@ -140,11 +134,6 @@ __global__ __launch_bounds__(kThreads) void charbonnier_bwd_kernel(const float* 
 }
 
 // ----------------------------------------------------------------------------------------------------------------- LPIPS
-int lpips_parts(int64_t HW) {
-  const int64_t b = (HW + kThreads - 1) / kThreads;
-  return b > kMaxParts ? kMaxParts : (int)b;
-}
-
 // grid (parts, 1, N): one pixel per thread and trip; the channels of a pixel are HW apart, neighbouring threads read neighbouring words
 __global__ __launch_bounds__(kThreads) void lpips_partial_kernel(const float* __restrict__ f0, const float* __restrict__ f1,
                                                                   const float* __restrict__ w, int Cc, int64_t HW,
@@ -168,14 +157,14 @@ __global__ __launch_bounds__(kThreads) void lpips_partial_kernel(const float* __
     }
     acc += pix;
   }
-  const double s = block_sum_all(acc);
+  const double s = block_sum_all<kThreads>(acc);
   if (threadIdx.x == 0) part[(int64_t)n * gridDim.x + blockIdx.x] = s;
 }
 
 __global__ __launch_bounds__(kThreads) void lpips_finalize_kernel(const double* __restrict__ part, int parts, int64_t HW,
                                                                    double* __restrict__ out) {
   const int n = blockIdx.x;
-  const double s = sum_partials(part + (int64_t)n * parts, parts, 1);
+  const double s = sum_partials<kThreads>(part + (int64_t)n * parts, parts, 1);
   if (threadIdx.x == 0) out[n] = out[n] + s / (double)HW;
 }
 
@@ -260,7 +249,7 @@ int hdiff_l1_mean_workspace(int64_t n, int64_t* bytes) {
   const int rc = check_count("l1_mean_workspace", n);
   if (rc != HDIFF_OK) return rc;
   HDIFF_CHECK_ARG(bytes, "l1_mean_workspace: null pointer");
-  *bytes = align256((int64_t)l1_parts(n) * (int64_t)sizeof(double));
+  *bytes = align256((int64_t)parts_for(n, kThreads * 8, kMaxParts) * (int64_t)sizeof(double));
   return HDIFF_OK;
 }
 
@@ -269,7 +258,7 @@ int hdiff_l1_mean_fwd(const float* a, const float* b, int64_t n, float* out, voi
   if (rc != HDIFF_OK) return rc;
   HDIFF_CHECK_ARG(a && out && scratch, "l1_mean_fwd: null pointer");
   (void)hipGetLastError();
-  const int parts = l1_parts(n);
+  const int parts = parts_for(n, kThreads * 8, kMaxParts);
   hipLaunchKernelGGL(l1_partial_kernel, dim3(parts), dim3(kThreads), 0, (hipStream_t)stream, a, b, n, (double*)scratch);
   hipLaunchKernelGGL(l1_finalize_kernel, dim3(1), dim3(kThreads), 0, (hipStream_t)stream, (const double*)scratch, parts, n, out);
   HDIFF_CHECK_LAUNCH("l1_mean_fwd kernels");
@@ -315,7 +304,7 @@ int hdiff_lpips_layer_workspace(int N, int C, int H, int W, int64_t* bytes) {
   const int rc = check_features("lpips_layer_workspace", N, C, H, W);
   if (rc != HDIFF_OK) return rc;
   HDIFF_CHECK_ARG(bytes, "lpips_layer_workspace: null pointer");
-  *bytes = align256((int64_t)N * lpips_parts((int64_t)H * W) * (int64_t)sizeof(double));
+  *bytes = align256((int64_t)N * parts_for((int64_t)H * W, kThreads, kMaxParts) * (int64_t)sizeof(double));
   return HDIFF_OK;
 }
 
@@ -326,7 +315,7 @@ int hdiff_lpips_layer(const float* f0, const float* f1, const float* w, int N, i
   HDIFF_CHECK_ARG(f0 && f1 && w && out && scratch, "lpips_layer: null pointer");
   (void)hipGetLastError();
   const int64_t HW = (int64_t)H * W;
-  const int parts = lpips_parts(HW);
+  const int parts = parts_for(HW, kThreads, kMaxParts);
   hipLaunchKernelGGL(lpips_partial_kernel, dim3(parts, 1, N), dim3(kThreads), 0, (hipStream_t)stream, f0, f1, w, C, HW,
                      (double*)scratch);
   hipLaunchKernelGGL(lpips_finalize_kernel, dim3(N), dim3(kThreads), 0, (hipStream_t)stream, (const double*)scratch, parts, HW, out);

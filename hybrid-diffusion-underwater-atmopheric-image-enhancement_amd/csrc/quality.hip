@@ -28,14 +28,14 @@
 #include <math.h>
 
 #include "common.h"
-#include "device.h"
+#include "radix_select.h"
+#include "reduce.h"
 
 using namespace hdiff;
 
 namespace {
 
-#include "quality_common.h"
-
+constexpr int kThreads = 256;
 constexpr int kTile = 32;
 constexpr int kWin = 7;
 constexpr int kSsimIn = kTile + kWin - 1;      // 38
@@ -47,19 +47,9 @@ constexpr int kSelects = 4;                    // select = plane * 2 + (0: left 
 constexpr int kMaxPixBlocks = 128;
 constexpr int kPixPerBlock = kThreads * 16;
 
-struct Select { unsigned prefix, rank, less, eq; };
+using Cut = Select<unsigned>;                  // on the 32-bit key of the fp32 sample
 
 __device__ __forceinline__ float scaled(float x) { return fminf(fmaxf(x, 0.0f), 1.0f) * 255.0f; }
-
-// order-preserving key of a finite fp32 value; -0 and +0 share a key
-__device__ __forceinline__ unsigned key_of(float f) {
-  if (f == 0.0f) f = 0.0f;
-  const unsigned u = __builtin_bit_cast(unsigned, f);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float value_of(unsigned k) {
-  return __builtin_bit_cast(float, (k & 0x80000000u) ? (k & 0x7fffffffu) : ~k);
-}
 
 // ---------------------------------------------------------------------------------------------------------------- PSNR / SSIM
 // rec: [N][3][tiles][3] = {sum of SSIM over the tile's valid positions, sum of squared differences over its pixels, flag}
@@ -128,7 +118,7 @@ __global__ __launch_bounds__(kThreads) void ssim_tile_kernel(const float* __rest
       ssum += num / den;
     }
   }
-  const double s = block_sum_all(ssum), d2 = block_sum_all(dsum);
+  const double s = block_sum_all<kThreads>(ssum), d2 = block_sum_all<kThreads>(dsum);
   if (threadIdx.x == 0) {
     double* o = rec + (((int64_t)n * 3 + c) * gridDim.x + blockIdx.x) * 3;
     o[0] = s; o[1] = d2; o[2] = bad ? 1.0 : 0.0;
@@ -142,9 +132,9 @@ __global__ __launch_bounds__(kThreads) void ssim_finalize_kernel(const double* _
   const double positions = (double)(H - kWin + 1) * (double)(W - kWin + 1);
   double ssim = 0.0, sq = 0.0, bad = 0.0;
   for (int c = 0; c < 3; ++c) {
-    ssim += sum_partials(r + (int64_t)c * tiles * 3, tiles, 3) / positions;
-    sq += sum_partials(r + (int64_t)c * tiles * 3 + 1, tiles, 3);
-    bad += sum_partials(r + (int64_t)c * tiles * 3 + 2, tiles, 3);
+    ssim += sum_partials<kThreads>(r + (int64_t)c * tiles * 3, tiles, 3) / positions;
+    sq += sum_partials<kThreads>(r + (int64_t)c * tiles * 3 + 1, tiles, 3);
+    bad += sum_partials<kThreads>(r + (int64_t)c * tiles * 3 + 2, tiles, 3);
   }
   if (threadIdx.x != 0) return;
   const double mse = sq / (3.0 * (double)H * (double)W);
@@ -158,7 +148,7 @@ __global__ __launch_bounds__(kThreads) void ssim_finalize_kernel(const double* _
 // ---------------------------------------------------------------------------------------------------------------- UIQM
 struct UiqmWs {
   unsigned* hist;      // [3 passes][N][kSelects][kBins]
-  Select* sel;         // [N][kSelects]
+  Cut* sel;            // [N][kSelects]
   unsigned* mbits;     // [N][3]  bit pattern of the largest Sobel magnitude
   unsigned* flag;      // [N]
   double* kept;        // [N][pix_blocks][2]
@@ -188,11 +178,7 @@ __global__ __launch_bounds__(kThreads) void uiqm_init_kernel(const UiqmParams P,
   if (blockIdx.x != 0) return;
   for (int i = threadIdx.x; i < P.N * 3; i += kThreads) ws.mbits[i] = 0u;
   for (int i = threadIdx.x; i < P.N; i += kThreads) ws.flag[i] = 0u;
-  for (int i = threadIdx.x; i < P.N * kSelects; i += kThreads) {
-    Select s;
-    s.prefix = 0u; s.rank = (i & 1) ? P.hi_rank : P.lo_rank; s.less = 0u; s.eq = 0u;
-    ws.sel[i] = s;
-  }
+  for (int i = threadIdx.x; i < P.N * kSelects; i += kThreads) ws.sel[i] = select_start<unsigned>((i & 1) ? P.hi_rank : P.lo_rank);
 }
 
 // One digit of the select: counts, per select, the samples whose key agrees with the select's prefix above `match_shift`
@@ -219,49 +205,21 @@ __global__ __launch_bounds__(kThreads) void uicm_hist_kernel(const UiqmParams P,
     for (int s = 0; s < kSelects; ++s) {
       const unsigned k = key[s >> 1];
       if (match_shift == 32) {
-        if ((s & 1) == 0) atomicAdd(&sh[s * kBins + (k >> bin_shift)], 1u);      // first digit: both selects of a plane share one histogram
+        if ((s & 1) == 0) atomicAdd(&sh[s * kBins + (k >> bin_shift)], 1u);      // first digit: select_hist's rule, one histogram per plane
       } else if ((k >> match_shift) == prefix[s]) {
         atomicAdd(&sh[s * kBins + ((k >> bin_shift) & mask)], 1u);
       }
     }
   }
   if (pass == 0 && bad) ws.flag[n] = 1u;
-  __syncthreads();
-  unsigned* g = ws.hist + ((int64_t)pass * P.N + n) * kSelects * kBins;
-  for (int i = threadIdx.x; i < kSelects * kBins; i += kThreads)
-    if (sh[i]) atomicAdd(&g[i], sh[i]);
+  select_flush<kThreads>(sh, ws.hist + ((int64_t)pass * P.N + n) * kSelects * kBins, kSelects * kBins);
 }
 
 // grid (kSelects, 1, N): the bin that holds the select's rank; prefix, rank within the bin, samples below and inside it
 __global__ __launch_bounds__(kThreads) void uicm_scan_kernel(const UiqmParams P, const UiqmWs ws, int pass, int bits) {
-  __shared__ unsigned cum[kThreads];
   const int s = blockIdx.x, n = blockIdx.z;
-  const int hs = pass == 0 ? (s & ~1) : s;      // the first digit's histogram is the plane's, kept under its left select
-  const unsigned* h = ws.hist + (((int64_t)pass * P.N + n) * kSelects + hs) * kBins;
-  const Select st = ws.sel[n * kSelects + s];
-  constexpr int per = kBins / kThreads;
-  unsigned cnt[per], local = 0u;
-#pragma unroll
-  for (int j = 0; j < per; ++j) {
-    cnt[j] = h[threadIdx.x * per + j];      // the bins past 2^bits of the last pass are zero
-    local += cnt[j];
-  }
-  cum[threadIdx.x] = local;
-  __syncthreads();
-  unsigned before = 0u;
-  for (int i = 0; i < (int)threadIdx.x; ++i) before += cum[i];
-  if (st.rank < before || st.rank >= before + local) return;
-#pragma unroll
-  for (int j = 0; j < per; ++j) {
-    if (st.rank < before + cnt[j]) {
-      Select o;
-      o.prefix = (st.prefix << bits) | (unsigned)(threadIdx.x * per + j);
-      o.rank = st.rank - before; o.less = st.less + before; o.eq = cnt[j];
-      ws.sel[n * kSelects + s] = o;
-      return;
-    }
-    before += cnt[j];
-  }
+  const unsigned* h = ws.hist + (((int64_t)pass * P.N + n) * kSelects + select_hist(pass, s)) * kBins;
+  select_scan<kThreads, kBins>(h, &ws.sel[n * kSelects + s], bits);
 }
 
 // kept: [N][pix_blocks][2]: per plane the double sum of the samples whose key lies strictly between the two cut keys
@@ -280,7 +238,7 @@ __global__ __launch_bounds__(kThreads) void uicm_kept_kernel(const UiqmParams P,
     if (k0 > lo0 && k0 < hi0) a0 += (double)rg;
     if (k1 > lo1 && k1 < hi1) a1 += (double)yb;
   }
-  const double s0 = block_sum_all(a0), s1 = block_sum_all(a1);
+  const double s0 = block_sum_all<kThreads>(a0), s1 = block_sum_all<kThreads>(a1);
   if (threadIdx.x == 0) {
     double* o = ws.kept + ((int64_t)n * P.pix_blocks + blockIdx.x) * 2;
     o[0] = s0; o[1] = s1;
@@ -289,8 +247,8 @@ __global__ __launch_bounds__(kThreads) void uicm_kept_kernel(const UiqmParams P,
 
 // The trimmed mean of one plane from the partial sums and the select's counts (every thread; ends with a barrier).
 __device__ float trimmed_mean(const UiqmParams& P, const UiqmWs& ws, int n, int plane) {
-  const double between = sum_partials(ws.kept + (int64_t)n * P.pix_blocks * 2 + plane, P.pix_blocks, 2);
-  const Select lo = ws.sel[n * kSelects + plane * 2], hi = ws.sel[n * kSelects + plane * 2 + 1];
+  const double between = sum_partials<kThreads>(ws.kept + (int64_t)n * P.pix_blocks * 2 + plane, P.pix_blocks, 2);
+  const Cut lo = ws.sel[n * kSelects + plane * 2], hi = ws.sel[n * kSelects + plane * 2 + 1];
   const double vlo = (double)value_of(lo.prefix), vhi = (double)value_of(hi.prefix);
   double total;
   if (lo.prefix == hi.prefix) {
@@ -316,7 +274,7 @@ __global__ __launch_bounds__(kThreads) void uicm_var_kernel(const UiqmParams P, 
     a0 += d0 * d0;
     a1 += d1 * d1;
   }
-  const double s0 = block_sum_all(a0), s1 = block_sum_all(a1);
+  const double s0 = block_sum_all<kThreads>(a0), s1 = block_sum_all<kThreads>(a1);
   if (threadIdx.x == 0) {
     double* o = ws.var + ((int64_t)n * P.pix_blocks + blockIdx.x) * 2;
     o[0] = s0; o[1] = s1;
@@ -472,11 +430,11 @@ __global__ __launch_bounds__(kThreads) void uism_kernel(const UiqmParams P, cons
 __global__ __launch_bounds__(kThreads) void uiqm_finalize_kernel(const UiqmParams P, const UiqmWs ws, double* __restrict__ out) {
   const int n = blockIdx.x;
   const double mu0 = (double)trimmed_mean(P, ws, n, 0), mu1 = (double)trimmed_mean(P, ws, n, 1);
-  const double var0 = sum_partials(ws.var + (int64_t)n * P.pix_blocks * 2, P.pix_blocks, 2) / (double)P.K;
-  const double var1 = sum_partials(ws.var + (int64_t)n * P.pix_blocks * 2 + 1, P.pix_blocks, 2) / (double)P.K;
+  const double var0 = sum_partials<kThreads>(ws.var + (int64_t)n * P.pix_blocks * 2, P.pix_blocks, 2) / (double)P.K;
+  const double var1 = sum_partials<kThreads>(ws.var + (int64_t)n * P.pix_blocks * 2 + 1, P.pix_blocks, 2) / (double)P.K;
   double e[3];
-  for (int c = 0; c < 3; ++c) e[c] = (2.0 / P.eme_blocks) * sum_partials(ws.eme + ((int64_t)n * 3 + c) * P.tiles, P.tiles, 1);
-  const double con = sum_partials(ws.con + (int64_t)n * P.tiles, P.tiles, 1);
+  for (int c = 0; c < 3; ++c) e[c] = (2.0 / P.eme_blocks) * sum_partials<kThreads>(ws.eme + ((int64_t)n * 3 + c) * P.tiles, P.tiles, 1);
+  const double con = sum_partials<kThreads>(ws.con + (int64_t)n * P.tiles, P.tiles, 1);
   if (threadIdx.x != 0) return;
   double uicm = (-0.0268 * sqrt(mu0 * mu0 + mu1 * mu1)) + (0.1586 * sqrt(var0 + var1));
   double uism = (0.299 * e[0]) + (0.587 * e[1]) + (0.144 * e[2]);
@@ -491,26 +449,20 @@ __global__ __launch_bounds__(kThreads) void uiqm_finalize_kernel(const UiqmParam
 }
 
 // ---------------------------------------------------------------------------------------------------------------- host side
-int pix_blocks(int64_t K) {
-  const int64_t b = (K + kPixPerBlock - 1) / kPixPerBlock;
-  return b > kMaxPixBlocks ? kMaxPixBlocks : (int)b;
-}
-
 int64_t ssim_bytes(int N, int tiles) { return align256((int64_t)N * 3 * tiles * 3 * (int64_t)sizeof(double)); }
 
 // the regions of the UIQM workspace, in order; returns its size
-int64_t uiqm_layout(char* base, int N, int tiles, int pb, UiqmWs* ws) {
-  int64_t off = 0;
-  auto take = [&](int64_t bytes) { char* p = base ? base + off : nullptr; off += align256(bytes); return p; };
-  ws->hist = (unsigned*)take((int64_t)3 * N * kSelects * kBins * (int64_t)sizeof(unsigned));
-  ws->sel = (Select*)take((int64_t)N * kSelects * (int64_t)sizeof(Select));
-  ws->mbits = (unsigned*)take((int64_t)N * 3 * (int64_t)sizeof(unsigned));
-  ws->flag = (unsigned*)take((int64_t)N * (int64_t)sizeof(unsigned));
-  ws->kept = (double*)take((int64_t)N * pb * 2 * (int64_t)sizeof(double));
-  ws->var = (double*)take((int64_t)N * pb * 2 * (int64_t)sizeof(double));
-  ws->eme = (double*)take((int64_t)N * 3 * tiles * (int64_t)sizeof(double));
-  ws->con = (double*)take((int64_t)N * tiles * (int64_t)sizeof(double));
-  return off;
+int64_t uiqm_layout(void* base, int N, int tiles, int pb, UiqmWs* ws) {
+  Carver c(base);
+  ws->hist = c.take<unsigned>((int64_t)3 * N * kSelects * kBins);
+  ws->sel = c.take<Cut>((int64_t)N * kSelects);
+  ws->mbits = c.take<unsigned>((int64_t)N * 3);
+  ws->flag = c.take<unsigned>(N);
+  ws->kept = c.take<double>((int64_t)N * pb * 2);
+  ws->var = c.take<double>((int64_t)N * pb * 2);
+  ws->eme = c.take<double>((int64_t)N * 3 * tiles);
+  ws->con = c.take<double>((int64_t)N * tiles);
+  return c.total();
 }
 
 }  // namespace
@@ -523,7 +475,7 @@ int hdiff_quality_workspace(int N, int H, int W, int64_t* bytes) {
   HDIFF_CHECK_ARG(bytes, "quality_workspace: null pointer");
   const int tiles = cdiv(W, kTile) * cdiv(H, kTile);
   UiqmWs ws;
-  const int64_t u = uiqm_layout(nullptr, N, tiles, pix_blocks((int64_t)H * W), &ws), s = ssim_bytes(N, tiles);
+  const int64_t u = uiqm_layout(nullptr, N, tiles, parts_for((int64_t)H * W, kPixPerBlock, kMaxPixBlocks), &ws), s = ssim_bytes(N, tiles);
   *bytes = u > s ? u : s;
   return HDIFF_OK;
 }
@@ -551,7 +503,7 @@ int hdiff_uiqm(const float* a, int N, int H, int W, double* out, void* scratch, 
   P.tiles_x = cdiv(W, kTile);
   P.tiles = P.tiles_x * cdiv(H, kTile);
   const int64_t K = (int64_t)H * W;
-  P.pix_blocks = pix_blocks(K);
+  P.pix_blocks = parts_for(K, kPixPerBlock, kMaxPixBlocks);
   P.K = (unsigned)K;
   const int64_t t_l = (int64_t)ceil(0.1 * (double)K), t_r = (int64_t)floor(0.1 * (double)K);
   P.lo_rank = (unsigned)(t_l + 1);
@@ -560,7 +512,7 @@ int hdiff_uiqm(const float* a, int N, int H, int W, double* out, void* scratch, 
   P.eme_blocks = (double)cdiv(H, 8) * (double)cdiv(W, 8);
   P.con_blocks = (double)(H / 8) * (double)(W / 8);
   UiqmWs ws;
-  uiqm_layout((char*)scratch, N, P.tiles, P.pix_blocks, &ws);
+  uiqm_layout(scratch, N, P.tiles, P.pix_blocks, &ws);
   hipStream_t s = (hipStream_t)stream;
   const dim3 blk(kThreads), pix(P.pix_blocks, 1, N);
   const int64_t nh = (int64_t)3 * N * kSelects * kBins;

@@ -3,7 +3,7 @@
 // pool and the nearest resize.  All HBM-bound streaming kernels; compiled with -ffp-contract=off so that the forward rounds like
 // the reference's separate tensor ops.  Every reduction is a fixed-order two-stage sum (no float atomics): bitwise reproducible.
 #include "common.h"
-#include "device.h"
+#include "reduce.h"
 
 using namespace hdiff;
 
@@ -11,35 +11,10 @@ using namespace hdiff;
 
 namespace {
 
-constexpr int kTailThreads = 256;
+constexpr int kTailThreads = 256;      // workgroup of the two loss kernels: their block sums are instantiated for it
 constexpr int kTailMaxBlocks = 1024;
 
-inline int tail_blocks(int64_t pixels) {
-  int64_t b = (pixels + kTailThreads - 1) / kTailThreads;
-  if (b > kTailMaxBlocks) b = kTailMaxBlocks;
-  return b < 1 ? 1 : (int)b;
-}
-
-inline int grid_for(int64_t n) {
-  int64_t blocks = (n + 255) / 256;
-  if (blocks > 256 * 32) blocks = 256 * 32;
-  return blocks < 1 ? 1 : (int)blocks;
-}
-
 __device__ __forceinline__ int clamp_t(int64_t t, int T) { return t < 0 ? 0 : (t >= T ? T - 1 : (int)t); }
-
-// Block-wide sum in a fixed order: wave sums, then wave 0 adds the four of them in index order.
-__device__ double block_sum_d(double v) {
-  __shared__ double part[kTailThreads / 64];
-  v = wave_sum(v);
-  const int w = threadIdx.x >> 6;
-  if ((threadIdx.x & 63) == 0) part[w] = v;
-  __syncthreads();
-  double s = 0.0;
-  if (threadIdx.x == 0)
-    for (int i = 0; i < (int)(blockDim.x >> 6); ++i) s += part[i];
-  return s;   // valid in thread 0
-}
 
 // One thread per pixel (b, p) of P = B * HW; channel c of pixel p of sample b sits at (b * 3 + c) * HW + p.
 //   mse = (np - noise)^2                                            F.mse_loss(reduction='none')        (Diffusion.py:102)
@@ -78,15 +53,13 @@ __global__ void train_b_loss_fwd_kernel(const float* __restrict__ np_, const flo
     const float nb = fmaxf(sqrtf(bn[0] * bn[0] + bn[1] * bn[1] + bn[2] * bn[2]), 1e-8f);
     acc += (double)((a[0] / na) * (bn[0] / nb) + (a[1] / na) * (bn[1] / nb) + (a[2] / na) * (bn[2] / nb));
   }
-  const double s = block_sum_d(acc);
+  const double s = block_sum_to0<kTailThreads>(acc);
   if (threadIdx.x == 0) partial[blockIdx.x] = s;
 }
 
 // One workgroup: col[0] = 1 - (sum of the partials in index order) / P.
 __global__ void train_b_loss_finalize_kernel(const double* __restrict__ partial, int nparts, int64_t P, float* __restrict__ col) {
-  double acc = 0.0;
-  for (int i = threadIdx.x; i < nparts; i += blockDim.x) acc += partial[i];
-  const double s = block_sum_d(acc);
+  const double s = sum_partials_to0<kTailThreads>(partial, nparts, 1);
   if (threadIdx.x == 0) col[0] = 1.0f - (float)(s / (double)P);
 }
 
@@ -194,7 +167,7 @@ extern "C" {
 
 int hdiff_train_b_loss_workspace(int64_t pixels, int64_t* bytes) {
   HDIFF_CHECK_ARG(bytes && pixels > 0, "train_b_loss_workspace: bad arguments");
-  *bytes = (int64_t)tail_blocks(pixels) * (int64_t)sizeof(double);
+  *bytes = (int64_t)parts_for(pixels, kTailThreads, kTailMaxBlocks) * (int64_t)sizeof(double);
   return HDIFF_OK;
 }
 
@@ -206,7 +179,7 @@ int hdiff_train_b_loss_fwd(const float* noise_pred, const float* noise, const fl
   HDIFF_CHECK_ARG(T > 0 && B > 0 && HW > 0, "train_b_loss_fwd: bad sizes");
   (void)hipGetLastError();
   const int64_t P = (int64_t)B * HW;
-  const int nb = tail_blocks(P);
+  const int nb = parts_for(P, kTailThreads, kTailMaxBlocks);
   double* part = (double*)workspace;
   hipLaunchKernelGGL(train_b_loss_fwd_kernel, dim3(nb), dim3(kTailThreads), 0, (hipStream_t)stream, noise_pred, noise, y_t, gt,
                      t, sqrt_ab, sqrt_1mab, T, HW, P, mse, y0_pred, part);
@@ -223,7 +196,7 @@ int hdiff_train_b_loss_bwd(const float* noise_pred, const float* noise, const fl
   HDIFF_CHECK_ARG(T > 0 && B > 0 && HW > 0, "train_b_loss_bwd: bad sizes");
   (void)hipGetLastError();
   const int64_t P = (int64_t)B * HW;
-  hipLaunchKernelGGL(train_b_loss_bwd_kernel, dim3(grid_for(P)), dim3(256), 0, (hipStream_t)stream, noise_pred, noise, y0_pred,
+  hipLaunchKernelGGL(train_b_loss_bwd_kernel, dim3(grid_ceil_8k(P)), dim3(256), 0, (hipStream_t)stream, noise_pred, noise, y0_pred,
                      gt, t, sqrt_ab, sqrt_1mab, T, HW, P, d_mse, d_y0, d_col, d_noise_pred);
   HDIFF_CHECK_LAUNCH("train_b_loss_bwd_kernel");
   return HDIFF_OK;
@@ -233,7 +206,7 @@ int hdiff_avgpool_global_bwd(const float* dy, float* dx, int BC, int HW, hdiff_s
   HDIFF_CHECK_ARG(dy && dx && BC > 0 && HW > 0, "avgpool_global_bwd: bad arguments");
   (void)hipGetLastError();
   const int64_t n = (int64_t)BC * HW;
-  hipLaunchKernelGGL(avgpool_global_bwd_kernel, dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream, dy, dx, HW, n);
+  hipLaunchKernelGGL(avgpool_global_bwd_kernel, dim3(grid_ceil_8k(n)), dim3(256), 0, (hipStream_t)stream, dy, dx, HW, n);
   HDIFF_CHECK_LAUNCH("avgpool_global_bwd_kernel");
   return HDIFF_OK;
 }
@@ -242,7 +215,7 @@ int hdiff_resize_nearest_bwd(const float* dy, float* dx, int BC, int H, int W, i
   HDIFF_CHECK_ARG(dy && dx && BC > 0 && H > 0 && W > 0 && OH > 0 && OW > 0, "resize_nearest_bwd: bad arguments");
   (void)hipGetLastError();
   const int64_t n = (int64_t)BC * H * W;
-  hipLaunchKernelGGL(resize_nearest_bwd_kernel, dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream, dy, dx, H, W, OH, OW,
+  hipLaunchKernelGGL(resize_nearest_bwd_kernel, dim3(grid_ceil_8k(n)), dim3(256), 0, (hipStream_t)stream, dy, dx, H, W, OH, OW,
                      (float)H / (float)OH, (float)W / (float)OW, n);
   HDIFF_CHECK_LAUNCH("resize_nearest_bwd_kernel");
   return HDIFF_OK;

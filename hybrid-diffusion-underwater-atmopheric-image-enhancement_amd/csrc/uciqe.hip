@@ -29,35 +29,26 @@
 #include <math.h>
 
 #include "common.h"
-#include "device.h"
+#include "radix_select.h"
+#include "reduce.h"
 
 using namespace hdiff;
 
 namespace {
 
-#include "quality_common.h"
-
+constexpr int kThreads = 256;
 constexpr int kBins = 2048;
 constexpr int kSelects = 2;                    // 0: the low cut, 1: the high cut
 constexpr int kPasses = 6;
 constexpr int kMaxPixBlocks = 256;
 constexpr int kPixPerBlock = kThreads * 8;
 
-struct Select { unsigned long long prefix; unsigned rank, less, eq, pad; };
-
-// order-preserving key of a finite double; -0 and +0 share a key (L comes out a few ulp below zero for near-black pixels)
-__device__ __forceinline__ unsigned long long key_of(double f) {
-  if (f == 0.0) f = 0.0;
-  const unsigned long long u = __builtin_bit_cast(unsigned long long, f);
-  return (u >> 63) ? ~u : (u | 0x8000000000000000ull);
-}
-__device__ __forceinline__ double value_of(unsigned long long k) {
-  return __builtin_bit_cast(double, (k >> 63) ? (k & 0x7fffffffffffffffull) : ~k);
-}
+// on the 64-bit key of L (L comes out a few ulp below zero for near-black pixels: -0 and +0 must share a key)
+using Cut = Select<unsigned long long>;
 
 struct UciqeWs {
   unsigned* hist;      // [kPasses][N][kSelects][kBins]
-  Select* sel;         // [N][kSelects]
+  Cut* sel;            // [N][kSelects]
   unsigned* flag;      // [N]
   double* part;        // [N][pix_blocks][2]  sum of chroma, sum of the saturation term
   double* tail;        // [N][pix_blocks][3]  sum of L below the low cut, above the high cut, sum of (chroma - mean)^2
@@ -80,11 +71,7 @@ __global__ __launch_bounds__(kThreads) void uciqe_init_kernel(const UciqeParams 
   if (blockIdx.x != 0) return;
   for (int i = threadIdx.x; i < P.N; i += kThreads) ws.flag[i] = 0u;
   const unsigned t = P.top ? P.top : 1u;      // top == 0: any rank inside the image; the result is not used
-  for (int i = threadIdx.x; i < P.N * kSelects; i += kThreads) {
-    Select s;
-    s.prefix = 0ull; s.rank = (i & 1) ? P.K - t : t - 1u; s.less = 0u; s.eq = 0u; s.pad = 0u;
-    ws.sel[i] = s;
-  }
+  for (int i = threadIdx.x; i < P.N * kSelects; i += kThreads) ws.sel[i] = select_start<unsigned long long>((i & 1) ? P.K - t : t - 1u);
 }
 
 __global__ __launch_bounds__(kThreads) void uciqe_lab_kernel(const UciqeParams P, const UciqeWs ws, const float* __restrict__ x) {
@@ -112,7 +99,7 @@ __global__ __launch_bounds__(kThreads) void uciqe_lab_kernel(const UciqeParams P
     sum_s += (c == 0.0 || L == 0.0) ? 0.0 : c / L;
   }
   if (bad) ws.flag[n] = 1u;
-  const double s0 = block_sum_all(sum_c), s1 = block_sum_all(sum_s);
+  const double s0 = block_sum_all<kThreads>(sum_c), s1 = block_sum_all<kThreads>(sum_s);
   if (threadIdx.x == 0) {
     double* o = ws.part + ((int64_t)n * P.pix_blocks + blockIdx.x) * 2;
     o[0] = s0; o[1] = s1;
@@ -136,48 +123,20 @@ __global__ __launch_bounds__(kThreads) void uciqe_hist_kernel(const UciqeParams 
     const unsigned long long k = key_of(lum[i]);
     const unsigned bin = (unsigned)(k >> bin_shift) & mask;
     if (match_shift == 64) {
-      atomicAdd(&sh[bin], 1u);      // first digit: both selects share one histogram
+      atomicAdd(&sh[bin], 1u);      // first digit: select_hist's rule, one histogram for both selects
     } else {
       if ((k >> match_shift) == p0) atomicAdd(&sh[bin], 1u);
       if ((k >> match_shift) == p1) atomicAdd(&sh[kBins + bin], 1u);
     }
   }
-  __syncthreads();
-  unsigned* g = ws.hist + ((int64_t)pass * P.N + n) * kSelects * kBins;
-  for (int i = threadIdx.x; i < kSelects * kBins; i += kThreads)
-    if (sh[i]) atomicAdd(&g[i], sh[i]);
+  select_flush<kThreads>(sh, ws.hist + ((int64_t)pass * P.N + n) * kSelects * kBins, kSelects * kBins);
 }
 
 // grid (kSelects, 1, N): the bin that holds the select's rank; prefix, rank within the bin, pixels below and inside it
 __global__ __launch_bounds__(kThreads) void uciqe_scan_kernel(const UciqeParams P, const UciqeWs ws, int pass, int bits) {
-  __shared__ unsigned cum[kThreads];
   const int s = blockIdx.x, n = blockIdx.z;
-  const int hs = pass == 0 ? 0 : s;      // the first digit's histogram is kept under the low select
-  const unsigned* h = ws.hist + (((int64_t)pass * P.N + n) * kSelects + hs) * kBins;
-  const Select st = ws.sel[n * kSelects + s];
-  constexpr int per = kBins / kThreads;
-  unsigned cnt[per], local = 0u;
-#pragma unroll
-  for (int j = 0; j < per; ++j) {
-    cnt[j] = h[threadIdx.x * per + j];      // the bins past 2^bits of the 10-bit passes are zero
-    local += cnt[j];
-  }
-  cum[threadIdx.x] = local;
-  __syncthreads();
-  unsigned before = 0u;
-  for (int i = 0; i < (int)threadIdx.x; ++i) before += cum[i];
-  if (st.rank < before || st.rank >= before + local) return;
-#pragma unroll
-  for (int j = 0; j < per; ++j) {
-    if (st.rank < before + cnt[j]) {
-      Select o;
-      o.prefix = (st.prefix << bits) | (unsigned long long)(threadIdx.x * per + j);
-      o.rank = st.rank - before; o.less = st.less + before; o.eq = cnt[j]; o.pad = 0u;
-      ws.sel[n * kSelects + s] = o;
-      return;
-    }
-    before += cnt[j];
-  }
+  const unsigned* h = ws.hist + (((int64_t)pass * P.N + n) * kSelects + select_hist(pass, s)) * kBins;
+  select_scan<kThreads, kBins>(h, &ws.sel[n * kSelects + s], bits);
 }
 
 __global__ __launch_bounds__(kThreads) void uciqe_tail_kernel(const UciqeParams P, const UciqeWs ws) {
@@ -186,7 +145,7 @@ __global__ __launch_bounds__(kThreads) void uciqe_tail_kernel(const UciqeParams 
   const double* lum = ws.lum + (int64_t)n * HW;
   const double* chr = ws.chroma + (int64_t)n * HW;
   const unsigned long long lo = ws.sel[n * kSelects].prefix, hi = ws.sel[n * kSelects + 1].prefix;
-  const double mean = sum_partials(ws.part + (int64_t)n * P.pix_blocks * 2, P.pix_blocks, 2) / (double)P.K;
+  const double mean = sum_partials<kThreads>(ws.part + (int64_t)n * P.pix_blocks * 2, P.pix_blocks, 2) / (double)P.K;
   double below = 0.0, above = 0.0, spread = 0.0;
   for (int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x; i < HW; i += (int64_t)gridDim.x * kThreads) {
     const double L = lum[i], d = chr[i] - mean;
@@ -195,7 +154,7 @@ __global__ __launch_bounds__(kThreads) void uciqe_tail_kernel(const UciqeParams 
     if (k > hi) above += L;
     spread += d * d;
   }
-  const double s0 = block_sum_all(below), s1 = block_sum_all(above), s2 = block_sum_all(spread);
+  const double s0 = block_sum_all<kThreads>(below), s1 = block_sum_all<kThreads>(above), s2 = block_sum_all<kThreads>(spread);
   if (threadIdx.x == 0) {
     double* o = ws.tail + ((int64_t)n * P.pix_blocks + blockIdx.x) * 3;
     o[0] = s0; o[1] = s1; o[2] = s2;
@@ -206,11 +165,11 @@ __global__ __launch_bounds__(kThreads) void uciqe_finalize_kernel(const UciqePar
   const int n = blockIdx.x;
   const double* part = ws.part + (int64_t)n * P.pix_blocks * 2;
   const double* tail = ws.tail + (int64_t)n * P.pix_blocks * 3;
-  const double sum_s = sum_partials(part + 1, P.pix_blocks, 2);
-  const double below = sum_partials(tail, P.pix_blocks, 3), above = sum_partials(tail + 1, P.pix_blocks, 3);
-  const double spread = sum_partials(tail + 2, P.pix_blocks, 3);
+  const double sum_s = sum_partials<kThreads>(part + 1, P.pix_blocks, 2);
+  const double below = sum_partials<kThreads>(tail, P.pix_blocks, 3), above = sum_partials<kThreads>(tail + 1, P.pix_blocks, 3);
+  const double spread = sum_partials<kThreads>(tail + 2, P.pix_blocks, 3);
   if (threadIdx.x != 0) return;
-  const Select lo = ws.sel[n * kSelects], hi = ws.sel[n * kSelects + 1];
+  const Cut lo = ws.sel[n * kSelects], hi = ws.sel[n * kSelects + 1];
   double sc = sqrt(spread / (double)P.K);
   double us = sum_s / (double)P.K;
   double conl = (double)NAN;
@@ -229,23 +188,17 @@ __global__ __launch_bounds__(kThreads) void uciqe_finalize_kernel(const UciqePar
 }
 
 // ---------------------------------------------------------------------------------------------------------------- host side
-int pix_blocks(int64_t K) {
-  const int64_t b = (K + kPixPerBlock - 1) / kPixPerBlock;
-  return b > kMaxPixBlocks ? kMaxPixBlocks : (int)b;
-}
-
 // the regions of the workspace, in order; returns its size
-int64_t uciqe_layout(char* base, int N, int64_t K, int pb, UciqeWs* ws) {
-  int64_t off = 0;
-  auto take = [&](int64_t bytes) { char* p = base ? base + off : nullptr; off += align256(bytes); return p; };
-  ws->hist = (unsigned*)take((int64_t)kPasses * N * kSelects * kBins * (int64_t)sizeof(unsigned));
-  ws->sel = (Select*)take((int64_t)N * kSelects * (int64_t)sizeof(Select));
-  ws->flag = (unsigned*)take((int64_t)N * (int64_t)sizeof(unsigned));
-  ws->part = (double*)take((int64_t)N * pb * 2 * (int64_t)sizeof(double));
-  ws->tail = (double*)take((int64_t)N * pb * 3 * (int64_t)sizeof(double));
-  ws->lum = (double*)take((int64_t)N * K * (int64_t)sizeof(double));
-  ws->chroma = (double*)take((int64_t)N * K * (int64_t)sizeof(double));
-  return off;
+int64_t uciqe_layout(void* base, int N, int64_t K, int pb, UciqeWs* ws) {
+  Carver c(base);
+  ws->hist = c.take<unsigned>((int64_t)kPasses * N * kSelects * kBins);
+  ws->sel = c.take<Cut>((int64_t)N * kSelects);
+  ws->flag = c.take<unsigned>(N);
+  ws->part = c.take<double>((int64_t)N * pb * 2);
+  ws->tail = c.take<double>((int64_t)N * pb * 3);
+  ws->lum = c.take<double>((int64_t)N * K);
+  ws->chroma = c.take<double>((int64_t)N * K);
+  return c.total();
 }
 
 }  // namespace
@@ -258,7 +211,7 @@ int hdiff_uciqe_workspace(int N, int H, int W, int64_t* bytes) {
   HDIFF_CHECK_ARG(bytes, "uciqe_workspace: null pointer");
   const int64_t K = (int64_t)H * W;
   UciqeWs ws;
-  *bytes = uciqe_layout(nullptr, N, K, pix_blocks(K), &ws);
+  *bytes = uciqe_layout(nullptr, N, K, parts_for(K, kPixPerBlock, kMaxPixBlocks), &ws);
   return HDIFF_OK;
 }
 
@@ -271,12 +224,12 @@ int hdiff_uciqe(const float* a, int N, int H, int W, double scale, double* out, 
   UciqeParams P;
   P.N = N; P.H = H; P.W = W;
   const int64_t K = (int64_t)H * W;
-  P.pix_blocks = pix_blocks(K);
+  P.pix_blocks = parts_for(K, kPixPerBlock, kMaxPixBlocks);
   P.K = (unsigned)K;
   P.top = (unsigned)nearbyint((0.01 * (double)H) * (double)W);      // numpy's round: half to even
   P.scale = scale;
   UciqeWs ws;
-  uciqe_layout((char*)scratch, N, K, P.pix_blocks, &ws);
+  uciqe_layout(scratch, N, K, P.pix_blocks, &ws);
   hipStream_t s = (hipStream_t)stream;
   const dim3 blk(kThreads), pix(P.pix_blocks, 1, N);
   const int64_t nh = (int64_t)kPasses * N * kSelects * kBins;
