@@ -145,9 +145,12 @@ class PerceptualLoss_dino(nn.Module):
     trunk keeps its random initialisation and one ``RuntimeWarning`` says so.  ``.perceptual`` is the ``hdiff_amd.dino.DinoV2Features``,
     ``.taps`` the ``(module names, tensor, multiplicity)`` list in use, ``.last_per_image`` the ``(B,)`` shares of the last call.  The
     attention probabilities (``attn.attn_drop``) are not hooked (``hdiff_amd.dino`` says why).  ``normalize_inputs=True`` is not
-    provided; ``version='dino'``, ``dinov2_vitg14`` and the ``_reg`` models raise ``ValueError``."""
+    provided; ``version='dino'``, ``dinov2_vitg14`` and the ``_reg`` models raise ``ValueError``.  ``dense``: ``"conv"`` (default) or
+    ``"tokens"``, the trunk's dense-layer route (``hdiff_amd.dino.dense_route``); with ``trunk=`` the trunk's own choice stands and the
+    two must not disagree."""
 
-    def __init__(self, model="dinov2_vits14", version="dinov2", layers=None, normalize_inputs=False, *, weights=None, trunk=None):
+    def __init__(self, model="dinov2_vits14", version="dinov2", layers=None, normalize_inputs=False, *, weights=None, trunk=None,
+                 dense=None):
         super().__init__()
         from ..dino import DinoV2Features, check_model_name, select_taps
         if normalize_inputs:
@@ -155,9 +158,11 @@ class PerceptualLoss_dino(nn.Module):
                                       "images go to the trunk as they are)")
         if trunk is None:
             check_model_name(model, version)
-            trunk = DinoV2Features(model)
+            trunk = DinoV2Features(model, dense="conv" if dense is None else dense)
         elif not isinstance(trunk, DinoV2Features):
             raise TypeError("PerceptualLoss_dino: trunk= must be a hdiff_amd.dino.DinoV2Features")
+        elif dense is not None and dense != trunk.dense:
+            raise ValueError(f"PerceptualLoss_dino: dense={dense!r} but the trunk was built with dense={trunk.dense!r}")
         self.perceptual = trunk
         self._model, self.version, self.layers = model, version, layers
         self.taps = select_taps(trunk.depth, layers)

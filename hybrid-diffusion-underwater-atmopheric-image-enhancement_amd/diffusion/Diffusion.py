@@ -94,7 +94,8 @@ class GaussianDiffusionTrainer(nn.Module):
     terms; their gradient reaches the model through ``y_0_pred``.  ``msssim_loss=Loss.loss.MSSSIMLoss()`` is the package's own
     MS-SSIM + L1 loss on the HIP path; any other callable runs under torch autograd.  ``dino_loss="native"`` builds
     ``Loss.loss.PerceptualLoss_dino(perceptual_dino, weights=dino_weights)``, the package's own DINOv2 term (``dino_weights``: the hub
-    checkpoint's state dict or its path; without it the trunk is random and warns).  The trunk is frozen and belongs to the trainer,
+    checkpoint's state dict or its path; without it the trunk is random and warns; ``dino_dense="tokens"`` runs its dense layers on
+    ``csrc/dense_tokens.hip``, default ``"conv"``).  The trunk is frozen and belongs to the trainer,
     not to ``model``: it is in no checkpoint, no EMA and no optimizer."""
 
     DINO_WEIGHT, MSSSIM_WEIGHT, COL_WEIGHT = 0.5, 0.0045, 1.0          # reference :165
@@ -106,6 +107,7 @@ class GaussianDiffusionTrainer(nn.Module):
         # (tests/test_train_b_cpu.py holds the signature to that)
         extra_losses = more.pop("extra_losses", None)
         dino_weights = more.pop("dino_weights", None)
+        dino_dense = more.pop("dino_dense", None)
         if more:
             raise TypeError(f"GaussianDiffusionTrainer.__init__() got an unexpected keyword argument '{next(iter(more))}'")
         self.extra_losses = _checked_extra_losses(extra_losses)
@@ -126,9 +128,11 @@ class GaussianDiffusionTrainer(nn.Module):
             if dino_loss != "native":
                 raise ValueError(f"GaussianDiffusionTrainer: dino_loss is a callable, None or 'native', got {dino_loss!r}")
             from ..Loss.loss import PerceptualLoss_dino
-            dino_loss = PerceptualLoss_dino(perceptual_dino, weights=dino_weights)
+            dino_loss = PerceptualLoss_dino(perceptual_dino, weights=dino_weights, dense=dino_dense)
         elif dino_weights is not None:
             raise ValueError("GaussianDiffusionTrainer: dino_weights goes with dino_loss='native'")
+        elif dino_dense is not None:
+            raise ValueError("GaussianDiffusionTrainer: dino_dense goes with dino_loss='native'")
         self.loss_perceptual_dino = dino_loss
         self.ms_ssim_loss = msssim_loss
         self._warned_missing = False

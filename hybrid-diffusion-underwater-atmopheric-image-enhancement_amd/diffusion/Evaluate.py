@@ -193,7 +193,7 @@ def _run_sets(config, task: str) -> Dict[str, Dict[str, object]]:
     features = _cfg(config, "distribution", None)
     if features is None and _cfg(config, "fd_model", None) is not None:
         from ..dino import DinoV2Features
-        trunk = DinoV2Features(_cfg(config, "fd_model"))
+        trunk = DinoV2Features(_cfg(config, "fd_model"), dense=_cfg(config, "fd_dense", "conv"))
         if _cfg(config, "fd_weights", None) is not None:
             trunk.load_dinov2(torch.load(_cfg(config, "fd_weights"), map_location="cpu"))
         features = quality.DinoFeatures(trunk).to(device)
@@ -218,7 +218,8 @@ def test(config, epoch=None) -> Dict[str, Dict[str, object]]:
     ``uciqe``, ``uciqe_scale`` (``evaluate``'s; absent: no UCIQE, ``res.txt`` as before), ``lpips`` (a ``quality.LPIPS``) or
     ``lpips_weights`` (the path of a file holding ``{"vgg": ..., "lin": ...}``; absent: no LPIPS, ``res.txt`` as before),
     ``distribution`` (a feature callable such as ``quality.DinoFeatures``, or a ``quality.DistributionMeter``) or ``fd_model``
-    (``"dinov2_vits14"`` / ``vitb14`` / ``vitl14``) with ``fd_weights`` (the path of the hub state dict, loaded with ``load_dinov2``;
+    (``"dinov2_vits14"`` / ``vitb14`` / ``vitl14``) with ``fd_weights`` (the path of the hub state dict, loaded with ``load_dinov2``) and ``fd_dense`` (``"conv"``, the default, or
+    ``"tokens"``: the trunk's dense-layer route;
     the images must fit the trunk: ``H - 4`` and ``W - 4`` multiples of 14; absent: no set-level scores, ``res.txt`` as before).
     ``epoch`` is accepted and unused, as in the reference.  Returns ``{set name: evaluate()'s dict}``."""
     return _run_sets(config, "test")

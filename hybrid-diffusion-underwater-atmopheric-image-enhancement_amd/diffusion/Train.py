@@ -25,7 +25,7 @@ Deliberate deviations from the reference:
     not fit ``parallel.FlatGradients`` as it stands); of ``device_list`` the first entry is used.
   * ``msssim_loss`` defaults to the package's ``Loss.loss.MSSSIMLoss()``; ``dino_loss`` is optional -- a callable, or ``"native"`` for
     the package's own ``Loss.loss.PerceptualLoss_dino`` with ``dino_weights`` (the hub checkpoint's state dict or its path; no weights
-    ship and none are fetched) -- and the trainer's warning stands when it is absent.  The trunk is frozen and belongs to the trainer:
+    ship and none are fetched) and ``dino_dense`` (``"conv"``, the default, or ``"tokens"``: the trunk's dense-layer route) -- and the trainer's warning stands when it is absent.  The trunk is frozen and belongs to the trainer:
     ``TERMS``, the records, the checkpoints, the EMA and the optimizer are the same with and without it.
 
 Additions, all optional (with none of them set the run is the loop above): ``dataset_root`` (one root for both sets, or a dict by
@@ -263,7 +263,8 @@ def train(config) -> Dict[str, object]:
     trainer = GaussianDiffusionTrainer(model, _cfg(config, "beta_1"), _cfg(config, "beta_T"), _cfg(config, "T"),
                                        dino_loss=_cfg(config, "dino_loss", None), msssim_loss=msssim_loss,
                                        extra_losses=_cfg(config, "extra_losses", None),
-                                       dino_weights=_cfg(config, "dino_weights", None)).to(device)              # :629
+                                       dino_weights=_cfg(config, "dino_weights", None),
+                                       dino_dense=_cfg(config, "dino_dense", None)).to(device)                  # :629
     ema_decay = _cfg(config, "ema_decay", None)
     ema = hdiff_optim.EMA(model.parameters(), decay=ema_decay) if ema_decay is not None else None
 

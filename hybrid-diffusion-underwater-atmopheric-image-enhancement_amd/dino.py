@@ -7,6 +7,8 @@ token at position 0.  The dense layers (patch embedding on the unfolded 588-row 
 ``autograd.fused_conv(k=1)`` calls on the ``L`` positions viewed as a plane (``plane_of``), the attention core is
 ``hdiff_mha_flash_fwd / _bwd`` on the ``(B, 3C, L)`` qkv -- whose row order ``[Q | K | V]``, head ``h`` on rows ``h * d .. h * d + d - 1`` of each third, IS DINOv2's
 ``reshape(B, N, 3, heads, D)``: no row of ``qkv.weight`` is permuted -- and everything else is a kernel of ``csrc/dino.hip``.
+``DinoV2Features(dense="tokens")`` runs the dense layers and their input gradients on ``csrc/dense_tokens.hip`` instead
+(``hdiff_amd.dense``; ``dense_route`` decides; the default ``"conv"`` is the route just described).
 ``dino_perceptual`` adds ``smooth_l1_loss(..., 'mean')`` over the taps; its backward is written out by hand (no autograd graph inside
 the trunk): every tap adds ``g * weight / n * clamp(a - b, -1, 1)`` to the gradient already flowing into its tensor, the dense layers
 run their dgrad route and no weight gradient exists.  Nothing here runs in ATen.
@@ -35,8 +37,8 @@ from . import _capi
 from . import engine as E
 from .perceptual import _fp32_gpu, _stream
 
-__all__ = ["DINO_CFGS", "DinoV2Features", "default_taps", "select_taps", "resize_pos_embed", "dino_perceptual", "layer_norm", "gelu",
-           "layer_scale", "unfold_patches", "assemble_tokens", "smooth_l1_taps"]
+__all__ = ["DINO_CFGS", "DinoV2Features", "dense_route", "default_taps", "select_taps", "resize_pos_embed", "dino_perceptual", "layer_norm",
+           "gelu", "layer_scale","unfold_patches", "assemble_tokens", "smooth_l1_taps"]
 
 DINO_CFGS: Dict[str, Dict[str, int]] = {
     "dinov2_vits14": dict(embed_dim=384, depth=12, heads=6),
@@ -240,8 +242,29 @@ def plane_of(L: int) -> Tuple[int, int]:
     return best[1], best[2]
 
 
-def _dense(x, weight, bias):
-    """``nn.Linear`` over the channels of ``(B, Cin, L)`` as a one-tap conv on ``(B, Cin, rows, columns)`` (``plane_of``)."""
+DENSE_ROUTES = ("conv", "tokens")
+_MODE_NAMES = {0: "f32", 1: "bf16x3", 2: "f16"}
+
+
+def dense_route(dense: str, mode: str) -> str:
+    """Which kernel family runs the trunk's dense layers, forward and input gradient: ``"conv"`` -- ``autograd.fused_conv(k=1)`` on the
+    token axis shown as a plane (``plane_of``) -- or ``"tokens"`` -- ``dense.linear_tokens`` / ``linear_tokens_dgrad``
+    (``csrc/dense_tokens.hip``).  ``dense`` is the trunk's ``dense=`` argument, ``mode`` the contraction mode's name.  The token kernel
+    contracts on bf16 triples only, so ``dense="tokens"`` in mode ``"f32"`` runs the conv route: the exact-fp32 arm stays one switch
+    away, bit for bit what ``dense="conv"`` runs there."""
+    if dense not in DENSE_ROUTES:
+        raise ValueError(f"DinoV2Features: dense must be one of {DENSE_ROUTES}, got {dense!r}")
+    if mode not in _MODE_NAMES.values():
+        raise ValueError(f"dense_route: contraction mode must be one of {sorted(_MODE_NAMES.values())}, got {mode!r}")
+    return "tokens" if dense == "tokens" and mode != "f32" else "conv"
+
+
+def _dense(x, weight, bias, route: str = "conv", packs=None):
+    """``nn.Linear`` over the channels of ``(B, Cin, L)``: the token kernel, or a one-tap conv on ``(B, Cin, rows, columns)``
+    (``plane_of``)."""
+    if route == "tokens":
+        from .dense import linear_tokens
+        return linear_tokens(x, weight, bias, cache=packs)
     from .autograd import fused_conv
     B, Cin, L = (int(v) for v in x.shape)
     Cout = int(weight.shape[0])
@@ -250,9 +273,12 @@ def _dense(x, weight, bias):
         return fused_conv(x.view(B, Cin, rows, cols), None, weight.view(Cout, Cin, 1, 1), bias, k=1).view(B, Cout, L)
 
 
-def _dense_dgrad(dy, weight):
-    """The input gradient of ``_dense``: ``autograd._FusedConv.backward``'s dgrad launch (the forward kernels on the weight read as
-    ``[in = Cout][out = Cin]``); the weight is frozen, so there is nothing else."""
+def _dense_dgrad(dy, weight, route: str = "conv", packs=None):
+    """The input gradient of ``_dense``: the token kernel on the transposed pack, or ``autograd._FusedConv.backward``'s dgrad launch
+    (the forward kernels on the weight read as ``[in = Cout][out = Cin]``); the weight is frozen, so there is nothing else."""
+    if route == "tokens":
+        from .dense import linear_tokens_dgrad
+        return linear_tokens_dgrad(dy, weight, cache=packs)
     from .autograd import _run_conv
     B, Cout, L = (int(v) for v in dy.shape)
     Cin = int(weight.shape[1])
@@ -386,11 +412,16 @@ class DinoV2Features(nn.Module):
     pos_grid=)`` builds a small trunk of the same architecture (tests); its head dim is any the attention kernels accept.  Without
     ``load_dinov2`` the weights are random (truncated normal 0.02, LayerScale 1, zero biases) and one ``RuntimeWarning`` says so.
     ``forward(x, layers=None)`` -> the tap tensors in ``select_taps`` order (``(B, C, L)``; the patch embedding ``(B, C, h*w)``; the
-    class token ``(B, C)``)."""
+    class token ``(B, C)``).  ``dense="tokens"`` runs every dense layer and every input gradient on ``csrc/dense_tokens.hip`` instead of the
+    one-tap conv (``dense_route``; the default ``"conv"`` launches what it always did; ``hdiff_amd.dense`` has the memory of the packs)."""
 
     def __init__(self, model: Optional[str] = "dinov2_vits14", *, embed_dim: Optional[int] = None, depth: Optional[int] = None,
-                 heads: Optional[int] = None, patch: int = PATCH, pos_grid: int = POS_GRID, version: str = "dinov2"):
+                 heads: Optional[int] = None, patch: int = PATCH, pos_grid: int = POS_GRID, version: str = "dinov2", dense: str = "conv"):
         super().__init__()
+        dense_route(dense, "f32")                        # raises for an unknown name
+        self.dense = dense
+        from .dense import PackCache
+        self._packs = PackCache()
         if embed_dim is None:
             check_model_name(model, version)
             cfg = DINO_CFGS[model]
@@ -443,6 +474,12 @@ class DinoV2Features(nn.Module):
             self._pos_cache[key] = pe[0].t().contiguous().to(device=dev, dtype=torch.float32)
         return self._pos_cache[key]
 
+    def _route(self) -> str:
+        """``dense_route`` at the contraction mode of this moment"""
+        if self.dense == "conv":
+            return "conv"
+        return dense_route(self.dense, _MODE_NAMES[_lib().hdiff_get_contraction_mode()])
+
     def _check(self, x):
         x = _fp32_gpu(x, "x")
         if x.dim() != 4 or int(x.shape[1]) != 3:
@@ -464,23 +501,24 @@ class DinoV2Features(nn.Module):
         Cc = self.embed_dim
         f: Dict[str, _Feat] = {}
         saved = []
+        route = self._route()
         with torch.cuda.device(x.device):
             pos = self._pos(h, w, x.device)
             pw = self.patch_embed.proj.weight
-            patch = _dense(_unfold(x), pw.view(Cc, -1), self.patch_embed.proj.bias)
+            patch = _dense(_unfold(x), pw.view(Cc, -1), self.patch_embed.proj.bias, route, self._packs)
             f["patch"] = _feat(patch)
             t = _tokens(patch, self.cls_token, pos)
             L = h * w + 1
             for i, blk in enumerate(self.blocks):
                 n1, m1, r1 = _ln(t, blk.norm1.weight, blk.norm1.bias, keep)
-                qkv = _dense(n1, blk.attn.qkv.weight, blk.attn.qkv.bias)
+                qkv = _dense(n1, blk.attn.qkv.weight, blk.attn.qkv.bias, route, self._packs)
                 o, lse = _flash_fwd(qkv, self.heads, keep)
-                p = _dense(o, blk.attn.proj.weight, blk.attn.proj.bias)
+                p = _dense(o, blk.attn.proj.weight, blk.attn.proj.bias, route, self._packs)
                 s1, t1 = _ls(p, blk.ls1.gamma, t)
                 n2, m2, r2 = _ln(t1, blk.norm2.weight, blk.norm2.bias, keep)
-                fc1 = _dense(n2, blk.mlp.fc1.weight, blk.mlp.fc1.bias)
+                fc1 = _dense(n2, blk.mlp.fc1.weight, blk.mlp.fc1.bias, route, self._packs)
                 act = _gelu(fc1)
-                fc2 = _dense(act, blk.mlp.fc2.weight, blk.mlp.fc2.bias)
+                fc2 = _dense(act, blk.mlp.fc2.weight, blk.mlp.fc2.bias, route, self._packs)
                 s2, t2 = _ls(fc2, blk.ls2.gamma, t1)
                 for key, val in (("norm1", n1), ("qkv", qkv), ("proj", p), ("ls1", s1), ("norm2", n2), ("fc1", fc1), ("act", act),
                                  ("fc2", fc2), ("ls2", s2), ("out", t2)):
@@ -541,6 +579,7 @@ class _DinoLossFn(Function):
         blocks_saved, t_last, mf, rf, (B, H, W) = ctx.saved
         dev = t_last.device
         g = g.contiguous()
+        route = trunk._route()
 
         def tap(key, grad):
             """the taps of ``key`` added to ``grad`` in place (a new tensor when nothing flows yet)"""
@@ -575,23 +614,23 @@ class _DinoLossFn(Function):
                 G = tap(f"{i}.out", G)
                 d = tap_apart(f"{i}.ls2", G)
                 d = tap(f"{i}.fc2", None if d is None else _ls_bwd(d, blk.ls2.gamma))
-                d = tap(f"{i}.act", None if d is None else _dense_dgrad(d, blk.mlp.fc2.weight))
+                d = tap(f"{i}.act", None if d is None else _dense_dgrad(d, blk.mlp.fc2.weight, route, trunk._packs))
                 d = tap(f"{i}.fc1", None if d is None else _gelu_bwd(fc1, d))
-                d = tap(f"{i}.norm2", None if d is None else _dense_dgrad(d, blk.mlp.fc1.weight))
+                d = tap(f"{i}.norm2", None if d is None else _dense_dgrad(d, blk.mlp.fc1.weight, route, trunk._packs))
                 if d is not None:
                     G = _ln_bwd(t1, blk.norm2.weight, m2, r2, d, G)
                 d = tap_apart(f"{i}.ls1", G)
                 d = tap(f"{i}.proj", None if d is None else _ls_bwd(d, blk.ls1.gamma))
-                d = None if d is None else _flash_bwd(qkv, o, lse, _dense_dgrad(d, blk.attn.proj.weight), trunk.heads)
+                d = None if d is None else _flash_bwd(qkv, o, lse, _dense_dgrad(d, blk.attn.proj.weight, route, trunk._packs), trunk.heads)
                 d = tap(f"{i}.qkv", d)
-                d = tap(f"{i}.norm1", None if d is None else _dense_dgrad(d, blk.attn.qkv.weight))
+                d = tap(f"{i}.norm1", None if d is None else _dense_dgrad(d, blk.attn.qkv.weight, route, trunk._packs))
                 if d is not None:
                     G = _ln_bwd(t, blk.norm1.weight, m1, r1, d, G)
             d = tap("patch", None if G is None else _tokens_bwd(G))
             if d is None:
                 return torch.zeros(B, 3, H, W, device=dev), None, None, None, None
             Cc = trunk.embed_dim
-            dx = _fold(_dense_dgrad(d, trunk.patch_embed.proj.weight.view(Cc, -1)), B, H, W)
+            dx = _fold(_dense_dgrad(d, trunk.patch_embed.proj.weight.view(Cc, -1), route, trunk._packs), B, H, W)
         return dx, None, None, None, None
 
 

@@ -765,6 +765,25 @@ int hdiff_smooth_l1_tap_fwd(const float* a, const float* t, int B, int64_t n_img
 int hdiff_smooth_l1_tap_total(const double* slots, int ntaps, int B, float* out, float* per_image, hdiff_stream_t stream);
 int hdiff_smooth_l1_tap_bwd(const float* a, const float* t, const float* g, int B, int64_t n_img, int64_t stride, int64_t img_stride,
                             float weight, const float* da_in, float* da_out, hdiff_stream_t stream);
+/* ------------------------------------------------------------------------------------------------------------------
+ * A dense layer along a token axis of any length (csrc/dense_tokens.hip): y[b, co, l] = bias[co] + sum_ci w[co, ci] x[b, ci, l] on
+ * fp32 channel-major x (B, Cin, L), y (B, Cout, L); bias may be NULL.  The contraction is the bf16-triple scheme of
+ * HDIFF_CONTRACT_BF16X3 (six piece products with i + j <= 2, fp32 accumulation) WHATEVER the contraction mode is: the caller chooses
+ * this entry or a convolution.  Any Cin, Cout, L >= 1 with Cin * L and Cout * L below 2^31.
+ *   hdiff_dense_pack_words  the 32-bit words of the pack of a GEMM with Cout outputs and Cin inputs: ceil(Cin / 16) * 3 * 64
+ *                           ceil(Cout / 64) * 8 (6 bytes per padded weight).
+ *   hdiff_dense_pack        w [Cout][Cin] (device, fp32) -> the pre-split operand wp3 (device, 16-byte aligned), K padded to 16 and the
+ *                           channels to 64 with zeros.  transposed != 0 packs w^T: a GEMM with Cin outputs and Cout inputs, the operand
+ *                           of the input gradient dx = w^T dy; its size is hdiff_dense_pack_words(Cin, Cout).
+ *   hdiff_dense_tokens      Cin, Cout are the GEMM's own (for the input gradient: Cin = rows of w, Cout = columns of w).  x values
+ *                           outside Cin x L are never multiplied (a NaN beside the tensor stays outside), nothing outside y is written.
+ * One launch each, no atomics, no workspace, a fixed accumulation order: bitwise repeatable, an image's numbers do not depend on its
+ * batch; legal under stream capture.  Additions to ABI 6.
+ * ------------------------------------------------------------------------------------------------------------------ */
+int hdiff_dense_pack_words(int Cout, int Cin, int64_t* words_out);
+int hdiff_dense_pack(const float* w, void* wp3, int Cout, int Cin, int transposed, hdiff_stream_t stream);
+int hdiff_dense_tokens(const float* x, const void* wp3, const float* bias, float* y, int B, int Cin, int Cout, int64_t L,
+                       hdiff_stream_t stream);
 /* final clip (:98) */
 int hdiff_clip(const float* x, float* y, float lo, float hi, int64_t n, hdiff_stream_t stream);
 /* out = a*x + b*y (y may be NULL): bias merges and other weight-preparation arithmetic */

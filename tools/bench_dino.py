@@ -5,7 +5,11 @@ weights) on the HIP path against the same trunk and the same taps written in pla
 power sampler.  A figure is the median over all timed calls of its arm, with the engine clock and board power sampled while that
 arm ran.
 
-  python tools/bench_dino.py --alternate 3 [--size 256] [--batch 2 16] [--reps 5] [--model dinov2_vits14]
+  python tools/bench_dino.py --alternate 3 [--size 256] [--batch 2 16] [--reps 5] [--model dinov2_vits14] [--dense conv tokens]
+
+``--dense`` names the dense-layer routes of the trunk (``dino.dense_route``) to time as arms of their own beside the torch arm, on one set
+of weights: the arms are then called ``conv`` / ``tokens`` instead of ``native``, every arm reports its fastest, median and slowest call
+and the median of each round, and ``a_over_b_median`` compares each pair.
 
 The torch arm is the yardstick, not the code under test.  No time here is a gate: there is no earlier number to hold.  One JSON line
 per measurement."""
@@ -19,6 +23,7 @@ ap.add_argument("--alternate", type=int, default=3); ap.add_argument("--size", t
 ap.add_argument("--batch", type=int, nargs="+", default=[2, 16]); ap.add_argument("--model", default="dinov2_vits14")
 ap.add_argument("--reps", type=int, default=5); ap.add_argument("--warmup", type=int, default=2)
 ap.add_argument("--mode", default=None, help="contraction mode (default: the library's)")
+ap.add_argument("--dense", nargs="+", default=None, choices=["conv", "tokens"], help="dense-layer routes to time as separate arms")
 a = ap.parse_args()
 if a.alternate < 1 or a.reps < 1:
     sys.exit("bench_dino.py: --alternate and --reps must be at least 1")
@@ -42,6 +47,16 @@ with warnings.catch_warnings():
 P = dict(trunk.named_parameters())
 HEADS, DEPTH, C = trunk.heads, trunk.depth, trunk.embed_dim
 TAPS = [(key, m) for _, key, m in native_loss.taps]
+NATIVE = [("native", native_loss)]
+if a.dense:
+    NATIVE = []
+    state = {k: v.detach().cpu() for k, v in trunk.state_dict().items()}
+    for choice in dict.fromkeys(a.dense):
+        with warnings.catch_warnings():
+            warnings.simplefilter("ignore")
+            arm = PerceptualLoss_dino(a.model, dense=choice)
+            arm.perceptual.load_dinov2(state)
+        NATIVE.append((choice, arm.to(dev)))
 
 
 def torch_features(x):
@@ -115,13 +130,21 @@ def measure(what, arms, x, y, B):
         mhz = [c["sclk_mhz_mean"] for c in clocks[name] if c.get("sclk_mhz_mean") is not None]
         watts = [c["board_power_w_mean"] for c in clocks[name] if c.get("board_power_w_mean") is not None]
         line[f"{name}_ms_median"], line[f"{name}_ms_min"] = round(t[len(t) // 2], 4), round(t[0], 4)
+        if a.dense:
+            line[f"{name}_ms_max"] = round(t[-1], 4)
+            rounds = [sorted(times[name][i * a.reps:(i + 1) * a.reps]) for i in range(a.alternate)]
+            line[f"{name}_ms_round_medians"] = [round(r[len(r) // 2], 4) for r in rounds]
         line[f"{name}_sclk_mhz_mean"] = round(sum(mhz) / len(mhz), 1) if mhz else None
         line[f"{name}_board_power_w_mean"] = round(sum(watts) / len(watts), 1) if watts else None
-    line["torch_over_native_median"] = round(line["torch_ms_median"] / line["native_ms_median"], 2)
-    vn, vt = last["native"][1].double(), last["torch"][1].double()
-    line["value_rel_diff"] = float(((vn - vt).abs() / vt.abs()).max())
-    gn, gt = last["native"][2], last["torch"][2]
-    line["grad_rel_l2_diff"] = float((gn - gt).norm() / gt.norm())
+    names = [name for name, _ in arms]
+    for i, over in enumerate(names):
+        for under in names[:i]:
+            line[f"{over}_over_{under}_median"] = round(line[f"{over}_ms_median"] / line[f"{under}_ms_median"], 2)
+    vt, gt = last["torch"][1].double(), last["torch"][2]
+    for name in names[:-1]:
+        tag = "" if name == "native" else f"{name}_"
+        line[f"{tag}value_rel_diff"] = float(((last[name][1].double() - vt).abs() / vt.abs()).max())
+        line[f"{tag}grad_rel_l2_diff"] = float((last[name][2] - gt).norm() / gt.norm())
     print(json.dumps(line), flush=True)
 
 
@@ -130,6 +153,6 @@ for B in a.batch:
     # the trainer's ranges: the prediction as y_0_pred / 255, the target in [-1, 1]
     x = (torch.rand(B, 3, a.size, a.size, generator=g) / 255.0).to(dev)
     y = (torch.rand(B, 3, a.size, a.size, generator=g) * 2 - 1).to(dev)
-    measure(f"PerceptualLoss_dino {a.model} fwd+bwd", (("native", native_loss), ("torch", torch_loss)), x, y, B)
+    measure(f"PerceptualLoss_dino {a.model} fwd+bwd", tuple(NATIVE) + (("torch", torch_loss),), x, y, B)
     del x, y
     torch.cuda.empty_cache()
