@@ -73,7 +73,7 @@ def write_res(path: str, result: Dict[str, object], keys=RES_KEYS) -> None:
 def evaluate(sampler, batches: Iterable, *, ddim_step: int, tile: Optional[int] = None, tile_overlap: Optional[int] = None,
              tile_batch: Optional[int] = None, save_dir: Optional[str] = None, collect: Optional[List[torch.Tensor]] = None,
              meter=None, solver: Optional[str] = None, spacing: Optional[str] = None, uciqe: bool = False,
-             uciqe_scale: float = 1.0, lpips=None, distribution=None) -> Dict[str, object]:
+             uciqe_scale: float = 1.0, lpips=None, distribution=None, transfer=None) -> Dict[str, object]:
     """Samples and scores a set.  ``batches`` yields ``(input, target)`` or ``(input, target, names)``: CHW images in [0, 255] as
     ``Underwater_Dataset`` / ``Atmospheric_Dataset`` produce them, batched.  Per batch: ``out = sampler(input, ddim=True,
     unconditional_guidance_scale=1, ddim_step=ddim_step, tile=...)`` (rotinas.py:907), then ``(out + 1) / 2`` is scored against
@@ -88,7 +88,16 @@ def evaluate(sampler, batches: Iterable, *, ddim_step: int, tile: Optional[int] 
     a feature callable (``quality.DinoFeatures``) from which one is made; it is updated beside the quality meter with the same
     ``(out + 1) / 2`` and ``target / 255``, the result gains ``"fd"`` and ``"kid"`` (of ALL the images the meter holds) and ``res.txt``
     two last lines, ``fd_orgin_avg:`` and ``kid_orgin_avg:``.  Without it nothing of that is constructed, launched or written.
+    ``transfer``: a ``(radius, eps)`` pair or a dict with those keys (``hdiff_amd.transfer``: guided full-resolution transfer); it needs
+    ``save_dir``, and every batch must then carry a FOURTH element, the list of its full-size uint8 ``[H_i, W_i, 3]`` originals (host
+    or device tensors, or arrays).  Each image's colour map is fitted from the batch's own ``input / 255`` (exactly what the model saw)
+    and ``clamp((out + 1) / 2, 0, 1)``, applied to its original and written to ``<save_dir>/full/<name>`` at the original's size.  The
+    scores, ``res.txt`` and the model-sized images are what they are without it; ``transfer`` without ``save_dir``, or a batch without
+    originals, raises ``ValueError`` before anything is sampled.
     Returns ``QualityMeter.compute()``'s dict."""
+    transfer = _transfer_settings(transfer)
+    if transfer is not None and save_dir is None:
+        raise ValueError("evaluate: transfer= writes full-size images and needs save_dir=")
     if distribution is not None and not isinstance(distribution, quality.DistributionMeter):
         distribution = quality.DistributionMeter(distribution)
     if meter is None:
@@ -99,6 +108,8 @@ def evaluate(sampler, batches: Iterable, *, ddim_step: int, tile: Optional[int] 
     dev = _device_of(sampler)
     if save_dir is not None:
         os.makedirs(save_dir, exist_ok=True)
+        if transfer is not None:
+            os.makedirs(os.path.join(save_dir, "full"), exist_ok=True)
     tile_kw = {} if tile is None else dict(tile=tile, tile_overlap=tile_overlap, tile_batch=tile_batch)
     tile_kw.update({k: v for k, v in (("solver", solver), ("spacing", spacing)) if v is not None})
     done = 0
@@ -106,6 +117,7 @@ def evaluate(sampler, batches: Iterable, *, ddim_step: int, tile: Optional[int] 
         for batch in batches:
             inp, target = batch[0], batch[1]
             names = list(batch[2]) if len(batch) > 2 else [f"{done + i:05d}.png" for i in range(int(inp.shape[0]))]
+            originals = _originals(batch, int(inp.shape[0])) if transfer is not None else None
             inp = (inp if dev is None else inp.to(dev)).float()
             target = (target if dev is None else target.to(dev)).float()
             out = sampler(inp, ddim=True, unconditional_guidance_scale=1, ddim_step=ddim_step, **tile_kw)
@@ -117,6 +129,8 @@ def evaluate(sampler, batches: Iterable, *, ddim_step: int, tile: Optional[int] 
                 collect.append(out)
             if save_dir is not None:
                 _save_batch(pred01, names, save_dir)
+            if transfer is not None:
+                _save_full(inp, pred01, originals, names, os.path.join(save_dir, "full"), transfer)
             done += int(inp.shape[0])
     result = meter.compute()
     if distribution is not None:
@@ -132,6 +146,43 @@ def evaluate(sampler, batches: Iterable, *, ddim_step: int, tile: Optional[int] 
     return result
 
 
+def _transfer_settings(transfer):
+    """``evaluate``'s ``transfer=`` as a checked ``(radius, eps)``, or None."""
+    if transfer is None:
+        return None
+    from ..transfer import transfer_settings
+    if isinstance(transfer, dict):
+        unknown = set(transfer) - {"radius", "eps"}
+        if unknown:
+            raise ValueError(f"evaluate: transfer= has unknown keys {sorted(unknown)}; it takes 'radius' and 'eps'")
+        return transfer_settings(transfer.get("radius", 8), transfer.get("eps", 1e-3))
+    if not isinstance(transfer, (tuple, list)) or len(transfer) != 2:
+        raise ValueError(f"evaluate: transfer= must be a (radius, eps) pair or a dict, got {transfer!r}")
+    return transfer_settings(transfer[0], transfer[1])
+
+
+def _originals(batch, count: int) -> list:
+    """The fourth element of a batch under ``transfer=``: one uint8 [H, W, 3] image per sample."""
+    if len(batch) < 4 or batch[3] is None:
+        raise ValueError("evaluate: with transfer= every batch is (input, target, names, originals); this one has no originals")
+    originals = [torch.as_tensor(o) for o in batch[3]]
+    if len(originals) != count:
+        raise ValueError(f"evaluate: the batch holds {count} images and {len(originals)} originals")
+    for o in originals:
+        if o.dtype != torch.uint8 or o.dim() != 3 or o.shape[2] != 3:
+            raise ValueError(f"evaluate: an original has dtype {o.dtype} and shape {tuple(o.shape)}; it must be a uint8 [H, W, 3] image")
+    return originals
+
+
+def _save_full(inp: torch.Tensor, pred01: torch.Tensor, originals: list, names: Sequence[str], full_dir: str, settings) -> None:
+    from PIL import Image
+    from .. import transfer as T
+    coef = T.guided_fit(inp / 255, pred01.clamp(0, 1), radius=settings[0], eps=settings[1])
+    for i, (orig, name) in enumerate(zip(originals, names)):
+        out = T.guided_apply(coef[i], orig.to(inp.device))
+        Image.fromarray(out.cpu().numpy()).save(os.path.join(full_dir, name))
+
+
 def _cfg(config, key: str, *default):
     if isinstance(config, dict):
         if key in config:
@@ -143,13 +194,18 @@ def _cfg(config, key: str, *default):
     raise KeyError(f"the configuration has no '{key}'")
 
 
-def _batched(dataset, batch_size: int) -> Iterator:
-    """(input [B,3,H,W], target [B,3,H,W], file names of the degraded images) in order, the last batch as short as it comes."""
+def _batched(dataset, batch_size: int, full: bool = False) -> Iterator:
+    """(input [B,3,H,W], target [B,3,H,W], file names of the degraded images) in order, the last batch as short as it comes.  ``full``
+    adds a fourth element: the degraded files at their own size, uint8 [H_i, W_i, 3] host tensors (``datasets.load_image``)."""
     for start in range(0, len(dataset), batch_size):
         idx = range(start, min(start + batch_size, len(dataset)))
         items = [dataset[i] for i in idx]
-        yield (torch.stack([it[0] for it in items]), torch.stack([it[1] for it in items]),
-               [os.path.basename(dataset.paths_a[i]) for i in idx])
+        batch = (torch.stack([it[0] for it in items]), torch.stack([it[1] for it in items]),
+                 [os.path.basename(dataset.paths_a[i]) for i in idx])
+        if full:
+            from ..datasets import load_image
+            batch = batch + ([torch.from_numpy(load_image(dataset.paths_a[i]).copy()) for i in idx],)
+        yield batch
 
 
 def _run_sets(config, task: str) -> Dict[str, Dict[str, object]]:
@@ -197,11 +253,14 @@ def _run_sets(config, task: str) -> Dict[str, Dict[str, object]]:
         if _cfg(config, "fd_weights", None) is not None:
             trunk.load_dinov2(torch.load(_cfg(config, "fd_weights"), map_location="cpu"))
         features = quality.DinoFeatures(trunk).to(device)
+    full = bool(_cfg(config, "full_resolution", False))
+    if full:
+        extra["transfer"] = (_cfg(config, "transfer_radius", 8), _cfg(config, "transfer_eps", 1e-3))
     results = {}
     for name, data in sets:
         if features is not None:      # one meter per set; a DistributionMeter from the configuration goes on filling across both
             extra["distribution"] = features if isinstance(features, quality.DistributionMeter) else quality.DistributionMeter(features)
-        results[name] = evaluate(sampler, _batched(data, int(_cfg(config, "batch_size"))), ddim_step=_cfg(config, "ddim_step"),
+        results[name] = evaluate(sampler, _batched(data, int(_cfg(config, "batch_size")), full), ddim_step=_cfg(config, "ddim_step"),
                                  tile=_cfg(config, "tile", None), tile_overlap=_cfg(config, "tile_overlap", None),
                                  tile_batch=_cfg(config, "tile_batch", None), save_dir=os.path.join(base, name),
                                  solver=_cfg(config, "solver", None), spacing=_cfg(config, "spacing", None), **extra)
@@ -220,13 +279,16 @@ def test(config, epoch=None) -> Dict[str, Dict[str, object]]:
     ``distribution`` (a feature callable such as ``quality.DinoFeatures``, or a ``quality.DistributionMeter``) or ``fd_model``
     (``"dinov2_vits14"`` / ``vitb14`` / ``vitl14``) with ``fd_weights`` (the path of the hub state dict, loaded with ``load_dinov2``) and ``fd_dense`` (``"conv"``, the default, or
     ``"tokens"``: the trunk's dense-layer route;
-    the images must fit the trunk: ``H - 4`` and ``W - 4`` multiples of 14; absent: no set-level scores, ``res.txt`` as before).
+    the images must fit the trunk: ``H - 4`` and ``W - 4`` multiples of 14; absent: no set-level scores, ``res.txt`` as before),
+    ``full_resolution`` (bool: every degraded file is also enhanced at its OWN size by guided transfer of the model-sized result and
+    written to ``<set>/full/<name>``, ``evaluate``'s ``transfer=``) with ``transfer_radius`` (default 8) and ``transfer_eps`` (default
+    1e-3; neither is backed by an image-quality figure; absent: nothing of it is loaded, launched or written).
     ``epoch`` is accepted and unused, as in the reference.  Returns ``{set name: evaluate()'s dict}``."""
     return _run_sets(config, "test")
 
 
 def inference(config, epoch=None) -> Dict[str, Dict[str, object]]:
     """``rotinas.inference(config, epoch)`` (``:1086``, ``Main.py --state eval``): the same loop on the validation split
-    (``task="val"``) of both sets, with ``test``'s keys, results under the same ``<result_root>/<checkpoint file>/<set>/``.  Every image
+    (``task="val"``) of both sets, with ``test``'s keys (``full_resolution``, ``transfer_radius``, ``transfer_eps`` among them), results under the same ``<result_root>/<checkpoint file>/<set>/``.  Every image
     is scored, under the file name of its degraded image, and the means are ``sum / len``."""
     return _run_sets(config, "val")

@@ -784,6 +784,43 @@ int hdiff_dense_pack_words(int Cout, int Cin, int64_t* words_out);
 int hdiff_dense_pack(const float* w, void* wp3, int Cout, int Cin, int transposed, hdiff_stream_t stream);
 int hdiff_dense_tokens(const float* x, const void* wp3, const float* bias, float* y, int B, int Cin, int Cout, int64_t L,
                        hdiff_stream_t stream);
+/* ------------------------------------------------------------------------------------------------------------------
+ * Guided full-resolution transfer (csrc/transfer.hip; tests/_transfer_def.py is the definition; hdiff_amd/transfer.py is the caller):
+ * the model's 256 x 256 result decides what the enhancement IS, as one affine colour map per pixel neighbourhood (He et al.'s guided
+ * filter with a colour guide, "fast" form), and the smoothly upsampled map is applied to the file at its own size.
+ *   hdiff_resample_workspace  bytes of `scratch` for hdiff_resample_u8 at (H, W) -> (h, w): the [H][w][3] intermediate in double
+ *   hdiff_resample_u8         img uint8 [H][W][3] (interleaved) -> out float [3][h][w] in [0, 255].  A triangle filter of support
+ *                             max(in / out, 1) per axis, horizontal pass first: output o has centre c = (o + 0.5) in / out, taps k from
+ *                             max(int(c - support + 0.5), 0) to min(int(c + support + 0.5), in) - 1, weights max(0, 1 - |(k + 0.5 - c) /
+ *                             support|) normalised to sum 1 in double, products added in tap order in double, one rounding to fp32
+ *                             (Pillow's BILINEAR reduce without its 8-bit rounding between the passes).  Equal sizes copy the bytes.
+ *                             H, W in [1, 16384]; h, w in [1, 4096].  Two launches
+ *   hdiff_guided_workspace    bytes of `scratch` for hdiff_guided_fit at (N, h, w): 21 + 12 double planes per image
+ *   hdiff_guided_fit          I, p: float [N][3][h][w] (guide and target, [0, 1] units) -> coef float [N][12][h][w], planes a[0][0..2],
+ *                             a[1][0..2], a[2][0..2], b[0..2].  Window of (y, x): [y-r, y+r] x [x-r, x+r] clipped to the image; a mean is
+ *                             the sum over it divided by its pixel count, the sum separable (x, then y) and DIRECT, in index order.
+ *                             Sigma = mean(I I^T) - mean(I) mean(I)^T + eps U, C[j][c] = mean(I_j p_c) - mean(I_j) mean(p_c), a[c] =
+ *                             Sigma^-1 C[:, c] (Cholesky), b[c] = mean(p_c) - a[c] . mean(I); then the same window mean of the twelve
+ *                             values.  Double from the loads to the one final rounding.  N in [1, 65535]; h, w in [1, 4096]; r in
+ *                             [1, 128]; eps finite and > 0.  Four launches
+ *   hdiff_guided_apply_f32    coef [N][12][h][w], full and out float [N][3][H][W]: out_c = A_c0 F_0 + A_c1 F_1 + A_c2 F_2 + b_c, each of
+ *                             the twelve planes interpolated at sy = clamp((Y + 0.5) h / H - 0.5, 0, h - 1), y0 = floor(sy), y1 =
+ *                             min(y0 + 1, h - 1), fy = sy - y0 and the same in x: along x at both rows, then along y.  clamp != 0: to
+ *                             [0, 1].  fp32; the tap is taken in integers, its weight from the integer remainder.  One launch
+ *   hdiff_guided_apply_u8     ONE image: coef [12][h][w], full and out uint8 [H][W][3]; F = (float)byte / 255.0f, out =
+ *                             rintf(255 * clamp(q, 0, 1)), half to even.  Rows may start on any byte.  One launch
+ *                             Both: h, w in [1, 4096]; H, W in [1, 16384]; H * W <= 2^30; (f32) N in [1, 65535].  out == full is allowed.
+ * A non-finite input value spoils its own image only.  No allocation, no synchronisation, no atomics: legal under stream capture,
+ * bitwise repeatable; an image's numbers do not depend on N or on its place in the batch.  Additions to ABI 6.
+ * ------------------------------------------------------------------------------------------------------------------ */
+int hdiff_resample_workspace(int H, int W, int h, int w, int64_t* bytes);
+int hdiff_resample_u8(const uint8_t* img, int H, int W, float* out, int h, int w, void* scratch, hdiff_stream_t stream);
+int hdiff_guided_workspace(int N, int h, int w, int64_t* bytes);
+int hdiff_guided_fit(const float* I, const float* p, int N, int h, int w, int r, double eps, float* coef, void* scratch,
+                     hdiff_stream_t stream);
+int hdiff_guided_apply_f32(const float* coef, int h, int w, const float* full, float* out, int N, int H, int W, int clamp,
+                           hdiff_stream_t stream);
+int hdiff_guided_apply_u8(const float* coef, int h, int w, const uint8_t* full, uint8_t* out, int H, int W, hdiff_stream_t stream);
 /* final clip (:98) */
 int hdiff_clip(const float* x, float* y, float lo, float hi, int64_t n, hdiff_stream_t stream);
 /* out = a*x + b*y (y may be NULL): bias merges and other weight-preparation arithmetic */
