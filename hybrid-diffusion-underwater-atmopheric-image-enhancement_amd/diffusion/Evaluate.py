@@ -22,6 +22,12 @@ Deliberate deviations from the reference:
   * UIQM's parts are ``getUIQM``'s own (``quality.uiqm``); the reference reports the parts of ``nmetrics`` beside ``getUIQM``'s total.
   * images are written with Pillow, rounded to the nearest integer (``cv2.imwrite`` of a float image in the reference, which also
     swaps the red and blue channels on the way).
+  * NIQE (``niqe=``; Mittal, Soundararajan, Bovik 2013) is not in the reference at all: it is the no-reference score for what UIQM and
+    UCIQE, both underwater colour measures, say nothing about -- the atmospheric sets, and the full-size results of ``transfer=``,
+    which have no target.  The pristine model comes from the caller (``quality.NIQEModel``; ``fit_niqe`` fits one on a set's targets);
+    agreement with the authors' MATLAB release is unpinned, and rows with a non-finite feature leave mean and covariance alike
+    (the release drops them per column for the mean).  ``res.txt`` then ends with ``niqe_orgin_avg:`` and, with ``transfer=``,
+    ``niqe_full_orgin_avg:``.
   * ``test`` scores every image of a set: the reference's loader drops the last incomplete batch.  Its file names are those of the
     degraded images.  ``inference`` does the same on the validation split, and its means are ``sum / len``: the reference's
     ``(sum + 1) / (len + 1)`` (``:1204-1211``) is not copied.
@@ -35,7 +41,8 @@ import torch
 
 from .. import quality
 
-__all__ = ["evaluate", "test", "inference", "RES_KEYS", "RES_KEYS_UCIQE", "RES_KEY_LPIPS", "RES_KEYS_DISTRIBUTION"]
+__all__ = ["evaluate", "test", "inference", "fit_niqe", "RES_KEYS", "RES_KEYS_UCIQE", "RES_KEY_LPIPS", "RES_KEYS_DISTRIBUTION",
+           "RES_KEY_NIQE", "RES_KEY_NIQE_FULL"]
 
 # res.txt: the reference's key for each measured score, in the reference's order (rotinas.py:967-982)
 RES_KEYS = (("psnr_orgin_avg:", "psnr"), ("ssim_orgin_avg:", "ssim"), ("uiqm_orgin_avg:", "uiqm"), ("uism_orgin_avg:", "uism"),
@@ -46,6 +53,9 @@ RES_KEYS_UCIQE = RES_KEYS[:3] + (("uciqe_orgin_avg:", "uciqe"),) + RES_KEYS[3:]
 RES_KEY_LPIPS = ("lpips_orgin_avg:", "lpips")
 # with the set-level scores: two last lines, behind LPIPS's where both are on
 RES_KEYS_DISTRIBUTION = (("fd_orgin_avg:", "fd"), ("kid_orgin_avg:", "kid"))
+# with NIQE: one last line, behind all of the above; with transfer= as well, one more for the full-size results
+RES_KEY_NIQE = ("niqe_orgin_avg:", "niqe")
+RES_KEY_NIQE_FULL = ("niqe_full_orgin_avg:", "niqe_full")
 
 
 def _device_of(sampler) -> Optional[torch.device]:
@@ -73,7 +83,7 @@ def write_res(path: str, result: Dict[str, object], keys=RES_KEYS) -> None:
 def evaluate(sampler, batches: Iterable, *, ddim_step: int, tile: Optional[int] = None, tile_overlap: Optional[int] = None,
              tile_batch: Optional[int] = None, save_dir: Optional[str] = None, collect: Optional[List[torch.Tensor]] = None,
              meter=None, solver: Optional[str] = None, spacing: Optional[str] = None, uciqe: bool = False,
-             uciqe_scale: float = 1.0, lpips=None, distribution=None, transfer=None) -> Dict[str, object]:
+             uciqe_scale: float = 1.0, lpips=None, distribution=None, transfer=None, niqe=None) -> Dict[str, object]:
     """Samples and scores a set.  ``batches`` yields ``(input, target)`` or ``(input, target, names)``: CHW images in [0, 255] as
     ``Underwater_Dataset`` / ``Atmospheric_Dataset`` produce them, batched.  Per batch: ``out = sampler(input, ddim=True,
     unconditional_guidance_scale=1, ddim_step=ddim_step, tile=...)`` (rotinas.py:907), then ``(out + 1) / 2`` is scored against
@@ -94,12 +104,24 @@ def evaluate(sampler, batches: Iterable, *, ddim_step: int, tile: Optional[int] 
     and ``clamp((out + 1) / 2, 0, 1)``, applied to its original and written to ``<save_dir>/full/<name>`` at the original's size.  The
     scores, ``res.txt`` and the model-sized images are what they are without it; ``transfer`` without ``save_dir``, or a batch without
     originals, raises ``ValueError`` before anything is sampled.
+    ``niqe``: a ``quality.NIQEModel`` or the path of one (``NIQEModel.load``); the default meter also scores NIQE of ``(out + 1) / 2``
+    at the model's ``patch`` (a ``meter`` passed in must report "niqe" itself), the result gains ``"niqe"`` (the mean over the images
+    whose score is defined) and ``"niqe_undefined"``, and ``res.txt`` a last line ``niqe_orgin_avg:``.  A model-sized image smaller than
+    ``patch`` raises ``ValueError``.  With ``transfer=`` as well every full-size result is scored once, at its own size, before it is
+    written (one synchronisation per image, beside the one of the file): the result gains ``"niqe_full"`` (the same mean),
+    ``"niqe_full_per_image"`` and ``"niqe_full_undefined"``, and ``res.txt`` one more line, ``niqe_full_orgin_avg:``.  Without it
+    nothing of that is loaded, launched or written.
     Returns ``QualityMeter.compute()``'s dict."""
     transfer = _transfer_settings(transfer)
     if transfer is not None and save_dir is None:
         raise ValueError("evaluate: transfer= writes full-size images and needs save_dir=")
     if distribution is not None and not isinstance(distribution, quality.DistributionMeter):
         distribution = quality.DistributionMeter(distribution)
+    if niqe is not None and not isinstance(niqe, quality.NIQEModel):
+        niqe = quality.NIQEModel.load(niqe)
+    full_scores: List[float] = []
+    if meter is None and niqe is not None:
+        meter = quality.QualityMeter(uciqe=bool(uciqe), uciqe_scale=uciqe_scale, lpips=lpips, niqe=niqe)
     if meter is None:
         if lpips is not None:
             meter = quality.QualityMeter(uciqe=bool(uciqe), uciqe_scale=uciqe_scale, lpips=lpips)
@@ -130,18 +152,25 @@ def evaluate(sampler, batches: Iterable, *, ddim_step: int, tile: Optional[int] 
             if save_dir is not None:
                 _save_batch(pred01, names, save_dir)
             if transfer is not None:
-                _save_full(inp, pred01, originals, names, os.path.join(save_dir, "full"), transfer)
+                full_scores += _save_full(inp, pred01, originals, names, os.path.join(save_dir, "full"), transfer, niqe)
             done += int(inp.shape[0])
     result = meter.compute()
     if distribution is not None:
         scores = distribution.compute()
         result["fd"], result["kid"] = scores["fd"], scores["kid"]
+    if niqe is not None and transfer is not None:
+        defined = [v for v in full_scores if v == v and abs(v) != float("inf")]
+        result["niqe_full"] = sum(defined) / len(defined) if defined else float("nan")
+        result["niqe_full_per_image"] = list(full_scores)
+        result["niqe_full_undefined"] = len(full_scores) - len(defined)
     if save_dir is not None:
         keys = RES_KEYS_UCIQE if uciqe else RES_KEYS
         if lpips is not None:
             keys = keys + (RES_KEY_LPIPS,)
         if distribution is not None:
             keys = keys + RES_KEYS_DISTRIBUTION
+        if niqe is not None:
+            keys = keys + (RES_KEY_NIQE,) + ((RES_KEY_NIQE_FULL,) if transfer is not None else ())
         write_res(os.path.join(save_dir, "res.txt"), result, keys)
     return result
 
@@ -174,13 +203,19 @@ def _originals(batch, count: int) -> list:
     return originals
 
 
-def _save_full(inp: torch.Tensor, pred01: torch.Tensor, originals: list, names: Sequence[str], full_dir: str, settings) -> None:
+def _save_full(inp: torch.Tensor, pred01: torch.Tensor, originals: list, names: Sequence[str], full_dir: str, settings,
+               niqe=None) -> List[float]:
+    """Writes the full-size results; with a ``quality.NIQEModel`` returns the NIQE of each, taken from the uint8 image that is written."""
     from PIL import Image
     from .. import transfer as T
     coef = T.guided_fit(inp / 255, pred01.clamp(0, 1), radius=settings[0], eps=settings[1])
+    scores: List[float] = []
     for i, (orig, name) in enumerate(zip(originals, names)):
         out = T.guided_apply(coef[i], orig.to(inp.device))
+        if niqe is not None:
+            scores.append(float(quality.niqe(out.permute(2, 0, 1).unsqueeze(0).float() / 255, niqe)[0]))
         Image.fromarray(out.cpu().numpy()).save(os.path.join(full_dir, name))
+    return scores
 
 
 def _cfg(config, key: str, *default):
@@ -256,6 +291,11 @@ def _run_sets(config, task: str) -> Dict[str, Dict[str, object]]:
     full = bool(_cfg(config, "full_resolution", False))
     if full:
         extra["transfer"] = (_cfg(config, "transfer_radius", 8), _cfg(config, "transfer_eps", 1e-3))
+    niqe_model = _cfg(config, "niqe_model", None)
+    if _cfg(config, "niqe", False) or niqe_model is not None:
+        if niqe_model is None:
+            raise ValueError("the configuration asks for niqe and names no 'niqe_model': fit one with fit_niqe, or load the release's")
+        extra["niqe"] = niqe_model if isinstance(niqe_model, quality.NIQEModel) else quality.NIQEModel.load(niqe_model)
     results = {}
     for name, data in sets:
         if features is not None:      # one meter per set; a DistributionMeter from the configuration goes on filling across both
@@ -282,7 +322,10 @@ def test(config, epoch=None) -> Dict[str, Dict[str, object]]:
     the images must fit the trunk: ``H - 4`` and ``W - 4`` multiples of 14; absent: no set-level scores, ``res.txt`` as before),
     ``full_resolution`` (bool: every degraded file is also enhanced at its OWN size by guided transfer of the model-sized result and
     written to ``<set>/full/<name>``, ``evaluate``'s ``transfer=``) with ``transfer_radius`` (default 8) and ``transfer_eps`` (default
-    1e-3; neither is backed by an image-quality figure; absent: nothing of it is loaded, launched or written).
+    1e-3; neither is backed by an image-quality figure; absent: nothing of it is loaded, launched or written),
+    ``niqe`` (bool) with ``niqe_model`` (the path of a ``quality.NIQEModel`` file, ``.npz`` or the release's ``.mat``, or a model;
+    ``evaluate``'s ``niqe=``: NIQE of every result at the model's ``patch``, and of every full-size result under ``full_resolution``;
+    absent: no NIQE, ``res.txt`` as before).
     ``epoch`` is accepted and unused, as in the reference.  Returns ``{set name: evaluate()'s dict}``."""
     return _run_sets(config, "test")
 
@@ -292,3 +335,35 @@ def inference(config, epoch=None) -> Dict[str, Dict[str, object]]:
     (``task="val"``) of both sets, with ``test``'s keys (``full_resolution``, ``transfer_radius``, ``transfer_eps`` among them), results under the same ``<result_root>/<checkpoint file>/<set>/``.  Every image
     is scored, under the file name of its degraded image, and the means are ``sum / len``."""
     return _run_sets(config, "val")
+
+
+def fit_niqe(config, *, out: str, split: str = "train", side: str = "target", patch: int = 96, sharp_threshold: float = 0.75,
+             quantize: bool = True):
+    """Fits NIQE's pristine model (``quality.NIQEModel.fit``) on the images of one side of ``config.underwater_data_name`` and
+    ``config.atmospheric_data_name``, opened the way ``test`` opens them (``dataset_root``, ``transforms``, ``batch_size``,
+    ``device_list``) with ``task=split``, and writes it to ``out`` (an ``.npz``).  ``side``: ``"target"`` (the clean images: what a
+    pristine model is meant to describe) or ``"input"``.  A set named ``None`` is left out.  Returns the model."""
+    from ..datasets import Atmospheric_Dataset, Underwater_Dataset
+    if side not in ("target", "input"):
+        raise ValueError(f"fit_niqe: side = {side!r}; 'target' or 'input'")
+    root = _cfg(config, "dataset_root", None)
+    transforms = _cfg(config, "transforms", None)
+    devices = _cfg(config, "device_list", None)
+    device = torch.device(devices[0] if devices else "cuda:0")
+    sets = []
+    for key, cls in (("underwater_data_name", Underwater_Dataset), ("atmospheric_data_name", Atmospheric_Dataset)):
+        name = _cfg(config, key, None)
+        if name is not None:
+            sets.append(cls(name, transforms=transforms, task=split, root=root.get(name) if isinstance(root, dict) else root))
+    if not sets:
+        raise ValueError("fit_niqe: the configuration names no set")
+    pick = 1 if side == "target" else 0
+
+    def images():
+        for data in sets:
+            for batch in _batched(data, int(_cfg(config, "batch_size", 8))):
+                yield batch[pick].to(device).float() / 255
+
+    model = quality.NIQEModel.fit(images(), patch=patch, sharp_threshold=sharp_threshold, quantize=quantize)
+    model.save(out)
+    return model

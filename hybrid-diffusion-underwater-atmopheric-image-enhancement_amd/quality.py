@@ -23,6 +23,13 @@ from the caller -- a torchvision ``vgg16`` state dict and the five ``lin`` layer
 Scaling constants, taps and formula were written from memory of that package: agreement with it is unpinned.  The other parts of ``nmetrics`` (its own UIQM variant) and the 8-bit OpenCV
 ``uw_metrics.uciqe``, which the reference never calls, stay on the host.  There is no CPU fallback: CPU tensors are refused.
 
+``niqe`` is the no-reference NIQE (Mittal, Soundararajan, Bovik 2013; ``csrc/niqe.hip``; ``tests/_niqe_def.py`` is the definition the
+kernels are held to): the distance between the Gaussian fitted to the 36 AGGD features of an image's blocks and a "pristine" model
+(``NIQEModel``: fitted on the device over clean images, or loaded).  It is the score for what UIQM and UCIQE, both underwater colour
+measures, do not cover.  Agreement with the authors' MATLAB release is unpinned; rows with a non-finite feature (blocks over a
+constant area) leave mean and covariance alike, where the release drops them per column for the mean, and the pseudo-inverse is
+numpy's on the host.
+
 The scores above are per image.  ``DistributionMeter`` scores a SET of outputs against a set of targets (``csrc/distribution.hip``): the
 Frechet distance between the Gaussians fitted to the two sets' features, and KID, the unbiased estimate of the squared maximum mean
 discrepancy under the kernel ``(x.y / d + 1)^3`` (Binkowski et al. 2018, "Demystifying MMD GANs").  With ``DinoFeatures`` the features
@@ -45,11 +52,14 @@ from . import _capi
 from . import engine as E
 
 __all__ = ["psnr_ssim", "uiqm", "uciqe", "LPIPS", "QualityMeter", "moments", "kid_sums", "kid", "frechet_from_moments", "DinoFeatures",
-           "DistributionMeter"]
+           "DistributionMeter", "niqe_features", "NIQEModel", "niqe_from_moments", "niqe"]
 
 COLUMNS = ("psnr", "ssim", "uiqm", "uicm", "uism", "uiconm")      # the columns of QualityMeter's per-image rows
 UCIQE_COLUMNS = ("uciqe", "uciqe_sc", "uciqe_conl", "uciqe_us")   # the four more of QualityMeter(uciqe=True)
 LPIPS_COLUMNS = ("lpips",)                                        # the last one of QualityMeter(lpips=metric)
+NIQE_COLUMNS = ("niqe",)                                          # the last one of QualityMeter(niqe=model), behind LPIPS's
+NIQE_ROW = 36                                                     # features of a block: 18 per scale
+NIQE_MOMENTS = NIQE_ROW + NIQE_ROW * NIQE_ROW + 1                 # mean, covariance, count of valid rows: per image
 
 
 def _image_batch(t: torch.Tensor, name: str) -> torch.Tensor:
@@ -233,9 +243,15 @@ class QualityMeter:
     ``UCIQE_COLUMNS`` = (uciqe, uciqe_sc, uciqe_conl, uciqe_us) of ``clip(pred, 0, 1) * uciqe_scale`` (``quality.uciqe``); without it
     the rows, the launches and ``compute``'s dict are those of the six columns alone.  With ``lpips=metric`` (an ``LPIPS``) every row
     gains ``LPIPS_COLUMNS`` = (lpips,) as its LAST column, behind UCIQE's where both are on: the distance of the prediction from its
-    target, NaN for the images of an ``update`` without one, and its mean is taken like PSNR's."""
+    target, NaN for the images of an ``update`` without one, and its mean is taken like PSNR's.  With ``niqe=model`` (a ``NIQEModel``)
+    every row gains ``NIQE_COLUMNS`` = (niqe,) as its LAST column, behind LPIPS's where both are on: ``update`` leaves the
+    ``NIQE_MOMENTS`` doubles of each image (``hdiff_niqe_moments``) in a second device bank and never synchronises, ``compute`` copies
+    that bank once and finishes every score on the host (``niqe_from_moments``).  The mean of the column is taken over the images
+    whose score is finite; ``"niqe_undefined"`` counts the others (fewer than two valid blocks, a NaN pixel).  An image smaller than
+    the model's ``patch`` is refused before a row is written.  Without ``niqe=`` nothing of it is allocated, launched or reported."""
 
-    def __init__(self, capacity: int = 64, *, uciqe: bool = False, uciqe_scale: float = 1.0, lpips: Optional[LPIPS] = None):
+    def __init__(self, capacity: int = 64, *, uciqe: bool = False, uciqe_scale: float = 1.0, lpips: Optional[LPIPS] = None,
+                 niqe: Optional["NIQEModel"] = None):
         self._capacity = max(1, int(capacity))
         self._uciqe, self._uciqe_scale = bool(uciqe), float(uciqe_scale)
         if lpips is not None and not isinstance(lpips, LPIPS):
@@ -244,6 +260,12 @@ class QualityMeter:
         self.columns = COLUMNS + UCIQE_COLUMNS if self._uciqe else COLUMNS
         if lpips is not None:
             self.columns = self.columns + LPIPS_COLUMNS
+        if niqe is not None and not isinstance(niqe, NIQEModel):
+            raise TypeError(f"QualityMeter: niqe must be a quality.NIQEModel, got {type(niqe).__name__}")
+        self._niqe = niqe
+        if niqe is not None:
+            self.columns = self.columns + NIQE_COLUMNS
+        self._niqe_bank: Optional[torch.Tensor] = None   # [capacity, NIQE_MOMENTS] float64 beside the rows
         self._rows: Optional[torch.Tensor] = None      # [capacity, 6 or 10] float64 on the device of the first update
         self._n = 0
         self._updates = []                             # (first row, rows, had a target): host bookkeeping
@@ -256,6 +278,8 @@ class QualityMeter:
             while self._capacity < extra:
                 self._capacity *= 2
             self._rows = torch.empty(self._capacity, len(self.columns), dtype=torch.float64, device=dev)
+            if self._niqe is not None:
+                self._niqe_bank = torch.empty(self._capacity, NIQE_MOMENTS, dtype=torch.float64, device=dev)
             return
         if self._rows.device != dev:
             raise RuntimeError(f"hdiff: QualityMeter holds rows on {self._rows.device}, the update is on {dev}")
@@ -265,6 +289,10 @@ class QualityMeter:
             grown = torch.empty(self._capacity, len(self.columns), dtype=torch.float64, device=dev)
             grown[:self._n].copy_(self._rows[:self._n])
             self._rows = grown
+            if self._niqe is not None:
+                bank = torch.empty(self._capacity, NIQE_MOMENTS, dtype=torch.float64, device=dev)
+                bank[:self._n].copy_(self._niqe_bank[:self._n])
+                self._niqe_bank = bank
 
     def update(self, pred01: torch.Tensor, target01: Optional[torch.Tensor] = None) -> None:
         pred = _image_batch(pred01, "pred01")
@@ -274,6 +302,8 @@ class QualityMeter:
         if self._lpips is not None and target is not None:
             self._lpips._checked(pred, target)                    # a size LPIPS cannot take is refused before a row is written
         N, _, H, W = (int(v) for v in pred.shape)
+        if self._niqe is not None:
+            _niqe_blocks(H, W, self._niqe.patch)                  # an image smaller than patch likewise
         dev = pred.device
         self._reserve(N, dev)
         with torch.cuda.device(dev):
@@ -294,12 +324,17 @@ class QualityMeter:
                 rows[:, 6].copy_(four[:, 3])
                 rows[:, 7:10].copy_(four[:, 0:3])
             if self._lpips is not None:
+                at = len(self.columns) - 1 - (1 if self._niqe is not None else 0)
                 if target is not None:
                     dist = torch.empty(N, dtype=torch.float64, device=dev)
                     self._lpips._into(pred, target, dist)
-                    rows[:, -1].copy_(dist)
+                    rows[:, at].copy_(dist)
                 else:
-                    rows[:, -1].fill_(float("nan"))
+                    rows[:, at].fill_(float("nan"))
+            if self._niqe is not None:
+                feats, sharp = _niqe_features_checked(pred, self._niqe.patch, self._niqe.quantize)
+                _niqe_moments_into(feats, sharp, 0.0, self._niqe_bank[self._n:self._n + N])
+                rows[:, -1].fill_(float("nan"))                   # filled by compute(), on the host
         self._updates.append((self._n, N, target is not None))
         self._n += N
 
@@ -307,8 +342,11 @@ class QualityMeter:
         """{"n", "psnr", "ssim", "uiqm", "uicm", "uism", "uiconm"} as float means over the images (an infinite PSNR makes the mean
         infinite, as the reference's ``sum(list) / len(list)`` does) and "per_image", the ``[n, 6]`` float64 rows; with ``uciqe=True``
         also the means of ``UCIQE_COLUMNS``, and "per_image" is ``[n, 10]``; with ``lpips=`` also "lpips" (over the images that had a
-        target) and one more column."""
+        target) and one more column; with ``niqe=`` also "niqe" (over the images whose score is finite), "niqe_undefined" (how many
+        are not) and one more column."""
         per = np.empty((0, len(self.columns))) if self._rows is None else self._rows[:self._n].cpu().numpy()
+        if self._niqe is not None and self._n:
+            per[:, -1] = _niqe_scores(self._niqe, self._niqe_bank[:self._n].cpu().numpy())
         paired = np.zeros(self._n, dtype=bool)
         for start, count, has_target in self._updates:
             paired[start:start + count] = has_target
@@ -316,6 +354,11 @@ class QualityMeter:
         for j, k in enumerate(self.columns):
             col = per[paired, j] if k in ("psnr", "ssim", "lpips") else per[:, j]
             res[k] = float(np.sum(col) / col.size) if col.size else float("nan")
+        if self._niqe is not None:
+            col = per[:, -1]
+            defined = col[np.isfinite(col)]
+            res["niqe"] = float(np.sum(defined) / defined.size) if defined.size else float("nan")
+            res["niqe_undefined"] = int(col.size - defined.size)
         res["per_image"] = per
         return res
 
@@ -525,3 +568,183 @@ class DistributionMeter:
         if np.isfinite(sums).all() and np.isfinite(fd):
             res["fd"], res["kid"] = fd, _kid_from_sums(sums, n, m)
         return res
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# NIQE: the no-reference score (csrc/niqe.hip; tests/_niqe_def.py is the definition)
+# ----------------------------------------------------------------------------------------------------------------------
+def _niqe_patch(patch) -> int:
+    if isinstance(patch, bool) or int(patch) != patch or int(patch) % 2 or not 8 <= int(patch) <= 512:
+        raise ValueError(f"niqe: patch = {patch!r}; the block side must be an even integer between 8 and 512")
+    return int(patch)
+
+
+def _niqe_blocks(H: int, W: int, patch: int) -> int:
+    """Whole blocks of ``patch`` x ``patch`` in an image of H x W; refuses an image that holds none."""
+    if H < patch or W < patch:
+        raise ValueError(f"niqe: an image of {H} x {W} holds no block of patch = {patch}; both sides must be at least patch")
+    if H > 16384 or W > 16384:
+        raise ValueError(f"niqe: an image of {H} x {W}; sides of at most 16384")
+    return (H // patch) * (W // patch)
+
+
+def _niqe_features_checked(img: torch.Tensor, patch: int, quantize: bool) -> Tuple[torch.Tensor, torch.Tensor]:
+    N, _, H, W = (int(v) for v in img.shape)
+    P = _niqe_blocks(H, W, patch)
+    lib = _capi.lib()
+    need = C.c_int64(0)
+    _capi.check(lib.hdiff_niqe_workspace(N, H, W, patch, C.byref(need)), "niqe_workspace")
+    with torch.cuda.device(img.device):
+        feats = torch.empty(N, P, NIQE_ROW, dtype=torch.float64, device=img.device)
+        sharp = torch.empty(N, P, dtype=torch.float64, device=img.device)
+        scratch = torch.empty(need.value, dtype=torch.uint8, device=img.device)
+        _capi.check(lib.hdiff_niqe_features(img.data_ptr(), N, H, W, patch, int(bool(quantize)), feats.data_ptr(), sharp.data_ptr(),
+                                            scratch.data_ptr(), _stream(img.device)), "niqe_features")
+    return feats, sharp
+
+
+def _niqe_moments_into(feats: torch.Tensor, sharp: torch.Tensor, threshold: float, out: torch.Tensor) -> None:
+    """``out``: a contiguous ``[N, NIQE_MOMENTS]`` float64 slice on the features' device."""
+    N, P = int(feats.shape[0]), int(feats.shape[1])
+    with torch.cuda.device(feats.device):
+        _capi.check(_capi.lib().hdiff_niqe_moments(feats.data_ptr(), sharp.data_ptr(), N, P, float(threshold), out.data_ptr(),
+                                                   _stream(feats.device)), "niqe_moments")
+
+
+def niqe_features(img01: torch.Tensor, *, patch: int = 96, quantize: bool = True) -> Tuple[torch.Tensor, torch.Tensor]:
+    """-> (feats ``[N, P, 36]``, sharp ``[N, P]``), float64 device tensors; never synchronises.  ``P`` is the number of whole
+    ``patch`` x ``patch`` blocks of the image, counted from its top-left corner (``patch`` even, 8 to 512; both sides at least
+    ``patch``).  A row holds the 18 AGGD features of a block of the contrast-normalised gray plane and the 18 of its counterpart on the
+    plane reduced by two; ``sharp`` is the mean local deviation of the block.  ``quantize`` rounds channels and gray to 8-bit values
+    first, as a written file holds them.  A block over a constant area has non-finite features; an image with a NaN pixel has NaN
+    everywhere."""
+    patch = _niqe_patch(patch)
+    return _niqe_features_checked(_image_batch(img01, "img01"), patch, quantize)
+
+
+class NIQEModel:
+    """The "pristine" model NIQE measures against: the mean ``[36]`` and covariance ``[36, 36]`` of the rows of sharp blocks of clean
+    images, with the ``patch`` and ``quantize`` they were taken at (host float64).  None ships and none is fetched: ``fit`` one on the
+    targets of a paired set, or ``load`` the parameters of the authors' release (agreement with that release is unpinned)."""
+
+    def __init__(self, mean, cov, *, patch: int = 96, quantize: bool = True):
+        self.patch, self.quantize = _niqe_patch(patch), bool(quantize)
+        self.mean = np.ascontiguousarray(_host64(mean).reshape(-1))
+        self.cov = np.ascontiguousarray(_host64(cov))
+        if self.mean.shape != (NIQE_ROW,) or self.cov.shape != (NIQE_ROW, NIQE_ROW):
+            raise ValueError(f"NIQEModel: mean of shape {_host64(mean).shape} and cov of shape {self.cov.shape}; [36] and [36, 36]")
+        if not (np.isfinite(self.mean).all() and np.isfinite(self.cov).all()):
+            raise ValueError("NIQEModel: the mean and the covariance must be finite")
+
+    def save(self, path: str) -> None:
+        """Writes an ``.npz`` with ``mean``, ``cov``, ``patch`` and ``quantize`` (to ``path`` as given: no suffix is appended)."""
+        with open(path, "wb") as f:
+            np.savez(f, mean=self.mean, cov=self.cov, patch=np.int64(self.patch), quantize=np.bool_(self.quantize))
+
+    @classmethod
+    def load(cls, path: str, *, patch: Optional[int] = None) -> "NIQEModel":
+        """An ``.npz`` written by ``save``, or a ``.mat`` holding ``mu_prisparam`` / ``cov_prisparam`` (the release's file, read with
+        ``scipy.io.loadmat``; those were taken at ``patch=96`` on 8-bit images).  ``patch``: the block side the caller is going to
+        use; a file that holds another one raises ``ValueError``."""
+        if str(path).lower().endswith(".mat"):
+            from scipy.io import loadmat
+            held = loadmat(str(path))
+            missing = [k for k in ("mu_prisparam", "cov_prisparam") if k not in held]
+            if missing:
+                raise ValueError(f"NIQEModel.load: {path} lacks {missing}")
+            model = cls(held["mu_prisparam"], held["cov_prisparam"], patch=96, quantize=True)
+        else:
+            with np.load(str(path)) as held:
+                missing = [k for k in ("mean", "cov", "patch") if k not in held.files]
+                if missing:
+                    raise ValueError(f"NIQEModel.load: {path} lacks {missing}")
+                model = cls(held["mean"], held["cov"], patch=int(held["patch"]),
+                            quantize=bool(held["quantize"]) if "quantize" in held.files else True)
+        if patch is not None and int(patch) != model.patch:
+            raise ValueError(f"NIQEModel.load: {path} was fitted at patch = {model.patch}, not at patch = {patch}")
+        return model
+
+    @classmethod
+    def fit(cls, batches, *, patch: int = 96, sharp_threshold: float = 0.75, quantize: bool = True) -> "NIQEModel":
+        """Fits the model on ``batches``: an iterable of ``[N, 3, H, W]`` (or ``[3, H, W]``) device images in [0, 1], of any sizes.  From
+        each image the finite rows whose ``sharp`` exceeds ``sharp_threshold * max(sharp of that image)`` are kept
+        (``hdiff_niqe_keep``); rows and selection stay in a device bank that doubles as it fills, and the mean and unbiased covariance
+        of the kept rows are taken by ``hdiff_niqe_pool_moments`` in bank order, so the result does not depend on how the set was cut
+        into batches.  Nothing synchronises before the one copy of the result.  Fewer than two kept rows raise ``ValueError``."""
+        patch = _niqe_patch(patch)
+        if not 0.0 <= float(sharp_threshold) < 1.0:
+            raise ValueError(f"NIQEModel.fit: sharp_threshold = {sharp_threshold!r}; in [0, 1)")
+        if torch.is_tensor(batches):
+            batches = [batches]
+        lib = _capi.lib()
+        bank = keep = None
+        n = 0
+        for batch in batches:
+            if torch.is_tensor(batch) and batch.dim() == 3:
+                batch = batch.unsqueeze(0)
+            img = _image_batch(batch, "batches")
+            feats, sharp = _niqe_features_checked(img, patch, quantize)
+            N, P = int(feats.shape[0]), int(feats.shape[1])
+            dev = img.device
+            if bank is not None and bank.device != dev:
+                raise RuntimeError(f"hdiff: NIQEModel.fit holds rows on {bank.device}, a batch is on {dev}")
+            if bank is None or n + N * P > int(bank.shape[0]):
+                capacity = 1024 if bank is None else int(bank.shape[0])
+                while capacity < n + N * P:
+                    capacity *= 2
+                grown, grown_keep = (torch.empty(capacity, NIQE_ROW, dtype=torch.float64, device=dev),
+                                     torch.empty(capacity, dtype=torch.int32, device=dev))
+                if bank is not None:
+                    grown[:n].copy_(bank[:n])
+                    grown_keep[:n].copy_(keep[:n])
+                bank, keep = grown, grown_keep
+            bank[n:n + N * P].copy_(feats.view(N * P, NIQE_ROW))
+            with torch.cuda.device(dev):
+                _capi.check(lib.hdiff_niqe_keep(feats.data_ptr(), sharp.data_ptr(), N, P, float(sharp_threshold),
+                                                keep[n:n + N * P].data_ptr(), _stream(dev)), "niqe_keep")
+            n += N * P
+        if bank is None:
+            raise ValueError("NIQEModel.fit: no images")
+        out = torch.empty(NIQE_MOMENTS, dtype=torch.float64, device=bank.device)
+        with torch.cuda.device(bank.device):
+            _capi.check(lib.hdiff_niqe_pool_moments(bank.data_ptr(), keep.data_ptr(), n, out.data_ptr(), _stream(bank.device)),
+                        "niqe_pool_moments")
+        host = out.cpu().numpy()
+        if host[-1] < 2:
+            raise ValueError(f"NIQEModel.fit: {int(host[-1])} of {n} rows are finite and sharp enough; at least two are needed")
+        return cls(host[:NIQE_ROW], host[NIQE_ROW:-1].reshape(NIQE_ROW, NIQE_ROW), patch=patch, quantize=quantize)
+
+
+def niqe_from_moments(model: NIQEModel, mean, cov, count: Optional[float] = None) -> float:
+    """``sqrt(d . pinv((cov_pris + cov) / 2) . d)`` with ``d = mu_pris - mean``, on the host in float64;
+    ``numpy.linalg.pinv(hermitian=True)`` at its default cutoff (the release's ``pinv`` uses MATLAB's tolerance).  NaN where the
+    image's moments are undefined: a non-finite entry (the kernel's covariance of fewer than two rows is NaN) or ``count`` < 2."""
+    if not isinstance(model, NIQEModel):
+        raise TypeError(f"niqe: model must be a quality.NIQEModel, got {type(model).__name__}")
+    m, c = _host64(mean).reshape(-1), _host64(cov)
+    if m.shape != (NIQE_ROW,) or c.shape != (NIQE_ROW, NIQE_ROW):
+        raise ValueError(f"niqe_from_moments: mean of shape {m.shape} and cov of shape {c.shape}; [36] and [36, 36]")
+    if (count is not None and count < 2) or not (np.isfinite(m).all() and np.isfinite(c).all()):
+        return float("nan")
+    d = model.mean - m
+    return float(np.sqrt(d @ np.linalg.pinv((model.cov + c) / 2.0, hermitian=True) @ d))
+
+
+def _niqe_scores(model: NIQEModel, rows: np.ndarray) -> np.ndarray:
+    """``[n, NIQE_MOMENTS]`` host rows -> ``[n]`` scores."""
+    return np.array([niqe_from_moments(model, r[:NIQE_ROW], r[NIQE_ROW:-1].reshape(NIQE_ROW, NIQE_ROW), r[-1]) for r in rows],
+                    dtype=np.float64).reshape(-1)
+
+
+def niqe(img01: torch.Tensor, model: NIQEModel) -> torch.Tensor:
+    """-> float64 ``[N]`` on the images' device: the NIQE of each image against ``model``, at the model's ``patch`` and ``quantize``;
+    lower is better.  The features and the per-image moments of the finite rows are taken on the device; then ONE copy of the
+    ``N x 1333`` doubles and the finish on the host (``niqe_from_moments``): this call SYNCHRONISES once.  NaN for an image with fewer
+    than two finite rows or with a NaN pixel."""
+    if not isinstance(model, NIQEModel):
+        raise TypeError(f"niqe: model must be a quality.NIQEModel, got {type(model).__name__}")
+    img = _image_batch(img01, "img01")
+    feats, sharp = _niqe_features_checked(img, model.patch, model.quantize)
+    out = torch.empty(int(img.shape[0]), NIQE_MOMENTS, dtype=torch.float64, device=img.device)
+    _niqe_moments_into(feats, sharp, 0.0, out)
+    return torch.from_numpy(_niqe_scores(model, out.cpu().numpy())).to(img.device)

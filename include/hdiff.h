@@ -662,6 +662,36 @@ int hdiff_uiqm(const float* a, int N, int H, int W, double* out, void* scratch, 
  * synchronisation, no float atomics: legal under stream capture, bitwise repeatable, independent of N and of the place in the batch. */
 int hdiff_uciqe_workspace(int N, int H, int W, int64_t* bytes);
 int hdiff_uciqe(const float* a, int N, int H, int W, double scale, double* out, void* scratch, hdiff_stream_t stream);
+/* NIQE (csrc/niqe.hip; Mittal, Soundararajan, Bovik 2013; tests/_niqe_def.py is the definition the kernels are held to; agreement with
+ * the authors' MATLAB release is unpinned).  img: fp32 [N][3][H][W] in [0, 1].  The gray plane (quantize != 0: channels and gray rounded
+ * to 8-bit values, as a file holds them) is cropped from the top-left corner to bh = H / patch by bw = W / patch whole blocks; P = bh bw.
+ * Per block and scale (block side patch, then patch / 2 on the plane reduced by the 8-tap bicubic): the 18 AGGD features of the
+ * mean-subtracted contrast-normalised block and of its four neighbour products (shifted circularly inside the block); a row is the 36
+ * features of a block, scale 1 first.  Everything in double.
+ *   hdiff_niqe_workspace     bytes of `scratch` for hdiff_niqe_features at (N, H, W, patch): four double planes per image
+ *   hdiff_niqe_features      feats [N][P][36], sharp [N][P] (the mean of sigma over the block at scale 1).  A block without negative or
+ *                            without positive values (a constant area) has non-finite features; an image with a NaN pixel inside the
+ *                            crop has NaN in every feature.  Nine launches, one more while the device's table is not built (the
+ *                            table kernel runs on the stream of the first call on a device: a first call on ANOTHER stream at the same
+ *                            time must be ordered behind it by the caller)
+ *   hdiff_niqe_moments       out [N][36 + 36 * 36 + 1]: mean, unbiased covariance and count of the VALID rows of each image, rows added
+ *                            in index order, two passes.  A row is valid if its 36 features are finite and, with sharp_threshold > 0,
+ *                            sharp > sharp_threshold * max(sharp of the image).  count < 2: NaN covariance; count = 0: NaN mean.  One launch
+ *   hdiff_niqe_keep          keep [N][P] (int, 0 / 1): the validity above, for a bank of rows that outlives its images.  One launch
+ *   hdiff_niqe_pool_moments  out [36 + 36 * 36 + 1] over the rows of a bank feats [rows][36] whose keep[r] != 0, in index order: the
+ *                            pristine fit over many images, without a copy to the host.  One launch
+ * N in [1, 65535]; H, W in [patch, 16384]; patch even, in [8, 512]; P <= 2^22; rows <= 2^26; sharp_threshold in [0, 1) (sharp may be
+ * NULL at 0).  No allocation, no synchronisation, no float atomics: legal under stream capture, bitwise repeatable; an image's rows and
+ * moments do not depend on N or on its place in the batch.  Deviations from the release, all deliberate: rows with a non-finite
+ * feature leave mean AND covariance (the release drops them per column for the mean); the score's pseudo-inverse is taken on the host
+ * with numpy's cutoff.  Additions to ABI 6. */
+int hdiff_niqe_workspace(int N, int H, int W, int patch, int64_t* bytes);
+int hdiff_niqe_features(const float* img, int N, int H, int W, int patch, int quantize, double* feats, double* sharp, void* scratch,
+                        hdiff_stream_t stream);
+int hdiff_niqe_moments(const double* feats, const double* sharp, int N, int P, double sharp_threshold, double* out,
+                       hdiff_stream_t stream);
+int hdiff_niqe_keep(const double* feats, const double* sharp, int N, int P, double sharp_threshold, int* keep, hdiff_stream_t stream);
+int hdiff_niqe_pool_moments(const double* feats, const int* keep, int rows, double* out, hdiff_stream_t stream);
 /* Set-level statistics of feature rows (csrc/distribution.hip; tests/_distribution_def.py is the definition): what a Frechet distance
  * and a KID over a feature extractor need.  Features are fp32, n rows of d values, value (r, i) at feats[r * row_stride + i * ch_stride]
  * (strides in elements, both >= 1), so the class-token view of a channel-major (B, C, L) tensor is read in place.  Outputs are double.

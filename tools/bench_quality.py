@@ -20,7 +20,13 @@ condition checked is that the added device time for the whole batch stays below 
 With ``--distribution`` four arms alternate: the device part of ``DistributionMeter.compute`` (``quality.moments`` of two banks of
 ``--rows`` x ``--width`` features and ``quality.kid_sums``), the host path it stands in for (copy the features, ``np.cov`` and three
 float64 Gram products), ``frechet_from_moments`` on the host, and one ``DistributionMeter.update`` of the batch (predictions and
-targets) through ``dinov2_vits14`` with random weights.  No condition is checked: the figures are reported as they come."""
+targets) through ``dinov2_vits14`` with random weights.  No condition is checked: the figures are reported as they come.
+
+With ``--niqe`` four arms alternate: ``QualityMeter.update`` without NIQE, ``QualityMeter(niqe=model).update`` at ``--niqe-patch``
+(default 32; the model is fitted on the targets of the batch), ``quality.niqe`` of ONE ``--niqe-full`` image (default 3024 x 4032) at
+patch 96 -- wall clock, its one synchronisation, copy and host finish included -- and the only host path that exists for it: copy the
+image, then the vectorised numpy definition ``tests/_niqe_def.py``.  The JSON line holds what NIQE adds per update and its ratio to one
+29.4 ms DDIM step, and the two full-size times.  No condition is checked."""
 import argparse
 import json
 import os
@@ -44,6 +50,10 @@ ap.add_argument("--warmup", type=int, default=5)
 ap.add_argument("--uciqe", action="store_true", help="time QualityMeter.update without / with UCIQE against uw_metrics.nmetrics on the host")
 ap.add_argument("--distribution", action="store_true", help="time the set-level scores: moments + KID sums against numpy on the host, "
                 "frechet_from_moments, and one DistributionMeter.update through dinov2_vits14")
+ap.add_argument("--niqe", action="store_true", help="time QualityMeter.update without / with NIQE, and quality.niqe of one full-size "
+                "image against the numpy definition on the host")
+ap.add_argument("--niqe-patch", type=int, default=32, help="--niqe: block side of the meter arm")
+ap.add_argument("--niqe-full", type=int, nargs=2, default=(3024, 4032), metavar=("H", "W"), help="--niqe: the full-size image")
 ap.add_argument("--rows", type=int, default=1024, help="--distribution: rows per feature bank")
 ap.add_argument("--width", type=int, default=384, help="--distribution: feature width")
 a = ap.parse_args()
@@ -58,8 +68,8 @@ pred = (target + 0.03 * torch.randn(a.batch, 3, a.size, a.size, generator=g)).cl
 pred_d, target_d = pred.to(dev), target.to(dev)
 
 
-def device_arm(uciqe=False):
-    meter = quality.QualityMeter(capacity=a.batch * (a.reps + a.warmup), uciqe=uciqe)
+def device_arm(uciqe=False, niqe=None):
+    meter = quality.QualityMeter(capacity=a.batch * (a.reps + a.warmup), uciqe=uciqe, niqe=niqe)
     for _ in range(a.warmup):
         meter.update(pred_d, target_d)
     torch.cuda.synchronize(dev)
@@ -123,6 +133,53 @@ if a.uciqe:
                       "added_ms_over_29.4_ms_ddim_step": (sum(added) / len(added)) / 29.4,
                       "host_ms_per_image_min": host_image_best, "added_device_batch_below_one_host_image": ok}))
     sys.exit(0 if ok else 1)
+
+if a.niqe:
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import _niqe_def as niqe_def  # noqa: E402
+    model = quality.NIQEModel.fit([target_d], patch=a.niqe_patch)
+    H, W = a.niqe_full
+    fy, fx = torch.meshgrid(torch.arange(H, dtype=torch.float32), torch.arange(W, dtype=torch.float32), indexing="ij")
+    full = torch.stack([0.5 + 0.3 * torch.sin(fx / 40 + c) * torch.cos(fy / 55 - c) for c in range(3)])
+    # the model: the same field with a quarter of the noise (this times the score and compares two implementations; it judges nothing)
+    model_full = quality.NIQEModel.fit([(full + 0.01 * torch.randn(3, H, W, generator=g)).clamp(0, 1)[None].to(dev)], patch=96)
+    full = (full + 0.04 * torch.randn(3, H, W, generator=g)).clamp(0, 1)[None].to(dev)
+    del fy, fx
+
+    def full_arm():
+        quality.niqe(full, model_full)
+        torch.cuda.synchronize(dev)
+        t0 = time.perf_counter()
+        for _ in range(5):
+            score = quality.niqe(full, model_full)          # synchronises once per call
+        return (time.perf_counter() - t0) * 1e3 / 5, float(score[0])
+
+    def full_host_arm():
+        t0 = time.perf_counter()
+        img = full[0].cpu().numpy()
+        score = niqe_def.niqe(img, model_full.mean, model_full.cov, 96)
+        return (time.perf_counter() - t0) * 1e3, score
+
+    times = {"meter_ms": [], "meter_with_niqe_ms": [], "full_device_ms": [], "full_host_definition_ms": []}
+    for rep in range(a.alternate):
+        per_update = lambda ms: f"{ms:.4f} ms per update of {a.batch} ({a.reps} updates between two events)"      # noqa: E731
+        ms0, _ = timed(device_arm, f"meter                 rep {rep}:", per_update)
+        ms1, res = timed(lambda: device_arm(niqe=model), f"meter with NIQE       rep {rep}:", per_update)
+        ms2, got = timed(full_arm, f"niqe of {H}x{W}    rep {rep}:", lambda ms: f"{ms:.3f} ms per image, wall clock (5 calls)")
+        ms3, want = timed(full_host_arm, f"host definition       rep {rep}:", lambda ms: f"{ms:.1f} ms per image (copy included)")
+        for k, ms in zip(times, (ms0, ms1, ms2, ms3)):
+            times[k].append(ms)
+        print(f"                      full-size score: device {got!r} host {want!r} rel {abs(got - want) / abs(want):.1e}; "
+              f"meter NIQE mean {res['niqe']:.6g}, undefined {res['niqe_undefined']}", flush=True)
+    summary = {k: {"mean": sum(v) / len(v), "min": min(v), "max": max(v), "repetitions": len(v)} for k, v in times.items()}
+    added = [w - p for w, p in zip(times["meter_with_niqe_ms"], times["meter_ms"])]
+    print(json.dumps({"metric": f"QualityMeter.update of one batch of {a.batch} at {a.size}x{a.size} without / with NIQE at patch "
+                                f"{a.niqe_patch}; quality.niqe of one {H}x{W} image at patch 96 against the numpy definition on the "
+                                f"host; alternating",
+                      "unit": "ms", "arms": summary, "niqe_added_ms_per_update": {"mean": sum(added) / len(added), "max": max(added)},
+                      "added_ms_over_29.4_ms_ddim_step": (sum(added) / len(added)) / 29.4,
+                      "full_host_over_device": summary["full_host_definition_ms"]["mean"] / summary["full_device_ms"]["mean"]}))
+    sys.exit(0)
 
 if a.distribution:
     import warnings
