@@ -14,7 +14,12 @@
 //     16-byte LDS read, and a tap is just a pixel offset;
 //   * the weights are not staged: hdiff_pack_conv_weight_x3 lays them out as [chunk][tap][piece][channel][16 ci], so a lane's
 //     A operand is one 16-byte global load (L1/L2 resident: every workgroup of the launch reads the same 55 KB per chunk);
-//   * per tap 6 piece pairs x (2 x 2) tiles = 24 MFMAs; the next tap's weight loads are issued before them.
+//   * per tap 6 piece pairs x (2 x 2) tiles = 24 MFMAs (a wave: 4 output rows x 6, pairs: x 3).
+//   * Loop order (in the kernel, "Tap-column order"): the taps form an NDY x NDX rectangle and are walked column by column.  The
+//     fp16-pair form reads each of the 4 + NDY - 1 patch rows of a tap column ONCE and feeds every (tap row, output row) that
+//     needs it (36 LDS reads per chunk of the 3x3 instead of 72), weights one tap column ahead; the bf16-triple and DROP forms
+//     keep one read per (tap, output row) with the weights two taps ahead, in the same column order of taps, so that every
+//     accumulator sums in the same order in both (a DROP launch with keep = 1 equals the plain launch bit for bit).
 //
 // PAIR (round 4): the same kernel with both operands as fp16 PAIRS instead of bf16 triples (v_mfma_f32_32x32x16_f16), for
 // convolutions with the GroupNorm + Swish prologue.  fp16 carries 11 significand bits, a pair x' = h0 + h1 holds 22-23 of
@@ -74,16 +79,19 @@ constexpr int DUMP_WORD = PIECE_WORDS;                // ... where the unused st
 __device__ constexpr int TERM_W[6] = {2, 1, 0, 1, 0, 0};
 __device__ constexpr int TERM_X[6] = {0, 1, 2, 0, 1, 0};
 
-// NT: taps of the launch (9 = the 3x3 conv, 6 / 4 = transposed-conv phases with fewer taps); OUTMAP: the output pixel of
-// (vy, vx) is (vy * out_sy + out_oy, vx * out_sx + out_ox) of an OH x OW plane (transposed-conv phases) instead of (vy, vx).
-// PAIR: fp16 pairs and three products instead of bf16 triples and six (header); every (NT, OUTMAP) the launcher can ask for.
+// NDY x NDX: the tap rectangle of the launch (3x3 = the plain conv; 3x2 / 2x3 / 2x2 = transposed-conv phases and parity planes
+// with fewer taps): tap (dyi, dxi) reads pixel (y + dy_min + dyi, x + dx_min + dxi) and its weights are tap tap_idx[dyi * NDX + dxi]
+// of the pack.  OUTMAP: the output pixel of (vy, vx) is (vy * out_sy + out_oy, vx * out_sx + out_ox) of an OH x OW plane
+// (transposed-conv phases) instead of (vy, vx).
+// PAIR: fp16 pairs and three products instead of bf16 triples and six (header); every (rectangle, OUTMAP) the launcher can ask for.
 // DROP: train-mode dropout behind the GroupNorm + Swish prologue (nn.Dropout between Swish and the conv, ModelCondition.py:185):
-// the keep words of a slot's four channels (one word per channel) are requested while the slot before it is staged, one tap of
-// MFMAs ahead (a padding slot fetches the word of its channel plane's first element and never looks at it), and the staged value
-// is kept ? swish(..) * inv_keep : 0.  A compile-time variant: the instantiations without it carry none of this.  The DROP
-// instantiations are built with OCC = 2, which holds the register allocator to the occupancy of their siblings.
-template <int NT, bool OUTMAP, bool PAIR, int OCC = 1, bool DROP = false>
+// the keep words of a slot's four channels (one word per channel) are requested while the slot before it is staged, one slot's
+// share of MFMAs ahead (a padding slot fetches the word of its channel plane's first element and never looks at it), and the
+// staged value is kept ? swish(..) * inv_keep : 0.  A compile-time variant: the instantiations without it carry none of this.
+// OCC = 2 for every instantiation: two waves per SIMD are the register bound (256 VGPRs) that all of them are built to.
+template <int NDY, int NDX, bool OUTMAP, bool PAIR, int OCC = 2, bool DROP = false>
 __global__ __launch_bounds__(THREADS, OCC) void conv3x3_x3_kernel(const ConvX3K p) {
+  constexpr int NT = NDY * NDX;
   constexpr int NP = PAIR ? 2 : 3;         // pieces per operand
   __shared__ __attribute__((aligned(16))) unsigned sXbuf[2][NP * PSTRIDE];     // double-buffered: chunk c + 1 is staged beside chunk c's MFMAs
   extern __shared__ __attribute__((aligned(16))) float sG[];     // [2][Cin]: GroupNorm scale | shift of this sample
@@ -131,9 +139,27 @@ __global__ __launch_bounds__(THREADS, OCC) void conv3x3_x3_kernel(const ConvX3K 
   // consecutive 16-byte blocks: conflict-free.  (Round 2's [pixel][8 words] put lanes 8 words apart: the operand reads were
   // 2-way and the 4-byte staging stores 8-way bank-conflicted -- SQ_LDS_BANK_CONFLICT was 60 % of the LDS-active cycles.)
   // staging slots: slot e = (channel quad jq = e / 340: channels 4 jq .. 4 jq + 3, patch pixel e % 340); 8-byte stores
-  int s_goff[NSLOT];      // offset of the pixel inside its channel plane (iy * W + ix; strided input: header), or -1 (zero padding / unused slot)
-  int s_lds[NSLOT];       // word offset inside a piece, or the dump word (unused slot)
-  int s_quad[NSLOT];
+  // Per slot ONE register for the global side: the byte offset of (first channel of the quad, pixel) from the chunk's first
+  // channel plane, 0 for zero padding / an unused slot, whose bit of s_ok is clear.  The four channel planes and the chunk are
+  // wave-uniform and go into the loads' scalar base ((16 channels) * IHW * 4 bytes < 2^31: every launch's input plane is below
+  // 2^25 pixels, conv_igemm.hip).  The quad itself is one comparison away (slot i holds quads (256 i) / 340 and the next one).
+  unsigned s_voff[NSLOT];
+  unsigned s_ok = 0u;
+  auto slot_quad = [&](int i) {
+    const int lo = (i * THREADS) / PPIX;
+    const int jq = lo + (tid + i * THREADS >= (lo + 1) * PPIX ? 1 : 0);
+    return jq < 4 ? jq : 3;
+  };
+  // the LDS side likewise: the word offset inside a piece, (jq >> 1) * HALF_WORDS + (e - 340 jq) * 4 + (jq & 1) * 2 for slot
+  // e = t + 256 i, is 4 t plus one of two constants; the dump word for an unused slot (jq = 4).  t is the thread id behind an
+  // empty asm of the chunk: six offsets computed where they are used cost three instructions each, kept across the loop six registers.
+  auto slot_lds = [&](int i, int t) {
+    const int lo = (i * THREADS) / PPIX;
+    auto konst = [&](int jq) { return (jq >> 1) * HALF_WORDS + (i * THREADS - jq * PPIX) * 4 + (jq & 1) * 2; };
+    const bool next = t + i * THREADS >= (lo + 1) * PPIX;
+    if (lo + 1 >= 4) return next ? DUMP_WORD : 4 * t + konst(lo);
+    return 4 * t + (next ? konst(lo + 1) : konst(lo));
+  };
 #pragma unroll
   for (int i = 0; i < NSLOT; ++i) {
     const int e = tid + i * THREADS;
@@ -141,10 +167,10 @@ __global__ __launch_bounds__(THREADS, OCC) void conv3x3_x3_kernel(const ConvX3K 
     const int py = pos / PW, px = pos - py * PW;
     const int iy = vy0 - 1 + py, ix = vx0 - 1 + px;
     const bool used = jq < 4;
-    s_quad[i] = used ? jq : 3;
-    s_lds[i] = used ? (jq >> 1) * HALF_WORDS + pos * 4 + (jq & 1) * 2 : DUMP_WORD;
     const int gy = iy * p.in_s + p.in_oy, gx = ix * p.in_s + p.in_ox;
-    s_goff[i] = (used && iy >= 0 && gy < p.IH && ix >= 0 && gx < p.IW) ? gy * p.IW + gx : -1;
+    const bool ok = used && iy >= 0 && gy < p.IH && ix >= 0 && gx < p.IW;
+    s_voff[i] = ok ? (unsigned)(4 * jq) * (unsigned)(4 * IHW) + (unsigned)(gy * p.IW + gx) * 4u : 0u;
+    s_ok |= ok ? 1u << i : 0u;
   }
   if (has_gn) {
     for (int i = tid; i < 2 * p.Cin; i += THREADS)
@@ -163,13 +189,11 @@ __global__ __launch_bounds__(THREADS, OCC) void conv3x3_x3_kernel(const ConvX3K 
 #pragma unroll
     for (int r = 0; r < 16; ++r) acc[nt][r] = 0.f;
 
-  // XAHEAD (the fp16-pair form): the patch of chunk c + 2 is requested at the START of chunk c into a second register set and
-  // moved over at its end -- requested at the end of chunk c (the bf16-triple form, whose taps take twice as long) the first
-  // staging slot of chunk c + 1 consumed its load 400 cycles after it had left.
-  constexpr bool XAHEAD = PAIR;
-  f32x4 xv[NSLOT], xv2[XAHEAD ? NSLOT : 1];
+  // The raw patch, ONE register set: a slot's registers are free once it is staged, and its values of the chunk after next are
+  // requested at the start of the next tap column (chunk loop below) -- most of a chunk ahead of their use, no second set, no copies.
+  f32x4 xv[NSLOT];
   // DROP: the four keep words of the slot that is staged NEXT (x1 == NULL and B * Cin * H * W < 2^31: checked on the host),
-  // requested while the slot before it is staged -- one tap of MFMAs ahead of their use, four registers in flight.  `tie` is a
+  // requested while the slot before it is staged -- one slot's share of MFMAs ahead of their use, four registers in flight.  `tie` is a
   // value of the slot just staged: the (empty) asm makes the element index depend on it.  Without it the compiler keeps the
   // 24 per-(slot, channel) parts of the indices as loop invariants and requests a chunk's words all at once, and the kernel --
   // 20 registers to spare at two waves per SIMD -- spills (31 VGPRs in the fp16-pair form).
@@ -178,7 +202,7 @@ __global__ __launch_bounds__(THREADS, OCC) void conv3x3_x3_kernel(const ConvX3K 
   auto fetch_keep = [&](int i, int c0, unsigned tie) {
     if constexpr (DROP) {
       const unsigned hw = (unsigned)IHW;
-      unsigned e = (unsigned)(b * p.Cin + c0 + 4 * s_quad[i]) * hw + (unsigned)(s_goff[i] >= 0 ? s_goff[i] : 0);
+      unsigned e = (unsigned)(b * p.Cin + c0) * hw + (s_voff[i] >> 2);
       asm("" : "+v"(e) : "v"(tie));
       ksh = 0;
 #pragma unroll
@@ -189,38 +213,34 @@ __global__ __launch_bounds__(THREADS, OCC) void conv3x3_x3_kernel(const ConvX3K 
       }
     }
   };
-  auto issue_loads_to = [&](f32x4 (&dst)[XAHEAD ? NSLOT : 1], int c0) {
+  // a 16-channel chunk never straddles the concat seam (C0 % 16 == 0 is checked on the host); the loads are unconditional: the
+  // address is always valid
+  auto load_slot = [&](int i, int c0) {
     const float* xbase = (c0 < p.C0) ? p.x0 + ((size_t)b * p.C0 + c0) * IHW : p.x1 + ((size_t)b * p.C1 + (c0 - p.C0)) * IHW;
 #pragma unroll
-    for (int i = 0; i < (XAHEAD ? NSLOT : 0); ++i) {
-      const bool ok = s_goff[i] >= 0;
-      const float* src = xbase + (size_t)(4 * s_quad[i]) * IHW + (ok ? s_goff[i] : 0);
-      const float v0 = src[0], v1 = src[IHW], v2 = src[2 * IHW], v3 = src[3 * IHW];
-      dst[i] = f32x4{ok ? v0 : 0.f, ok ? v1 : 0.f, ok ? v2 : 0.f, ok ? v3 : 0.f};
-    }
+    for (int k = 0; k < 4; ++k) xv[i][k] = *reinterpret_cast<const float*>(reinterpret_cast<const char*>(xbase + k * IHW) + s_voff[i]);
   };
   auto issue_loads = [&](int c0) {
-    // a 16-channel chunk never straddles the concat seam (C0 % 16 == 0 is checked on the host)
-    const float* xbase = (c0 < p.C0) ? p.x0 + ((size_t)b * p.C0 + c0) * IHW : p.x1 + ((size_t)b * p.C1 + (c0 - p.C0)) * IHW;
 #pragma unroll
-    for (int i = 0; i < NSLOT; ++i) {
-      const bool ok = s_goff[i] >= 0;
-      const float* src = xbase + (size_t)(4 * s_quad[i]) * IHW + (ok ? s_goff[i] : 0);
-      const float v0 = src[0], v1 = src[IHW], v2 = src[2 * IHW], v3 = src[3 * IHW];   // unconditional: the address is always valid
-      xv[i] = f32x4{ok ? v0 : 0.f, ok ? v1 : 0.f, ok ? v2 : 0.f, ok ? v3 : 0.f};
-    }
+    for (int i = 0; i < NSLOT; ++i) load_slot(i, c0);
   };
   // Branch-free: a slot outside the image stages 0 by a select, a thread's unused last slot writes to a dump word behind the
   // piece planes -- with per-slot branches the GroupNorm table reads of a slot could not be issued before the previous slot
   // had finished, and every slot paid an LDS round trip of its own (11 per chunk and wave).
-  auto stage_slot = [&](auto gn_tag, int i, int c0, unsigned* sX) {
+  auto stage_slot = [&](auto gn_tag, int i, int c0, unsigned* sX, int t) {
     constexpr bool GN = decltype(gn_tag)::value;
+    const int lds = slot_lds(i, t);
     f32x4 v = xv[i];
+    if (!GN) {                  // (zero padding: the load read a valid address, the value is dropped here)
+      const bool inside = (s_ok >> i) & 1u;
+#pragma unroll
+      for (int k = 0; k < 4; ++k) v[k] = inside ? v[k] : 0.f;
+    }
     if (GN) {
-      const int ci = c0 + 4 * s_quad[i];
+      const int ci = c0 + 4 * slot_quad(i);
       const f32x4 sc = *reinterpret_cast<const f32x4*>(&sG[ci]);
       const f32x4 sh = *reinterpret_cast<const f32x4*>(&sG[p.Cin + ci]);
-      const bool inside = s_goff[i] >= 0;
+      const bool inside = (s_ok >> i) & 1u;
 #pragma unroll
       for (int k = 0; k < 4; ++k) {
         if constexpr (DROP) {
@@ -241,43 +261,131 @@ __global__ __launch_bounds__(THREADS, OCC) void conv3x3_x3_kernel(const ConvX3K 
       split2(v[0] * xs, v[1] * xs, one, a0, a1);
       split2(v[2] * xs, v[3] * xs, one, c0w, c1w);
       if (HDIFF_MUTANT & 1) { a1 &= 0xffe0ffe0u; c1w &= 0xffe0ffe0u; }      // (mutation test: 2^-16 of every activation dropped)
-      *reinterpret_cast<u32x2*>(&sX[s_lds[i]]) = u32x2{a0, c0w};
-      *reinterpret_cast<u32x2*>(&sX[PSTRIDE + s_lds[i]]) = u32x2{a1, c1w};
+      *reinterpret_cast<u32x2*>(&sX[lds]) = u32x2{a0, c0w};
+      *reinterpret_cast<u32x2*>(&sX[PSTRIDE + lds]) = u32x2{a1, c1w};
     } else {
       unsigned a0, a1, a2, c0w, c1w, c2w;
       split3(v[0], v[1], a0, a1, a2);
       split3(v[2], v[3], c0w, c1w, c2w);
-      *reinterpret_cast<u32x2*>(&sX[s_lds[i]]) = u32x2{a0, c0w};
-      *reinterpret_cast<u32x2*>(&sX[PSTRIDE + s_lds[i]]) = u32x2{a1, c1w};
-      *reinterpret_cast<u32x2*>(&sX[2 * PSTRIDE + s_lds[i]]) = u32x2{a2, c2w};
+      *reinterpret_cast<u32x2*>(&sX[lds]) = u32x2{a0, c0w};
+      *reinterpret_cast<u32x2*>(&sX[PSTRIDE + lds]) = u32x2{a1, c1w};
+      *reinterpret_cast<u32x2*>(&sX[2 * PSTRIDE + lds]) = u32x2{a2, c2w};
     }
   };
   auto store_staged = [&](auto gn_tag, int c0, unsigned* sX) {
 #pragma unroll
-    for (int i = 0; i < NSLOT; ++i) stage_slot(gn_tag, i, c0, sX);
+    for (int i = 0; i < NSLOT; ++i) stage_slot(gn_tag, i, c0, sX, tid);
   };
 
   // operand addresses: B = 8 channels (h picks the half) of pixel (row, l31) of this wave's N tile; A = 8 input channels of
   // output channel co0 + mt*32 + l31
-  int boff[4];
-#pragma unroll
-  for (int nt = 0; nt < 4; ++nt) boff[nt] = h * HALF_WORDS + ((wn * 4 + nt) * PW + l31) * 4;
-  const unsigned* wlane = p.wp3 + ((size_t)(co0 + wm * 32 + l31) * 8 + h * 4);
+  // (bbase: patch row 0 of the wave's rows at the rectangle's first tap; a patch row and a tap column are immediates from there)
+  const int bbase = h * HALF_WORDS + ((wn * 4 + p.dy_min + 1) * PW + l31 + p.dx_min + 1) * 4;
+  // (a wave-uniform 64-bit base in scalar registers plus ONE 32-bit byte offset per lane: the loads take the base from SGPRs, and
+  // no per-tap address pair occupies vector registers)
+  const unsigned wlane = (unsigned)((co0 + wm * 32 + l31) * 8 + h * 4) * 4u;
   const size_t w_piece = (size_t)p.CoutPad * 8;            // words between pieces
   const size_t w_tap = NP * w_piece, w_chunk = NT * w_tap;
 
-  auto load_w = [&](u32x4 (&wa)[NP], int chunk, int tap) {
-    const unsigned* wb = wlane + (size_t)chunk * w_chunk + (size_t)tap * w_tap;
+  // Tap-column order.  The B operand of (tap row dyi, output row nt) is patch row nt + dyi of the tap's column: it depends on
+  // nt + dyi only, so per tap column a wave needs NR = 4 + NDY - 1 patch rows, not 4 NDY.  One step = (tap column dxi, patch row r):
+  // the row's NP pieces are read from LDS ONCE and feed every (dyi, nt = r - dyi) with 0 <= nt < 4 -- up to NDY accumulators,
+  // whose product chains are interleaved (small terms first within each accumulator).  3x3 pairs: 36 reads of 16 bytes per chunk
+  // instead of 72.  The per-accumulator summation order is column-major over the taps.
+  constexpr int NR = 4 + NDY - 1, STEPS = NDX * NR;
+  auto load_wcol = [&](u32x4 (&wc)[NDY][NP], int chunk, int dxi, unsigned wl) {
 #pragma unroll
-    for (int pc = 0; pc < NP; ++pc) wa[pc] = *reinterpret_cast<const u32x4*>(wb + pc * w_piece);
+    for (int dyi = 0; dyi < NDY; ++dyi) {
+      const unsigned* wb = p.wp3 + (size_t)chunk * w_chunk + (size_t)p.tap_idx[dyi * NDX + dxi] * w_tap;     // (scalar table)
+#pragma unroll
+      for (int pc = 0; pc < NP; ++pc)
+        wc[dyi][pc] = *reinterpret_cast<const u32x4*>(reinterpret_cast<const char*>(wb + pc * w_piece) + wl);
+    }
   };
-  // One unit = (tap, pixel row nt): 6 MFMAs on acc[nt] (PAIR: 3).  The B operands of unit u + 1 are read from LDS at the start of unit
-  // u and the weights of tap + 2 are requested at the start of tap (two taps = 1 500 MFMA cycles ahead: an L2 hit under load
-  // takes about one tap), so that no unit starts by waiting for its own operands.
-  auto load_x = [&](u32x4 (&xp)[NP], const unsigned* sX, int tap, int nt) {
-    const int toff = p.tap_off[tap];                    // ((dy + 1) * PW + (dx + 1)) * 4, wave-uniform
+  auto load_row = [&](u32x4 (&xp)[NP], const unsigned* sX, int dxi, int r) {
 #pragma unroll
-    for (int pc = 0; pc < NP; ++pc) xp[pc] = *reinterpret_cast<const u32x4*>(&sX[pc * PSTRIDE + boff[nt] + toff]);
+    for (int pc = 0; pc < NP; ++pc) xp[pc] = *reinterpret_cast<const u32x4*>(&sX[pc * PSTRIDE + bbase + (r * PW + dxi) * 4]);
+  };
+  auto mma_row = [&](const u32x4 (&wc)[NDY][NP], const u32x4 (&xp)[NP], int r) {
+    constexpr int NTERM = PAIR ? 3 : 6;
+#pragma unroll
+    for (int t = 0; t < NTERM; ++t) {
+      const int tw = PAIR ? (t == 0 ? 1 : 0) : TERM_W[t], tx = PAIR ? (t == 1 ? 1 : 0) : TERM_X[t];      // pairs: w1 x0, w0 x1, w0 x0
+      if (!PAIR && (HDIFF_MUTANT & 1) && tw == 0 && tx == 2) continue;
+#pragma unroll
+      for (int dyi = 0; dyi < NDY; ++dyi) {
+        const int nt = r - dyi;
+        if (nt < 0 || nt >= 4) continue;
+        if constexpr (PAIR) acc[nt] = mfma_f16(wc[dyi][tw], xp[tx], acc[nt]);
+        else acc[nt] = mfma_bf16(wc[dyi][tw], xp[tx], acc[nt]);
+      }
+    }
+  };
+
+  // Chunk loop, ONE barrier per chunk: while the matrix core works through chunk c (LDS buffer c & 1), the vector pipe turns
+  // the raw patch of chunk c + 1 (in registers since the previous chunk) into split pieces in the other buffer, the NSLOT
+  // staging slots spread evenly behind the steps' MFMAs; the global loads of chunk c + 2 leave once those registers are free.
+  // The B operands run one step ahead.  The weight operands form ONE stream over (chunk, tap column), one column ahead of its
+  // use, through two register sets of NDY taps each (a column of the 3x3 pairs is 36 MFMAs = 1 150 cycles: an L2 hit under load
+  // takes about a third of that); the last column of a chunk requests the first column of the next one, so that no chunk begins
+  // by waiting for its weights.  With an odd NDX that column arrives in set 1 and is moved to set 0 at the end of the chunk.
+  u32x4 w[2][NDY][NP];
+  auto chunk = [&](auto gn_tag, auto more_tag, int c, int nchunks) {
+    constexpr bool more = decltype(more_tag)::value;      // compile time: the staging must not sit in a block of its own
+    const unsigned* sX = sXbuf[c & 1];
+    unsigned* sNext = sXbuf[(c + 1) & 1];
+    u32x4 xp[2][NP];
+    // (the thread id and the lane's weight offset behind an empty asm: what is computed from them stays inside the chunk.  Left
+    //  loop-invariant, the six LDS offsets and a 64-bit vector address per tap and piece are kept in registers across the loop.)
+    int t = tid;
+    unsigned wl = wlane;
+    asm volatile("" : "+v"(t), "+v"(wl));
+    load_row(xp[0], sX, 0, 0);
+#pragma unroll
+    for (int dxi = 0; dxi < NDX; ++dxi) {
+      // the patch registers freed by the column before: their slots of chunk c + 2 (first column: of chunk c + 1, freed by the
+      // last column of chunk c - 1; the prologue has loaded all of chunk 1)
+      if (dxi == 0 ? (c > 0 && c + 1 < nchunks) : (c + 2 < nchunks)) {
+#pragma unroll
+        for (int i = 0; i < NSLOT; ++i)
+          if ((((i + 1) * STEPS) / NSLOT - 1) / NR == (dxi + NDX - 1) % NDX) load_slot(i, (dxi == 0 ? c + 1 : c + 2) * 16);
+      }
+      if (dxi + 1 < NDX) load_wcol(w[(dxi + 1) & 1], c, dxi + 1, wl);
+      else if (more) load_wcol(w[NDX & 1], c + 1, 0, wl);
+#pragma unroll
+      for (int r = 0; r < NR; ++r) {
+        const int g = dxi * NR + r;
+        if (g + 1 < STEPS) load_row(xp[(g + 1) & 1], sX, (g + 1) / NR, (g + 1) % NR);
+        mma_row(w[dxi & 1], xp[g & 1], r);
+        if (more) {
+#pragma unroll
+          for (int i = 0; i < NSLOT; ++i)
+            if (((i + 1) * STEPS) / NSLOT - 1 == g) stage_slot(gn_tag, i, (c + 1) * 16, sNext, t);
+        }
+      }
+    }
+    if (more && (NDX & 1)) {
+#pragma unroll
+      for (int dyi = 0; dyi < NDY; ++dyi)
+#pragma unroll
+        for (int pc = 0; pc < NP; ++pc) w[0][dyi][pc] = w[1][dyi][pc];
+    }
+    __syncthreads();
+  };
+
+  // Tap-major order (the bf16-triple and the DROP instantiations: with a column of weight sets in flight beside the column in use
+  // they do not fit 256 registers -- profiles/conv_tap_columns.txt).  The taps of the rectangle are walked one by one, COLUMN by
+  // column: every accumulator sums in the order of the column form, so the two forms give the same bits.  A tap is four units,
+  // one per output row, of NP (NP + 1) / 2 MFMAs each, and every unit has a B read of its own.  The B operands run one unit
+  // ahead, the weights two taps ahead through a ring of three sets (WSTREAM: a tap count that is a multiple of three keeps the
+  // ring's phase from chunk to chunk); one staging slot behind each tap's MFMAs, its registers reloaded at the start of the
+  // next tap.
+  constexpr bool WSTREAM = (NT % 3 == 0);
+  u32x4 wr[3][NP];
+  auto load_w = [&](u32x4 (&wa)[NP], int chunk, int tap, unsigned wl) {
+    const unsigned* wb = p.wp3 + (size_t)chunk * w_chunk + (size_t)p.tap_idx[(tap % NDY) * NDX + tap / NDY] * w_tap;
+#pragma unroll
+    for (int pc = 0; pc < NP; ++pc) wa[pc] = *reinterpret_cast<const u32x4*>(reinterpret_cast<const char*>(wb + pc * w_piece) + wl);
   };
   auto mma_unit = [&](const u32x4 (&wa)[NP], const u32x4 (&xp)[NP], int nt) {
     if constexpr (PAIR) {                  // small products first
@@ -290,52 +398,49 @@ __global__ __launch_bounds__(THREADS, OCC) void conv3x3_x3_kernel(const ConvX3K 
         if (!((HDIFF_MUTANT & 1) && TERM_W[t] == 0 && TERM_X[t] == 2)) acc[nt] = mfma_bf16(wa[TERM_W[t]], xp[TERM_X[t]], acc[nt]);
     }
   };
-
-  // Chunk loop, ONE barrier per chunk: while the matrix core works through chunk c (LDS buffer c & 1), the vector pipe turns
-  // the raw patch of chunk c + 1 (in registers since the previous chunk) into split pieces in the other buffer, one or two
-  // staging slots behind every tap's MFMAs; the global loads of chunk c + 2 leave once those registers are free.
-  // The weight operands form ONE stream over (chunk, tap), two taps ahead of their use, through a ring of three register sets
-  // (WSTREAM: a tap count that is a multiple of three keeps the ring's phase from chunk to chunk; before, every chunk began by
-  // requesting its first two taps and waiting for them -- with half the matrix time per tap the fp16-pair form spent 38 % of
-  // its wave time waiting, SQ_WAIT_ANY).
-  constexpr bool WSTREAM = (NT % 3 == 0);
-  u32x4 w[3][NP];
-  auto chunk = [&](auto gn_tag, auto more_tag, int c, int nchunks) {
-    constexpr bool more = decltype(more_tag)::value;      // compile time: the staging must not sit in a block of its own
+  auto chunk_taps = [&](auto gn_tag, auto more_tag, int c, int nchunks) {
+    constexpr bool more = decltype(more_tag)::value;
     const unsigned* sX = sXbuf[c & 1];
     unsigned* sNext = sXbuf[(c + 1) & 1];
     u32x4 xp[2][NP];
-    if (XAHEAD && c + 2 < nchunks) issue_loads_to(xv2, (c + 2) * 16);
+    int t = tid;
+    unsigned wl = wlane;
+    asm volatile("" : "+v"(t), "+v"(wl));
     if (!WSTREAM || c == 0) {
-      load_w(w[0], c, 0);
-      load_w(w[1], c, 1);
+      load_w(wr[0], c, 0, wl);
+      load_w(wr[1], c, 1, wl);
     }
-    load_x(xp[0], sX, 0, 0);
+    load_row(xp[0], sX, 0, 0);          // unit (tap, nt) reads patch row nt + tap % NDY of tap column tap / NDY
 #pragma unroll
     for (int tap = 0; tap < NT; ++tap) {
-      if (tap + 2 < NT) load_w(w[(tap + 2) % 3], c, tap + 2);
-      else if (WSTREAM && more) load_w(w[(tap + 2) % 3], c + 1, tap + 2 - NT);      // the next chunk's first two taps
+      // slot i is staged behind tap min(i, NT - 1); its registers take chunk c + 2 at the next tap, those of the last tap chunk
+      // c + 1 at the first tap of the next chunk
+      if (tap == 0 ? (c > 0 && c + 1 < nchunks) : (c + 2 < nchunks)) {
+#pragma unroll
+        for (int i = 0; i < NSLOT; ++i)
+          if ((i < NT - 1 ? i : NT - 1) == (tap + NT - 1) % NT) load_slot(i, (tap == 0 ? c + 1 : c + 2) * 16);
+      }
+      if (tap + 2 < NT) load_w(wr[(tap + 2) % 3], c, tap + 2, wl);
+      else if (WSTREAM && more) load_w(wr[(tap + 2) % 3], c + 1, tap + 2 - NT, wl);      // the next chunk's first two taps
 #pragma unroll
       for (int nt = 0; nt < 4; ++nt) {
         const int u = tap * 4 + nt;
-        if (u + 1 < 4 * NT) load_x(xp[(u + 1) & 1], sX, (u + 1) / 4, (u + 1) % 4);
-        mma_unit(w[tap % 3], xp[u & 1], nt);
+        if (u + 1 < 4 * NT) load_row(xp[(u + 1) & 1], sX, ((u + 1) / 4) / NDY, (u + 1) % 4 + ((u + 1) / 4) % NDY);
+        mma_unit(wr[tap % 3], xp[u & 1], nt);
       }
-      if (more && tap < NSLOT) stage_slot(gn_tag, tap, (c + 1) * 16, sNext);
-    }
-    if (more) {
+      if (more) {
 #pragma unroll
-      for (int i = NT; i < NSLOT; ++i) stage_slot(gn_tag, i, (c + 1) * 16, sNext);     // fewer taps than staging slots
-    }
-    if constexpr (XAHEAD) {
-      if (c + 2 < nchunks) {
-#pragma unroll
-        for (int i = 0; i < NSLOT; ++i) xv[i] = xv2[i];
+        for (int i = 0; i < NSLOT; ++i)
+          if ((i < NT - 1 ? i : NT - 1) == tap) stage_slot(gn_tag, i, (c + 1) * 16, sNext, t);
       }
-    } else {
-      if (c + 2 < nchunks) issue_loads((c + 2) * 16);
     }
     __syncthreads();
+  };
+  // which of the two: the column order where it fits the registers of two waves per SIMD without scratch
+  constexpr bool COLS = PAIR && !DROP;
+  auto run_chunk = [&](auto gn_tag, auto more_tag, int c, int nchunks) {
+    if constexpr (COLS) chunk(gn_tag, more_tag, c, nchunks);
+    else chunk_taps(gn_tag, more_tag, c, nchunks);
   };
 
   const int nchunks = p.Cin / 16;
@@ -345,13 +450,14 @@ __global__ __launch_bounds__(THREADS, OCC) void conv3x3_x3_kernel(const ConvX3K 
   if (has_gn) store_staged(std::true_type{}, 0, sXbuf[0]);
   else store_staged(std::false_type{}, 0, sXbuf[0]);
   if (nchunks > 1) issue_loads(16);
+  if constexpr (COLS) load_wcol(w[0], 0, 0, wlane);
   __syncthreads();
   if (has_gn) {
-    for (int c = 0; c + 1 < nchunks; ++c) chunk(std::true_type{}, std::true_type{}, c, nchunks);
-    chunk(std::true_type{}, std::false_type{}, nchunks - 1, nchunks);
+    for (int c = 0; c + 1 < nchunks; ++c) run_chunk(std::true_type{}, std::true_type{}, c, nchunks);
+    run_chunk(std::true_type{}, std::false_type{}, nchunks - 1, nchunks);
   } else {
-    for (int c = 0; c + 1 < nchunks; ++c) chunk(std::false_type{}, std::true_type{}, c, nchunks);
-    chunk(std::false_type{}, std::false_type{}, nchunks - 1, nchunks);
+    for (int c = 0; c + 1 < nchunks; ++c) run_chunk(std::false_type{}, std::true_type{}, c, nchunks);
+    run_chunk(std::false_type{}, std::false_type{}, nchunks - 1, nchunks);
   }
 
   // ---- epilogue: + bias + per-sample channel vector + residual, NCHW store (32 consecutive pixels per register row).
@@ -574,24 +680,53 @@ void launch_conv3x3_x3(const ConvX3K& k, int B, hipStream_t stream) {
   dim3 grid(k.tiles_x * tiles_y, cdiv(k.Cout, 64), B);
   const size_t dyn = (size_t)2 * k.Cin * sizeof(float);
   const bool outmap = !(k.out_sy == 1 && k.out_oy == 0 && k.out_sx == 1 && k.out_ox == 0 && k.OH == k.H && k.OW == k.W);
+  const int rect = k.ndy * 10 + k.ndx;     // 33, 32, 23 or 22 (conv_tap_rect)
+#define HDIFF_X3_LAUNCH(NDY, NDX, ...) \
+  hipLaunchKernelGGL((conv3x3_x3_kernel<NDY, NDX, __VA_ARGS__>), grid, dim3(THREADS), dyn, stream, k)
   if (k.keep_bits != nullptr) {            // train-mode dropout in the prologue (hdiff_conv2d_fwd_dropout checked the descriptor)
-    if (k.act_scale != nullptr) hipLaunchKernelGGL((conv3x3_x3_kernel<9, false, true, 2, true>), grid, dim3(THREADS), dyn, stream, k);
-    else hipLaunchKernelGGL((conv3x3_x3_kernel<9, false, false, 2, true>), grid, dim3(THREADS), dyn, stream, k);
+    if (k.act_scale != nullptr) HDIFF_X3_LAUNCH(3, 3, false, true, 2, true);
+    else HDIFF_X3_LAUNCH(3, 3, false, false, 2, true);
     return;
   }
   if (k.act_scale != nullptr || k.absmax_in != nullptr) {      // fp16 pairs: the input's range is known (the dispatcher checked the shape)
-    if (k.ntaps == 9 && !outmap) hipLaunchKernelGGL((conv3x3_x3_kernel<9, false, true>), grid, dim3(THREADS), dyn, stream, k);
-    else if (k.ntaps == 9) hipLaunchKernelGGL((conv3x3_x3_kernel<9, true, true>), grid, dim3(THREADS), dyn, stream, k);
-    else if (k.ntaps == 6 && !outmap) hipLaunchKernelGGL((conv3x3_x3_kernel<6, false, true>), grid, dim3(THREADS), dyn, stream, k);   // (parity planes
-    else if (k.ntaps == 4 && !outmap) hipLaunchKernelGGL((conv3x3_x3_kernel<4, false, true>), grid, dim3(THREADS), dyn, stream, k);   //  of the 5x5 / s2)
-    else if (k.ntaps == 6) hipLaunchKernelGGL((conv3x3_x3_kernel<6, true, true>), grid, dim3(THREADS), dyn, stream, k);
-    else hipLaunchKernelGGL((conv3x3_x3_kernel<4, true, true>), grid, dim3(THREADS), dyn, stream, k);
+    if (rect == 33 && !outmap) HDIFF_X3_LAUNCH(3, 3, false, true);
+    else if (rect == 33) HDIFF_X3_LAUNCH(3, 3, true, true);
+    else if (rect == 32 && !outmap) HDIFF_X3_LAUNCH(3, 2, false, true);      // (parity planes of the 5x5 / s2 ...
+    else if (rect == 23 && !outmap) HDIFF_X3_LAUNCH(2, 3, false, true);
+    else if (rect == 22 && !outmap) HDIFF_X3_LAUNCH(2, 2, false, true);
+    else if (rect == 32) HDIFF_X3_LAUNCH(3, 2, true, true);                  //  ... transposed-conv phases)
+    else if (rect == 23) HDIFF_X3_LAUNCH(2, 3, true, true);
+    else HDIFF_X3_LAUNCH(2, 2, true, true);
     return;
   }
-  if (k.ntaps == 9 && !outmap) hipLaunchKernelGGL((conv3x3_x3_kernel<9, false, false>), grid, dim3(THREADS), dyn, stream, k);
-  else if (k.ntaps == 9) hipLaunchKernelGGL((conv3x3_x3_kernel<9, true, false>), grid, dim3(THREADS), dyn, stream, k);
-  else if (k.ntaps == 6) hipLaunchKernelGGL((conv3x3_x3_kernel<6, true, false>), grid, dim3(THREADS), dyn, stream, k);
-  else hipLaunchKernelGGL((conv3x3_x3_kernel<4, true, false>), grid, dim3(THREADS), dyn, stream, k);
+  if (rect == 33 && !outmap) HDIFF_X3_LAUNCH(3, 3, false, false);
+  else if (rect == 33) HDIFF_X3_LAUNCH(3, 3, true, false);
+  else if (rect == 32) HDIFF_X3_LAUNCH(3, 2, true, false);
+  else if (rect == 23) HDIFF_X3_LAUNCH(2, 3, true, false);
+  else HDIFF_X3_LAUNCH(2, 2, true, false);
+#undef HDIFF_X3_LAUNCH
+}
+
+// The taps of a launch as a rectangle: fills ndy, ndx, dy_min, dx_min and tap_idx (tap t of the list = tap t of the pack) and
+// returns true if the ntaps distinct offsets, all in [-1, 1]^2, are exactly the 3x3, 3x2, 2x3 or 2x2 rectangle they span.
+bool conv_tap_rect(ConvTapRect& k, int ntaps, const int* dy, const int* dx) {
+  if (ntaps < 1 || ntaps > 9) return false;
+  int y0 = 1, y1 = -1, x0 = 1, x1 = -1;
+  for (int t = 0; t < ntaps; ++t) {
+    if (dy[t] < -1 || dy[t] > 1 || dx[t] < -1 || dx[t] > 1) return false;
+    y0 = dy[t] < y0 ? dy[t] : y0; y1 = dy[t] > y1 ? dy[t] : y1;
+    x0 = dx[t] < x0 ? dx[t] : x0; x1 = dx[t] > x1 ? dx[t] : x1;
+  }
+  const int ndy = y1 - y0 + 1, ndx = x1 - x0 + 1;
+  if (ndy < 2 || ndx < 2 || ndy * ndx != ntaps) return false;
+  for (int i = 0; i < 9; ++i) k.tap_idx[i] = i < ntaps ? -1 : 0;
+  for (int t = 0; t < ntaps; ++t) {
+    int& slot = k.tap_idx[(dy[t] - y0) * ndx + (dx[t] - x0)];
+    if (slot >= 0) return false;               // a tap listed twice
+    slot = t;
+  }
+  k.ntaps = ntaps; k.ndy = ndy; k.ndx = ndx; k.dy_min = y0; k.dx_min = x0;
+  return true;
 }
 
 }  // namespace hdiff

@@ -658,6 +658,7 @@ struct ConvRoute {
   const unsigned* pair_pack;        // the fp16-pair pack of the three PAIRS routes, NULL otherwise ...
   int pair_taps;                    // ... and its tap count: the tail {bits of max |w|, 2^-t, 2^t, 0} follows the taps' words
   bool absmax_tail;                 // conv_out_absmax_kernel follows: no epilogue of this route fills range->absmax_out
+  hdiff::ConvTapRect rect;          // the three X3 routes: the descriptor's taps as the kernel's rectangle (x3_geometry)
 };
 
 // The 5x5 / stride-2 / pad-2 conv (DownSample with its 3x3 folded in): 25 taps in row-major order over the whole output, no
@@ -673,19 +674,15 @@ bool s2_5x5_geometry(const hdiff_conv_desc* d, bool identity) {
 
 // A stride-1 conv whose taps all lie in the 3x3 neighbourhood -- the plain 3x3 / pad-1 conv (9 taps, output grid = input grid:
 // `same`) and the output-parity phases of ConvTranspose2d(5, stride 2) (9 / 6 / 6 / 4 taps, output pixel (2y + py, 2x + px)).
-bool x3_geometry(const hdiff_conv_desc* d, bool same) {
+bool x3_geometry(const hdiff_conv_desc* d, bool same, hdiff::ConvTapRect& rect) {
   if ((d->ntaps != 9 && d->ntaps != 6 && d->ntaps != 4) || d->in_stride != 1) return false;
   if (d->VH != d->H || d->VW != d->W) return false;
   const bool phase = d->out_sy == 2 && d->out_sx == 2 && (d->out_oy == 0 || d->out_oy == 1) && (d->out_ox == 0 || d->out_ox == 1) &&
                      d->OH == 2 * d->H && d->OW == 2 * d->W && d->residual == nullptr;
   if (!same && !phase) return false;
-  unsigned seen = 0;
-  for (int t = 0; t < d->ntaps; ++t) {
-    if (d->tap_dy[t] < -1 || d->tap_dy[t] > 1 || d->tap_dx[t] < -1 || d->tap_dx[t] > 1) return false;
-    const unsigned bit = 1u << ((d->tap_dy[t] + 1) * 3 + (d->tap_dx[t] + 1));
-    if (seen & bit) return false;                 // a tap listed twice: not a launch any of the x3 packs describes
-    seen |= bit;
-  }
+  // distinct taps that fill the rectangle they span (3x3, 3x2, 2x3, 2x2): the kernel walks the taps column by column.  A tap
+  // listed twice or a ragged set is not a launch any of the x3 packs describes.
+  if (!hdiff::conv_tap_rect(rect, d->ntaps, d->tap_dy, d->tap_dx)) return false;
   // the plain 3x3 pack (hdiff_pack_conv_weight_x3, forward and mirrored / transposed) stores tap t = (t / 3, t % 3): a
   // descriptor that lists its nine taps in another order keeps the fp32 kernel, which reads the order from the descriptor.
   // (Tap LISTS -- the transposed-conv phases -- are packed from the caller's own list by hdiff_pack_conv_weight_x3_taps;
@@ -710,11 +707,12 @@ bool direct_1x1_geometry(const hdiff_conv_desc* d, bool same) {
 // dropout: the dropout form (hdiff_conv2d_fwd_dropout) carries no range struct.
 ConvRoute conv_route(const hdiff_conv_desc* d, const hdiff_conv_range* r, bool dropout) {
   const bool split = hdiff::split_operands_on();
+  hdiff::ConvTapRect rect{};
   if (!split || dropout) r = nullptr;            // the words matter in the split-operand mode only
   // the split-operand kernels fill range->absmax_out in their epilogue; behind the two others a small launch does
   auto take = [&](int route, const void* pack = nullptr, int taps = 0) {
     const bool tail = r != nullptr && r->absmax_out != nullptr && (route == HDIFF_CONV_ROUTE_IGEMM || route == HDIFF_CONV_ROUTE_DIRECT_1X1);
-    return ConvRoute{route, r, (const unsigned*)pack, taps, tail};
+    return ConvRoute{route, r, (const unsigned*)pack, taps, tail, rect};
   };
   const bool identity = d->out_sy == 1 && d->out_oy == 0 && d->out_sx == 1 && d->out_ox == 0;
   const bool same = identity && d->OH == d->H && d->OW == d->W;          // output grid = input grid
@@ -726,11 +724,14 @@ ConvRoute conv_route(const hdiff_conv_desc* d, const hdiff_conv_range* r, bool d
   const bool ch16 = Cin % 16 == 0 && (d->C1 == 0 || d->C0 % 16 == 0);
   // ... and conv3x3_x3.hip (32x8 pixels x 64 output channels per workgroup) a launch large enough to fill the chip: small ones keep
   // the split-K path of the fp32 kernel
+  // (Its patch loads address the 16 channel planes of a chunk by a scalar base and 32-bit lane offsets.  No test here: every
+  // launch it gets has an input plane below 2^25 pixels -- VH x VW = H x W in x3_geometry, checked by the entry's validation, and
+  // s2_5x5_geometry's own bound -- so 16 planes stay below 2^31 bytes.)
   const bool x3_fills = split && ch16 && Cin <= 4096 && (long)cdiv(d->VW, 32) * cdiv(d->VH, 8) * cdiv(d->Cout, 64) * d->B >= 192;
 
   // four stride-1 pair convolutions over the input's parity planes (conv3x3_x3.hip, the plane pack)
   if (x3_fills && word && r->wp_h2_s2 != nullptr && s2_5x5_geometry(d, identity)) return take(HDIFF_CONV_ROUTE_S2_PAIRS_WORD, r->wp_h2_s2, 25);
-  if (x3_fills && x3_geometry(d, same)) {
+  if (x3_fills && x3_geometry(d, same, rect)) {
     // fp16 pairs (three products) instead of bf16 triples (six) for the plain 3x3 conv whose input range the caller knows:
     // behind the GroupNorm + Swish prologue (or an activation tensor made from it), bounded by the GroupNorm weights (act_scale
     // from hdiff_gn_act_scale, weights from hdiff_pack_conv_weight_h2) ...
@@ -793,10 +794,14 @@ static int conv2d_fwd_launch(const hdiff_conv_desc* d, ConvCfg& c, const ConvRou
       const size_t per_tap = (size_t)(q.Cin / 16) * 2 * d->CoutPad * 8;
       size_t taps_before = 0;
       for (int g = 0; g < 4; ++g) {          // plane (oy, ox) = (g >> 1, g & 1): 9, 6, 6, 4 taps
-        int ky[9], kx[9];
+        int ky[9], kx[9], dy[9], dx[9];
         q.in_oy = g >> 1; q.in_ox = g & 1;
-        q.ntaps = hdiff::s2_plane_taps(q.in_oy, q.in_ox, ky, kx);
-        for (int t = 0; t < q.ntaps; ++t) q.tap_off[t] = (((ky[t] - 2 - q.in_oy) / 2 + 1) * 34 + ((kx[t] - 2 - q.in_ox) / 2 + 1)) * 4;
+        const int ntaps = hdiff::s2_plane_taps(q.in_oy, q.in_ox, ky, kx);
+        for (int t = 0; t < ntaps; ++t) { dy[t] = (ky[t] - 2 - q.in_oy) / 2; dx[t] = (kx[t] - 2 - q.in_ox) / 2; }
+        if (!hdiff::conv_tap_rect(q, ntaps, dy, dx)) {       // (3x3, 3x2, 2x3, 2x2 by construction)
+          hdiff::set_error("conv2d_fwd: parity plane %d of the stride-2 conv is no tap rectangle", g);
+          return HDIFF_ERR_INVALID;
+        }
         q.wp3 = rt.pair_pack + taps_before * per_tap;
         // The LAST launch carries bias and addvec, behind the partial sums: out = (acc + partial) + bias is rounded once at the
         // size of the result, like the one-launch kernel's acc + bias.  With the bias in the first launch every later launch rounds
@@ -819,8 +824,7 @@ static int conv2d_fwd_launch(const hdiff_conv_desc* d, ConvCfg& c, const ConvRou
       hdiff::ConvX3K q = x3_args(d, rt);
       q.absmax_out = absmax_out;
       q.bias = d->bias; q.gn_scale = d->gn_scale; q.gn_shift = d->gn_shift; q.addvec = d->addvec; q.residual = d->residual;
-      q.ntaps = d->ntaps;
-      for (int t = 0; t < d->ntaps; ++t) q.tap_off[t] = ((d->tap_dy[t] + 1) * 34 + (d->tap_dx[t] + 1)) * 4;
+      static_cast<hdiff::ConvTapRect&>(q) = rt.rect;
       q.keep_bits = keep_bits; q.inv_keep = inv_keep;
       hdiff::launch_conv3x3_x3(q, d->B, s);
       HDIFF_CHECK_LAUNCH("conv3x3_x3_kernel");

@@ -6,10 +6,17 @@
 
 namespace hdiff {
 
+// the taps of a conv3x3_x3.hip launch: an ndy x ndx rectangle (3x3, 3x2, 2x3 or 2x2) of offsets (dy_min + dyi, dx_min + dxi) inside
+// [-1, 1]^2; the kernel walks it column by column.  Filled by conv_tap_rect, never by hand.
+struct ConvTapRect {
+  int ntaps;                       // ndy * ndx: 9, 6 or 4
+  int ndy, ndx, dy_min, dx_min;
+  int tap_idx[9];                  // [dyi * ndx + dxi]: which tap of the packed weights that offset is (used for the weight address only)
+};
 // conv3x3_x3.hip: split-bf16 convolution over the 3x3 neighbourhood (plain 3x3 / stride-1 convs, the four output-parity
 // phases of the transposed 5x5 / stride-2 conv and the four input-parity planes of the 5x5 / stride-2 conv: every tap offset
 // lies in [-1, 1]^2)
-struct ConvX3K {
+struct ConvX3K : ConvTapRect {
   const float* x0;
   const float* x1;
   int C0, C1, Cin, H, W;
@@ -22,8 +29,6 @@ struct ConvX3K {
   const float* residual;
   float* out;
   int tiles_x;
-  int ntaps;                       // 9, 6 or 4
-  int tap_off[9];                  // LDS word offset of the tap inside the staged patch: ((dy + 1) * 34 + (dx + 1)) * 4
   int OH, OW, out_sy, out_oy, out_sx, out_ox;     // output pixel (vy * out_sy + out_oy, vx * out_sx + out_ox) of an OH x OW plane
   // fp16-pair form (plain 3x3 behind GroupNorm + Swish): wp3 then holds [Cin/16][9][2][CoutPad][8] words of w 2^t
   const float* act_scale;          // device {2^s, 2^-s} of the staged activations (hdiff_gn_act_scale), NULL = bf16 triples
@@ -45,6 +50,9 @@ struct ConvX3K {
   int residual_first;              // != 0: out = (acc + residual) + (bias + addvec) instead of (acc + (bias + addvec)) + residual
 };
 void launch_conv3x3_x3(const ConvX3K& k, int B, hipStream_t stream);
+// the tap list (dy[t], dx[t]), t = its index in the pack, as a rectangle; false (k is then unspecified) if the list is not a full 3x3, 3x2, 2x3 or
+// 2x2 rectangle inside [-1, 1]^2 (the kernel has no form for it)
+bool conv_tap_rect(ConvTapRect& k, int ntaps, const int* dy, const int* dx);
 // taps (ky, kx) of the 5x5 kernel that read input parity plane (oy, ox) of a stride-2 conv, in the order of the plane-grouped
 // pair pack (hdiff_pack_conv_weight_h2_s2); returns their number: 9, 6, 6 or 4
 int s2_plane_taps(int oy, int ox, int* ky, int* kx);

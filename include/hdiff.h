@@ -152,7 +152,7 @@ typedef struct hdiff_conv_desc {
    * full-resolution 1x1 / stride-1 conv with a ONE-tap pack from hdiff_pack_conv_weight_x3_taps (Cin % 16 == 0, H * W % 256 == 0);
    * NULL = always the fp32-input MFMA.  Tap order: hdiff_pack_conv_weight_x3 stores tap t = (t / 3, t % 3), so a plain 3x3
    * launch must list tap_dy[t] = t / 3 - 1, tap_dx[t] = t % 3 - 1 (any other order of the nine taps, and any list with a
-   * repeated tap, runs the fp32 kernel on wp instead); a pack made by hdiff_pack_conv_weight_x3_taps holds the taps in
+   * repeated tap or one that does not fill the 3x3, 3x2, 2x3 or 2x2 rectangle it spans, runs the fp32 kernel on wp instead); a pack made by hdiff_pack_conv_weight_x3_taps holds the taps in
    * the order of the list it was given, and the descriptor has to list them in that same order. */
   const void* wp_x3;
   /* optional (ABI 5): the fp16-pair form of the same kernel for the plain 3x3 / pad-1 conv WITH the GroupNorm + Swish prologue
