@@ -192,6 +192,9 @@ _PROTOS = {
     "hdiff_tile_ddim_step": (C.c_int, [C.c_void_p] * 12 + [C.c_int, C.c_void_p] + [C.c_int] * 8 + [C.c_void_p]),
     "hdiff_dpmpp_step": (C.c_int, [C.c_void_p] * 6 + [C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_void_p]),
     "hdiff_tile_dpmpp_step": (C.c_int, [C.c_void_p] * 13 + [C.c_int, C.c_int, C.c_void_p] + [C.c_int] * 8 + [C.c_void_p]),
+    "hdiff_randn_rows": (C.c_int, [C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_uint64, C.c_void_p]),
+    "hdiff_ddim_eta_step": (C.c_int, [C.c_void_p] * 6 + [C.c_int64, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
+    "hdiff_sample_stats": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
     "hdiff_resize_nearest": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "hdiff_avgpool_global": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "hdiff_train_b_loss_workspace": (C.c_int, [C.c_int64, C.POINTER(C.c_int64)]),

@@ -1,8 +1,10 @@
 // The per-step kernels of both samplers (gfx950): the seven update kernels -- ancestral DDPM, strided DDIM and DPM-Solver++(2M) of
 // the label-conditioned sampler (DiffusionFreeGuidence/DiffusionCondition.py; classifier-free guidance and the captured loop's
 // bookkeeping), DDIM and DPM-Solver++(2M) of the image-conditioned one (diffusion/Diffusion.py), untiled and over overlapping
-// windows -- and what a step runs around them: the time-vector fills, the counter decrement and the window crop.  All HBM- or
-// latency-bound streaming kernels, one launch beside a whole UNet evaluation.
+// windows -- and what a step runs around them: the time-vector fills, the counter decrement and the window crop.  Behind them the
+// three kernels of multi-sample posterior sampling: the DDIM update with its stochastic term (eta), the per-sample normal fill and
+// the mean / spread over an image's samples.  All HBM- or latency-bound streaming kernels, one launch beside a whole UNet
+// evaluation.
 //
 // Every update must round exactly like separate fp32 tensor ops (the reference's mul / sub / add; for the added solvers a plain
 // torch program of the same lines): one rounding per written operation.  fma contraction is forbidden in this file (hipcc
@@ -339,6 +341,87 @@ __global__ void dpmpp_step_kernel(const float* y, const float* __restrict__ eps,
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
+// Multi-sample posterior sampling of the image-conditioned sampler (diffusion/Diffusion.py, `posterior` and `eta=`): a batch is
+// `rows` samples of n_per floats, and every sample draws ALL its noise from a Philox stream of its own -- seeds[row], quads counted
+// WITHIN the row -- so that a sample's numbers depend on neither its place in the batch nor on the batch's size.
+// ---------------------------------------------------------------------------------------------------------------------
+// row r = hdiff_randn(n_per, seeds[r], offset), bit for bit: quad q of a row is Philox counter (q, offset) under the row's seed; the
+// last quad of a row with n_per % 4 != 0 is partly used and the next row starts a fresh one.  `wide`: out is 16-byte aligned and
+// n_per % 4 == 0, so every quad of every row is one aligned 16-byte store.
+__global__ void randn_rows_kernel(float* __restrict__ out, int64_t n_per, int64_t nq_row, int64_t nq,
+                                  const uint64_t* __restrict__ seeds, uint64_t offset, int wide) {
+  for (int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; g < nq; g += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t r = g / nq_row, q = g - r * nq_row;
+    const float4 zz = normal4(seeds[r], (uint64_t)q, offset);
+    const float z[4] = {zz.x, zz.y, zz.z, zz.w};
+    st4(out + r * n_per, q << 2, n_per, wide != 0, z);
+  }
+}
+
+// Diffusion.py:259-267 with the reference's stochastic term kept (eta != 0 there):
+//   y0 = (y - eps * sqrt(1 - at)) / sqrt(at) ;  y' = ((sqrt(at_next) * y0) + (c1 * z)) + (c2 * eps)
+// tab[k] = {sqrt(1 - at), sqrt(at), sqrt(at_next), c1, c2}.  z is read from `noise` or drawn per row: elements 4q .. 4q + 3 of
+// hdiff_randn(n_per, seeds[row], offset = k), StepNoise's convention.  The noise is added at every step, the last included, as the
+// reference's line does.  Every element is read and written by one thread: y and y_next may be the same buffer.
+__global__ void ddim_eta_step_kernel(const float* y, const float* __restrict__ eps, const float* __restrict__ noise, float* y_next,
+                                     const float* __restrict__ tab, const uint64_t* __restrict__ seeds, int64_t n_per,
+                                     int64_t nq_row, int64_t nq, const int32_t* __restrict__ step_ptr, int nsteps,
+                                     int32_t* __restrict__ nan_flag, int vec) {
+  const int k = step_index(*step_ptr, nsteps);
+  const float* row = tab + 5 * (size_t)k;
+  const float s1m = row[0], sa = row[1], san = row[2], c1 = row[3], c2 = row[4];
+  bool bad = false;
+  for (int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; g < nq; g += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t r = g / nq_row, q = g - r * nq_row, i0 = q << 2, base = r * n_per;
+    const bool wide = vec != 0;
+    float yv[4], ev[4], z[4], v[4];
+    ld4(y + base, i0, n_per, wide, yv);
+    ld4(eps + base, i0, n_per, wide, ev);
+    if (noise != nullptr) {
+      ld4(noise + base, i0, n_per, wide, z);
+    } else {
+      const float4 zz = normal4(seeds[r], (uint64_t)q, (uint64_t)(uint32_t)k);
+      z[0] = zz.x; z[1] = zz.y; z[2] = zz.z; z[3] = zz.w;
+    }
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const float y0 = (yv[e] - ev[e] * s1m) / sa;
+      v[e] = ((san * y0) + (c1 * z[e])) + (c2 * ev[e]);
+      bad |= (i0 + e < n_per) && (v[e] != v[e]);
+    }
+    st4(y_next + base, i0, n_per, wide, v);
+  }
+  flag_nan(bad, nan_flag);
+}
+
+// Mean and spread of the K samples of every image, samples [B][K][n] -> mean, std [B][n].  Per element, in double, in replica order:
+//   m = (x_0 + x_1 + ... ) / K ;  std = sqrt(((x_0 - m)^2 + (x_1 - m)^2 + ...) / (K - 1)), exactly 0 for K = 1
+// each rounded once to fp32.  One thread per element, K coalesced reads twice over (the second pass hits the cache); no atomics, the
+// order of the sums is fixed.  An element's result depends on its own K values alone.
+__global__ void sample_stats_kernel(const float* __restrict__ x, int K, int64_t n, int64_t total, float* __restrict__ mean,
+                                    float* __restrict__ sd) {
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t b = i / n, j = i - b * n;
+    const float* p = x + b * K * n + j;
+    double s = (double)p[0];
+    for (int k = 1; k < K; ++k) s = s + (double)p[(int64_t)k * n];
+    const double m = s / (double)K;
+    double sq = 0.0;
+    if (K > 1) {
+      const double d0 = (double)p[0] - m;
+      sq = d0 * d0;
+      for (int k = 1; k < K; ++k) {
+        const double d = (double)p[(int64_t)k * n] - m;
+        sq = sq + d * d;
+      }
+      sq = sqrt(sq / (double)(K - 1));
+    }
+    mean[i] = (float)m;
+    sd[i] = (float)sq;
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
 // Image-conditioned sampler over overlapping windows (diffusion/Diffusion.py, `tile=`): the crop of model-sized windows out of
 // the full image, and the one full-image kernel of a step -- the weighted blend of the windows' noise estimates fused with the
 // update.  One float per thread and iteration, the 64-bit linear index taken apart by division (not profiled on their own: a few
@@ -588,6 +671,44 @@ int hdiff_dpmpp_step(const float* y, const float* eps, float* y_next, float* x0_
   hipLaunchKernelGGL(dpmpp_step_kernel, dim3(grid_ceil_8k(n, 4)), dim3(256), 0, (hipStream_t)stream, y, eps, y_next, x0_prev, tab,
                      step_ptr, nsteps, clip_x0, nan_flag, n, vec);
   HDIFF_CHECK_LAUNCH("dpmpp_step_kernel");
+  return HDIFF_OK;
+}
+
+int hdiff_randn_rows(float* out, int rows, int64_t n_per, const uint64_t* seeds, uint64_t offset, hdiff_stream_t stream) {
+  HDIFF_CHECK_ARG(out && seeds, "randn_rows: null pointer");
+  HDIFF_CHECK_ARG(rows > 0 && n_per > 0, "randn_rows: bad sizes rows=%d n_per=%lld", rows, (long long)n_per);
+  (void)hipGetLastError();  // drop any stale error left by another HIP user in this thread
+  const int64_t nq_row = (n_per + 3) >> 2, nq = nq_row * rows;
+  const int wide = aligned16(out) && (n_per & 3) == 0;
+  hipLaunchKernelGGL(randn_rows_kernel, dim3(grid_ceil_8k(nq)), dim3(256), 0, (hipStream_t)stream, out, n_per, nq_row, nq, seeds,
+                     offset, wide);
+  HDIFF_CHECK_LAUNCH("randn_rows_kernel");
+  return HDIFF_OK;
+}
+
+int hdiff_ddim_eta_step(const float* y, const float* eps, const float* noise, float* y_next, const float* tab,
+                        const uint64_t* seeds, int64_t n_per, const int32_t* step_ptr, int nsteps, int32_t* nan_flag, int rows,
+                        hdiff_stream_t stream) {
+  HDIFF_CHECK_ARG(y && eps && y_next && tab && step_ptr && nan_flag && (noise || seeds), "ddim_eta_step: null pointer");
+  HDIFF_CHECK_ARG(rows > 0 && n_per > 0 && nsteps > 0, "ddim_eta_step: bad sizes rows=%d n_per=%lld nsteps=%d", rows,
+                  (long long)n_per, nsteps);
+  (void)hipGetLastError();  // drop any stale error left by another HIP user in this thread
+  const int64_t nq_row = (n_per + 3) >> 2, nq = nq_row * rows;
+  const int vec = aligned16(y) && aligned16(eps) && aligned16(noise) && aligned16(y_next) && (n_per & 3) == 0;
+  hipLaunchKernelGGL(ddim_eta_step_kernel, dim3(grid_ceil_8k(nq)), dim3(256), 0, (hipStream_t)stream, y, eps, noise, y_next, tab,
+                     seeds, n_per, nq_row, nq, step_ptr, nsteps, nan_flag, vec);
+  HDIFF_CHECK_LAUNCH("ddim_eta_step_kernel");
+  return HDIFF_OK;
+}
+
+int hdiff_sample_stats(const float* samples, int B, int K, int64_t n, float* mean, float* std, hdiff_stream_t stream) {
+  HDIFF_CHECK_ARG(samples && mean && std, "sample_stats: null pointer");
+  HDIFF_CHECK_ARG(B > 0 && K > 0 && n > 0, "sample_stats: bad sizes B=%d K=%d n=%lld", B, K, (long long)n);
+  (void)hipGetLastError();  // drop any stale error left by another HIP user in this thread
+  const int64_t total = (int64_t)B * n;
+  hipLaunchKernelGGL(sample_stats_kernel, dim3(grid_ceil_8k(total)), dim3(256), 0, (hipStream_t)stream, samples, K, n, total, mean,
+                     std);
+  HDIFF_CHECK_LAUNCH("sample_stats_kernel");
   return HDIFF_OK;
 }
 

@@ -19,7 +19,10 @@ the noise estimates are blended where they overlap and ONE DDIM update is applie
 (``csrc/sampler_step.hip``).  Without ``tile`` nothing changes.  ``forward(..., solver="dpmpp2m", spacing=, timesteps=)`` replaces the
 first-order DDIM update by DPM-Solver++(2M) on logSNR-uniform time steps (``dpmpp_table`` / ``logsnr_timesteps`` of
 ``schedules`` with ``shift=1``: this sampler reads ``alphas_bar[t + 1]``) -- still one model evaluation and one update kernel per
-step (the same file), untiled and over windows.  Without ``solver`` nothing changes.
+step (the same file), untiled and over windows.  Without ``solver`` nothing changes.  ``forward(..., eta=, seed=, image_ids=)`` puts the
+reference's ``c1 * randn`` term back with per-image Philox streams, and ``posterior(img, K, ...)`` draws K samples per image in one
+plan and returns their mean and per-pixel spread (the same file: ``hdiff_ddim_eta_step``, ``hdiff_randn_rows``,
+``hdiff_sample_stats``).  Without those arguments nothing changes.
 
 Trainer underneath: q_sample and the 3 + 3 channel concat are HIP launches, the DynamicUNet runs its autograd path
 (``autograd.dyn_unet_forward_with_grad``) and the loss tail -- the squared error, ``y_0_pred`` and the angular-colour term,
@@ -43,10 +46,11 @@ import torch.nn.functional as F
 from .. import _capi
 from .. import engine as E
 from ..engine import gpu_input as _gpu_input, index_vector as _timesteps
-from ..schedules import _checked_timesteps, check_solver_spacing, dpmpp_table, logsnr_timesteps, spacing_of
+from ..schedules import (Y_T_OFFSET, _checked_timesteps, check_solver_spacing, dpmpp_table, logsnr_timesteps, posterior_seed,
+                         spacing_of)
 
 __all__ = ["extract", "GaussianDiffusionTrainer", "GaussianDiffusionSampler", "tile_origins", "tile_weights", "logsnr_timesteps",
-           "dpmpp_table"]
+           "dpmpp_table", "posterior_seed", "PosteriorSamples"]
 
 
 def extract(v, t, x_shape):
@@ -288,9 +292,12 @@ def _dpmpp_tables(sampler: "GaussianDiffusionSampler", seq, device):
     return tab.float().contiguous().to(device), torch.tensor(seq, dtype=torch.int32, device=device)
 
 
-def _ddim_tables(sampler: "GaussianDiffusionSampler", ddim_step: Optional[int], device, seq: Optional[List[int]] = None):
+def _ddim_tables(sampler: "GaussianDiffusionSampler", ddim_step: Optional[int], device, seq: Optional[List[int]] = None,
+                 eta: Optional[float] = None):
     """-> (tab[n, 4] fp32, t_tab[n] int32), indexed by the down-counting step counter k (k = n - 1 first): the same fp32 ops as
-    the reference's :250-262, on the reference's time steps or on the increasing list ``seq``."""
+    the reference's :250-262, on the reference's time steps or on the increasing list ``seq``.  With ``eta`` (a number, 0 included)
+    the reference's ``eta = 0`` is replaced by it and the rows are ``[n, 5]`` = {sqrt(1 - at), sqrt(at), sqrt(at_next), c1, c2}, the
+    rows of ``hdiff_ddim_eta_step``; ``eta=0`` gives the four columns of the call without it bit for bit, and c1 = 0."""
     seq = _uniform_sequence(ddim_step) if seq is None else list(seq)
     seq_next = [-1] + seq[:-1]
     ab = sampler.alphas_bar
@@ -299,27 +306,70 @@ def _ddim_tables(sampler: "GaussianDiffusionSampler", ddim_step: Optional[int], 
     ab = ab.to(device)
     at = ab[torch.tensor(seq, device=device) + 1].float()
     at_next = ab[torch.tensor(seq_next, device=device) + 1].float()
-    c1 = 0 * ((1 - at / at_next) * (1 - at_next) / (1 - at)).sqrt()
+    c1 = (0 if eta is None else eta) * ((1 - at / at_next) * (1 - at_next) / (1 - at)).sqrt()
     c2 = ((1 - at_next) - c1 ** 2).sqrt()
-    tab = torch.stack([(1 - at).sqrt(), at.sqrt(), at_next.sqrt(), c2], dim=1).contiguous()
+    cols = [(1 - at).sqrt(), at.sqrt(), at_next.sqrt(), c2]
+    if eta is not None:
+        if not bool(torch.isfinite(c2).all()):
+            raise ValueError(f"eta = {eta} is too large for these time steps: (1 - at_next) - c1^2 is negative at some step")
+        cols.insert(3, c1)
+    tab = torch.stack(cols, dim=1).contiguous()
     return tab, torch.tensor(seq, dtype=torch.int32, device=device)
 
 
-def _loop_tables(sampler: "GaussianDiffusionSampler", B: int, H: int, W: int, device, ddim_step: Optional[int], seq, solver: str):
+def _loop_tables(sampler: "GaussianDiffusionSampler", B: int, H: int, W: int, device, ddim_step: Optional[int], seq, solver: str,
+                 eta: Optional[float] = None):
     """-> (tab, t_tab, x0_prev) of the DDIM loop on the increasing time steps ``seq`` (None: the reference's, from ``ddim_step``).
     ``x0_prev`` is the full-size history solver="dpmpp2m" reads (from the second step on) and writes, else None."""
     if solver == "dpmpp2m":
         tab, t_tab = _dpmpp_tables(sampler, _uniform_sequence(ddim_step) if seq is None else seq, device)
         return tab, t_tab, torch.empty(B, 3, H, W, device=device)
-    return _ddim_tables(sampler, ddim_step, device, seq) + (None,)
+    return _ddim_tables(sampler, ddim_step, device, seq, eta) + (None,)
+
+
+def _checked_eta(eta) -> float:
+    if isinstance(eta, bool) or not isinstance(eta, (int, float)) or eta != eta or eta in (float("inf"), -float("inf")) or eta < 0:
+        raise ValueError(f"eta must be a finite number >= 0, got {eta!r}")
+    return float(eta)
+
+
+def _row_seeds(seed: int, image_ids, B: int, replicas: int = 1) -> List[int]:
+    """The Philox seeds of a batch of ``B`` images x ``replicas`` samples, image-major, as the int64 bit patterns a torch tensor
+    holds.  An entry of ``image_ids`` is an integer (replica r of it is ``posterior_seed(seed, id, r)``) or, for one row of a batch laid
+    out by hand, an ``(image, replica)`` pair."""
+    ids = list(range(B)) if image_ids is None else list(image_ids)
+    if len(ids) != B:
+        raise ValueError(f"image_ids names {len(ids)} images, the batch holds {B}")
+    out = []
+    for entry in ids:
+        pair = isinstance(entry, (tuple, list))
+        if pair and (len(entry) != 2 or replicas != 1):
+            raise ValueError(f"image_ids: an entry is an integer or an (image, replica) pair of a single-sample call, got {entry!r}")
+        for r in range(replicas):
+            s = posterior_seed(seed, entry[0] if pair else entry, entry[1] if pair else r)
+            out.append(s - (1 << 64) if s >= (1 << 63) else s)
+    return out
+
+
+class PosteriorSamples:
+    """What ``GaussianDiffusionSampler.posterior`` returns: ``mean`` and ``std`` ``[B, 3, H, W]`` over the K clipped samples of every
+    image (``hdiff_sample_stats``), and ``samples`` ``[B, K, 3, H, W]`` or None."""
+
+    __slots__ = ("mean", "std", "samples")
+
+    def __init__(self, mean: torch.Tensor, std: torch.Tensor, samples: Optional[torch.Tensor]):
+        self.mean, self.std, self.samples = mean, std, samples
 
 
 class _StepPlan:
     """One captured sampling step for a fixed (B, H, W) and mode: fill t -> DynamicUNet -> update -> advance the counter."""
 
     def __init__(self, sampler: "GaussianDiffusionSampler", B: int, H: int, W: int, device, ddim_step: Optional[int],
-                 inject_noise: bool = False, seed: int = 0, solver: str = "ddim", seq: Optional[List[int]] = None):
-        """``seq``: the increasing time steps of the DDIM / DPM-Solver++(2M) loop (None: the reference's, from ``ddim_step``)."""
+                 inject_noise: bool = False, seed: int = 0, solver: str = "ddim", seq: Optional[List[int]] = None,
+                 eta: Optional[float] = None):
+        """``seq``: the increasing time steps of the DDIM / DPM-Solver++(2M) loop (None: the reference's, from ``ddim_step``).
+        ``eta``: the DDIM loop with its stochastic term (``hdiff_ddim_eta_step``): row b draws under ``self.seeds[b]``, which the
+        caller fills before a run, or reads ``self.noise`` with ``inject_noise``."""
         self.unet = sampler.model.plan_for(B, H, W, device, True)
         up = self.unet
         if up.out_hw != (H, W):
@@ -347,13 +397,18 @@ class _StepPlan:
                    self.sigma.data_ptr(), self.step.data_ptr(), int(sampler.T), C.c_double(0.0), C.c_uint64(seed),
                    self.nan_flag.data_ptr(), n)
         else:
-            self.tab, self.t_tab, self.x0_prev = _loop_tables(sampler, B, H, W, device, ddim_step, seq, solver)
+            self.tab, self.t_tab, self.x0_prev = _loop_tables(sampler, B, H, W, device, ddim_step, seq, solver, eta)
             self.n_steps = int(self.t_tab.numel())
             p.call("hdiff_fill_from_table", up.t.data_ptr(), self.t_tab.data_ptr(), self.step.data_ptr(), self.n_steps, B)
             p.ops.extend(up.plan.ops)
             if solver == "dpmpp2m":         # the same step with the second-order update; the plan owns the x0 history
                 p.call("hdiff_dpmpp_step", up.y.data_ptr(), up.out.data_ptr(), up.y.data_ptr(), self.x0_prev.data_ptr(),
                        self.tab.data_ptr(), self.step.data_ptr(), self.n_steps, 0, self.nan_flag.data_ptr(), n)
+            elif eta is not None:           # the same step with c1 * z kept: one Philox stream per row, or the injected draws
+                self.seeds = torch.zeros(B, dtype=torch.int64, device=device)
+                p.call("hdiff_ddim_eta_step", up.y.data_ptr(), up.out.data_ptr(), self.noise.data_ptr() if inject_noise else None,
+                       up.y.data_ptr(), self.tab.data_ptr(), self.seeds.data_ptr(), 3 * H * W, self.step.data_ptr(), self.n_steps,
+                       self.nan_flag.data_ptr(), B)
             else:
                 p.call("hdiff_ddim_step", up.y.data_ptr(), up.out.data_ptr(), up.y.data_ptr(), self.tab.data_ptr(),
                        self.step.data_ptr(), self.n_steps, self.nan_flag.data_ptr(), n)
@@ -469,7 +524,8 @@ class GaussianDiffusionSampler(nn.Module):
     def forward(self, input_image, ddim=False, unconditional_guidance_scale=1, ddim_step=None, *, y_T=None,
                 noise_by_step: Optional[List[torch.Tensor]] = None, trajectory: Optional[List[torch.Tensor]] = None,
                 tile: Optional[int] = None, tile_overlap: Optional[int] = None, tile_batch: Optional[int] = None,
-                solver: str = "ddim", spacing: Optional[str] = None, timesteps=None):
+                solver: str = "ddim", spacing: Optional[str] = None, timesteps=None, eta: float = 0.0, seed: Optional[int] = None,
+                image_ids=None):
         """``y_T`` / ``noise_by_step`` inject the random draws (parity runs; ``noise_by_step[k]`` is the k-th per-step draw of
         the ancestral loop, in call order); by default they come from torch's generator exactly where the reference draws
         them.  ``trajectory`` collects the pre-clip y_t after every step.  Called with autograd enabled (the reference would
@@ -492,8 +548,27 @@ class GaussianDiffusionSampler(nn.Module):
           * ``spacing``: the ``ddim_step`` time steps tau -- "uniform", the reference's ``range(0, 1000, int(1000 / ddim_step))``, or
             "logsnr", ``logsnr_timesteps(betas, ddim_step, shift=1)``; ``None`` is uniform for "ddim" and logsnr for "dpmpp2m".
           * ``timesteps``: an explicit strictly increasing list in ``[0, T - 2]`` in place of ``ddim_step`` (and of ``spacing``).
-        The model's time input at step k is ``tau_k``, as in the reference's loop."""
+        The model's time input at step k is ``tau_k``, as in the reference's loop.
+
+        The reference's stochastic term and per-image noise (additions; ``ddim=True``, ``solver="ddim"``, untiled):
+          * ``eta``: a finite number >= 0 in place of the ``eta = 0`` the reference has written in (:260): every step, the last
+            included, adds ``c1 * z`` with ``c1 = eta * sqrt((1 - at / at_next) * (1 - at_next) / (1 - at))`` (``hdiff_ddim_eta_step``).
+            ``z`` of row b at the step whose counter reads k is ``hdiff_randn(3HW, s_b, offset = k)``, or ``noise_by_step[j]`` for the
+            j-th step in call order.  ``eta=0`` runs what ran before.
+          * ``seed`` / ``image_ids``: ``s_b = posterior_seed(seed, image_ids[b], 0)`` (``image_ids`` defaults to ``range(B)``; an entry
+            may be an ``(image, replica)`` pair).  With ``seed`` given and no ``y_T``, ``y_T`` of row b is ``hdiff_randn(3HW, s_b,
+            offset = 2^32 - 1)``: the call then reads nothing of torch's generator, and a row's result does not depend on the batch
+            it is in.  ``seed=None`` with ``eta > 0`` draws one int64 from torch's CPU generator, as the ancestral path does."""
         seq = self._solver_arguments(ddim, ddim_step, solver, spacing, timesteps)
+        eta = _checked_eta(eta)
+        if eta > 0 and (not ddim or solver != "ddim"):
+            raise ValueError("eta > 0 needs ddim=True and solver='ddim': DPM-Solver++(2M) here is the deterministic multistep solver")
+        if (eta > 0 or seed is not None or image_ids is not None) and tile is not None:
+            raise ValueError("eta / seed / image_ids are not available with tile: the windowed loop is deterministic")
+        if (seed is not None or image_ids is not None) and not ddim:
+            raise ValueError("seed / image_ids need ddim=True")
+        if image_ids is not None and seed is None and eta == 0:
+            raise ValueError("image_ids was given without seed")
         if tile is None:
             if tile_overlap is not None or tile_batch is not None:
                 raise ValueError("tile_overlap / tile_batch were given without tile")
@@ -519,7 +594,7 @@ class GaussianDiffusionSampler(nn.Module):
                 return self._forward_tiled(input_image, ddim_step, y_T, trajectory, tile, tile_overlap, tile_batch, solver, spacing,
                                            seq)
             return self._forward(input_image, ddim, unconditional_guidance_scale, ddim_step, y_T, noise_by_step, trajectory, solver,
-                                 spacing, seq)
+                                 spacing, seq, eta, seed, image_ids)
 
     def _solver_arguments(self, ddim, ddim_step, solver, spacing, timesteps):
         """-> the time steps of the loop as a tuple, or None for the reference's own (``ValueError`` otherwise).  Looks at no
@@ -561,16 +636,18 @@ class GaussianDiffusionSampler(nn.Module):
         sp.unet.plan.pack_weights()     # once per call: also catches writes through p.data, which p._version does not see
         return sp
 
-    def _run(self, sp, y_buffer, n_steps, eager, noise_by_step, trajectory):
+    def _run(self, sp, y_buffer, n_steps, eager, noise_by_step, trajectory, noise_steps=None, out=None, n=None):
         """``n_steps`` runs (eager) or replays of the captured step on the state in ``y_buffer``, then the clip.
-        ``noise_by_step[k]`` goes into the plan's noise buffer before step k (the last step adds none)."""
+        ``noise_by_step[k]`` goes into the plan's noise buffer before step k (the last step adds none; ``noise_steps=n_steps``: every
+        step does, the loop with ``eta``).  ``out`` / ``n``: clip the first ``n`` floats into ``out`` in place of a new tensor."""
+        noise_steps = n_steps - 1 if noise_steps is None else noise_steps
         sp.step.fill_(n_steps - 1)
         sp.nan_flag.zero_()
         stream = torch.cuda.current_stream(y_buffer.device).cuda_stream
         if not eager:
             sp.plan.capture()
         for k in range(n_steps):
-            if noise_by_step is not None and k < n_steps - 1:
+            if noise_by_step is not None and k < noise_steps:
                 sp.noise.copy_(noise_by_step[k])
             if eager:
                 sp.plan.run(stream)
@@ -578,8 +655,9 @@ class GaussianDiffusionSampler(nn.Module):
                 sp.plan.replay(stream)
             if trajectory is not None:
                 trajectory.append(y_buffer.clone())
-        out = torch.empty_like(y_buffer)
-        _capi.check(_capi.lib().hdiff_clip(y_buffer.data_ptr(), out.data_ptr(), C.c_float(-1.0), C.c_float(1.0), sp.n, stream),
+        if out is None:
+            out, n = torch.empty_like(y_buffer), sp.n
+        _capi.check(_capi.lib().hdiff_clip(y_buffer.data_ptr(), out.data_ptr(), C.c_float(-1.0), C.c_float(1.0), n, stream),
                     "clip")
         return out
 
@@ -600,20 +678,97 @@ class GaussianDiffusionSampler(nn.Module):
         eager = trajectory is not None or sp.n_steps < self.GRAPH_MIN_STEPS
         return self._run(sp, sp.y, sp.n_steps, eager, None, trajectory)
 
+    def _step_plan(self, B, H, W, dev, ddim_step, inject, seed, solver, spacing, seq, eta):
+        """The untiled plan of ``forward`` and ``posterior``.  Without ``eta`` the key and the launch list are those of the call
+        before ``eta`` existed; with it the key gains one entry and the seeds live in the plan's device buffer, not in the key."""
+        mode = _capi.lib().hdiff_get_contraction_mode()
+        key = (B, H, W, str(dev), ddim_step, inject, seed, mode, None, None, None, solver, spacing, seq)   # the three None: tile, ...
+        if eta > 0:
+            return self._plan(key + (("eta", eta),), dev, lambda: _StepPlan(self, B, H, W, dev, ddim_step, inject, seed, solver, seq, eta))
+        return self._plan(key, dev, lambda: _StepPlan(self, B, H, W, dev, ddim_step, inject, seed, solver, seq))
+
     def _forward(self, input_image, ddim, unconditional_guidance_scale, ddim_step, y_T, noise_by_step, trajectory, solver="ddim",
-                 spacing=None, seq=None):
+                 spacing=None, seq=None, eta=0.0, row_seed=None, image_ids=None):
         img, ddim_step = self._input(input_image, ddim, ddim_step, seq)
         B, _, H, W = (int(v) for v in img.shape)
         dev = img.device
-        inject = (not ddim) and noise_by_step is not None
+        inject = ((not ddim) or eta > 0) and noise_by_step is not None
         seed = 0 if (ddim or inject) else int(torch.empty((), dtype=torch.int64).random_().item())
-        mode = _capi.lib().hdiff_get_contraction_mode()
-        sp = self._plan((B, H, W, str(dev), ddim_step, inject, seed, mode, None, None, None, solver, spacing, seq), dev,
-                        lambda: _StepPlan(self, B, H, W, dev, ddim_step, inject, seed, solver, seq))     # the three None: tile, ...
+        seeds, drawn = None, row_seed is None       # per-row Philox seeds; a drawn seed leaves y_T to torch's generator, as before
+        if row_seed is not None or (eta > 0 and not inject):
+            if drawn:
+                row_seed = int(torch.empty((), dtype=torch.int64).random_().item())
+            seeds = torch.tensor(_row_seeds(row_seed, image_ids, B), dtype=torch.int64).to(dev)
+        sp = self._step_plan(B, H, W, dev, ddim_step, inject, seed, solver, spacing, seq, eta)
         self.model.dynamic_forward(torch.cat([img, img], dim=1))    # the reference runs it on every call (requires_grad only)
-        y = torch.randn_like(img) if y_T is None else y_T            # :226 / :239
+        if y_T is None and seeds is not None and not drawn:
+            y = torch.empty_like(img)
+            _capi.check(_capi.lib().hdiff_randn_rows(y.data_ptr(), B, 3 * H * W, seeds.data_ptr(), C.c_uint64(Y_T_OFFSET),
+                                                     torch.cuda.current_stream(dev).cuda_stream), "randn_rows")
+        else:
+            y = torch.randn_like(img) if y_T is None else y_T        # :226 / :239
         up = sp.unet
         up.cond.copy_(img)
         up.y.copy_(y)
+        if eta > 0 and seeds is not None:
+            sp.seeds.copy_(seeds)
         eager = inject or trajectory is not None or sp.n_steps < self.GRAPH_MIN_STEPS
-        return self._run(sp, up.y, sp.n_steps, eager, noise_by_step if inject else None, trajectory)
+        return self._run(sp, up.y, sp.n_steps, eager, noise_by_step if inject else None, trajectory,
+                         sp.n_steps if eta > 0 else None)
+
+    def posterior(self, input_image, samples, *, ddim_step=None, timesteps=None, spacing=None, solver="ddim", eta=0.0, seed=0,
+                  image_ids=None, sample_batch=None, keep_samples=False) -> PosteriorSamples:
+        """``samples`` = K draws of the DDIM loop per image, their mean and their per-pixel spread (an addition to the reference's
+        surface).  Sample ``(b, r)`` is what ``forward`` returns for image b under the Philox seed ``posterior_seed(seed,
+        image_ids[b], r)``: its ``y_T`` and, with ``eta > 0``, the noise of every step come from that one stream, so a sample depends
+        on neither its batch, ``sample_batch`` nor K, and the first K samples of a larger run are the samples of the K run.
+        ONE step plan at batch ``min(B * K, sample_batch)`` is looped over chunks of samples (the conditioning image repeated per
+        replica, ``y_T`` from ``hdiff_randn_rows``; a short last chunk is padded with repeats of the last sample, whose results are
+        dropped); every clipped sample lands in one ``[B, K, 3, H, W]`` buffer and one ``hdiff_sample_stats`` launch follows.
+        ``solver="dpmpp2m"`` needs ``eta == 0``: the samples then differ through ``y_T`` alone.  The hipGraph policy is ``forward``'s
+        (``GRAPH_MIN_STEPS``); nothing here synchronises.
+        -> ``PosteriorSamples``: ``mean`` ``[B, 3, H, W]``, the mean of the clipped samples, in [-1, 1]; ``std``, the same shape,
+        their unbiased standard deviation (0 for K = 1); ``samples`` with ``keep_samples``, else None."""
+        K = _int_arg("samples", samples, 1)
+        eta = _checked_eta(eta)
+        if eta > 0 and solver != "ddim":
+            raise ValueError("eta > 0 needs solver='ddim': DPM-Solver++(2M) here is the deterministic multistep solver")
+        if sample_batch is not None:
+            sample_batch = _int_arg("sample_batch", sample_batch, 1)
+        _int_arg("seed", seed, -(1 << 63))
+        seq = self._solver_arguments(True, ddim_step, solver, spacing, timesteps)
+        if torch.is_grad_enabled() and input_image.requires_grad:
+            raise RuntimeError("GaussianDiffusionSampler.posterior: the input requires grad, but the sampling loop runs under "
+                               "torch.no_grad() and cannot be differentiated; detach it or call under torch.no_grad()")
+        with torch.no_grad():
+            img, ddim_step = self._input(input_image, True, ddim_step, seq)
+            B, _, H, W = (int(v) for v in img.shape)
+            dev, per = img.device, 3 * H * W
+            R = B * K
+            PB = R if sample_batch is None else min(R, sample_batch)
+            chunks = [(r0, min(PB, R - r0)) for r0 in range(0, R, PB)]
+            rows = _row_seeds(seed, image_ids, B, K)
+            # one upload: the R seeds in order, then those of every chunk's slots (a padding slot repeats the last sample, as
+            # hdiff_tile_gather does)
+            table = torch.tensor(rows + [rows[min(r0 + s, R - 1)] for r0, _ in chunks for s in range(PB)], dtype=torch.int64).to(dev)
+            seeds = table[R:]
+            sp = self._step_plan(PB, H, W, dev, ddim_step, False, 0, solver, spacing, seq, eta)
+            self.model.dynamic_forward(torch.cat([img, img], dim=1))
+            lib, up = _capi.lib(), sp.unet
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            cond = img.repeat_interleave(K, dim=0).contiguous()
+            y_T = torch.empty(R, 3, H, W, device=dev)
+            _capi.check(lib.hdiff_randn_rows(y_T.data_ptr(), R, per, table.data_ptr(), C.c_uint64(Y_T_OFFSET), stream), "randn_rows")
+            out = torch.empty(B, K, 3, H, W, device=dev)
+            zero = torch.zeros(1, dtype=torch.int32, device=dev)
+            eager = sp.n_steps < self.GRAPH_MIN_STEPS
+            for c, (r0, valid) in enumerate(chunks):
+                for src, dst in ((cond, up.cond), (y_T, up.y)):       # samples r0 .. r0 + PB - 1, the last one repeated
+                    _capi.check(lib.hdiff_tile_gather(src.data_ptr(), dst.data_ptr(), zero.data_ptr(), zero.data_ptr(), R, 3, H, W, 1, 1,
+                                                      H, W, r0, PB, stream), "tile_gather")
+                if eta > 0:
+                    sp.seeds.copy_(seeds[c * PB:(c + 1) * PB])
+                self._run(sp, up.y, sp.n_steps, eager, None, None, out=out.view(R, per)[r0], n=valid * per)
+            mean, std = torch.empty(B, 3, H, W, device=dev), torch.empty(B, 3, H, W, device=dev)
+            _capi.check(lib.hdiff_sample_stats(out.data_ptr(), B, K, per, mean.data_ptr(), std.data_ptr(), stream), "sample_stats")
+        return PosteriorSamples(mean, std, out if keep_samples else None)

@@ -83,7 +83,8 @@ def write_res(path: str, result: Dict[str, object], keys=RES_KEYS) -> None:
 def evaluate(sampler, batches: Iterable, *, ddim_step: int, tile: Optional[int] = None, tile_overlap: Optional[int] = None,
              tile_batch: Optional[int] = None, save_dir: Optional[str] = None, collect: Optional[List[torch.Tensor]] = None,
              meter=None, solver: Optional[str] = None, spacing: Optional[str] = None, uciqe: bool = False,
-             uciqe_scale: float = 1.0, lpips=None, distribution=None, transfer=None, niqe=None) -> Dict[str, object]:
+             uciqe_scale: float = 1.0, lpips=None, distribution=None, transfer=None, niqe=None, samples: Optional[int] = None,
+             eta: float = 0.0, sample_seed: int = 0, sample_batch: Optional[int] = None, std_gain: float = 4.0) -> Dict[str, object]:
     """Samples and scores a set.  ``batches`` yields ``(input, target)`` or ``(input, target, names)``: CHW images in [0, 255] as
     ``Underwater_Dataset`` / ``Atmospheric_Dataset`` produce them, batched.  Per batch: ``out = sampler(input, ddim=True,
     unconditional_guidance_scale=1, ddim_step=ddim_step, tile=...)`` (rotinas.py:907), then ``(out + 1) / 2`` is scored against
@@ -111,7 +112,28 @@ def evaluate(sampler, batches: Iterable, *, ddim_step: int, tile: Optional[int] 
     written (one synchronisation per image, beside the one of the file): the result gains ``"niqe_full"`` (the same mean),
     ``"niqe_full_per_image"`` and ``"niqe_full_undefined"``, and ``res.txt`` one more line, ``niqe_full_orgin_avg:``.  Without it
     nothing of that is loaded, launched or written.
+    ``samples=K`` (an integer >= 1): every batch goes through ``sampler.posterior(input, K, eta=eta, seed=sample_seed,
+    image_ids=<the running indices of its images in the set>, sample_batch=sample_batch, ...)`` in place of one ``sampler`` call.  The
+    MEAN of the K clipped samples is the image that is scored, saved, and handed to ``distribution`` and ``transfer``; a second meter
+    of the same configuration scores every replica, and the result gains ``"samples"`` (K), ``"per_sample"`` (``{column: [the set
+    mean of replica 0, 1, ...]}``), ``"sample_avg"`` / ``"sample_std"`` (``{column: mean / unbiased std of those K set means}``; the
+    spread is 0 for K = 1) and ``"uncertainty"`` (the mean of ``std / 2``, the per-pixel spread on the [0, 1] scale, over the set).
+    ``res.txt`` keeps its lines and gains, behind them, ``samples:``, for every per-image score ``<name>_sample_avg:`` and
+    ``<name>_sample_std:`` (``psnr_sample_avg:`` ...; the set-level ``fd`` / ``kid`` and ``niqe_full`` have none), and
+    ``uncertainty_avg:``.  With ``save_dir``, ``<save_dir>/std/<name>`` holds ``rint(255 * clamp(std_gain * std / 2, 0, 1))``;
+    ``std_gain`` is a display constant and nothing backs its default.  The noise of an image belongs to its index in the set: the
+    result depends on neither torch's generator nor the batch size.  ``tile`` cannot be combined with it.  Without ``samples`` (and
+    with ``eta == 0``) nothing of this is constructed, launched or written; ``eta`` without ``samples`` is refused.
     Returns ``QualityMeter.compute()``'s dict."""
+    if samples is None and eta != 0:
+        raise ValueError("evaluate: eta= goes with samples=")
+    if samples is not None:
+        if isinstance(samples, bool) or not isinstance(samples, int) or samples < 1:
+            raise ValueError(f"evaluate: samples must be an integer >= 1, got {samples!r}")
+        if tile is not None:
+            raise ValueError("evaluate: samples= cannot be combined with tile=")
+        if not hasattr(sampler, "posterior"):
+            raise TypeError("evaluate: samples= needs a sampler with a posterior() method (diffusion.Diffusion.GaussianDiffusionSampler)")
     transfer = _transfer_settings(transfer)
     if transfer is not None and save_dir is None:
         raise ValueError("evaluate: transfer= writes full-size images and needs save_dir=")
@@ -134,6 +156,11 @@ def evaluate(sampler, batches: Iterable, *, ddim_step: int, tile: Optional[int] 
             os.makedirs(os.path.join(save_dir, "full"), exist_ok=True)
     tile_kw = {} if tile is None else dict(tile=tile, tile_overlap=tile_overlap, tile_batch=tile_batch)
     tile_kw.update({k: v for k, v in (("solver", solver), ("spacing", spacing)) if v is not None})
+    replicas = None
+    if samples is not None:
+        replicas = _ReplicaScores(meter, samples)
+        if save_dir is not None:
+            os.makedirs(os.path.join(save_dir, "std"), exist_ok=True)
     done = 0
     with torch.no_grad():
         for batch in batches:
@@ -142,7 +169,15 @@ def evaluate(sampler, batches: Iterable, *, ddim_step: int, tile: Optional[int] 
             originals = _originals(batch, int(inp.shape[0])) if transfer is not None else None
             inp = (inp if dev is None else inp.to(dev)).float()
             target = (target if dev is None else target.to(dev)).float()
-            out = sampler(inp, ddim=True, unconditional_guidance_scale=1, ddim_step=ddim_step, **tile_kw)
+            if replicas is None:
+                out = sampler(inp, ddim=True, unconditional_guidance_scale=1, ddim_step=ddim_step, **tile_kw)
+            else:
+                post = sampler.posterior(inp, samples, ddim_step=ddim_step, eta=eta, seed=sample_seed, sample_batch=sample_batch,
+                                         image_ids=range(done, done + int(inp.shape[0])), keep_samples=True, **tile_kw)
+                out = post.mean
+                replicas.update(post, target / 255)
+                if save_dir is not None:
+                    _save_batch(std_gain * post.std / 2, names, os.path.join(save_dir, "std"))
             pred01 = (out + 1) / 2                                                        # :912
             meter.update(pred01, target / 255)
             if distribution is not None:
@@ -163,6 +198,8 @@ def evaluate(sampler, batches: Iterable, *, ddim_step: int, tile: Optional[int] 
         result["niqe_full"] = sum(defined) / len(defined) if defined else float("nan")
         result["niqe_full_per_image"] = list(full_scores)
         result["niqe_full_undefined"] = len(full_scores) - len(defined)
+    if replicas is not None:
+        result.update(replicas.compute())
     if save_dir is not None:
         keys = RES_KEYS_UCIQE if uciqe else RES_KEYS
         if lpips is not None:
@@ -171,8 +208,63 @@ def evaluate(sampler, batches: Iterable, *, ddim_step: int, tile: Optional[int] 
             keys = keys + RES_KEYS_DISTRIBUTION
         if niqe is not None:
             keys = keys + (RES_KEY_NIQE,) + ((RES_KEY_NIQE_FULL,) if transfer is not None else ())
-        write_res(os.path.join(save_dir, "res.txt"), result, keys)
+        if replicas is not None:
+            flat, keys = sample_res_lines(result, keys)
+            write_res(os.path.join(save_dir, "res.txt"), flat, keys)
+        else:
+            write_res(os.path.join(save_dir, "res.txt"), result, keys)
     return result
+
+
+def sample_res_lines(result: Dict[str, object], keys):
+    """-> (flat result, keys) for ``write_res`` under ``samples=``: today's ``keys`` in their order, then ``samples:``, then for each of
+    them that the replicas were scored for ``<name>_sample_avg:`` and ``<name>_sample_std:``, then ``uncertainty_avg:``."""
+    flat = dict(result)
+    keys = tuple(keys) + (("samples:", "samples"),)
+    for _, name in keys[:-1]:
+        if name in result["sample_avg"]:
+            flat[f"{name}_sample_avg"], flat[f"{name}_sample_std"] = result["sample_avg"][name], result["sample_std"][name]
+            keys += ((f"{name}_sample_avg:", f"{name}_sample_avg"), (f"{name}_sample_std:", f"{name}_sample_std"))
+    return flat, keys + (("uncertainty_avg:", "uncertainty"),)
+
+
+class _ReplicaScores:
+    """The per-replica side of ``evaluate(samples=K)``: a second meter of ``meter``'s configuration, updated with every replica of every
+    batch, and the running sum of ``std / 2`` on the device.  Nothing here synchronises before ``compute``."""
+
+    def __init__(self, meter, K: int):
+        if not isinstance(meter, quality.QualityMeter):
+            raise ValueError("evaluate: samples= needs a quality.QualityMeter (its configuration is copied for the replicas)")
+        self.K = K
+        self.meter = quality.QualityMeter(uciqe=meter._uciqe, uciqe_scale=meter._uciqe_scale, lpips=meter._lpips, niqe=meter._niqe)
+        self.replica_of_update: List[int] = []
+        self.spread = None          # [sum of std / 2, elements] as a float64 device pair
+
+    def update(self, post, target01: torch.Tensor) -> None:
+        for r in range(self.K):
+            self.meter.update((post.samples[:, r] + 1) / 2, target01)
+            self.replica_of_update.append(r)
+        part = torch.stack([(post.std.double() / 2).sum(), torch.tensor(float(post.std.numel()), dtype=torch.float64,
+                                                                          device=post.std.device)])
+        self.spread = part if self.spread is None else self.spread + part
+
+    def compute(self) -> Dict[str, object]:
+        import numpy as np
+        scores = self.meter.compute()
+        per = np.asarray(scores["per_image"], dtype=np.float64)
+        replica = np.concatenate([np.full(n, r) for (_, n, _), r in zip(self.meter._updates, self.replica_of_update)]) \
+            if self.replica_of_update else np.zeros(0)
+        per_sample: Dict[str, List[float]] = {}
+        for j, name in enumerate(self.meter.columns):
+            cols = [per[replica == r, j] for r in range(self.K)]
+            if name == "niqe":          # the meter's own rule for this column: over the images whose score is finite
+                cols = [c[np.isfinite(c)] for c in cols]
+            per_sample[name] = [float(c.mean()) if c.size else float("nan") for c in cols]
+        avg = {name: float(np.mean(v)) for name, v in per_sample.items()}
+        std = {name: float(np.std(v, ddof=1)) if self.K > 1 else 0.0 for name, v in per_sample.items()}
+        total, count = (0.0, 0.0) if self.spread is None else self.spread.tolist()
+        return {"samples": self.K, "per_sample": per_sample, "sample_avg": avg, "sample_std": std,
+                "uncertainty": total / count if count else float("nan")}
 
 
 def _transfer_settings(transfer):
@@ -296,6 +388,11 @@ def _run_sets(config, task: str) -> Dict[str, Dict[str, object]]:
         if niqe_model is None:
             raise ValueError("the configuration asks for niqe and names no 'niqe_model': fit one with fit_niqe, or load the release's")
         extra["niqe"] = niqe_model if isinstance(niqe_model, quality.NIQEModel) else quality.NIQEModel.load(niqe_model)
+    if _cfg(config, "samples", None) is not None:
+        extra.update(samples=_cfg(config, "samples"), eta=_cfg(config, "ddim_eta", 0.0), sample_seed=_cfg(config, "sample_seed", 0),
+                     sample_batch=_cfg(config, "sample_batch", None))
+    elif any(_cfg(config, k, None) is not None for k in ("ddim_eta", "sample_seed", "sample_batch")):
+        raise ValueError("the configuration gives ddim_eta / sample_seed / sample_batch without 'samples'")
     results = {}
     for name, data in sets:
         if features is not None:      # one meter per set; a DistributionMeter from the configuration goes on filling across both
@@ -325,7 +422,11 @@ def test(config, epoch=None) -> Dict[str, Dict[str, object]]:
     1e-3; neither is backed by an image-quality figure; absent: nothing of it is loaded, launched or written),
     ``niqe`` (bool) with ``niqe_model`` (the path of a ``quality.NIQEModel`` file, ``.npz`` or the release's ``.mat``, or a model;
     ``evaluate``'s ``niqe=``: NIQE of every result at the model's ``patch``, and of every full-size result under ``full_resolution``;
-    absent: no NIQE, ``res.txt`` as before).
+    absent: no NIQE, ``res.txt`` as before),
+    ``samples`` (K >= 1: ``evaluate``'s ``samples=``, the mean of K posterior samples per image is scored and saved, the per-pixel spread
+    goes to ``<set>/std/<name>`` and ``res.txt`` gains the draw-to-draw spread of every score) with ``ddim_eta`` (default 0),
+    ``sample_seed`` (default 0) and ``sample_batch`` (the most samples per model evaluation; absent: one draw from torch's generator
+    per image, ``res.txt`` as before).
     ``epoch`` is accepted and unused, as in the reference.  Returns ``{set name: evaluate()'s dict}``."""
     return _run_sets(config, "test")
 

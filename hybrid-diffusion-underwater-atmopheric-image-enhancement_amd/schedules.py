@@ -1,8 +1,8 @@
 """The time steps and coefficient tables of the samplers' strided loops, shared by the label-conditioned sampler
 (``DiffusionFreeGuidence.DiffusionCondition``) and the image-conditioned one (``diffusion.Diffusion``, which reads
 ``alphas_bar[t + 1]``: ``shift=1``): ``ddim_timesteps`` / ``ddim_table`` of the strided DDIM update (Song et al. 2021),
-``logsnr_timesteps`` / ``dpmpp_table`` of DPM-Solver++(2M) (Lu et al. 2022), and the validation of ``solver`` / ``spacing`` /
-``timesteps`` both ``forward`` signatures share.  Everything here runs on the CPU in float64 and loads no native library; both
+``logsnr_timesteps`` / ``dpmpp_table`` of DPM-Solver++(2M) (Lu et al. 2022), the validation of ``solver`` / ``spacing`` /
+``timesteps`` both ``forward`` signatures share, and ``posterior_seed``, the seed of one sample of a multi-sample run.  Everything here runs on the CPU in float64 and loads no native library; both
 sampler modules re-export the public names."""
 from __future__ import annotations
 
@@ -10,7 +10,7 @@ from typing import List, Optional, Sequence, Tuple
 
 import torch
 
-__all__ = ["SOLVERS", "SPACINGS", "ddim_timesteps", "ddim_table", "logsnr_timesteps", "dpmpp_table"]
+__all__ = ["SOLVERS", "SPACINGS", "ddim_timesteps", "ddim_table", "logsnr_timesteps", "dpmpp_table", "posterior_seed"]
 
 SOLVERS = ("ddim", "dpmpp2m")
 SPACINGS = ("uniform", "logsnr")
@@ -160,3 +160,27 @@ def dpmpp_table(betas, timesteps: Sequence[int], shift: int = 0, final_alpha_bar
         rows[k] = torch.stack([torch.sqrt(1.0 - a), torch.sqrt(a), A, B, Cc])
         h_prev = h
     return torch.stack(rows)
+
+
+_M64 = (1 << 64) - 1
+
+
+def _splitmix64(z: int) -> int:
+    z = (z + 0x9E3779B97F4A7C15) & _M64
+    z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & _M64
+    z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & _M64
+    return z ^ (z >> 31)
+
+
+def posterior_seed(seed: int, image_id: int, replica: int) -> int:
+    """The Philox seed of sample ``(image_id, replica)`` of a posterior run under ``seed``, a uint64:
+    ``mix(mix(mix(seed) ^ image_id) ^ replica)`` with ``mix`` the splitmix64 step, everything mod 2^64.  All noise of that sample is
+    drawn under this one seed -- ``y_T`` is ``hdiff_randn(3HW, s, offset = 2^32 - 1)``, the noise of the step whose device counter reads
+    k is ``hdiff_randn(3HW, s, offset = k)`` -- so it belongs to the image, not to a place in a batch.  Pure integer arithmetic."""
+    for name, v in (("seed", seed), ("image_id", image_id), ("replica", replica)):
+        if isinstance(v, bool) or int(v) != v:
+            raise ValueError(f"posterior_seed: {name} must be an integer, got {v!r}")
+    return _splitmix64(_splitmix64(_splitmix64(int(seed) & _M64) ^ (int(image_id) & _M64)) ^ (int(replica) & _M64))
+
+
+Y_T_OFFSET = (1 << 32) - 1      # the Philox offset of a posterior sample's y_T; the step noise uses offsets 0 .. n_steps - 1

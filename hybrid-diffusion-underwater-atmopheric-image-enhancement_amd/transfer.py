@@ -21,7 +21,7 @@ from __future__ import annotations
 
 import ctypes as C
 import math
-from typing import Dict, Tuple, Union
+from typing import Dict, Optional, Tuple, Union
 
 import torch
 
@@ -185,7 +185,9 @@ class GuidedEnhancer:
     """``enhance(img)``: one uint8 ``[H, W, 3]`` device image -> the enhanced uint8 ``[H, W, 3]``.
 
       1. ``low = resample(img, size)``
-      2. ``out = sampler(low[None], ddim=True, **sampler_kwargs)`` (``ddim_step``, ``solver``, ``spacing``, ``y_T`` pass through)
+      2. ``out = sampler(low[None], ddim=True, **sampler_kwargs)`` (``ddim_step``, ``solver``, ``spacing``, ``y_T`` pass through); with
+         ``samples=K``: ``out = sampler.posterior(low[None], K, eta=eta, seed=seed, **sampler_kwargs).mean``, the mean of K samples --
+         the better target for a fit that discards a sample's own texture anyway (``sample_batch`` passes through)
       3. ``pred01 = clamp((out + 1) / 2, 0, 1)``
       4. ``coef = guided_fit(low[None] / 255, pred01, radius=radius, eps=eps)``
       5. ``guided_apply(coef[0], img)``
@@ -194,9 +196,18 @@ class GuidedEnhancer:
     of the guided-filter literature for a 256-pixel grid and NO image-quality figure backs them; the diffusion sample's own fine texture
     does not survive the fit, by design (module docstring)."""
 
-    def __init__(self, sampler, *, size: Union[int, Tuple[int, int]] = 256, radius: int = 8, eps: float = 1e-3, **sampler_kwargs):
+    def __init__(self, sampler, *, size: Union[int, Tuple[int, int]] = 256, radius: int = 8, eps: float = 1e-3,
+                 samples: Optional[int] = None, eta: float = 0.0, seed: int = 0, **sampler_kwargs):
         if not callable(sampler):
             raise TypeError("hdiff: GuidedEnhancer needs a callable sampler")
+        if samples is None and eta != 0:
+            raise ValueError("hdiff: GuidedEnhancer: eta= goes with samples=")
+        if samples is not None:
+            if isinstance(samples, bool) or not isinstance(samples, int) or samples < 1:
+                raise ValueError(f"hdiff: GuidedEnhancer: samples must be an integer >= 1, got {samples!r}")
+            if not hasattr(sampler, "posterior"):
+                raise TypeError("hdiff: GuidedEnhancer(samples=) needs a sampler with a posterior() method")
+        self.samples, self.eta, self.seed = samples, eta, seed
         self.sampler = sampler
         self.size = _size_pair(size)
         self.radius, self.eps = transfer_settings(radius, eps)
@@ -216,7 +227,10 @@ class GuidedEnhancer:
                 self._fit_ws[dev] = _fit_scratch(1, h, w, dev)
             low = torch.empty(3, h, w, dtype=torch.float32, device=dev)
             _resample_into(img, low, self._resample_ws[key])
-            out = self.sampler(low[None], ddim=True, **self.sampler_kwargs)
+            if self.samples is None:
+                out = self.sampler(low[None], ddim=True, **self.sampler_kwargs)
+            else:
+                out = self.sampler.posterior(low[None], self.samples, eta=self.eta, seed=self.seed, **self.sampler_kwargs).mean
             pred01 = ((out + 1) / 2).clamp(0, 1)
             if pred01.shape != (1, 3, h, w) or pred01.device != dev:
                 raise RuntimeError(f"hdiff: the sampler returned {tuple(out.shape)} on {out.device} for a (1, 3, {h}, {w}) input on {dev}")

@@ -548,6 +548,28 @@ int hdiff_concat2(const float* a, const float* b, float* out, int B, int64_t n0,
 int hdiff_dpmpp_step(const float* y, const float* eps, float* y_next, float* x0_prev, const float* tab /* [nsteps][5] */,
                      const int32_t* step_ptr, int nsteps, int clip_x0, int32_t* nan_flag, int64_t n, hdiff_stream_t stream);
 /* ------------------------------------------------------------------------------------------------------------------
+ * Multi-sample posterior sampling of the same sampler (`posterior`, `eta=`; additions to the reference and to ABI 6).  A batch is
+ * `rows` samples of n_per floats; sample r draws ALL its noise from the Philox stream of seeds[r] (device memory), quads counted
+ * WITHIN the row, so a sample's numbers depend on neither its place in the batch nor on the batch's size.
+ *   hdiff_randn_rows      row r of out [rows][n_per] is hdiff_randn(n_per, seeds[r], offset) bit for bit; with n_per % 4 != 0 the last
+ *                         quad of a row is partly used and the next row starts a fresh one
+ *   hdiff_ddim_eta_step   Diffusion.py:259-267 with the stochastic term kept: y0 = (y - eps*tab[k][0]) / tab[k][1] ;
+ *                         y_next = ((tab[k][2]*y0) + (tab[k][3]*z)) + (tab[k][4]*eps), one fp32 rounding per written operation,
+ *                         k = *step_ptr clamped into [0, nsteps), tab[k] = {sqrt(1-at), sqrt(at), sqrt(at_next), c1, c2}.  z is
+ *                         read from `noise` [rows][n_per] or, with noise == NULL, drawn: row r is hdiff_randn(n_per, seeds[r],
+ *                         offset = k).  Noise is added at every step, k = 0 included.  y and y_next may alias; any 4-byte aligned
+ *                         pointers; nan_flag is OR-ed with 1 on a NaN output; with tab[k][3] == 0 and finite z the result equals
+ *                         hdiff_ddim_step's
+ *   hdiff_sample_stats    samples [B][K][n] -> mean, std [B][n]: per element, in double, in replica order, m = (sum x_k) / K and
+ *                         std = sqrt(sum (x_k - m)^2 / (K - 1)), exactly 0 for K = 1; each rounded once to fp32
+ * One launch each; no allocation, no synchronisation, no float atomics: legal under stream capture, bitwise repeatable.
+ * ------------------------------------------------------------------------------------------------------------------ */
+int hdiff_randn_rows(float* out, int rows, int64_t n_per, const uint64_t* seeds, uint64_t offset, hdiff_stream_t stream);
+int hdiff_ddim_eta_step(const float* y, const float* eps, const float* noise /* or NULL */, float* y_next,
+                        const float* tab /* [nsteps][5] */, const uint64_t* seeds /* [rows]; may be NULL with noise */,
+                        int64_t n_per, const int32_t* step_ptr, int nsteps, int32_t* nan_flag, int rows, hdiff_stream_t stream);
+int hdiff_sample_stats(const float* samples, int B, int K, int64_t n, float* mean, float* std, hdiff_stream_t stream);
+/* ------------------------------------------------------------------------------------------------------------------
  * Overlapping-window DDIM sampling of the second tree's sampler (the `tile=` argument; an addition to the reference).
  * Layout: per axis a table of window origins (origin_y[ny], origin_x[nx]); window (b, iy, ix) has index (b*ny + iy)*nx + ix
  * and covers rows origin_y[iy] .. + th - 1 and columns origin_x[ix] .. + tw - 1 of a [B][C][H][W] tensor (th <= H, tw <= W).
