@@ -1,7 +1,8 @@
 // The radix select of the score kernels: the value at a given rank of a plane of samples, found digit by digit on the order-preserving
 // integer key of each sample, exact at ties.  quality.hip runs it on 32-bit keys of fp32 values (UICM's two cuts of two planes: 4 selects
-// per image, 3 digits), uciqe.hip on 64-bit keys of doubles (the two cuts of L: 2 selects, 6 digits).  Beside device.h, this header and
-// reduce.h are the only ones that hold device code; no kernel of profiles/roofline_traffic.json reaches either of them.
+// per image, 3 digits), uciqe.hip on 64-bit keys of doubles (the two cuts of L: 2 selects, 6 digits), color_diff.hip likewise (the 95th
+// percentile of the CIEDE2000 plane: 1 select, 6 digits).  Beside device.h, this header, reduce.h and lab.h are the only ones that hold
+// device code; no kernel of profiles/roofline_traffic.json reaches any of them.
 //
 // One digit is two launches of the including file's own kernels, which do its addressing and call in here:
 //   histogram  every workgroup counts its samples into an LDS histogram per select -- the file's own loop: the two read different data

@@ -1,6 +1,6 @@
-// The fixed-order double sums of the score and loss kernels (msssim.hip, train_b_ops.hip, quality.hip, uciqe.hip, perceptual.hip,
-// dino.hip, distribution.hip).  Beside device.h, this header and radix_select.h are the only ones that hold device code; no kernel of
-// profiles/roofline_traffic.json reaches either of them.
+// The fixed-order double sums of the score and loss kernels (msssim.hip, train_b_ops.hip, quality.hip, uciqe.hip, color_diff.hip,
+// perceptual.hip, dino.hip, distribution.hip).  Beside device.h, this header, radix_select.h and lab.h are the only ones that hold device
+// code; no kernel of profiles/roofline_traffic.json reaches any of them.
 //
 // THE ORDER OF THE ADDITIONS IS THE CONTRACT: results are pinned bit for bit, and every function here adds in exactly one order.
 //   1. inside a wave, wave_sum's xor ladder (device.h: offsets 32, 16, 8, 4, 2, 1);

@@ -3,7 +3,7 @@
 // are held to, hdiff_amd/uw_metrics.nmetrics the host restatement).  Conventions are those of quality.hip: input fp32 [N][3][H][W] with
 // nominal range [0, 1], images on blockIdx.z, grids and partial counts functions of H and W alone, outputs float64, one row per image.
 //
-// Per pixel, in double: rgb = double(min(max(x, 0), 1)) * scale (the clip in fp32), sRGB -> linear -> XYZ (D65) -> CIE L*a*b*,
+// Per pixel, in double: rgb = double(min(max(x, 0), 1)) * scale (the clip in fp32), sRGB -> linear -> XYZ (D65) -> CIE L*a*b* (lab.h),
 // chroma = sqrt(a^2 + b^2), saturation = chroma / L (0 where chroma or L is 0).  Per image:
 //   sc   = sqrt(mean((chroma - mean(chroma))^2))                     two passes
 //   conl = mean(the `top` largest L) - mean(the `top` smallest L)    top = round_half_even(0.01 H W); NaN when top == 0
@@ -29,6 +29,7 @@
 #include <math.h>
 
 #include "common.h"
+#include "lab.h"
 #include "radix_select.h"
 #include "reduce.h"
 
@@ -62,9 +63,6 @@ struct UciqeParams {
   double scale;
 };
 
-__device__ __forceinline__ double srgb_to_linear(double v) { return v > 0.04045 ? pow((v + 0.055) / 1.055, 2.4) : v / 12.92; }
-__device__ __forceinline__ double lab_f(double t) { return t > 0.008856 ? cbrt(t) : 7.787 * t + 16.0 / 116.0; }
-
 __global__ __launch_bounds__(kThreads) void uciqe_init_kernel(const UciqeParams P, const UciqeWs ws) {
   const int64_t nh = (int64_t)kPasses * P.N * kSelects * kBins;
   for (int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x; i < nh; i += (int64_t)gridDim.x * kThreads) ws.hist[i] = 0u;
@@ -85,13 +83,9 @@ __global__ __launch_bounds__(kThreads) void uciqe_lab_kernel(const UciqeParams P
   for (int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x; i < HW; i += (int64_t)gridDim.x * kThreads) {
     const float xr = img[i], xg = img[HW + i], xb = img[2 * HW + i];
     bad |= non_finite(xr) || non_finite(xg) || non_finite(xb);
-    const double r = srgb_to_linear((double)fminf(fmaxf(xr, 0.0f), 1.0f) * P.scale);
-    const double g = srgb_to_linear((double)fminf(fmaxf(xg, 0.0f), 1.0f) * P.scale);
-    const double b = srgb_to_linear((double)fminf(fmaxf(xb, 0.0f), 1.0f) * P.scale);
-    const double fx = lab_f(((0.412453 * r + 0.357580 * g) + 0.180423 * b) / 0.95047);
-    const double fy = lab_f(((0.212671 * r + 0.715160 * g) + 0.072169 * b) / 1.0);
-    const double fz = lab_f(((0.019334 * r + 0.119193 * g) + 0.950227 * b) / 1.08883);
-    const double L = 116.0 * fy - 16.0, ca = 500.0 * (fx - fy), cb = 200.0 * (fy - fz);
+    double L, ca, cb;
+    srgb_to_lab((double)fminf(fmaxf(xr, 0.0f), 1.0f) * P.scale, (double)fminf(fmaxf(xg, 0.0f), 1.0f) * P.scale,
+                (double)fminf(fmaxf(xb, 0.0f), 1.0f) * P.scale, L, ca, cb);
     const double c = sqrt(ca * ca + cb * cb);
     lum[i] = L;
     chr[i] = c;

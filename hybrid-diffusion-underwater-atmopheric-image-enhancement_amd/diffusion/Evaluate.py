@@ -28,6 +28,11 @@ Deliberate deviations from the reference:
     agreement with the authors' MATLAB release is unpinned, and rows with a non-finite feature leave mean and covariance alike
     (the release drops them per column for the mean).  ``res.txt`` then ends with ``niqe_orgin_avg:`` and, with ``transfer=``,
     ``niqe_full_orgin_avg:``.
+  * the colour differences (``color=True``; ``quality.color_difference``) are not in the reference either: the mean CIEDE2000 of every
+    result against its target, its 95th percentile over the pixels, the mean CIE76 and the mean angular error in degrees -- the
+    scores dehazing and low-light benchmarks report beside PSNR and SSIM, and the only ones here that say how far the COLOUR is from
+    the target's.  ``res.txt`` then ends with ``ciede2000_orgin_avg:``, ``ciede2000_p95_orgin_avg:``, ``deltae76_orgin_avg:`` and
+    ``angular_orgin_avg:``.
   * ``test`` scores every image of a set: the reference's loader drops the last incomplete batch.  Its file names are those of the
     degraded images.  ``inference`` does the same on the validation split, and its means are ``sum / len``: the reference's
     ``(sum + 1) / (len + 1)`` (``:1204-1211``) is not copied.
@@ -42,7 +47,7 @@ import torch
 from .. import quality
 
 __all__ = ["evaluate", "test", "inference", "fit_niqe", "RES_KEYS", "RES_KEYS_UCIQE", "RES_KEY_LPIPS", "RES_KEYS_DISTRIBUTION",
-           "RES_KEY_NIQE", "RES_KEY_NIQE_FULL"]
+           "RES_KEY_NIQE", "RES_KEY_NIQE_FULL", "RES_KEYS_COLOR"]
 
 # res.txt: the reference's key for each measured score, in the reference's order (rotinas.py:967-982)
 RES_KEYS = (("psnr_orgin_avg:", "psnr"), ("ssim_orgin_avg:", "ssim"), ("uiqm_orgin_avg:", "uiqm"), ("uism_orgin_avg:", "uism"),
@@ -56,6 +61,9 @@ RES_KEYS_DISTRIBUTION = (("fd_orgin_avg:", "fd"), ("kid_orgin_avg:", "kid"))
 # with NIQE: one last line, behind all of the above; with transfer= as well, one more for the full-size results
 RES_KEY_NIQE = ("niqe_orgin_avg:", "niqe")
 RES_KEY_NIQE_FULL = ("niqe_full_orgin_avg:", "niqe_full")
+# with the colour differences: four last lines, behind all of the above
+RES_KEYS_COLOR = (("ciede2000_orgin_avg:", "ciede2000"), ("ciede2000_p95_orgin_avg:", "ciede2000_p95"),
+                  ("deltae76_orgin_avg:", "deltae76"), ("angular_orgin_avg:", "angular"))
 
 
 def _device_of(sampler) -> Optional[torch.device]:
@@ -84,7 +92,8 @@ def evaluate(sampler, batches: Iterable, *, ddim_step: int, tile: Optional[int] 
              tile_batch: Optional[int] = None, save_dir: Optional[str] = None, collect: Optional[List[torch.Tensor]] = None,
              meter=None, solver: Optional[str] = None, spacing: Optional[str] = None, uciqe: bool = False,
              uciqe_scale: float = 1.0, lpips=None, distribution=None, transfer=None, niqe=None, samples: Optional[int] = None,
-             eta: float = 0.0, sample_seed: int = 0, sample_batch: Optional[int] = None, std_gain: float = 4.0) -> Dict[str, object]:
+             eta: float = 0.0, sample_seed: int = 0, sample_batch: Optional[int] = None, std_gain: float = 4.0,
+             color: bool = False) -> Dict[str, object]:
     """Samples and scores a set.  ``batches`` yields ``(input, target)`` or ``(input, target, names)``: CHW images in [0, 255] as
     ``Underwater_Dataset`` / ``Atmospheric_Dataset`` produce them, batched.  Per batch: ``out = sampler(input, ddim=True,
     unconditional_guidance_scale=1, ddim_step=ddim_step, tile=...)`` (rotinas.py:907), then ``(out + 1) / 2`` is scored against
@@ -112,6 +121,11 @@ def evaluate(sampler, batches: Iterable, *, ddim_step: int, tile: Optional[int] 
     written (one synchronisation per image, beside the one of the file): the result gains ``"niqe_full"`` (the same mean),
     ``"niqe_full_per_image"`` and ``"niqe_full_undefined"``, and ``res.txt`` one more line, ``niqe_full_orgin_avg:``.  Without it
     nothing of that is loaded, launched or written.
+    ``color=True``: the default meter also scores the colour differences of ``(out + 1) / 2`` from ``target / 255``
+    (``quality.QualityMeter(color=True)``; a ``meter`` passed in must report them itself), the result gains ``"ciede2000"``,
+    ``"ciede2000_p95"``, ``"deltae76"`` and ``"angular"``, and ``res.txt`` four lines behind every other one: ``ciede2000_orgin_avg:``,
+    ``ciede2000_p95_orgin_avg:``, ``deltae76_orgin_avg:`` and ``angular_orgin_avg:`` (under ``samples=`` their ``_sample_avg:`` /
+    ``_sample_std:`` lines follow like the other per-image scores').  Without it nothing of that is launched or written.
     ``samples=K`` (an integer >= 1): every batch goes through ``sampler.posterior(input, K, eta=eta, seed=sample_seed,
     image_ids=<the running indices of its images in the set>, sample_batch=sample_batch, ...)`` in place of one ``sampler`` call.  The
     MEAN of the K clipped samples is the image that is scored, saved, and handed to ``distribution`` and ``transfer``; a second meter
@@ -142,6 +156,8 @@ def evaluate(sampler, batches: Iterable, *, ddim_step: int, tile: Optional[int] 
     if niqe is not None and not isinstance(niqe, quality.NIQEModel):
         niqe = quality.NIQEModel.load(niqe)
     full_scores: List[float] = []
+    if meter is None and color:
+        meter = quality.QualityMeter(uciqe=bool(uciqe), uciqe_scale=uciqe_scale, lpips=lpips, niqe=niqe, color=True)
     if meter is None and niqe is not None:
         meter = quality.QualityMeter(uciqe=bool(uciqe), uciqe_scale=uciqe_scale, lpips=lpips, niqe=niqe)
     if meter is None:
@@ -208,6 +224,8 @@ def evaluate(sampler, batches: Iterable, *, ddim_step: int, tile: Optional[int] 
             keys = keys + RES_KEYS_DISTRIBUTION
         if niqe is not None:
             keys = keys + (RES_KEY_NIQE,) + ((RES_KEY_NIQE_FULL,) if transfer is not None else ())
+        if color:
+            keys = keys + RES_KEYS_COLOR
         if replicas is not None:
             flat, keys = sample_res_lines(result, keys)
             write_res(os.path.join(save_dir, "res.txt"), flat, keys)
@@ -236,7 +254,8 @@ class _ReplicaScores:
         if not isinstance(meter, quality.QualityMeter):
             raise ValueError("evaluate: samples= needs a quality.QualityMeter (its configuration is copied for the replicas)")
         self.K = K
-        self.meter = quality.QualityMeter(uciqe=meter._uciqe, uciqe_scale=meter._uciqe_scale, lpips=meter._lpips, niqe=meter._niqe)
+        self.meter = quality.QualityMeter(uciqe=meter._uciqe, uciqe_scale=meter._uciqe_scale, lpips=meter._lpips, niqe=meter._niqe,
+                                          color=meter._color)
         self.replica_of_update: List[int] = []
         self.spread = None          # [sum of std / 2, elements] as a float64 device pair
 
@@ -388,6 +407,8 @@ def _run_sets(config, task: str) -> Dict[str, Dict[str, object]]:
         if niqe_model is None:
             raise ValueError("the configuration asks for niqe and names no 'niqe_model': fit one with fit_niqe, or load the release's")
         extra["niqe"] = niqe_model if isinstance(niqe_model, quality.NIQEModel) else quality.NIQEModel.load(niqe_model)
+    if _cfg(config, "color", False):
+        extra["color"] = True
     if _cfg(config, "samples", None) is not None:
         extra.update(samples=_cfg(config, "samples"), eta=_cfg(config, "ddim_eta", 0.0), sample_seed=_cfg(config, "sample_seed", 0),
                      sample_batch=_cfg(config, "sample_batch", None))
@@ -423,6 +444,8 @@ def test(config, epoch=None) -> Dict[str, Dict[str, object]]:
     ``niqe`` (bool) with ``niqe_model`` (the path of a ``quality.NIQEModel`` file, ``.npz`` or the release's ``.mat``, or a model;
     ``evaluate``'s ``niqe=``: NIQE of every result at the model's ``patch``, and of every full-size result under ``full_resolution``;
     absent: no NIQE, ``res.txt`` as before),
+    ``color`` (bool: ``evaluate``'s ``color=``, CIEDE2000 with its 95th percentile, CIE76 and the angular error of every result against
+    its target; absent: none of them, ``res.txt`` as before),
     ``samples`` (K >= 1: ``evaluate``'s ``samples=``, the mean of K posterior samples per image is scored and saved, the per-pixel spread
     goes to ``<set>/std/<name>`` and ``res.txt`` gains the draw-to-draw spread of every score) with ``ddim_eta`` (default 0),
     ``sample_seed`` (default 0) and ``sample_batch`` (the most samples per model evaluation; absent: one draw from torch's generator

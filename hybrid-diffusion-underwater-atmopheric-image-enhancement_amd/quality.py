@@ -1,5 +1,6 @@
-"""PSNR / SSIM / UIQM (``csrc/quality.hip``) and UCIQE (``csrc/uciqe.hip``) on the device: the per-image scores of the reference's
-evaluation (``utils/rotinas.py:916-931``) taken where the sampler leaves its output, without a copy to the host per batch.
+"""PSNR / SSIM / UIQM (``csrc/quality.hip``), UCIQE (``csrc/uciqe.hip``) and the colour differences (``csrc/color_diff.hip``) on the
+device: the per-image scores of the reference's evaluation (``utils/rotinas.py:916-931``) taken where the sampler leaves its output,
+without a copy to the host per batch.
 
 Inputs are ``[N, 3, H, W]`` device tensors with nominal range [0, 1]; the kernels score ``clip(x, 0, 1) * 255`` as an fp32 image,
 which is what ``np.clip(img, 0, 1) * 255`` hands the reference's metric calls.  Definitions:
@@ -12,6 +13,12 @@ which is what ``np.clip(img, 0, 1) * 255`` hands the reference's metric calls.  
     kernels are held to) of ``clip(x, 0, 1) * scale``.  ``scale=1`` scores the image on its colour range; ``scale=255`` evaluates what
     the reference's call evaluates (a float image in [0, 255] handed to a conversion that takes floats as [0, 1]).  An image of fewer
     than 50 pixels has ``conl = uciqe = NaN``, as on the host.
+
+``color_difference`` scores what none of the above measures: how far a prediction's COLOUR is from its target's.  Per pixel, CIE L*a*b*
+of both images (the conversion of ``uciqe`` at ``scale=1``), CIEDE2000 after Sharma, Wu and Dalal 2005 with ``kL = kC = kH = 1``, CIE76,
+and the angle between the two clipped RGB vectors; per image the mean and the nearest-rank 95th percentile of CIEDE2000, the mean CIE76
+and the mean angle in degrees over the pixels where neither image is black (``tests/_color_def.py`` is the definition the kernels are
+held to; ``tests/golden/ciede2000_sharma.json``, the published table, pins the formula).  The reference has no such score.
 
 A non-finite input value makes the scores of its image NaN and leaves the rest of the batch alone.  Results are bitwise repeatable
 and do not depend on the batch an image is scored in.
@@ -51,11 +58,12 @@ import torch
 from . import _capi
 from . import engine as E
 
-__all__ = ["psnr_ssim", "uiqm", "uciqe", "LPIPS", "QualityMeter", "moments", "kid_sums", "kid", "frechet_from_moments", "DinoFeatures",
-           "DistributionMeter", "niqe_features", "NIQEModel", "niqe_from_moments", "niqe"]
+__all__ = ["psnr_ssim", "uiqm", "uciqe", "color_difference", "ciede2000_lab", "LPIPS", "QualityMeter", "moments", "kid_sums", "kid",
+           "frechet_from_moments", "DinoFeatures", "DistributionMeter", "niqe_features", "NIQEModel", "niqe_from_moments", "niqe"]
 
 COLUMNS = ("psnr", "ssim", "uiqm", "uicm", "uism", "uiconm")      # the columns of QualityMeter's per-image rows
 UCIQE_COLUMNS = ("uciqe", "uciqe_sc", "uciqe_conl", "uciqe_us")   # the four more of QualityMeter(uciqe=True)
+COLOR_COLUMNS = ("ciede2000", "ciede2000_p95", "deltae76", "angular")      # four more with QualityMeter(color=True), behind UCIQE's
 LPIPS_COLUMNS = ("lpips",)                                        # the last one of QualityMeter(lpips=metric)
 NIQE_COLUMNS = ("niqe",)                                          # the last one of QualityMeter(niqe=model), behind LPIPS's
 NIQE_ROW = 36                                                     # features of a block: 18 per scale
@@ -90,6 +98,12 @@ def _uciqe_scratch(N: int, H: int, W: int, dev) -> torch.Tensor:
     return torch.empty(need.value, dtype=torch.uint8, device=dev)
 
 
+def _color_scratch(N: int, H: int, W: int, dev) -> torch.Tensor:
+    need = C.c_int64(0)
+    _capi.check(_capi.lib().hdiff_color_diff_workspace(N, H, W, C.byref(need)), "color_diff_workspace")
+    return torch.empty(need.value, dtype=torch.uint8, device=dev)
+
+
 def _stream(dev) -> int:
     return torch.cuda.current_stream(dev).cuda_stream
 
@@ -109,6 +123,14 @@ def _uciqe_into(img: torch.Tensor, scale: float, out: torch.Tensor, scratch: tor
     N, _, H, W = (int(v) for v in img.shape)
     _capi.check(_capi.lib().hdiff_uciqe(img.data_ptr(), N, H, W, float(scale), out.data_ptr(), scratch.data_ptr(),
                                         _stream(img.device)), "uciqe")
+
+
+def _color_into(pred: torch.Tensor, target: torch.Tensor, out: torch.Tensor, scratch: torch.Tensor,
+                map_out: Optional[torch.Tensor] = None) -> None:
+    N, _, H, W = (int(v) for v in pred.shape)
+    _capi.check(_capi.lib().hdiff_color_diff(pred.data_ptr(), target.data_ptr(), N, H, W, out.data_ptr(),
+                                             None if map_out is None else map_out.data_ptr(), scratch.data_ptr(),
+                                             _stream(pred.device)), "color_diff")
 
 
 def psnr_ssim(pred01: torch.Tensor, target01: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
@@ -142,6 +164,45 @@ def uciqe(img01: torch.Tensor, *, scale: float = 1.0) -> Tuple[torch.Tensor, tor
     with torch.cuda.device(img.device):
         _uciqe_into(img, scale, out, _uciqe_scratch(N, H, W, img.device))
     return out[:, 0], out[:, 1], out[:, 2], out[:, 3]
+
+
+def color_difference(pred01: torch.Tensor, target01: torch.Tensor, *, with_map: bool = False):
+    """-> (de00[N], de00_p95[N], de76[N], angular[N]), float64 device tensors: the mean CIEDE2000 between ``clip(pred01, 0, 1)`` and
+    ``clip(target01, 0, 1)``, its nearest-rank 95th percentile over the pixels, the mean CIE76, and the mean angle in degrees between
+    the RGB vectors over the pixels where neither is black (NaN when there is none).  ``with_map``: a fifth element, the per-pixel
+    CIEDE2000 as an fp32 ``[N, 1, H, W]`` tensor.  Never synchronises."""
+    pred, target = _image_batch(pred01, "pred01"), _image_batch(target01, "target01")
+    if pred.shape != target.shape or pred.device != target.device:
+        raise ValueError("Input images must have the same dimensions.")
+    N, _, H, W = (int(v) for v in pred.shape)
+    out = torch.empty(N, 4, dtype=torch.float64, device=pred.device)
+    de_map = torch.empty(N, 1, H, W, dtype=torch.float32, device=pred.device) if with_map else None
+    with torch.cuda.device(pred.device):
+        _color_into(pred, target, out, _color_scratch(N, H, W, pred.device), de_map)
+    scores = (out[:, 0], out[:, 1], out[:, 2], out[:, 3])
+    return scores + (de_map,) if with_map else scores
+
+
+def ciede2000_lab(lab1: torch.Tensor, lab2: torch.Tensor) -> torch.Tensor:
+    """-> float64 ``[n]`` on the device: CIEDE2000 (``kL = kC = kH = 1``) between the rows of two float64 ``[n, 3]`` device tensors of
+    (L, a, b), through the device function ``color_difference`` uses.  For data that is Lab already."""
+    for t, name in ((lab1, "lab1"), (lab2, "lab2")):
+        if not torch.is_tensor(t):
+            raise TypeError(f"hdiff: '{name}' must be a tensor, got {type(t).__name__}")
+        if not t.is_cuda:                           # engine.require_gpu_tensor's refusal; its dtype rule does not apply to Lab rows
+            raise RuntimeError(f"hdiff: '{name}' lives on {t.device}; the HIP path needs an MI355X device tensor "
+                               "(there is deliberately no CPU fallback)")
+    a, b = lab1.detach().contiguous(), lab2.detach().contiguous()
+    if a.dtype != torch.float64 or b.dtype != torch.float64 or a.dim() != 2 or a.shape[1] != 3 or a.shape[0] < 1:
+        raise RuntimeError(f"hdiff: ciede2000_lab takes float64 [n, 3] rows, got {a.dtype} {tuple(a.shape)} and {b.dtype} "
+                           f"{tuple(b.shape)}")
+    if a.shape != b.shape or a.device != b.device:
+        raise ValueError("ciede2000_lab: the two sets of rows must have the same shape and device")
+    out = torch.empty(int(a.shape[0]), dtype=torch.float64, device=a.device)
+    with torch.cuda.device(a.device):
+        _capi.check(_capi.lib().hdiff_ciede2000_lab(a.data_ptr(), b.data_ptr(), int(a.shape[0]), out.data_ptr(), _stream(a.device)),
+                    "ciede2000_lab")
+    return out
 
 
 class LPIPS:
@@ -241,7 +302,10 @@ class QualityMeter:
     Rows are ``COLUMNS`` = (psnr, ssim, uiqm, uicm, uism, uiconm); psnr / ssim are NaN for the images of an ``update`` without a
     target, and the means of those two are taken over the images that had one.  With ``uciqe=True`` every row gains
     ``UCIQE_COLUMNS`` = (uciqe, uciqe_sc, uciqe_conl, uciqe_us) of ``clip(pred, 0, 1) * uciqe_scale`` (``quality.uciqe``); without it
-    the rows, the launches and ``compute``'s dict are those of the six columns alone.  With ``lpips=metric`` (an ``LPIPS``) every row
+    the rows, the launches and ``compute``'s dict are those of the six columns alone.  With ``color=True`` every row gains
+    ``COLOR_COLUMNS`` = (ciede2000, ciede2000_p95, deltae76, angular) of the prediction against its target (``color_difference``),
+    behind UCIQE's where both are on and in front of LPIPS's and NIQE's: NaN for the images of an ``update`` without a target, and
+    their means are taken like PSNR's; without it nothing of it is allocated, launched or reported.  With ``lpips=metric`` (an ``LPIPS``) every row
     gains ``LPIPS_COLUMNS`` = (lpips,) as its LAST column, behind UCIQE's where both are on: the distance of the prediction from its
     target, NaN for the images of an ``update`` without one, and its mean is taken like PSNR's.  With ``niqe=model`` (a ``NIQEModel``)
     every row gains ``NIQE_COLUMNS`` = (niqe,) as its LAST column, behind LPIPS's where both are on: ``update`` leaves the
@@ -251,13 +315,16 @@ class QualityMeter:
     the model's ``patch`` is refused before a row is written.  Without ``niqe=`` nothing of it is allocated, launched or reported."""
 
     def __init__(self, capacity: int = 64, *, uciqe: bool = False, uciqe_scale: float = 1.0, lpips: Optional[LPIPS] = None,
-                 niqe: Optional["NIQEModel"] = None):
+                 niqe: Optional["NIQEModel"] = None, color: bool = False):
         self._capacity = max(1, int(capacity))
         self._uciqe, self._uciqe_scale = bool(uciqe), float(uciqe_scale)
         if lpips is not None and not isinstance(lpips, LPIPS):
             raise TypeError(f"QualityMeter: lpips must be a quality.LPIPS, got {type(lpips).__name__}")
         self._lpips = lpips
+        self._color = bool(color)
         self.columns = COLUMNS + UCIQE_COLUMNS if self._uciqe else COLUMNS
+        if self._color:
+            self.columns = self.columns + COLOR_COLUMNS
         if lpips is not None:
             self.columns = self.columns + LPIPS_COLUMNS
         if niqe is not None and not isinstance(niqe, NIQEModel):
@@ -323,6 +390,13 @@ class QualityMeter:
                 _uciqe_into(pred, self._uciqe_scale, four, _uciqe_scratch(N, H, W, dev))
                 rows[:, 6].copy_(four[:, 3])
                 rows[:, 7:10].copy_(four[:, 0:3])
+            if self._color:
+                at = 10 if self._uciqe else 6
+                if target is not None:
+                    _color_into(pred, target, four, _color_scratch(N, H, W, dev))
+                    rows[:, at:at + 4].copy_(four)
+                else:
+                    rows[:, at:at + 4].fill_(float("nan"))
             if self._lpips is not None:
                 at = len(self.columns) - 1 - (1 if self._niqe is not None else 0)
                 if target is not None:
@@ -341,8 +415,8 @@ class QualityMeter:
     def compute(self) -> Dict[str, object]:
         """{"n", "psnr", "ssim", "uiqm", "uicm", "uism", "uiconm"} as float means over the images (an infinite PSNR makes the mean
         infinite, as the reference's ``sum(list) / len(list)`` does) and "per_image", the ``[n, 6]`` float64 rows; with ``uciqe=True``
-        also the means of ``UCIQE_COLUMNS``, and "per_image" is ``[n, 10]``; with ``lpips=`` also "lpips" (over the images that had a
-        target) and one more column; with ``niqe=`` also "niqe" (over the images whose score is finite), "niqe_undefined" (how many
+        also the means of ``UCIQE_COLUMNS``, and "per_image" is ``[n, 10]``; with ``color=True`` also the means of ``COLOR_COLUMNS`` (over the images that had a
+        target) and four more columns; with ``lpips=`` also "lpips" (likewise) and one more column; with ``niqe=`` also "niqe" (over the images whose score is finite), "niqe_undefined" (how many
         are not) and one more column."""
         per = np.empty((0, len(self.columns))) if self._rows is None else self._rows[:self._n].cpu().numpy()
         if self._niqe is not None and self._n:
@@ -352,7 +426,7 @@ class QualityMeter:
             paired[start:start + count] = has_target
         res: Dict[str, object] = {"n": int(self._n)}
         for j, k in enumerate(self.columns):
-            col = per[paired, j] if k in ("psnr", "ssim", "lpips") else per[:, j]
+            col = per[paired, j] if k in ("psnr", "ssim", "lpips") or k in COLOR_COLUMNS else per[:, j]
             res[k] = float(np.sum(col) / col.size) if col.size else float("nan")
         if self._niqe is not None:
             col = per[:, -1]

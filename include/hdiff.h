@@ -684,6 +684,25 @@ int hdiff_uiqm(const float* a, int N, int H, int W, double* out, void* scratch, 
  * synchronisation, no float atomics: legal under stream capture, bitwise repeatable, independent of N and of the place in the batch. */
 int hdiff_uciqe_workspace(int N, int H, int W, int64_t* bytes);
 int hdiff_uciqe(const float* a, int N, int H, int W, double scale, double* out, void* scratch, hdiff_stream_t stream);
+/* Colour difference between a prediction and its target, per image (csrc/color_diff.hip; tests/_color_def.py is the definition the
+ * kernels are held to; the reference has no such score).  pred, target: fp32 [N][3][H][W]; rgb = double(min(max(x, 0), 1)) of both is
+ * converted to CIE L*a*b* (sRGB, D65, the conversion of hdiff_uciqe) in double.  Per pixel: CIEDE2000 after Sharma, Wu and Dalal 2005
+ * with kL = kC = kH = 1 (pinned to their published table by tests/golden/ciede2000_sharma.json), CIE76, and the angle in degrees
+ * between the two clipped RGB vectors, atan2(|u x v|, u . v), counted where neither vector is black.
+ *   hdiff_color_diff_workspace   bytes of `scratch` for hdiff_color_diff at (N, H, W) (one double plane per image, the histograms and the
+ *                                partials)
+ *   hdiff_color_diff             out[n] = {mean CIEDE2000, its nearest-rank 95th percentile (element (95 H W + 99) / 100 - 1 of the
+ *                                ascending sort), mean CIE76, mean angle over the counted pixels (NaN when there are none)}; map: NULL, or
+ *                                fp32 [N][1][H][W] that receives the per-pixel CIEDE2000 rounded once; fifteen launches
+ *   hdiff_ciede2000_lab          out[i] = CIEDE2000 of the double rows lab1[i], lab2[i] ([n][3]: L, a, b) through the same device function;
+ *                                n in [1, 2^30]; one launch, no scratch
+ * N in [1, 65535], H, W >= 1, H * W <= 2^30.  The percentile is selected on the 64-bit key of the double and is exact at ties.  A
+ * non-finite input value in either image makes the four scores of ITS image NaN.  No allocation, no synchronisation, no float atomics:
+ * legal under stream capture, bitwise repeatable, independent of N and of the place in the batch.  Additions to ABI 6. */
+int hdiff_color_diff_workspace(int N, int H, int W, int64_t* bytes);
+int hdiff_color_diff(const float* pred, const float* target, int N, int H, int W, double* out, float* map, void* scratch,
+                     hdiff_stream_t stream);
+int hdiff_ciede2000_lab(const double* lab1, const double* lab2, int64_t n, double* out, hdiff_stream_t stream);
 /* NIQE (csrc/niqe.hip; Mittal, Soundararajan, Bovik 2013; tests/_niqe_def.py is the definition the kernels are held to; agreement with
  * the authors' MATLAB release is unpinned).  img: fp32 [N][3][H][W] in [0, 1].  The gray plane (quantize != 0: channels and gray rounded
  * to 8-bit values, as a file holds them) is cropped from the top-left corner to bh = H / patch by bw = W / patch whole blocks; P = bh bw.

@@ -26,7 +26,13 @@ With ``--niqe`` four arms alternate: ``QualityMeter.update`` without NIQE, ``Qua
 (default 32; the model is fitted on the targets of the batch), ``quality.niqe`` of ONE ``--niqe-full`` image (default 3024 x 4032) at
 patch 96 -- wall clock, its one synchronisation, copy and host finish included -- and the only host path that exists for it: copy the
 image, then the vectorised numpy definition ``tests/_niqe_def.py``.  The JSON line holds what NIQE adds per update and its ratio to one
-29.4 ms DDIM step, and the two full-size times.  No condition is checked."""
+29.4 ms DDIM step, and the two full-size times.  No condition is checked.
+
+With ``--color`` five arms alternate: ``QualityMeter.update`` plain, with UCIQE (the comparable multi-launch score, for scale) and with
+the colour differences (``color=True``: CIEDE2000, its 95th percentile, CIE76, the angular error); ``quality.color_difference`` of a
+batch of 8 x 8 images, which is the cost of its fifteen launches with next to no arithmetic behind them; and the host path the kernel
+replaces: copy both batches, then the vectorised numpy CIEDE2000 of ``tests/_color_def.py`` per image.  The JSON line holds what the
+colour columns and what UCIQE add per update, and the launch floor.  No condition is checked."""
 import argparse
 import json
 import os
@@ -52,6 +58,8 @@ ap.add_argument("--distribution", action="store_true", help="time the set-level 
                 "frechet_from_moments, and one DistributionMeter.update through dinov2_vits14")
 ap.add_argument("--niqe", action="store_true", help="time QualityMeter.update without / with NIQE, and quality.niqe of one full-size "
                 "image against the numpy definition on the host")
+ap.add_argument("--color", action="store_true", help="time QualityMeter.update without / with the colour differences (and with UCIQE, "
+                "for scale) against a vectorised numpy CIEDE2000 on the host")
 ap.add_argument("--niqe-patch", type=int, default=32, help="--niqe: block side of the meter arm")
 ap.add_argument("--niqe-full", type=int, nargs=2, default=(3024, 4032), metavar=("H", "W"), help="--niqe: the full-size image")
 ap.add_argument("--rows", type=int, default=1024, help="--distribution: rows per feature bank")
@@ -68,8 +76,8 @@ pred = (target + 0.03 * torch.randn(a.batch, 3, a.size, a.size, generator=g)).cl
 pred_d, target_d = pred.to(dev), target.to(dev)
 
 
-def device_arm(uciqe=False, niqe=None):
-    meter = quality.QualityMeter(capacity=a.batch * (a.reps + a.warmup), uciqe=uciqe, niqe=niqe)
+def device_arm(uciqe=False, niqe=None, color=False):
+    meter = quality.QualityMeter(capacity=a.batch * (a.reps + a.warmup), uciqe=uciqe, niqe=niqe, color=color)
     for _ in range(a.warmup):
         meter.update(pred_d, target_d)
     torch.cuda.synchronize(dev)
@@ -133,6 +141,58 @@ if a.uciqe:
                       "added_ms_over_29.4_ms_ddim_step": (sum(added) / len(added)) / 29.4,
                       "host_ms_per_image_min": host_image_best, "added_device_batch_below_one_host_image": ok}))
     sys.exit(0 if ok else 1)
+
+if a.color:
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import _color_def as color_def  # noqa: E402
+    tiny_p, tiny_t = pred_d[:, :, :8, :8].contiguous(), target_d[:, :, :8, :8].contiguous()
+
+    def floor_arm():
+        """``color_difference`` where the fifteen launches are all there is: a batch of 8 x 8 images."""
+        for _ in range(a.warmup):
+            quality.color_difference(tiny_p, tiny_t)
+        torch.cuda.synchronize(dev)
+        start, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        start.record()
+        for _ in range(a.reps):
+            out = quality.color_difference(tiny_p, tiny_t)
+        end.record()
+        end.synchronize()
+        return start.elapsed_time(end) / a.reps, out
+
+    def color_host_arm():
+        t0 = time.perf_counter()
+        p, t = pred_d.cpu().numpy(), target_d.cpu().numpy()
+        rows = [float(np.mean(color_def.pixels_def(p[i], t[i])[0])) for i in range(a.batch)]
+        return (time.perf_counter() - t0) * 1e3, rows
+
+    times = {"meter_ms": [], "meter_with_uciqe_ms": [], "meter_with_color_ms": [], "color_launch_floor_ms": [], "host_ciede2000_batch_ms": []}
+    for rep in range(a.alternate):
+        per_update = lambda ms: f"{ms:.4f} ms per update of {a.batch} ({a.reps} updates between two events)"      # noqa: E731
+        ms0, _ = timed(device_arm, f"meter             rep {rep}:", per_update)
+        ms1, _ = timed(lambda: device_arm(uciqe=True), f"meter with UCIQE  rep {rep}:", per_update)
+        ms2, res = timed(lambda: device_arm(color=True), f"meter with colour rep {rep}:", per_update)
+        ms3, _ = timed(floor_arm, f"colour at 8x8     rep {rep}:",
+                       lambda ms: f"{ms:.4f} ms per call of {a.batch} ({a.reps} calls between two events)")
+        ms4, rows = timed(color_host_arm, f"host CIEDE2000    rep {rep}:",
+                          lambda ms: f"{ms:.2f} ms per batch of {a.batch} = {ms / a.batch:.2f} ms per image (copy included)")
+        for k, ms in zip(times, (ms0, ms1, ms2, ms3, ms4)):
+            times[k].append(ms)
+        gap = max(abs(res["per_image"][i, 6] - rows[i]) / abs(rows[i]) for i in range(a.batch))
+        print(f"                  device against host on this batch: mean CIEDE2000 rel {gap:.1e}; set mean {res['ciede2000']:.6g}, "
+              f"p95 {res['ciede2000_p95']:.6g}, CIE76 {res['deltae76']:.6g}, angular {res['angular']:.6g} deg", flush=True)
+    summary = {k: {"mean": sum(v) / len(v), "min": min(v), "max": max(v), "repetitions": len(v)} for k, v in times.items()}
+    added = [w - p for w, p in zip(times["meter_with_color_ms"], times["meter_ms"])]
+    added_uciqe = [w - p for w, p in zip(times["meter_with_uciqe_ms"], times["meter_ms"])]
+    print(json.dumps({"metric": f"QualityMeter.update of one batch of {a.batch} at {a.size}x{a.size} plain / with UCIQE / with the colour "
+                                f"differences; color_difference of {a.batch} images of 8x8 (its launches alone); a vectorised numpy "
+                                f"CIEDE2000 per image on the host; alternating",
+                      "unit": "ms", "arms": summary, "color_added_ms_per_update": {"mean": sum(added) / len(added), "max": max(added)},
+                      "uciqe_added_ms_per_update": {"mean": sum(added_uciqe) / len(added_uciqe), "max": max(added_uciqe)},
+                      "launch_floor_over_color_added": summary["color_launch_floor_ms"]["mean"] / (sum(added) / len(added)),
+                      "added_ms_over_29.4_ms_ddim_step": (sum(added) / len(added)) / 29.4,
+                      "host_over_added_device": summary["host_ciede2000_batch_ms"]["mean"] / (sum(added) / len(added))}))
+    sys.exit(0)
 
 if a.niqe:
     sys.path.insert(0, os.path.join(ROOT, "tests"))
