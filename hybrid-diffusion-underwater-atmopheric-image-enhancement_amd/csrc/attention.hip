@@ -538,6 +538,21 @@ void launch_v(const float* qkv, float* o, float* lse2, int B, int C, int heads, 
 // and hdiff_mha_flash_fwd_route reports it.  Touches no device.  nq: query tiles per wave of mha_flash_fwd_kernel, as main
 // kernel or as check pass; check: it runs in check mode behind the route's fixed-reference kernel.
 struct MhaFwdRoute { int route, nq, check; };
+
+// The d_head 16 fp16-pair kernel with 256 or 384 queries per workgroup (attention_h2.hip).  Cost of a form = rounds x queries per
+// workgroup, rounds = ceil(pairs ceil(L / QB) / slots) with two workgroups per CU on the MI355X's 256 CUs (the chip this library
+// is built for: no device is asked).  The 384 form's cost is multiplied by H2_Q384_G, its measured time per query against the 256
+// form's; it is taken only where that is cheaper, ties go to 256.
+// H2_Q384_G (profiles/attention_fwd_q384.txt): batch 16, C 128, L 65536, the forms alternating five times in one process: 126.93 ms
+// against 130.79 ms per call = 0.9705, at 43 rounds x 384 against 64 x 256 query units = 1.0078 -> 0.9705 / 1.0078 = 0.963.
+constexpr int H2_WG_SLOTS = 2 * 256;
+constexpr double H2_Q384_G = 0.963;
+bool h2_q384_cheaper(int B, int heads, int L) {
+  const int64_t pairs = (int64_t)B * heads;
+  const int64_t r256 = (pairs * cdiv(L, 256) + H2_WG_SLOTS - 1) / H2_WG_SLOTS, r384 = (pairs * cdiv(L, 384) + H2_WG_SLOTS - 1) / H2_WG_SLOTS;
+  return H2_Q384_G * (double)(r384 * 384) < (double)(r256 * 256);
+}
+
 MhaFwdRoute mha_fwd_route(int B, int C, int heads, int L, bool want_lse, int64_t ws_bytes, int mode) {
   const int D = C / heads;
   // d_head 48 / 64 (ch_mult containing 3 or 4 at ch = 128: C = 384 / 512): the running-max kernel with one query tile per
@@ -548,7 +563,7 @@ MhaFwdRoute mha_fwd_route(int B, int C, int heads, int L, bool want_lse, int64_t
     const int64_t need = mha_fwd_x3p_workspace(B, C, heads, L);
     const bool ws_ok = need != 0 && ws_bytes >= need;
     if (mode == HDIFF_CONTRACT_F16 && !want_lse && ws_ok) return {HDIFF_MHA_FWD_ROUTE_F16_SINGLE, 4, 1};
-    if (ws_ok && D == 16) return {HDIFF_MHA_FWD_ROUTE_H2_PAIRS, 4, 1};
+    if (ws_ok && D == 16) return {h2_q384_cheaper(B, heads, L) ? HDIFF_MHA_FWD_ROUTE_H2_PAIRS_Q384 : HDIFF_MHA_FWD_ROUTE_H2_PAIRS, 4, 1};
     // d_head 32 on the fixed-reference kernel: 134 TFLOP/s against 120 on the running-max kernel (L = 16 384, batch 16)
     if (ws_ok && D == 32) return {HDIFF_MHA_FWD_ROUTE_X3P_PAIRS, 4, 1};
     if (L % KT == 0 && (D == 16 || D == 32)) return {HDIFF_MHA_FWD_ROUTE_X3_TRIPLES, 4, 1};
@@ -568,7 +583,8 @@ void launch_d(const float* qkv, float* o, float* lse2, int B, int C, int heads, 
   if constexpr (D < 48) {      // mha_fwd_route sends d_head 48 / 64 to RUNNING_MAX with nq 1
     switch (rt.route) {
       case HDIFF_MHA_FWD_ROUTE_F16_SINGLE: launch_mha_fwd_f16(qkv, o, B, C, heads, L, qscale, ws, stream); break;
-      case HDIFF_MHA_FWD_ROUTE_H2_PAIRS: launch_mha_fwd_h2(qkv, o, lse2, B, C, heads, L, qscale, ws, stream); break;
+      case HDIFF_MHA_FWD_ROUTE_H2_PAIRS: launch_mha_fwd_h2(qkv, o, lse2, B, C, heads, L, qscale, ws, 4, stream); break;
+      case HDIFF_MHA_FWD_ROUTE_H2_PAIRS_Q384: launch_mha_fwd_h2(qkv, o, lse2, B, C, heads, L, qscale, ws, 6, stream); break;
       case HDIFF_MHA_FWD_ROUTE_X3P_PAIRS: launch_mha_fwd_x3p(qkv, o, lse2, B, C, heads, L, qscale, ws, stream); break;
       case HDIFF_MHA_FWD_ROUTE_X3_TRIPLES: launch_mha_fwd_x3(qkv, o, lse2, B, C, heads, L, qscale, stream); break;
       case HDIFF_MHA_FWD_ROUTE_FAST_F32:
@@ -592,12 +608,17 @@ static int mha_fwd_check_shape(int B, int C, int heads, int L) {
 }
 
 static int mha_flash_fwd_any(const float* qkv, float* o, float* lse2, int B, int C, int heads, int L, void* ws,
-                             int64_t ws_bytes, hipStream_t s) {
+                             int64_t ws_bytes, hipStream_t s, int as_route = -1) {
   HDIFF_CHECK_ARG(qkv && o, "mha_flash_fwd: null pointer");
   const int rc = mha_fwd_check_shape(B, C, heads, L);
   if (rc != HDIFF_OK) return rc;
   // (a NULL ws comes with ws_bytes = 0: hdiff_mha_flash_fwd passes that, hdiff_mha_flash_fwd_ws checks it)
-  const MhaFwdRoute rt = mha_fwd_route(B, C, heads, L, lse2 != nullptr, ws_bytes, contraction_mode());
+  MhaFwdRoute rt = mha_fwd_route(B, C, heads, L, lse2 != nullptr, ws_bytes, contraction_mode());
+  if (as_route >= 0 && as_route != rt.route) {      // hdiff_mha_flash_fwd_ws_as: only between the two forms of the d_head 16 pair kernel
+    auto h2 = [](int r) { return r == HDIFF_MHA_FWD_ROUTE_H2_PAIRS || r == HDIFF_MHA_FWD_ROUTE_H2_PAIRS_Q384; };
+    HDIFF_CHECK_ARG(h2(as_route) && h2(rt.route), "mha_flash_fwd_ws_as: route %d is no form of this call's route %d", as_route, rt.route);
+    rt.route = as_route;
+  }
   (void)hipGetLastError();  // drop any stale error left by another HIP user in this thread
   with_head_dim(C / heads, [&](auto d) { launch_d<decltype(d)::value>(qkv, o, lse2, B, C, heads, L, ws, rt, s); });
   HDIFF_CHECK_LAUNCH("mha_flash_fwd_kernel");
@@ -621,6 +642,13 @@ extern "C" int hdiff_mha_flash_fwd_ws(const float* qkv, float* o, float* lse2, i
                                       int64_t ws_bytes, hdiff_stream_t stream) {
   HDIFF_CHECK_ARG(ws_bytes >= 0 && (ws != nullptr || ws_bytes == 0), "mha_flash_fwd_ws: workspace pointer / size mismatch");
   return mha_flash_fwd_any(qkv, o, lse2, B, C, heads, L, ws, ws_bytes, (hipStream_t)stream);
+}
+
+extern "C" int hdiff_mha_flash_fwd_ws_as(const float* qkv, float* o, float* lse2, int B, int C, int heads, int L, void* ws,
+                                         int64_t ws_bytes, int route, hdiff_stream_t stream) {
+  HDIFF_CHECK_ARG(ws_bytes >= 0 && (ws != nullptr || ws_bytes == 0), "mha_flash_fwd_ws: workspace pointer / size mismatch");
+  HDIFF_CHECK_ARG(route >= 0, "mha_flash_fwd_ws_as: route %d", route);
+  return mha_flash_fwd_any(qkv, o, lse2, B, C, heads, L, ws, ws_bytes, (hipStream_t)stream, route);
 }
 
 extern "C" int hdiff_mha_flash_fwd_route(int B, int C, int heads, int L, int want_lse, int64_t ws_bytes, int* route_out,

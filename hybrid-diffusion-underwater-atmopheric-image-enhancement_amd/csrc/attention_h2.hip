@@ -253,12 +253,28 @@ __global__ __launch_bounds__(THREADS) void v_split_h2_kernel(const float* __rest
   }
 }
 
+// f(integral_constant<int, I>) for I = FROM .. TO - 1, written out at compile time
+template <int FROM, int TO, class F>
+__device__ __forceinline__ void static_for(F&& f) {
+  if constexpr (FROM < TO) {
+    f(std::integral_constant<int, FROM>{});
+    static_for<FROM + 1, TO>(f);
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// NQ query tiles of 16 per wave, QB = 64 NQ queries per four-wave workgroup; every 64-key tile is staged (global -> LDS), waited
+// for behind one barrier and read into operand registers ONCE per workgroup / wave, whatever NQ is -- so the larger NQ, the
+// smaller those costs per query.  NQ = 4 (256 queries) and NQ = 6 (384 queries: 17 more registers per extra tile -- Q operands
+// 8, O 4, -m 4, l 1 -- still two workgroups per CU, the second one in the barrier's shadow); mha_fwd_route picks.  The grid is
+// ceil(L / QB): with L a multiple of 256, the last workgroup of the 384 form may hold query tiles at or past L; such a tile
+// reads the Q rows of tile 0 of the head (valid memory), runs every stage like the others and stores nothing.
 // ---------------------------------------------------------------------------------------------------------------------
 template <int D, int NQ>
 __global__ __launch_bounds__(THREADS, 2) void mha_flash_fwd_h2_kernel(const __bf16* __restrict__ ws, float* __restrict__ out,
                                                                       float* __restrict__ lse2, int C, int L, float one) {
   static_assert(D == 16, "head dim: two terms share one MFMA's 32 contraction slots");
-  static_assert(NQ == 4, "the stage pipeline is written for four query tiles per wave");
+  static_assert(NQ >= 4 && (NQ & 1) == 0, "the S / P double buffers alternate by the query tile's parity: an even number of tiles per wave");
   constexpr int NKP = 4;                   // K pieces (see PAIR_SHIFT)
   constexpr int NKS = 2;                   // K operand sets per 16 keys = QK^T MFMAs per 16x16 score tile
   constexpr int NQK = NKS;
@@ -268,6 +284,7 @@ __global__ __launch_bounds__(THREADS, 2) void mha_flash_fwd_h2_kernel(const __bf
   constexpr int VROWB = KT * 2 + 8;        // bytes per d row of one V piece (+8: the 16 rows of an operand read spread over banks)
   constexpr int VPART = D * VROWB;
   constexpr int QB = 64 * NQ;              // queries per workgroup (4 waves x NQ tiles of 16)
+  constexpr bool RAGGED = 256 % QB != 0;   // L is a multiple of 256: the last workgroup may reach past L (whole query tiles)
   constexpr int VBASE = NKP * KPART;
   constexpr int BUFB = VBASE + 2 * VPART;
   __shared__ __attribute__((aligned(16))) unsigned char smem[2][BUFB];
@@ -285,7 +302,7 @@ __global__ __launch_bounds__(THREADS, 2) void mha_flash_fwd_h2_kernel(const __bf
 
   const size_t piece_n = (size_t)L * D;
   const __bf16* wsq = ws + ((size_t)b * gridDim.y + head) * F_COUNT * piece_n;
-  // Q operands of the wave's four query tiles, in registers for the whole kernel: [query tile][MFMA].  The workspace holds q0 and
+  // Q operands of the wave's NQ query tiles, in registers for the whole kernel: [query tile][MFMA].  The workspace holds q0 and
   // q1 2^8; q0 2^-8 and q1 are their multiples (v_pk_mul_f16 by 2^-8: exact, or rounded into fp16's subnormals like the split
   // pass would have).
   u32x4 qop[NQ][NQK];
@@ -293,7 +310,8 @@ __global__ __launch_bounds__(THREADS, 2) void mha_flash_fwd_h2_kernel(const __bf
     const unsigned dn2 = PAIR_DOWN2;
 #pragma unroll
     for (int qt = 0; qt < NQ; ++qt) {
-      const int q = qblk0 + qt * 16 + i16;
+      const int qt0 = qblk0 + qt * 16;
+      const int q = (RAGGED && qt0 >= L ? 0 : qt0) + i16;      // a tile past L: rows 0 .. 15, never stored
       const u32x4 q0 = *reinterpret_cast<const u32x4*>(wsq + (size_t)q * D + doff);
       const u32x4 q1s = *reinterpret_cast<const u32x4*>(wsq + piece_n + (size_t)q * D + doff);
       const u32x4 sel = hi ? q1s : q0;  // this lane's half of the pairing: (q0, q0 2^-8) on the low slots, (q1 2^8, q1) on the high ones
@@ -428,7 +446,7 @@ __global__ __launch_bounds__(THREADS, 2) void mha_flash_fwd_h2_kernel(const __bf
     return fmaxf(mx, __shfl_xor(mx, 32, 64));
   };
   // One stage = the vector work of (tile, query tile QT): S[par] -> P pieces in pop[par] -- hand-interleaved with the
-  // MFMAs of the neighbouring stages: Q K^T for the NEXT stage (into S[par ^ 1]; for QT = 3 that is query tile 0 of the
+  // MFMAs of the neighbouring stages: Q K^T for the NEXT stage (into S[par ^ 1]; for QT = NQ - 1 that is query tile 0 of the
   // next key tile, whose K operands are in kop by then) and P V of the PREVIOUS one (pop[par ^ 1]).  The order is written
   // out and fenced slot by slot (one MFMA, about three vector instructions): left to the scheduler the MFMAs of a stage
   // clump, and a vector instruction only runs beside an MFMA, not instead of waiting for one.
@@ -506,7 +524,9 @@ __global__ __launch_bounds__(THREADS, 2) void mha_flash_fwd_h2_kernel(const __bf
   };
 
   // Key tile t (buffer t & 1).  On entry: kop = K(t), S[0] = scores of (t, query tile 0), global loads of tile t + 1 in
-  // flight; unless FIRST, vop = V(t - 1) and pop[1] = P(t - 1, 3) with its P V pending.
+  // flight; unless FIRST, vop = V(t - 1) and pop[1] = P(t - 1, NQ - 1) with its P V pending.
+  // Stages 0 .. NQ - 1; the hand-over of tile t + 1 (V into LDS, the wait for its K runs, the barrier, the loads of tile t + 2) sits
+  // in the middle, behind stage NQ / 2 - 1, and K(t + 1) rolls into kop in stage NQ - 2, whose Q K^T is the last one on K(t).
   auto tile_fn = [&](auto first_tag, int t) {
     constexpr bool FIRST = decltype(first_tag)::value;
     using Pend = std::integral_constant<bool, !FIRST>;
@@ -514,14 +534,18 @@ __global__ __launch_bounds__(THREADS, 2) void mha_flash_fwd_h2_kernel(const __bf
     if constexpr (FIRST) load_v(buf);
     stage_fn(std::integral_constant<int, 0>{}, first_tag, Pend{});
     if constexpr (!FIRST) load_v(buf);
-    stage_fn(std::integral_constant<int, 1>{}, first_tag, std::true_type{});
-    stage_store(buf ^ 1);                 // tile t + 1: its buffer was last read before the previous tile's barrier
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // this wave's K runs of tile t + 1 have landed in buffer buf ^ 1
-    __syncthreads();
-    stage_load((t + 2 < ntiles) ? t + 2 : ntiles - 1);
-    dma_k((t + 2 < ntiles) ? t + 2 : ntiles - 1, buf);      // buffer buf is free: K(t) sits in kop since the last tile, V(t) was read above
-    stage_fn(std::integral_constant<int, 2>{}, first_tag, std::true_type{}, buf ^ 1);    // K(t + 1) follows K(t) through kop
-    stage_fn(std::integral_constant<int, 3>{}, first_tag, std::true_type{});
+    static_for<1, NQ>([&](auto qt_tag) {
+      constexpr int QT = decltype(qt_tag)::value;
+      if constexpr (QT == NQ - 2) stage_fn(qt_tag, first_tag, std::true_type{}, buf ^ 1);    // K(t + 1) follows K(t) through kop
+      else stage_fn(qt_tag, first_tag, std::true_type{});
+      if constexpr (QT == NQ / 2 - 1) {
+        stage_store(buf ^ 1);                 // tile t + 1: its buffer was last read before the previous tile's barrier
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // this wave's K runs of tile t + 1 have landed in buffer buf ^ 1
+        __syncthreads();
+        stage_load((t + 2 < ntiles) ? t + 2 : ntiles - 1);
+        dma_k((t + 2 < ntiles) ? t + 2 : ntiles - 1, buf);      // buffer buf is free: K(t) sits in kop since the last tile, V(t) was read above
+      }
+    });
   };
 
   stage_load(0);
@@ -549,6 +573,7 @@ __global__ __launch_bounds__(THREADS, 2) void mha_flash_fwd_h2_kernel(const __bf
     const bool bad = !(lt < OVERFLOW_LIMIT);            // NaN / inf inputs: hand this query block to the fp32 kernel's check pass
     const float inv = bad ? __builtin_nanf("") : 1.0f / lt;
     const int q = qblk0 + qt * 16 + i16;
+    if (RAGGED && qblk0 + qt * 16 >= L) continue;      // a whole tile past L (wave-uniform): nothing of it is stored
     if (lse2 != nullptr && g == 0)
       lse2[((size_t)b * gridDim.y + head) * L + q] = bad ? __builtin_nanf("") : __builtin_amdgcn_logf(lt) - negm4[qt][0];
 #pragma unroll
@@ -581,13 +606,17 @@ void launch_qk_split_h2(const float* qkv, void* ws, int B, int C, int heads, int
 }
 
 // The d_head 16 forward on fp16 pairs (scores: four balanced products; P.V: three) on its own operand layout in the workspace.
-// Precondition (HDIFF_MHA_FWD_ROUTE_H2_PAIRS): d_head 16 and ws holds mha_fwd_x3p_workspace bytes, non-zero for this shape.
-void launch_mha_fwd_h2(const float* qkv, float* o, float* lse2, int B, int C, int heads, int L, float qscale, void* ws,
+// Precondition (HDIFF_MHA_FWD_ROUTE_H2_PAIRS, _Q384): d_head 16 and ws holds mha_fwd_x3p_workspace bytes, non-zero for this shape
+// (so L is a multiple of 256, >= 512).  nq: query tiles per wave, 4 (256 queries per workgroup) or 6 (384, the last workgroup ragged).
+void launch_mha_fwd_h2(const float* qkv, float* o, float* lse2, int B, int C, int heads, int L, float qscale, void* ws, int nq,
                        hipStream_t stream) {
   launch_qk_split_h2(qkv, ws, B, C, heads, L, qscale, stream);
   launch_v_split_h2(qkv, ws, B, C, heads, L, stream);
-  hipLaunchKernelGGL((mha_flash_fwd_h2_kernel<16, 4>), dim3(L / 256, heads, B), dim3(THREADS), 0, stream, (const __bf16*)ws, o, lse2,
-                     C, L, 1.0f);
+  const dim3 grid(cdiv(L, 64 * nq), heads, B);
+  if (nq == 6)
+    hipLaunchKernelGGL((mha_flash_fwd_h2_kernel<16, 6>), grid, dim3(THREADS), 0, stream, (const __bf16*)ws, o, lse2, C, L, 1.0f);
+  else
+    hipLaunchKernelGGL((mha_flash_fwd_h2_kernel<16, 4>), grid, dim3(THREADS), 0, stream, (const __bf16*)ws, o, lse2, C, L, 1.0f);
 }
 
 }  // namespace hdiff

@@ -343,12 +343,17 @@ enum {
   HDIFF_MHA_FWD_ROUTE_RUNNING_MAX = 0, /* mha_flash_fwd_kernel<D, nq> alone (check = 0) */
   HDIFF_MHA_FWD_ROUTE_FAST_F32 = 1,    /* mha_flash_fwd_fast_kernel<D, 4>, then the check pass */
   HDIFF_MHA_FWD_ROUTE_X3_TRIPLES = 2,  /* mha_flash_fwd_x3_kernel (splits in its loop), then the check pass */
-  HDIFF_MHA_FWD_ROUTE_H2_PAIRS = 3,    /* d_head 16 on the pre-split workspace, then the check pass */
+  HDIFF_MHA_FWD_ROUTE_H2_PAIRS = 3,    /* d_head 16 on the pre-split workspace, 256 queries per workgroup, then the check pass */
   HDIFF_MHA_FWD_ROUTE_X3P_PAIRS = 4,   /* d_head 32 on the pre-split workspace, then the check pass */
-  HDIFF_MHA_FWD_ROUTE_F16_SINGLE = 5   /* f16 mode, no log-sum-exp, single fp16 pieces, then the check pass */
+  HDIFF_MHA_FWD_ROUTE_F16_SINGLE = 5,  /* f16 mode, no log-sum-exp, single fp16 pieces, then the check pass */
+  HDIFF_MHA_FWD_ROUTE_H2_PAIRS_Q384    /* (6) H2_PAIRS with 384 queries per workgroup, where rounds x queries says it is cheaper: same bits */
 };
 int hdiff_mha_flash_fwd_route(int B, int C, int heads, int L, int want_lse, int64_t ws_bytes, int* route_out, int* nq_out,
                               int* check_out);
+/* hdiff_mha_flash_fwd_ws on a named route (tests, A/B timing): `route` is the one hdiff_mha_flash_fwd_route answers for the call, or
+ * the other of H2_PAIRS / H2_PAIRS_Q384 where it answers one of these two; every other value is refused. */
+int hdiff_mha_flash_fwd_ws_as(const float* qkv, float* o, float* lse2 /*[B][heads][L] or NULL*/, int B, int C, int heads, int L,
+                              void* ws, int64_t ws_bytes, int route, hdiff_stream_t stream);
 /* Single-head attention with a head wider than 64 channels: softmax(q k^T * C^-1/2) v with d_head = C, the core of the
  * reference's AttnBlock (ModelCondition.py:109-116; dead code there, built for completeness: one workgroup per query row,
  * L + C floats of LDS).  qkv [B][3C][L] rows [q | k | v], o [B][C][L].  Heads of width <= 64: hdiff_mha_flash_fwd, heads = 1. */

@@ -1,5 +1,5 @@
 """Dev tool (round 6): what clock and board power does ONE hot kernel hold when it runs back to back?
-  python tools/kernel_power.py bwd16|bwd32|fwd16|fwd32|conv3 [batch] [seconds] [--no-lse] [--contract f32|bf16x3|f16]
+  python tools/kernel_power.py bwd16|bwd32|fwd16|fwd32|conv3 [batch] [seconds] [--no-lse] [--contract f32|bf16x3|f16] [--route N]
 (conv3: the 128 -> 128 3x3 convolution at 256x256 behind GroupNorm, fp16 pairs; --no-lse: the forward as inference calls it, lse2 = NULL --
 with --contract f16 that is the call the single-piece fp16 kernels of attention_f16.hip take)
 Runs the launch in a loop for `seconds` (default 4) after a 1 s warm-up, samples the engine clock and the board power from sysfs at
@@ -25,7 +25,12 @@ if "--contract" in sys.argv:
     i = sys.argv.index("--contract")
     hdiff_amd.set_contraction_mode(sys.argv[i + 1])
     del sys.argv[i:i + 2]
-what = sys.argv[1] if len(sys.argv) > 1 else "bwd16"
+route = None          # --route N: the forward on that HDIFF_MHA_FWD_ROUTE_* (hdiff_mha_flash_fwd_ws_as: 3 / 6 = the d_head 16 pair kernel's 256 / 384 form)
+if "--route" in sys.argv:
+    i = sys.argv.index("--route")
+    route = int(sys.argv[i + 1])
+    del sys.argv[i:i + 2]
+what =sys.argv[1] if len(sys.argv) > 1 else "bwd16"
 B = int(sys.argv[2]) if len(sys.argv) > 2 else (16 if what.startswith("fwd") else 4)
 secs = float(sys.argv[3]) if len(sys.argv) > 3 else 4.0
 if what == "conv3":
@@ -61,7 +66,11 @@ elif what.startswith("fwd"):
     ws = torch.empty(max(need.value, 16), dtype=torch.uint8, device="cuda")
 
     def run():
-        rc = lib.hdiff_mha_flash_fwd_ws(qkv.data_ptr(), o.data_ptr(), None if no_lse else lse.data_ptr(), B, Cc, 8, L, ws.data_ptr(), need.value, s)
+        if route is None:
+            rc = lib.hdiff_mha_flash_fwd_ws(qkv.data_ptr(), o.data_ptr(), None if no_lse else lse.data_ptr(), B, Cc, 8, L, ws.data_ptr(), need.value, s)
+        else:
+            rc = lib.hdiff_mha_flash_fwd_ws_as(qkv.data_ptr(), o.data_ptr(), None if no_lse else lse.data_ptr(), B, Cc, 8, L, ws.data_ptr(), need.value,
+                                               route, s)
         assert rc == 0, lib.hdiff_last_error()
 else:
     d_o = torch.randn(B, Cc, L, device="cuda")
@@ -98,5 +107,5 @@ ms = e0.elapsed_time(e1) / n
 c = clock.summary()
 if what == "conv3":
     ms /= 50
-print(f"{what} [{hdiff_amd.get_contraction_mode()}{', no lse' if no_lse else ''}] B={B} C={Cc} L={L}: {ms:.3f} ms per launch over {n} launches; sclk {c.get('sclk_mhz_mean')} MHz "
+print(f"{what} [{hdiff_amd.get_contraction_mode()}{', no lse' if no_lse else ''}{'' if route is None else f', route {route}'}] B={B} C={Cc} L={L}: {ms:.3f} ms per launch over {n} launches; sclk {c.get('sclk_mhz_mean')} MHz "
       f"(min {c.get('sclk_mhz_min')}, max {c.get('sclk_mhz_max')}), board {c.get('board_power_w_mean')} W", flush=True)
