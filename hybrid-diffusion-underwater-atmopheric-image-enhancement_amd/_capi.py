@@ -197,11 +197,16 @@ _PROTOS = {
     "hdiff_randn_rows": (C.c_int, [C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_uint64, C.c_void_p]),
     "hdiff_ddim_eta_step": (C.c_int, [C.c_void_p] * 6 + [C.c_int64, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
     "hdiff_sample_stats": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "hdiff_v_to_eps": (C.c_int, [C.c_void_p] * 5 + [C.c_int, C.c_int, C.c_int64, C.c_void_p]),
     "hdiff_resize_nearest": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "hdiff_avgpool_global": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "hdiff_train_b_loss_workspace": (C.c_int, [C.c_int64, C.POINTER(C.c_int64)]),
     "hdiff_train_b_loss_fwd": (C.c_int, [C.c_void_p] * 7 + [C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 5),
     "hdiff_train_b_loss_bwd": (C.c_int, [C.c_void_p] * 7 + [C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 5),
+    "hdiff_train_b_tail_fwd": (C.c_int, [C.c_void_p] * 7 + [C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 4 +
+                               [C.c_int, C.c_void_p, C.c_float, C.c_void_p]),
+    "hdiff_train_b_tail_bwd": (C.c_int, [C.c_void_p] * 7 + [C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 4 +
+                               [C.c_int, C.c_void_p, C.c_float, C.c_void_p]),
     "hdiff_msssim_l1_workspace": (C.c_int, [C.POINTER(MsssimDesc), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "hdiff_msssim_l1_fwd": (C.c_int, [C.POINTER(MsssimDesc)] + [C.c_void_p] * 6),
     "hdiff_msssim_l1_bwd": (C.c_int, [C.POINTER(MsssimDesc)] + [C.c_void_p] * 7),

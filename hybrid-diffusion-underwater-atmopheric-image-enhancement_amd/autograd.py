@@ -712,10 +712,12 @@ class _ResizeFn(Function):
 
 class _TrainTailFn(Function):
     """The trainer's loss tail (diffusion/Diffusion.py:102-107, :172-174) in one launch pair: -> (mse [B,3,H,W], y0_pred
-    [B,3,H,W], col_loss []).  Backward: ONE pass forming d noise_pred from the three incoming gradients (any may be absent)."""
+    [B,3,H,W], col_loss []).  Backward: ONE pass forming d noise_pred from the three incoming gradients (any may be absent).
+    ``mode``: None runs the reference's own pair (``hdiff_train_b_loss_fwd`` / ``_bwd``); ``(prediction code, weight table or None,
+    y0 divisor)`` runs ``hdiff_train_b_tail_fwd`` / ``_bwd`` with those arguments."""
 
     @staticmethod
-    def forward(ctx, noise_pred, noise, y_t, gt, t, sa, s1m):
+    def forward(ctx, noise_pred, noise, y_t, gt, t, sa, s1m, mode=None):
         noise_pred = noise_pred.contiguous()
         lib = _capi.lib()
         B, Cc, H, W = (int(v) for v in noise_pred.shape)
@@ -727,10 +729,14 @@ class _TrainTailFn(Function):
         nbytes = C.c_int64(0)
         _capi.check(lib.hdiff_train_b_loss_workspace(B * H * W, C.byref(nbytes)), "train_b_loss_workspace")
         ws = torch.empty(nbytes.value // 4, dtype=torch.float32, device=dev)
-        _capi.check(lib.hdiff_train_b_loss_fwd(noise_pred.data_ptr(), noise.data_ptr(), y_t.data_ptr(), gt.data_ptr(), t.data_ptr(),
-                                               sa.data_ptr(), s1m.data_ptr(), int(sa.numel()), B, H * W, mse.data_ptr(),
-                                               y0.data_ptr(), col.data_ptr(), ws.data_ptr(), _stream(dev)), "train_b_loss_fwd")
+        args = (noise_pred.data_ptr(), noise.data_ptr(), y_t.data_ptr(), gt.data_ptr(), t.data_ptr(), sa.data_ptr(), s1m.data_ptr(),
+                int(sa.numel()), B, H * W, mse.data_ptr(), y0.data_ptr(), col.data_ptr(), ws.data_ptr())
+        if mode is None:
+            _capi.check(lib.hdiff_train_b_loss_fwd(*args, _stream(dev)), "train_b_loss_fwd")
+        else:
+            _capi.check(lib.hdiff_train_b_tail_fwd(*args, mode[0], _p(mode[1]), C.c_float(mode[2]), _stream(dev)), "train_b_tail_fwd")
         ctx.set_materialize_grads(False)
+        ctx.mode = mode
         ctx.save_for_backward(noise_pred, noise, y0, gt, t, sa, s1m)
         return mse, y0, col
 
@@ -742,17 +748,38 @@ class _TrainTailFn(Function):
             B, _, H, W = (int(v) for v in noise_pred.shape)
             d_np = torch.empty_like(noise_pred)
             d_mse, d_y0, d_col = _c(d_mse), _c(d_y0), _c(d_col)
-            _capi.check(_capi.lib().hdiff_train_b_loss_bwd(noise_pred.data_ptr(), noise.data_ptr(), y0.data_ptr(), gt.data_ptr(),
-                                                           t.data_ptr(), sa.data_ptr(), s1m.data_ptr(), int(sa.numel()), B, H * W,
-                                                           _p(d_mse), _p(d_y0), _p(d_col), d_np.data_ptr(),
-                                                           _stream(noise_pred.device)), "train_b_loss_bwd")
-        return d_np, None, None, None, None, None, None
+            lib, mode, s = _capi.lib(), ctx.mode, _stream(noise_pred.device)
+            args = (noise_pred.data_ptr(), noise.data_ptr(), y0.data_ptr(), gt.data_ptr(), t.data_ptr(), sa.data_ptr(), s1m.data_ptr(),
+                    int(sa.numel()), B, H * W, _p(d_mse), _p(d_y0), _p(d_col), d_np.data_ptr())
+            if mode is None:
+                _capi.check(lib.hdiff_train_b_loss_bwd(*args, s), "train_b_loss_bwd")
+            else:
+                _capi.check(lib.hdiff_train_b_tail_bwd(*args, mode[0], _p(mode[1]), C.c_float(mode[2]), s), "train_b_tail_bwd")
+        return d_np, None, None, None, None, None, None, None
 
 
-def train_b_loss_tail(noise_pred, noise, y_t, gt, t, sqrt_ab, sqrt_1mab):
-    """(mse, y0_pred, col_loss) of GaussianDiffusionTrainer.forward; sqrt_ab / sqrt_1mab are fp32 tables of length T."""
+PREDICTION_CODES = {"eps": 0, "v": 1}          # HDIFF_PREDICT_EPS / HDIFF_PREDICT_V (include/hdiff.h)
+
+
+def train_b_loss_tail(noise_pred, noise, y_t, gt, t, sqrt_ab, sqrt_1mab, prediction="eps", weight_tab=None, y0_div=255.0):
+    """(mse, y0_pred, col_loss) of GaussianDiffusionTrainer.forward; sqrt_ab / sqrt_1mab are fp32 tables of length T.
+    ``prediction``: what ``noise_pred`` (the network's output) stands for, "eps" or "v"; ``weight_tab``: an fp32 table of length T
+    whose entry at ``t`` multiplies the squared error (None: no multiply); ``y0_div``: the divisor of ``y0_pred`` (the reference's
+    literal 255).  With all three at their defaults this launches the reference's own pair, as before they existed."""
+    if prediction not in PREDICTION_CODES:
+        raise ValueError(f"hdiff: prediction must be one of {tuple(PREDICTION_CODES)}, got {prediction!r}")
+    y0_div = float(y0_div)
+    if y0_div != y0_div or y0_div == 0.0:
+        raise ValueError(f"hdiff: y0_div must be a number other than 0, got {y0_div!r}")
+    mode = None
+    if prediction != "eps" or weight_tab is not None or y0_div != 255.0:
+        if weight_tab is not None:
+            weight_tab = weight_tab.contiguous()
+            if weight_tab.dtype != torch.float32 or weight_tab.numel() != sqrt_ab.numel() or weight_tab.device != sqrt_ab.device:
+                raise ValueError("hdiff: weight_tab must be an fp32 table of the schedule's length on the schedule's device")
+        mode = (PREDICTION_CODES[prediction], weight_tab, y0_div)
     return _TrainTailFn.apply(noise_pred, noise.contiguous(), y_t.contiguous(), gt.contiguous(), t.contiguous(),
-                              sqrt_ab.contiguous(), sqrt_1mab.contiguous())
+                              sqrt_ab.contiguous(), sqrt_1mab.contiguous(), mode)
 
 
 class MsssimConfig:

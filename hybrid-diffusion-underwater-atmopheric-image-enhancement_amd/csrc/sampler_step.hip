@@ -3,8 +3,8 @@
 // bookkeeping), DDIM and DPM-Solver++(2M) of the image-conditioned one (diffusion/Diffusion.py), untiled and over overlapping
 // windows -- and what a step runs around them: the time-vector fills, the counter decrement and the window crop.  Behind them the
 // three kernels of multi-sample posterior sampling: the DDIM update with its stochastic term (eta), the per-sample normal fill and
-// the mean / spread over an image's samples.  All HBM- or latency-bound streaming kernels, one launch beside a whole UNet
-// evaluation.
+// the mean / spread over an image's samples -- and the conversion that lets a v-prediction network feed any of the image-conditioned
+// updates.  All HBM- or latency-bound streaming kernels, one launch beside a whole UNet evaluation.
 //
 // Every update must round exactly like separate fp32 tensor ops (the reference's mul / sub / add; for the added solvers a plain
 // torch program of the same lines): one rounding per written operation.  fma contraction is forbidden in this file (hipcc
@@ -34,6 +34,9 @@ __device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? l
 
 // a device-resident counter's value as an index into a table of `count` rows: never outside it, whatever the counter holds
 __device__ __forceinline__ int step_index(int k, int count) { return k < 0 ? 0 : (k >= count ? count - 1 : k); }
+
+// a time step read from device memory as an index into a table of T rows: never outside it
+__device__ __forceinline__ int time_index(int64_t t, int T) { return t < 0 ? 0 : (t >= T ? T - 1 : (int)t); }
 
 // the NaN check of the reference's per-step assert, evaluated once after the loop from this flag: one atomic per wave that saw one
 __device__ __forceinline__ void flag_nan(bool bad, int32_t* nan_flag) {
@@ -394,6 +397,45 @@ __global__ void ddim_eta_step_kernel(const float* y, const float* __restrict__ e
   flag_nan(bad, nan_flag);
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// A v-prediction network in front of the image-conditioned sampler's updates (Salimans & Ho 2022): the model's output becomes the
+// noise estimate every update kernel above and below takes,
+//   out = a * out + s * y,   a = sa_tab[t[b]], s = s1m_tab[t[b]]  of the row's own time step
+// in place, one launch behind the UNet, two products and one sum rounded apart.  The tables are sqrt(alphas_bar) and
+// sqrt(1 - alphas_bar) at the index the model is CALLED with -- the trainer's q_sample indexing, not the DDIM loop's
+// alphas_bar[t + 1].  The B rows of n_per floats are walked as one run of quads: a quad may straddle two rows (n_per = 3 H W is odd
+// for odd sizes), so the row is tracked per element; 16-byte accesses on aligned buffers, the last quad of the run element by
+// element.  HBM traffic: 12 bytes per element.  An element's result depends on its own two inputs alone.
+// ---------------------------------------------------------------------------------------------------------------------
+__global__ void v_to_eps_kernel(float* out, const float* __restrict__ y, const int64_t* __restrict__ t,
+                                const float* __restrict__ sa_tab, const float* __restrict__ s1m_tab, int T, int B, int64_t n_per,
+                                int64_t n, int vec) {
+  const int64_t nq = (n + 3) >> 2;
+  for (int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; q < nq; q += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t i0 = q << 2;
+    const bool wide = vec != 0 && i0 + 3 < n;
+    float ov[4], yv[4], v[4];
+    ld4(out, i0, n, wide, ov);
+    ld4(y, i0, n, wide, yv);
+    int64_t b = i0 / n_per, rem = i0 - b * n_per;
+    int k = time_index(t[b], T);
+    float a = sa_tab[k], s = s1m_tab[k];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      if (rem == n_per) {                           // the quad runs on into the next row (past the last one: values never stored)
+        rem = 0;
+        b = b + 1 < B ? b + 1 : B - 1;
+        k = time_index(t[b], T);
+        a = sa_tab[k];
+        s = s1m_tab[k];
+      }
+      v[e] = a * ov[e] + s * yv[e];
+      ++rem;
+    }
+    st4(out, i0, n, wide, v);
+  }
+}
+
 // Mean and spread of the K samples of every image, samples [B][K][n] -> mean, std [B][n].  Per element, in double, in replica order:
 //   m = (x_0 + x_1 + ... ) / K ;  std = sqrt(((x_0 - m)^2 + (x_1 - m)^2 + ...) / (K - 1)), exactly 0 for K = 1
 // each rounded once to fp32.  One thread per element, K coalesced reads twice over (the second pass hits the cache); no atomics, the
@@ -698,6 +740,19 @@ int hdiff_ddim_eta_step(const float* y, const float* eps, const float* noise, fl
   hipLaunchKernelGGL(ddim_eta_step_kernel, dim3(grid_ceil_8k(nq)), dim3(256), 0, (hipStream_t)stream, y, eps, noise, y_next, tab,
                      seeds, n_per, nq_row, nq, step_ptr, nsteps, nan_flag, vec);
   HDIFF_CHECK_LAUNCH("ddim_eta_step_kernel");
+  return HDIFF_OK;
+}
+
+int hdiff_v_to_eps(float* out, const float* y, const int64_t* t, const float* sqrt_ab, const float* sqrt_1mab, int T, int B,
+                   int64_t n_per, hdiff_stream_t stream) {
+  HDIFF_CHECK_ARG(out && y && t && sqrt_ab && sqrt_1mab, "v_to_eps: null pointer");
+  HDIFF_CHECK_ARG(T > 0 && B > 0 && n_per > 0, "v_to_eps: bad sizes T=%d B=%d n_per=%lld", T, B, (long long)n_per);
+  (void)hipGetLastError();  // drop any stale error left by another HIP user in this thread
+  const int64_t n = (int64_t)B * n_per;
+  const int vec = aligned16(out) && aligned16(y);
+  hipLaunchKernelGGL(v_to_eps_kernel, dim3(grid_ceil_8k(n, 4)), dim3(256), 0, (hipStream_t)stream, out, y, t, sqrt_ab, sqrt_1mab, T,
+                     B, n_per, n, vec);
+  HDIFF_CHECK_LAUNCH("v_to_eps_kernel");
   return HDIFF_OK;
 }
 

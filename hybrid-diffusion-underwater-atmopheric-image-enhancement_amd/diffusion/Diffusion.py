@@ -31,6 +31,13 @@ callables (``dino_loss=``, ``msssim_loss=``); a term without one is returned as 
 form: ``dino_loss="native"`` builds ``Loss.loss.PerceptualLoss_dino`` (a frozen DINOv2 ViT on ``csrc/dino.hip`` and the package's
 dense-layer and attention kernels; ``dino_weights=`` is the hub checkpoint's state dict, nothing is fetched), and
 ``Loss.loss.MSSSIMLoss()`` (``csrc/msssim.hip``) is what to pass as ``msssim_loss=``; nothing here imports torch.hub or kornia.
+
+What the network predicts (an addition to the reference's surface): ``prediction="v"`` on the trainer makes the model's output
+``v = sqrt(ab) * noise - sqrt(1 - ab) * x_0`` (Salimans & Ho 2022) -- the tail forms that target, ``y_0_pred = (sqrt(ab) * y_t -
+sqrt(1 - ab) * v) / y0_divisor`` and its chain into the output in the same kernel pair -- and ``loss_weighting="min_snr"`` weights the
+squared error by ``schedules.min_snr_weights`` (Hang et al. 2023).  The sampler takes the same ``prediction="v"``: one
+``hdiff_v_to_eps`` launch behind the UNet turns the output into the noise estimate every update kernel takes, so all loops and
+solvers serve both kinds of checkpoint.  Without those arguments nothing changes.
 """
 from __future__ import annotations
 
@@ -46,11 +53,11 @@ import torch.nn.functional as F
 from .. import _capi
 from .. import engine as E
 from ..engine import gpu_input as _gpu_input, index_vector as _timesteps
-from ..schedules import (Y_T_OFFSET, _checked_timesteps, check_solver_spacing, dpmpp_table, logsnr_timesteps, posterior_seed,
-                         spacing_of)
+from ..schedules import (Y_T_OFFSET, _checked_timesteps, check_loss_weighting, check_prediction, check_snr_gamma, check_solver_spacing,
+                         dpmpp_table, logsnr_timesteps, min_snr_weights, posterior_seed, spacing_of)
 
 __all__ = ["extract", "GaussianDiffusionTrainer", "GaussianDiffusionSampler", "tile_origins", "tile_weights", "logsnr_timesteps",
-           "dpmpp_table", "posterior_seed", "PosteriorSamples"]
+           "dpmpp_table", "posterior_seed", "PosteriorSamples", "min_snr_weights"]
 
 
 def extract(v, t, x_shape):
@@ -100,7 +107,18 @@ class GaussianDiffusionTrainer(nn.Module):
     ``Loss.loss.PerceptualLoss_dino(perceptual_dino, weights=dino_weights)``, the package's own DINOv2 term (``dino_weights``: the hub
     checkpoint's state dict or its path; without it the trunk is random and warns; ``dino_dense="tokens"`` runs its dense layers on
     ``csrc/dense_tokens.hip``, default ``"conv"``).  The trunk is frozen and belongs to the trainer,
-    not to ``model``: it is in no checkpoint, no EMA and no optimizer."""
+    not to ``model``: it is in no checkpoint, no EMA and no optimizer.
+
+    Further keywords (not in the reference; each at its default runs what ran before, bit for bit):
+      * ``prediction``: "eps" (the model's output is the noise) or "v" (it is ``a * noise - s * x_0`` with ``a = sqrt_alphas_bar[t]``,
+        ``s = sqrt_one_minus_alphas_bar[t]``).  With "v" the squared error is taken against that target, ``y_0_pred = (a * y_t - s *
+        out) / y0_divisor`` and its chain into the output is ``-s / y0_divisor``: bounded by 1 at every t, where the eps form's
+        ``s / a`` reaches 157 at t = 999.  A checkpoint trained with "v" must be sampled with ``GaussianDiffusionSampler(...,
+        prediction="v")``.
+      * ``loss_weighting``: None, or "min_snr": ``mse_loss`` (the returned map and its share of ``loss``) is multiplied per sample by
+        ``min_snr_weights(betas, snr_gamma, prediction)[t]``; the terms taken on ``y_0_pred`` are not weighted.  ``snr_gamma``
+        (default 5.0): a finite number > 0.
+      * ``y0_divisor`` (default 255.0, the reference's trailing ``/ 255.0``, :106-107): a finite number other than 0."""
 
     DINO_WEIGHT, MSSSIM_WEIGHT, COL_WEIGHT = 0.5, 0.0045, 1.0          # reference :165
 
@@ -112,8 +130,15 @@ class GaussianDiffusionTrainer(nn.Module):
         extra_losses = more.pop("extra_losses", None)
         dino_weights = more.pop("dino_weights", None)
         dino_dense = more.pop("dino_dense", None)
+        self.prediction = check_prediction(more.pop("prediction", "eps"))
+        self.loss_weighting = check_loss_weighting(more.pop("loss_weighting", None))
+        self.snr_gamma = check_snr_gamma(more.pop("snr_gamma", 5.0))
+        self.y0_divisor = more.pop("y0_divisor", 255.0)
         if more:
             raise TypeError(f"GaussianDiffusionTrainer.__init__() got an unexpected keyword argument '{next(iter(more))}'")
+        if isinstance(self.y0_divisor, bool) or not isinstance(self.y0_divisor, (int, float)) or self.y0_divisor != self.y0_divisor \
+                or self.y0_divisor in (0, float("inf"), -float("inf")):
+            raise ValueError(f"GaussianDiffusionTrainer: y0_divisor must be a finite number other than 0, got {self.y0_divisor!r}")
         self.extra_losses = _checked_extra_losses(extra_losses)
         self.extra_terms = {}
         held = [fn for _, _, fn in self.extra_losses if isinstance(fn, nn.Module)]
@@ -125,6 +150,10 @@ class GaussianDiffusionTrainer(nn.Module):
         alphas_bar = torch.cumprod(1. - self.betas, dim=0)
         self.register_buffer('sqrt_alphas_bar', torch.sqrt(alphas_bar))
         self.register_buffer('sqrt_one_minus_alphas_bar', torch.sqrt(1. - alphas_bar))
+        # min-SNR-gamma weights of the squared error: float64 -> fp32 once, here; travels with .to(device) but is in no state_dict (the
+        # reference's trainer has no such buffer).  None: the tail multiplies by nothing
+        self.register_buffer('mse_weights', None if self.loss_weighting is None else
+                             min_snr_weights(self.betas, self.snr_gamma, self.prediction).float(), persistent=False)
         self.num = 0
         self.stage = 0
         self.perceptual_vgg, self.perceptual_dino = perceptual_vgg, perceptual_dino
@@ -198,7 +227,11 @@ class GaussianDiffusionTrainer(nn.Module):
                 noise_pred = self.model(x6, t, gt_images, context_zero=bool(context_zero))
             from ..autograd import train_b_loss_tail
             # mse_loss (:102), y_0_pred with the reference's trailing / 255.0 (sic, :106-107: kept), colour term (:172)
-            mse_loss, y_0_pred, col = train_b_loss_tail(noise_pred, noise, y_t, gt_images, t, sa, s1m)
+            # (with prediction="v" `noise_pred` is the network's v: the tail forms its target and y_0_pred accordingly; with the three
+            # arguments at their defaults it launches what it launched before they existed)
+            w = None if self.mse_weights is None else self.mse_weights.to(dev)
+            mse_loss, y_0_pred, col = train_b_loss_tail(noise_pred, noise, y_t, gt_images, t, sa, s1m, prediction=self.prediction,
+                                                        weight_tab=w, y0_div=float(self.y0_divisor))
         zero = torch.zeros((), device=dev)
         loss = mse_loss
         perceptual_dino, msssim = zero, zero
@@ -361,8 +394,24 @@ class PosteriorSamples:
         self.mean, self.std, self.samples = mean, std, samples
 
 
+def _emit_v_to_eps(holder, p, sampler: "GaussianDiffusionSampler", up, rows: int, n_per: int, device) -> None:
+    """With ``sampler.prediction == "v"``: one ``hdiff_v_to_eps`` on the UNet plan's output, reading the state the model saw
+    (``up.y``) and the time vector it was called with (``up.t``), so that whatever follows takes a noise estimate.  The tables are
+    the TRAINER's -- ``sqrt(alphas_bar)[t]`` and ``sqrt(1 - alphas_bar)[t]``, float64 -> fp32 once -- not the DDIM loop's
+    ``alphas_bar[t + 1]``: the model was trained against the former.  ``holder`` (the step plan) keeps them alive.  With "eps"
+    nothing is emitted."""
+    if sampler.prediction != "v":
+        return
+    if not hasattr(holder, "v_sa"):
+        holder.v_sa = torch.sqrt(sampler.alphas_bar).float().to(device).contiguous()
+        holder.v_s1m = torch.sqrt(1. - sampler.alphas_bar).float().to(device).contiguous()
+    p.call("hdiff_v_to_eps", up.out.data_ptr(), up.y.data_ptr(), up.t.data_ptr(), holder.v_sa.data_ptr(), holder.v_s1m.data_ptr(),
+           int(sampler.T), rows, n_per)
+
+
 class _StepPlan:
-    """One captured sampling step for a fixed (B, H, W) and mode: fill t -> DynamicUNet -> update -> advance the counter."""
+    """One captured sampling step for a fixed (B, H, W) and mode: fill t -> DynamicUNet [-> v to eps] -> update -> advance the
+    counter."""
 
     def __init__(self, sampler: "GaussianDiffusionSampler", B: int, H: int, W: int, device, ddim_step: Optional[int],
                  inject_noise: bool = False, seed: int = 0, solver: str = "ddim", seq: Optional[List[int]] = None,
@@ -391,6 +440,7 @@ class _StepPlan:
             self.n_steps = sampler.T
             p.call("hdiff_fill_t", up.t.data_ptr(), self.step.data_ptr(), B)
             p.ops.extend(up.plan.ops)
+            _emit_v_to_eps(self, p, sampler, up, B, 3 * H * W, device)
             # noise: injected buffer (parity runs) or drawn in-kernel (Philox, counter = (seed, step, element))
             p.call("hdiff_ddpm_step", up.y.data_ptr(), up.out.data_ptr(), up.out.data_ptr(),
                    self.noise.data_ptr() if inject_noise else None, up.y.data_ptr(), self.c1.data_ptr(), self.c2.data_ptr(),
@@ -401,6 +451,7 @@ class _StepPlan:
             self.n_steps = int(self.t_tab.numel())
             p.call("hdiff_fill_from_table", up.t.data_ptr(), self.t_tab.data_ptr(), self.step.data_ptr(), self.n_steps, B)
             p.ops.extend(up.plan.ops)
+            _emit_v_to_eps(self, p, sampler, up, B, 3 * H * W, device)
             if solver == "dpmpp2m":         # the same step with the second-order update; the plan owns the x0 history
                 p.call("hdiff_dpmpp_step", up.y.data_ptr(), up.out.data_ptr(), up.y.data_ptr(), self.x0_prev.data_ptr(),
                        self.tab.data_ptr(), self.step.data_ptr(), self.n_steps, 0, self.nan_flag.data_ptr(), n)
@@ -458,6 +509,7 @@ class _TiledStepPlan:
                 p.call("hdiff_tile_gather", src.data_ptr(), dst.data_ptr(), self.oy.data_ptr(), self.ox.data_ptr(), B, 3, H, W,
                        ny, nx, th, tw, w0, n_slots)
             p.ops.extend(up.plan.ops)
+            _emit_v_to_eps(self, p, sampler, up, n_slots, 3 * th * tw, device)       # per chunk, on the gathered windows of y
             if self.eps is not up.out:
                 # the plan's output is reused by the next chunk: keep this chunk's estimates (a gather whose windows are whole
                 # samples is a copy; the padding slots are left behind)
@@ -480,14 +532,20 @@ class _TiledStepPlan:
 class GaussianDiffusionSampler(nn.Module):
     """forward(input_image, ddim=False, unconditional_guidance_scale=1, ddim_step=None) -> enhanced image clipped to [-1, 1]
     (reference diffusion/Diffusion.py:182-269).  ``input_image`` is in [0, 255] (divided by 255 here, as there).
-    ``tile=`` (not in the reference) samples an image of any size through overlapping model-sized windows: see ``forward``."""
+    ``tile=`` (not in the reference) samples an image of any size through overlapping model-sized windows: see ``forward``.
+    ``prediction`` (not in the reference): "eps", or "v" for a model trained with ``GaussianDiffusionTrainer(..., prediction="v")`` --
+    every step then runs one ``hdiff_v_to_eps`` behind the model (per chunk of windows with ``tile``), in front of whichever update the
+    call asks for: the ancestral loop, DDIM, ``solver="dpmpp2m"``, ``eta`` / ``posterior`` and ``tile`` all take it.  Sampling a v
+    checkpoint as "eps" (or the reverse) raises nothing and returns noise: ``Evaluate`` reads the ``prediction.json`` the training
+    driver writes for that reason."""
 
     GRAPH_MIN_STEPS = 4
 
-    def __init__(self, model, beta_1, beta_T, T):
+    def __init__(self, model, beta_1, beta_T, T, *, prediction: str = "eps"):
         super().__init__()
         self.model = model
         self.T = T
+        self.prediction = check_prediction(prediction)
         self.register_buffer('betas', torch.linspace(beta_1, beta_T, T).double())
         alphas = 1. - self.betas
         alphas_bar = torch.cumprod(alphas, dim=0)
@@ -519,6 +577,12 @@ class GaussianDiffusionSampler(nn.Module):
         var = torch.cat([self.posterior_var[1:2], self.betas[1:]])
         var = extract(var, t, input.shape)
         eps = self.model(input, t)
+        if self.prediction == "v":
+            eps, y, tt, dev = eps.contiguous(), y_t.contiguous(), t.to(torch.int64).contiguous(), y_t.device
+            sa, s1m = torch.sqrt(self.alphas_bar).float().to(dev), torch.sqrt(1. - self.alphas_bar).float().to(dev)
+            _capi.check(_capi.lib().hdiff_v_to_eps(eps.data_ptr(), y.data_ptr(), tt.data_ptr(), sa.data_ptr(), s1m.data_ptr(),
+                                                   int(self.T), int(y.shape[0]), y.numel() // int(y.shape[0]),
+                                                   torch.cuda.current_stream(dev).cuda_stream), "v_to_eps")
         return self.predict_xt_prev_mean_from_eps(t, eps, y_t), var
 
     def forward(self, input_image, ddim=False, unconditional_guidance_scale=1, ddim_step=None, *, y_T=None,
@@ -628,7 +692,10 @@ class GaussianDiffusionSampler(nn.Module):
         return img, (int(ddim_step) if ddim and seq is None else None)
 
     def _plan(self, key, device, make):
-        """The one live step plan: a graph bakes its seed and contraction mode, and a rebuilt UNet plan retires it."""
+        """The one live step plan: a graph bakes its seed and contraction mode, and a rebuilt UNet plan retires it.  What the model
+        predicts decides the launch list, so it is part of the key (for "eps" the key is the one it was)."""
+        if self.prediction != "eps":
+            key = key + (("prediction", self.prediction),)
         sp = self._plans.get(key)
         if sp is None or sp.unet is not self.model.plan_for(sp.n_slots, sp.th, sp.tw, device, True):
             sp = make()

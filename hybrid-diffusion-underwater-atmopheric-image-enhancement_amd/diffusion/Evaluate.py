@@ -47,7 +47,7 @@ import torch
 from .. import quality
 
 __all__ = ["evaluate", "test", "inference", "fit_niqe", "RES_KEYS", "RES_KEYS_UCIQE", "RES_KEY_LPIPS", "RES_KEYS_DISTRIBUTION",
-           "RES_KEY_NIQE", "RES_KEY_NIQE_FULL", "RES_KEYS_COLOR"]
+           "RES_KEY_NIQE", "RES_KEY_NIQE_FULL", "RES_KEYS_COLOR", "PREDICTION_FILE", "read_prediction", "resolve_prediction"]
 
 # res.txt: the reference's key for each measured score, in the reference's order (rotinas.py:967-982)
 RES_KEYS = (("psnr_orgin_avg:", "psnr"), ("ssim_orgin_avg:", "ssim"), ("uiqm_orgin_avg:", "uiqm"), ("uism_orgin_avg:", "uism"),
@@ -340,6 +340,33 @@ def _cfg(config, key: str, *default):
     raise KeyError(f"the configuration has no '{key}'")
 
 
+PREDICTION_FILE = "prediction.json"      # what Train.train leaves beside the checkpoints of a run whose prediction is not "eps"
+
+
+def read_prediction(path: str) -> Dict[str, object]:
+    """The four values of a ``prediction.json``: ``prediction``, ``loss_weighting``, ``snr_gamma``, ``y0_divisor``."""
+    import json
+    with open(path) as f:
+        held = json.load(f)
+    if not isinstance(held, dict) or "prediction" not in held:
+        raise ValueError(f"{path} holds no 'prediction'")
+    return held
+
+
+def resolve_prediction(config, pretrained_path: str) -> str:
+    """What the checkpoint at ``pretrained_path`` predicts: the configuration's ``prediction`` key, else the ``prediction.json`` lying
+    beside the checkpoint, else "eps".  When both are present and disagree this raises: a v checkpoint sampled as eps (or the reverse)
+    fails nowhere and returns noise."""
+    from ..schedules import check_prediction
+    given = _cfg(config, "prediction", None)
+    beside = os.path.join(os.path.dirname(os.path.abspath(pretrained_path)), PREDICTION_FILE)
+    recorded = read_prediction(beside)["prediction"] if os.path.isfile(beside) else None
+    if given is not None and recorded is not None and given != recorded:
+        raise ValueError(f"the configuration says prediction = {given!r}, but {beside} records that the checkpoints of that run were "
+                         f"trained with prediction = {recorded!r}")
+    return check_prediction(given if given is not None else (recorded if recorded is not None else "eps"))
+
+
 def _batched(dataset, batch_size: int, full: bool = False) -> Iterator:
     """(input [B,3,H,W], target [B,3,H,W], file names of the degraded images) in order, the last batch as short as it comes.  ``full``
     adds a fourth element: the degraded files at their own size, uint8 [H_i, W_i, 3] host tensors (``datasets.load_image``)."""
@@ -377,10 +404,12 @@ def _run_sets(config, task: str) -> Dict[str, Dict[str, object]]:
     model = DynamicUNet(T=_cfg(config, "T"), ch=_cfg(config, "channel"), ch_mult=_cfg(config, "channel_mult"),
                         num_res_blocks=_cfg(config, "num_res_blocks"), dropout=0.)
     path = _cfg(config, "pretrained_path")
+    prediction = resolve_prediction(config, path)
     ckpt = torch.load(path, map_location="cpu")
     model.load_state_dict({k.replace("module.", ""): v for k, v in ckpt.items()})
     model.eval()
-    sampler = GaussianDiffusionSampler(model, _cfg(config, "beta_1"), _cfg(config, "beta_T"), _cfg(config, "T")).to(device)
+    sampler = GaussianDiffusionSampler(model, _cfg(config, "beta_1"), _cfg(config, "beta_T"), _cfg(config, "T"),
+                                       **({} if prediction == "eps" else {"prediction": prediction})).to(device)
 
     base = os.path.join(_cfg(config, "result_root", os.path.join("output", "result")), os.path.basename(path))
     extra = {}
@@ -449,7 +478,10 @@ def test(config, epoch=None) -> Dict[str, Dict[str, object]]:
     ``samples`` (K >= 1: ``evaluate``'s ``samples=``, the mean of K posterior samples per image is scored and saved, the per-pixel spread
     goes to ``<set>/std/<name>`` and ``res.txt`` gains the draw-to-draw spread of every score) with ``ddim_eta`` (default 0),
     ``sample_seed`` (default 0) and ``sample_batch`` (the most samples per model evaluation; absent: one draw from torch's generator
-    per image, ``res.txt`` as before).
+    per image, ``res.txt`` as before),
+    ``prediction`` ("eps" or "v": what the checkpoint's network predicts, the sampler's ``prediction=``; absent: read from the
+    ``prediction.json`` beside ``pretrained_path`` if ``Train.train`` left one, else "eps"; present and different from that file:
+    ``ValueError``, see ``resolve_prediction``).
     ``epoch`` is accepted and unused, as in the reference.  Returns ``{set name: evaluate()'s dict}``."""
     return _run_sets(config, "test")
 

@@ -55,6 +55,12 @@ dicts, stage index, epoch within the stage, step counter, the torch CPU and devi
 restores all of it and continues at the next epoch; across a stage boundary it begins stage 1 with a fresh optimizer, as the
 uninterrupted run does.
 
+``prediction`` ("eps", the default, or "v"), ``loss_weighting`` (None or "min_snr"), ``snr_gamma`` (5.0) and ``y0_divisor`` (255.0) are
+the trainer's keywords of those names (``prediction_settings``).  The state file records the four values and ``resume`` under other
+values raises.  When ``prediction`` is not "eps" the driver also writes ``<output_path>/ckpt/prediction.json`` with them -- the
+checkpoints stay plain state dicts, and ``Evaluate.test`` reads that file so that such a checkpoint is not sampled as eps.  A run
+without the keys writes the files it wrote before.
+
 Returns ``{"losses": {term: [mean per epoch]}, "lr": [per epoch], "validation": [records], "files": [paths written], "steps": n,
 "epochs": global epochs done, "finished": bool}``.
 """
@@ -66,10 +72,10 @@ from typing import Dict, List, Optional, Tuple
 
 import torch
 
-from .Evaluate import _cfg
+from .Evaluate import PREDICTION_FILE, _cfg
 
 __all__ = ["train", "data_plan", "stage_plan", "checkpoint_epochs", "checkpoint_name", "final_name", "expected_files", "lr_sequence",
-           "TERMS", "STATE_FILE"]
+           "TERMS", "STATE_FILE", "PREDICTION_FILE", "prediction_settings", "write_prediction_file"]
 
 TERMS = ("loss", "mse_loss", "perceptual_dino", "msssim", "col_loss")       # the trainer's return order (rotinas.py:439)
 WEIGHT_DECAY = 1e-4                                                          # rotinas.py:660
@@ -114,7 +120,33 @@ def expected_files(config) -> List[str]:
     names = [checkpoint_name(g, plan[si]["name"], u, a, k)
              for g, si, _ in checkpoint_epochs(plan[0]["epochs"], plan[1]["epochs"], _cfg(config, "save_checkpoint")) for k in kinds]
     names += [final_name(plan[0]["epochs"] + plan[1]["epochs"], u, a, k) for k in kinds]
+    if prediction_settings(config)["prediction"] != "eps":
+        names.append(PREDICTION_FILE)
     return sorted(names + [STATE_FILE])
+
+
+def prediction_settings(config) -> Dict[str, object]:
+    """What the network is asked to predict and how the squared error is weighted, validated on the host: ``{"prediction",
+    "loss_weighting", "snr_gamma", "y0_divisor"}`` -- the trainer's keywords of those names, the state file's record of them and the
+    content of ``prediction.json``.  With none of the keys set: the reference's eps-prediction, unweighted, ``/ 255``."""
+    from ..schedules import check_loss_weighting, check_prediction, check_snr_gamma
+    y0_divisor = _cfg(config, "y0_divisor", 255.0)
+    if isinstance(y0_divisor, bool) or not isinstance(y0_divisor, (int, float)) or y0_divisor != y0_divisor \
+            or y0_divisor in (0, float("inf"), -float("inf")):
+        raise ValueError(f"hdiff_amd.diffusion.Train: y0_divisor = {y0_divisor!r}; a finite number other than 0")
+    return {"prediction": check_prediction(_cfg(config, "prediction", "eps")),
+            "loss_weighting": check_loss_weighting(_cfg(config, "loss_weighting", None)),
+            "snr_gamma": check_snr_gamma(_cfg(config, "snr_gamma", 5.0)), "y0_divisor": float(y0_divisor)}
+
+
+def write_prediction_file(ckpt_dir: str, settings: Dict[str, object]) -> str:
+    """``<ckpt_dir>/prediction.json`` with the four values; ``Evaluate.resolve_prediction`` reads it.  -> its path."""
+    import json
+    path = os.path.join(ckpt_dir, PREDICTION_FILE)
+    with open(path, "w") as f:
+        json.dump(settings, f, indent=1, sort_keys=True)
+        f.write("\n")
+    return path
 
 
 def data_plan(config) -> Dict[str, object]:
@@ -220,6 +252,8 @@ def train(config) -> Dict[str, object]:
 
     _refuse_data_parallel(config)
     plan = data_plan(config)
+    predict = prediction_settings(config)
+    default_predict = predict == prediction_settings({})
     device = _device(config)
     if _cfg(config, "wandb", False):
         warnings.warn("hdiff_amd.diffusion.Train.train: wandb is not wired; nothing is logged there", RuntimeWarning, stacklevel=2)
@@ -264,7 +298,8 @@ def train(config) -> Dict[str, object]:
                                        dino_loss=_cfg(config, "dino_loss", None), msssim_loss=msssim_loss,
                                        extra_losses=_cfg(config, "extra_losses", None),
                                        dino_weights=_cfg(config, "dino_weights", None),
-                                       dino_dense=_cfg(config, "dino_dense", None)).to(device)                  # :629
+                                       dino_dense=_cfg(config, "dino_dense", None),
+                                       **({} if default_predict else predict)).to(device)                       # :629
     ema_decay = _cfg(config, "ema_decay", None)
     ema = hdiff_optim.EMA(model.parameters(), decay=ema_decay) if ema_decay is not None else None
 
@@ -285,6 +320,10 @@ def train(config) -> Dict[str, object]:
     resume = _cfg(config, "resume", None)
     if resume is not None:
         resumed = torch.load(resume, map_location="cpu", weights_only=False)
+        was = resumed.get("prediction", prediction_settings({}))       # a state file from before the keys existed: their defaults
+        if was != predict:
+            raise RuntimeError(f"hdiff_amd.diffusion.Train.train: the state file was written with {was} and the configuration asks for "
+                               f"{predict}: a network goes on being trained for what it was trained for")
         model.load_state_dict(resumed["model"])
         if (ema is None) != (resumed["ema"] is None):
             raise RuntimeError("hdiff_amd.diffusion.Train.train: the state file and the configuration disagree about ema_decay")
@@ -313,9 +352,13 @@ def train(config) -> Dict[str, object]:
         torch.save({"model": model.state_dict(), "ema": None if ema is None else ema.state_dict(),
                     "optimizer": None if opt is None else opt.state_dict(),
                     "schedulers": None if opt is None else _sched_state(warm, cosine),
-                    "stage": si, "epoch": e, "num": num, "record": record,
+                    "stage": si, "epoch": e, "num": num, "record": record, "prediction": predict,
                     "rng_cpu": torch.get_rng_state(), "rng_device": torch.cuda.get_rng_state(device)}, state_path)
 
+    if predict["prediction"] != "eps":          # beside the checkpoints, which stay plain state dicts: Evaluate reads it
+        path = write_prediction_file(ckpt_dir, predict)
+        if path not in record["files"]:
+            record["files"].append(path)
     done_epochs = sum(s["epochs"] for s in stages[:first_stage]) + first_epoch
     stopped, opt, warm, cosine = False, None, None, None
     for si in range(first_stage, len(stages)):

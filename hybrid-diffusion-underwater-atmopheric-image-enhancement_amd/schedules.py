@@ -2,7 +2,8 @@
 (``DiffusionFreeGuidence.DiffusionCondition``) and the image-conditioned one (``diffusion.Diffusion``, which reads
 ``alphas_bar[t + 1]``: ``shift=1``): ``ddim_timesteps`` / ``ddim_table`` of the strided DDIM update (Song et al. 2021),
 ``logsnr_timesteps`` / ``dpmpp_table`` of DPM-Solver++(2M) (Lu et al. 2022), the validation of ``solver`` / ``spacing`` /
-``timesteps`` both ``forward`` signatures share, and ``posterior_seed``, the seed of one sample of a multi-sample run.  Everything here runs on the CPU in float64 and loads no native library; both
+``timesteps`` both ``forward`` signatures share, ``posterior_seed``, the seed of one sample of a multi-sample run, and what the
+image-conditioned tree's ``prediction`` / ``loss_weighting`` arguments may be, with ``min_snr_weights``.  Everything here runs on the CPU in float64 and loads no native library; both
 sampler modules re-export the public names."""
 from __future__ import annotations
 
@@ -10,7 +11,8 @@ from typing import List, Optional, Sequence, Tuple
 
 import torch
 
-__all__ = ["SOLVERS", "SPACINGS", "ddim_timesteps", "ddim_table", "logsnr_timesteps", "dpmpp_table", "posterior_seed"]
+__all__ = ["SOLVERS", "SPACINGS", "PREDICTIONS", "LOSS_WEIGHTINGS", "ddim_timesteps", "ddim_table", "logsnr_timesteps", "dpmpp_table",
+           "posterior_seed", "min_snr_weights"]
 
 SOLVERS = ("ddim", "dpmpp2m")
 SPACINGS = ("uniform", "logsnr")
@@ -160,6 +162,44 @@ def dpmpp_table(betas, timesteps: Sequence[int], shift: int = 0, final_alpha_bar
         rows[k] = torch.stack([torch.sqrt(1.0 - a), torch.sqrt(a), A, B, Cc])
         h_prev = h
     return torch.stack(rows)
+
+
+PREDICTIONS = ("eps", "v")
+LOSS_WEIGHTINGS = (None, "min_snr")
+
+
+def check_prediction(prediction) -> str:
+    """``ValueError`` for a ``prediction`` that names none of ``PREDICTIONS``: what the network's output stands for, the noise
+    ("eps") or ``v = sqrt(ab) * noise - sqrt(1 - ab) * x_0`` (Salimans & Ho 2022)."""
+    if not isinstance(prediction, str) or prediction not in PREDICTIONS:
+        raise ValueError(f"prediction must be one of {PREDICTIONS}, got {prediction!r}")
+    return prediction
+
+
+def check_loss_weighting(loss_weighting):
+    if loss_weighting is not None and (not isinstance(loss_weighting, str) or loss_weighting not in LOSS_WEIGHTINGS):
+        raise ValueError(f"loss_weighting must be one of {LOSS_WEIGHTINGS}, got {loss_weighting!r}")
+    return loss_weighting
+
+
+def check_snr_gamma(gamma) -> float:
+    if isinstance(gamma, bool) or not isinstance(gamma, (int, float)) or gamma != gamma or gamma in (float("inf"), -float("inf")) \
+            or gamma <= 0:
+        raise ValueError(f"snr_gamma must be a finite number > 0, got {gamma!r}")
+    return float(gamma)
+
+
+def min_snr_weights(betas, gamma: float = 5.0, prediction: str = "eps") -> torch.Tensor:
+    """Min-SNR-gamma weights of the squared-error term (Hang et al. 2023), float64 ``[T]``: with ``ab = cumprod(1 - betas)`` and
+    ``snr = ab / (1 - ab)``, ``w = min(snr, gamma) / snr`` for ``prediction="eps"`` and ``min(snr, gamma) / (snr + 1)`` for ``"v"``
+    (the v target's own scale is ``snr + 1`` times the noise's).  ``ValueError`` for a ``gamma`` that is not a finite number > 0 or an
+    unknown ``prediction``.  Computed on the CPU; the trainer casts each entry to fp32 once."""
+    check_prediction(prediction)
+    gamma = check_snr_gamma(gamma)
+    ab = _alphas_bar(betas)
+    snr = ab / (1.0 - ab)
+    capped = torch.clamp(snr, max=float(gamma))
+    return capped / snr if prediction == "eps" else capped / (snr + 1.0)
 
 
 _M64 = (1 << 64) - 1

@@ -575,6 +575,18 @@ int hdiff_ddim_eta_step(const float* y, const float* eps, const float* noise /* 
                         int64_t n_per, const int32_t* step_ptr, int nsteps, int32_t* nan_flag, int rows, hdiff_stream_t stream);
 int hdiff_sample_stats(const float* samples, int B, int K, int64_t n, float* mean, float* std, hdiff_stream_t stream);
 /* ------------------------------------------------------------------------------------------------------------------
+ * A v-prediction network (v = sqrt(ab) * noise - sqrt(1 - ab) * x_0, Salimans & Ho 2022) in front of the same sampler's updates (the
+ * sampler's `prediction="v"`; an addition to the reference and to ABI 6).
+ *   hdiff_v_to_eps   row b of out [B][n_per], in place:  out = sqrt_ab[t[b]] * out + sqrt_1mab[t[b]] * y  -- the noise estimate that
+ *                    every update above takes, two products and one sum, one fp32 rounding each.  sqrt_ab / sqrt_1mab: fp32 tables
+ *                    of length T at the index the model was CALLED with (the trainer's alphas_bar[t], not the DDIM loop's
+ *                    alphas_bar[t + 1]); t[b] is clamped into [0, T).  y [B][n_per] is the state the model saw.  Any 4-byte aligned
+ *                    pointers and any n_per; an element's result depends on its own two inputs alone
+ * One launch; no allocation, no synchronisation, no atomics: legal under stream capture, bitwise repeatable.
+ * ------------------------------------------------------------------------------------------------------------------ */
+int hdiff_v_to_eps(float* out, const float* y, const int64_t* t, const float* sqrt_ab, const float* sqrt_1mab, int T, int B,
+                   int64_t n_per, hdiff_stream_t stream);
+/* ------------------------------------------------------------------------------------------------------------------
  * Overlapping-window DDIM sampling of the second tree's sampler (the `tile=` argument; an addition to the reference).
  * Layout: per axis a table of window origins (origin_y[ny], origin_x[nx]); window (b, iy, ix) has index (b*ny + iy)*nx + ix
  * and covers rows origin_y[iy] .. + th - 1 and columns origin_x[ix] .. + tw - 1 of a [B][C][H][W] tensor (th <= H, tw <= W).
@@ -616,6 +628,16 @@ int hdiff_tile_dpmpp_step(float* y, const float* eps_w, float* x0_prev, const in
  *                            partial sums, reduced in a fixed order: bitwise reproducible)
  *   hdiff_train_b_loss_bwd   d_noise_pred from d_mse [B][3][HW], d_y0 (an external dL/dy0_pred) and d_col (device scalar),
  *                            each of which may be NULL, in one pass
+ *   hdiff_train_b_tail_fwd / _bwd   the same pair (the same kernels) with what the network's output `out` stands for, an optional
+ *                            weight of the squared error and the y0 divisor as arguments (additions to the reference and to ABI 6).
+ *                            With a = sqrt_ab[t], s = sqrt_1mab[t], one fp32 rounding per written operation:
+ *                              HDIFF_PREDICT_EPS  target = noise               y0_pred = ((1 / a) * (y_t - s * out)) / y0_div
+ *                                                 dy0/dout = -(1 / a) * s / y0_div
+ *                              HDIFF_PREDICT_V    target = a * noise - s * gt  y0_pred = (a * y_t - s * out) / y0_div
+ *                                                 dy0/dout = -s / y0_div                            (Salimans & Ho 2022)
+ *                            mse = weight_tab[t] * (out - target)^2 with a table of length T, (out - target)^2 with NULL (no multiply
+ *                            is executed); the weight reaches the mse term alone, forward and backward.  y0_div: any number but
+ *                            0.  (HDIFF_PREDICT_EPS, NULL, 255.0f) is hdiff_train_b_loss_fwd / _bwd, which forward here
  *   hdiff_avgpool_global_bwd dx[bc][i] = dy[bc] / HW (AdaptiveAvgPool2d((1,1)), Model.py:150)
  *   hdiff_resize_nearest_bwd the backward of hdiff_resize_nearest ([BC][H][W] -> [BC][OH][OW]) in gather form: dx[bc][iy][ix] =
  *                            the sum, in increasing output order, of the dy elements that read it (no atomics)
@@ -627,6 +649,15 @@ int hdiff_train_b_loss_fwd(const float* noise_pred, const float* noise, const fl
 int hdiff_train_b_loss_bwd(const float* noise_pred, const float* noise, const float* y0_pred, const float* gt, const int64_t* t,
                            const float* sqrt_ab, const float* sqrt_1mab, int T, int B, int HW, const float* d_mse,
                            const float* d_y0, const float* d_col, float* d_noise_pred, hdiff_stream_t stream);
+enum { HDIFF_PREDICT_EPS = 0, HDIFF_PREDICT_V = 1 };
+int hdiff_train_b_tail_fwd(const float* out, const float* noise, const float* y_t, const float* gt, const int64_t* t,
+                           const float* sqrt_ab, const float* sqrt_1mab, int T, int B, int HW, float* mse, float* y0_pred,
+                           float* col, void* workspace, int prediction, const float* weight_tab /* [T] or NULL */, float y0_div,
+                           hdiff_stream_t stream);
+int hdiff_train_b_tail_bwd(const float* out, const float* noise, const float* y0_pred, const float* gt, const int64_t* t,
+                           const float* sqrt_ab, const float* sqrt_1mab, int T, int B, int HW, const float* d_mse,
+                           const float* d_y0, const float* d_col, float* d_out, int prediction,
+                           const float* weight_tab /* [T] or NULL */, float y0_div, hdiff_stream_t stream);
 int hdiff_avgpool_global_bwd(const float* dy, float* dx, int BC, int HW, hdiff_stream_t stream);
 int hdiff_resize_nearest_bwd(const float* dy, float* dx, int BC, int H, int W, int OH, int OW, hdiff_stream_t stream);
 /* ------------------------------------------------------------------------------------------------------------------

@@ -27,7 +27,12 @@ No 8-GPU run has been made from the build box (one GPU); the driver can run this
                                                                              process (--alternate) with engine clock and board
                                                                              power, then the EMA launch and the AdamW launches
                                                                              alone by device events, with the parameter count and
-                                                                             the bytes each streams (12 and 32 per parameter)."""
+                                                                             the bytes each streams (12 and 32 per parameter).
+  python tools/bench_train.py --tree b --size 256 --batch 2 --steps 10 --prediction v [--loss-weighting min_snr]
+                                                                             the same step with the eps trainer and with a
+                                                                             prediction="v" trainer on the same model, the two
+                                                                             arms alternating in one process (--alternate) with
+                                                                             engine clock and board power."""
 import argparse, json, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__))); sys.path.insert(0, ROOT)
 import torch
@@ -42,7 +47,10 @@ ap.add_argument("--msssim", choices=("none", "native"), default="none",
                 help="--tree b: none = no MS-SSIM term (default); native = the HIP MS-SSIM + L1 loss, reported beside a run without it")
 ap.add_argument("--ema", action="store_true", help="--tree b: the step with and without hdiff_amd.optim.EMA.update(), alternating")
 ap.add_argument("--ema-decay", type=float, default=0.9999)
-ap.add_argument("--alternate", type=int, default=3, help="--ema: repetitions of the pair of arms")
+ap.add_argument("--alternate", type=int, default=3, help="--ema / --prediction: repetitions of the pair of arms")
+ap.add_argument("--prediction", choices=("eps", "v"), default="eps",
+                help="--tree b: v = the step of a prediction='v' trainer beside the eps trainer's, alternating")
+ap.add_argument("--loss-weighting", choices=("min_snr",), default=None, help="--tree b: the trainer's loss_weighting of the second arm")
 ap.add_argument("--rehearse-one-gpu", action="store_true",
                 help="dev: the data-parallel code path with every rank on cuda:0 over gloo (RCCL refuses two ranks on one device)")
 a = ap.parse_args()
@@ -177,9 +185,67 @@ def tree_b_ema(size, batch, steps, warmup, dropout, decay, alternate):
     return out
 
 
+def tree_b_prediction(size, batch, steps, warmup, dropout, prediction, weighting, alternate):
+    """The step of tree_b_steps with the reference's eps trainer and with prediction= / loss_weighting=, arms alternating on ONE model
+    and optimizer (two trainers around it), engine clock and board power beside each timing."""
+    import time
+    import warnings
+    import bench
+    from hdiff_amd import optim as HO
+    from hdiff_amd.diffusion.Diffusion import GaussianDiffusionTrainer
+    from hdiff_amd.diffusion.Model import DynamicUNet
+    dev = torch.device("cuda", 0)
+    torch.manual_seed(0)
+    m = DynamicUNet(T=1000, ch=128, ch_mult=[1, 2, 2, 2], num_res_blocks=2, dropout=dropout).to(dev).train()
+    name = prediction + ("" if weighting is None else "+" + weighting)
+    trainers = {"eps": GaussianDiffusionTrainer(m, 1e-4, 0.02, 1000),
+                name: GaussianDiffusionTrainer(m, 1e-4, 0.02, 1000, prediction=prediction, loss_weighting=weighting)}
+    opt = HO.AdamW(m.parameters(), lr=1e-4, weight_decay=1e-4)
+    g = torch.Generator().manual_seed(1)
+    label = torch.randint(0, 256, (batch, 3, size, size), generator=g).to(torch.uint8).to(dev)
+    inp = (label.float() * torch.tensor([0.4, 0.9, 1.0], device=dev).view(1, 3, 1, 1)).to(torch.uint8)
+
+    def arm(tr, count):
+        times = []
+        for _ in range(count):
+            torch.cuda.synchronize(dev)
+            t0 = time.perf_counter()
+            opt.zero_grad()
+            tr(label, inp, 0)[0].mean().backward()
+            opt.step(max_grad_norm=1.0)
+            torch.cuda.synchronize(dev)
+            times.append(1e3 * (time.perf_counter() - t0))
+        return sorted(times)
+
+    out = {"tree": "b", "config": "ch=128,ch_mult=[1,2,2,2],num_res_blocks=2,dropout=%g" % dropout, "size": size, "batch": batch,
+           "steps": steps, "warmup": warmup, "gpu": torch.cuda.get_device_name(dev), "arms": []}
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore", RuntimeWarning)
+        for tr in trainers.values():
+            arm(tr, warmup)
+        for rep in range(alternate):
+            for arm_name, tr in trainers.items():
+                clock = bench.ClockSampler(0)
+                with clock:
+                    t = arm(tr, steps)
+                c = clock.summary()
+                rec = {"arm": arm_name, "rep": rep, "ms_per_step_median": round(t[len(t) // 2], 3), "ms_per_step_min": round(t[0], 3),
+                       "sclk_mhz_mean": c.get("sclk_mhz_mean"), "board_power_w_mean": c.get("board_power_w_mean")}
+                out["arms"].append(rec)
+                print(json.dumps(rec), flush=True)
+    for arm_name in trainers:
+        out[arm_name + "_ms_per_step"] = sorted(r["ms_per_step_median"] for r in out["arms"] if r["arm"] == arm_name)[alternate // 2]
+    return out
+
+
 if a.tree == "b":
     if a.gpus not in (None, 1):
         sys.exit("bench_train.py --tree b: one GPU only (no data-parallel path for the second tree)")
+    if a.prediction != "eps" or a.loss_weighting is not None:
+        res = tree_b_prediction(a.size, a.batch, a.steps, a.warmup, a.dropout, a.prediction, a.loss_weighting, a.alternate)
+        res.pop("arms")
+        print(json.dumps(res), flush=True)
+        sys.exit(0)
     if a.ema:
         res = tree_b_ema(a.size, a.batch, a.steps, a.warmup, a.dropout, a.ema_decay, a.alternate)
         res.pop("arms")
