@@ -1,7 +1,8 @@
 """Shared by tests/test_gpu_strided_geometry.py (which runs these shapes) and tests/test_wgrad_route_cpu.py (which pins their
 weight-gradient routes without a GPU): the strided / transposed / short-plane cases, each the smallest shape at which the property
 named beside it holds, and the weight-gradient descriptors their backward passes launch -- built the way autograd._run_wgrad
-builds them, with fake non-null pointers (hdiff_conv2d_wgrad_route dereferences none).
+builds them, with fake non-null pointers (hdiff_conv2d_wgrad_route dereferences none).  The "-fast" cases put fused_conv's two fast
+weight-gradient kernels (conv_wgrad3x3.hip) through the same test; tests/_wgrad_fast_cases.py probes those kernels tile by tile.
 
 Tile facts, from the two launchers (conv_wgrad.hip, conv_igemm.hip): the pixel tile is 2^t columns x 128 / 2^t rows of the
 virtual output grid (VH x VW), 2^t = VW rounded up to a power of two, 32 at most -- so VW > 16 means 4 x 32 tiles in the weight
@@ -83,6 +84,11 @@ CASES = [
     ("conv3x3-gn-3x24-short", "conv3-gn", (32, 64, 3, 24), GENERIC, "GroupNorm + Swish prologue, 3 rows"),
     ("conv1x1-2x20-short", "conv1", (64, 96, 2, 20), GENERIC, "no prologue, 32-channel chunks, 2 rows"),
     ("conv3x3-gn-dropout-3x24-short", "conv3-gn-drop", (32, 64, 3, 24), GENERIC, "the dropout instantiation, 3 rows"),
+    # fused_conv on the two fast kernels (conv_wgrad3x3.hip): dy = "edge" then holds the first column of the last 32-wide tile
+    ("conv3x3-gn-4x64-fast", "conv3-gn", (32, 128, 4, 64), FAST_3X3, "2x2 tiles of 2x32 behind GroupNorm + Swish: every tile two borders"),
+    ("conv3x3-gn-dropout-4x64-fast", "conv3-gn-drop", (32, 128, 4, 64), FAST_3X3, "the same plane in the dropout instantiation"),
+    ("conv1x1-8x16-fast", "conv1", (64, 128, 8, 16), FAST_1X1, "two 64-pixel tiles per image, 64 of the 128 staged input columns dead"),
+    ("conv3x3-6x96-fast", "conv3", (32, 128, 6, 96), FAST_3X3, "no prologue (the UpSample conv's form), 3x3 tiles: one interior"),
 ]
 CASE_IDS = [c[0] for c in CASES]
 
@@ -96,6 +102,8 @@ def case_descs(kind, shape):
         return [(d, 0) for d in phase_descs(cin, cout, B, H, W)]
     if kind == "conv1":
         return [(plain_desc(1, cin, cout, B, H, W), 0)]
+    if kind == "conv3":
+        return [(plain_desc(3, cin, cout, B, H, W), 0)]
     return [(plain_desc(3, cin, cout, B, H, W, gn=True), 1 if kind == "conv3-gn-drop" else 0)]
 
 

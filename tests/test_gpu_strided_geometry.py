@@ -1,5 +1,7 @@
-"""The stride-2 and output-parity convolutions at 32-wide tiles, and the generic weight gradient on planes shorter than its tile,
-through the autograd entry points the trainers use (A._DownFn, A._TConvFn, A._StridedConvFn, A.fused_conv).
+"""The stride-2 and output-parity convolutions at 32-wide tiles, the generic weight gradient on planes shorter than its tile, and
+fused_conv at small planes of several 32-wide tiles that take the fast weight-gradient kernels ("-fast": the 3x3 behind GroupNorm + Swish,
+with dropout and without a prologue, and the 1x1), through the autograd entry points the trainers use (A._DownFn, A._TConvFn,
+A._StridedConvFn, A.fused_conv).
 
 tests/test_gpu_backward.py runs these ops on planes whose virtual output is at most 16 wide; both launchers pick another program
 above that (tests/_strided_geometry_cases.py lists the cases and what each reaches).  Every case here
@@ -63,7 +65,7 @@ def inputs(cid):
     else:
         k = 1 if kind == "conv1" else 3
         t.update(w=rn(cout, cin, k, k) / math.sqrt(cin * k * k), b=rn(cout))
-        if kind != "conv1":
+        if kind not in ("conv1", "conv3"):
             t.update(gamma=rn(cin) * 0.5 + 1, beta=rn(cin) * 0.3)
     t["dy_randn"] = rn(*out_shape(kind, cout, H, W))
     return t
@@ -95,6 +97,8 @@ def hip_op(kind, t, seed):
         return A._StridedConvFn.apply(t["x"], t["w"], t["b"])
     if kind == "conv1":
         return A.fused_conv(t["x"], None, t["w"], t["b"], k=1)
+    if kind == "conv3":
+        return A.fused_conv(t["x"], None, t["w"], t["b"], k=3)
     if kind == "conv3-gn":
         return A.fused_conv(t["x"], None, t["w"], t["b"], t["gamma"], t["beta"], k=3)
     torch.manual_seed(seed)          # fused_conv draws the dropout seed from torch's generator
@@ -123,6 +127,8 @@ def ref_op(kind, t, mask):
         return F.conv2d(t["x"], t["w"], t["b"], stride=2, padding=1)
     if kind == "conv1":
         return F.conv2d(t["x"], t["w"], t["b"])
+    if kind == "conv3":
+        return F.conv2d(t["x"], t["w"], t["b"], padding=1)
     a = F.group_norm(t["x"], 32, t["gamma"], t["beta"], 1e-5)
     a = a * torch.sigmoid(a)
     if mask is not None:

@@ -254,6 +254,11 @@ EXPECTED = {
     "case tconv-32x32 phase (1, 1)": ROWS1,
     "case enc-3to8-64x64": ROWS2,
     "case enc-8to16-9x70": ROWS2,
+    # the "-fast" cases: the routes their shapes were chosen to take (both predicates are unchanged since that commit)
+    "case conv3x3-gn-4x64-fast": FAST_3X3,
+    "case conv3x3-gn-dropout-4x64-fast": FAST_3X3,
+    "case conv1x1-8x16-fast": FAST_1X1,
+    "case conv3x3-6x96-fast": FAST_3X3,
 }
 
 
@@ -306,7 +311,8 @@ def test_the_gpu_cases_name_their_routes():
             assert K.route_of(d, dropout) == route, cid
         seen.add(route)
         assert cid.endswith("-short") == (route == GENERIC), cid
-    assert seen == {GENERIC, ROWS1, ROWS2}
+        assert cid.endswith("-fast") == (route in (FAST_1X1, FAST_3X3)), cid
+    assert seen == {FAST_1X1, FAST_3X3, GENERIC, ROWS1, ROWS2}
 
 
 def test_the_workspace_query_follows_the_route():
