@@ -283,6 +283,9 @@ _PROTOS = {
     "hdiff_randn": (C.c_int, [C.c_void_p, C.c_int64, C.c_uint64, C.c_uint64, C.c_void_p]),
     "hdiff_batch_assemble": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_uint64, C.c_uint32,
                                        C.c_uint64, C.c_uint64, C.c_int, C.c_uint64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "hdiff_synth_params": (C.c_int, [C.c_void_p, C.c_int, C.c_uint64, C.c_uint32, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64,
+                                     C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "hdiff_synth_apply": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "hdiff_graph_begin": (C.c_int, [C.c_void_p]),
     "hdiff_graph_end": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p)]),
     "hdiff_graph_launch": (C.c_int, [C.c_void_p, C.c_void_p]),

@@ -14,7 +14,9 @@ change the mapping the model is to learn.
   * ``Augment(hflip, vflip, rot90, crop, crop_min)``: validated settings; ``thresholds(H)`` are the integers the kernel takes.
   * ``build_cache(dataset, path=None)`` -> ``PairCache`` (``a``, ``b``, ``names``, ``fingerprint``; ``.to(device)``).
   * ``epoch_indices(n, batch_size, epoch=, seed=, shuffle=, drop_last=)``: the batches of one epoch, on the host.
-  * ``DeviceLoader(cache, batch_size, shuffle=, drop_last=, augment=, seed=)``: ``len``, ``set_epoch``, iteration.
+  * ``DeviceLoader(cache, batch_size, shuffle=, drop_last=, augment=, seed=, synth=, synth_prob=, synth_epoch=)``: ``len``,
+    ``set_epoch``, iteration.  ``synth`` (``hdiff_amd/synth.py``) replaces the INPUT of a pair by a synthetic degradation of its
+    augmented target: that is not a colour augmentation of a real pair, it is how clean images alone become pairs.
 """
 from __future__ import annotations
 
@@ -234,10 +236,15 @@ class DeviceLoader:
     transforms are functions of it): a resumed run that sets the epoch it continues with draws what the uninterrupted run draws.
 
     ``__iter__`` draws one ``int64`` from torch's default CPU generator and discards it.  ``DataLoader.__iter__`` does exactly that for
-    its base seed, with any ``num_workers``; matching it is what makes a run identical bit for bit when only the loader is switched."""
+    its base seed, with any ``num_workers``; matching it is what makes a run identical bit for bit when only the loader is switched.
+
+    ``synth`` (a ``synth.Synth``): after the batch is assembled, the input of each sample selected with probability ``synth_prob`` is
+    overwritten by the degradation of its (augmented) label, two more launches per batch; the draw is a function of ``(seed, epoch,
+    sample index)`` like the transform.  ``synth_epoch`` fixes the epoch of that draw (a validation split is degraded the same way at
+    every checkpoint).  With ``synth=None`` the loader makes exactly the launches it makes without the option."""
 
     def __init__(self, cache: PairCache, batch_size: int, *, shuffle: bool = False, drop_last: bool = True,
-                 augment: Optional[Augment] = None, seed: int = 0):
+                 augment: Optional[Augment] = None, seed: int = 0, synth=None, synth_prob=1.0, synth_epoch: Optional[int] = None):
         if not cache.a.is_cuda:
             raise RuntimeError(f"hdiff: DeviceLoader needs a cache on the MI355X (cache.to(device)); this one lives on {cache.a.device} "
                                "(there is deliberately no CPU fallback)")
@@ -253,6 +260,15 @@ class DeviceLoader:
         self._settings = dict(_NO_AUGMENT, crop_lo_h=H) if augment is None else augment.thresholds(H)
         if self._settings["rot90"] and H != W:
             raise ValueError(f"DeviceLoader: rot90 needs square images, the cache holds {H} x {W}")
+        if synth is not None:
+            from .synth import Synth
+            if not isinstance(synth, Synth):
+                raise TypeError(f"DeviceLoader: synth must be a Synth or None, got {type(synth).__name__}")
+            synth.thresholds(synth_prob)                      # refuses a probability outside [0, 1]
+            if synth_epoch is not None and not 0 <= int(synth_epoch) < 2 ** 31:
+                raise ValueError(f"DeviceLoader: synth_epoch = {synth_epoch}; between 0 and 2^31 - 1")
+        self.synth, self.synth_prob = synth, synth_prob
+        self.synth_epoch = None if synth_epoch is None else int(synth_epoch)
 
     def __len__(self) -> int:
         n = len(self.cache)
@@ -277,6 +293,10 @@ class DeviceLoader:
             idx = on_device[start:start + len(batch)]
             start += len(batch)
             out_a, out_b = assemble(self.cache.a, self.cache.b, idx, seed=self.seed, epoch=epoch, **self._settings)
+            if self.synth is not None:
+                from .synth import degrade
+                degrade(out_b, idx, synth=self.synth, seed=self.seed, epoch=epoch if self.synth_epoch is None else self.synth_epoch,
+                        prob=self.synth_prob, out=out_a)
             if self.cache.names is None:
                 yield [out_a, out_b]
             else:

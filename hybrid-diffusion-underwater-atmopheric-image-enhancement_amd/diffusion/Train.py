@@ -35,7 +35,7 @@ file: a clean interruption), ``ema_decay`` (``None``: no EMA), ``resume`` (a sta
 ``(step number, model)`` run after every optimizer step, for logging), ``extra_losses`` (handed to the trainer unchanged: a sequence
 of ``(name, weight, callable)`` added to ``loss``, e.g. ``Loss.loss.PerceptualLoss_vgg`` / ``CharbonnierLoss``; ``TERMS``, the records
 and the checkpoints are the same with and without it), and the data keys ``device_cache``, ``cache_dir``, ``augment``,
-``shuffle``, ``data_seed`` (below).
+``shuffle``, ``data_seed``, ``synthetic``, ``synthetic_prob``, ``synthetic_val`` (below).
 
 With ``device_cache=True`` each of the four splits is decoded once (``device_data.build_cache``, stored under ``cache_dir``, default
 ``<output_path>/cache``, and reused while the files' fingerprint holds), kept on the device as ``uint8``, and every batch is assembled
@@ -45,6 +45,14 @@ gives each training pair ONE geometric transform, drawn from ``(data_seed, globa
 training set per epoch from the same key.  ``data_seed`` defaults to ``seed or 0``.  Test loaders never shuffle or augment.  Before
 every training epoch the driver calls ``set_epoch(global epoch)``, so a resumed run draws what the uninterrupted one draws.
 ``augment`` or ``shuffle`` without ``device_cache`` raises: the sets' host ``transforms`` run once per image and cannot be paired.
+
+``synthetic`` (a ``synth.Synth``, its ``as_dict()``, or ``{"atmospheric": ..., "underwater": ...}`` for one per stage, ``None`` for a
+stage without) draws the INPUT of a training pair from its augmented target on the device (``hdiff_amd/synth.py``): with probability
+``synthetic_prob`` (1.0) per sample, from ``(data_seed, global epoch, sample index)``.  That is how a clean-only set, whose cache
+holds ``b is a``, trains anything but the identity.  ``synthetic_val`` (False) degrades the stage's test loader too, under a key that
+does not move with the epoch: the only validation a clean-only set can have.  ``synthetic`` without ``device_cache`` raises.  The
+state file records the three values (``synthetic_plan``) and ``resume`` under other values raises; a run without the keys builds and
+writes what it did before.
 
 With ``ema_decay`` an ``optim.EMA`` of all weights is updated after every optimizer step and lives across the stage boundary (the
 optimizer does not); every checkpoint gets a sibling ``..._ema.pt`` (``EMA.shadow_state_dict``: the same keys, so ``Evaluate.test``
@@ -74,7 +82,7 @@ import torch
 
 from .Evaluate import PREDICTION_FILE, _cfg
 
-__all__ = ["train", "data_plan", "stage_plan", "checkpoint_epochs", "checkpoint_name", "final_name", "expected_files", "lr_sequence",
+__all__ = ["train", "data_plan", "synthetic_plan", "stage_plan", "checkpoint_epochs", "checkpoint_name", "final_name", "expected_files", "lr_sequence",
            "TERMS", "STATE_FILE", "PREDICTION_FILE", "prediction_settings", "write_prediction_file"]
 
 TERMS = ("loss", "mse_loss", "perceptual_dino", "msssim", "col_loss")       # the trainer's return order (rotinas.py:439)
@@ -174,6 +182,40 @@ def data_plan(config) -> Dict[str, object]:
     return {"device_cache": device_cache, "cache_dir": str(cache_dir), "augment": augment, "shuffle": shuffle, "data_seed": data_seed}
 
 
+def synthetic_plan(config) -> Optional[Dict[str, object]]:
+    """The synthetic degradation of the run, validated on the host: ``None`` without the ``synthetic`` key, else ``{"synthetic":
+    {"atmospheric": Synth or None, "underwater": Synth or None}, "synthetic_prob", "synthetic_val"}``."""
+    from ..synth import Synth
+    given = _cfg(config, "synthetic", None)
+    if given is None:
+        for key in ("synthetic_prob", "synthetic_val"):
+            if _cfg(config, key, None) is not None:
+                raise ValueError(f"hdiff_amd.diffusion.Train: {key} without synthetic")
+        return None
+    if not bool(_cfg(config, "device_cache", False)):
+        raise ValueError("hdiff_amd.diffusion.Train: synthetic needs device_cache=True: the degradation is drawn on the device, behind "
+                         "the batch assembly")
+    kinds = ("atmospheric", "underwater")
+    if isinstance(given, dict) and given and set(given) <= set(kinds):
+        per_stage = {k: None if given.get(k) is None else Synth.from_dict(given[k]) for k in kinds}
+    else:
+        per_stage = {k: Synth.from_dict(given) for k in kinds}
+    if all(v is None for v in per_stage.values()):
+        raise ValueError("hdiff_amd.diffusion.Train: synthetic names no stage")
+    prob = _cfg(config, "synthetic_prob", None)
+    prob = 1.0 if prob is None else prob
+    next(v for v in per_stage.values() if v is not None).thresholds(prob)          # refuses a probability outside [0, 1]
+    return {"synthetic": per_stage, "synthetic_prob": prob, "synthetic_val": bool(_cfg(config, "synthetic_val", False))}
+
+
+def _synthetic_record(plan) -> Optional[Dict[str, object]]:
+    """What the state file keeps of a ``synthetic_plan``: plain values, comparable with ``==``."""
+    if plan is None:
+        return None
+    return {"synthetic": {k: None if v is None else v.as_dict() for k, v in plan["synthetic"].items()},
+            "synthetic_prob": plan["synthetic_prob"], "synthetic_val": plan["synthetic_val"]}
+
+
 def _schedulers(optimizer, multiplier: float, epochs: int):
     from ..Scheduler import GradualWarmupScheduler
     cosine = torch.optim.lr_scheduler.CosineAnnealingLR(optimizer=optimizer, T_max=epochs, eta_min=0, last_epoch=-1)      # :661-662
@@ -252,6 +294,7 @@ def train(config) -> Dict[str, object]:
 
     _refuse_data_parallel(config)
     plan = data_plan(config)
+    synthetic = synthetic_plan(config)
     predict = prediction_settings(config)
     default_predict = predict == prediction_settings({})
     device = _device(config)
@@ -267,16 +310,20 @@ def train(config) -> Dict[str, object]:
     transforms = _cfg(config, "transforms", None)
     batch_size, workers = int(_cfg(config, "batch_size")), int(_cfg(config, "num_workers", 4))
 
-    def loader(data, name, task):                                                                   # :602-605
+    def loader(data, name, task, kind):                                                             # :602-605
         if not plan["device_cache"]:
             return DataLoader(data, batch_size=batch_size, num_workers=workers, drop_last=True, pin_memory=True)
         from ..device_data import DeviceLoader, build_cache
         cache = build_cache(data, os.path.join(plan["cache_dir"], f"{name}_{task}.pt"), num_workers=workers).to(device)
         train_side = task == "train"
+        extra = {}
+        if synthetic is not None and synthetic["synthetic"][kind] is not None and (train_side or synthetic["synthetic_val"]):
+            extra = dict(synth=synthetic["synthetic"][kind], synth_prob=synthetic["synthetic_prob"],
+                         synth_epoch=None if train_side else 0)
         return DeviceLoader(cache, batch_size, shuffle=plan["shuffle"] and train_side, drop_last=True,
-                            augment=plan["augment"] if train_side else None, seed=plan["data_seed"])
+                            augment=plan["augment"] if train_side else None, seed=plan["data_seed"], **extra)
 
-    loaders = {(kind, task): loader(cls(name, transforms=transforms, task=task, root=root_of(name)), name, task)
+    loaders = {(kind, task): loader(cls(name, transforms=transforms, task=task, root=root_of(name)), name, task, kind)
                for kind, cls, name in (("underwater", Underwater_Dataset, u_name), ("atmospheric", Atmospheric_Dataset, a_name))
                for task in ("train", "test")}
 
@@ -324,6 +371,10 @@ def train(config) -> Dict[str, object]:
         if was != predict:
             raise RuntimeError(f"hdiff_amd.diffusion.Train.train: the state file was written with {was} and the configuration asks for "
                                f"{predict}: a network goes on being trained for what it was trained for")
+        if resumed.get("synthetic", None) != _synthetic_record(synthetic):
+            raise RuntimeError(f"hdiff_amd.diffusion.Train.train: the state file was written with synthetic = {resumed.get('synthetic')} "
+                               f"and the configuration asks for {_synthetic_record(synthetic)}: a resumed run draws what the "
+                               "uninterrupted one draws")
         model.load_state_dict(resumed["model"])
         if (ema is None) != (resumed["ema"] is None):
             raise RuntimeError("hdiff_amd.diffusion.Train.train: the state file and the configuration disagree about ema_decay")
@@ -353,6 +404,7 @@ def train(config) -> Dict[str, object]:
                     "optimizer": None if opt is None else opt.state_dict(),
                     "schedulers": None if opt is None else _sched_state(warm, cosine),
                     "stage": si, "epoch": e, "num": num, "record": record, "prediction": predict,
+                    **({} if synthetic is None else {"synthetic": _synthetic_record(synthetic)}),
                     "rng_cpu": torch.get_rng_state(), "rng_device": torch.cuda.get_rng_state(device)}, state_path)
 
     if predict["prediction"] != "eps":          # beside the checkpoints, which stay plain state dicts: Evaluate reads it

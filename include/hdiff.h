@@ -989,6 +989,57 @@ int hdiff_batch_assemble(const uint8_t* a, const uint8_t* b, const int64_t* idx,
                          uint8_t* out_a, uint8_t* out_b, hdiff_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------------------------
+ * Synthetic degradation: the degraded input of a pair drawn from its clean target on the device (csrc/synth_degrade.hip;
+ * tests/_synth_def.py is the definition; hdiff_amd/synth.py is the caller).  Two launches per batch.
+ *
+ * hdiff_synth_params fills table [B][HDIFF_SYNTH_PARAMS] (double, the columns below) and zseeds [B].  Sample i = idx[j] at `epoch`
+ * reads w_k = philox4x32_10(seed, i, 2^32 + 8 epoch + k), k < 8 -- counters hdiff_batch_assemble (2 epoch, 2 epoch + 1 < 2^32) never
+ * uses.  A uniform draw is u(r) = (r + 0.5) 2^-32, a range draw lo + (hi - lo) u(r) in three separately rounded double operations, a
+ * switch is r < threshold (a probability scaled to [0, 2^32]), a choice among n is (r n) >> 32:
+ *   selected w0[0] < th_select, medium w0[1] < th_medium, exposure w0[2] < th_exposure, noise w0[3] < th_noise;
+ *   n_types > 0: type = (w1[0] n_types) >> 32, beta_c = type_beta[type][c]; else type = -1, beta_c = beta(w1[1]) for all c;
+ *   veil_c = clamp01(airlight(w1[2]) + veil[c](w2[c]));  d_lo, d_hi = min, max of depth(w1[3]), depth(w2[3]);
+ *   m = field_mean(w3[0]), gx = field_grad(w3[1]), gy = field_grad(w3[2]), gamma = gamma(w3[3]);
+ *   a_k = field_amp(w4[k]), gain = gain(w4[3]);  fx_k = w5[k] >> 30, shot = shot(w5[3]);  fy_k = w6[k] >> 30, read = read(w6[3]);
+ *   phi_k = 0 + (2 pi - 0) u(w7[k]), 2 pi = 6.283185307179586.
+ * A stage that is switched off leaves beta_c = 0, (gamma, gain) = (1, 1), (shot, read) = (0, 0) in the table.  zseeds[j] =
+ * mix(mix(mix(mix(0x73796E74685F7A31) ^ seed) ^ i) ^ epoch), mix the splitmix64 step.  The table equals the definition bit for bit.
+ * Refused: null pointers; B < 1; a threshold above 2^32; epoch >= 2^31; n_types outside [0, HDIFF_SYNTH_MAX_TYPES]; a range that is not
+ * finite with lo <= hi; a negative beta, depth, gain, shot or read; gamma <= 0.
+ *
+ * hdiff_synth_apply overwrites inp[j] ([B][3][H][W] uint8) for every sample whose `selected` column is 1 and leaves the others as they
+ * are.  Per pixel (x, y) and channel c, in double, in this order:
+ *   J = label / 255, u = (x + 0.5) / W, v = (y + 0.5) / H
+ *   s = clamp01(((m + gx (u - 0.5)) + gy (v - 0.5)) + sum_k a_k cos(2 pi (fx_k u + fy_k v) + phi_k)),  d = d_lo + (d_hi - d_lo) s
+ *   T = exp(-(beta_c d)), I = J T + veil_c (1 - T);   I = gain pow(I, gamma) (no pow when gamma == 1);
+ *   I = I + sqrt(max(shot I, 0) + read^2) z;   byte = floor(255 clamp01(I) + 0.5)
+ * with z element (c H + y) W + x of the row hdiff_randn_rows gives for zseeds[j] at offset HDIFF_SYNTH_Z_OFFSET (the same fp32 bits,
+ * widened).  Refused: null pointers; B < 1; H or W outside [1, 4096].  No atomics, no scratch, no allocation, no synchronisation: both
+ * entries are legal under stream capture; the bytes of sample j depend on (label[j], idx[j], seed, epoch, settings) alone.
+ * Additions to ABI 6.
+ * ------------------------------------------------------------------------------------------------------------------ */
+#define HDIFF_SYNTH_MAX_TYPES 16
+#define HDIFF_SYNTH_Z_OFFSET (1ull << 33)
+enum {
+  HDIFF_SYNTH_SELECTED = 0, HDIFF_SYNTH_TYPE = 1, HDIFF_SYNTH_M = 2, HDIFF_SYNTH_GX = 3, HDIFF_SYNTH_GY = 4, HDIFF_SYNTH_AMP = 5,
+  HDIFF_SYNTH_FX = 8, HDIFF_SYNTH_FY = 11, HDIFF_SYNTH_PHI = 14, HDIFF_SYNTH_D_LO = 17, HDIFF_SYNTH_D_HI = 18, HDIFF_SYNTH_BETA = 19,
+  HDIFF_SYNTH_VEIL = 22, HDIFF_SYNTH_GAMMA = 25, HDIFF_SYNTH_GAIN = 26, HDIFF_SYNTH_SHOT = 27, HDIFF_SYNTH_READ = 28,
+  HDIFF_SYNTH_PARAMS = 29
+};
+typedef struct {
+  int n_types;                                        /* 0: beta is drawn from `beta`, one value for the three channels */
+  double type_beta[HDIFF_SYNTH_MAX_TYPES][3];         /* attenuation per metre of each water type: -ln N(red, green, blue) */
+  double beta[2], airlight[2], veil[3][2], depth[2];  /* every range is {lo, hi} */
+  double field_mean[2], field_grad[2], field_amp[2];
+  double gamma[2], gain[2], shot[2], read[2];
+} hdiff_synth_settings;
+int hdiff_synth_params(const int64_t* idx, int B, uint64_t seed, uint32_t epoch, const hdiff_synth_settings* settings,
+                       uint64_t th_select, uint64_t th_medium, uint64_t th_exposure, uint64_t th_noise, double* table,
+                       uint64_t* zseeds, hdiff_stream_t stream);
+int hdiff_synth_apply(const uint8_t* label, const double* table, const uint64_t* zseeds, int B, int H, int W, uint8_t* inp,
+                      hdiff_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------------------------
  * hipGraph helpers: capture everything enqueued on `stream` between begin/end, replay it later.
  * ------------------------------------------------------------------------------------------------------------------ */
 int hdiff_graph_begin(hdiff_stream_t stream);

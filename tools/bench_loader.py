@@ -16,6 +16,13 @@ against the 78 images/s that the measured 51.18 ms step of the default DynamicUN
 
     python tools/bench_loader.py [--files 64] [--size 4032x3024] [--alternate 3] [--batch 2] [--workers 4] [--reps 2000]
 
+``--synth`` measures the synthetic degradation (hdiff_amd/synth.py) instead: a clean-only cache of ``--files`` procedural scenes at
+256x256 (no files), and ``DeviceLoader`` without the generator, with ``Synth.underwater()`` plus sensor noise (every stage on, every
+sample selected) and with that behind the augmentation, alternating in the same way.  ``synth.degrade`` alone on a resident batch is
+timed too, which is the two kernels without the Python around the loader.
+
+    python tools/bench_loader.py --synth [--files 64] [--alternate 3] [--batch 2] [--reps 2000]
+
 Prints one line per timing and one JSON summary line.  No condition is checked: the figures are the result."""
 import argparse
 import json
@@ -42,6 +49,7 @@ ap.add_argument("--alternate", type=int, default=3)
 ap.add_argument("--batch", type=int, default=2, help="pairs per batch")
 ap.add_argument("--workers", type=int, default=4)
 ap.add_argument("--reps", type=int, default=2000, help="epochs between the two device events of a device arm")
+ap.add_argument("--synth", action="store_true", help="the synthetic-degradation arms on procedural scenes, no host arms")
 a = ap.parse_args()
 dev = torch.device("cuda", 0)
 torch.cuda.set_device(0)
@@ -111,6 +119,50 @@ def device_arm(loader):
     ms = start.elapsed_time(end)
     return n / (ms * 1e-3), f"{a.reps} epochs = {n} images in {ms:.1f} ms between two device events, {ms / (a.reps * len(loader)) * 1e3:.0f} us per batch"
 
+
+def synth_arms():
+    from hdiff_amd import synth as SY
+    clean = torch.from_numpy(SY.procedural_scenes(a.files, 256, 256, seed=0))
+    cache = DD.PairCache(clean, clean, None, "procedural").to(dev)
+    s = SY.Synth.underwater(gamma=(0.7, 1.6), gain=(0.6, 1.1), shot=(0.0, 0.01), read=(0.0, 0.02))
+    augment = DD.Augment(hflip=0.5, vflip=0.5, rot90=True, crop=0.5, crop_min=0.5)
+    loaders = {"device_plain": DD.DeviceLoader(cache, a.batch),
+               "device_synth": DD.DeviceLoader(cache, a.batch, synth=s),
+               "device_augmented_synth": DD.DeviceLoader(cache, a.batch, shuffle=True, augment=augment, seed=1, synth=s)}
+    idx = torch.arange(a.files, dtype=torch.int64, device=dev)
+    label, out = cache.a.clone(), torch.empty_like(cache.a)
+
+    def kernels_arm():
+        SY.degrade(label, idx, synth=s, seed=1, epoch=0, out=out)
+        torch.cuda.synchronize(dev)
+        start, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        reps = max(a.reps // 20, 1)
+        start.record()
+        for e in range(reps):
+            SY.degrade(label, idx, synth=s, seed=1, epoch=e, out=out)
+        end.record()
+        end.synchronize()
+        ms = start.elapsed_time(end)
+        return reps * a.files / (ms * 1e-3), f"{reps} batches of {a.files} images in {ms:.1f} ms, {ms / reps * 1e3:.0f} us per batch of two launches"
+
+    rates = {k: [] for k in loaders}
+    rates["degrade_alone"] = []
+    for rep_ in range(a.alternate):
+        for k, loader in loaders.items():
+            rates[k].append(timed(lambda: device_arm(loader), f"{k:>22} rep {rep_}:"))
+        rates["degrade_alone"].append(timed(kernels_arm, f"{'degrade_alone':>22} rep {rep_}:"))
+    consumed = STEP_IMAGES / (STEP_MS * 1e-3)
+    summary = {k: {"mean": sum(v) / len(v), "min": min(v), "max": max(v), "repetitions": len(v)} for k, v in rates.items()}
+    print(json.dumps({"metric": f"images/s of device_data.DeviceLoader at 256x256, batch {a.batch} pairs, over {a.files} procedural scenes: "
+                                "without the synthetic degradation, with it, and with it behind the augmentation, alternating; "
+                                "degrade_alone counts degraded images of one resident batch",
+                      "unit": "images/s", "arms": summary, "step_consumes_images_per_s": consumed,
+                      "over_the_step": {k: v["mean"] / consumed for k, v in summary.items()}}))
+
+
+if a.synth:
+    synth_arms()
+    sys.exit(0)
 
 with tempfile.TemporaryDirectory() as tmp:
     sets, caches, build_s = {}, {}, {}
