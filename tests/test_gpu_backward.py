@@ -201,13 +201,14 @@ def test_flash_attention_backward(d, H, W, B):
 
 @pytest.mark.parametrize("d", [16, 32])
 def test_split_bf16_attention_backward_is_another_program_fp32_class_and_reproducible(d):
-    """attention_bwd_x3.hip (d_head 16 / 32, bf16x3 mode): B = 4, L = 8192 gives each workgroup SEVERAL key blocks, so the dQ slab
-    takes the plain store of the first block AND the in-order L2 float adds of the later ones.  The result must differ from the
-    fp32-input kernel's (another program ran), sit in the same error class against float64, and repeat bit for bit."""
+    """attention_bwd_h2.hip (d_head 16 / 32, bf16x3 mode): B = 16, L = 8192 gives each workgroup TWO key blocks of 256 (16 key ranges
+    over 32 blocks: hdiff_mha_flash_bwd_route, asserted below; B = 4 gave 32 ranges of one block, a launch without a single L2 add),
+    so the dQ slab takes the plain store of the first block AND the in-order L2 float add of the second.  The result must differ
+    from the fp32-input kernel's (another program ran), sit in the same error class against float64, and repeat bit for bit."""
     import ctypes as C
     from hdiff_amd import _capi
     lib = _capi.lib()
-    heads, L, B = 8, 8192, 4
+    heads, L, B = 8, 8192, 16
     Cc = heads * d
     g = torch.Generator().manual_seed(11 + d)
     qkv = (torch.randn(B, 3 * Cc, L, generator=g) * 1.3).to(DEV)
@@ -231,6 +232,10 @@ def test_split_bf16_attention_backward_is_another_program_fp32_class_and_reprodu
         return dqkv, need.value
 
     try:
+        _capi.check(lib.hdiff_set_contraction_mode(1))
+        route = [C.c_int(-1) for _ in range(4)]
+        _capi.check(lib.hdiff_mha_flash_bwd_route(B, Cc, heads, L, *(C.byref(v) for v in route)), "route")
+        assert route[0].value == 1 and 1 <= route[3].value < L // 256, [v.value for v in route]      # H2_PAIRS, a range holds > 1 block
         g32, need32 = bwd(0)
         gx3, needx3 = bwd(1)
         gx3_again, _ = bwd(1)

@@ -26,7 +26,9 @@ FWD = ["tests/test_gpu_ops.py::test_conv3x3_split_bf16_is_fp32_class",
        "tests/test_gpu_ops.py::test_conv3x3_fp16_pairs_is_fp32_class",
        "tests/test_gpu_ops.py::test_conv1x1_split_bf16_is_fp32_class",
        "tests/test_gpu_ops.py::test_flash_attention_split_bf16_is_fp32_class"]
-BWD = ["tests/test_gpu_backward.py::test_attention_backward_fp16_pairs_error_class_every_pair"]
+# ... and the same gates where a key range holds two blocks of 256 keys (sweep<false> of the d_head 16 kernel, the !first_kb path of d_head 32)
+MULTIBLOCK = ["tests/test_gpu_attn_bwd_h2.py::test_multiblock_error_class[seam2-d%d-plain]" % d for d in (16, 32)]
+BWD = ["tests/test_gpu_backward.py::test_attention_backward_fp16_pairs_error_class_every_pair"] + MULTIBLOCK
 # the shapes of the default 32x32, batch-80 training run (partial tiles, guarded epilogue): {test: parametrizations}, each must turn red
 DEFAULT32 = {"tests/test_gpu_ops.py::test_conv3x3_fp16_pairs_default32_shapes": 14,
              "tests/test_gpu_ops.py::test_conv3x3_split_bf16_default32_upsample_conv": 2,
@@ -76,6 +78,8 @@ def test_a_dropped_low_order_piece_product_turns_the_error_class_tests_red():
     assert len(att_pre) == 4, att_pre
     bwd = [l for l in failed if "test_attention_backward_fp16_pairs_error_class_every_pair" in l]
     assert len(bwd) == 2, (bwd, out[-2000:])                                 # the backward at both head widths (dP and dV^T products)
+    multi = [l for l in failed if l.split(" ")[1] in MULTIBLOCK]
+    assert len(multi) == 2, (multi, out[-2000:])                             # ... and with two key blocks per range
     # the second library: P V of the d_head 16 forward, third-piece terms of dS
     rc, out, failed = _run(["tests/test_gpu_ops.py::test_flash_attention_split_bf16_is_fp32_class"] + BWD, mutant2)
     assert rc == 1, out[-3000:]
@@ -84,6 +88,8 @@ def test_a_dropped_low_order_piece_product_turns_the_error_class_tests_red():
     assert not [l for l in failed if "test_flash_attention_split_bf16_is_fp32_class" in l and "[32-" in l], failed
     bwd = [l for l in failed if "test_attention_backward_fp16_pairs_error_class_every_pair" in l]
     assert len(bwd) == 2, (bwd, out[-2000:])
+    multi = [l for l in failed if l.split(" ")[1] in MULTIBLOCK]
+    assert len(multi) == 2, (multi, out[-2000:])
     # and the same selection is green on the real library (the suite runs it anyway; here: same process environment)
     rc, out, failed = _run(FWD + BWD + list(DEFAULT32))
     assert rc == 0, out[-3000:]
