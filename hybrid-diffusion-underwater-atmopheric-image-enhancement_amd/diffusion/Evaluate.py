@@ -47,7 +47,7 @@ import torch
 from .. import quality
 
 __all__ = ["evaluate", "test", "inference", "fit_niqe", "RES_KEYS", "RES_KEYS_UCIQE", "RES_KEY_LPIPS", "RES_KEYS_DISTRIBUTION",
-           "RES_KEY_NIQE", "RES_KEY_NIQE_FULL", "RES_KEYS_COLOR", "PREDICTION_FILE", "read_prediction", "resolve_prediction"]
+           "RES_KEY_NIQE", "RES_KEY_NIQE_FULL", "RES_KEYS_COLOR", "baseline_res_lines", "PREDICTION_FILE", "read_prediction", "resolve_prediction"]
 
 # res.txt: the reference's key for each measured score, in the reference's order (rotinas.py:967-982)
 RES_KEYS = (("psnr_orgin_avg:", "psnr"), ("ssim_orgin_avg:", "ssim"), ("uiqm_orgin_avg:", "uiqm"), ("uism_orgin_avg:", "uism"),
@@ -93,7 +93,7 @@ def evaluate(sampler, batches: Iterable, *, ddim_step: int, tile: Optional[int] 
              meter=None, solver: Optional[str] = None, spacing: Optional[str] = None, uciqe: bool = False,
              uciqe_scale: float = 1.0, lpips=None, distribution=None, transfer=None, niqe=None, samples: Optional[int] = None,
              eta: float = 0.0, sample_seed: int = 0, sample_batch: Optional[int] = None, std_gain: float = 4.0,
-             color: bool = False) -> Dict[str, object]:
+             color: bool = False, baselines=None) -> Dict[str, object]:
     """Samples and scores a set.  ``batches`` yields ``(input, target)`` or ``(input, target, names)``: CHW images in [0, 255] as
     ``Underwater_Dataset`` / ``Atmospheric_Dataset`` produce them, batched.  Per batch: ``out = sampler(input, ddim=True,
     unconditional_guidance_scale=1, ddim_step=ddim_step, tile=...)`` (rotinas.py:907), then ``(out + 1) / 2`` is scored against
@@ -126,6 +126,13 @@ def evaluate(sampler, batches: Iterable, *, ddim_step: int, tile: Optional[int] 
     ``"ciede2000_p95"``, ``"deltae76"`` and ``"angular"``, and ``res.txt`` four lines behind every other one: ``ciede2000_orgin_avg:``,
     ``ciede2000_p95_orgin_avg:``, ``deltae76_orgin_avg:`` and ``angular_orgin_avg:`` (under ``samples=`` their ``_sample_avg:`` /
     ``_sample_std:`` lines follow like the other per-image scores').  Without it nothing of that is launched or written.
+    ``baselines``: a sequence of names out of ``hdiff_amd.classical.BASELINES`` (``"input"``, ``"gray_world"``, ``"dcp"``, ``"udcp"``,
+    ``"inverted_dcp"``) or ``(name, callable)`` pairs, a callable taking the ``[0, 1]`` input batch to an image batch of the same shape.
+    Per baseline a second meter of the main meter's configuration (a ``quality.QualityMeter``) is updated per batch with
+    ``fn(input / 255)`` against ``target / 255``; the result gains ``"baselines": {name: that meter's compute() dict}`` and ``res.txt``,
+    behind every other line (the ``samples=`` lines included), one line ``<score>_<name>_avg:`` per baseline in the order given, for
+    every per-image score the main meter reports (the set-level ``fd`` / ``kid`` and ``niqe_full`` have none).  An unknown name raises
+    before anything is sampled.  Without it nothing of that is constructed, launched or written.
     ``samples=K`` (an integer >= 1): every batch goes through ``sampler.posterior(input, K, eta=eta, seed=sample_seed,
     image_ids=<the running indices of its images in the set>, sample_batch=sample_batch, ...)`` in place of one ``sampler`` call.  The
     MEAN of the K clipped samples is the image that is scored, saved, and handed to ``distribution`` and ``transfer``; a second meter
@@ -148,6 +155,11 @@ def evaluate(sampler, batches: Iterable, *, ddim_step: int, tile: Optional[int] 
             raise ValueError("evaluate: samples= cannot be combined with tile=")
         if not hasattr(sampler, "posterior"):
             raise TypeError("evaluate: samples= needs a sampler with a posterior() method (diffusion.Diffusion.GaussianDiffusionSampler)")
+    if baselines is not None:
+        from ..classical import resolve_baselines
+        baselines = resolve_baselines(baselines)
+        if meter is not None and not isinstance(meter, quality.QualityMeter):
+            raise ValueError("evaluate: baselines= needs a quality.QualityMeter (its configuration is copied for every baseline)")
     transfer = _transfer_settings(transfer)
     if transfer is not None and save_dir is None:
         raise ValueError("evaluate: transfer= writes full-size images and needs save_dir=")
@@ -177,6 +189,7 @@ def evaluate(sampler, batches: Iterable, *, ddim_step: int, tile: Optional[int] 
         replicas = _ReplicaScores(meter, samples)
         if save_dir is not None:
             os.makedirs(os.path.join(save_dir, "std"), exist_ok=True)
+    baseline_meters = None if baselines is None else [(name, fn, _meter_like(meter)) for name, fn in baselines]
     done = 0
     with torch.no_grad():
         for batch in batches:
@@ -196,6 +209,9 @@ def evaluate(sampler, batches: Iterable, *, ddim_step: int, tile: Optional[int] 
                     _save_batch(std_gain * post.std / 2, names, os.path.join(save_dir, "std"))
             pred01 = (out + 1) / 2                                                        # :912
             meter.update(pred01, target / 255)
+            if baseline_meters is not None:
+                for _, fn, other in baseline_meters:
+                    other.update(fn(inp / 255), target / 255)
             if distribution is not None:
                 distribution.update(pred01, target / 255)
             if collect is not None:
@@ -216,6 +232,8 @@ def evaluate(sampler, batches: Iterable, *, ddim_step: int, tile: Optional[int] 
         result["niqe_full_undefined"] = len(full_scores) - len(defined)
     if replicas is not None:
         result.update(replicas.compute())
+    if baseline_meters is not None:
+        result["baselines"] = {name: other.compute() for name, _, other in baseline_meters}
     if save_dir is not None:
         keys = RES_KEYS_UCIQE if uciqe else RES_KEYS
         if lpips is not None:
@@ -226,12 +244,32 @@ def evaluate(sampler, batches: Iterable, *, ddim_step: int, tile: Optional[int] 
             keys = keys + (RES_KEY_NIQE,) + ((RES_KEY_NIQE_FULL,) if transfer is not None else ())
         if color:
             keys = keys + RES_KEYS_COLOR
+        flat = result
         if replicas is not None:
             flat, keys = sample_res_lines(result, keys)
-            write_res(os.path.join(save_dir, "res.txt"), flat, keys)
-        else:
-            write_res(os.path.join(save_dir, "res.txt"), result, keys)
+        if baseline_meters is not None:
+            flat, keys = baseline_res_lines(flat, keys, meter.columns)
+        write_res(os.path.join(save_dir, "res.txt"), flat, keys)
     return result
+
+
+def _meter_like(meter):
+    """A new ``quality.QualityMeter`` of ``meter``'s configuration."""
+    return quality.QualityMeter(uciqe=meter._uciqe, uciqe_scale=meter._uciqe_scale, lpips=meter._lpips, niqe=meter._niqe,
+                                color=meter._color)
+
+
+def baseline_res_lines(result: Dict[str, object], keys, columns):
+    """-> (flat result, keys) for ``write_res`` under ``baselines=``: ``keys`` in their order, then per baseline in the order given one
+    ``<score>_<name>_avg:`` for each of today's ``*_orgin_avg:`` lines whose score is a column of the meter."""
+    flat = dict(result)
+    keys = tuple(keys)
+    scores = [k for label, k in keys if label.endswith("_orgin_avg:") and k in columns]
+    for name, scored in result["baselines"].items():
+        for k in scores:
+            flat[f"{k}_{name}_avg"] = scored[k]
+            keys += ((f"{k}_{name}_avg:", f"{k}_{name}_avg"),)
+    return flat, keys
 
 
 def sample_res_lines(result: Dict[str, object], keys):
@@ -254,8 +292,7 @@ class _ReplicaScores:
         if not isinstance(meter, quality.QualityMeter):
             raise ValueError("evaluate: samples= needs a quality.QualityMeter (its configuration is copied for the replicas)")
         self.K = K
-        self.meter = quality.QualityMeter(uciqe=meter._uciqe, uciqe_scale=meter._uciqe_scale, lpips=meter._lpips, niqe=meter._niqe,
-                                          color=meter._color)
+        self.meter = _meter_like(meter)
         self.replica_of_update: List[int] = []
         self.spread = None          # [sum of std / 2, elements] as a float64 device pair
 
@@ -443,6 +480,8 @@ def _run_sets(config, task: str) -> Dict[str, Dict[str, object]]:
                      sample_batch=_cfg(config, "sample_batch", None))
     elif any(_cfg(config, k, None) is not None for k in ("ddim_eta", "sample_seed", "sample_batch")):
         raise ValueError("the configuration gives ddim_eta / sample_seed / sample_batch without 'samples'")
+    if _cfg(config, "baselines", None) is not None:
+        extra["baselines"] = _cfg(config, "baselines")
     results = {}
     for name, data in sets:
         if features is not None:      # one meter per set; a DistributionMeter from the configuration goes on filling across both
@@ -479,6 +518,9 @@ def test(config, epoch=None) -> Dict[str, Dict[str, object]]:
     goes to ``<set>/std/<name>`` and ``res.txt`` gains the draw-to-draw spread of every score) with ``ddim_eta`` (default 0),
     ``sample_seed`` (default 0) and ``sample_batch`` (the most samples per model evaluation; absent: one draw from torch's generator
     per image, ``res.txt`` as before),
+    ``baselines`` (``evaluate``'s ``baselines=``: names out of ``classical.BASELINES`` or ``(name, callable)`` pairs, each scored on
+    ``input / 255`` against the targets beside the model, ``res.txt`` gains ``<score>_<name>_avg:`` lines; absent: nothing of it is
+    constructed, launched or written),
     ``prediction`` ("eps" or "v": what the checkpoint's network predicts, the sampler's ``prediction=``; absent: read from the
     ``prediction.json`` beside ``pretrained_path`` if ``Train.train`` left one, else "eps"; present and different from that file:
     ``ValueError``, see ``resolve_prediction``).

@@ -1040,6 +1040,41 @@ int hdiff_synth_apply(const uint8_t* label, const double* table, const uint64_t*
                       hdiff_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------------------------
+ * Classical baselines: the dark-channel prior and its variants, gray-world / shades-of-gray white balance (csrc/classical.hip;
+ * tests/_classical_def.py is the definition; hdiff_amd/classical.py is the caller).  Images are float [N][3][H][W], clipped to [0, 1]
+ * in fp32 as they are read (a NaN clips to 0); `invert` reads X = fp32(1 - clip(I)) in their place.  N <= 65535, H W <= 2^30.
+ *
+ *   hdiff_classical_point_min   out[n][y][x] = min over the channel set (channels = 3: R, G, B; 2: G, B) of X_c, or, with `airlight`
+ *                               ([N][3], every entry > 0), of fp32(double(X_c) / double(A_c)).  One launch.
+ *   hdiff_classical_window_min  out = the minimum of `in` ([N][H][W]) over the (2 r + 1)^2 window clipped at the border, r = patch / 2,
+ *                               patch odd in [1, 63]; with affine != 0, out = fp32(1 - omega double(min)).  `in` and `out` must not
+ *                               overlap.  One launch, 32 x 32 output tiles with a halo of r.
+ *   hdiff_classical_airlight    `dark` [N][H][W] finite.  cut[n] = the element of ascending rank H W - n_top of dark[n] (1 <= n_top <=
+ *                               H W; radix select on the fp32 key, three digits); among the pixels with dark >= cut the one with the
+ *                               largest (double(X_R) + double(X_G)) + double(X_B), the lowest index at equal sums;
+ *                               airlight[n][c] = max(X_c there, fp32(1 / 255)).  Nine launches; integer atomics only.
+ *   hdiff_classical_recover     out_c = fp32(clamp((double(X_c) - A_c) / max(double(t), t0) + A_c, 0, 1)), t [N][H][W], t0 > 0; with
+ *                               `invert`, out_c = fp32(1 - that).  One launch.
+ *   hdiff_white_balance         m_c = (mean of double(X_c)^p)^(1 / p) per image and channel (fixed-order double sums; no pow at p = 1;
+ *                               the exact maximum at p = inf), g_c = ((m_0 + m_1) + m_2) / 3 / max(m_c, 1e-6) -> gains [N][3] (double),
+ *                               out_c = fp32(clamp(double(X_c) g_c, 0, 1)).  p >= 1.  Three launches.
+ * No float atomics, no allocation, no synchronisation: every entry is legal under stream capture, and image n of every output depends
+ * on image n of the inputs alone.  Additions to ABI 6.
+ * ------------------------------------------------------------------------------------------------------------------ */
+int hdiff_classical_point_min(const float* img, int N, int H, int W, int channels, int invert, const float* airlight, float* out,
+                              hdiff_stream_t stream);
+int hdiff_classical_window_min(const float* in, int N, int H, int W, int patch, int affine, double omega, float* out,
+                               hdiff_stream_t stream);
+int hdiff_classical_airlight_workspace(int N, int H, int W, int64_t* bytes);
+int hdiff_classical_airlight(const float* img, const float* dark, int N, int H, int W, int invert, int64_t n_top, float* airlight,
+                             float* cut, void* scratch, hdiff_stream_t stream);
+int hdiff_classical_recover(const float* img, const float* t, const float* airlight, int N, int H, int W, int invert, double t0,
+                            float* out, hdiff_stream_t stream);
+int hdiff_white_balance_workspace(int N, int H, int W, int64_t* bytes);
+int hdiff_white_balance(const float* img, int N, int H, int W, double p, double* gains, float* out, void* scratch,
+                        hdiff_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------------------------
  * hipGraph helpers: capture everything enqueued on `stream` between begin/end, replay it later.
  * ------------------------------------------------------------------------------------------------------------------ */
 int hdiff_graph_begin(hdiff_stream_t stream);

@@ -1,0 +1,149 @@
+"""The classical baselines for one batch of 8 images at 256x256, two ways, ALTERNATELY inside one process, engine clock and board power
+sampled beside each timing (bench.ClockSampler):
+
+  (a) hip: ``classical.dehaze`` (each prior, with and without the guided refinement) and ``classical.white_balance``, timed by device
+      events around ``--reps`` consecutive calls (nothing synchronises in between);
+  (b) torch: the same steps in plain torch ops on the device -- ``-max_pool2d(-x)`` for the windowed minimum, ``torch.topk`` for the
+      cut, a gather for the airlight, elementwise ops for transmission and recovery (fp32 throughout, so NOT the definition's
+      rounding: it is the comparison arm, not a reference).  The refinement is ``transfer.guided_fit`` / ``guided_apply`` in both arms.
+
+It also times ``Evaluate.evaluate`` over ``--eval-batches`` batches with a stand-in sampler (one elementwise op, so the loop and the
+scores are what is timed) without and with ``baselines=("input", "gray_world", "dcp")``, wall clock with one synchronisation.
+
+    python tools/bench_classical.py [--batch 8] [--size 256] [--alternate 3] [--reps 20] [--warmup 3]
+
+Prints one line per timing and one JSON summary line.  No condition is checked: the figures are reported as they come."""
+import argparse
+import json
+import math
+import os
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+import torch  # noqa: E402
+import torch.nn.functional as F  # noqa: E402
+import hdiff_amd  # noqa: E402,F401
+import bench  # noqa: E402
+from hdiff_amd import classical, transfer  # noqa: E402
+from hdiff_amd.diffusion import Evaluate  # noqa: E402
+
+ap = argparse.ArgumentParser()
+ap.add_argument("--batch", type=int, default=8)
+ap.add_argument("--size", type=int, default=256)
+ap.add_argument("--alternate", type=int, default=3)
+ap.add_argument("--reps", type=int, default=20)
+ap.add_argument("--warmup", type=int, default=3)
+ap.add_argument("--eval-batches", type=int, default=4)
+a = ap.parse_args()
+dev = torch.device("cuda", 0)
+torch.cuda.set_device(0)
+g = torch.Generator().manual_seed(0)
+# image-like content: smooth colour fields plus noise under a grey veil
+yy, xx = torch.meshgrid(torch.arange(a.size, dtype=torch.float32), torch.arange(a.size, dtype=torch.float32), indexing="ij")
+base = torch.stack([0.5 + 0.4 * torch.sin(xx / 25 + c) * torch.cos(yy / 35 - c) for c in range(3)])
+clean = (base[None] + 0.05 * torch.randn(a.batch, 3, a.size, a.size, generator=g)).clamp(0, 1)
+depth = (0.3 + 0.6 * yy / a.size)[None, None]
+img = (clean * depth + 0.85 * (1 - depth)).clamp(0, 1).to(dev)
+clean = clean.to(dev)
+PATCH, OMEGA, T0, TOP, REFINE = 15, 0.95, 0.1, 1e-3, (16, 1e-3)
+
+
+def window_min_torch(x):
+    return -F.max_pool2d(-x, PATCH, stride=1, padding=PATCH // 2)      # max_pool2d pads with -inf: the window is clipped at the border
+
+
+def dehaze_torch(x, prior, refine):
+    x = x.clamp(0, 1)
+    if prior == "inverted_dcp":
+        x = 1 - x
+    ch = x[:, 1:] if prior == "udcp" else x
+    N, _, H, W = x.shape
+    dark = window_min_torch(ch.amin(1, keepdim=True)).reshape(N, -1)
+    n_top = max(1, int(math.floor(TOP * H * W)))
+    cut = torch.topk(dark, n_top, dim=1).values[:, -1:]
+    total = x.double().sum(1).reshape(N, -1).masked_fill(dark < cut, -1.0)
+    at = total.argmax(1)
+    A = x.reshape(N, 3, -1).gather(2, at[:, None, None].expand(N, 3, 1)).clamp_min(1 / 255)[..., None]
+    ratio = x / A
+    t = 1 - OMEGA * window_min_torch((ratio[:, 1:] if prior == "udcp" else ratio).amin(1, keepdim=True))
+    if refine is not None:
+        coef = transfer.guided_fit(x, t.expand(N, 3, H, W).contiguous(), radius=refine[0], eps=refine[1])
+        t = transfer.guided_apply(coef, x, clamp=False)[:, :1]
+    J = ((x - A) / t.clamp_min(T0) + A).clamp(0, 1)
+    return 1 - J if prior == "inverted_dcp" else J
+
+
+def white_balance_torch(x):
+    x = x.clamp(0, 1)
+    m = x.double().mean((2, 3))
+    gains = m.mean(1, keepdim=True) / m.clamp_min(1e-6)
+    return (x.double() * gains[:, :, None, None]).clamp(0, 1).float()
+
+
+def device_arm(fn):
+    for _ in range(a.warmup):
+        out = fn()
+    torch.cuda.synchronize(dev)
+    start, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    start.record()
+    for _ in range(a.reps):
+        out = fn()
+    end.record()
+    end.synchronize()
+    return start.elapsed_time(end) / a.reps, out
+
+
+def stand_in_sampler(inp, **kwargs):
+    return inp / 127.5 - 1
+
+
+def evaluate_arm(baselines):
+    batches = [((img * 255), (clean * 255)) for _ in range(a.eval_batches)]
+    Evaluate.evaluate(stand_in_sampler, batches[:1], ddim_step=1, baselines=baselines)
+    torch.cuda.synchronize(dev)
+    t0 = time.perf_counter()
+    res = Evaluate.evaluate(stand_in_sampler, batches, ddim_step=1, baselines=baselines)
+    torch.cuda.synchronize(dev)
+    return (time.perf_counter() - t0) * 1e3 / a.eval_batches, res
+
+
+def timed(arm, label, fmt):
+    clock = bench.ClockSampler(0)
+    with clock:
+        ms, res = arm()
+    c = clock.summary()
+    print(f"{label} {fmt(ms)}  sclk {c.get('sclk_mhz_mean')} MHz  board {c.get('board_power_w_mean')} W", flush=True)
+    return ms, res
+
+
+cases = [(f"dehaze {prior}{'' if refine is None else ' refined'}",
+          (lambda p=prior, r=refine: classical.dehaze(img, prior=p, patch=PATCH, omega=OMEGA, t0=T0, top=TOP, refine=r)),
+          (lambda p=prior, r=refine: dehaze_torch(img, p, r)))
+         for prior in ("dcp", "udcp", "inverted_dcp") for refine in (None, REFINE)]
+cases.append(("white_balance p=1", lambda: classical.white_balance(img, p=1.0), lambda: white_balance_torch(img)))
+times = {}
+per_call = lambda ms: f"{ms:.4f} ms per call on {a.batch} x {a.size}x{a.size} ({a.reps} calls between two events)"      # noqa: E731
+for rep in range(a.alternate):
+    for name, hip, ref in cases:
+        ms0, out0 = timed(lambda: device_arm(hip), f"{name:34s} hip   rep {rep}:", per_call)
+        ms1, out1 = timed(lambda: device_arm(ref), f"{name:34s} torch rep {rep}:", per_call)
+        times.setdefault(name, {"hip_ms": [], "torch_ms": []})
+        times[name]["hip_ms"].append(ms0)
+        times[name]["torch_ms"].append(ms1)
+        if rep == 0:
+            print(f"{'':34s} max |hip - torch| on this batch: {(out0 - out1).abs().max().item():.2e}", flush=True)
+    per_batch = lambda ms: f"{ms:.3f} ms per batch of {a.batch} ({a.eval_batches} batches, wall clock)"      # noqa: E731
+    ms0, _ = timed(lambda: evaluate_arm(None), f"{'evaluate':34s} plain rep {rep}:", per_batch)
+    ms1, res = timed(lambda: evaluate_arm(("input", "gray_world", "dcp")), f"{'evaluate with three baselines':34s}       rep {rep}:", per_batch)
+    times.setdefault("evaluate", {"plain_ms": [], "with_baselines_ms": []})
+    times["evaluate"]["plain_ms"].append(ms0)
+    times["evaluate"]["with_baselines_ms"].append(ms1)
+    if rep == 0:
+        print("   PSNR of the batch: " + ", ".join(f"{n} {res['baselines'][n]['psnr']:.2f} dB" for n in res["baselines"]), flush=True)
+summary = {name: {k: {"mean": sum(v) / len(v), "min": min(v), "max": max(v), "repetitions": len(v)} for k, v in arms.items()}
+           for name, arms in times.items()}
+print(json.dumps({"metric": f"classical baselines on one batch of {a.batch} at {a.size}x{a.size}: hdiff_amd.classical against the same "
+                            "steps in torch ops on the device, alternating; Evaluate.evaluate per batch without / with three baselines",
+                  "unit": "ms", "arms": summary}))
