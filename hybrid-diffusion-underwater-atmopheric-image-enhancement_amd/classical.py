@@ -17,6 +17,19 @@ photographs of several hundred pixels), ``refine=(16, 1e-3)`` (a choice for 256-
 published implementation of the dark-channel prior; nor any figure on real photographs.  The README records what the definition
 gives on this repository's own procedural scenes.
 
+Contrast from the histogram (``csrc/contrast.hip``), the family that raises the no-reference scores without inverting anything:
+
+    out = classical.clahe(img01, clip_limit=2.0, grid=(8, 8), space="lab")   # CLAHE on 8-bit planes: CIE L* alone, or "rgb": each channel
+    out = classical.equalize(img01, space="rgb")                              # global equalisation, the rule of Pillow's ImageOps.equalize
+    Evaluate.evaluate(sampler, batches, ddim_step=20, baselines=("input", "clahe_lab", "equalize"))      # CONTRAST_BASELINES
+
+``tests/_contrast_def.py`` is their definition; the quantised planes, every table and the ``"rgb"`` output equal it bit for bit, the
+``"lab"`` output of ``clahe`` is its fp32 value or the neighbour, and ``equalize`` equals it bit for bit in both spaces and is
+Pillow's byte for byte in ``"rgb"``.  NOT pinned: agreement with OpenCV's
+``createCLAHE`` (the algorithm is written from memory, none is installed to compare with, and the padding knowingly differs: the
+plane is padded to the next multiple of the grid and no further), the defaults ``clip_limit=2.0`` and ``grid=(8, 8)``, any figure on
+real photographs.
+
 Everything runs on the current stream, allocates through torch's caching allocator and never synchronises; there is no CPU fallback."""
 from __future__ import annotations
 
@@ -29,7 +42,8 @@ import torch
 from . import _capi
 from . import engine as E
 
-__all__ = ["dark_channel", "dehaze", "white_balance", "BASELINES", "resolve_baselines", "dehaze_settings", "PRIORS"]
+__all__ = ["dark_channel", "dehaze", "white_balance", "clahe", "equalize", "BASELINES", "CONTRAST_BASELINES", "resolve_baselines",
+           "dehaze_settings", "PRIORS"]
 
 PRIORS = {"dcp": ("rgb", False), "udcp": ("gb", False), "inverted_dcp": ("rgb", True)}      # the prior's channel set; inverted image
 _CHANNELS = {"rgb": 3, "gb": 2}
@@ -209,6 +223,121 @@ def white_balance(img01: torch.Tensor, *, p: float = 1.0, return_gains: bool = F
     return (out, gains) if return_gains else out
 
 
+# ---------------------------------------------------------------------------------------------------------------- contrast
+_SPACES = {"rgb": 3, "lab": 1}         # the 8-bit planes a space is enhanced on: each channel, or CIE L* alone
+_MAX_TILES = 16
+
+
+def _f32(v: float) -> float:
+    """One rounding to fp32.  A quotient of two fp32 values taken in double and rounded here is the fp32 quotient (53 >= 2 * 24 + 2)."""
+    return C.c_float(v).value
+
+
+def _space(space) -> int:
+    if space not in _SPACES:
+        raise ValueError(f"hdiff: 'space' = {space!r}; one of {sorted(_SPACES)}")
+    return _SPACES[space]
+
+
+def _grid(grid) -> Tuple[int, int]:
+    if not isinstance(grid, (tuple, list)) or len(grid) != 2 or any(isinstance(g, bool) or not isinstance(g, int) for g in grid):
+        raise ValueError(f"hdiff: 'grid' must be a (tiles_y, tiles_x) pair of ints, got {grid!r}")
+    ty, tx = grid
+    if not (1 <= ty <= _MAX_TILES and 1 <= tx <= _MAX_TILES):
+        raise ValueError(f"hdiff: 'grid' = {tuple(grid)!r}; each value between 1 and {_MAX_TILES}")
+    return ty, tx
+
+
+def _clip_limit(clip_limit) -> float:
+    clip_limit = _number("clip_limit", clip_limit)
+    if not clip_limit >= 0.0:          # NaN fails the comparison
+        raise ValueError(f"hdiff: 'clip_limit' = {clip_limit!r}; it must be at least 0 (0: no clipping)")
+    return clip_limit
+
+
+def _fits(H: int, W: int, ty: int, tx: int) -> None:
+    if H < ty or W < tx:
+        raise ValueError(f"hdiff: a {H} x {W} image cannot be cut into a ({ty}, {tx}) grid; it needs H >= tiles_y and W >= tiles_x")
+
+
+def _tile_constants(H: int, W: int, ty: int, tx: int, clip_limit: float):
+    """What the kernels are handed for an ``H x W`` plane: ``(clip, scale, inv_th, inv_tw)`` -- the count a tile's bin is cut at (the
+    tile's area where nothing is cut) and the three fp32 constants, each one division on the host."""
+    th, tw = -(-H // ty), -(-W // tx)
+    area = th * tw
+    clip = area
+    if clip_limit > 0.0:
+        c = clip_limit * float(area) / 256.0
+        clip = area if c >= area else max(1, int(math.floor(c)))      # a clip above the area cuts nothing, like the area itself
+    return clip, _f32(255.0 / _f32(area)), _f32(1.0 / _f32(th)), _f32(1.0 / _f32(tw))
+
+
+def _quantise(x: torch.Tensor, planes: int) -> torch.Tensor:
+    N, _, H, W = (int(v) for v in x.shape)
+    q = torch.empty(N, planes, H, W, dtype=torch.uint8, device=x.device)
+    _capi.check(_capi.lib().hdiff_contrast_quantise(x.data_ptr(), N, H, W, int(planes == 1), q.data_ptr(), _stream(x.device)),
+                "contrast_quantise")
+    return q
+
+
+def _apply(x: torch.Tensor, q: torch.Tensor, lut: torch.Tensor, ty: int, tx: int, inv_th: float, inv_tw: float) -> torch.Tensor:
+    N, _, H, W = (int(v) for v in x.shape)
+    out = torch.empty_like(x)
+    _capi.check(_capi.lib().hdiff_contrast_apply(x.data_ptr(), q.data_ptr(), lut.data_ptr(), N, H, W, int(q.shape[1] == 1), ty, tx,
+                                                 inv_th, inv_tw, out.data_ptr(), _stream(x.device)), "contrast_apply")
+    return out
+
+
+def clahe(img01: torch.Tensor, *, clip_limit: float = 2.0, grid: Tuple[int, int] = (8, 8), space: str = "lab",
+          return_parts: bool = False):
+    """float ``[N, 3, H, W]`` in [0, 1] units -> float32, the same shape: contrast-limited adaptive histogram equalisation of the
+    8-bit planes of ``space`` (``"rgb"``: each channel as its own plane; ``"lab"``: CIE L* alone, a and b kept).
+
+      1. ``q`` = the planes quantised to bytes (``floor(X 255 + 0.5)``, or ``floor(L 2.55 + 0.5)``), ``X = clip(img01, 0, 1)``
+      2. per tile of the ``grid = (tiles_y, tiles_x)`` (1 to 16 each; the plane padded right and bottom to a multiple by reflection): the
+         256-bin histogram, cut at ``max(1, floor(clip_limit area / 256))`` with the excess spread over the bins in one pass
+         (``clip_limit=0``: no cut, plain adaptive equalisation), and its cumulative sum scaled to 0..255: the tile's table
+      3. every pixel through the four tables around it, blended bilinearly in fp32, rounded to a byte
+      4. back to float: ``q' / 255``, or ``lab_to_srgb(q' / 2.55, a, b)`` clipped to [0, 1]
+
+    ``tests/_contrast_def.py`` writes every operation out; ``q``, the tables and the ``"rgb"`` output equal it bit for bit.  With
+    ``return_parts`` -> ``(out, parts)``, ``parts`` a dict of ``q`` (uint8 ``[N, P, H, W]``, ``P`` = 3 or 1) and ``lut`` (uint8
+    ``[N, P, tiles_y, tiles_x, 256]``).  Neither default is backed by a figure on photographs (module docstring)."""
+    planes, (ty, tx), clip_limit = _space(space), _grid(grid), _clip_limit(clip_limit)
+    if torch.is_tensor(img01) and img01.dim() == 4:      # a grid too fine for the image is a ValueError wherever the tensor lives:
+        _fits(int(img01.shape[2]), int(img01.shape[3]), ty, tx)      # ahead of `_images`, which refuses a CPU tensor
+    x = _images(img01)
+    N, _, H, W = (int(v) for v in x.shape)
+    clip, scale, inv_th, inv_tw = _tile_constants(H, W, ty, tx, clip_limit)
+    with torch.cuda.device(x.device):
+        q = _quantise(x, planes)
+        lut = torch.empty(N, planes, ty, tx, 256, dtype=torch.uint8, device=x.device)
+        _capi.check(_capi.lib().hdiff_clahe_luts(q.data_ptr(), N, planes, H, W, ty, tx, clip, scale, lut.data_ptr(), _stream(x.device)),
+                    "clahe_luts")
+        out = _apply(x, q, lut, ty, tx, inv_th, inv_tw)
+    return (out, {"q": q, "lut": lut}) if return_parts else out
+
+
+def equalize(img01: torch.Tensor, *, space: str = "rgb", return_parts: bool = False):
+    """float ``[N, 3, H, W]`` in [0, 1] units -> float32, the same shape: global histogram equalisation of the 8-bit planes of
+    ``space`` by the rule of Pillow's ``ImageOps.equalize`` -- ``lut[i] = (step // 2 + sum(h[:i])) // step`` with ``step = (H W - the
+    last filled bin's count) // 255``, at most 255; a plane with fewer than two filled bins, or with ``step == 0``, is left as it is.
+    With ``return_parts`` -> ``(out, parts)``, ``parts`` a dict of ``q`` (uint8 ``[N, P, H, W]``) and ``lut`` (uint8 ``[N, P, 256]``)."""
+    planes = _space(space)
+    x = _images(img01)
+    N, _, H, W = (int(v) for v in x.shape)
+    need = C.c_int64(0)
+    _capi.check(_capi.lib().hdiff_equalize_luts_workspace(N, planes, H, W, C.byref(need)), "equalize_luts_workspace")
+    with torch.cuda.device(x.device):
+        q = _quantise(x, planes)
+        scratch = torch.empty(need.value, dtype=torch.uint8, device=x.device)
+        lut = torch.empty(N, planes, 256, dtype=torch.uint8, device=x.device)
+        _capi.check(_capi.lib().hdiff_equalize_luts(q.data_ptr(), N, planes, H, W, lut.data_ptr(), scratch.data_ptr(), _stream(x.device)),
+                    "equalize_luts")
+        out = _apply(x, q, lut, 0, 0, 1.0, 1.0)
+    return (out, {"q": q, "lut": lut}) if return_parts else out
+
+
 def _identity(img01: torch.Tensor) -> torch.Tensor:
     return img01
 
@@ -223,17 +352,31 @@ BASELINES: Dict[str, Callable[[torch.Tensor], torch.Tensor]] = {
 }
 
 
+# the contrast family, each with the defaults above.  A table of its own: ``BASELINES`` is the set of inverses of the image-formation
+# model and stays as it is; and there is no bare "clahe" -- the name has to say which planes were enhanced, the two differ in every score
+CONTRAST_BASELINES: Dict[str, Callable[[torch.Tensor], torch.Tensor]] = {
+    "clahe_lab": lambda img01: clahe(img01, space="lab"),
+    "clahe_rgb": lambda img01: clahe(img01, space="rgb"),
+    "equalize": lambda img01: equalize(img01, space="rgb"),
+}
+
+
 def resolve_baselines(baselines) -> Sequence[Tuple[str, Callable]]:
-    """``evaluate``'s ``baselines=`` as a list of ``(name, callable)``: names out of ``BASELINES`` or pairs of the caller's own.  Raises
-    on an unknown name, a name that is not a plain word, a duplicate, or something that cannot be called -- on the host."""
+    """``evaluate``'s ``baselines=`` as a list of ``(name, callable)``: names out of ``BASELINES``, then out of ``CONTRAST_BASELINES``, or
+    pairs of the caller's own.  Raises on an unknown name, a name that is not a plain word, a duplicate, or something that cannot be
+    called -- on the host."""
     if isinstance(baselines, (str, bytes)) or not isinstance(baselines, (tuple, list)):
         raise TypeError(f"hdiff: 'baselines' must be a sequence of names or (name, callable) pairs, got {baselines!r}")
     out = []
     for b in baselines:
         if isinstance(b, str):
-            if b not in BASELINES:
-                raise ValueError(f"hdiff: unknown baseline {b!r}; one of {sorted(BASELINES)}, or a (name, callable) pair")
-            name, fn = b, BASELINES[b]
+            if b in BASELINES:
+                name, fn = b, BASELINES[b]
+            elif b in CONTRAST_BASELINES:
+                name, fn = b, CONTRAST_BASELINES[b]
+            else:
+                raise ValueError(f"hdiff: unknown baseline {b!r}; one of {sorted(BASELINES)} or {sorted(CONTRAST_BASELINES)}, or a "
+                                 "(name, callable) pair")
         elif isinstance(b, (tuple, list)) and len(b) == 2 and isinstance(b[0], str) and callable(b[1]):
             name, fn = b
         else:

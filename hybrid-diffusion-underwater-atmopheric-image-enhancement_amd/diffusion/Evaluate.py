@@ -127,7 +127,8 @@ def evaluate(sampler, batches: Iterable, *, ddim_step: int, tile: Optional[int] 
     ``ciede2000_p95_orgin_avg:``, ``deltae76_orgin_avg:`` and ``angular_orgin_avg:`` (under ``samples=`` their ``_sample_avg:`` /
     ``_sample_std:`` lines follow like the other per-image scores').  Without it nothing of that is launched or written.
     ``baselines``: a sequence of names out of ``hdiff_amd.classical.BASELINES`` (``"input"``, ``"gray_world"``, ``"dcp"``, ``"udcp"``,
-    ``"inverted_dcp"``) or ``(name, callable)`` pairs, a callable taking the ``[0, 1]`` input batch to an image batch of the same shape.
+    ``"inverted_dcp"``) or ``classical.CONTRAST_BASELINES`` (``"clahe_lab"``, ``"clahe_rgb"``, ``"equalize"``; there is no bare
+    ``"clahe"``: the name says which planes were enhanced) or ``(name, callable)`` pairs, a callable taking the ``[0, 1]`` input batch to an image batch of the same shape.
     Per baseline a second meter of the main meter's configuration (a ``quality.QualityMeter``) is updated per batch with
     ``fn(input / 255)`` against ``target / 255``; the result gains ``"baselines": {name: that meter's compute() dict}`` and ``res.txt``,
     behind every other line (the ``samples=`` lines included), one line ``<score>_<name>_avg:`` per baseline in the order given, for
@@ -518,8 +519,8 @@ def test(config, epoch=None) -> Dict[str, Dict[str, object]]:
     goes to ``<set>/std/<name>`` and ``res.txt`` gains the draw-to-draw spread of every score) with ``ddim_eta`` (default 0),
     ``sample_seed`` (default 0) and ``sample_batch`` (the most samples per model evaluation; absent: one draw from torch's generator
     per image, ``res.txt`` as before),
-    ``baselines`` (``evaluate``'s ``baselines=``: names out of ``classical.BASELINES`` or ``(name, callable)`` pairs, each scored on
-    ``input / 255`` against the targets beside the model, ``res.txt`` gains ``<score>_<name>_avg:`` lines; absent: nothing of it is
+    ``baselines`` (``evaluate``'s ``baselines=``: names out of ``classical.BASELINES`` or ``classical.CONTRAST_BASELINES``, or ``(name,
+    callable)`` pairs, each scored on ``input / 255`` against the targets beside the model, ``res.txt`` gains ``<score>_<name>_avg:`` lines; absent: nothing of it is
     constructed, launched or written),
     ``prediction`` ("eps" or "v": what the checkpoint's network predicts, the sampler's ``prediction=``; absent: read from the
     ``prediction.json`` beside ``pretrained_path`` if ``Train.train`` left one, else "eps"; present and different from that file:

@@ -1075,6 +1075,40 @@ int hdiff_white_balance(const float* img, int N, int H, int W, double p, double*
                         hdiff_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------------------------
+ * Contrast baselines: CLAHE and global histogram equalisation on 8-bit planes (csrc/contrast.hip; tests/_contrast_def.py is the
+ * definition; hdiff_amd/classical.py is the caller).  Images are float [N][3][H][W], clipped to [0, 1] in fp32 as they are read (a NaN
+ * clips to 0).  `lab` == 0: P = 3 planes, one per channel; `lab` != 0: P = 1 plane, CIE L* (csrc/lab.h).  N <= 65535, H W <= 2^30.
+ *
+ *   hdiff_contrast_quantise  q [N][P][H][W] (uint8): q_c = floor(double(X_c) 255 + 0.5), or q = clamp(floor(L 2.55 + 0.5), 0, 255).
+ *                            One launch.
+ *   hdiff_clahe_luts         lut [N][P][tiles_y][tiles_x][256] (uint8).  1 <= tiles <= 16, H >= tiles_y, W >= tiles_x.  The plane is
+ *                            padded right and bottom to multiples of the grid by reflect-101 (read through the index map); th =
+ *                            ceil(H / tiles_y), tw = ceil(W / tiles_x), area = th tw.  Per tile: h = the histogram of the padded tile;
+ *                            excess = sum(max(h - clip, 0)); h = min(h, clip) + excess / 256; with r = excess % 256 > 0 and step =
+ *                            256 / r, h[k step] += 1 for k < r; lut[i] = min(rint(fp32(cumsum(h)[i]) scale), 255), the product in
+ *                            fp32, halves to even.  The caller passes clip (1 <= clip <= area; area clips nothing) and scale =
+ *                            fp32(255) / fp32(area).  One launch, one workgroup per tile, integer LDS atomics.
+ *   hdiff_equalize_luts      lut [N][P][256] (uint8), Pillow's ImageOps.equalize: with fewer than two filled bins, or step = (H W -
+ *                            the last filled bin's count) / 255 == 0, the identity; otherwise lut[i] = min((step / 2 + sum(h[:i])) /
+ *                            step, 255).  Two launches: per-workgroup histograms in slots of `scratch`, then their sum in index order.
+ *   hdiff_contrast_apply     q' = lut[q] (tiles_y == tiles_x == 0: one table per plane), or the blend of four tables: fx = fp32(x) inv_tw
+ *                            - 0.5f, x1 = floor(fx), xa = fx - x1, xa1 = 1 - xa, tiles max(x1, 0) and min(x1 + 1, tiles_x - 1), the
+ *                            same in y; res = (l11 xa1 + l12 xa) ya1 + (l21 xa1 + l22 xa) ya, seven fp32 roundings; q' =
+ *                            clamp(rint(res), 0, 255).  inv_th = fp32(1) / fp32(th) and inv_tw likewise come from the caller.  Then
+ *                            out_c = fp32(double(q'_c) / 255), or with `lab` out = fp32(clamp(lab_to_srgb(q' / 2.55, a, b), 0, 1)), a
+ *                            and b recomputed from X.  `out` must not be `img`.  One launch.
+ * No float atomics, no allocation, no synchronisation: every entry is legal under stream capture, and image n of every output depends
+ * on image n of the inputs alone.  Additions to ABI 6.
+ * ------------------------------------------------------------------------------------------------------------------ */
+int hdiff_contrast_quantise(const float* img, int N, int H, int W, int lab, uint8_t* q, hdiff_stream_t stream);
+int hdiff_clahe_luts(const uint8_t* q, int N, int planes, int H, int W, int tiles_y, int tiles_x, int64_t clip, float scale,
+                     uint8_t* lut, hdiff_stream_t stream);
+int hdiff_equalize_luts_workspace(int N, int planes, int H, int W, int64_t* bytes);
+int hdiff_equalize_luts(const uint8_t* q, int N, int planes, int H, int W, uint8_t* lut, void* scratch, hdiff_stream_t stream);
+int hdiff_contrast_apply(const float* img, const uint8_t* q, const uint8_t* lut, int N, int H, int W, int lab, int tiles_y, int tiles_x,
+                         float inv_th, float inv_tw, float* out, hdiff_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------------------------
  * hipGraph helpers: capture everything enqueued on `stream` between begin/end, replay it later.
  * ------------------------------------------------------------------------------------------------------------------ */
 int hdiff_graph_begin(hdiff_stream_t stream);
